@@ -204,6 +204,7 @@ struct c3d_ctx {
     bool last_two_point = false;           // the last multi-step launch was k_cluster_tp (its range held two-point minimiser steps)
     int last_path = 0;                     // 0 per-step, 2 k_cluster, 3 fp64 reference (what the last run_ops used)
     bool last_general = false;             // the last per-step launch took the general-form kernel (general tails, or an op without restraint weight)
+    bool last_fold64 = false;              // the last fp64 step launch took k64_step<4, false, true> (shipped potential, restraint weight != 0)
 
     double last_ms = 0;
     long last_steps = 0, last_launches = 0;
@@ -838,6 +839,10 @@ int run_ops_segment(c3d_ctx* c, size_t nops, bool zero_w) {
         hipError_t e = c3d::launch_export64(dev_model(c), c->b64, c->parity, c->buf.X[c->parity], c->buf.V[c->parity], c->buf.P[c->parity], c->stream);
         if (e != hipSuccess) return fail(C3D_ERR_HIP, std::string("fp64 export: ") + hipGetErrorString(e));
         c->last_path = 3;
+        // launch_step64's choice for the range's last op (a graph replay does not pass through launch_op): the FOLD form for the shipped
+        // potential's fast form wherever the restraint weight is not zero
+        const c3d::DevModel m = dev_model(c);
+        c->last_fold64 = c->pc > 0 && m.noe_pot == 4 && !general_tail(m) && c->stages[c->program[c->pc - 1].stage].w_all != 0.0f;
     }
     return C3D_OK;
 }
@@ -1668,7 +1673,7 @@ extern "C" const char* c3d_step_kernel_name(const c3d_ctx* c) {
     const char* rs1 = (!general_tail(m) && m.rs == 1.0f) ? "true" : "false";
     if (c->last_path == 2) snprintf(buf, sizeof(buf), "c3d::k_cluster%s<%d, %d, %d, %d, %s>", c->last_two_point ? "_tp" : "", m.noe_pot, c->cl_plan.rpw, m.npad / 256, m.wl, c->cl_plan.late_tiles ? "true" : "false");
     else if (use_sym(c)) snprintf(buf, sizeof(buf), "c3d::k_pairs_sym<%d, %s, false>", m.noe_pot, rs1);
-    else if (c->precision == 64) snprintf(buf, sizeof(buf), "c3d::k64_step<%d, %s>", m.noe_pot, general_tail(m) ? "true" : "false");
+    else if (c->precision == 64) snprintf(buf, sizeof(buf), "c3d::k64_step<%d, %s, %s>", m.noe_pot, general_tail(m) ? "true" : "false", c->last_fold64 ? "true" : "false");
     else if (wide_step(c, m, general_tail(m) || c->last_general)) snprintf(buf, sizeof(buf), "c3d::k_step<4, false, 4, false, 16, true>");
     else snprintf(buf, sizeof(buf), "c3d::k_step<%d, %s, %d, %s, 8, false>", m.noe_pot, gen, m.rpw, (m.wl == 4 && m.nleft == 0) ? "false" : "true");
     return buf;

@@ -142,7 +142,8 @@ int c3d_set_schedule(c3d_ctx* ctx, const c3d_stage* stages, int n_stages, const 
  *                   (a device that does not expose 8 XCDs gets no cluster plan; a launch that ends without its completion
  *                   mark or with a time-out is re-run on the per-step path)
  *   precision       32 (default) or 64: the fp64 reference kernels (c3d_f64.hip); call before c3d_init_replicas.  The fp64 step stages a
- *                   replica's coordinates in LDS: at most 2560 beads (c3d_init_replicas returns C3D_ERR_INVALID beyond; fp32: 8192)
+ *                   replica's coordinates in LDS: at most 2560 beads (c3d_init_replicas returns C3D_ERR_INVALID beyond).  The fp32 kernels
+ *                   stage 3 * npad floats of a replica in LDS: at most 5120 beads (c3d_set_if_matrix / c3d_set_restraints refuse more)
  *   symmetric       1: symmetric-tile kernels for large N (c3d_sym.hip; opt-in); call before c3d_init_replicas
  *   eval_rows_per_wave  4 (default) / 2 / -2: form of the forces hook (c3d_eval_forces) — four rows per wave with the scalar pair term; 2 = two
  *                   rows per wave, the step kernels' code (shipped potential: the packed pair term); -2 = two rows per wave, scalar pair

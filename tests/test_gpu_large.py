@@ -71,6 +71,78 @@ def test_two_point_stage_on_the_wide_per_step_kernel_follows_the_oracle_at_n2500
         O.set_two_point_steps(1000)
 
 
+def test_md_kinds_on_the_wide_per_step_kernel_follow_the_oracle_at_n2500(solver, big):
+    """The wide per-step kernel, k_step<4, false, 4, false, 16, true>, through the MD kinds at N = 2500 x 2 (the test above holds it to the
+    oracle for the minimiser kinds only): 8 FIRE steps from the coil, 12 MD steps at 2000 K (kind 4 begins the stage, then kind 0), 8 steps
+    of kind 1.  Measured worst: 8.1e-5 A (coordinates)."""
+    from chromosome3d_amd import default_fire, default_model, make_stages, pipeline
+    from oracle import oracle as O
+    from tests.util import oracle_fire_from
+    IF, _ = big
+    n = IF.shape[0]
+    stages = [(2, 8, 0.0, 1.0, 20.0, 0.5, 0.0), (0, 12, 0.003, 0.4, 0.003, 0.9, 2000.0), (1, 8, 0.005, 1.0, 0.05, 1.0, 1500.0)]
+    m, fire = default_model(), default_fire()
+    solver.set_model(m)
+    d10 = pipeline.IF2dist_new(solver, IF)
+    solver.set_schedule(make_stages(stages), fire)
+    solver.init_replicas(2, 82364, 0)
+    x0 = solver.coords()
+    assert solver.run_steps(10 ** 6) == 28
+    assert solver.step_kernel_name == "c3d::k_step<4, false, 4, false, 16, true>", solver.step_kernel_name
+    x, v = solver.coords(), solver.velocities()
+    om, of = oracle_model_from(m, n), oracle_fire_from(fire)
+    worst = 0.0
+    for r in range(2):
+        xo, vo, ev = O.run_schedule(om, d10, O.make_stages(stages), of, 82364, r, x0=x0[r].astype(np.float64))
+        xc = x[r].astype(np.float64)
+        xc -= xc.mean(0)
+        assert ev == 28
+        worst = max(worst, float(np.abs(xc - xo).max()))
+        assert np.abs(v[r] - vo).max() < 2e-3 * max(1.0, np.abs(vo).max())
+    assert worst < 2e-3, worst
+    print(f"N=2500 MD kinds on the wide kernel: worst {worst:.2e} A")
+
+
+@pytest.mark.parametrize("n", [5120, 4097])
+def test_fp32_path_at_its_bead_limit_follows_the_oracle(solver, n):
+    """The fp32 path at the largest size it accepts (5120 beads: 3 npad floats of a replica in LDS, step_lds_bytes 61 744 of 65 536 B) and
+    at 4097 (odd: the last wide workgroup owns a tile of one bead): K1 bit-exact; forces and energies of two coordinate sets (stretched,
+    collapsed) against the oracle; Newton's third law; ten FIRE and ten MD steps through the wide per-step kernel against the oracle.
+    Measured worst after the 20 steps: 4.0e-5 A (5120), 5.0e-5 A (4097)."""
+    from chromosome3d_amd import default_fire, default_model, make_stages, pipeline
+    from oracle import oracle as O
+    from tests.util import oracle_fire_from
+    IF, truth = synthetic_if(n, seed=n)
+    m, fire = default_model(), default_fire()
+    solver.set_model(m)
+    d10 = pipeline.IF2dist_new(solver, IF)
+    assert np.array_equal(d10, O.if_to_dist10(IF))
+    del IF
+    om = oracle_model_from(m, n)
+    solver.init_replicas(1, 82364, 0)
+    for x in (truth.astype(np.float32) * 1.1, random_coil(n, 3) * 0.3):
+        solver.set_coords(x[None])
+        F, e = solver.eval(1.0, 1.0, 0.85)
+        Fo, eo = O.energy_force(om, d10, x.astype(np.float64), 1.0, 1.0, float(np.float32(0.85)))
+        assert (np.abs(F[0] - Fo) <= 1e-5 * np.abs(Fo) + 1e-6 * np.abs(Fo).max()).all(), np.abs(F[0] - Fo).max()
+        assert np.allclose(e[0], eo, rtol=1e-7, atol=1e-6), (e[0], eo)
+        assert np.abs(F[0].sum(0)).max() < 5e-5 * np.abs(F[0]).sum(0).max()          # Newton's third law
+    stages = [(2, 10, 0.0, 1.0, 20.0, 0.5, 0.0), (0, 10, 0.003, 0.4, 0.003, 0.9, 2000.0)]
+    solver.set_schedule(make_stages(stages), fire)
+    solver.init_replicas(1, 82364, 0)
+    x0 = solver.coords()
+    assert solver.run_steps(10 ** 6) == 20
+    assert solver.step_kernel_name == "c3d::k_step<4, false, 4, false, 16, true>", solver.step_kernel_name
+    xo, vo, ev = O.run_schedule(om, d10, O.make_stages(stages), oracle_fire_from(fire), 82364, 0, x0=x0[0].astype(np.float64))
+    xc = solver.coords()[0].astype(np.float64)
+    xc -= xc.mean(0)
+    assert ev == 20
+    worst = float(np.abs(xc - xo).max())
+    assert worst < 2e-3, worst
+    assert np.abs(solver.velocities()[0] - vo).max() < 2e-3 * max(1.0, np.abs(vo).max())
+    print(f"N={n}: worst {worst:.2e} A after 20 steps")
+
+
 def test_anneal_recovers_synthetic_structure(solver, big):
     """Ground truth is known: after the schedule the model's pair distances correlate with the
     generating structure's (Spearman > 0.9) and Spearman(IF, d) is strongly negative."""

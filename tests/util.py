@@ -87,13 +87,25 @@ def synthetic_if(n, seed=20161015, K=11.0, alpha=0.5, sigma=0.2, radius=None):
             if np.linalg.norm(cand) <= radius:
                 break
         x[i] = cand
-    d = np.linalg.norm(x[:, None, :] - x[None, :, :], axis=-1)
-    np.fill_diagonal(d, 1.0)
-    IF = (K / d) ** (1.0 / alpha)
+    # element for element the arithmetic of the whole-matrix form, in row chunks: at most three n x n arrays live at once (630 MB at
+    # n = 5120, where the n x n x 3 difference tensor alone would take 630 MB)
+    ch = 256
+    IF = np.empty((n, n))
+    for a in range(0, n, ch):
+        d = np.linalg.norm(x[a:a + ch, None, :] - x[None, :, :], axis=-1)
+        np.fill_diagonal(d[:, a:], 1.0)
+        IF[a:a + ch] = (K / d) ** (1.0 / alpha)
+    del d
     g = rng.normal(size=(n, n))
-    g = (g + g.T) / np.sqrt(2.0)
-    IF = IF * np.exp(sigma * g)
-    IF = (IF + IF.T) / 2.0
+    gs = np.empty((n, n))
+    for a in range(0, n, ch):
+        gs[a:a + ch] = (g[a:a + ch] + g[:, a:a + ch].T) / np.sqrt(2.0)
+    del g
+    for a in range(0, n, ch):
+        IF[a:a + ch] = IF[a:a + ch] * np.exp(sigma * gs[a:a + ch])
+    for a in range(0, n, ch):
+        gs[a:a + ch] = (IF[a:a + ch] + IF[:, a:a + ch].T) / 2.0
+    IF = gs
     np.fill_diagonal(IF, 0.0)
     np.fill_diagonal(IF, 10.0 * IF.max(axis=1))
     return IF, x - x.mean(0)
