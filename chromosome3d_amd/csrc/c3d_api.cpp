@@ -240,6 +240,21 @@ void drop_graphs(c3d_ctx* c) {
     for (auto& kv : c->graphs) (void)hipGraphExecDestroy(kv.second);
     c->graphs.clear();
 }
+// Everything else a context holds, once its streams have drained: graphs, replica state, targets, the program, claim sets, staging, score
+// scratch, events, streams.  c3d_destroy's alone; the caller holds the gate.
+void release_context(c3d_ctx* c) {
+    for (hipStream_t s : c->gstream) if (s) (void)hipStreamSynchronize(s);
+    drop_graphs(c);
+    free_replica_buffers(c);
+    dev_free(c->buf.tgt); dev_free(c->buf.tgs2);
+    dev_free(c->d_prog); dev_free(c->d_claim); dev_free(c->d_score);
+    if (c->h_tmo) (void)hipHostFree(c->h_tmo);
+    if (c->h_stage) (void)hipHostFree(c->h_stage);
+    for (hipEvent_t e : {c->ev0, c->ev1, c->kev0, c->kev1, c->fork_ev}) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->gev) if (e) (void)hipEventDestroy(e);
+    for (hipStream_t s : c->gstream) if (s && s != c->stream) (void)hipStreamDestroy(s);
+    if (c->stream) (void)hipStreamDestroy(c->stream);
+}
 
 c3d::DevModel dev_model(const c3d_ctx* c) {
     c3d::DevModel m{};
@@ -362,6 +377,16 @@ void build_program(c3d_ctx* c) {
     c->prog_dirty = true;
 }
 
+// What a change of configuration (c3d_set_model / c3d_set_schedule / c3d_set_option) makes stale
+enum Stale : unsigned { STALE_REPLICAS = 1, STALE_GRAPHS = 2, STALE_PAIR_TARGETS = 4, STALE_PROGRAM = 8 };
+// the caller holds the gate when this releases anything device-side (drop_stale_gated)
+void drop_stale(c3d_ctx* c, unsigned stale) {
+    if (stale & STALE_REPLICAS) free_replica_buffers(c);
+    if (stale & STALE_PAIR_TARGETS) dev_free(c->buf.tgs2);
+    if (stale & STALE_PROGRAM) build_program(c);       // drops the graphs
+    else if (stale & STALE_GRAPHS) drop_graphs(c);
+}
+
 int upload_targets(c3d_ctx* c, const std::vector<float>& enc) {
     dev_free(c->buf.tgt); dev_free(c->buf.tgs2);
     HIP_TRY(hipMalloc(&c->buf.tgt, sizeof(float) * enc.size()));
@@ -410,17 +435,22 @@ int active_groups(const c3d_ctx* c) { return std::min(c->ngroups, std::max(c->nr
 // kernels.  Round 5 left that to the runtime and to helper threads, and eight contexts of one process starting together — c3d_batch
 // --devices 4 --lanes 2 --map-devices-to 0 — ended in a DEVICE exception once (rc -13: the runtime's GPU-core-dump helper does not
 // exist on the box, the process died on its pipe before the runtime could say which exception; DESIGN.md section 6 "code objects").
-// Since round 6 nothing is lazy and nothing is concurrent:
+// That a load beside other HIP calls of the process caused it is a hypothesis: the record does not name the exception.  The rule that
+// follows from it — no code object loads while any thread of the process is inside the HIP runtime for this library:
 //   * a unit is loaded by ensure_units() alone — the calling thread, one unit at a time, g_units.rw held EXCLUSIVELY;
-//   * every public entry that issues device work (kernels, copies, fills) holds g_units.rw SHARED for its whole duration (struct Entry)
-//     and names the units it can need before it takes it: a unit is never loaded while any thread of the process can launch;
+//   * every HIP call of a context runs inside a public entry that holds g_units.rw SHARED for its whole duration (struct Entry): kernels,
+//     copies and fills (C3D_ENTRY, which first loads the units the context's configuration can launch from), and allocation, release,
+//     stream / event / graph creation and destruction, synchronisation (C3D_GATE, which loads nothing).  The only calls outside are the
+//     device queries of c3d_create and c3d_device_count (hipGetDeviceCount, hipGetDeviceProperties, hipDeviceGetAttribute) and
+//     hipSetDevice, which precede the gate;
 //   * c3d_create loads what a default job runs (per-step + K1 unit, both multi-step units of the shipped potential, scoring) before it
-//     returns — 13 ms once per process and device, 24 ms for all sixteen: profiles/r06_create_with_code_objects.txt (c3d_set_process_option
-//     "preload": 2 = all sixteen, 0 = each at the first entry that
-//     needs it); the multi-step and embedding units also get their dynamic-LDS allowance there (hipFuncSetAttribute per instantiation:
-//     state of the runtime, so it belongs under the same lock), and a launch changes no runtime state afterwards;
+//     makes its first stream — +13 ms once per process and device, +24 ms for all sixteen: profiles/r06_create_with_code_objects.txt
+//     (c3d_set_process_option "preload": 2 = all sixteen, 0 = each at the first entry that needs it); the multi-step and embedding units
+//     also get their dynamic-LDS allowance there (hipFuncSetAttribute per instantiation: state of the runtime, so it belongs under the
+//     same lock), and a launch changes no runtime state afterwards;
 //   * a load that fails is reported (C3D_ERR_HIP) and not remembered as done.
-// No helper thread of the library touches the HIP runtime any more (the IF-rank worker is host arithmetic only).
+// No helper thread of the library touches the HIP runtime (the IF-rank worker is host arithmetic only).  tools/sanitize/hip_stub.cpp
+// checks the rule on the CPU: every HIP function it fakes but those queries counts as device work, and a load beside any of them fails.
 enum Unit : unsigned {
     UNIT_DEVICE = 0, UNIT_SCORE, UNIT_CLUSTER_BASE, UNIT_EMBED, UNIT_F64, UNIT_SYM,
     UNIT_CLUSTER_P0, UNIT_CLUSTER_TP0 = UNIT_CLUSTER_P0 + 5, UNIT_COUNT = UNIT_CLUSTER_TP0 + 5
@@ -509,18 +539,20 @@ int ensure_units(int device, unsigned mask) {
 unsigned units_wanted(const c3d_ctx* c) {
     unsigned m = unit_bit(UNIT_DEVICE) | unit_bit(UNIT_SCORE);
     const int pot = std::min(std::max(dev_model(c).noe_pot, 0), 4);
-    if (c->cluster != 0 && c->resident != 0) m |= unit_bit(UNIT_CLUSTER_P0 + (unsigned)pot) | unit_bit(UNIT_CLUSTER_TP0 + (unsigned)pot);
+    if (c->cluster != 0 && c->resident != 0 && c->precision != 64)          // fp64 never takes the multi-step path (run_ops_segment)
+        m |= unit_bit(UNIT_CLUSTER_P0 + (unsigned)pot) | unit_bit(UNIT_CLUSTER_TP0 + (unsigned)pot);
     if (c->precision == 64) m |= unit_bit(UNIT_F64);
     if (c->sym > 0) m |= unit_bit(UNIT_SYM);
     return m;
 }
-// A public entry that issues device work: current device, units present, launch side of the lock — in that order
+// A public entry: current device, units present (launching entries only), shared side of the gate — in that order.  Every HIP call of a
+// context runs inside one; only the device queries of c3d_create (count, properties, attributes) come before it.
 struct Entry {
     int rc = C3D_OK;
     bool locked = false;
-    explicit Entry(const c3d_ctx* c, unsigned extra = 0) {
+    Entry(const c3d_ctx* c, unsigned extra, bool launches) {
         if (hipSetDevice(c->device) != hipSuccess) { rc = fail(C3D_ERR_HIP, "hipSetDevice failed"); return; }
-        rc = ensure_units(c->device, units_wanted(c) | extra);
+        if (launches) rc = ensure_units(c->device, units_wanted(c) | extra);
         if (rc != C3D_OK) return;
         if (t_entry_depth++ == 0) { g_units.rw.lock_shared(); locked = true; }
     }
@@ -532,9 +564,25 @@ struct Entry {
     Entry(const Entry&) = delete;
     Entry& operator=(const Entry&) = delete;
 };
-#define C3D_ENTRY(c, extra)             \
-    Entry entry__((c), (extra));        \
+// entries that launch kernels, copy or fill: they load what the context's configuration (and `extra`) can launch from
+#define C3D_ENTRY(c, extra)                 \
+    Entry entry__((c), (extra), true);      \
     if (entry__.rc != C3D_OK) return entry__.rc
+// entries that only allocate, free, create, destroy or synchronise: they load nothing
+#define C3D_GATE(c)                         \
+    Entry entry__((c), 0u, false);          \
+    if (entry__.rc != C3D_OK) return entry__.rc
+
+// c3d_set_schedule / c3d_set_option: drops what a change made stale, inside the gate when that releases anything device-side (the replica
+// state is allocated from X[0] and t10 on: c3d_init_replicas)
+int drop_stale_gated(c3d_ctx* c, unsigned stale) {
+    const bool device_side = ((stale & STALE_REPLICAS) && (c->buf.X[0] || c->b64.t10)) || ((stale & STALE_PAIR_TARGETS) && c->buf.tgs2) ||
+                             ((stale & (STALE_GRAPHS | STALE_PROGRAM)) && !c->graphs.empty());
+    if (!device_side) { drop_stale(c, stale); return C3D_OK; }
+    C3D_GATE(c);
+    drop_stale(c, stale);
+    return C3D_OK;
+}
 
 bool use_sym(const c3d_ctx* c) {
     if (!c->d_sym_scratch) return false;
@@ -601,8 +649,8 @@ int launch_op(c3d_ctx* c, const Op& op, int g, int par) {
 int plan_cluster(c3d_ctx* c) {
     c3d::DevModel m = dev_model(c);
     m.nrep = c->nrep; m.nrep_g = c->nrep; m.rep_base = 0;
-    c->cl_ok = c3d::cluster_plan(m, c->num_cus, c->num_xcc, c->cluster_geom, c->cluster_late, c->xcd_count, &c->cl_plan);
-    if (!c->cl_ok) return C3D_OK;
+    c->cl_ok = false;                          // until the records fit: a failure below leaves the per-step path, not a stale plan
+    if (!c3d::cluster_plan(m, c->num_cus, c->num_xcc, c->cluster_geom, c->cluster_late, c->xcd_count, &c->cl_plan)) return C3D_OK;
     c->cl_plan.device = c->device;
     const size_t bytes = c3d::cluster_record_bytes(m, c->cl_plan);
     if (!c->d_crec || bytes > c->crec_bytes) {
@@ -612,6 +660,7 @@ int plan_cluster(c3d_ctx* c) {
         c->crec_bytes = bytes;
     }
     c->cl_seq = 0;                             // the next launch wipes the records and the slot counters
+    c->cl_ok = true;
     return C3D_OK;
 }
 
@@ -651,7 +700,7 @@ void account_ops(c3d_ctx* c, size_t nops) {
 int run_cluster(c3d_ctx* c, size_t nops, bool* ran) {
     if (c->prog_dirty) {
         if (c->prog_runs.size() > c->prog_cap) {
-            if (c->d_prog) { HIP_TRY(hipStreamSynchronize(c->stream)); (void)hipFree(c->d_prog); c->d_prog = nullptr; }
+            if (c->d_prog) { HIP_TRY(hipStreamSynchronize(c->stream)); dev_free(c->d_prog); }
             c->prog_cap = std::max<size_t>(c->prog_runs.size(), 256);
             HIP_TRY(hipMalloc(&c->d_prog, sizeof(c3d::StepRun) * c->prog_cap));
         }
@@ -1007,14 +1056,23 @@ extern "C" int c3d_create(int device, c3d_ctx** out) {
     HIP_TRY(hipGetDeviceProperties(&prop, device));
     if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
         return fail(C3D_ERR_NO_DEVICE, std::string("device is ") + prop.gcnArchName + ", libc3d is built for gfx950 only");
+    int num_xcc = 0;
+    if (hipDeviceGetAttribute(&num_xcc, hipDeviceAttributeNumberOfXccs, device) != hipSuccess) num_xcc = 0;   // unknown: no cluster kernel
+    // Code objects ("code objects" above): what a default job launches from is loaded HERE, on this thread, before the context makes its first
+    // HIP resource — not by a helper thread beside the caller's first launches, as in rounds 4-5 (that saved the first job of a process ~13 ms
+    // and is where the one device exception of round 5 was met).  Later contexts of the device find the units loaded (one atomic load).
+    if (const int pre = g_preload.load())
+        if (const int rc = ensure_units(device, pre >= 2 ? kUnitsAll : kUnitsDefault)) return rc;
     c3d_ctx* c = new c3d_ctx();
     c->device = device;
     c->num_cus = prop.multiProcessorCount;
-    if (hipDeviceGetAttribute(&c->num_xcc, hipDeviceAttributeNumberOfXccs, device) != hipSuccess) c->num_xcc = 0;   // unknown: no cluster kernel
+    c->num_xcc = num_xcc;
     c3d_default_model(&c->model);
     c3d_default_fire(&c->fire);
     c->stages.resize(c3d_default_schedule(nullptr, 0, 3000));
     c3d_default_schedule(c->stages.data(), (int)c->stages.size(), 3000);
+    Entry gate(c, 0u, false);
+    if (gate.rc != C3D_OK) { delete c; return gate.rc; }
     bool ok = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) == hipSuccess &&
               hipEventCreate(&c->ev0) == hipSuccess && hipEventCreate(&c->ev1) == hipSuccess &&
               hipEventCreate(&c->kev0) == hipSuccess && hipEventCreate(&c->kev1) == hipSuccess &&
@@ -1029,16 +1087,8 @@ extern "C" int c3d_create(int device, c3d_ctx** out) {
         c->h_tmo[1] = 0;
     }
     if (!ok) {
-        c3d_destroy(c);
+        c3d_destroy(c);                // a nested entry: the gate is this one
         return fail(C3D_ERR_HIP, "cannot create HIP stream/events");
-    }
-    // Code objects ("code objects" above): what a default job launches from is loaded HERE, on this thread, before the caller can launch
-    // anything — not by a helper thread beside the caller's first launches, as in rounds 4-5 (that saved the first job of a process ~13 ms
-    // and is where the one device exception of round 5 was met).  Later contexts of the device find the units loaded (one atomic load).
-    {
-        const int pre = g_preload.load();
-        const int rc = pre ? ensure_units(device, pre >= 2 ? kUnitsAll : kUnitsDefault) : C3D_OK;
-        if (rc != C3D_OK) { c3d_destroy(c); return rc; }
     }
     *out = c;
     return C3D_OK;
@@ -1046,26 +1096,11 @@ extern "C" int c3d_create(int device, c3d_ctx** out) {
 
 extern "C" void c3d_destroy(c3d_ctx* c) {
     if (!c) return;
-    c->ifr.release();
-    hipSetDevice(c->device);
-    for (int g = 0; g < c3d_ctx::kMaxGroups; ++g) if (c->gstream[g]) hipStreamSynchronize(c->gstream[g]);
-    drop_graphs(c);
-    free_replica_buffers(c);
-    dev_free(c->buf.tgt); dev_free(c->buf.tgs2);
-    dev_free(c->d_prog); dev_free(c->d_claim);
-    if (c->h_tmo) (void)hipHostFree(c->h_tmo);
-    if (c->h_stage) (void)hipHostFree(c->h_stage);
-    dev_free(c->d_score);
-    if (c->ev0) hipEventDestroy(c->ev0);
-    if (c->ev1) hipEventDestroy(c->ev1);
-    if (c->kev0) hipEventDestroy(c->kev0);
-    if (c->kev1) hipEventDestroy(c->kev1);
-    for (int g = 1; g < c3d_ctx::kMaxGroups; ++g) {
-        if (c->gstream[g]) hipStreamDestroy(c->gstream[g]);
-        if (c->gev[g]) hipEventDestroy(c->gev[g]);
+    c->ifr.release();                  // host arithmetic only: joined before the gate is taken
+    {
+        Entry gate(c, 0u, false);      // hipSetDevice cannot fail for a device c3d_create accepted; the context goes either way
+        release_context(c);
     }
-    if (c->fork_ev) hipEventDestroy(c->fork_ev);
-    if (c->stream) hipStreamDestroy(c->stream);
     delete c;
 }
 
@@ -1078,19 +1113,16 @@ extern "C" int c3d_set_model(c3d_ctx* c, const c3d_model* m) {
         return fail(C3D_ERR_INVALID, "c3d_set_model: parameter out of range");
     if (c->have_targets && m->min_sep != c->model.min_sep)
         return fail(C3D_ERR_INVALID, "c3d_set_model: min_sep must be set before the targets are built");
+    // the fp64 target matrix encodes "no restraint" per potential: rebuilt by a launch (fp64 contexts load no potential-specific unit)
+    const bool targets64 = c->precision == 64 && c->b64.T;
+    Entry entry(c, 0u, targets64);
+    if (entry.rc != C3D_OK) return entry.rc;
     c->model = *m;
     c->model.msoexp = msoexp;
-    dev_free(c->buf.tgs2);                 // the pre-scaled pair targets of the per-step kernel carry 1 / mrs: rebuilt on demand
-    build_program(c);
-    if (c->have_replicas) {                // the multi-step kernel's plan depends on the potential
-        HIP_TRY(hipSetDevice(c->device));
+    drop_stale(c, STALE_PAIR_TARGETS | STALE_PROGRAM);   // the pre-scaled pair targets of the per-step kernel carry 1 / mrs: rebuilt on demand
+    if (c->have_replicas)                  // the multi-step kernel's plan depends on the potential
         if (int rc = plan_cluster(c)) return rc;
-    }
-    if (c->precision == 64 && c->b64.T) {                              // the fp64 target matrix encodes "no restraint" per potential
-        C3D_ENTRY(c, 0u);
-        return build_targets64(c);
-    }
-    return C3D_OK;
+    return targets64 ? build_targets64(c) : C3D_OK;
 }
 
 extern "C" int c3d_set_schedule(c3d_ctx* c, const c3d_stage* st, int n_stages, const c3d_fire_params* fire, float gtol,
@@ -1102,99 +1134,75 @@ extern "C" int c3d_set_schedule(c3d_ctx* c, const c3d_stage* st, int n_stages, c
     if (fire) c->fire = *fire;
     c->gtol = gtol;
     if (check_every > 0) c->check_every = check_every;
-    build_program(c);
-    return C3D_OK;
+    return drop_stale_gated(c, STALE_PROGRAM);
 }
 
 extern "C" int c3d_set_option(c3d_ctx* c, const char* key, double value) {
     if (!c || !key) return fail(C3D_ERR_INVALID, "c3d_set_option: null argument");
-    if (!strcmp(key, "use_graph")) { c->use_graph = value != 0; return C3D_OK; }
-    if (!strcmp(key, "rows_per_wave")) {
+    unsigned stale = 0;                    // what the new value invalidates: dropped below, in one place
+    if (!strcmp(key, "use_graph")) c->use_graph = value != 0;
+    else if (!strcmp(key, "rows_per_wave")) {
         if (value != 1 && value != 2 && value != 4) return fail(C3D_ERR_INVALID, "rows_per_wave must be 1, 2 or 4");
         c->rpw = (int)value;
-        drop_graphs(c);
-        return C3D_OK;
-    }
-    if (!strcmp(key, "replica_groups")) {   // groups stepped concurrently on separate streams
+        stale = STALE_GRAPHS;
+    } else if (!strcmp(key, "replica_groups")) {   // groups stepped concurrently on separate streams
         if (value < 1 || value > c3d_ctx::kMaxGroups) return fail(C3D_ERR_INVALID, "replica_groups must be 1..4");
         c->ngroups = (int)value;
-        drop_graphs(c);
-        return C3D_OK;
-    }
-    if (!strcmp(key, "event_timing")) { c->event_timing = value != 0; return C3D_OK; }
-    if (!strcmp(key, "kernel_timing")) { c->kernel_timing = value != 0; return C3D_OK; }
-    if (!strcmp(key, "resident")) { c->resident = value < 0 ? -1 : (value != 0); c->resident_skip = 0; return C3D_OK; }
-    if (!strcmp(key, "precision")) {       // 32 (the product kernels) or 64 (the fp64 reference step); call before c3d_init_replicas
+        stale = STALE_GRAPHS;
+    } else if (!strcmp(key, "event_timing")) c->event_timing = value != 0;
+    else if (!strcmp(key, "kernel_timing")) c->kernel_timing = value != 0;
+    else if (!strcmp(key, "resident")) { c->resident = value < 0 ? -1 : (value != 0); c->resident_skip = 0; }
+    else if (!strcmp(key, "precision")) {  // 32 (the product kernels) or 64 (the fp64 reference step); call before c3d_init_replicas
         if (value != 32 && value != 64) return fail(C3D_ERR_INVALID, "precision must be 32 or 64");
         c->precision = (int)value;
-        free_replica_buffers(c);
-        drop_graphs(c);
-        return C3D_OK;
-    }
-    if (!strcmp(key, "eval_rows_per_wave")) {
+        stale = STALE_REPLICAS | STALE_GRAPHS;
+    } else if (!strcmp(key, "eval_rows_per_wave")) {
         if (value != 2 && value != 4 && value != -2) return fail(C3D_ERR_INVALID, "eval_rows_per_wave must be 4, 2 (packed pair term) or -2 (two rows per wave, scalar pair term)");
         c->eval_rpw = (int)value;
-        return C3D_OK;
-    }
-    if (!strcmp(key, "pair_targets")) { c->pair_targets = value != 0; dev_free(c->buf.tgs2); drop_graphs(c); return C3D_OK; }
-    if (!strcmp(key, "wide_tiles")) { c->wide_tiles = value != 0; drop_graphs(c); return C3D_OK; }
-    if (!strcmp(key, "symmetric")) {       // takes effect at the next c3d_init_replicas with a new replica count / matrix
-        c->sym = value > 0;
-        free_replica_buffers(c);
-        drop_graphs(c);
-        return C3D_OK;
-    }
-    if (!strcmp(key, "start")) {           // A5: 0 = Philox random coil, 1 = extended strand as extn.inp lays it out (:2413-2416)
+    } else if (!strcmp(key, "pair_targets")) { c->pair_targets = value != 0; stale = STALE_PAIR_TARGETS | STALE_GRAPHS; }
+    else if (!strcmp(key, "wide_tiles")) { c->wide_tiles = value != 0; stale = STALE_GRAPHS; }
+    else if (!strcmp(key, "symmetric")) { c->sym = value > 0; stale = STALE_REPLICAS | STALE_GRAPHS; }   // takes effect at the next c3d_init_replicas with a new replica count / matrix
+    else if (!strcmp(key, "start")) {      // A5: 0 = Philox random coil, 1 = extended strand as extn.inp lays it out (:2413-2416)
         if (value != 0 && value != 1) return fail(C3D_ERR_INVALID, "start must be 0 (random coil) or 1 (extended strand)");
         c->start_mode = (int)value;
-        return C3D_OK;
-    }
-    if (!strcmp(key, "cluster")) { c->cluster = value < 0 ? -1 : (value != 0); return C3D_OK; }
-    if (!strcmp(key, "resident_inject_timeout")) { c->inject_timeout = value != 0; return C3D_OK; }   // test hook
-    if (!strcmp(key, "narrow_columns")) { c->narrow_columns = value != 0; free_replica_buffers(c); drop_graphs(c); return C3D_OK; }
-    if (!strcmp(key, "cluster_static_placement")) { c->static_place = value != 0; c->inject_misplaced = value == 2; return C3D_OK; }   // 0: per-XCD atomic slot counters; 2: test hook
-    if (!strcmp(key, "cluster_inject_incomplete")) { c->inject_incomplete = value != 0; return C3D_OK; }   // test hook
-    if (!strcmp(key, "cluster_num_xcc")) { c->num_xcc = (int)value; free_replica_buffers(c); return C3D_OK; }   // test hook: pretend a partitioned device
-    if (!strcmp(key, "prefetch_ranks")) { c->prefetch_ranks = value != 0; return C3D_OK; }
-    if (!strcmp(key, "final_minimiser_steps")) {
+    } else if (!strcmp(key, "cluster")) c->cluster = value < 0 ? -1 : (value != 0);
+    else if (!strcmp(key, "resident_inject_timeout")) c->inject_timeout = value != 0;   // test hook
+    else if (!strcmp(key, "narrow_columns")) { c->narrow_columns = value != 0; stale = STALE_REPLICAS | STALE_GRAPHS; }
+    else if (!strcmp(key, "cluster_static_placement")) { c->static_place = value != 0; c->inject_misplaced = value == 2; }   // 0: per-XCD atomic slot counters; 2: test hook
+    else if (!strcmp(key, "cluster_inject_incomplete")) c->inject_incomplete = value != 0;   // test hook
+    else if (!strcmp(key, "cluster_num_xcc")) { c->num_xcc = (int)value; stale = STALE_REPLICAS; }   // test hook: pretend a partitioned device
+    else if (!strcmp(key, "prefetch_ranks")) c->prefetch_ranks = value != 0;
+    else if (!strcmp(key, "final_minimiser_steps")) {
         if (value < 2) return fail(C3D_ERR_INVALID, "c3d_set_option: final_minimiser_steps >= 2");
         c->bb_steps = (int)value;
-        if (!c->stages.empty()) build_program(c);
-        return C3D_OK;
-    }
-    if (!strcmp(key, "final_minimiser")) {       // what a stage of kind 5 runs: 1 (default) two-point step size then FIRE, 0 FIRE throughout
+        stale = STALE_PROGRAM;
+    } else if (!strcmp(key, "final_minimiser")) {  // what a stage of kind 5 runs: 1 (default) two-point step size then FIRE, 0 FIRE throughout
         if (value != 0 && value != 1) return fail(C3D_ERR_INVALID, "c3d_set_option: final_minimiser is 0 (FIRE) or 1 (two-point step size)");
         c->final_bb = value != 0;
-        if (!c->stages.empty()) build_program(c);
-        return C3D_OK;
-    }
-    if (!strcmp(key, "cluster_xcd_count")) {      // 1..8 XCDs for this context's multi-step launches; re-plans: before c3d_init_replicas
+        stale = STALE_PROGRAM;
+    } else if (!strcmp(key, "cluster_xcd_count")) {   // 1..8 XCDs for this context's multi-step launches; re-plans: before c3d_init_replicas
         const int v = (int)value;
         if (v < 1 || v > 8 || c->xcd_base + v > 8) return fail(C3D_ERR_INVALID, "cluster_xcd_count: 1..8, and cluster_xcd_base + cluster_xcd_count <= 8");
-        c->xcd_count = v; free_replica_buffers(c); return C3D_OK;
-    }
-    if (!strcmp(key, "cluster_xcd_base")) {       // first XCD of the set; may change between launches (the plan depends on the count only)
+        c->xcd_count = v;
+        stale = STALE_REPLICAS;
+    } else if (!strcmp(key, "cluster_xcd_base")) {    // first XCD of the set; may change between launches (the plan depends on the count only)
         const int v = (int)value;
         if (v < 0 || v + c->xcd_count > 8) return fail(C3D_ERR_INVALID, "cluster_xcd_base: 0 .. 8 - cluster_xcd_count");
-        c->xcd_base = v; return C3D_OK;
-    }
-    if (!strcmp(key, "cluster_late_tiles")) { c->cluster_late = value != 0 ? -1 : 0; free_replica_buffers(c); return C3D_OK; }   // measurement knob: 0 = never; before c3d_init_replicas
-    if (!strcmp(key, "cluster_geometry")) {  // measurement knob: 100 CW + 10 RPW + helpers (0 = planner); before c3d_init_replicas
+        c->xcd_base = v;
+    } else if (!strcmp(key, "cluster_late_tiles")) { c->cluster_late = value != 0 ? -1 : 0; stale = STALE_REPLICAS; }   // measurement knob: 0 = never; before c3d_init_replicas
+    else if (!strcmp(key, "cluster_geometry")) {   // measurement knob: 100 CW + 10 RPW + helpers (0 = planner); before c3d_init_replicas
         if (value < 0 || value > 1699) return fail(C3D_ERR_INVALID, "cluster_geometry = 100 compute waves + 10 rows per wave + helper waves");
         c->cluster_geom = (int)value;
-        free_replica_buffers(c);
-        return C3D_OK;
-    }
-    if (!strcmp(key, "spin_wait_us")) { c->spin_wait_us = value < 0 ? 0 : value; return C3D_OK; }
-    if (!strcmp(key, "resident_min_ops")) { c->resident_min_ops = value < 1 ? 1 : (int)value; return C3D_OK; }
-    if (!strcmp(key, "stage_dma")) { c->stage_dma = value != 0; drop_graphs(c); return C3D_OK; }
-    if (!strcmp(key, "graph_chunk")) {
+        stale = STALE_REPLICAS;
+    } else if (!strcmp(key, "spin_wait_us")) c->spin_wait_us = value < 0 ? 0 : value;
+    else if (!strcmp(key, "resident_min_ops")) c->resident_min_ops = value < 1 ? 1 : (int)value;
+    else if (!strcmp(key, "stage_dma")) { c->stage_dma = value != 0; stale = STALE_GRAPHS; }
+    else if (!strcmp(key, "graph_chunk")) {
         if (value < 8) return fail(C3D_ERR_INVALID, "graph_chunk must be >= 8");
         c->graph_chunk = (int)value & ~1;   // even: a chunk returns to the starting parity
-        drop_graphs(c);
-        return C3D_OK;
-    }
-    return fail(C3D_ERR_INVALID, std::string("unknown option ") + key);
+        stale = STALE_GRAPHS;
+    } else return fail(C3D_ERR_INVALID, std::string("unknown option ") + key);
+    return drop_stale_gated(c, stale);
 }
 
 // 3*npad floats of LDS per workgroup must stay below the 64 KB a launch gets without opt-in

@@ -139,7 +139,7 @@ hipError_t launch_cluster(const DevModel& m, const DevFire& fp, const ClusterPla
 // Code objects.  The runtime loads a code object at the first use of one of its kernels; libc3d does not leave that to chance: every
 // translation unit that holds kernels exports a function that loads its code object on the current device (and, for the multi-step
 // units, gives every instantiation its dynamic-LDS allowance), and the loader of c3d_api.cpp ("code objects") calls them one at a time,
-// under a lock that every launching entry of the library holds shared — no code object is loaded while a thread of the process can launch.
+// under a lock that every entry of the library holds shared around its HIP calls — no code object is loaded beside any of them.
 hipError_t preload_device_unit();
 hipError_t preload_cluster_base_unit();
 hipError_t preload_cluster_unit(int pot, bool two_point);

@@ -7,8 +7,8 @@
 //   2. c3d_batch --devices 8 --lanes 3                      the production shape on an 8-GPU node: 24 contexts (the stub shows 8 devices)
 //   3. an API storm: twelve threads, each with its own context, through configurations that want DIFFERENT code objects (the shipped
 //      potential, the three other potentials' multi-step units, fp64, symmetric tiles, the embedding, the tear16 hook) while the others
-//      launch — the loader must take each unit once, and never beside a launch.
-// Passes when TSan reports nothing (halt_on_error) and the stub counted no load that overlapped a launch.
+//      launch — the loader must take each unit once, and never beside another HIP call.
+// Passes when TSan reports nothing (halt_on_error) and the stub counted no load that overlapped a HIP call (hip_stub.cpp).
 #include <sys/stat.h>
 
 #include <atomic>
@@ -140,7 +140,7 @@ int main(int argc, char** argv) {
     REQ(c3d_stub_loads() == 4 + failed_attempts + 4 * 7);   // device 0 had them; seven more devices x four units
     // 3. configurations that want other units, from twelve threads at once
     api_storm(8);
-    printf("executor under TSan: %ld launches (%ld multi-step), %ld unit loads, %ld load/launch overlaps\n", c3d_stub_launches(),
+    printf("executor under TSan: %ld HIP calls (%ld multi-step launches), %ld unit loads, %ld load/launch overlaps\n", c3d_stub_launches(),
            c3d_stub_cluster_launches(), c3d_stub_loads(), c3d_stub_violations());
     REQ(c3d_stub_violations() == 0);
     REQ(c3d_stub_cluster_launches() > 0);

@@ -6,8 +6,11 @@
 // computes nothing — except K1, which is restated on the host so that the executor has restraints to write, and the multi-step launcher,
 // which writes the completion mark its kernel would write (every seventh launch does not: the abandoned-launch path runs too).
 //
-// Beyond what TSan sees by itself, the stub CHECKS the loader's contract (c3d_api.cpp "code objects"): a unit's load function and a launch
-// must never overlap in time, whatever the thread — c3d_stub_violations() counts the overlaps, the harness fails on any.
+// Beyond what TSan sees by itself, the stub CHECKS the loader's contract (c3d_api.cpp "code objects"): a unit's load function and any HIP
+// call of the library must never overlap in time, whatever the thread.  Every function below counts as device work (LaunchScope) except
+// the device queries and pure look-ups — hipGetDeviceCount, hipSetDevice, hipGetDevicePropertiesR0600, hipDeviceGetAttribute,
+// hipHostGetDevicePointer, hipGetErrorString — so allocation, release, stream / event / graph creation and destruction and synchronisation
+// are checked as well as launches, copies and fills; c3d_stub_violations() counts the overlaps, the harness fails on any.
 // Test infrastructure; never linked into the product.
 #include <hip/hip_runtime_api.h>
 
@@ -76,29 +79,29 @@ hipError_t hipGetDevicePropertiesR0600(hipDeviceProp_tR0600* p, int) {
 }
 hipError_t hipDeviceGetAttribute(int* v, hipDeviceAttribute_t a, int) { *v = a == hipDeviceAttributeNumberOfXccs ? 8 : 0; return hipSuccess; }
 const char* hipGetErrorString(hipError_t e) { return e == hipSuccess ? "no error" : "stub error"; }
-hipError_t hipMalloc(void** p, size_t n) { *p = calloc(n ? n : 1, 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
-hipError_t hipFree(void* p) { free(p); return hipSuccess; }
-hipError_t hipHostMalloc(void** p, size_t n, unsigned) { *p = calloc(n ? n : 1, 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
-hipError_t hipHostFree(void* p) { free(p); return hipSuccess; }
+hipError_t hipMalloc(void** p, size_t n) { LaunchScope ls; *p = calloc(n ? n : 1, 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
+hipError_t hipFree(void* p) { LaunchScope ls; free(p); return hipSuccess; }
+hipError_t hipHostMalloc(void** p, size_t n, unsigned) { LaunchScope ls; *p = calloc(n ? n : 1, 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
+hipError_t hipHostFree(void* p) { LaunchScope ls; free(p); return hipSuccess; }
 hipError_t hipHostGetDevicePointer(void** d, void* h, unsigned) { *d = h; return hipSuccess; }
 hipError_t hipMemcpyAsync(void* dst, const void* src, size_t n, hipMemcpyKind, hipStream_t) { LaunchScope ls; memcpy(dst, src, n); return hipSuccess; }
 hipError_t hipMemsetAsync(void* dst, int v, size_t n, hipStream_t) { LaunchScope ls; memset(dst, v, n); return hipSuccess; }
-hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { *s = reinterpret_cast<hipStream_t>(calloc(1, 8)); return hipSuccess; }
-hipError_t hipStreamDestroy(hipStream_t s) { free(s); return hipSuccess; }
-hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
-hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { return hipSuccess; }
-hipError_t hipEventCreate(hipEvent_t* e) { *e = reinterpret_cast<hipEvent_t>(calloc(1, 8)); return hipSuccess; }
-hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { return hipEventCreate(e); }
-hipError_t hipEventDestroy(hipEvent_t e) { free(e); return hipSuccess; }
-hipError_t hipEventRecord(hipEvent_t, hipStream_t) { return hipSuccess; }
-hipError_t hipEventSynchronize(hipEvent_t) { return hipSuccess; }
-hipError_t hipEventElapsedTime(float* ms, hipEvent_t, hipEvent_t) { *ms = 0.001f; return hipSuccess; }
+hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { LaunchScope ls; *s = reinterpret_cast<hipStream_t>(calloc(1, 8)); return hipSuccess; }
+hipError_t hipStreamDestroy(hipStream_t s) { LaunchScope ls; free(s); return hipSuccess; }
+hipError_t hipStreamSynchronize(hipStream_t) { LaunchScope ls; return hipSuccess; }
+hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { LaunchScope ls; return hipSuccess; }
+hipError_t hipEventCreate(hipEvent_t* e) { LaunchScope ls; *e = reinterpret_cast<hipEvent_t>(calloc(1, 8)); return hipSuccess; }
+hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { LaunchScope ls; *e = reinterpret_cast<hipEvent_t>(calloc(1, 8)); return hipSuccess; }
+hipError_t hipEventDestroy(hipEvent_t e) { LaunchScope ls; free(e); return hipSuccess; }
+hipError_t hipEventRecord(hipEvent_t, hipStream_t) { LaunchScope ls; return hipSuccess; }
+hipError_t hipEventSynchronize(hipEvent_t) { LaunchScope ls; return hipSuccess; }
+hipError_t hipEventElapsedTime(float* ms, hipEvent_t, hipEvent_t) { LaunchScope ls; *ms = 0.001f; return hipSuccess; }
 // stream capture / graphs: the per-step path replays graphs; here a capture records nothing and a graph launch is one "launch"
-hipError_t hipStreamBeginCapture(hipStream_t, hipStreamCaptureMode) { return hipSuccess; }
-hipError_t hipStreamEndCapture(hipStream_t, hipGraph_t* g) { *g = reinterpret_cast<hipGraph_t>(calloc(1, 8)); return hipSuccess; }
-hipError_t hipGraphInstantiate(hipGraphExec_t* ge, hipGraph_t, hipGraphNode_t*, char*, size_t) { *ge = reinterpret_cast<hipGraphExec_t>(calloc(1, 8)); return hipSuccess; }
-hipError_t hipGraphDestroy(hipGraph_t g) { free(g); return hipSuccess; }
-hipError_t hipGraphExecDestroy(hipGraphExec_t g) { free(g); return hipSuccess; }
+hipError_t hipStreamBeginCapture(hipStream_t, hipStreamCaptureMode) { LaunchScope ls; return hipSuccess; }
+hipError_t hipStreamEndCapture(hipStream_t, hipGraph_t* g) { LaunchScope ls; *g = reinterpret_cast<hipGraph_t>(calloc(1, 8)); return hipSuccess; }
+hipError_t hipGraphInstantiate(hipGraphExec_t* ge, hipGraph_t, hipGraphNode_t*, char*, size_t) { LaunchScope ls; *ge = reinterpret_cast<hipGraphExec_t>(calloc(1, 8)); return hipSuccess; }
+hipError_t hipGraphDestroy(hipGraph_t g) { LaunchScope ls; free(g); return hipSuccess; }
+hipError_t hipGraphExecDestroy(hipGraphExec_t g) { LaunchScope ls; free(g); return hipSuccess; }
 hipError_t hipGraphLaunch(hipGraphExec_t, hipStream_t) { LaunchScope ls; return hipSuccess; }
 }
 

@@ -18,7 +18,7 @@ TSAN_OPTIONS=halt_on_error=1 "$TMP/host_tsan" "$MATRIX" "$MODEL" "$TMP" tsan
 fi
 # the executor and the context code under TSan, fake HIP layer (no libamdhip64, no kernels)
 CSRC="$ROOT/chromosome3d_amd/csrc"
-TF="-std=c++17 -O1 -g -fsanitize=thread -fno-omit-frame-pointer -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Wno-unused-result"
+TF="-std=c++17 -O1 -g -fsanitize=thread -fno-omit-frame-pointer -D__HIP_PLATFORM_AMD__ -I${ROCM_PATH:-/opt/rocm}/include -Wno-unused-result"
 g++ $TF -c "$CSRC/c3d_api.cpp" -o "$TMP/api.o" &
 g++ $TF -c "$CSRC/c3d_host.cpp" -o "$TMP/host.o" &
 g++ $TF -Dmain=c3d_batch_main -c "$CSRC/c3d_batch_main.cpp" -o "$TMP/batch.o" &
@@ -30,7 +30,7 @@ mkdir -p "$TMP/run"
 TSAN_OPTIONS="halt_on_error=1 second_deadlock_stack=1" "$TMP/executor_tsan" "$TMP/run" > "$TMP/executor.log" 2>&1 || { tail -40 "$TMP/executor.log"; rm -rf "$TMP"; exit 1; }
 tail -1 "$TMP/executor.log"
 # the same harness under AddressSanitizer + UBSan (leaks included): the host code of the contexts and the executor touches no freed or foreign memory
-AF="-std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Wno-unused-result"
+AF="-std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -D__HIP_PLATFORM_AMD__ -I${ROCM_PATH:-/opt/rocm}/include -Wno-unused-result"
 g++ $AF -c "$CSRC/c3d_api.cpp" -o "$TMP/a_api.o" &
 g++ $AF -c "$CSRC/c3d_host.cpp" -o "$TMP/a_host.o" &
 g++ $AF -Dmain=c3d_batch_main -c "$CSRC/c3d_batch_main.cpp" -o "$TMP/a_batch.o" &
