@@ -65,17 +65,17 @@ def job_costs(mats):
 PAIR_MAX_BEADS = 270      # a four-XCD geometry exists up to 288 beads (5 replicas per XCD x 6 workgroups of 48 rows); it pays up to ~270 (profiles/r05_config4_paired_anneals.txt: N = 287 anneals in 16.3 ms on half a device, 13.2 on all of it)
 
 
-def _prepare(solver, IF, models, seed, min_steps, gtol, xcds):
+def _prepare(solver, IF, models, seed, min_steps, gtol, xcds, final_kind=5):
     solver.set_option("cluster_xcd_base", 0)
     solver.set_option("cluster_xcd_count", xcds)
     solver.set_model(default_model())
     d10 = pipeline.IF2dist_new(solver, IF)
-    solver.set_schedule(default_schedule(min_steps), None, gtol, 250)
+    solver.set_schedule(default_schedule(min_steps, final_kind), None, gtol, 250)
     solver.init_replicas(models, seed, 0)
     return d10
 
 
-def solve_assigned(solver, mats, mine, models=20, seed=82364, min_steps=3000, gtol=1e-2, out=None, on_job=None, second=None):
+def solve_assigned(solver, mats, mine, models=20, seed=82364, min_steps=3000, gtol=1e-2, out=None, on_job=None, second=None, final_kind=5):
     """Solve the chromosomes with indices `mine`; returns records [len(mine) * models, 5]:
     chromosome index, replica, E_noe, Spearman(IF, d), anneal ms.  on_job(cid, solver) is called after every anneal (bookkeeping hooks).
     `second` = another context on the same GPU: two consecutive chromosomes of at most PAIR_MAX_BEADS beads then anneal SIDE BY SIDE, one on
@@ -106,8 +106,8 @@ def solve_assigned(solver, mats, mine, models=20, seed=82364, min_steps=3000, gt
         k = queue.pop(0)
         if second is not None and queue and small(k) and small(queue[0]):
             k2 = queue.pop(0)
-            da = _prepare(solver, mats[cids[k]], models, seed, min_steps, gtol, 4)
-            db = _prepare(second, mats[cids[k2]], models, seed, min_steps, gtol, 4)
+            da = _prepare(solver, mats[cids[k]], models, seed, min_steps, gtol, 4, final_kind)
+            db = _prepare(second, mats[cids[k2]], models, seed, min_steps, gtol, 4, final_kind)
             if solver.stat("cluster_ok") and second.stat("cluster_ok"):
                 second.set_option("cluster_xcd_base", 4)
                 err = []
@@ -127,7 +127,7 @@ def solve_assigned(solver, mats, mine, models=20, seed=82364, min_steps=3000, gt
                 collect(second, k2, db)
                 continue
             queue.insert(0, k2)                   # no four-XCD geometry for one of them: one after the other, whole device
-        d10 = _prepare(solver, mats[cids[k]], models, seed, min_steps, gtol, 8)
+        d10 = _prepare(solver, mats[cids[k]], models, seed, min_steps, gtol, 8, final_kind)
         solver.run()
         collect(solver, k, d10)
     order = {k: i for i, k in enumerate(mine)}

@@ -201,6 +201,12 @@ struct c3d_ctx {
     long k1_recomputed = 0, k1_patched = 0;   // K1: near-tie elements redone on the host in the reference's order / changed by it
     long graph_captures = 0, graph_launches = 0, step_launches = 0, resident_launches = 0, cluster_launches = 0;
     bool has_two_point = false;            // the program holds two-point minimiser steps (run_ops splits ranges at their borders)
+    bool has_lbfgs = false;                // the program holds L-BFGS steps (kinds 8 / 9: run_ops splits ranges at their borders, per-step path only)
+    int lbfgs_mem = 5;                     // option lbfgs_memory: pairs an L-BFGS stage keeps (1..8), fixed at the stage's first step
+    c3d::LbfgsBuffers lb{};                // the L-BFGS history, tile sums and state (ensure_lbfgs), freed with the replica buffers
+    long lbfgs_steps = 0;                  // L-BFGS steps run (stat "lbfgs_steps")
+    int lbfgs_parity = -1;                 // parity the last L-BFGS step left its state in (stat "lbfgs_resets")
+    bool last_lbfgs = false;               // the last per-step range ran L-BFGS steps (c3d_step_kernel_name)
     bool last_two_point = false;           // the last multi-step launch was k_cluster_tp (its range held two-point minimiser steps)
     int last_path = 0;                     // 0 per-step, 2 k_cluster, 3 fp64 reference (what the last run_ops used)
     bool last_general = false;             // the last per-step launch took the general-form kernel (general tails, or an op without restraint weight)
@@ -232,6 +238,8 @@ void free_replica_buffers(c3d_ctx* c) {
     c->crec_bytes = 0; c->cl_ok = false;
     dev_free(c->buf.Vinit); dev_free(c->buf.E); dev_free(c->d_feval);
     dev_free(c->d_sym_scratch); dev_free(c->d_sym_tiles);
+    dev_free(c->lb.hist); dev_free(c->lb.part); dev_free(c->lb.S[0]); dev_free(c->lb.S[1]);
+    c->lbfgs_parity = -1;
     dev_free(c->b64.T); dev_free(c->b64.t10); dev_free(c->b64.Vinit);
     for (int k = 0; k < 2; ++k) { dev_free(c->b64.X[k]); dev_free(c->b64.V[k]); dev_free(c->b64.P[k]); dev_free(c->b64.S[k]); }
     c->have_replicas = false;
@@ -334,23 +342,29 @@ c3d::DevStep dev_step(const c3d_ctx* c, int kind, float dt, float w_all, float w
     return p;
 }
 
+bool is_two_point(int kind) { return kind == 5 || kind == 6; }
+bool is_lbfgs(int kind) { return kind == 8 || kind == 9; }
+
 void build_program(c3d_ctx* c) {
     c->program.clear();
     int prev_kind = -1;
     for (size_t s = 0; s < c->stages.size(); ++s) {
         const c3d_stage& st = c->stages[s];
-        if (st.kind == 2 || st.kind == 5) {
+        if (st.kind == 2 || st.kind == 5 || st.kind == 8) {
             // kind 3 / 6 = first step of a minimiser's run (fresh state).  A stage of kind 5 starts with the two-point step-size minimiser
             // (kinds 6 / 5) and hands over to FIRE (3 / 2) after bb_steps of them if the exit test has not ended the stage by then: the
             // two-point method has no descent guarantee — one replica in a few hundred ends in a cycle of long moves instead of a minimum —
             // and FIRE finishes what it leaves (the CPU restatement does the same: c3o_run_schedule).  Option final_minimiser = 0: kind 5 runs as FIRE throughout.
-            const int nbb = st.kind == 5 && c->final_bb ? std::min(st.nsteps, c->bb_steps) : 0;
+            // A stage of kind 8 runs L-BFGS (kinds 9 / 8) for its first final_minimiser_steps steps and hands over to FIRE the same way;
+            // option final_minimiser does not apply to it.
+            const bool lbfgs = st.kind == 8;
+            const int nbb = (st.kind == 5 && c->final_bb) || lbfgs ? std::min(st.nsteps, c->bb_steps) : 0;
             for (int k = 0; k < st.nsteps; ++k) {
-                const int kind = k < nbb ? (k == 0 ? 6 : 5) : (k == nbb ? 3 : 2);
+                const int kind = k < nbb ? (k == 0 ? (lbfgs ? 9 : 6) : (lbfgs ? 8 : 5)) : (k == nbb ? 3 : 2);
                 c->program.push_back({dev_step(c, kind, 0.0f, st.w_all, st.w_vdw, st.repel_s, 0.0f), (int)s, true});
             }
         } else {
-            if (prev_kind == 2 || prev_kind == 5 || prev_kind == -1)
+            if (prev_kind == 2 || prev_kind == 5 || prev_kind == 8 || prev_kind == -1)
                 c->program.push_back({dev_step(c, 4, 0.0f, st.w_all, st.w_vdw, st.repel_s, st.t_bath), (int)s, false});
             for (int k = 0; k < st.nsteps; ++k)
                 c->program.push_back({dev_step(c, st.kind, st.dt, st.w_all, st.w_vdw, st.repel_s, st.t_bath), (int)s, true});
@@ -361,7 +375,9 @@ void build_program(c3d_ctx* c) {
     c->zero_weight = false;
     for (const Op& op : c->program) c->zero_weight = c->zero_weight || op.p.w_rs == 0.0f;
     c->has_two_point = false;
-    for (const Op& op : c->program) c->has_two_point = c->has_two_point || op.p.kind >= 5;
+    for (const Op& op : c->program) c->has_two_point = c->has_two_point || is_two_point(op.p.kind);
+    c->has_lbfgs = false;
+    for (const Op& op : c->program) c->has_lbfgs = c->has_lbfgs || is_lbfgs(op.p.kind);
     drop_graphs(c);
     // run-length code of the whole program (a FIRE stage is 2 runs, the cool ramp 81) for the cluster kernel
     c->prog_runs.clear();
@@ -613,6 +629,21 @@ bool wide_step(const c3d_ctx* c, const c3d::DevModel& m, bool general) {
     return c->wide_tiles && c->pair_targets && !general && m.noe_pot == 4 && m.wl == 4 && m.nleft == 0 && c->npad > 1024 && c->rpw == 2;
 }
 
+// The L-BFGS history (2 x 8 pairs x 3 x npad floats a replica: sized for the largest memory, so that lbfgs_memory never reallocates), the
+// tile sums and the state, zeroed; allocated outside any stream capture (run_ops_segment), freed with the replica buffers
+int ensure_lbfgs(c3d_ctx* c) {
+    if (c->lb.hist) return C3D_OK;
+    const size_t hist = c3d::lbfgs_hist_floats(c->npad) * c->nrep, part = (size_t)c->nrep * c->ntiles * c3d::kLbfgsQ;
+    HIP_TRY(hipMalloc(&c->lb.hist, sizeof(float) * hist));
+    HIP_TRY(hipMalloc(&c->lb.part, sizeof(float) * part));
+    for (int k = 0; k < 2; ++k) HIP_TRY(hipMalloc(&c->lb.S[k], sizeof(c3d::LbfgsState) * c->nrep));
+    HIP_TRY(hipMemsetAsync(c->lb.hist, 0, sizeof(float) * hist, c->stream));
+    HIP_TRY(hipMemsetAsync(c->lb.part, 0, sizeof(float) * part, c->stream));
+    for (int k = 0; k < 2; ++k) HIP_TRY(hipMemsetAsync(c->lb.S[k], 0, sizeof(c3d::LbfgsState) * c->nrep, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));          // the step launches run on the group streams
+    return C3D_OK;
+}
+
 int ensure_pair_targets(c3d_ctx* c, const c3d::DevModel& m) {
     if (c->buf.tgs2 || !c->pair_targets || m.noe_pot != 4 || m.wl != 4 || m.nleft != 0 || c->npad <= 1024 || c->rpw != 2 || !c->buf.tgt) return C3D_OK;
     HIP_TRY(hipMalloc(&c->buf.tgs2, sizeof(float) * c3d::pair_targets_floats(c->n, c->npad)));
@@ -636,6 +667,12 @@ int launch_op(c3d_ctx* c, const Op& op, int g, int par) {
         return C3D_OK;
     }
     c->last_general = general_step(m, op.p);
+    if (is_lbfgs(op.p.kind)) {             // two launches: forces + tile sums, then sums + direction + move (symmetric tiles do not apply)
+        hipError_t e = c3d::launch_lbfgs_eval(m, op.p, c->buf, c->lb, par, c->lbfgs_mem, c->last_general, wide_step(c, m, c->last_general), c->gstream[g]);
+        if (e == hipSuccess) e = c3d::launch_lbfgs_move(m, op.p, dev_fire(c), c->buf, c->lb, par, c->lbfgs_mem, c->gstream[g]);
+        if (e != hipSuccess) return fail(C3D_ERR_HIP, std::string("L-BFGS step launch: ") + hipGetErrorString(e));
+        return C3D_OK;
+    }
     hipError_t e = use_sym(c) ? c3d::launch_step_sym(m, op.p, dev_fire(c), c->buf, par, c->d_sym_tiles, c->d_sym_scratch, c->gstream[g])
                               : c3d::launch_step(m, op.p, dev_fire(c), c->buf, par, c->last_general, wide_step(c, m, c->last_general), c->gstream[g]);
     if (e != hipSuccess) return fail(C3D_ERR_HIP, std::string("step launch: ") + hipGetErrorString(e));
@@ -724,7 +761,7 @@ int run_cluster(c3d_ctx* c, size_t nops, bool* ran) {
     pl.static_place = c->static_place ? (c->inject_misplaced ? 2 : 1) : 0;
     pl.xcd_base = c->xcd_base;
     pl.two_point = false;
-    for (size_t k = 0; k < nops && !pl.two_point; ++k) pl.two_point = c->program[c->pc + k].p.kind >= 5;
+    for (size_t k = 0; k < nops && !pl.two_point; ++k) pl.two_point = is_two_point(c->program[c->pc + k].p.kind);
     c->last_two_point = pl.two_point;
     c->inject_misplaced = false;
     c->h_tmo[2] = 0;
@@ -770,21 +807,27 @@ int run_cluster(c3d_ctx* c, size_t nops, bool* ran) {
 
 // run program ops [pc, pc + nops): eager or via cached graphs; every replica group advances on its
 // own stream (fork from / join into stream 0 around the call)
-int run_ops_segment(c3d_ctx* c, size_t nops, bool zero_w);
+int run_ops_segment(c3d_ctx* c, size_t nops, bool zero_w, bool lbfgs = false);
 
 // A stage without restraint weight (w_all = 0: the clamp form divides by it) takes the general kernels; the ops around it keep the
 // multi-step launches: the range is split where the weight changes between zero and non-zero.
 // The range is also split where two-point minimiser steps (kinds 5 / 6) begin or end: a multi-step launch that holds any of them runs
 // k_cluster_tp, 2.5 % slower per step than k_cluster (c3d_cluster.hip) — the MD stages before a final stage of kind 5 keep their kernel
-// also when a caller asks for the whole schedule in one c3d_run_steps.
+// also when a caller asks for the whole schedule in one c3d_run_steps.  And where L-BFGS steps (kinds 9 / 8) begin or end: they run on the
+// per-step path only (k_lbfgs_eval + k_lbfgs_move), the MD stages and the FIRE hand-over around them keep the multi-step kernel.
 int run_ops(c3d_ctx* c, size_t nops) {
-    if ((!c->zero_weight && !c->has_two_point) || c->precision == 64) return run_ops_segment(c, nops, false);
+    if ((!c->zero_weight && !c->has_two_point && !c->has_lbfgs) || c->precision == 64) return run_ops_segment(c, nops, false);
     const size_t end = c->pc + nops;
     while (c->pc < end) {
-        const bool z = c->program[c->pc].p.w_rs == 0.0f, tp = c->program[c->pc].p.kind >= 5;
+        const c3d::DevStep& p0 = c->program[c->pc].p;
+        const bool z = p0.w_rs == 0.0f, tp = is_two_point(p0.kind), lb = is_lbfgs(p0.kind);
         size_t k = 1;
-        while (c->pc + k < end && (c->program[c->pc + k].p.w_rs == 0.0f) == z && (c->program[c->pc + k].p.kind >= 5) == tp) ++k;
-        const int rc = run_ops_segment(c, k, z);
+        while (c->pc + k < end) {
+            const c3d::DevStep& p = c->program[c->pc + k].p;
+            if ((p.w_rs == 0.0f) != z || is_two_point(p.kind) != tp || is_lbfgs(p.kind) != lb) break;
+            ++k;
+        }
+        const int rc = run_ops_segment(c, k, z, lb);
         if (rc) return rc;
     }
     return C3D_OK;
@@ -801,9 +844,9 @@ int ensure_group_streams(c3d_ctx* c, int G) {
     return C3D_OK;
 }
 
-int run_ops_segment(c3d_ctx* c, size_t nops, bool zero_w) {
+int run_ops_segment(c3d_ctx* c, size_t nops, bool zero_w, bool lbfgs) {
     if (nops == 0) return C3D_OK;
-    if (c->precision == 64 || zero_w) { }                                           // fp64: the per-step path below (k64_step), never the cluster kernel
+    if (c->precision == 64 || zero_w || lbfgs) { }          // fp64 (k64_step) and L-BFGS steps: the per-step path below, never the cluster kernel
     else if (c->resident_skip > 0 && c->resident < 1) --c->resident_skip;     // cooling off after an abandoned launch
     else if (nops >= (size_t)c->resident_min_ops && nops < ((size_t)1 << 20)) {
         bool ran = false;
@@ -813,9 +856,12 @@ int run_ops_segment(c3d_ctx* c, size_t nops, bool zero_w) {
     }
     c->last_path = 0;
     c->ev1_recorded = false;
-    if (c->precision != 64 && !use_sym(c)) {          // (before any stream capture begins: it allocates and synchronises)
+    if (c->precision != 64 && (!use_sym(c) || lbfgs)) {          // (before any stream capture begins: it allocates and synchronises)
         if (int rc = ensure_pair_targets(c, dev_model(c))) return rc;
     }
+    if (lbfgs)
+        if (int rc = ensure_lbfgs(c)) return rc;
+    c->last_lbfgs = lbfgs;
     const int G = active_groups(c);
     if (int rc = ensure_group_streams(c, G)) return rc;
     // every replica group advances on its own stream (fork from / join into stream 0 around the range): while one
@@ -837,13 +883,13 @@ int run_ops_segment(c3d_ctx* c, size_t nops, bool zero_w) {
                 }
             }
         } else {
-            // one graph per (range, parity, group); homogeneous FIRE ranges (same stage, all kind 2) share a graph
-            // regardless of pc
+            // one graph per (range, parity, group); homogeneous minimiser ranges (same stage, all kind 2, all 5 or all 8) share a graph
+            // regardless of pc (kind 8 keeps its ring head and counts on the device)
             const Op& first = c->program[c->pc];
             const Op& last = c->program[c->pc + chunk - 1];
             long sig = (long)c->pc;
-            if ((first.p.kind == 2 || first.p.kind == 5) && last.p.kind == first.p.kind && first.stage == last.stage)
-                sig = -(long)(first.stage + 1) - (first.p.kind == 5 ? 1000000L : 0L);     // (a stage of kind 5 has a two-point part and a FIRE part)
+            if ((first.p.kind == 2 || first.p.kind == 5 || first.p.kind == 8) && last.p.kind == first.p.kind && first.stage == last.stage)
+                sig = -(long)(first.stage + 1) - (first.p.kind == 5 ? 1000000L : first.p.kind == 8 ? 2000000L : 0L);     // (a stage of kind 5 or 8 has a minimiser part and a FIRE part)
             if (c->graphs.size() >= 2048) {                        // bounded: a caller with ever new ranges starts over
                 for (int g = 0; g < G; ++g) HIP_TRY(hipStreamSynchronize(c->gstream[g]));
                 drop_graphs(c);
@@ -872,6 +918,7 @@ int run_ops_segment(c3d_ctx* c, size_t nops, bool zero_w) {
             }
         }
         c->step_launches += (long)chunk * G;
+        if (lbfgs) { c->lbfgs_steps += (long)chunk; c->lbfgs_parity = c->parity ^ (int)(chunk & 1); }
         if (chunk & 1) c->parity ^= 1;
         for (size_t k = 0; k < chunk; ++k)
             if (c->program[c->pc + k].counted) { ++c->steps_done; ++c->last_steps; }
@@ -1128,8 +1175,11 @@ extern "C" int c3d_set_model(c3d_ctx* c, const c3d_model* m) {
 extern "C" int c3d_set_schedule(c3d_ctx* c, const c3d_stage* st, int n_stages, const c3d_fire_params* fire, float gtol,
                                 int check_every) {
     if (!c || !st || n_stages < 1) return fail(C3D_ERR_INVALID, "c3d_set_schedule: bad arguments");
-    for (int k = 0; k < n_stages; ++k)
-        if (st[k].kind < 0 || (st[k].kind > 2 && st[k].kind != 5) || st[k].nsteps < 0) return fail(C3D_ERR_INVALID, "c3d_set_schedule: bad stage");
+    for (int k = 0; k < n_stages; ++k) {
+        if (st[k].kind < 0 || (st[k].kind > 2 && st[k].kind != 5 && st[k].kind != 8) || st[k].nsteps < 0) return fail(C3D_ERR_INVALID, "c3d_set_schedule: bad stage");
+        if (st[k].kind == 8 && c->precision == 64)
+            return fail(C3D_ERR_INVALID, "c3d_set_schedule: a stage of kind 8 (L-BFGS) has no fp64 form; set precision 32 first");
+    }
     c->stages.assign(st, st + n_stages);
     if (fire) c->fire = *fire;
     c->gtol = gtol;
@@ -1154,6 +1204,9 @@ extern "C" int c3d_set_option(c3d_ctx* c, const char* key, double value) {
     else if (!strcmp(key, "resident")) { c->resident = value < 0 ? -1 : (value != 0); c->resident_skip = 0; }
     else if (!strcmp(key, "precision")) {  // 32 (the product kernels) or 64 (the fp64 reference step); call before c3d_init_replicas
         if (value != 32 && value != 64) return fail(C3D_ERR_INVALID, "precision must be 32 or 64");
+        if (value == 64)
+            for (const c3d_stage& st : c->stages)
+                if (st.kind == 8) return fail(C3D_ERR_INVALID, "precision 64: the schedule holds a stage of kind 8 (L-BFGS), which has no fp64 form");
         c->precision = (int)value;
         stale = STALE_REPLICAS | STALE_GRAPHS;
     } else if (!strcmp(key, "eval_rows_per_wave")) {
@@ -1180,6 +1233,10 @@ extern "C" int c3d_set_option(c3d_ctx* c, const char* key, double value) {
         if (value != 0 && value != 1) return fail(C3D_ERR_INVALID, "c3d_set_option: final_minimiser is 0 (FIRE) or 1 (two-point step size)");
         c->final_bb = value != 0;
         stale = STALE_PROGRAM;
+    } else if (!strcmp(key, "lbfgs_memory")) {     // pairs a kind-8 stage keeps; takes effect at the next stage's first step
+        if (value != (int)value || value < 1 || value > c3d::kLbfgsMaxPairs) return fail(C3D_ERR_INVALID, "c3d_set_option: lbfgs_memory is 1..8");
+        c->lbfgs_mem = (int)value;
+        stale = STALE_GRAPHS;
     } else if (!strcmp(key, "cluster_xcd_count")) {   // 1..8 XCDs for this context's multi-step launches; re-plans: before c3d_init_replicas
         const int v = (int)value;
         if (v < 1 || v > 8 || c->xcd_base + v > 8) return fail(C3D_ERR_INVALID, "cluster_xcd_count: 1..8, and cluster_xcd_base + cluster_xcd_count <= 8");
@@ -1582,7 +1639,7 @@ extern "C" int c3d_run(c3d_ctx* c) {
     int rc = begin_timing(c);
     if (rc) return rc;
     const int last_stage = (int)c->stages.size() - 1;
-    const bool early = c->gtol > 0.0f && last_stage >= 0 && (c->stages[last_stage].kind == 2 || c->stages[last_stage].kind == 5);
+    const bool early = c->gtol > 0.0f && last_stage >= 0 && (c->stages[last_stage].kind == 2 || c->stages[last_stage].kind == 5 || c->stages[last_stage].kind == 8);
     // everything before the final minimisation
     size_t nfixed = c->program.size() - c->pc;
     if (early) {
@@ -1652,6 +1709,19 @@ extern "C" int c3d_get_stat(const c3d_ctx* c, const char* key, double* value) {
         if (rc) return rc;
         *value = rms;
     }
+    else if (!strcmp(key, "lbfgs_steps")) *value = (double)c->lbfgs_steps;
+    else if (!strcmp(key, "lbfgs_resets")) {
+        // memory drops of the last L-BFGS stage, summed over the replicas (device state of the parity its last step wrote)
+        *value = 0;
+        if (c->lbfgs_parity >= 0 && c->lb.S[c->lbfgs_parity]) {
+            C3D_ENTRY(c, 0u);
+            if (int rc = read_back(const_cast<c3d_ctx*>(c), c->lb.S[c->lbfgs_parity], sizeof(c3d::LbfgsState) * c->nrep)) return rc;
+            const c3d::LbfgsState* h = static_cast<const c3d::LbfgsState*>(c->h_stage);
+            long r = 0;
+            for (int k = 0; k < c->nrep; ++k) r += h[k].resets;
+            *value = (double)r;
+        }
+    }
     else if (!strcmp(key, "k1_recomputed")) *value = (double)c->k1_recomputed;
     else if (!strcmp(key, "k1_patched")) *value = (double)c->k1_patched;
     else if (!strcmp(key, "last_path")) *value = (double)c->last_path;
@@ -1680,6 +1750,10 @@ extern "C" const char* c3d_step_kernel_name(const c3d_ctx* c) {
     const char* gen = (general_tail(m) || c->last_general) ? "true" : "false";     // of the last op launched on the per-step path
     const char* rs1 = (!general_tail(m) && m.rs == 1.0f) ? "true" : "false";
     if (c->last_path == 2) snprintf(buf, sizeof(buf), "c3d::k_cluster%s<%d, %d, %d, %d, %s>", c->last_two_point ? "_tp" : "", m.noe_pot, c->cl_plan.rpw, m.npad / 256, m.wl, c->cl_plan.late_tiles ? "true" : "false");
+    else if (c->last_lbfgs && c->precision != 64) {     // the force pass of an L-BFGS step (k_lbfgs_move follows it)
+        if (wide_step(c, m, general_tail(m) || c->last_general)) snprintf(buf, sizeof(buf), "c3d::k_lbfgs_eval<4, false, 4, false, 16, true>");
+        else snprintf(buf, sizeof(buf), "c3d::k_lbfgs_eval<%d, %s, %d, %s, 8, false>", m.noe_pot, gen, m.rpw, (m.wl == 4 && m.nleft == 0) ? "false" : "true");
+    }
     else if (use_sym(c)) snprintf(buf, sizeof(buf), "c3d::k_pairs_sym<%d, %s, false>", m.noe_pot, rs1);
     else if (c->precision == 64) snprintf(buf, sizeof(buf), "c3d::k64_step<%d, %s, %s>", m.noe_pot, general_tail(m) ? "true" : "false", c->last_fold64 ? "true" : "false");
     else if (wide_step(c, m, general_tail(m) || c->last_general)) snprintf(buf, sizeof(buf), "c3d::k_step<4, false, 4, false, 16, true>");

@@ -6,6 +6,7 @@
 //   K3  k_step<> (MD kinds)            K2 + leap-frog update, Berendsen / velocity-rescale
 //                                      thermostat, COM removal    (deck :1646-1700, :1729-1782)
 //   K4  k_step<> (FIRE kinds)          K2 + FIRE minimiser update (deck :1790-1803, L-BFGS there)
+//   K4b k_lbfgs_eval / k_lbfgs_move   K2 + L-BFGS step of stage kind 8 (c3d_lbfgs.h; deck :1790-1803)
 //   K6  k_energy                       fp64 energies per replica  (REMARK noe, :602-618)
 //       (assessment / Spearman scoring of resident replicas: c3d_score.hip)
 //
@@ -494,6 +495,12 @@ hipError_t launch_if_to_target(const double* IF, int n, int npad, double alpha, 
                        dist10, tgt, flags, nflag);
     return hipGetLastError();
 }
+
+}  // namespace c3d
+
+#include "c3d_lbfgs.h"
+
+namespace c3d {
 
 hipError_t preload_device_unit() {
     hipFuncAttributes a;

@@ -49,7 +49,8 @@ struct DevModel {
 
 struct DevStep {
     int kind;        // 0 MD T-coupling, 1 MD velocity rescale, 2 FIRE step, 3 first FIRE step of a stage, 4 MD begin,
-                     // 5 two-point step-size (Barzilai-Borwein) minimiser step, 6 its first step of a stage
+                     // 5 two-point step-size (Barzilai-Borwein) minimiser step, 6 its first step of a stage,
+                     // 8 L-BFGS step, 9 its first step of a stage (k_lbfgs_eval + k_lbfgs_move only: never k_step / k_cluster)
     float dt;
     float w_all;     // weights * w
     float w_noe2n;   // -2 * w_all * s_noe
@@ -98,6 +99,31 @@ hipError_t launch_eval_forces(const DevModel& m, const DevStep& p, const DevBuff
 hipError_t launch_energy(const DevModel& m, const DevStep& p, const DevBuffers& b, int parity, float s_noe,
                          float k_rep, double rep_r2, hipStream_t s);
 hipError_t launch_centre(const DevModel& m, const DevBuffers& b, int parity, hipStream_t s);
+// L-BFGS stage (kinds 8 / 9, per-step path only): two launches a step.  k_lbfgs_eval = the step kernel's forces (same tile_forces<> and
+// template choices as launch_step) and per-tile sums of the dot products the compact form (Byrd-Nocedal-Schnabel) needs; k_lbfgs_move =
+// the replica sums in fp64, the 2m x 2m algebra (redundantly in every workgroup of a replica) and the move.  Layouts:
+//   hist  [nrep][2: s, y][kLbfgsMaxPairs slots][3][npad]   the pairs, a ring of `mem` slots (a workgroup touches its own rows only)
+//   part  [nrep][ntiles][kLbfgsQ]                             per tile: slot j: (F.s_j, F.y_j, s_j.y, y_j.y) at 4j, then s.s, F.F
+//         (F = this evaluation's force, (s, y) = the pair this evaluation completes: s in slot nxt, y = F_prev - F written there)
+//   S     [2][nrep] LbfgsState, double buffered by step parity; V[parity^1] = the force of the evaluation, P[parity^1] = (move.move, F.F, 0, 0)
+constexpr int kLbfgsMaxPairs = 8;
+constexpr int kLbfgsQ = 4 * kLbfgsMaxPairs + 4;
+struct LbfgsState {
+    int cnt, head, mem, resets;      // pairs held, slot of the newest, ring size m (fixed at the stage's first step), memory drops
+    double gamma;                    // H0 = gamma I
+    double SY[kLbfgsMaxPairs][kLbfgsMaxPairs];   // s_slot(i) . y_slot(j) (the upper triangle in age order is read)
+    double YY[kLbfgsMaxPairs][kLbfgsMaxPairs];
+};
+struct LbfgsBuffers {
+    float* hist;
+    float* part;
+    LbfgsState* S[2];
+};
+__host__ __device__ inline size_t lbfgs_hist_floats(int npad) { return (size_t)2 * kLbfgsMaxPairs * 3 * npad; }   // per replica
+hipError_t launch_lbfgs_eval(const DevModel& m, const DevStep& p, const DevBuffers& b, const LbfgsBuffers& lb, int parity, int mem,
+                             bool general_tail, bool wide, hipStream_t s);
+hipError_t launch_lbfgs_move(const DevModel& m, const DevStep& p, const DevFire& fp, const DevBuffers& b, const LbfgsBuffers& lb, int parity,
+                             int mem, hipStream_t s);
 size_t pair_targets_floats(int n, int npad);           // size of DevBuffers::tgs2
 hipError_t launch_pair_targets(const DevModel& m, const float* tgt, float* tgs2, hipStream_t s);
 struct StepRun {    // `count` consecutive steps with the same parameters

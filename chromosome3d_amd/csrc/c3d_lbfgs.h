@@ -1,0 +1,322 @@
+// c3d_lbfgs.h — the L-BFGS stage (kinds 8 / 9) of the per-step path: k_lbfgs_eval and k_lbfgs_move.  Included by c3d_device.hip only:
+// the kernels live in that unit's code object (no unit of their own).
+//
+// One L-BFGS step = two launches per replica group.  The direction needs global sums of the gradient just computed (its projections on
+// the stored pairs: tools/minimiser_study.py lbfgs_fixed_step, late = False), and on the per-step path the kernel boundary is the only
+// synchronisation between workgroups:
+//   k_lbfgs_eval  forces of the rows (tile_forces<>, the choices launch_step makes), y = F_prev - F into the ring, per-tile sums of
+//                 F.s_j, F.y_j, s_j.y, y_j.y, s.s, F.F (c3d_internal.h "L-BFGS stage")
+//   k_lbfgs_move  every workgroup of a replica: the tile sums in fp64 in one fixed order, the pair test, the new column of S'Y and Y'Y,
+//                 the two triangular solves of the compact form, the descent test (thread 0, LDS); then its rows: the direction
+//                 gamma F - sum top_i s_i + gamma sum u_i y_i, the per-bead cap, the move, s into the ring, the tile sums P.
+// Fixed unit step, no energy, no line search.  Everything that varies from step to step (ring head, counts) lives on the device: one
+// captured graph serves every chunk of a stage.
+#pragma once
+
+namespace c3d {
+
+// fixed tree over the 8 rows of a tile (the order of tile_sum8)
+__device__ __forceinline__ float row_sum8(const float* q, int stride) {
+    return ((q[0] + q[stride]) + (q[2 * stride] + q[3 * stride])) + ((q[4 * stride] + q[5 * stride]) + (q[6 * stride] + q[7 * stride]));
+}
+
+template <int POT, bool GEN, int RPW, bool NC, int TR = kTileRows, bool WIDE = false>
+__global__ __launch_bounds__(64 * TR / RPW) __attribute__((amdgpu_waves_per_eu(WIDE ? 4 : 1))) void k_lbfgs_eval(
+    const float* __restrict__ xin, const float* __restrict__ tgt, const float* __restrict__ fprev, float* __restrict__ fout,
+    float* __restrict__ hist, float* __restrict__ part, const LbfgsState* __restrict__ sin, const DevModel m, const DevStep p,
+    const int mem0) {
+    constexpr int WAVES = TR / RPW;
+    constexpr int BLOCK = 64 * WAVES;
+    constexpr int TILES = TR / kTileRows;
+    constexpr int Q = kLbfgsQ;
+    static_assert(TR % kTileRows == 0 && TILES >= 1 && TILES <= 2, "a workgroup owns one or two 8-row tiles");
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    int tile, rep;
+    if (!block_to_tile(m, tile, rep)) return;
+    tile *= TILES;
+    if (tile >= m.ntiles) return;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int npad = m.npad;
+    float* xs = smem;
+    float* ys = smem + npad;
+    float* zs = smem + 2 * npad;
+    float* rowq = smem + 3 * npad;              // [TR][Q]
+    const size_t roff = (size_t)rep * 3 * npad;
+    const int row0 = tile * kTileRows + wave * RPW;
+    const int row = row0 + lane;
+    const bool fin_lane = lane < RPW;
+    const bool finisher = fin_lane && row < m.n;
+
+    if (m.stage_dma) lds_dma_copy<BLOCK>(xin + roff, smem, 3 * npad, tid);
+    else for (int b = 4 * tid; b < 3 * npad; b += 4 * BLOCK) *reinterpret_cast<float4*>(smem + b) = *reinterpret_cast<const float4*>(xin + roff + b);
+    float4 tv[RPW];
+    if (pair_targets_in_use<POT, GEN, RPW, NC>(m)) pair_targets_prefetch(m, row0, lane, 0, tv);
+    else tile_prefetch<RPW, NC>(m, tgt, row0, lane, 0, tv);
+    const bool first = p.kind == 9;
+    int mem = mem0, nxt = 0;
+    if (!first) {      // (clamped into the ring whatever the state holds: a stage always begins with kind 9, which sets it)
+        mem = min(max(sin[rep].mem, 1), kLbfgsMaxPairs);
+        nxt = min(max(sin[rep].head, 0), mem - 1) + 1;
+        if (nxt == mem) nxt = 0;
+    }
+    float fpx = 0.0f, fpy = 0.0f, fpz = 0.0f;
+    const size_t ix = roff + row, iy = ix + npad, iz = iy + npad;
+    if (finisher && !first) { fpx = fprev[ix]; fpy = fprev[iy]; fpz = fprev[iz]; }
+    __syncthreads();
+
+    float Fx = 0.0f, Fy = 0.0f, Fz = 0.0f;
+    tile_forces<POT, GEN, RPW, NC, true, WIDE>(m, p, tgt, xs, ys, zs, row0, lane, tv, Fx, Fy, Fz);
+
+    if (fin_lane) {
+        float* q = rowq + (row - tile * kTileRows) * Q;
+        for (int k = 0; k < Q; ++k) q[k] = 0.0f;
+        if (finisher) {
+            fout[ix] = Fx; fout[iy] = Fy; fout[iz] = Fz;
+            q[Q - 3] = fmaf(Fx, Fx, fmaf(Fy, Fy, Fz * Fz));
+            if (!first) {
+                float* hs = hist + (size_t)rep * lbfgs_hist_floats(npad) + row;            // slot j, component c: + (3 j + c) npad
+                float* hy = hs + (size_t)3 * kLbfgsMaxPairs * npad;
+                const float yx = fpx - Fx, yy = fpy - Fy, yz = fpz - Fz;
+                float* yn = hy + (size_t)3 * nxt * npad;
+                yn[0] = yx; yn[npad] = yy; yn[2 * npad] = yz;
+                const float* sn = hs + (size_t)3 * nxt * npad;
+                const float sx = sn[0], sy = sn[npad], sz = sn[2 * npad];
+                q[Q - 4] = fmaf(sx, sx, fmaf(sy, sy, sz * sz));
+#pragma unroll
+                for (int j = 0; j < kLbfgsMaxPairs; ++j) {
+                    if (j >= mem) break;
+                    float ax, ay, az, bx, by, bz;
+                    if (j == nxt) { ax = sx; ay = sy; az = sz; bx = yx; by = yy; bz = yz; }
+                    else {
+                        const float* a = hs + (size_t)3 * j * npad;
+                        const float* b = hy + (size_t)3 * j * npad;
+                        ax = a[0]; ay = a[npad]; az = a[2 * npad]; bx = b[0]; by = b[npad]; bz = b[2 * npad];
+                    }
+                    q[4 * j + 0] = fmaf(Fx, ax, fmaf(Fy, ay, Fz * az));
+                    q[4 * j + 1] = fmaf(Fx, bx, fmaf(Fy, by, Fz * bz));
+                    q[4 * j + 2] = fmaf(ax, yx, fmaf(ay, yy, az * yz));
+                    q[4 * j + 3] = fmaf(bx, yx, fmaf(by, yy, bz * yz));
+                }
+            }
+        }
+    }
+    __syncthreads();
+    for (int t = tid; t < TILES * Q; t += BLOCK) {
+        const int tt = t / Q, k = t - tt * Q;
+        if (tile + tt < m.ntiles) part[((size_t)rep * m.ntiles + tile + tt) * Q + k] = row_sum8(rowq + tt * kTileRows * Q + k, Q);
+    }
+}
+
+// rows per workgroup of the move
+constexpr int kLbfgsMoveRows = 256;
+
+__global__ __launch_bounds__(kLbfgsMoveRows) void k_lbfgs_move(
+    const float* __restrict__ xin, float* __restrict__ xout, const float* __restrict__ fcur, float* __restrict__ hist,
+    const float* __restrict__ part, float* __restrict__ pout, const LbfgsState* __restrict__ sin, LbfgsState* __restrict__ sout,
+    const DevModel m, const DevStep p, const DevFire fp, const int mem0) {
+    constexpr int Q = kLbfgsQ, M = kLbfgsMaxPairs;
+    __shared__ double sums[Q];
+    __shared__ LbfgsState st;
+    __shared__ float coef[1 + 2 * M];            // gamma, then a_j (of s_j), b_j (of y_j) by slot
+    __shared__ int shi[2];                       // slot mask of the pairs in the direction, slot of the move's s
+    __shared__ float dd[kLbfgsMoveRows];
+    const int rep = m.rep_base + blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const bool first = p.kind == 9;
+    // 1. replica sums of the tile partials in fp64: lane l takes tiles l, l + 64, ... in order, then a butterfly (the same order in every
+    //    workgroup, whatever the replica group)
+    const float* pr = part + (size_t)rep * m.ntiles * Q;
+    for (int k = wave; k < Q; k += kLbfgsMoveRows / 64) {
+        double a = 0.0;
+        for (int t = lane; t < m.ntiles; t += 64) a += (double)pr[(size_t)t * Q + k];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o);
+        if (lane == 0) sums[k] = a;
+    }
+    if (!first) {
+        const double* src = reinterpret_cast<const double*>(sin + rep);
+        double* dst = reinterpret_cast<double*>(&st);
+        for (int k = tid; k < (int)(sizeof(LbfgsState) / sizeof(double)); k += kLbfgsMoveRows) dst[k] = src[k];
+    }
+    __syncthreads();
+    // 2. the compact form, serially (a few hundred fp64 operations)
+    if (tid == 0) {
+        if (first) {
+            st.cnt = 0; st.mem = mem0; st.head = mem0 - 1; st.resets = 0;
+            st.gamma = (double)(fp.dt_start * fp.dt_start * m.acc);       // kind 6's first step length
+        } else {
+            st.mem = min(max(st.mem, 1), M);
+            st.head = min(max(st.head, 0), st.mem - 1);
+            st.cnt = min(max(st.cnt, 0), st.mem);
+            const int mem = st.mem;
+            const int nx = st.head + 1 == mem ? 0 : st.head + 1;
+            const double sy = sums[4 * nx + 2], yy = sums[4 * nx + 3], ss = sums[Q - 4];
+            if (sy > 1e-12 * sqrt(ss * yy)) {
+                st.head = nx;
+                st.cnt = min(st.cnt + 1, mem);
+                for (int i = 0; i < st.cnt; ++i) {
+                    int sl = nx - i; if (sl < 0) sl += mem;
+                    st.SY[sl][nx] = sums[4 * sl + 2];
+                    st.YY[sl][nx] = sums[4 * sl + 3];
+                    st.YY[nx][sl] = sums[4 * sl + 3];
+                }
+                st.gamma = sy / yy;
+            } else {
+                st.cnt = 0;
+                st.resets += 1;
+                st.gamma *= 2.0;
+            }
+            st.gamma = fmin(fmax(st.gamma, 1e-7), 1e2);
+        }
+        const int mem = st.mem, cnt = st.cnt;
+        const double g = st.gamma, ff = sums[Q - 3];
+        int sl[M];
+        double ps[M], py[M], u[M], w[M], top[M];
+        for (int i = 0; i < cnt; ++i) {                  // age order: i = 0 the oldest pair
+            int k = st.head - (cnt - 1) + i; if (k < 0) k += mem;
+            sl[i] = k;
+            ps[i] = -sums[4 * k];                        // S'g, Y'g with g = -F
+            py[i] = -sums[4 * k + 1];
+        }
+        for (int i = cnt - 1; i >= 0; --i) {             // R u = S'g, R = upper triangle of S'Y
+            double a = ps[i];
+            for (int j = i + 1; j < cnt; ++j) a -= st.SY[sl[i]][sl[j]] * u[j];
+            u[i] = a / st.SY[sl[i]][sl[i]];
+        }
+        for (int i = 0; i < cnt; ++i) {                  // w = (D + gamma Y'Y) u - gamma Y'g
+            double a = st.SY[sl[i]][sl[i]] * u[i];
+            for (int j = 0; j < cnt; ++j) a += g * st.YY[sl[i]][sl[j]] * u[j];
+            w[i] = a - g * py[i];
+        }
+        for (int i = 0; i < cnt; ++i) {                  // R' top = w
+            double a = w[i];
+            for (int j = 0; j < i; ++j) a -= st.SY[sl[j]][sl[i]] * top[j];
+            top[i] = a / st.SY[sl[i]][sl[i]];
+        }
+        // d = -H g = gamma F - sum top_i s_i + gamma sum u_i y_i;  F.d > 0 or the memory goes
+        double fd = g * ff;
+        for (int i = 0; i < cnt; ++i) fd += top[i] * ps[i] - g * u[i] * py[i];
+        int mask = 0;
+        for (int j = 0; j < 2 * M; ++j) coef[1 + j] = 0.0f;
+        if (fd > 0.0) {
+            for (int i = 0; i < cnt; ++i) { coef[1 + sl[i]] = (float)(-top[i]); coef[1 + M + sl[i]] = (float)(g * u[i]); mask |= 1 << sl[i]; }
+        } else {
+            st.cnt = 0;
+            st.resets += 1;
+        }
+        coef[0] = (float)g;
+        shi[0] = mask;
+        shi[1] = st.head + 1 == mem ? 0 : st.head + 1;   // where this move's s goes: the slot the next evaluation completes
+    }
+    __syncthreads();
+    // 3. the rows of this workgroup
+    const int i = blockIdx.x * kLbfgsMoveRows + tid;
+    const int npad = m.npad;
+    const size_t roff = (size_t)rep * 3 * npad;
+    float d2 = 0.0f;
+    if (i < m.n) {
+        const size_t ix = roff + i, iy = ix + npad, iz = iy + npad;
+        const float c = coef[0];
+        float dx = c * fcur[ix], dy = c * fcur[iy], dz = c * fcur[iz];
+        float* hs = hist + (size_t)rep * lbfgs_hist_floats(npad) + i;
+        float* hy = hs + (size_t)3 * M * npad;
+        const int mask = shi[0];
+#pragma unroll
+        for (int j = 0; j < M; ++j) {
+            if (!(mask & (1 << j))) continue;
+            const float a = coef[1 + j], b = coef[1 + M + j];
+            const float* s = hs + (size_t)3 * j * npad;
+            const float* y = hy + (size_t)3 * j * npad;
+            dx = fmaf(a, s[0], fmaf(b, y[0], dx));
+            dy = fmaf(a, s[npad], fmaf(b, y[npad], dy));
+            dz = fmaf(a, s[2 * npad], fmaf(b, y[2 * npad], dz));
+        }
+        const float ms2 = fp.max_step * fp.max_step;
+        const float l2 = fmaf(dx, dx, fmaf(dy, dy, dz * dz));
+        const float scl = l2 > ms2 ? fp.max_step * __builtin_amdgcn_rsqf(l2) : 1.0f;
+        dx *= scl; dy *= scl; dz *= scl;
+        xout[ix] = xin[ix] + dx; xout[iy] = xin[iy] + dy; xout[iz] = xin[iz] + dz;
+        float* sn = hs + (size_t)3 * shi[1] * npad;
+        sn[0] = dx; sn[npad] = dy; sn[2 * npad] = dz;
+        d2 = fmaf(dx, dx, fmaf(dy, dy, dz * dz));
+    }
+    dd[tid] = d2;
+    __syncthreads();
+    // 4. P[parity^1] of this workgroup's tiles: (move.move, F.F of the evaluation, 0, 0) — the exit test reads .y, the finiteness test all
+    constexpr int WT = kLbfgsMoveRows / kTileRows;
+    const int t = blockIdx.x * WT + tid;
+    if (tid < WT && t < m.ntiles)
+        reinterpret_cast<float4*>(pout)[(size_t)rep * m.ntiles + t] = make_float4(row_sum8(dd + kTileRows * tid, 1), pr[(size_t)t * Q + Q - 3], 0.0f, 0.0f);
+    // 5. the replica's state: one workgroup writes it
+    if (blockIdx.x == 0) {
+        const double* src = reinterpret_cast<const double*>(&st);
+        double* dst = reinterpret_cast<double*>(sout + rep);
+        for (int k = tid; k < (int)(sizeof(LbfgsState) / sizeof(double)); k += kLbfgsMoveRows) dst[k] = src[k];
+    }
+}
+
+static size_t lbfgs_eval_lds_bytes(const DevModel& m, int tile_rows) { return sizeof(float) * ((size_t)3 * m.npad + (size_t)kLbfgsQ * tile_rows); }
+
+template <int POT, bool GEN, int RPW>
+static hipError_t launch_lbfgs_eval_r(const DevModel& m0, const DevStep& p, const DevBuffers& b, const LbfgsBuffers& lb, int par, int mem,
+                                      bool wide, hipStream_t s) {
+    const int q = par ^ 1;
+    DevModel m = m0;
+    m.tgs2 = (POT == 4 && !GEN && RPW == 2 && m.wl == 4 && m.nleft == 0) ? b.tgs2 : nullptr;      // (the kernels that read it)
+    if constexpr (POT == 4 && !GEN && RPW == 2) {
+        if (wide && m.wl == 4 && m.nleft == 0 && m.tgs2) {      // launch_step's wide form: 16 rows a workgroup, four a wave
+            constexpr int TR = 2 * kTileRows;
+            const int nwg = (m.ntiles + 1) / 2;
+            hipLaunchKernelGGL((k_lbfgs_eval<4, false, 4, false, TR, true>), dim3(8, m.nrep_g, (nwg + 7) / 8), dim3(64 * TR / 4),
+                               lbfgs_eval_lds_bytes(m, TR), s, b.X[par], b.tgt, b.V[par], b.V[q], lb.hist, lb.part, lb.S[par], m, p, mem);
+            return hipGetLastError();
+        }
+    }
+    if (m.wl == 4 && m.nleft == 0)
+        hipLaunchKernelGGL((k_lbfgs_eval<POT, GEN, RPW, false>), grid_blocks(m), dim3(64 * kTileRows / RPW), lbfgs_eval_lds_bytes(m, kTileRows), s,
+                           b.X[par], b.tgt, b.V[par], b.V[q], lb.hist, lb.part, lb.S[par], m, p, mem);
+    else
+        hipLaunchKernelGGL((k_lbfgs_eval<POT, GEN, RPW, true>), grid_blocks(m), dim3(64 * kTileRows / RPW), lbfgs_eval_lds_bytes(m, kTileRows), s,
+                           b.X[par], b.tgt, b.V[par], b.V[q], lb.hist, lb.part, lb.S[par], m, p, mem);
+    return hipGetLastError();
+}
+template <int POT, bool GEN>
+static hipError_t launch_lbfgs_eval_t(const DevModel& m, const DevStep& p, const DevBuffers& b, const LbfgsBuffers& lb, int par, int mem,
+                                      bool wide, hipStream_t s) {
+    switch (m.rpw) {
+        case 1: return launch_lbfgs_eval_r<POT, GEN, 1>(m, p, b, lb, par, mem, wide, s);
+        case 2: return launch_lbfgs_eval_r<POT, GEN, 2>(m, p, b, lb, par, mem, wide, s);
+        default: return launch_lbfgs_eval_r<POT, GEN, 4>(m, p, b, lb, par, mem, wide, s);
+    }
+}
+
+hipError_t launch_lbfgs_eval(const DevModel& m, const DevStep& p, const DevBuffers& b, const LbfgsBuffers& lb, int parity, int mem,
+                             bool general_tail, bool wide, hipStream_t s) {
+    if (mem < 1 || mem > kLbfgsMaxPairs) return hipErrorInvalidValue;
+    if (!general_tail) {
+        switch (m.noe_pot) {
+            case 0: return launch_lbfgs_eval_t<0, false>(m, p, b, lb, parity, mem, wide, s);
+            case 1: return launch_lbfgs_eval_t<1, false>(m, p, b, lb, parity, mem, wide, s);
+            case 3: return launch_lbfgs_eval_t<3, false>(m, p, b, lb, parity, mem, wide, s);
+            case 4: return launch_lbfgs_eval_t<4, false>(m, p, b, lb, parity, mem, wide, s);
+            default: return launch_lbfgs_eval_t<2, false>(m, p, b, lb, parity, mem, wide, s);
+        }
+    }
+    switch (m.noe_pot) {
+        case 0: return launch_lbfgs_eval_t<0, true>(m, p, b, lb, parity, mem, wide, s);
+        case 1: return launch_lbfgs_eval_t<1, true>(m, p, b, lb, parity, mem, wide, s);
+        case 3: return launch_lbfgs_eval_t<3, true>(m, p, b, lb, parity, mem, wide, s);
+        case 4: return launch_lbfgs_eval_t<4, true>(m, p, b, lb, parity, mem, wide, s);
+        default: return launch_lbfgs_eval_t<2, true>(m, p, b, lb, parity, mem, wide, s);
+    }
+}
+
+hipError_t launch_lbfgs_move(const DevModel& m, const DevStep& p, const DevFire& fp, const DevBuffers& b, const LbfgsBuffers& lb, int parity,
+                             int mem, hipStream_t s) {
+    if (mem < 1 || mem > kLbfgsMaxPairs) return hipErrorInvalidValue;
+    const int q = parity ^ 1;
+    hipLaunchKernelGGL(k_lbfgs_move, dim3((m.n + kLbfgsMoveRows - 1) / kLbfgsMoveRows, m.nrep_g), dim3(kLbfgsMoveRows), 0, s,
+                       b.X[parity], b.X[q], b.V[q], lb.hist, lb.part, b.P[q], lb.S[parity], lb.S[q], m, p, fp, mem);
+    return hipGetLastError();
+}
+
+}  // namespace c3d

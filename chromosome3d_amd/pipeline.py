@@ -175,11 +175,11 @@ def model_similarity(xa, xb):
 
 
 def build_models(solver, model_count=MODELCOUNT, seed=MD_SEED, first_replica=0, model=None, stages=None, fire=None,
-                 gtol=1e-2, check_every=250):
+                 gtol=1e-2, check_every=250, final_kind=5):
     """The replacement of `cns_solve < dgsa.inp` (:254-289): runs the whole annealing schedule
     for model_count replicas on the GPU and returns (xyz [M,N,3], energies [M,3])."""
     solver.set_model(model if model is not None else default_model())
-    solver.set_schedule(stages if stages is not None else default_schedule(), fire or default_fire(), gtol, check_every)
+    solver.set_schedule(stages if stages is not None else default_schedule(final_kind=final_kind), fire or default_fire(), gtol, check_every)
     solver.init_replicas(model_count, seed, first_replica)
     solver.run()
     return solver.coords(), solver.energies()

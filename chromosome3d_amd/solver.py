@@ -24,11 +24,15 @@ def default_fire(**kw):
     return f
 
 
-def default_schedule(min_steps=3000):
+def default_schedule(min_steps=3000, final_kind=5):
+    """The library's default schedule; final_kind 8 makes its final stage an L-BFGS stage (then FIRE) instead of kind 5."""
+    if final_kind not in (2, 5, 8):
+        raise ValueError("final_kind is 2 (FIRE), 5 (two-point step sizes) or 8 (L-BFGS)")
     L = _l.load()
     n = L.c3d_default_schedule(None, 0, min_steps)
     arr = (_l.Stage * n)()
     L.c3d_default_schedule(arr, n, min_steps)
+    arr[n - 1].kind = final_kind
     return arr
 
 

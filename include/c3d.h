@@ -74,7 +74,14 @@ typedef struct {
                             over it, taken one evaluation late (the replica sums of a step reach the next one) — for the first
                             `final_minimiser_steps` (1000) steps, then FIRE for what is left of nsteps: half the evaluations FIRE needs
                             to the same exit test, the same minima; the default schedule's final stage since round 5
-                            (option final_minimiser = 0: a stage of kind 5 is a FIRE stage)                                        */
+                            (option final_minimiser = 0: a stage of kind 5 is a FIRE stage)
+                          8 L-BFGS minimise (opt-in; the reference's method, deck :1790-1803): m = lbfgs_memory pairs (5), the compact
+                            form from the projections of the current gradient, a fixed unit step, no energy, no line search, each bead's
+                            move capped at fire.max_step, a pair kept only if its curvature is positive, the memory dropped when the
+                            direction is not downhill — for the first `final_minimiser_steps` steps, then FIRE from a fresh state for what
+                            is left of nsteps (option final_minimiser does not apply to it).  Per-step path only: two launches a step
+                            (k_lbfgs_eval, k_lbfgs_move), whatever `resident` says; no fp64 form (precision 64 refuses it); symmetric
+                            tiles do not apply to its steps.  About half the force evaluations of kind 5 to the same exit test      */
     int32_t nsteps;
     float dt;          /* ps (MD)                                                        */
     float w_all;       /* `weights * w`                                                  */
@@ -143,8 +150,10 @@ int c3d_set_schedule(c3d_ctx* ctx, const c3d_stage* stages, int n_stages, const 
  *                   mark or with a time-out is re-run on the per-step path)
  *   precision       32 (default) or 64: the fp64 reference kernels (c3d_f64.hip); call before c3d_init_replicas.  The fp64 step stages a
  *                   replica's coordinates in LDS: at most 2560 beads (c3d_init_replicas returns C3D_ERR_INVALID beyond).  The fp32 kernels
- *                   stage 3 * npad floats of a replica in LDS: at most 5120 beads (c3d_set_if_matrix / c3d_set_restraints refuse more)
- *   symmetric       1: symmetric-tile kernels for large N (c3d_sym.hip; opt-in); call before c3d_init_replicas
+ *                   stage 3 * npad floats of a replica in LDS: at most 5120 beads (c3d_set_if_matrix / c3d_set_restraints refuse more).
+ *                   64 and a schedule with a stage of kind 8 exclude each other: whichever call comes second returns C3D_ERR_INVALID
+ *   symmetric       1: symmetric-tile kernels for large N (c3d_sym.hip; opt-in); call before c3d_init_replicas.  Not for the L-BFGS steps of
+ *                   a kind-8 stage: they run their own kernels
  *   eval_rows_per_wave  4 (default) / 2 / -2: form of the forces hook (c3d_eval_forces) — four rows per wave with the scalar pair term; 2 = two
  *                   rows per wave, the step kernels' code (shipped potential: the packed pair term); -2 = two rows per wave, scalar pair
  *                   term.  2 and -2 return the same bits (a -m gpu test); test knob
@@ -163,7 +172,8 @@ int c3d_set_schedule(c3d_ctx* ctx, const c3d_stage* stages, int n_stages, const 
  *                   (measurement knob; stat "rank_prefetch_hits")
  *   final_minimiser 1 (default) / 0: what a stage of kind 5 (the default schedule's final stage) runs — two-point step sizes handing over to
  *                   FIRE after final_minimiser_steps, or FIRE throughout as in rounds 1-4.  Stages of kind 2 are FIRE whatever this says
- *   final_minimiser_steps   1000 (default): two-point steps of a kind-5 stage before FIRE takes it over (>= 2)
+ *   final_minimiser_steps   1000 (default): two-point steps of a kind-5 stage, L-BFGS steps of a kind-8 stage, before FIRE takes it over (>= 2)
+ *   lbfgs_memory    1..8 (default 5): pairs (s, y) a stage of kind 8 keeps; takes effect at the next first step of such a stage
  *   start           0 (default) random coil, 1 extended strand (chromosome3D.pl:2413-2416)
  *   use_graph       != 0: per-step path replays hipGraphs (default 1)
  *   replica_groups  1..4 stream groups of the per-step path (default 2);  graph_chunk, rows_per_wave,
@@ -200,7 +210,8 @@ int c3d_set_coords(c3d_ctx* ctx, const float* xyz);
 int c3d_get_coords(c3d_ctx* ctx, float* xyz);
 /* (after a range that ended inside the two-point part of a final stage — kind 5, its first final_minimiser_steps steps — the velocity
  *  slot holds the previous evaluation's FORCE per bead, kcal/mol/A: that minimiser has no velocities and keeps its history there;
- *  after MD and FIRE steps it is the velocity in A/ps) */
+ *  after MD and FIRE steps it is the velocity in A/ps; the same holds inside the L-BFGS part of a stage of kind 8: the slot holds the force of
+ *  the last evaluation) */
 int c3d_get_velocities(c3d_ctx* ctx, float* v);
 
 /* --- solve -------------------------------------------------------------------------- */
@@ -224,14 +235,16 @@ int c3d_last_timing(const c3d_ctx* ctx, double* ms_total, long* steps, long* lau
  * "k1_recomputed" (elements of the last c3d_set_if_matrix that sat within 1e-10 of a "%.1f" rounding tie and were redone
  * on the host in the reference's operation order), "k1_patched" (how many of those changed, since c3d_create),
  * "rms_force" (largest RMS force component over the replicas at the last minimiser step: the quantity c3d_run holds
- * against gtol, the stand-in for L-BFGS's convergence test of chromosome3D.pl:1800-1803). */
+ * against gtol, the stand-in for L-BFGS's convergence test of chromosome3D.pl:1800-1803), "lbfgs_steps" (L-BFGS steps run, kind 8),
+ * "lbfgs_resets" (memory drops of the last kind-8 stage since its first step, summed over the replicas: read from the device). */
 int c3d_get_stat(const c3d_ctx* ctx, const char* key, double* value);
 /* Test hook, no reference counterpart: the multi-step kernel's hand-off trusts a 16-byte unit once its tag word matches — i.e. that a
  * 16-byte aligned store is never observed half-written by a 16-byte load on gfx950.  This runs that exact store / load pair (one producer
  * workgroup, a consumer workgroup on every other CU, the context's stream) for `iterations` rewrites of 1024 units and returns the number
  * of unit reads, of TORN units (must be 0) and of reads that saw a new value. */
 int c3d_debug_tear16(c3d_ctx* ctx, int iterations, unsigned long long* unit_reads, unsigned long long* torn, unsigned long long* fresh);
-/* Name of the step kernel the last c3d_run / c3d_run_steps ran on, as a profiler prints it (thread-local string). */
+/* Name of the step kernel the last c3d_run / c3d_run_steps ran on, as a profiler prints it (thread-local string); after a range of L-BFGS
+ * steps the force pass, k_lbfgs_eval<...>. */
 const char* c3d_step_kernel_name(const c3d_ctx* ctx);
 
 /* One evaluation through the production pair kernel at the replicas' current coordinates:
