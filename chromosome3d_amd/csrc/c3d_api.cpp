@@ -53,6 +53,15 @@ struct Op {
     bool counted;   // a force evaluation = one SA step
 };
 
+// What the last op of the last range ran: the kernel family and its form, as chosen for the launch (c3d_step_kernel_name formats it)
+struct KernelRecord {
+    enum Family { NONE, STEP, LBFGS_EVAL, PAIRS_SYM, STEP64, CLUSTER } family = NONE;
+    c3d::StepForm step{};                        // STEP, LBFGS_EVAL
+    c3d::Form64 f64{};                           // STEP64
+    int pot = 0, rpw = 0, nb = 0, wl = 0;        // PAIRS_SYM (pot), CLUSTER
+    bool rs1 = false, late = false, tp = false;  // PAIRS_SYM (rs1), CLUSTER
+};
+
 // ---- Philox4x32-10 (Salmon et al. SC'11): initial coordinates / velocities ------------------
 inline void philox4x32(const uint32_t ctr_in[4], const uint32_t key_in[2], uint32_t out[4]) {
     uint32_t c[4] = {ctr_in[0], ctr_in[1], ctr_in[2], ctr_in[3]};
@@ -206,11 +215,8 @@ struct c3d_ctx {
     c3d::LbfgsBuffers lb{};                // the L-BFGS history, tile sums and state (ensure_lbfgs), freed with the replica buffers
     long lbfgs_steps = 0;                  // L-BFGS steps run (stat "lbfgs_steps")
     int lbfgs_parity = -1;                 // parity the last L-BFGS step left its state in (stat "lbfgs_resets")
-    bool last_lbfgs = false;               // the last per-step range ran L-BFGS steps (c3d_step_kernel_name)
-    bool last_two_point = false;           // the last multi-step launch was k_cluster_tp (its range held two-point minimiser steps)
     int last_path = 0;                     // 0 per-step, 2 k_cluster, 3 fp64 reference (what the last run_ops used)
-    bool last_general = false;             // the last per-step launch took the general-form kernel (general tails, or an op without restraint weight)
-    bool last_fold64 = false;              // the last fp64 step launch took k64_step<4, false, true> (shipped potential, restraint weight != 0)
+    KernelRecord ran;                      // the kernel the last op of the last range ran (c3d_step_kernel_name)
 
     double last_ms = 0;
     long last_steps = 0, last_launches = 0;
@@ -309,13 +315,6 @@ c3d::DevModel dev_model(const c3d_ctx* c) {
     m.inv_n = 1.0f / (float)c->n;
     return m;
 }
-// default tails: the force stays at its value at the switch distance (slope 2 rs above, 2 mrs below for noe_pot 3)
-bool general_tail(const c3d::DevModel& m) {
-    if (!(m.tail_b == 0.0f && m.tail_c == 2.0f * m.rs)) return true;
-    return m.noe_pot == 3 && !(m.mtail_b == 0.0f && m.mtail_c == 2.0f * m.mrs);      // (device potential 4 is a fast form by construction)
-}
-// the kernels of the general form also serve a step whose restraint weight is zero (the clamp form divides by it)
-bool general_step(const c3d::DevModel& m, const c3d::DevStep& p) { return general_tail(m) || p.w_rs == 0.0f; }
 c3d::DevFire dev_fire(const c3d_ctx* c) {
     c3d::DevFire f;
     f.dt_start = c->fire.dt_start; f.dt_max = c->fire.dt_max; f.f_inc = c->fire.f_inc; f.f_dec = c->fire.f_dec;
@@ -623,11 +622,6 @@ int build_targets64(c3d_ctx* c) {
 
 // Per-step kernel beyond the cluster kernel's reach (no narrow column block: every n > 1024), device potential 4: the resident per-pair
 // constants of row pairs (DevModel::tgs2), built on first use after the targets or the model changed
-// the per-step kernel's wide form: the shipped potential's clamp forms on a problem beyond the multi-step kernel's reach whose columns fill
-// whole blocks (every n > 1024 the library pads that way), at the default two rows per wave of the narrow form it replaces
-bool wide_step(const c3d_ctx* c, const c3d::DevModel& m, bool general) {
-    return c->wide_tiles && c->pair_targets && !general && m.noe_pot == 4 && m.wl == 4 && m.nleft == 0 && c->npad > 1024 && c->rpw == 2;
-}
 
 // The L-BFGS history (2 x 8 pairs x 3 x npad floats a replica: sized for the largest memory, so that lbfgs_memory never reallocates), the
 // tile sums and the state, zeroed; allocated outside any stream capture (run_ops_segment), freed with the replica buffers
@@ -645,12 +639,31 @@ int ensure_lbfgs(c3d_ctx* c) {
 }
 
 int ensure_pair_targets(c3d_ctx* c, const c3d::DevModel& m) {
-    if (c->buf.tgs2 || !c->pair_targets || m.noe_pot != 4 || m.wl != 4 || m.nleft != 0 || c->npad <= 1024 || c->rpw != 2 || !c->buf.tgt) return C3D_OK;
+    if (c->buf.tgs2 || !c->pair_targets || !c3d::pair_targets_fit(m) || c->npad <= 1024 || !c->buf.tgt) return C3D_OK;
     HIP_TRY(hipMalloc(&c->buf.tgs2, sizeof(float) * c3d::pair_targets_floats(c->n, c->npad)));
     hipError_t e = c3d::launch_pair_targets(m, c->buf.tgt, c->buf.tgs2, c->stream);
     if (e != hipSuccess) return fail(C3D_ERR_HIP, std::string("pair targets: ") + hipGetErrorString(e));
     HIP_TRY(hipStreamSynchronize(c->stream));          // the step launches run on the group streams
     return C3D_OK;
+}
+// The kernel an op runs on the per-step path and its form: launch_op launches what this says, run_ops_segment records it for the range's
+// last op (a graph replay does not pass through launch_op)
+KernelRecord op_kernel(const c3d_ctx* c, const c3d::DevModel& m, const Op& op) {
+    KernelRecord k;
+    if (c->precision == 64) {              // launch_step64 makes the same choice from the same doubles
+        double mh[15];
+        model_host64(c, mh);
+        k.family = KernelRecord::STEP64;
+        k.f64 = c3d::form64(m.noe_pot, mh, c->stages[op.stage].w_all);
+    } else if (!is_lbfgs(op.p.kind) && use_sym(c)) {      // (symmetric tiles do not apply to L-BFGS steps)
+        k.family = KernelRecord::PAIRS_SYM;
+        k.pot = c3d::device_pot(m.noe_pot);
+        k.rs1 = c3d::sym_rs1(m);
+    } else {
+        k.family = is_lbfgs(op.p.kind) ? KernelRecord::LBFGS_EVAL : KernelRecord::STEP;
+        k.step = c3d::step_form(m, op.p, c->wide_tiles, c->pair_targets, c->buf.tgs2 != nullptr);
+    }
+    return k;
 }
 // one SA-step launch for replica group g, reading parity `par`
 int launch_op(c3d_ctx* c, const Op& op, int g, int par) {
@@ -666,15 +679,16 @@ int launch_op(c3d_ctx* c, const Op& op, int g, int par) {
         if (e64 != hipSuccess) return fail(C3D_ERR_HIP, std::string("fp64 step launch: ") + hipGetErrorString(e64));
         return C3D_OK;
     }
-    c->last_general = general_step(m, op.p);
-    if (is_lbfgs(op.p.kind)) {             // two launches: forces + tile sums, then sums + direction + move (symmetric tiles do not apply)
-        hipError_t e = c3d::launch_lbfgs_eval(m, op.p, c->buf, c->lb, par, c->lbfgs_mem, c->last_general, wide_step(c, m, c->last_general), c->gstream[g]);
+    const KernelRecord k = op_kernel(c, m, op);
+    if (k.family == KernelRecord::LBFGS_EVAL) {       // two launches: forces + tile sums, then sums + direction + move
+        hipError_t e = c3d::launch_lbfgs_eval(m, op.p, c->buf, c->lb, par, c->lbfgs_mem, k.step, c->gstream[g]);
         if (e == hipSuccess) e = c3d::launch_lbfgs_move(m, op.p, dev_fire(c), c->buf, c->lb, par, c->lbfgs_mem, c->gstream[g]);
         if (e != hipSuccess) return fail(C3D_ERR_HIP, std::string("L-BFGS step launch: ") + hipGetErrorString(e));
         return C3D_OK;
     }
-    hipError_t e = use_sym(c) ? c3d::launch_step_sym(m, op.p, dev_fire(c), c->buf, par, c->d_sym_tiles, c->d_sym_scratch, c->gstream[g])
-                              : c3d::launch_step(m, op.p, dev_fire(c), c->buf, par, c->last_general, wide_step(c, m, c->last_general), c->gstream[g]);
+    hipError_t e = k.family == KernelRecord::PAIRS_SYM
+                       ? c3d::launch_step_sym(m, op.p, dev_fire(c), c->buf, par, c->d_sym_tiles, c->d_sym_scratch, c->gstream[g])
+                       : c3d::launch_step(m, op.p, dev_fire(c), c->buf, par, k.step, c->gstream[g]);
     if (e != hipSuccess) return fail(C3D_ERR_HIP, std::string("step launch: ") + hipGetErrorString(e));
     return C3D_OK;
 }
@@ -704,7 +718,7 @@ int plan_cluster(c3d_ctx* c) {
 // Can the ops run as one k_cluster launch (a replica on a few 1024-thread workgroups of one XCD)?
 bool cluster_ok(c3d_ctx* c) {
     if (!c->resident || !c->cluster || !c->cl_ok || !c->d_crec) return false;
-    return !general_tail(dev_model(c));        // (ops without restraint weight never get here: run_ops splits the range at them)
+    return !c3d::general_tail(dev_model(c));        // (ops without restraint weight never get here: run_ops splits the range at them)
 }
 
 // after a multi-step launch: did a workgroup give up (or was that injected)?  The launch reads parity p and writes
@@ -762,7 +776,6 @@ int run_cluster(c3d_ctx* c, size_t nops, bool* ran) {
     pl.xcd_base = c->xcd_base;
     pl.two_point = false;
     for (size_t k = 0; k < nops && !pl.two_point; ++k) pl.two_point = is_two_point(c->program[c->pc + k].p.kind);
-    c->last_two_point = pl.two_point;
     c->inject_misplaced = false;
     c->h_tmo[2] = 0;
     const auto h0 = std::chrono::steady_clock::now();
@@ -801,6 +814,10 @@ int run_cluster(c3d_ctx* c, size_t nops, bool* ran) {
     if (launch_was_abandoned(c, (seq << 20) | 1u)) { *ran = false; c->ev1_recorded = false; return C3D_OK; }
     *ran = true;
     c->last_path = 2;
+    KernelRecord& k = c->ran;
+    k = KernelRecord();
+    k.family = KernelRecord::CLUSTER;
+    k.pot = c3d::device_pot(m.noe_pot); k.rpw = pl.rpw; k.nb = m.npad / 256; k.wl = m.wl; k.late = pl.late_tiles != 0; k.tp = pl.two_point;
     account_ops(c, nops);
     return C3D_OK;
 }
@@ -861,7 +878,6 @@ int run_ops_segment(c3d_ctx* c, size_t nops, bool zero_w, bool lbfgs) {
     }
     if (lbfgs)
         if (int rc = ensure_lbfgs(c)) return rc;
-    c->last_lbfgs = lbfgs;
     const int G = active_groups(c);
     if (int rc = ensure_group_streams(c, G)) return rc;
     // every replica group advances on its own stream (fork from / join into stream 0 around the range): while one
@@ -935,11 +951,8 @@ int run_ops_segment(c3d_ctx* c, size_t nops, bool zero_w, bool lbfgs) {
         hipError_t e = c3d::launch_export64(dev_model(c), c->b64, c->parity, c->buf.X[c->parity], c->buf.V[c->parity], c->buf.P[c->parity], c->stream);
         if (e != hipSuccess) return fail(C3D_ERR_HIP, std::string("fp64 export: ") + hipGetErrorString(e));
         c->last_path = 3;
-        // launch_step64's choice for the range's last op (a graph replay does not pass through launch_op): the FOLD form for the shipped
-        // potential's fast form wherever the restraint weight is not zero
-        const c3d::DevModel m = dev_model(c);
-        c->last_fold64 = c->pc > 0 && m.noe_pot == 4 && !general_tail(m) && c->stages[c->program[c->pc - 1].stage].w_all != 0.0f;
     }
+    c->ran = op_kernel(c, dev_model(c), c->program[c->pc - 1]);
     return C3D_OK;
 }
 
@@ -1421,7 +1434,7 @@ extern "C" int c3d_init_replicas(c3d_ctx* c, int nrep, uint64_t seed, uint32_t f
             c3d::DevModel m = dev_model(c);
             m.nrep = nrep; m.nrep_g = nrep; m.rep_base = 0;
             // symmetric-tile kernels (large N): tile list and the partial-force slabs
-            if (!general_tail(m) && c->sym > 0) {
+            if (!c3d::general_tail(m) && c->sym > 0) {
                 int Q, G, od, dg;
                 c3d::sym_geometry(m, &Q, &G, &od, &dg);
                 std::vector<int2> tl((size_t)od + dg);
@@ -1742,22 +1755,27 @@ extern "C" int c3d_get_stat(const c3d_ctx* c, const char* key, double* value) {
     return C3D_OK;
 }
 
-// name of the kernel the last range ran on, as rocprofv3 prints it (without the argument list)
+// name of the kernel the last op of the last range ran on, as rocprofv3 prints it (without the argument list): the record its launch was made from
 extern "C" const char* c3d_step_kernel_name(const c3d_ctx* c) {
     static thread_local char buf[96];
     if (!c) return "";
-    const c3d::DevModel m = dev_model(c);
-    const char* gen = (general_tail(m) || c->last_general) ? "true" : "false";     // of the last op launched on the per-step path
-    const char* rs1 = (!general_tail(m) && m.rs == 1.0f) ? "true" : "false";
-    if (c->last_path == 2) snprintf(buf, sizeof(buf), "c3d::k_cluster%s<%d, %d, %d, %d, %s>", c->last_two_point ? "_tp" : "", m.noe_pot, c->cl_plan.rpw, m.npad / 256, m.wl, c->cl_plan.late_tiles ? "true" : "false");
-    else if (c->last_lbfgs && c->precision != 64) {     // the force pass of an L-BFGS step (k_lbfgs_move follows it)
-        if (wide_step(c, m, general_tail(m) || c->last_general)) snprintf(buf, sizeof(buf), "c3d::k_lbfgs_eval<4, false, 4, false, 16, true>");
-        else snprintf(buf, sizeof(buf), "c3d::k_lbfgs_eval<%d, %s, %d, %s, 8, false>", m.noe_pot, gen, m.rpw, (m.wl == 4 && m.nleft == 0) ? "false" : "true");
+    const KernelRecord& k = c->ran;
+    auto tf = [](bool b) { return b ? "true" : "false"; };
+    switch (k.family) {
+        case KernelRecord::CLUSTER:
+            snprintf(buf, sizeof(buf), "c3d::k_cluster%s<%d, %d, %d, %d, %s>", k.tp ? "_tp" : "", k.pot, k.rpw, k.nb, k.wl, tf(k.late));
+            break;
+        case KernelRecord::STEP64: snprintf(buf, sizeof(buf), "c3d::k64_step<%d, %s, %s>", k.f64.pot, tf(k.f64.gen), tf(k.f64.fold)); break;
+        case KernelRecord::PAIRS_SYM: snprintf(buf, sizeof(buf), "c3d::k_pairs_sym<%d, %s, false>", k.pot, tf(k.rs1)); break;
+        case KernelRecord::STEP:
+        case KernelRecord::LBFGS_EVAL: {      // (after an L-BFGS step: its force pass, k_lbfgs_move follows it)
+            const char* kernel = k.family == KernelRecord::STEP ? "k_step" : "k_lbfgs_eval";
+            if (k.step.wide) snprintf(buf, sizeof(buf), "c3d::%s<4, false, 4, false, 16, true>", kernel);
+            else snprintf(buf, sizeof(buf), "c3d::%s<%d, %s, %d, %s, 8, false>", kernel, k.step.pot, tf(k.step.gen), k.step.rpw, tf(k.step.nc));
+            break;
+        }
+        default: return "";
     }
-    else if (use_sym(c)) snprintf(buf, sizeof(buf), "c3d::k_pairs_sym<%d, %s, false>", m.noe_pot, rs1);
-    else if (c->precision == 64) snprintf(buf, sizeof(buf), "c3d::k64_step<%d, %s, %s>", m.noe_pot, general_tail(m) ? "true" : "false", c->last_fold64 ? "true" : "false");
-    else if (wide_step(c, m, general_tail(m) || c->last_general)) snprintf(buf, sizeof(buf), "c3d::k_step<4, false, 4, false, 16, true>");
-    else snprintf(buf, sizeof(buf), "c3d::k_step<%d, %s, %d, %s, 8, false>", m.noe_pot, gen, m.rpw, (m.wl == 4 && m.nleft == 0) ? "false" : "true");
     return buf;
 }
 
@@ -1767,7 +1785,7 @@ extern "C" int c3d_eval(c3d_ctx* c, float w_all, float w_vdw, float repel_s, flo
     const c3d::DevModel m = dev_model(c);
     const c3d::DevStep p = dev_step(c, 3, 0.0f, w_all, w_vdw, repel_s, 0.0f);
     if (F) {
-        hipError_t err = c3d::launch_eval_forces(m, p, c->buf, c->parity, c->d_feval, general_step(m, p), c->eval_rpw, c->stream);
+        hipError_t err = c3d::launch_eval_forces(m, p, c->buf, c->parity, c->d_feval, c3d::general_step(m, p), c->eval_rpw, c->stream);
         if (err != hipSuccess) return fail(C3D_ERR_HIP, std::string("eval launch: ") + hipGetErrorString(err));
         int rc = get_soa(c, c->d_feval, F);
         if (rc) return rc;

@@ -708,68 +708,49 @@ static hipError_t cluster_go(const DevModel& m, const DevFire& fp, const Cluster
 #undef C3D_CL_LAUNCH
     return hipGetLastError();
 }
+// The instantiations of a potential's multi-step kernel, written once: f(RPW, NB, WL, LATE) for every (RPW, NB) below at WL = 4 and — the
+// CNS soft-square only (cluster_plan refuses the others) — at the narrower last blocks WL = 3, 2, 1; LATE = true where cluster_late_ok.
+// cluster_geom launches from this list and cluster_prepare_unit gives every entry its LDS allowance.
+template <int POT, class F>
+static void for_each_cluster_form(F&& f) {
+    auto widths = [&](auto R, auto B) {
+        auto w = [&](auto W) {
+            f(R, B, W, bool_c<false>{});
+            if constexpr (cluster_late_ok(POT, R, B, W)) f(R, B, W, bool_c<true>{});
+        };
+        w(int_c<4>{});
+        if constexpr (POT >= 3) { w(int_c<3>{}); w(int_c<2>{}); w(int_c<1>{}); }
+    };
+    widths(int_c<1>{}, int_c<1>{}); widths(int_c<1>{}, int_c<2>{}); widths(int_c<1>{}, int_c<3>{}); widths(int_c<1>{}, int_c<4>{});
+    widths(int_c<2>{}, int_c<1>{}); widths(int_c<2>{}, int_c<2>{}); widths(int_c<2>{}, int_c<3>{}); widths(int_c<2>{}, int_c<4>{});
+    widths(int_c<3>{}, int_c<1>{}); widths(int_c<3>{}, int_c<2>{});
+    widths(int_c<4>{}, int_c<1>{}); widths(int_c<4>{}, int_c<2>{});
+}
 template <int POT>
 static hipError_t cluster_geom(const DevModel& m, const DevFire& fp, const ClusterPlan& pl, const AnnealIO& io, const float* tgt, void* rec,
                                const StepRun* runs, int run0, int skip0, int nsteps, unsigned tag_base, unsigned* timeout, unsigned* claim,
                                hipStream_t s) {
-#define C3D_GO(R, B, W)                                                                                                 \
-    do {                                                                                                                \
-        if constexpr (cluster_late_ok(POT, R, B, W)) {                                                                  \
-            if (pl.late_tiles) return cluster_go<POT, R, B, W, true>(m, fp, pl, io, tgt, rec, runs, run0, skip0, nsteps, tag_base, timeout, claim, s); \
-        }                                                                                                               \
-        if (pl.late_tiles) return hipErrorInvalidValue;                                                                 \
-        return cluster_go<POT, R, B, W, false>(m, fp, pl, io, tgt, rec, runs, run0, skip0, nsteps, tag_base, timeout, claim, s); \
-    } while (0)
-#define C3D_CL(R, B)                                                                                                    \
-    if (pl.rpw == R && m.npad == 256 * B) {                                                                             \
-        if (m.wl == 4) C3D_GO(R, B, 4);                                                                                 \
-        if constexpr (POT >= 3) {   /* narrower last blocks: the CNS soft-square only (cluster_plan refuses the others)    */      \
-            if (m.wl == 3) C3D_GO(R, B, 3);                                                                             \
-            if (m.wl == 2) C3D_GO(R, B, 2);                                                                             \
-            if (m.wl == 1) C3D_GO(R, B, 1);                                                                             \
-        }                                                                                                               \
-        return hipErrorInvalidValue;                                                                                    \
-    }
-    C3D_CL(1, 1); C3D_CL(1, 2); C3D_CL(1, 3); C3D_CL(1, 4);
-    C3D_CL(2, 1); C3D_CL(2, 2); C3D_CL(2, 3); C3D_CL(2, 4);
-    C3D_CL(3, 1); C3D_CL(3, 2);
-    C3D_CL(4, 1); C3D_CL(4, 2);
-#undef C3D_CL
-#undef C3D_GO
-    return hipErrorInvalidValue;
+    hipError_t e = hipErrorInvalidValue;      // (a geometry outside the list)
+    for_each_cluster_form<POT>([&](auto R, auto B, auto W, auto L) {
+        if (pl.rpw == R && m.npad == 256 * B && m.wl == W && (pl.late_tiles != 0) == L)
+            e = cluster_go<POT, R, B, W, L>(m, fp, pl, io, tgt, rec, runs, run0, skip0, nsteps, tag_base, timeout, claim, s);
+    });
+    return e;
 }
 
 // Loads the code object that holds this unit's kernels on the CURRENT device and allows every instantiation in it the dynamic LDS a
 // launch may ask for (more than the 64 KB a kernel gets by default; hipFuncSetAttribute is per function and device).  Called once per
 // (unit, device) by the loader of c3d_api.cpp while it holds its lock exclusively: after it, a launch from this unit changes no state of
-// the runtime.  Walks the table cluster_geom dispatches over.
+// the runtime.
 template <int POT, bool TP>
 static hipError_t cluster_prepare_unit() {
     hipError_t e = hipSuccess;
-#define C3D_PREP1(R, B, W, L)                                                                                            \
-    do {                                                                                                                 \
-        if (e == hipSuccess) {                                                                                           \
-            if constexpr (TP) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cluster_tp<POT, R, B, W, L>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-            else e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cluster<POT, R, B, W, L>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-        }                                                                                                                \
-    } while (0)
-#define C3D_PREP_W(R, B, W)                                                                                              \
-    do {                                                                                                                 \
-        C3D_PREP1(R, B, W, false);                                                                                       \
-        if constexpr (cluster_late_ok(POT, R, B, W)) C3D_PREP1(R, B, W, true);                                           \
-    } while (0)
-#define C3D_PREP(R, B)                                                                                                   \
-    do {                                                                                                                 \
-        C3D_PREP_W(R, B, 4);                                                                                             \
-        if constexpr (POT >= 3) { C3D_PREP_W(R, B, 3); C3D_PREP_W(R, B, 2); C3D_PREP_W(R, B, 1); }                      \
-    } while (0)
-    C3D_PREP(1, 1); C3D_PREP(1, 2); C3D_PREP(1, 3); C3D_PREP(1, 4);
-    C3D_PREP(2, 1); C3D_PREP(2, 2); C3D_PREP(2, 3); C3D_PREP(2, 4);
-    C3D_PREP(3, 1); C3D_PREP(3, 2);
-    C3D_PREP(4, 1); C3D_PREP(4, 2);
-#undef C3D_PREP
-#undef C3D_PREP_W
-#undef C3D_PREP1
+    for_each_cluster_form<POT>([&](auto R, auto B, auto W, auto L) {
+        const void* k;
+        if constexpr (TP) k = reinterpret_cast<const void*>(&k_cluster_tp<POT, R, B, W, L>);
+        else k = reinterpret_cast<const void*>(&k_cluster<POT, R, B, W, L>);
+        if (e == hipSuccess) e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    });
     return e;
 }
 
@@ -792,29 +773,29 @@ hipError_t C3D_CL_CAT(launch_cluster_pot, C3D_CLUSTER_POT)(const DevModel& m, co
 }
 hipError_t C3D_CL_CAT(preload_cluster_pot, C3D_CLUSTER_POT)() { return cluster_prepare_unit<C3D_CLUSTER_POT, false>(); }
 #else
+using ClusterLaunch = hipError_t(const DevModel& m, const DevFire& fp, const ClusterPlan& pl, const AnnealIO& io, const float* tgt, void* rec,
+                                 const StepRun* runs, int run0, int skip0, int nsteps, unsigned tag_base, unsigned* timeout, unsigned* claim,
+                                 hipStream_t s);
 #if defined(C3D_CLUSTER_SPLIT)
-#define C3D_CL_DECL(P) hipError_t launch_cluster_pot##P(const DevModel& m, const DevFire& fp, const ClusterPlan& pl, const AnnealIO& io, const float* tgt, void* rec, const StepRun* runs, int run0, int skip0, int nsteps, unsigned tag_base, unsigned* timeout, unsigned* claim, hipStream_t s); hipError_t preload_cluster_pot##P();
-C3D_CL_DECL(0) C3D_CL_DECL(1) C3D_CL_DECL(2) C3D_CL_DECL(3) C3D_CL_DECL(4)
-#undef C3D_CL_DECL
-#define C3D_CL_DECL(P) hipError_t launch_cluster_tp_pot##P(const DevModel& m, const DevFire& fp, const ClusterPlan& pl, const AnnealIO& io, const float* tgt, void* rec, const StepRun* runs, int run0, int skip0, int nsteps, unsigned tag_base, unsigned* timeout, unsigned* claim, hipStream_t s); hipError_t preload_cluster_tp_pot##P();
-C3D_CL_DECL(0) C3D_CL_DECL(1) C3D_CL_DECL(2) C3D_CL_DECL(3) C3D_CL_DECL(4)
-#undef C3D_CL_DECL
-#define C3D_CL_POT(P) (pl.two_point ? launch_cluster_tp_pot##P(m, fp, pl, io, tgt, rec, runs, run0, skip0, nsteps, tag_base, timeout, claim, s) : launch_cluster_pot##P(m, fp, pl, io, tgt, rec, runs, run0, skip0, nsteps, tag_base, timeout, claim, s))
-#else
-#define C3D_CL_POT(P) cluster_geom<P>(m, fp, pl, io, tgt, rec, runs, run0, skip0, nsteps, tag_base, timeout, claim, s)
+// the per-potential units' entries, by [two_point][potential]
+ClusterLaunch launch_cluster_pot0, launch_cluster_pot1, launch_cluster_pot2, launch_cluster_pot3, launch_cluster_pot4;
+ClusterLaunch launch_cluster_tp_pot0, launch_cluster_tp_pot1, launch_cluster_tp_pot2, launch_cluster_tp_pot3, launch_cluster_tp_pot4;
+hipError_t preload_cluster_pot0(), preload_cluster_pot1(), preload_cluster_pot2(), preload_cluster_pot3(), preload_cluster_pot4();
+hipError_t preload_cluster_tp_pot0(), preload_cluster_tp_pot1(), preload_cluster_tp_pot2(), preload_cluster_tp_pot3(), preload_cluster_tp_pot4();
+static ClusterLaunch* const kClusterLaunch[2][5] = {{launch_cluster_pot0, launch_cluster_pot1, launch_cluster_pot2, launch_cluster_pot3, launch_cluster_pot4},
+                                                    {launch_cluster_tp_pot0, launch_cluster_tp_pot1, launch_cluster_tp_pot2, launch_cluster_tp_pot3, launch_cluster_tp_pot4}};
+static hipError_t (*const kClusterPreload[2][5])() = {{preload_cluster_pot0, preload_cluster_pot1, preload_cluster_pot2, preload_cluster_pot3, preload_cluster_pot4},
+                                                      {preload_cluster_tp_pot0, preload_cluster_tp_pot1, preload_cluster_tp_pot2, preload_cluster_tp_pot3, preload_cluster_tp_pot4}};
 #endif
 hipError_t launch_cluster(const DevModel& m, const DevFire& fp, const ClusterPlan& pl, const AnnealIO& io, const float* tgt, void* rec,
                           const StepRun* runs, int run0, int skip0, int nsteps, unsigned tag_base, unsigned* timeout, unsigned* claim,
                           hipStream_t s) {
-    switch (m.noe_pot) {
-        case 0: return C3D_CL_POT(0);
-        case 1: return C3D_CL_POT(1);
-        case 3: return C3D_CL_POT(3);
-        case 4: return C3D_CL_POT(4);
-        default: return C3D_CL_POT(2);
-    }
+#if defined(C3D_CLUSTER_SPLIT)
+    return kClusterLaunch[pl.two_point][device_pot(m.noe_pot)](m, fp, pl, io, tgt, rec, runs, run0, skip0, nsteps, tag_base, timeout, claim, s);
+#else
+    return with_pot(m.noe_pot, [&](auto POT) { return cluster_geom<POT>(m, fp, pl, io, tgt, rec, runs, run0, skip0, nsteps, tag_base, timeout, claim, s); });
+#endif
 }
-#undef C3D_CL_POT
 
 AnnealIO anneal_io(const DevBuffers& b, int parity) {
     const int q = parity ^ 1;
@@ -827,24 +808,11 @@ AnnealIO anneal_io(const DevBuffers& b, int parity) {
 // the unit that holds the multi-step kernels of device potential `pot` — k_cluster (two_point false) or k_cluster_tp —, loaded and
 // prepared on the current device (cluster_prepare_unit); pot outside 0..4 is an error
 hipError_t preload_cluster_unit(int pot, bool two_point) {
+    if (pot < 0 || pot > 4) return hipErrorInvalidValue;
 #if defined(C3D_CLUSTER_SPLIT)
-    switch (pot) {
-        case 0: return two_point ? preload_cluster_tp_pot0() : preload_cluster_pot0();
-        case 1: return two_point ? preload_cluster_tp_pot1() : preload_cluster_pot1();
-        case 2: return two_point ? preload_cluster_tp_pot2() : preload_cluster_pot2();
-        case 3: return two_point ? preload_cluster_tp_pot3() : preload_cluster_pot3();
-        case 4: return two_point ? preload_cluster_tp_pot4() : preload_cluster_pot4();
-        default: return hipErrorInvalidValue;
-    }
+    return kClusterPreload[two_point][pot]();
 #else
-    switch (pot) {
-        case 0: return two_point ? cluster_prepare_unit<0, true>() : cluster_prepare_unit<0, false>();
-        case 1: return two_point ? cluster_prepare_unit<1, true>() : cluster_prepare_unit<1, false>();
-        case 2: return two_point ? cluster_prepare_unit<2, true>() : cluster_prepare_unit<2, false>();
-        case 3: return two_point ? cluster_prepare_unit<3, true>() : cluster_prepare_unit<3, false>();
-        case 4: return two_point ? cluster_prepare_unit<4, true>() : cluster_prepare_unit<4, false>();
-        default: return hipErrorInvalidValue;
-    }
+    return with_pot(pot, [&](auto POT) { return with_bool(two_point, [&](auto TP) { return cluster_prepare_unit<POT, TP>(); }); });
 #endif
 }
 // the planner's own unit: k_tear16 (c3d_debug_tear16) and nothing else in the split build

@@ -219,57 +219,23 @@ hipError_t launch_pair_targets(const DevModel& m, const float* tgt, float* tgs2,
 
 static size_t step_lds_bytes(const DevModel& m, int tile_rows = kTileRows) { return sizeof(float) * ((size_t)3 * m.npad + 4 * tile_rows + 12); }   // xyz + rowq + the step scalars' hand-over
 
-template <int POT, bool GEN, int RPW>
-static hipError_t launch_step_r(const DevModel& m0, const DevStep& p, const DevFire& fp, const DevBuffers& b, int par, bool wide,
-                                hipStream_t s) {
+// the form step_form chose: the narrow k_step<pot, gen, rpw, nc> or the wide one (16 rows a workgroup, four a wave, resident pair targets)
+hipError_t launch_step(const DevModel& m0, const DevStep& p, const DevFire& fp, const DevBuffers& b, int par, const StepForm& f, hipStream_t s) {
     const int q = par ^ 1;
     DevModel m = m0;
-    m.tgs2 = (POT == 4 && !GEN && RPW == 2 && m.wl == 4 && m.nleft == 0) ? b.tgs2 : nullptr;      // (the kernels that read it)
-    if constexpr (POT == 4 && !GEN && RPW == 2) {
-        if (wide && m.wl == 4 && m.nleft == 0 && m.tgs2) {      // 16 rows a workgroup, four a wave (two packed row pairs; resident pair targets)
-            constexpr int TR = 2 * kTileRows;
-            const int nwg = (m.ntiles + 1) / 2;
-            hipLaunchKernelGGL((k_step<4, false, 4, false, TR, true>), dim3(8, m.nrep_g, (nwg + 7) / 8), dim3(64 * TR / 4), step_lds_bytes(m, TR), s,
-                               b.P[par], b.X[par], b.tgt, b.V[par], b.Vinit, b.S[par], b.X[q], b.V[q], b.P[q], b.S[q], m, p, fp);
-            return hipGetLastError();
-        }
-    }
-    if (m.wl == 4 && m.nleft == 0)      // no narrow last block, no left-over columns: the variant without that code
-        hipLaunchKernelGGL((k_step<POT, GEN, RPW, false>), grid_blocks(m), dim3(64 * kTileRows / RPW), step_lds_bytes(m), s,
+    m.tgs2 = f.pairs ? b.tgs2 : nullptr;      // (the kernels that read it)
+    if (f.wide) {
+        constexpr int TR = 2 * kTileRows;
+        const int nwg = (m.ntiles + 1) / 2;
+        hipLaunchKernelGGL((k_step<4, false, 4, false, TR, true>), dim3(8, m.nrep_g, (nwg + 7) / 8), dim3(64 * TR / 4), step_lds_bytes(m, TR), s,
                            b.P[par], b.X[par], b.tgt, b.V[par], b.Vinit, b.S[par], b.X[q], b.V[q], b.P[q], b.S[q], m, p, fp);
-    else
-        hipLaunchKernelGGL((k_step<POT, GEN, RPW, true>), grid_blocks(m), dim3(64 * kTileRows / RPW), step_lds_bytes(m), s,
+        return hipGetLastError();
+    }
+    return with_pot(f.pot, [&](auto POT) { return with_bool(f.gen, [&](auto GEN) { return with_rpw(f.rpw, [&](auto RPW) { return with_bool(f.nc, [&](auto NC) {
+        hipLaunchKernelGGL((k_step<POT, GEN, RPW, NC>), grid_blocks(m), dim3(64 * kTileRows / RPW), step_lds_bytes(m), s,
                            b.P[par], b.X[par], b.tgt, b.V[par], b.Vinit, b.S[par], b.X[q], b.V[q], b.P[q], b.S[q], m, p, fp);
-    return hipGetLastError();
-}
-template <int POT, bool GEN>
-static hipError_t launch_step_t(const DevModel& m, const DevStep& p, const DevFire& fp, const DevBuffers& b, int par, bool wide,
-                                hipStream_t s) {
-    switch (m.rpw) {
-        case 1: return launch_step_r<POT, GEN, 1>(m, p, fp, b, par, wide, s);
-        case 2: return launch_step_r<POT, GEN, 2>(m, p, fp, b, par, wide, s);
-        default: return launch_step_r<POT, GEN, 4>(m, p, fp, b, par, wide, s);
-    }
-}
-
-hipError_t launch_step(const DevModel& m, const DevStep& p, const DevFire& fp, const DevBuffers& b, int parity,
-                       bool general_tail, bool wide, hipStream_t s) {
-    if (!general_tail) {
-        switch (m.noe_pot) {
-            case 0: return launch_step_t<0, false>(m, p, fp, b, parity, wide, s);
-            case 1: return launch_step_t<1, false>(m, p, fp, b, parity, wide, s);
-            case 3: return launch_step_t<3, false>(m, p, fp, b, parity, wide, s);
-            case 4: return launch_step_t<4, false>(m, p, fp, b, parity, wide, s);
-            default: return launch_step_t<2, false>(m, p, fp, b, parity, wide, s);
-        }
-    }
-    switch (m.noe_pot) {
-        case 0: return launch_step_t<0, true>(m, p, fp, b, parity, wide, s);
-        case 1: return launch_step_t<1, true>(m, p, fp, b, parity, wide, s);
-        case 3: return launch_step_t<3, true>(m, p, fp, b, parity, wide, s);
-        case 4: return launch_step_t<4, true>(m, p, fp, b, parity, wide, s);
-        default: return launch_step_t<2, true>(m, p, fp, b, parity, wide, s);
-    }
+        return hipGetLastError();
+    }); }); }); });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -307,21 +273,17 @@ __global__ __launch_bounds__(64 * kTileRows / ERPW) void k_eval_forces(const Dev
 hipError_t launch_eval_forces(const DevModel& m, const DevStep& p, const DevBuffers& b, int parity, float* Fout,
                               bool general_tail, int rows_per_wave, hipStream_t s) {
     const size_t lds = sizeof(float) * (size_t)3 * m.npad;
-    const dim3 g = grid_blocks(m), blk(kEvalBlock);
+    const dim3 g = grid_blocks(m);
     static_assert(kEvalRowsPerWave == 4, "the hook's default form is four rows per wave");
-#define C3D_EVAL(POT, GEN) hipLaunchKernelGGL((k_eval_forces<POT, GEN, 4>), g, blk, lds, s, m, p, b.tgt, b.X[parity], Fout)
-    if (!general_tail) {
-        if (m.noe_pot == 0) C3D_EVAL(0, false); else if (m.noe_pot == 1) C3D_EVAL(1, false); else if (m.noe_pot == 3) C3D_EVAL(3, false);
-        else if (m.noe_pot == 4) {
-            if (rows_per_wave == 2) hipLaunchKernelGGL((k_eval_forces<4, false, 2, true>), g, dim3(64 * kTileRows / 2), lds, s, m, p, b.tgt, b.X[parity], Fout);
-            else if (rows_per_wave == -2) hipLaunchKernelGGL((k_eval_forces<4, false, 2, false>), g, dim3(64 * kTileRows / 2), lds, s, m, p, b.tgt, b.X[parity], Fout);
-            else C3D_EVAL(4, false);
-        } else C3D_EVAL(2, false);
-    } else {
-        if (m.noe_pot == 0) C3D_EVAL(0, true); else if (m.noe_pot == 1) C3D_EVAL(1, true); else if (m.noe_pot == 3) C3D_EVAL(3, true); else if (m.noe_pot == 4) C3D_EVAL(4, true); else C3D_EVAL(2, true);
-    }
-#undef C3D_EVAL
-    return hipGetLastError();
+    return with_pot(m.noe_pot, [&](auto POT) { return with_bool(general_tail, [&](auto GEN) {
+        if constexpr (POT == 4 && !GEN)
+            if (rows_per_wave == 2 || rows_per_wave == -2) return with_bool(rows_per_wave == 2, [&](auto PACKED) {
+                hipLaunchKernelGGL((k_eval_forces<4, false, 2, PACKED>), g, dim3(64 * kTileRows / 2), lds, s, m, p, b.tgt, b.X[parity], Fout);
+                return hipGetLastError();
+            });
+        hipLaunchKernelGGL((k_eval_forces<POT, GEN, 4>), g, dim3(kEvalBlock), lds, s, m, p, b.tgt, b.X[parity], Fout);
+        return hipGetLastError();
+    }); });
 }
 
 // ---------------------------------------------------------------------------------------------

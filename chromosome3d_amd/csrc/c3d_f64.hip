@@ -473,16 +473,11 @@ static Model64 model64(const DevModel& d, const double* host) {
     // lower side beyond mrs: dE/dD = mtail_c - mtail_b / D^(mexp + 1)
     m.mrs = host[4]; m.mtail_c = host[3]; m.mtail_b = (m.mtail_c - 2.0 * m.mrs) * m.mrs * m.mrs * (m.mexp == 2 ? m.mrs : 1.0);
     m.nmrs4 = -(m.mrs * m.mrs) * (m.mrs * m.mrs);
-    if (m.noe_pot == 4 && !(m.mexp == 2 && m.mtail_c == 0.0 && m.tail_b == 0.0 && m.tail_c == 2.0 * m.rs)) m.noe_pot = 3;   // (cannot happen: same test in doubles)
+    m.noe_pot = form64(d.noe_pot, host, 0.0).pot;
     m.k_bond = host[5]; m.b0 = host[6]; m.k_ang = host[7]; m.a0 = host[8]; m.r0_rep = host[9]; m.k_rep = host[10]; m.mass = host[11]; m.fbeta = host[12];
     { const int ndf = 3 * d.n - 3; m.t_fac = m.mass / kAccel64 / ((ndf > 0 ? ndf : 1) * kBoltz64); m.inv_n = 1.0 / d.n; }
     return m;
 }
-static bool general64(const Model64& m) {
-    if (!(m.tail_b == 0.0 && m.tail_c == 2.0 * m.rs)) return true;
-    return m.noe_pot == 3 && !(m.mtail_b == 0.0 && m.mtail_c == 2.0 * m.mrs);     // potential 4 has a fast form of its own
-}
-
 hipError_t launch_step64(const DevModel& d, const double* model_host, const double* step_host, const double* fire_host, int fire_n_min,
                          const Buffers64& b, int parity, hipStream_t s) {
     const Model64 m = model64(d, model_host);
@@ -504,24 +499,22 @@ hipError_t launch_step64(const DevModel& d, const double* model_host, const doub
     const size_t lds = sizeof(double) * ((size_t)3 * m.np + 4 * kTileRows + 8);
     FireState64* sin = reinterpret_cast<FireState64*>(b.S[parity]);
     FireState64* sout = reinterpret_cast<FireState64*>(b.S[q]);
-#define C3D_STEP64(POT, GEN) hipLaunchKernelGGL((k64_step<POT, GEN>), grid, blk, lds, s, m, p, fp, d.rep_base, b.T, b.X[parity], b.V[parity], b.Vinit, \
-                                                b.P[parity], sin, b.X[q], b.V[q], b.P[q], sout)
-    if (!general64(m)) {
-        if (m.noe_pot == 0) C3D_STEP64(0, false); else if (m.noe_pot == 1) C3D_STEP64(1, false); else if (m.noe_pot == 3) C3D_STEP64(3, false);
-        else if (m.noe_pot == 4) {
-            if (p.w_all != 0.0) hipLaunchKernelGGL((k64_step<4, false, true>), grid, blk, lds, s, m, p, fp, d.rep_base, b.T, b.X[parity], b.V[parity], b.Vinit, b.P[parity],
-                                                   sin, b.X[q], b.V[q], b.P[q], sout);
-            else C3D_STEP64(4, false);
-        } else C3D_STEP64(2, false);
-    } else {
-        if (m.noe_pot == 0) C3D_STEP64(0, true); else if (m.noe_pot == 1) C3D_STEP64(1, true); else if (m.noe_pot == 3) C3D_STEP64(3, true); else C3D_STEP64(2, true);
-    }
-#undef C3D_STEP64
-    return hipGetLastError();
+    const Form64 f = form64(d.noe_pot, model_host, p.w_all);
+    return with_pot(f.pot, [&](auto P) {
+        return with_bool(f.gen, [&](auto G) {
+            return with_bool(f.fold, [&](auto F) {
+                constexpr int POT = G && P == 4 ? 2 : P;            // (the general forms have no potential-4 kernel: form64 never asks for one)
+                constexpr bool FOLD = F && POT == 4 && !G;
+                hipLaunchKernelGGL((k64_step<POT, G, FOLD>), grid, blk, lds, s, m, p, fp, d.rep_base, b.T, b.X[parity], b.V[parity], b.Vinit, b.P[parity],
+                                   sin, b.X[q], b.V[q], b.P[q], sout);
+                return hipGetLastError();
+            });
+        });
+    });
 }
 hipError_t launch_targets64(const DevModel& d, const double* model_host, int min_sep, const int32_t* t10, double* T, hipStream_t s) {
-    const Model64 m = model64(d, model_host);
-    const double none = (m.noe_pot == 4 && !general64(m)) ? kNoTarget64 : 0.0;        // what pair64 of the kernel that will run expects
+    const Form64 f = form64(d.noe_pot, model_host, 0.0);
+    const double none = (f.pot == 4 && !f.gen) ? kNoTarget64 : 0.0;        // what pair64 of the kernel that will run expects
     hipLaunchKernelGGL(k64_targets, dim3(d.n), dim3(256), 0, s, d.n, cols64(d.n), min_sep, none, t10, T);
     return hipGetLastError();
 }

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 namespace c3d {
 
@@ -90,10 +91,56 @@ struct DevBuffers {
     double* E;      // [nrep][4]
 };
 
+// Runtime choices -> template arguments: f is called with std::integral_constant arguments (a generic lambda)
+template <int V> using int_c = std::integral_constant<int, V>;
+template <bool V> using bool_c = std::integral_constant<bool, V>;
+inline int device_pot(int noe_pot) { return noe_pot == 0 || noe_pot == 1 || noe_pot == 3 || noe_pot == 4 ? noe_pot : 2; }   // anything else runs as 2
+template <class F> hipError_t with_pot(int pot, F&& f) {
+    switch (device_pot(pot)) {
+        case 0: return f(int_c<0>{});
+        case 1: return f(int_c<1>{});
+        case 3: return f(int_c<3>{});
+        case 4: return f(int_c<4>{});
+        default: return f(int_c<2>{});
+    }
+}
+template <class F> hipError_t with_rpw(int rpw, F&& f) { return rpw == 1 ? f(int_c<1>{}) : rpw == 2 ? f(int_c<2>{}) : f(int_c<4>{}); }
+template <class F> hipError_t with_bool(bool b, F&& f) { return b ? f(bool_c<true>{}) : f(bool_c<false>{}); }
+
+// default tails: the force stays at its value at the switch distance (slope 2 rs above, 2 mrs below for noe_pot 3)
+inline bool general_tail(const DevModel& m) {
+    if (!(m.tail_b == 0.0f && m.tail_c == 2.0f * m.rs)) return true;
+    return m.noe_pot == 3 && !(m.mtail_b == 0.0f && m.mtail_c == 2.0f * m.mrs);      // (device potential 4 is a fast form by construction)
+}
+// the kernels of the general form also serve a step whose restraint weight is zero (the clamp form divides by it)
+inline bool general_step(const DevModel& m, const DevStep& p) { return general_tail(m) || p.w_rs == 0.0f; }
+// DevModel::tgs2 serves device potential 4 at two rows per wave without a narrow last block (ensure_pair_targets builds it beyond n = 1024)
+inline bool pair_targets_fit(const DevModel& m) { return device_pot(m.noe_pot) == 4 && m.rpw == 2 && m.wl == 4 && m.nleft == 0; }
+
+// The form of a per-step kernel (k_step, k_lbfgs_eval): k<pot, gen, rpw, nc>, or the wide k<4, false, 4, false, 16, true> — 16 rows a
+// workgroup, four a wave, resident pair targets: problems beyond the multi-step kernel's reach.  Decided once per op: the launch and
+// c3d_step_kernel_name both read it.  Switches: the context's options wide_tiles and pair_targets, and whether tgs2 is built.
+struct StepForm {
+    int pot;
+    bool gen;
+    int rpw;
+    bool nc, pairs, wide;            // pairs: DevModel::tgs2 passed to the kernel
+};
+inline StepForm step_form(const DevModel& m, const DevStep& p, bool wide_tiles, bool pair_targets, bool tgs2_built) {
+    StepForm f;
+    f.pot = device_pot(m.noe_pot);
+    f.rpw = m.rpw == 1 || m.rpw == 2 ? m.rpw : 4;
+    f.gen = general_step(m, p);
+    f.nc = !(m.wl == 4 && m.nleft == 0);
+    f.pairs = !f.gen && pair_targets_fit(m) && tgs2_built;
+    f.wide = wide_tiles && pair_targets && f.pairs && m.npad > 1024;
+    return f;
+}
+// the symmetric-tile kernel's RS1 (k_pairs_sym: c3d_sym.hip)
+inline bool sym_rs1(const DevModel& m) { return m.rs == 1.0f; }
+
 // host-callable launchers (defined in c3d_device.hip)
-// wide: 16 rows a workgroup and four a wave (the shipped potential, clamp forms, no narrow last block; the caller decides: n > 1024)
-hipError_t launch_step(const DevModel& m, const DevStep& p, const DevFire& fp, const DevBuffers& b, int parity,
-                       bool general_tail, bool wide, hipStream_t s);
+hipError_t launch_step(const DevModel& m, const DevStep& p, const DevFire& fp, const DevBuffers& b, int parity, const StepForm& f, hipStream_t s);
 hipError_t launch_eval_forces(const DevModel& m, const DevStep& p, const DevBuffers& b, int parity, float* Fout,
                               bool general_tail, int rows_per_wave, hipStream_t s);
 hipError_t launch_energy(const DevModel& m, const DevStep& p, const DevBuffers& b, int parity, float s_noe,
@@ -121,7 +168,7 @@ struct LbfgsBuffers {
 };
 __host__ __device__ inline size_t lbfgs_hist_floats(int npad) { return (size_t)2 * kLbfgsMaxPairs * 3 * npad; }   // per replica
 hipError_t launch_lbfgs_eval(const DevModel& m, const DevStep& p, const DevBuffers& b, const LbfgsBuffers& lb, int parity, int mem,
-                             bool general_tail, bool wide, hipStream_t s);
+                             const StepForm& f, hipStream_t s);
 hipError_t launch_lbfgs_move(const DevModel& m, const DevStep& p, const DevFire& fp, const DevBuffers& b, const LbfgsBuffers& lb, int parity,
                              int mem, hipStream_t s);
 size_t pair_targets_floats(int n, int npad);           // size of DevBuffers::tgs2
@@ -199,6 +246,23 @@ struct Buffers64 {
 };
 int cols64(int n);
 constexpr int kMaxBeads64 = 2560;     // 3 * 8 * np bytes of LDS must stay below the 64 KB a launch gets without opt-in
+// k64_step<pot, gen, fold>'s form, decided in doubles over the fp64 model (model_host, below) for the launch, the target encoding and
+// c3d_step_kernel_name alike: gen = a general tail, fold = the fast soft lower side (device potential 4) at a restraint weight w_all != 0
+struct Form64 {
+    int pot;
+    bool gen, fold;
+};
+inline Form64 form64(int noe_pot, const double* model_host, double w_all) {
+    const double* h = model_host;
+    const int mexp = (int)h[14] == 2 ? 2 : 1;
+    const double rs = h[1], tail_c = h[2] * h[1], tail_b = (tail_c - 2.0 * rs) * rs * rs;
+    const double mrs = h[4], mtail_c = h[3], mtail_b = (mtail_c - 2.0 * mrs) * mrs * mrs * (mexp == 2 ? mrs : 1.0);
+    Form64 f;
+    f.pot = noe_pot == 4 && !(mexp == 2 && mtail_c == 0.0 && tail_b == 0.0 && tail_c == 2.0 * rs) ? 3 : device_pot(noe_pot);   // (cannot happen)
+    f.gen = !(tail_b == 0.0 && tail_c == 2.0 * rs) || (f.pot == 3 && !(mtail_b == 0.0 && mtail_c == 2.0 * mrs));     // (potential 4 has a fast form of its own)
+    f.fold = f.pot == 4 && !f.gen && w_all != 0.0;
+    return f;
+}
 hipError_t launch_step64(const DevModel& d, const double* model_host, const double* step_host, const double* fire_host, int fire_n_min,
                          const Buffers64& b, int parity, hipStream_t s);
 hipError_t launch_targets64(const DevModel& d, const double* model_host, int min_sep, const int32_t* t10, double* T, hipStream_t s);

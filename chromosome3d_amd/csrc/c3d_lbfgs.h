@@ -256,58 +256,25 @@ __global__ __launch_bounds__(kLbfgsMoveRows) void k_lbfgs_move(
 
 static size_t lbfgs_eval_lds_bytes(const DevModel& m, int tile_rows) { return sizeof(float) * ((size_t)3 * m.npad + (size_t)kLbfgsQ * tile_rows); }
 
-template <int POT, bool GEN, int RPW>
-static hipError_t launch_lbfgs_eval_r(const DevModel& m0, const DevStep& p, const DevBuffers& b, const LbfgsBuffers& lb, int par, int mem,
-                                      bool wide, hipStream_t s) {
+// launch_step's form, with the kernel of an L-BFGS evaluation
+hipError_t launch_lbfgs_eval(const DevModel& m0, const DevStep& p, const DevBuffers& b, const LbfgsBuffers& lb, int par, int mem,
+                             const StepForm& f, hipStream_t s) {
+    if (mem < 1 || mem > kLbfgsMaxPairs) return hipErrorInvalidValue;
     const int q = par ^ 1;
     DevModel m = m0;
-    m.tgs2 = (POT == 4 && !GEN && RPW == 2 && m.wl == 4 && m.nleft == 0) ? b.tgs2 : nullptr;      // (the kernels that read it)
-    if constexpr (POT == 4 && !GEN && RPW == 2) {
-        if (wide && m.wl == 4 && m.nleft == 0 && m.tgs2) {      // launch_step's wide form: 16 rows a workgroup, four a wave
-            constexpr int TR = 2 * kTileRows;
-            const int nwg = (m.ntiles + 1) / 2;
-            hipLaunchKernelGGL((k_lbfgs_eval<4, false, 4, false, TR, true>), dim3(8, m.nrep_g, (nwg + 7) / 8), dim3(64 * TR / 4),
-                               lbfgs_eval_lds_bytes(m, TR), s, b.X[par], b.tgt, b.V[par], b.V[q], lb.hist, lb.part, lb.S[par], m, p, mem);
-            return hipGetLastError();
-        }
+    m.tgs2 = f.pairs ? b.tgs2 : nullptr;      // (the kernels that read it)
+    if (f.wide) {
+        constexpr int TR = 2 * kTileRows;
+        const int nwg = (m.ntiles + 1) / 2;
+        hipLaunchKernelGGL((k_lbfgs_eval<4, false, 4, false, TR, true>), dim3(8, m.nrep_g, (nwg + 7) / 8), dim3(64 * TR / 4),
+                           lbfgs_eval_lds_bytes(m, TR), s, b.X[par], b.tgt, b.V[par], b.V[q], lb.hist, lb.part, lb.S[par], m, p, mem);
+        return hipGetLastError();
     }
-    if (m.wl == 4 && m.nleft == 0)
-        hipLaunchKernelGGL((k_lbfgs_eval<POT, GEN, RPW, false>), grid_blocks(m), dim3(64 * kTileRows / RPW), lbfgs_eval_lds_bytes(m, kTileRows), s,
+    return with_pot(f.pot, [&](auto POT) { return with_bool(f.gen, [&](auto GEN) { return with_rpw(f.rpw, [&](auto RPW) { return with_bool(f.nc, [&](auto NC) {
+        hipLaunchKernelGGL((k_lbfgs_eval<POT, GEN, RPW, NC>), grid_blocks(m), dim3(64 * kTileRows / RPW), lbfgs_eval_lds_bytes(m, kTileRows), s,
                            b.X[par], b.tgt, b.V[par], b.V[q], lb.hist, lb.part, lb.S[par], m, p, mem);
-    else
-        hipLaunchKernelGGL((k_lbfgs_eval<POT, GEN, RPW, true>), grid_blocks(m), dim3(64 * kTileRows / RPW), lbfgs_eval_lds_bytes(m, kTileRows), s,
-                           b.X[par], b.tgt, b.V[par], b.V[q], lb.hist, lb.part, lb.S[par], m, p, mem);
-    return hipGetLastError();
-}
-template <int POT, bool GEN>
-static hipError_t launch_lbfgs_eval_t(const DevModel& m, const DevStep& p, const DevBuffers& b, const LbfgsBuffers& lb, int par, int mem,
-                                      bool wide, hipStream_t s) {
-    switch (m.rpw) {
-        case 1: return launch_lbfgs_eval_r<POT, GEN, 1>(m, p, b, lb, par, mem, wide, s);
-        case 2: return launch_lbfgs_eval_r<POT, GEN, 2>(m, p, b, lb, par, mem, wide, s);
-        default: return launch_lbfgs_eval_r<POT, GEN, 4>(m, p, b, lb, par, mem, wide, s);
-    }
-}
-
-hipError_t launch_lbfgs_eval(const DevModel& m, const DevStep& p, const DevBuffers& b, const LbfgsBuffers& lb, int parity, int mem,
-                             bool general_tail, bool wide, hipStream_t s) {
-    if (mem < 1 || mem > kLbfgsMaxPairs) return hipErrorInvalidValue;
-    if (!general_tail) {
-        switch (m.noe_pot) {
-            case 0: return launch_lbfgs_eval_t<0, false>(m, p, b, lb, parity, mem, wide, s);
-            case 1: return launch_lbfgs_eval_t<1, false>(m, p, b, lb, parity, mem, wide, s);
-            case 3: return launch_lbfgs_eval_t<3, false>(m, p, b, lb, parity, mem, wide, s);
-            case 4: return launch_lbfgs_eval_t<4, false>(m, p, b, lb, parity, mem, wide, s);
-            default: return launch_lbfgs_eval_t<2, false>(m, p, b, lb, parity, mem, wide, s);
-        }
-    }
-    switch (m.noe_pot) {
-        case 0: return launch_lbfgs_eval_t<0, true>(m, p, b, lb, parity, mem, wide, s);
-        case 1: return launch_lbfgs_eval_t<1, true>(m, p, b, lb, parity, mem, wide, s);
-        case 3: return launch_lbfgs_eval_t<3, true>(m, p, b, lb, parity, mem, wide, s);
-        case 4: return launch_lbfgs_eval_t<4, true>(m, p, b, lb, parity, mem, wide, s);
-        default: return launch_lbfgs_eval_t<2, true>(m, p, b, lb, parity, mem, wide, s);
-    }
+        return hipGetLastError();
+    }); }); }); });
 }
 
 hipError_t launch_lbfgs_move(const DevModel& m, const DevStep& p, const DevFire& fp, const DevBuffers& b, const LbfgsBuffers& lb, int parity,

@@ -238,16 +238,7 @@ static hipError_t sym_go(const DevModel& m, const DevStep& p, const DevFire& fp,
 hipError_t launch_step_sym(const DevModel& m, const DevStep& p, const DevFire& fp, const DevBuffers& b, int parity, const void* tiles,
                            float* scratch, hipStream_t s) {
     const int2* t = reinterpret_cast<const int2*>(tiles);
-    const bool rs1 = m.rs == 1.0f;
-#define C3D_SYM(POT) return rs1 ? sym_go<POT, true>(m, p, fp, b, parity, t, scratch, s) : sym_go<POT, false>(m, p, fp, b, parity, t, scratch, s)
-    switch (m.noe_pot) {
-        case 0: C3D_SYM(0);
-        case 1: C3D_SYM(1);
-        case 3: C3D_SYM(3);
-        case 4: C3D_SYM(4);
-        default: C3D_SYM(2);
-    }
-#undef C3D_SYM
+    return with_pot(m.noe_pot, [&](auto POT) { return with_bool(sym_rs1(m), [&](auto RS1) { return sym_go<POT, RS1>(m, p, fp, b, parity, t, scratch, s); }); });
 }
 
 hipError_t preload_sym_unit() {

@@ -243,8 +243,9 @@ int c3d_get_stat(const c3d_ctx* ctx, const char* key, double* value);
  * workgroup, a consumer workgroup on every other CU, the context's stream) for `iterations` rewrites of 1024 units and returns the number
  * of unit reads, of TORN units (must be 0) and of reads that saw a new value. */
 int c3d_debug_tear16(c3d_ctx* ctx, int iterations, unsigned long long* unit_reads, unsigned long long* torn, unsigned long long* fresh);
-/* Name of the step kernel the last c3d_run / c3d_run_steps ran on, as a profiler prints it (thread-local string); after a range of L-BFGS
- * steps the force pass, k_lbfgs_eval<...>. */
+/* Name of the kernel the last op of the last range of c3d_run / c3d_run_steps ran on, as a profiler prints it (thread-local string): the
+ * choice that op's launch was made from, also when the range was replayed from a captured graph.  After an L-BFGS step the force pass,
+ * k_lbfgs_eval<...>; "" before the first range. */
 const char* c3d_step_kernel_name(const c3d_ctx* ctx);
 
 /* One evaluation through the production pair kernel at the replicas' current coordinates:

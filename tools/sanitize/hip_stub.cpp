@@ -116,7 +116,7 @@ hipError_t preload_embed_unit() { LoadScope l; return load_result(); }
 hipError_t preload_f64_unit() { LoadScope l; return load_result(); }
 hipError_t preload_sym_unit() { LoadScope l; return load_result(); }
 
-hipError_t launch_step(const DevModel&, const DevStep&, const DevFire&, const DevBuffers&, int, bool, bool, hipStream_t) { LaunchScope ls; return hipSuccess; }
+hipError_t launch_step(const DevModel&, const DevStep&, const DevFire&, const DevBuffers&, int, const StepForm&, hipStream_t) { LaunchScope ls; return hipSuccess; }
 hipError_t launch_eval_forces(const DevModel&, const DevStep&, const DevBuffers&, int, float*, bool, int, hipStream_t) { LaunchScope ls; return hipSuccess; }
 hipError_t launch_energy(const DevModel& m, const DevStep&, const DevBuffers& b, int, float, float, double, hipStream_t) {
     LaunchScope ls;
@@ -126,7 +126,7 @@ hipError_t launch_energy(const DevModel& m, const DevStep&, const DevBuffers& b,
 hipError_t launch_centre(const DevModel&, const DevBuffers&, int, hipStream_t) { LaunchScope ls; return hipSuccess; }
 size_t pair_targets_floats(int n, int npad) { return (size_t)n * npad; }
 hipError_t launch_pair_targets(const DevModel&, const float*, float*, hipStream_t) { LaunchScope ls; return hipSuccess; }
-hipError_t launch_lbfgs_eval(const DevModel&, const DevStep&, const DevBuffers&, const LbfgsBuffers&, int, int, bool, bool, hipStream_t) { LaunchScope ls; return hipSuccess; }
+hipError_t launch_lbfgs_eval(const DevModel&, const DevStep&, const DevBuffers&, const LbfgsBuffers&, int, int, const StepForm&, hipStream_t) { LaunchScope ls; return hipSuccess; }
 hipError_t launch_lbfgs_move(const DevModel&, const DevStep&, const DevFire&, const DevBuffers&, const LbfgsBuffers&, int, int, hipStream_t) { LaunchScope ls; return hipSuccess; }
 AnnealIO anneal_io(const DevBuffers& b, int parity) {
     const int q = parity ^ 1;
