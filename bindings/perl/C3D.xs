@@ -91,6 +91,7 @@ solve(matrix_path, out_dir, id, models, K, alpha, seed, device, embed)
         c3d_default_model(&model);
         C3D_TRY(c3d_set_model(ctx, &model));
         C3D_TRY(c3d_parse_if_file(matrix_path, &IF, &n));
+        if (n > C3D_MAX_BEADS_DEFAULT && n <= C3D_MAX_BEADS_LIMIT) C3D_TRY(c3d_set_option(ctx, "max_beads", n));
         C3D_TRY(c3d_set_if_matrix(ctx, IF, n, alpha, K));
         d10 = (int32_t*)malloc(sizeof(int32_t) * (size_t)n * n);
         C3D_TRY(c3d_get_dist10(ctx, d10));

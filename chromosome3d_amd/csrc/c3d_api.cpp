@@ -138,6 +138,8 @@ struct c3d_ctx {
     int eval_rpw = 4;                      // option "eval_rows_per_wave": 4 = scalar pair term in the forces hook, 2 = the packed one, -2 = scalar at two rows per wave
     bool pair_targets = true;              // option "pair_targets": the per-step kernel's resident row-pair constants (measurement knob)
     bool wide_tiles = true;                // option "wide_tiles": beyond the multi-step kernel's reach, 16 rows a workgroup and 4 a wave (measurement knob)
+    int max_beads = 5120;                  // option "max_beads": the largest matrix c3d_set_if_matrix / c3d_set_restraints accept (5120..16384)
+    int column_chunk = 0;                  // option "column_chunk": 0 = the library's choice, else the chunked form's CHUNK (c3d::column_chunk_for)
     float* d_feval = nullptr;
     size_t rep_floats = 0;           // 3*npad per replica
     bool have_targets = false, have_replicas = false;
@@ -661,7 +663,7 @@ KernelRecord op_kernel(const c3d_ctx* c, const c3d::DevModel& m, const Op& op) {
         k.rs1 = c3d::sym_rs1(m);
     } else {
         k.family = is_lbfgs(op.p.kind) ? KernelRecord::LBFGS_EVAL : KernelRecord::STEP;
-        k.step = c3d::step_form(m, op.p, c->wide_tiles, c->pair_targets, c->buf.tgs2 != nullptr);
+        k.step = c3d::step_form(m, op.p, c->wide_tiles, c->pair_targets, c->buf.tgs2 != nullptr, c->column_chunk);
     }
     return k;
 }
@@ -1267,6 +1269,16 @@ extern "C" int c3d_set_option(c3d_ctx* c, const char* key, double value) {
     } else if (!strcmp(key, "spin_wait_us")) c->spin_wait_us = value < 0 ? 0 : value;
     else if (!strcmp(key, "resident_min_ops")) c->resident_min_ops = value < 1 ? 1 : (int)value;
     else if (!strcmp(key, "stage_dma")) { c->stage_dma = value != 0; stale = STALE_GRAPHS; }
+    else if (!strcmp(key, "max_beads")) {          // the caller's consent to the memory of a large matrix (c3d.h); before c3d_set_if_matrix
+        if (value != (int)value || value < C3D_MAX_BEADS_DEFAULT || value > C3D_MAX_BEADS_LIMIT)
+            return fail(C3D_ERR_INVALID, "max_beads must be an integer from 5120 to 16384");
+        c->max_beads = (int)value;
+    } else if (!strcmp(key, "column_chunk")) {     // test and measurement knob: the per-step kernels' column source (same bits either way)
+        if (value != (int)value || (value != 0 && !c3d::column_chunk_valid((int)value)))
+            return fail(C3D_ERR_INVALID, "column_chunk must be 0 (the library's choice), 256, 1024 or 2048");
+        c->column_chunk = (int)value;
+        stale = STALE_GRAPHS;
+    }
     else if (!strcmp(key, "graph_chunk")) {
         if (value < 8) return fail(C3D_ERR_INVALID, "graph_chunk must be >= 8");
         c->graph_chunk = (int)value & ~1;   // even: a chunk returns to the starting parity
@@ -1275,14 +1287,28 @@ extern "C" int c3d_set_option(c3d_ctx* c, const char* key, double value) {
     return drop_stale_gated(c, stale);
 }
 
-// 3*npad floats of LDS per workgroup must stay below the 64 KB a launch gets without opt-in
-static constexpr int kMaxBeads = 5120;
+// The largest matrix a context accepts: kDefaultMaxBeads unless the option max_beads raises it, up to kMaxBeadsLimit.  Up to
+// c3d::kMaxStagedCols the per-step kernels stage a replica's coordinates in LDS; beyond, they run in the chunked form (c3d_chunked.h).
+// The default stays where the staged form ends: a larger matrix needs ~8 n npad bytes per context (targets and pair targets) and K1's
+// transient copies of the matrix, which the caller agrees to by raising the limit.
+static constexpr int kDefaultMaxBeads = C3D_MAX_BEADS_DEFAULT;
+static constexpr int kMaxBeadsLimit = C3D_MAX_BEADS_LIMIT;
+static_assert(kDefaultMaxBeads == c3d::kMaxStagedCols, "the default limit is the staged form's");
+static int too_many_beads(const c3d_ctx* c, const char* fn, int n) {
+    char b[192];
+    if (c->max_beads == kDefaultMaxBeads)
+        snprintf(b, sizeof b, "%s: %d beads: more than %d are accepted only after c3d_set_option(\"max_beads\", n) (up to %d)", fn, n,
+                 kDefaultMaxBeads, kMaxBeadsLimit);
+    else
+        snprintf(b, sizeof b, "%s: %d beads: more than max_beads = %d (the option goes up to %d)", fn, n, c->max_beads, kMaxBeadsLimit);
+    return fail(C3D_ERR_INVALID, b);
+}
 // c3d_set_if_matrix computes the Spearman's IF ranks ahead of c3d_score_replicas up to this many beads (memory: see there)
 static constexpr int kRankPrefetchBeads = 2048;
 
 extern "C" int c3d_set_if_matrix(c3d_ctx* c, const double* IF, int n, double alpha, double K) {
     if (!c || !IF || n < 2) return fail(C3D_ERR_INVALID, "c3d_set_if_matrix: bad arguments");
-    if (n > kMaxBeads) return fail(C3D_ERR_INVALID, "c3d_set_if_matrix: more than 5120 beads are not supported by this build");
+    if (n > c->max_beads) return too_many_beads(c, "c3d_set_if_matrix", n);
     C3D_ENTRY(c, 0u);
     free_replica_buffers(c);
     set_dims(c, n);
@@ -1378,7 +1404,7 @@ extern "C" int c3d_set_if_matrix(c3d_ctx* c, const double* IF, int n, double alp
 
 extern "C" int c3d_set_restraints(c3d_ctx* c, int n, int R, const int32_t* ri, const int32_t* rj, const int32_t* rt10) {
     if (!c || n < 2 || R < 0 || (R > 0 && (!ri || !rj || !rt10))) return fail(C3D_ERR_INVALID, "c3d_set_restraints: bad arguments");
-    if (n > kMaxBeads) return fail(C3D_ERR_INVALID, "c3d_set_restraints: more than 5120 beads are not supported by this build");
+    if (n > c->max_beads) return too_many_beads(c, "c3d_set_restraints", n);
     C3D_ENTRY(c, 0u);
     free_replica_buffers(c);
     c->ifr.release();
@@ -1414,6 +1440,8 @@ extern "C" int c3d_num_restraints(const c3d_ctx* c) { return c ? c->R : 0; }
 extern "C" int c3d_init_replicas(c3d_ctx* c, int nrep, uint64_t seed, uint32_t first_replica) {
     if (!c || nrep < 1) return fail(C3D_ERR_INVALID, "c3d_init_replicas: bad arguments");
     if (!c->have_targets) return fail(C3D_ERR_INVALID, "c3d_init_replicas: set the IF matrix / restraints first");
+    if (c->sym > 0 && c->npad > c3d::kMaxStagedCols && c->precision != 64)
+        return fail(C3D_ERR_INVALID, "c3d_init_replicas: symmetric tiles stage a replica in LDS and take at most 5120 beads; set symmetric 0");
     C3D_ENTRY(c, 0u);
     if (c->have_replicas && nrep != c->nrep) free_replica_buffers(c);
     c->nrep = nrep; c->seed = seed; c->first_rep = first_replica;
@@ -1770,7 +1798,10 @@ extern "C" const char* c3d_step_kernel_name(const c3d_ctx* c) {
         case KernelRecord::STEP:
         case KernelRecord::LBFGS_EVAL: {      // (after an L-BFGS step: its force pass, k_lbfgs_move follows it)
             const char* kernel = k.family == KernelRecord::STEP ? "k_step" : "k_lbfgs_eval";
-            if (k.step.wide) snprintf(buf, sizeof(buf), "c3d::%s<4, false, 4, false, 16, true>", kernel);
+            if (k.step.chunk) {               // k_*_chunked<pot, gen, rpw, tile rows, wide, CHUNK> (c3d_chunked.h)
+                if (k.step.wide) snprintf(buf, sizeof(buf), "c3d::%s_chunked<4, false, 4, 16, true, %d>", kernel, k.step.chunk);
+                else snprintf(buf, sizeof(buf), "c3d::%s_chunked<%d, %s, %d, 8, false, %d>", kernel, k.step.pot, tf(k.step.gen), k.step.rpw, k.step.chunk);
+            } else if (k.step.wide) snprintf(buf, sizeof(buf), "c3d::%s<4, false, 4, false, 16, true>", kernel);
             else snprintf(buf, sizeof(buf), "c3d::%s<%d, %s, %d, %s, 8, false>", kernel, k.step.pot, tf(k.step.gen), k.step.rpw, tf(k.step.nc));
             break;
         }
@@ -1785,7 +1816,8 @@ extern "C" int c3d_eval(c3d_ctx* c, float w_all, float w_vdw, float repel_s, flo
     const c3d::DevModel m = dev_model(c);
     const c3d::DevStep p = dev_step(c, 3, 0.0f, w_all, w_vdw, repel_s, 0.0f);
     if (F) {
-        hipError_t err = c3d::launch_eval_forces(m, p, c->buf, c->parity, c->d_feval, c3d::general_step(m, p), c->eval_rpw, c->stream);
+        hipError_t err = c3d::launch_eval_forces(m, p, c->buf, c->parity, c->d_feval, c3d::general_step(m, p), c->eval_rpw,
+                                                 c3d::column_chunk_for(m, c->column_chunk), c->stream);
         if (err != hipSuccess) return fail(C3D_ERR_HIP, std::string("eval launch: ") + hipGetErrorString(err));
         int rc = get_soa(c, c->d_feval, F);
         if (rc) return rc;

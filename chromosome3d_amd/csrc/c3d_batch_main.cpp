@@ -105,6 +105,7 @@ bool solve_one(c3d_ctx* ctx, const Options& o, Job& job, XcdBroker& gpu) {
     TRY(c3d_parse_if_file(job.path.c_str(), &IF, &n));
     std::vector<double> if_copy(IF, IF + (size_t)n * n);
     c3d_free(IF);
+    if (n > C3D_MAX_BEADS_DEFAULT && n <= C3D_MAX_BEADS_LIMIT) TRY(c3d_set_option(ctx, "max_beads", n));   // (the context's limit follows the job)
     TRY(c3d_set_if_matrix(ctx, if_copy.data(), n, o.alpha, o.K));
     const double t_k1 = now_s();
     std::vector<int32_t> d10((size_t)n * n);

@@ -219,11 +219,20 @@ hipError_t launch_pair_targets(const DevModel& m, const float* tgt, float* tgs2,
 
 static size_t step_lds_bytes(const DevModel& m, int tile_rows = kTileRows) { return sizeof(float) * ((size_t)3 * m.npad + 4 * tile_rows + 12); }   // xyz + rowq + the step scalars' hand-over
 
-// the form step_form chose: the narrow k_step<pot, gen, rpw, nc> or the wide one (16 rows a workgroup, four a wave, resident pair targets)
+// the chunked form's launchers (c3d_chunked.h, included below)
+hipError_t launch_step_chunked(const DevModel& m, const DevStep& p, const DevFire& fp, const DevBuffers& b, int par, const StepForm& f, hipStream_t s);
+hipError_t launch_lbfgs_eval_chunked(const DevModel& m, const DevStep& p, const DevBuffers& b, const LbfgsBuffers& lb, int par, int mem,
+                                     const StepForm& f, hipStream_t s);
+hipError_t launch_eval_forces_chunked(const DevModel& m, const DevStep& p, const DevBuffers& b, int parity, float* Fout, bool general_tail,
+                                      int rows_per_wave, int chunk, hipStream_t s);
+
+// the form step_form chose: the narrow k_step<pot, gen, rpw, nc> or the wide one (16 rows a workgroup, four a wave, resident pair targets),
+// staged or chunked
 hipError_t launch_step(const DevModel& m0, const DevStep& p, const DevFire& fp, const DevBuffers& b, int par, const StepForm& f, hipStream_t s) {
     const int q = par ^ 1;
     DevModel m = m0;
     m.tgs2 = f.pairs ? b.tgs2 : nullptr;      // (the kernels that read it)
+    if (f.chunk) return launch_step_chunked(m, p, fp, b, par, f, s);
     if (f.wide) {
         constexpr int TR = 2 * kTileRows;
         const int nwg = (m.ntiles + 1) / 2;
@@ -271,7 +280,8 @@ __global__ __launch_bounds__(64 * kTileRows / ERPW) void k_eval_forces(const Dev
 }
 
 hipError_t launch_eval_forces(const DevModel& m, const DevStep& p, const DevBuffers& b, int parity, float* Fout,
-                              bool general_tail, int rows_per_wave, hipStream_t s) {
+                              bool general_tail, int rows_per_wave, int chunk, hipStream_t s) {
+    if (chunk) return launch_eval_forces_chunked(m, p, b, parity, Fout, general_tail, rows_per_wave, chunk, s);
     const size_t lds = sizeof(float) * (size_t)3 * m.npad;
     const dim3 g = grid_blocks(m);
     static_assert(kEvalRowsPerWave == 4, "the hook's default form is four rows per wave");
@@ -461,6 +471,7 @@ hipError_t launch_if_to_target(const double* IF, int n, int npad, double alpha, 
 }  // namespace c3d
 
 #include "c3d_lbfgs.h"
+#include "c3d_chunked.h"
 
 namespace c3d {
 

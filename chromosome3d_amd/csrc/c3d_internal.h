@@ -120,13 +120,30 @@ inline bool pair_targets_fit(const DevModel& m) { return device_pot(m.noe_pot) =
 // The form of a per-step kernel (k_step, k_lbfgs_eval): k<pot, gen, rpw, nc>, or the wide k<4, false, 4, false, 16, true> — 16 rows a
 // workgroup, four a wave, resident pair targets: problems beyond the multi-step kernel's reach.  Decided once per op: the launch and
 // c3d_step_kernel_name both read it.  Switches: the context's options wide_tiles and pair_targets, and whether tgs2 is built.
+//
+// The column source (chunk): 0 = the replica's whole coordinate array staged in LDS (k_step, k_lbfgs_eval, k_eval_forces), else the
+// chunked form with that many columns per pass (k_step_chunked, ...: c3d_chunked.h) — column_chunk_for decides it.
 struct StepForm {
     int pot;
     bool gen;
     int rpw;
     bool nc, pairs, wide;            // pairs: DevModel::tgs2 passed to the kernel
+    int chunk;
 };
-inline StepForm step_form(const DevModel& m, const DevStep& p, bool wide_tiles, bool pair_targets, bool tgs2_built) {
+// The staged kernels put 3 npad floats of coordinates in LDS: up to the 64 KB a launch gets without opting in (n <= 5120, 61 440 B plus
+// the tile's own few hundred bytes).  Beyond that the chunked form runs, kDefaultColumnChunk columns a pass: the fastest CHUNK at every
+// size measured, 4096 .. 16384 beads (24 KB of buffers, LDS no limit on the workgroups of a CU; profiles/r08_large_maps.md).
+constexpr int kMaxStagedCols = 5120;
+constexpr int kDefaultColumnChunk = 1024;
+inline bool column_chunk_valid(int chunk) { return chunk == 256 || chunk == 1024 || chunk == 2048; }   // the instantiated set
+// option = the context's column_chunk: 0 = the library's choice, else that CHUNK wherever a chunked form exists.  Layouts with a narrow
+// last block (n <= 1024, whose coordinates always fit) have none.
+inline int column_chunk_for(const DevModel& m, int option) {
+    if (!(m.wl == 4 && m.nleft == 0)) return 0;
+    if (option > 0) return option;
+    return m.npad <= kMaxStagedCols ? 0 : kDefaultColumnChunk;
+}
+inline StepForm step_form(const DevModel& m, const DevStep& p, bool wide_tiles, bool pair_targets, bool tgs2_built, int column_chunk) {
     StepForm f;
     f.pot = device_pot(m.noe_pot);
     f.rpw = m.rpw == 1 || m.rpw == 2 ? m.rpw : 4;
@@ -134,6 +151,7 @@ inline StepForm step_form(const DevModel& m, const DevStep& p, bool wide_tiles, 
     f.nc = !(m.wl == 4 && m.nleft == 0);
     f.pairs = !f.gen && pair_targets_fit(m) && tgs2_built;
     f.wide = wide_tiles && pair_targets && f.pairs && m.npad > 1024;
+    f.chunk = column_chunk_for(m, column_chunk);
     return f;
 }
 // the symmetric-tile kernel's RS1 (k_pairs_sym: c3d_sym.hip)
@@ -142,7 +160,7 @@ inline bool sym_rs1(const DevModel& m) { return m.rs == 1.0f; }
 // host-callable launchers (defined in c3d_device.hip)
 hipError_t launch_step(const DevModel& m, const DevStep& p, const DevFire& fp, const DevBuffers& b, int parity, const StepForm& f, hipStream_t s);
 hipError_t launch_eval_forces(const DevModel& m, const DevStep& p, const DevBuffers& b, int parity, float* Fout,
-                              bool general_tail, int rows_per_wave, hipStream_t s);
+                              bool general_tail, int rows_per_wave, int chunk, hipStream_t s);   // chunk: column_chunk_for
 hipError_t launch_energy(const DevModel& m, const DevStep& p, const DevBuffers& b, int parity, float s_noe,
                          float k_rep, double rep_r2, hipStream_t s);
 hipError_t launch_centre(const DevModel& m, const DevBuffers& b, int parity, hipStream_t s);

@@ -263,6 +263,7 @@ hipError_t launch_lbfgs_eval(const DevModel& m0, const DevStep& p, const DevBuff
     const int q = par ^ 1;
     DevModel m = m0;
     m.tgs2 = f.pairs ? b.tgs2 : nullptr;      // (the kernels that read it)
+    if (f.chunk) return launch_lbfgs_eval_chunked(m, p, b, lb, par, mem, f, s);
     if (f.wide) {
         constexpr int TR = 2 * kTileRows;
         const int nwg = (m.ntiles + 1) / 2;

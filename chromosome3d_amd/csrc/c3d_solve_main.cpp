@@ -124,6 +124,8 @@ int main(int argc, char** argv) {
     double* IF = nullptr;
     if (!if_path.empty()) {
         CHECK(c3d_parse_if_file(if_path.c_str(), &IF, &n));
+        // a matrix beyond the default limit is what the user asked for: raise the limit to it (the library refuses beyond its ceiling)
+        if (n > C3D_MAX_BEADS_DEFAULT && n <= C3D_MAX_BEADS_LIMIT) CHECK(c3d_set_option(ctx, "max_beads", n));
         CHECK(c3d_set_if_matrix(ctx, IF, n, alpha, K));
         std::vector<int32_t> d10((size_t)n * n);
         CHECK(c3d_get_dist10(ctx, d10.data()));
@@ -137,6 +139,7 @@ int main(int argc, char** argv) {
         c3d_free(pi); c3d_free(pj); c3d_free(pt);
         n = n_beads;
         for (int k = 0; k < R; ++k) { if (ri[k] > n) n = ri[k]; if (rj[k] > n) n = rj[k]; }
+        if (n > C3D_MAX_BEADS_DEFAULT && n <= C3D_MAX_BEADS_LIMIT) CHECK(c3d_set_option(ctx, "max_beads", n));
         CHECK(c3d_set_restraints(ctx, n, R, ri.data(), rj.data(), rt.data()));
     }
 

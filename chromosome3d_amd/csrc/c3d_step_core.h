@@ -450,10 +450,21 @@ __device__ __forceinline__ void pair_targets_prefetch(const DevModel& m, int row
 // m.nleft == 0: every N > 1024 among them) carries none of the narrow-column code — the per-step kernel is launched once per SA
 // step and pays for every kilobyte of code it drags along (N = 2500: 26.5 against 27.2 us per step)
 // PACKED4 = the packed form also at four rows per wave (two row pairs: the wide-tile step kernel of large problems, NC = false)
-template <int POT, bool GEN, int RPW, bool NC = true, bool PACKED = true, bool PACKED4 = false>
-__device__ __forceinline__ void tile_forces(const DevModel& m, const DevStep& p, const float* __restrict__ tgt,
-                                            const float* xs, const float* ys, const float* zs, int row0, int lane,
-                                            float4 (&tv)[RPW], float& Fx, float& Fy, float& Fz) {
+// Where the pair loop reads its COLUMN coordinates (the row side — a row's own coordinates, its chain neighbours — always comes from xs,
+// ys, zs): COLS::enter(jb) runs at the top of column block jb, COLS::load(jb, lane, ...) reads the lane's four columns of it.
+// ColsStaged = the replica's whole coordinate array staged in LDS: the loops read the columns from xs, ys, zs as they always did (the
+// existing kernels' machine code stays byte for byte what it was: tools/isa_compare.py).  The chunked form (c3d_chunked.h) stages
+// CHUNK columns at a time; it exists for NC = false only.
+struct ColsStaged {
+    static constexpr bool kStaged = true;      // the loops read xs, ys, zs themselves, as they always did
+    __device__ __forceinline__ void enter(int) const {}
+    __device__ __forceinline__ void load(int, int, float4&, float4&, float4&) const {}
+};
+template <int POT, bool GEN, int RPW, bool NC, bool PACKED, bool PACKED4, class COLS>
+__device__ __forceinline__ void tile_forces_cols(const DevModel& m, const DevStep& p, const float* __restrict__ tgt,
+                                                 const float* xs, const float* ys, const float* zs, const COLS& cols, int row0, int lane,
+                                                 float4 (&tv)[RPW], float& Fx, float& Fy, float& Fz) {
+    static_assert(COLS::kStaged || !NC, "the narrow last block and the left-over columns read the staged arrays");
     float fx[RPW], fy[RPW], fz[RPW];
     float xi[RPW], yi[RPW], zi[RPW];
 #pragma unroll
@@ -489,6 +500,7 @@ __device__ __forceinline__ void tile_forces(const DevModel& m, const DevStep& p,
         }
         const float2v on2 = float2v{on, on};
         for (int jb = 0; jb < nfull; ++jb) {
+            cols.enter(jb);
             float4 t2[RPW];
             const int jn = min(jb + 2, nblk - 1);           // the last blocks re-read the last one (in bounds)
             if (pairs) pair_targets_prefetch<RPW>(m, row0, lane, jn, t2);
@@ -496,10 +508,11 @@ __device__ __forceinline__ void tile_forces(const DevModel& m, const DevStep& p,
 #pragma unroll
                 for (int r = 0; r < RPW; ++r) t2[r] = *reinterpret_cast<const float4*>(trow[r] + 256 * jn);
             }
-            const int j = 256 * jb + 4 * lane;
-            const float4 xj = *reinterpret_cast<const float4*>(xs + j);
-            const float4 yj = *reinterpret_cast<const float4*>(ys + j);
-            const float4 zj = *reinterpret_cast<const float4*>(zs + j);
+            float4 xj, yj, zj;
+            if constexpr (COLS::kStaged) {
+                const int j = 256 * jb + 4 * lane;
+                xj = *reinterpret_cast<const float4*>(xs + j); yj = *reinterpret_cast<const float4*>(ys + j); zj = *reinterpret_cast<const float4*>(zs + j);
+            } else cols.load(jb, lane, xj, yj, zj);
             const float2v x01 = float2v{xj.x, xj.y}, x23 = float2v{xj.z, xj.w}, y01 = float2v{yj.x, yj.y}, y23 = float2v{yj.z, yj.w};
             const float2v z01 = float2v{zj.x, zj.y}, z23 = float2v{zj.z, zj.w};
             if (pairs) {
@@ -544,12 +557,14 @@ __device__ __forceinline__ void tile_forces(const DevModel& m, const DevStep& p,
         }
         const float2v on2 = float2v{m.inv_rs, m.inv_rs};
         for (int jb = 0; jb < nfull; ++jb) {
+            cols.enter(jb);
             float4 t1[RPW];
             pair_targets_prefetch<RPW>(m, row0, lane, min(jb + 1, nblk - 1), t1);      // the last block re-reads itself (in bounds)
-            const int j = 256 * jb + 4 * lane;
-            const float4 xj = *reinterpret_cast<const float4*>(xs + j);
-            const float4 yj = *reinterpret_cast<const float4*>(ys + j);
-            const float4 zj = *reinterpret_cast<const float4*>(zs + j);
+            float4 xj, yj, zj;
+            if constexpr (COLS::kStaged) {
+                const int j = 256 * jb + 4 * lane;
+                xj = *reinterpret_cast<const float4*>(xs + j); yj = *reinterpret_cast<const float4*>(ys + j); zj = *reinterpret_cast<const float4*>(zs + j);
+            } else cols.load(jb, lane, xj, yj, zj);
             const float2v x01 = float2v{xj.x, xj.y}, x23 = float2v{xj.z, xj.w}, y01 = float2v{yj.x, yj.y}, y23 = float2v{yj.z, yj.w};
             const float2v z01 = float2v{zj.x, zj.y}, z23 = float2v{zj.z, zj.w};
 #pragma unroll
@@ -572,15 +587,17 @@ __device__ __forceinline__ void tile_forces(const DevModel& m, const DevStep& p,
     }
     const PairK k = pair_k(m, p);
     for (int jb = 0; jb < nfull; ++jb) {
+        cols.enter(jb);
         float4 tn[RPW];
         const int jn = jb + 1 < nblk ? jb + 1 : jb;     // the last block re-reads itself (in bounds)
 #pragma unroll
         for (int r = 0; r < RPW; ++r)      // always the four-column form (right unless the next block is a narrow last one: redone below)
             tn[r] = *reinterpret_cast<const float4*>(tgt + (size_t)min(row0 + r, m.n - 1) * m.npad + 256 * jn + 4 * lane);
-        const int j = 256 * jb + 4 * lane;
-        const float4 xj = *reinterpret_cast<const float4*>(xs + j);
-        const float4 yj = *reinterpret_cast<const float4*>(ys + j);
-        const float4 zj = *reinterpret_cast<const float4*>(zs + j);
+        float4 xj, yj, zj;
+        if constexpr (COLS::kStaged) {
+            const int j = 256 * jb + 4 * lane;
+            xj = *reinterpret_cast<const float4*>(xs + j); yj = *reinterpret_cast<const float4*>(ys + j); zj = *reinterpret_cast<const float4*>(zs + j);
+        } else cols.load(jb, lane, xj, yj, zj);
 #pragma unroll
         for (int r = 0; r < RPW; ++r)
             pair_quad<POT, GEN>(m, p, k, pair_b<GEN>(m, tv[r]), pair_a<GEN>(m, p, tv[r]), xi[r], yi[r], zi[r], xj, yj, zj, fx[r], fy[r], fz[r]);
@@ -597,6 +614,13 @@ __device__ __forceinline__ void tile_forces(const DevModel& m, const DevStep& p,
             pair_quad_w<POT, GEN>(m, p, k, width, pair_b<GEN>(m, tv[r]), pair_a<GEN>(m, p, tv[r]), xi[r], yi[r], zi[r], xj, yj, zj, fx[r], fy[r], fz[r]);
     }
     reduce_and_chain<POT, RPW, GEN, NC>(m, p, tgt, xs, ys, zs, row0, lane, fx, fy, fz, Fx, Fy, Fz);
+}
+// the staged form: rows and columns from the same LDS arrays
+template <int POT, bool GEN, int RPW, bool NC = true, bool PACKED = true, bool PACKED4 = false>
+__device__ __forceinline__ void tile_forces(const DevModel& m, const DevStep& p, const float* __restrict__ tgt,
+                                            const float* xs, const float* ys, const float* zs, int row0, int lane,
+                                            float4 (&tv)[RPW], float& Fx, float& Fy, float& Fz) {
+    tile_forces_cols<POT, GEN, RPW, NC, PACKED, PACKED4>(m, p, tgt, xs, ys, zs, ColsStaged{}, row0, lane, tv, Fx, Fy, Fz);
 }
 
 // clamp form with the per-pair constants resident for a whole launch (cluster kernel, compute waves): tv = pair_b in

@@ -44,7 +44,11 @@ def make_stages(rows):
 
 
 class Solver:
-    """c3d_ctx wrapper.  Raises lib.C3DError when no gfx950 device / library is available."""
+    """c3d_ctx wrapper.  Raises lib.C3DError when no gfx950 device / library is available.
+
+    Matrices of up to 5120 beads are accepted by default; set_option("max_beads", n) before set_if_matrix / set_restraints raises the
+    limit up to 16384 (the per-step kernels then run in their chunked form).  That is consent to the memory: about 8 n npad bytes stay
+    resident per context (2.1 GB at 16384) and K1 takes 21 n^2 bytes more while it runs.  precision 64 keeps its 2560-bead limit."""
 
     def __init__(self, device=0):
         self._L = _l.load()

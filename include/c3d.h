@@ -149,11 +149,23 @@ int c3d_set_schedule(c3d_ctx* ctx, const c3d_stage* stages, int n_stages, const 
  *                   (a device that does not expose 8 XCDs gets no cluster plan; a launch that ends without its completion
  *                   mark or with a time-out is re-run on the per-step path)
  *   precision       32 (default) or 64: the fp64 reference kernels (c3d_f64.hip); call before c3d_init_replicas.  The fp64 step stages a
- *                   replica's coordinates in LDS: at most 2560 beads (c3d_init_replicas returns C3D_ERR_INVALID beyond).  The fp32 kernels
- *                   stage 3 * npad floats of a replica in LDS: at most 5120 beads (c3d_set_if_matrix / c3d_set_restraints refuse more).
+ *                   replica's coordinates in LDS: at most 2560 beads (c3d_init_replicas returns C3D_ERR_INVALID beyond).  The fp32 path takes
+ *                   up to 5120 beads by default and up to 16384 behind max_beads (below); c3d_set_if_matrix / c3d_set_restraints refuse more.
  *                   64 and a schedule with a stage of kind 8 exclude each other: whichever call comes second returns C3D_ERR_INVALID
+ *   max_beads       5120 (default) .. 16384 (C3D_MAX_BEADS_DEFAULT .. C3D_MAX_BEADS_LIMIT): the largest matrix c3d_set_if_matrix and
+ *                   c3d_set_restraints accept; set it before them (other values: C3D_ERR_INVALID).  Raising it is consent to the memory of a
+ *                   large matrix: about 8 n npad bytes per context stay resident (targets and the pair targets; npad = n rounded up to
+ *                   256): 0.55 GB at 8192 beads, 2.1 GB at 16384; c3d_set_if_matrix takes 21 n^2 bytes more while it runs (the matrix
+ *                   and its powers in fp64, the integer tenths, flags: 5.6 GB at 16384) and the host keeps the n^2 integer tenths (1 GB).
+ *                   Beyond 5120 beads the fp32 step kernels run in their chunked form (below).  Not beyond 5120: precision 64 (2560),
+ *                   symmetric 1 (c3d_init_replicas refuses it), c3d_embed_replicas (its own LDS limit, about 4550 beads)
+ *   column_chunk    0 (default): where the per-step kernels read a column's coordinates — 0 = the library's choice: the replica's whole
+ *                   coordinate array staged in LDS while it fits (n <= 5120: exactly the kernels of earlier releases), beyond that the
+ *                   chunked form, which streams 1024 columns at a time through two LDS buffers; 256, 1024 or 2048 = the chunked
+ *                   form with that many columns a pass at every n > 1024 (smaller problems have a narrow last column block and stay
+ *                   staged).  Same bits either way (test and measurement knob)
  *   symmetric       1: symmetric-tile kernels for large N (c3d_sym.hip; opt-in); call before c3d_init_replicas.  Not for the L-BFGS steps of
- *                   a kind-8 stage: they run their own kernels
+ *                   a kind-8 stage: they run their own kernels.  At most 5120 beads
  *   eval_rows_per_wave  4 (default) / 2 / -2: form of the forces hook (c3d_eval_forces) — four rows per wave with the scalar pair term; 2 = two
  *                   rows per wave, the step kernels' code (shipped potential: the packed pair term); -2 = two rows per wave, scalar pair
  *                   term.  2 and -2 return the same bits (a -m gpu test); test knob
@@ -183,6 +195,9 @@ int c3d_set_schedule(c3d_ctx* ctx, const c3d_stage* stages, int n_stages, const 
  *   spin_wait_us    how long c3d_run_steps watches the completion mark a multi-step launch writes into host-mapped memory before it
  *                   falls back to hipStreamSynchronize (default 400; 0 = always synchronise).  Results are untouched by it. */
 int c3d_set_option(c3d_ctx* ctx, const char* key, double value);
+/* the option max_beads: its default and its largest value */
+#define C3D_MAX_BEADS_DEFAULT 5120
+#define C3D_MAX_BEADS_LIMIT 16384
 
 /* Process-wide switches, to be set before the first c3d_create (no environment variable is read by the library):
  *   preload         which code objects c3d_create loads before it returns (the library never leaves a load to the runtime's first-launch

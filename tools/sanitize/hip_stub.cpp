@@ -117,7 +117,7 @@ hipError_t preload_f64_unit() { LoadScope l; return load_result(); }
 hipError_t preload_sym_unit() { LoadScope l; return load_result(); }
 
 hipError_t launch_step(const DevModel&, const DevStep&, const DevFire&, const DevBuffers&, int, const StepForm&, hipStream_t) { LaunchScope ls; return hipSuccess; }
-hipError_t launch_eval_forces(const DevModel&, const DevStep&, const DevBuffers&, int, float*, bool, int, hipStream_t) { LaunchScope ls; return hipSuccess; }
+hipError_t launch_eval_forces(const DevModel&, const DevStep&, const DevBuffers&, int, float*, bool, int, int, hipStream_t) { LaunchScope ls; return hipSuccess; }
 hipError_t launch_energy(const DevModel& m, const DevStep&, const DevBuffers& b, int, float, float, double, hipStream_t) {
     LaunchScope ls;
     for (int r = 0; r < m.nrep; ++r) { b.E[4 * r] = 1000.0 + 7.0 * ((r * 5) % m.nrep); b.E[4 * r + 1] = 1.0; b.E[4 * r + 2] = 2.0; b.E[4 * r + 3] = 0.0; }   // distinct "energies": c3d_rank has something to order
