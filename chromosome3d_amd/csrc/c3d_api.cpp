@@ -1288,7 +1288,7 @@ extern "C" int c3d_set_option(c3d_ctx* c, const char* key, double value) {
 }
 
 // The largest matrix a context accepts: kDefaultMaxBeads unless the option max_beads raises it, up to kMaxBeadsLimit.  Up to
-// c3d::kMaxStagedCols the per-step kernels stage a replica's coordinates in LDS; beyond, they run in the chunked form (c3d_chunked.h).
+// c3d::kMaxStagedCols the per-step kernels stage a replica's coordinates in LDS; beyond, they run in the chunked form (ColsChunked, c3d_step_core.h).
 // The default stays where the staged form ends: a larger matrix needs ~8 n npad bytes per context (targets and pair targets) and K1's
 // transient copies of the matrix, which the caller agrees to by raising the limit.
 static constexpr int kDefaultMaxBeads = C3D_MAX_BEADS_DEFAULT;
@@ -1798,7 +1798,7 @@ extern "C" const char* c3d_step_kernel_name(const c3d_ctx* c) {
         case KernelRecord::STEP:
         case KernelRecord::LBFGS_EVAL: {      // (after an L-BFGS step: its force pass, k_lbfgs_move follows it)
             const char* kernel = k.family == KernelRecord::STEP ? "k_step" : "k_lbfgs_eval";
-            if (k.step.chunk) {               // k_*_chunked<pot, gen, rpw, tile rows, wide, CHUNK> (c3d_chunked.h)
+            if (k.step.chunk) {               // k_*_chunked<pot, gen, rpw, tile rows, wide, CHUNK>
                 if (k.step.wide) snprintf(buf, sizeof(buf), "c3d::%s_chunked<4, false, 4, 16, true, %d>", kernel, k.step.chunk);
                 else snprintf(buf, sizeof(buf), "c3d::%s_chunked<%d, %s, %d, 8, false, %d>", kernel, k.step.pot, tf(k.step.gen), k.step.rpw, k.step.chunk);
             } else if (k.step.wide) snprintf(buf, sizeof(buf), "c3d::%s<4, false, 4, false, 16, true>", kernel);

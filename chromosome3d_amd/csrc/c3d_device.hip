@@ -2,7 +2,8 @@
 //
 //   K1  k_if_pow_sum / k_if_quantise   IF -> target distance      (chromosome3D.pl:130-161, 181-206)
 //   K2  tile_forces<>                  all-pairs NOE-style restraint + repel force for a tile of
-//                                      rows, bead xyz staged in LDS, wave64 butterfly reduction
+//                                      rows, bead xyz in LDS (staged whole or chunk by chunk: the
+//                                      column sources of c3d_step_core.h), wave64 butterfly reduction
 //   K3  k_step<> (MD kinds)            K2 + leap-frog update, Berendsen / velocity-rescale
 //                                      thermostat, COM removal    (deck :1646-1700, :1729-1782)
 //   K4  k_step<> (FIRE kinds)          K2 + FIRE minimiser update (deck :1790-1803, L-BFGS there)
@@ -10,6 +11,9 @@
 //   K6  k_energy                       fp64 energies per replica  (REMARK noe, :602-618)
 //       (assessment / Spearman scoring of resident replicas: c3d_score.hip)
 //
+// K3/K4, K4b's evaluation and the forces hook each have two entry points over one body (c3d_*_body.inc): the staged form (k_step, ...)
+// copies a replica's whole coordinate array into LDS, up to n = 5120; the chunked form (k_step_chunked, ..., NC = false only) streams the
+// columns through two LDS buffers of CHUNK columns and reads the row side from global memory, up to n = 16384.
 // One launch = one SA step for every replica of a group.  A workgroup (kTileRows / RPW waves, RPW
 // rows per wave; 4 waves x 2 rows by default) owns kTileRows = 8 consecutive rows of one replica's
 // N x N pair matrix, lanes run along the columns, 4 columns per lane per block; the kernel boundary is the only inter-workgroup
@@ -46,12 +50,14 @@ __device__ __forceinline__ bool block_to_tile(const DevModel& m, int& tile, int&
     tile = blockIdx.z * 8 + blockIdx.x;
     return tile < m.ntiles;
 }
-inline dim3 grid_blocks(const DevModel& m) { return dim3(8, m.nrep_g, (m.ntiles + 7) / 8); }
+// (tiles = 8-row tiles a workgroup owns: 2 in the wide form)
+inline dim3 grid_blocks(const DevModel& m, int tiles = 1) { return dim3(8, m.nrep_g, ((m.ntiles + tiles - 1) / tiles + 7) / 8); }
 
 
 // ---------------------------------------------------------------------------------------------
 // K3/K4: one SA step (MD leap-frog or FIRE) for all replicas.
-// Workgroup = kTileRows / RPW waves; LDS: xs[npad] ys[npad] zs[npad] | wpart[WAVES][4].
+// Workgroup = kTileRows / RPW waves; LDS: the coordinates (xs[npad] ys[npad] zs[npad], or the two chunk buffers) | rowq[TR][4] | the
+// step scalars' hand-over [12].
 // Latency plan of one workgroup (the kernel is latency-, not bandwidth-bound at N ~ 500):
 //   1. issue every independent global load up front: first target block of the wave's rows, the
 //      previous step's partial sums, own-row velocities, the bead coordinates
@@ -66,130 +72,25 @@ inline dim3 grid_blocks(const DevModel& m) { return dim3(8, m.nrep_g, (m.ntiles 
 #ifndef C3D_SHARE_SCALARS
 #define C3D_SHARE_SCALARS 1      // 0: measurement builds in which every wave derives the step's scalars for itself (rounds 1-4)
 #endif
+
 template <int POT, bool GEN, int RPW, bool NC, int TR = kTileRows, bool WIDE = false>
 __global__ __launch_bounds__(64 * TR / RPW) __attribute__((amdgpu_waves_per_eu(WIDE ? 4 : 1))) void k_step(
     const float* __restrict__ pin, const float* __restrict__ xin, const float* __restrict__ tgt,
     const float* __restrict__ vin, const float* __restrict__ vinit, const FireState* __restrict__ sin,
     float* __restrict__ xout, float* __restrict__ vout, float* __restrict__ pout, FireState* __restrict__ sout,
     const DevModel m, const DevStep p, const DevFire fp) {
-    constexpr int WAVES = TR / RPW;
-    constexpr int BLOCK = 64 * WAVES;
-    constexpr int TILES = TR / kTileRows;       // 8-row tiles of this workgroup
-    static_assert(TR % kTileRows == 0 && TILES >= 1 && TILES <= 2, "a workgroup owns one or two 8-row tiles");
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    C3D_STAMP(6);      // before any kernel argument beyond the preloaded ones is needed
-    {   // The 280-byte kernarg block spans five 64-byte lines and the scalar cache is cold at every launch: the
-        // compiler fetches the arguments where they are first used, one ~550-cycle miss after the other.  Touch
-        // the four lines beyond the preloaded pointers at once; the later loads then hit.
-        static_assert(10 * sizeof(void*) + sizeof(DevModel) + sizeof(DevStep) + sizeof(DevFire) >= 0x100 + 4,
-                      "the touched offsets must lie inside the explicit kernel arguments");
-        static_assert(10 * sizeof(void*) + sizeof(DevModel) + sizeof(DevStep) + sizeof(DevFire) <= 0x140,
-                      "a sixth 64-byte line of kernel arguments needs a sixth touch");
-        const auto ka = __builtin_amdgcn_kernarg_segment_ptr();
-        unsigned t0, t1, t2, t3;
-        asm volatile("s_load_dword %0, %4, 0x40\n\ts_load_dword %1, %4, 0x80\n\ts_load_dword %2, %4, 0xc0\n\ts_load_dword %3, %4, 0x100\n\ts_waitcnt lgkmcnt(0)"
-                     : "=&s"(t0), "=&s"(t1), "=&s"(t2), "=&s"(t3) : "s"(ka) : "memory");
-    }
-    int tile, rep;
-    if (!block_to_tile(m, tile, rep)) return;   // (tile = the workgroup's number among those of its replica)
-    tile *= TILES;                              // its first 8-row tile
-    if (tile >= m.ntiles) return;
-    C3D_STAMP(0);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int npad = m.npad;
-    float* xs = smem;
-    float* ys = smem + npad;
-    float* zs = smem + 2 * npad;
-    float* rowq = smem + 3 * npad;              // [TR][4] per-row contributions to the replica sums
-    const size_t roff = (size_t)rep * 3 * npad;
-    const int row0 = tile * kTileRows + wave * RPW;
-    const int row = row0 + lane;                // the row this lane finishes (lanes < RPW only)
-    const bool fin_lane = lane < RPW;
-    const bool finisher = fin_lane && row < m.n;
-    const size_t ix = roff + row, iy = ix + npad, iz = iy + npad;
-    const bool needs_partials = p.kind == 0 || p.kind == 1 || p.kind == 2 || p.kind == 5;
-
-    // ---- 1. every independent global load is issued before anything waits -------------------
-    if (m.stage_dma) lds_dma_copy<BLOCK>(xin + roff, smem, 3 * npad, tid);
-    else for (int b = 4 * tid; b < 3 * npad; b += 4 * BLOCK) *reinterpret_cast<float4*>(smem + b) = *reinterpret_cast<const float4*>(xin + roff + b);
-    // the first partial-sum entry of every lane is only ISSUED here: adding it up right away would park the wave
-    // on this cold load before the target and velocity loads below are even on their way
-    const float4* pp = reinterpret_cast<const float4*>(pin) + (size_t)rep * m.ntiles;
-    float4 q0 = make_float4(0, 0, 0, 0);
-    if (needs_partials && lane < m.ntiles && (!WIDE || !C3D_SHARE_SCALARS || wave == 0)) q0 = pp[lane];      // (wave 0 alone forms the replica sums, below)
-    float4 tv[RPW];
-    if (p.kind != 4) {
-        if (pair_targets_in_use<POT, GEN, RPW, NC>(m)) pair_targets_prefetch(m, row0, lane, 0, tv);
-        else tile_prefetch<RPW, NC>(m, tgt, row0, lane, 0, tv);
-    }
-    float vx0 = 0.0f, vy0 = 0.0f, vz0 = 0.0f;
-    if (finisher && p.kind != 3 && p.kind != 6) {
-        const float* vsrc = p.kind == 4 ? vinit : vin;
-        vx0 = vsrc[ix]; vy0 = vsrc[iy]; vz0 = vsrc[iz];
-    }
-    FireState st;
-    st.dt = fp.dt_start; st.alpha = fp.alpha_start; st.npos = 0; st.pad = 0;
-    if (p.kind == 2 || p.kind == 5) st = sin[rep];
-    // WIDE (large N: hundreds of tile sums): ONE wave of the workgroup forms the replica sums and the step's scalars and hands them to the
-    // others through LDS across the barrier that waits for the coordinates anyway — the same values, the same bits (every wave used to
-    // derive them for itself: ~90 of a wave's ~2200 VALU instructions per step at N = 2500, three quarters of them redundant)
-    constexpr bool SHARE = WIDE && C3D_SHARE_SCALARS;       // (narrow form, N = 455 x 20, same box: 6.92 us per step shared against 6.78 per wave — its
-                                                            //  waves would wait at the barrier for a chain they used to run beside their own loads)
-    float* const scb = rowq + 4 * TR;           // [12]: StepScalars (6) + FireState (4)
-    const bool sums_here = !SHARE || wave == 0;
-    float4 psum = make_float4(0, 0, 0, 0);
-    if (needs_partials && sums_here) {   // one float4 per tile; ntiles <= 64 for N <= 512
-        psum.x += q0.x; psum.y += q0.y; psum.z += q0.z; psum.w += q0.w;
-        for (int t = lane + 64; t < m.ntiles; t += 64) {
-            const float4 q = pp[t];
-            psum.x += q.x; psum.y += q.y; psum.z += q.z; psum.w += q.w;
-        }
-    }
-    C3D_STAMP(1);
-
-    // ---- 2. scalars per wave (no barrier of their own; every wave ends with the same values) -----------------
-    StepScalars sc;
-    sc.lam = 1.0f; sc.cmx = sc.cmy = sc.cmz = 0.0f; sc.keep = 0.0f; sc.mix = 0.0f;
-    if (sums_here) {
-        if (needs_partials) psum = wave_sum4(psum);
-        sc = step_scalars(m, p, fp, psum, st);
-        if ((p.kind == 2 || p.kind == 3 || p.kind == 5 || p.kind == 6) && tile == 0 && tid == 0) sout[rep] = st;
-        if constexpr (SHARE) {
-            if (lane == 0) {
-                scb[0] = sc.lam; scb[1] = sc.cmx; scb[2] = sc.cmy; scb[3] = sc.cmz; scb[4] = sc.keep; scb[5] = sc.mix;
-                scb[6] = st.dt; scb[7] = st.alpha; reinterpret_cast<int*>(scb)[8] = st.npos; reinterpret_cast<int*>(scb)[9] = st.pad;
-            }
-        }
-    }
-    C3D_STAMP(2);
-    __syncthreads();
-    if constexpr (SHARE) {
-        if (!sums_here) {
-            sc.lam = scb[0]; sc.cmx = scb[1]; sc.cmy = scb[2]; sc.cmz = scb[3]; sc.keep = scb[4]; sc.mix = scb[5];
-            st.dt = scb[6]; st.alpha = scb[7]; st.npos = reinterpret_cast<const int*>(scb)[8]; st.pad = reinterpret_cast<const int*>(scb)[9];
-        }
-    }
-    C3D_STAMP(3);
-
-    // ---- 3. K2: pair forces for this wave's rows ---------------------------------------------
-    float Fx = 0.0f, Fy = 0.0f, Fz = 0.0f;
-    if (p.kind != 4) tile_forces<POT, GEN, RPW, NC, true, WIDE>(m, p, tgt, xs, ys, zs, row0, lane, tv, Fx, Fy, Fz);
-
-    C3D_STAMP(4);
-    // ---- 4. epilogue: lanes 0..RPW-1 finish one row each --------------------------------------
-    float4 q = make_float4(0, 0, 0, 0);   // this lane's contribution to the tile's partial sums
-    if (finisher) {
-        float vx, vy, vz, xn, yn, zn;
-        finish_row(m, p, fp, sc, st, Fx, Fy, Fz, xs[row], ys[row], zs[row], vx0, vy0, vz0, xn, yn, zn, vx, vy, vz, q);
-        xout[ix] = xn; xout[iy] = yn; xout[iz] = zn;
-        vout[ix] = vx; vout[iy] = vy; vout[iz] = vz;
-    }
-    // tile partial sums: the fixed tree of tile_sum8 over the eight rows (deterministic, the cluster kernel's order)
-    if (fin_lane) reinterpret_cast<float4*>(rowq)[row - tile * kTileRows] = q;
-    __syncthreads();
-    if (tid < TILES && tile + tid < m.ntiles)
-        reinterpret_cast<float4*>(pout)[(size_t)rep * m.ntiles + tile + tid] = tile_sum8(reinterpret_cast<const float4*>(rowq) + kTileRows * tid);
-    C3D_STAMP(5);
+    using COLS = ColsStaged;
+#include "c3d_step_body.inc"
+}
+template <int POT, bool GEN, int RPW, int TR, bool WIDE, int CHUNK>
+__global__ __launch_bounds__(64 * TR / RPW) __attribute__((amdgpu_waves_per_eu(WIDE ? 4 : 1))) void k_step_chunked(
+    const float* __restrict__ pin, const float* __restrict__ xin, const float* __restrict__ tgt,
+    const float* __restrict__ vin, const float* __restrict__ vinit, const FireState* __restrict__ sin,
+    float* __restrict__ xout, float* __restrict__ vout, float* __restrict__ pout, FireState* __restrict__ sout,
+    const DevModel m, const DevStep p, const DevFire fp) {
+    constexpr bool NC = false;
+    using COLS = ColsChunked<CHUNK, 64 * TR / RPW>;
+#include "c3d_step_body.inc"
 }
 
 #ifdef C3D_STAMPS
@@ -217,34 +118,34 @@ hipError_t launch_pair_targets(const DevModel& m, const float* tgt, float* tgs2,
     return hipGetLastError();
 }
 
-static size_t step_lds_bytes(const DevModel& m, int tile_rows = kTileRows) { return sizeof(float) * ((size_t)3 * m.npad + 4 * tile_rows + 12); }   // xyz + rowq + the step scalars' hand-over
-
-// the chunked form's launchers (c3d_chunked.h, included below)
-hipError_t launch_step_chunked(const DevModel& m, const DevStep& p, const DevFire& fp, const DevBuffers& b, int par, const StepForm& f, hipStream_t s);
-hipError_t launch_lbfgs_eval_chunked(const DevModel& m, const DevStep& p, const DevBuffers& b, const LbfgsBuffers& lb, int par, int mem,
-                                     const StepForm& f, hipStream_t s);
-hipError_t launch_eval_forces_chunked(const DevModel& m, const DevStep& p, const DevBuffers& b, int parity, float* Fout, bool general_tail,
-                                      int rows_per_wave, int chunk, hipStream_t s);
+// dynamic LDS of a per-step kernel: the coordinates (chunk 0: the replica's whole array, 3 npad floats; else the two chunk buffers,
+// 6 chunk floats: COLS::lds_floats) and row_floats of the workgroup's own
+static size_t step_lds_bytes(const DevModel& m, int chunk, size_t row_floats) {
+    return sizeof(float) * ((chunk ? (size_t)6 * chunk : (size_t)3 * m.npad) + row_floats);
+}
 
 // the form step_form chose: the narrow k_step<pot, gen, rpw, nc> or the wide one (16 rows a workgroup, four a wave, resident pair targets),
-// staged or chunked
+// staged (k_step<..., nc>) or chunked (k_step_chunked<..., CHUNK>: nc is false wherever a chunk is chosen)
 hipError_t launch_step(const DevModel& m0, const DevStep& p, const DevFire& fp, const DevBuffers& b, int par, const StepForm& f, hipStream_t s) {
     const int q = par ^ 1;
     DevModel m = m0;
     m.tgs2 = f.pairs ? b.tgs2 : nullptr;      // (the kernels that read it)
-    if (f.chunk) return launch_step_chunked(m, p, fp, b, par, f, s);
-    if (f.wide) {
-        constexpr int TR = 2 * kTileRows;
-        const int nwg = (m.ntiles + 1) / 2;
-        hipLaunchKernelGGL((k_step<4, false, 4, false, TR, true>), dim3(8, m.nrep_g, (nwg + 7) / 8), dim3(64 * TR / 4), step_lds_bytes(m, TR), s,
+    const int tr = f.wide ? 2 * kTileRows : kTileRows;
+    const auto go = [&](auto kernel, int rpw) {      // (LDS: the coordinates, rowq and the step scalars' hand-over)
+        hipLaunchKernelGGL(kernel, grid_blocks(m, tr / kTileRows), dim3(64 * tr / rpw), step_lds_bytes(m, f.chunk, 4 * tr + 12), s,
                            b.P[par], b.X[par], b.tgt, b.V[par], b.Vinit, b.S[par], b.X[q], b.V[q], b.P[q], b.S[q], m, p, fp);
         return hipGetLastError();
-    }
-    return with_pot(f.pot, [&](auto POT) { return with_bool(f.gen, [&](auto GEN) { return with_rpw(f.rpw, [&](auto RPW) { return with_bool(f.nc, [&](auto NC) {
-        hipLaunchKernelGGL((k_step<POT, GEN, RPW, NC>), grid_blocks(m), dim3(64 * kTileRows / RPW), step_lds_bytes(m), s,
-                           b.P[par], b.X[par], b.tgt, b.V[par], b.Vinit, b.S[par], b.X[q], b.V[q], b.P[q], b.S[q], m, p, fp);
-        return hipGetLastError();
-    }); }); }); });
+    };
+    return with_chunk(f.chunk, [&](auto CH) {
+        if (f.wide) {
+            if constexpr (CH == 0) return go(k_step<4, false, 4, false, 2 * kTileRows, true>, 4);
+            else return go(k_step_chunked<4, false, 4, 2 * kTileRows, true, CH>, 4);
+        }
+        return with_pot(f.pot, [&](auto POT) { return with_bool(f.gen, [&](auto GEN) { return with_rpw(f.rpw, [&](auto RPW) {
+            if constexpr (CH == 0) return with_bool(f.nc, [&](auto NC) { return go(k_step<POT, GEN, RPW, NC>, RPW); });
+            else return go(k_step_chunked<POT, GEN, RPW, kTileRows, false, CH>, RPW);
+        }); }); });
+    });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -252,48 +153,38 @@ hipError_t launch_step(const DevModel& m0, const DevStep& p, const DevFire& fp, 
 // ---------------------------------------------------------------------------------------------
 // ERPW = rows per wave: 4 (the scalar pair term, what the force tests against the CPU restatement go through) or, for the shipped potential, 2 in either form of
 // the pair term — packed (pair_term2, the step kernels' code) or scalar: a row's force has the same bits from both, which is what ties
-// the packed form to the scalar one in the test suite (option "eval_rows_per_wave": 4, 2 = packed, -2 = two rows per wave, scalar)
+// the packed form to the scalar one in the test suite (option "eval_rows_per_wave": 4, 2 = packed, -2 = two rows per wave, scalar).
 template <int POT, bool GEN, int ERPW, bool PACKED = true>
 __global__ __launch_bounds__(64 * kTileRows / ERPW) void k_eval_forces(const DevModel m, const DevStep p,
                                                        const float* __restrict__ tgt, const float* __restrict__ xin,
                                                        float* __restrict__ fout) {
-    constexpr int BLOCK = 64 * kTileRows / ERPW;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    int tile, rep;
-    if (!block_to_tile(m, tile, rep)) return;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int npad = m.npad;
-    const size_t roff = (size_t)rep * 3 * npad;
-    const int row0 = tile * kTileRows + wave * ERPW;
-    float4 tv[ERPW];
-    tile_prefetch<ERPW>(m, tgt, row0, lane, 0, tv);
-    for (int b = tid; b < 3 * npad; b += BLOCK) smem[b] = xin[roff + b];
-    __syncthreads();
-    float Fx, Fy, Fz;
-    tile_forces<POT, GEN, ERPW, true, PACKED>(m, p, tgt, smem, smem + npad, smem + 2 * npad, row0, lane, tv, Fx, Fy, Fz);
-    const int row = row0 + lane;
-    if (lane < ERPW && row < m.n) {
-        fout[roff + row] = Fx;
-        fout[roff + npad + row] = Fy;
-        fout[roff + 2 * npad + row] = Fz;
-    }
+    using COLS = ColsStaged;
+#include "c3d_eval_forces_body.inc"
+}
+template <int POT, bool GEN, int ERPW, bool PACKED, int CHUNK>
+__global__ __launch_bounds__(64 * kTileRows / ERPW) void k_eval_forces_chunked(const DevModel m, const DevStep p,
+                                                               const float* __restrict__ tgt, const float* __restrict__ xin,
+                                                               float* __restrict__ fout) {
+    using COLS = ColsChunked<CHUNK, 64 * kTileRows / ERPW>;
+#include "c3d_eval_forces_body.inc"
 }
 
 hipError_t launch_eval_forces(const DevModel& m, const DevStep& p, const DevBuffers& b, int parity, float* Fout,
                               bool general_tail, int rows_per_wave, int chunk, hipStream_t s) {
-    if (chunk) return launch_eval_forces_chunked(m, p, b, parity, Fout, general_tail, rows_per_wave, chunk, s);
-    const size_t lds = sizeof(float) * (size_t)3 * m.npad;
-    const dim3 g = grid_blocks(m);
     static_assert(kEvalRowsPerWave == 4, "the hook's default form is four rows per wave");
-    return with_pot(m.noe_pot, [&](auto POT) { return with_bool(general_tail, [&](auto GEN) {
+    const auto go = [&](auto kernel, int erpw) {
+        hipLaunchKernelGGL(kernel, grid_blocks(m), dim3(64 * kTileRows / erpw), step_lds_bytes(m, chunk, 0), s, m, p, b.tgt, b.X[parity], Fout);
+        return hipGetLastError();
+    };
+    return with_chunk(chunk, [&](auto CH) { return with_pot(m.noe_pot, [&](auto POT) { return with_bool(general_tail, [&](auto GEN) {
         if constexpr (POT == 4 && !GEN)
             if (rows_per_wave == 2 || rows_per_wave == -2) return with_bool(rows_per_wave == 2, [&](auto PACKED) {
-                hipLaunchKernelGGL((k_eval_forces<4, false, 2, PACKED>), g, dim3(64 * kTileRows / 2), lds, s, m, p, b.tgt, b.X[parity], Fout);
-                return hipGetLastError();
+                if constexpr (CH == 0) return go(k_eval_forces<4, false, 2, PACKED>, 2);
+                else return go(k_eval_forces_chunked<4, false, 2, PACKED, CH>, 2);
             });
-        hipLaunchKernelGGL((k_eval_forces<POT, GEN, 4>), g, dim3(kEvalBlock), lds, s, m, p, b.tgt, b.X[parity], Fout);
-        return hipGetLastError();
-    }); });
+        if constexpr (CH == 0) return go(k_eval_forces<POT, GEN, 4>, 4);
+        else return go(k_eval_forces_chunked<POT, GEN, 4, true, CH>, 4);
+    }); }); });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -471,7 +362,6 @@ hipError_t launch_if_to_target(const double* IF, int n, int npad, double alpha, 
 }  // namespace c3d
 
 #include "c3d_lbfgs.h"
-#include "c3d_chunked.h"
 
 namespace c3d {
 

@@ -122,7 +122,7 @@ inline bool pair_targets_fit(const DevModel& m) { return device_pot(m.noe_pot) =
 // c3d_step_kernel_name both read it.  Switches: the context's options wide_tiles and pair_targets, and whether tgs2 is built.
 //
 // The column source (chunk): 0 = the replica's whole coordinate array staged in LDS (k_step, k_lbfgs_eval, k_eval_forces), else the
-// chunked form with that many columns per pass (k_step_chunked, ...: c3d_chunked.h) — column_chunk_for decides it.
+// chunked form with that many columns per pass (k_step_chunked, ...: ColsChunked, c3d_step_core.h) — column_chunk_for decides it.
 struct StepForm {
     int pot;
     bool gen;

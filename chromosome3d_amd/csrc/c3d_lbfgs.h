@@ -4,7 +4,8 @@
 // One L-BFGS step = two launches per replica group.  The direction needs global sums of the gradient just computed (its projections on
 // the stored pairs: tools/minimiser_study.py lbfgs_fixed_step, late = False), and on the per-step path the kernel boundary is the only
 // synchronisation between workgroups:
-//   k_lbfgs_eval  forces of the rows (tile_forces<>, the choices launch_step makes), y = F_prev - F into the ring, per-tile sums of
+//   k_lbfgs_eval  forces of the rows (tile_forces<>, the choices launch_step makes; staged or chunked, as k_step: the body is
+//                 c3d_lbfgs_eval_body.inc), y = F_prev - F into the ring, per-tile sums of
 //                 F.s_j, F.y_j, s_j.y, y_j.y, s.s, F.F (c3d_internal.h "L-BFGS stage")
 //   k_lbfgs_move  every workgroup of a replica: the tile sums in fp64 in one fixed order, the pair test, the new column of S'Y and Y'Y,
 //                 the two triangular solves of the compact form, the descent test (thread 0, LDS); then its rows: the direction
@@ -20,91 +21,23 @@ __device__ __forceinline__ float row_sum8(const float* q, int stride) {
     return ((q[0] + q[stride]) + (q[2 * stride] + q[3 * stride])) + ((q[4 * stride] + q[5 * stride]) + (q[6 * stride] + q[7 * stride]));
 }
 
+
 template <int POT, bool GEN, int RPW, bool NC, int TR = kTileRows, bool WIDE = false>
 __global__ __launch_bounds__(64 * TR / RPW) __attribute__((amdgpu_waves_per_eu(WIDE ? 4 : 1))) void k_lbfgs_eval(
     const float* __restrict__ xin, const float* __restrict__ tgt, const float* __restrict__ fprev, float* __restrict__ fout,
     float* __restrict__ hist, float* __restrict__ part, const LbfgsState* __restrict__ sin, const DevModel m, const DevStep p,
     const int mem0) {
-    constexpr int WAVES = TR / RPW;
-    constexpr int BLOCK = 64 * WAVES;
-    constexpr int TILES = TR / kTileRows;
-    constexpr int Q = kLbfgsQ;
-    static_assert(TR % kTileRows == 0 && TILES >= 1 && TILES <= 2, "a workgroup owns one or two 8-row tiles");
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    int tile, rep;
-    if (!block_to_tile(m, tile, rep)) return;
-    tile *= TILES;
-    if (tile >= m.ntiles) return;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int npad = m.npad;
-    float* xs = smem;
-    float* ys = smem + npad;
-    float* zs = smem + 2 * npad;
-    float* rowq = smem + 3 * npad;              // [TR][Q]
-    const size_t roff = (size_t)rep * 3 * npad;
-    const int row0 = tile * kTileRows + wave * RPW;
-    const int row = row0 + lane;
-    const bool fin_lane = lane < RPW;
-    const bool finisher = fin_lane && row < m.n;
-
-    if (m.stage_dma) lds_dma_copy<BLOCK>(xin + roff, smem, 3 * npad, tid);
-    else for (int b = 4 * tid; b < 3 * npad; b += 4 * BLOCK) *reinterpret_cast<float4*>(smem + b) = *reinterpret_cast<const float4*>(xin + roff + b);
-    float4 tv[RPW];
-    if (pair_targets_in_use<POT, GEN, RPW, NC>(m)) pair_targets_prefetch(m, row0, lane, 0, tv);
-    else tile_prefetch<RPW, NC>(m, tgt, row0, lane, 0, tv);
-    const bool first = p.kind == 9;
-    int mem = mem0, nxt = 0;
-    if (!first) {      // (clamped into the ring whatever the state holds: a stage always begins with kind 9, which sets it)
-        mem = min(max(sin[rep].mem, 1), kLbfgsMaxPairs);
-        nxt = min(max(sin[rep].head, 0), mem - 1) + 1;
-        if (nxt == mem) nxt = 0;
-    }
-    float fpx = 0.0f, fpy = 0.0f, fpz = 0.0f;
-    const size_t ix = roff + row, iy = ix + npad, iz = iy + npad;
-    if (finisher && !first) { fpx = fprev[ix]; fpy = fprev[iy]; fpz = fprev[iz]; }
-    __syncthreads();
-
-    float Fx = 0.0f, Fy = 0.0f, Fz = 0.0f;
-    tile_forces<POT, GEN, RPW, NC, true, WIDE>(m, p, tgt, xs, ys, zs, row0, lane, tv, Fx, Fy, Fz);
-
-    if (fin_lane) {
-        float* q = rowq + (row - tile * kTileRows) * Q;
-        for (int k = 0; k < Q; ++k) q[k] = 0.0f;
-        if (finisher) {
-            fout[ix] = Fx; fout[iy] = Fy; fout[iz] = Fz;
-            q[Q - 3] = fmaf(Fx, Fx, fmaf(Fy, Fy, Fz * Fz));
-            if (!first) {
-                float* hs = hist + (size_t)rep * lbfgs_hist_floats(npad) + row;            // slot j, component c: + (3 j + c) npad
-                float* hy = hs + (size_t)3 * kLbfgsMaxPairs * npad;
-                const float yx = fpx - Fx, yy = fpy - Fy, yz = fpz - Fz;
-                float* yn = hy + (size_t)3 * nxt * npad;
-                yn[0] = yx; yn[npad] = yy; yn[2 * npad] = yz;
-                const float* sn = hs + (size_t)3 * nxt * npad;
-                const float sx = sn[0], sy = sn[npad], sz = sn[2 * npad];
-                q[Q - 4] = fmaf(sx, sx, fmaf(sy, sy, sz * sz));
-#pragma unroll
-                for (int j = 0; j < kLbfgsMaxPairs; ++j) {
-                    if (j >= mem) break;
-                    float ax, ay, az, bx, by, bz;
-                    if (j == nxt) { ax = sx; ay = sy; az = sz; bx = yx; by = yy; bz = yz; }
-                    else {
-                        const float* a = hs + (size_t)3 * j * npad;
-                        const float* b = hy + (size_t)3 * j * npad;
-                        ax = a[0]; ay = a[npad]; az = a[2 * npad]; bx = b[0]; by = b[npad]; bz = b[2 * npad];
-                    }
-                    q[4 * j + 0] = fmaf(Fx, ax, fmaf(Fy, ay, Fz * az));
-                    q[4 * j + 1] = fmaf(Fx, bx, fmaf(Fy, by, Fz * bz));
-                    q[4 * j + 2] = fmaf(ax, yx, fmaf(ay, yy, az * yz));
-                    q[4 * j + 3] = fmaf(bx, yx, fmaf(by, yy, bz * yz));
-                }
-            }
-        }
-    }
-    __syncthreads();
-    for (int t = tid; t < TILES * Q; t += BLOCK) {
-        const int tt = t / Q, k = t - tt * Q;
-        if (tile + tt < m.ntiles) part[((size_t)rep * m.ntiles + tile + tt) * Q + k] = row_sum8(rowq + tt * kTileRows * Q + k, Q);
-    }
+    using COLS = ColsStaged;
+#include "c3d_lbfgs_eval_body.inc"
+}
+template <int POT, bool GEN, int RPW, int TR, bool WIDE, int CHUNK>
+__global__ __launch_bounds__(64 * TR / RPW) __attribute__((amdgpu_waves_per_eu(WIDE ? 4 : 1))) void k_lbfgs_eval_chunked(
+    const float* __restrict__ xin, const float* __restrict__ tgt, const float* __restrict__ fprev, float* __restrict__ fout,
+    float* __restrict__ hist, float* __restrict__ part, const LbfgsState* __restrict__ sin, const DevModel m, const DevStep p,
+    const int mem0) {
+    constexpr bool NC = false;
+    using COLS = ColsChunked<CHUNK, 64 * TR / RPW>;
+#include "c3d_lbfgs_eval_body.inc"
 }
 
 // rows per workgroup of the move
@@ -254,8 +187,6 @@ __global__ __launch_bounds__(kLbfgsMoveRows) void k_lbfgs_move(
     }
 }
 
-static size_t lbfgs_eval_lds_bytes(const DevModel& m, int tile_rows) { return sizeof(float) * ((size_t)3 * m.npad + (size_t)kLbfgsQ * tile_rows); }
-
 // launch_step's form, with the kernel of an L-BFGS evaluation
 hipError_t launch_lbfgs_eval(const DevModel& m0, const DevStep& p, const DevBuffers& b, const LbfgsBuffers& lb, int par, int mem,
                              const StepForm& f, hipStream_t s) {
@@ -263,19 +194,22 @@ hipError_t launch_lbfgs_eval(const DevModel& m0, const DevStep& p, const DevBuff
     const int q = par ^ 1;
     DevModel m = m0;
     m.tgs2 = f.pairs ? b.tgs2 : nullptr;      // (the kernels that read it)
-    if (f.chunk) return launch_lbfgs_eval_chunked(m, p, b, lb, par, mem, f, s);
-    if (f.wide) {
-        constexpr int TR = 2 * kTileRows;
-        const int nwg = (m.ntiles + 1) / 2;
-        hipLaunchKernelGGL((k_lbfgs_eval<4, false, 4, false, TR, true>), dim3(8, m.nrep_g, (nwg + 7) / 8), dim3(64 * TR / 4),
-                           lbfgs_eval_lds_bytes(m, TR), s, b.X[par], b.tgt, b.V[par], b.V[q], lb.hist, lb.part, lb.S[par], m, p, mem);
-        return hipGetLastError();
-    }
-    return with_pot(f.pot, [&](auto POT) { return with_bool(f.gen, [&](auto GEN) { return with_rpw(f.rpw, [&](auto RPW) { return with_bool(f.nc, [&](auto NC) {
-        hipLaunchKernelGGL((k_lbfgs_eval<POT, GEN, RPW, NC>), grid_blocks(m), dim3(64 * kTileRows / RPW), lbfgs_eval_lds_bytes(m, kTileRows), s,
+    const int tr = f.wide ? 2 * kTileRows : kTileRows;
+    const auto go = [&](auto kernel, int rpw) {
+        hipLaunchKernelGGL(kernel, grid_blocks(m, tr / kTileRows), dim3(64 * tr / rpw), step_lds_bytes(m, f.chunk, (size_t)kLbfgsQ * tr), s,
                            b.X[par], b.tgt, b.V[par], b.V[q], lb.hist, lb.part, lb.S[par], m, p, mem);
         return hipGetLastError();
-    }); }); }); });
+    };
+    return with_chunk(f.chunk, [&](auto CH) {
+        if (f.wide) {
+            if constexpr (CH == 0) return go(k_lbfgs_eval<4, false, 4, false, 2 * kTileRows, true>, 4);
+            else return go(k_lbfgs_eval_chunked<4, false, 4, 2 * kTileRows, true, CH>, 4);
+        }
+        return with_pot(f.pot, [&](auto POT) { return with_bool(f.gen, [&](auto GEN) { return with_rpw(f.rpw, [&](auto RPW) {
+            if constexpr (CH == 0) return with_bool(f.nc, [&](auto NC) { return go(k_lbfgs_eval<POT, GEN, RPW, NC>, RPW); });
+            else return go(k_lbfgs_eval_chunked<POT, GEN, RPW, kTileRows, false, CH>, RPW);
+        }); }); });
+    });
 }
 
 hipError_t launch_lbfgs_move(const DevModel& m, const DevStep& p, const DevFire& fp, const DevBuffers& b, const LbfgsBuffers& lb, int parity,

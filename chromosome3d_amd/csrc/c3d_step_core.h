@@ -451,19 +451,83 @@ __device__ __forceinline__ void pair_targets_prefetch(const DevModel& m, int row
 // step and pays for every kilobyte of code it drags along (N = 2500: 26.5 against 27.2 us per step)
 // PACKED4 = the packed form also at four rows per wave (two row pairs: the wide-tile step kernel of large problems, NC = false)
 // Where the pair loop reads its COLUMN coordinates (the row side — a row's own coordinates, its chain neighbours — always comes from xs,
-// ys, zs): COLS::enter(jb) runs at the top of column block jb, COLS::load(jb, lane, ...) reads the lane's four columns of it.
-// ColsStaged = the replica's whole coordinate array staged in LDS: the loops read the columns from xs, ys, zs as they always did (the
-// existing kernels' machine code stays byte for byte what it was: tools/isa_compare.py).  The chunked form (c3d_chunked.h) stages
-// CHUNK columns at a time; it exists for NC = false only.
+// ys, zs): COLS::enter(jb) runs at the top of column block jb, COLS::load(jb, lane, ...) reads the lane's four columns of it.  The
+// per-step kernels' bodies (c3d_*_body.inc: k_step, k_lbfgs_eval, k_eval_forces and their *_chunked entry points) build either source
+// from the same arguments (LDS, the replica's coordinates in global memory, npad, thread, LDS-DMA on); lds_floats = the LDS floats the
+// coordinates take ahead of the kernel's own, copy(0) = the prologue's copy.
+// ColsStaged = the replica's whole coordinate array staged in LDS, the rows read from there too: the loops read the columns from xs, ys,
+// zs themselves, as they always did (the staged kernels' machine code stays byte for byte what it was: tools/isa_compare.py).
 struct ColsStaged {
-    static constexpr bool kStaged = true;      // the loops read xs, ys, zs themselves, as they always did
+    static constexpr bool kStaged = true;
+    __device__ ColsStaged(float*, const float*, int, int, bool) {}
+    __device__ static int lds_floats(int npad) { return 3 * npad; }
+    __device__ __forceinline__ void copy(int) const {}          // (the kernel's prologue copies the whole array itself)
     __device__ __forceinline__ void enter(int) const {}
     __device__ __forceinline__ void load(int, int, float4&, float4&, float4&) const {}
 };
+// ColsChunked = TWO LDS buffers of 3 CHUNK columns, buf = [2][3][CHUNK], src = the replica's coordinates in global memory [3][npad];
+// before a workgroup computes chunk c it starts the copy of chunk c + 1 into the other buffer, one barrier per chunk.  The LDS a
+// workgroup takes is sized by CHUNK, never by n.  Only layouts without a narrow last block (NC = false: every n > 1024) have this form.
+// BLOCK = threads of the workgroup
+template <int CHUNK, int BLOCK>
+struct ColsChunked {
+    static constexpr bool kStaged = false;
+    static constexpr int BPC = CHUNK / 256;          // column blocks per chunk
+    static_assert(CHUNK % 256 == 0 && (BPC & (BPC - 1)) == 0, "CHUNK: a power of two times 256 columns");
+    float* buf;
+    const float* src;
+    int npad, tid;
+    bool dma;
+    __device__ static int lds_floats(int) { return 6 * CHUNK; }
+    // chunk c (columns CHUNK c .. min(CHUNK (c + 1), npad) - 1: a multiple of 256, as lds_dma_copy wants) into buffer c & 1
+    __device__ __forceinline__ void copy(int c) const {
+        const int c0 = CHUNK * c, cnt = min(CHUNK, npad - c0);
+        float* dst = buf + (c & 1) * 3 * CHUNK;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float* s = src + (size_t)k * npad + c0;
+            float* d = dst + k * CHUNK;
+            if (dma) {   // lds_dma_copy's instructions (a call of it from here changed the address arithmetic of the staged kernels' calls)
+                const int lane = tid & 63;
+                for (int b = 4 * tid; b < cnt; b += 4 * BLOCK)
+                    __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)(s + b),
+                                                     (void __attribute__((address_space(3)))*)(d + (b - 4 * lane)), 16, 0, 0);
+            } else for (int b = 4 * tid; b < cnt; b += 4 * BLOCK) *reinterpret_cast<float4*>(d + b) = *reinterpret_cast<const float4*>(s + b);
+        }
+    }
+    // top of column block jb: at the first block of chunk c > 0 wait for chunk c (this wave's copies: vmcnt; everyone's: the barrier,
+    // which also means every wave is done with chunk c - 1), then start chunk c + 1 into the buffer chunk c - 1 leaves free.  Chunk 0
+    // was started by the kernel's prologue and made visible by its barrier.
+    __device__ __forceinline__ void enter(int jb) const {
+        if (jb & (BPC - 1)) return;
+        const int c = jb / BPC;
+        if (c > 0) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+        }
+        if (CHUNK * (c + 1) < npad) copy(c + 1);
+    }
+    __device__ __forceinline__ void load(int jb, int lane, float4& xj, float4& yj, float4& zj) const {
+        const float* b = buf + ((jb / BPC) & 1) * 3 * CHUNK + 256 * (jb & (BPC - 1)) + 4 * lane;
+        xj = *reinterpret_cast<const float4*>(b);
+        yj = *reinterpret_cast<const float4*>(b + CHUNK);
+        zj = *reinterpret_cast<const float4*>(b + 2 * CHUNK);
+    }
+};
+// the column source of a launch: chunk = StepForm::chunk (0: ColsStaged, else ColsChunked<chunk, ...>: the instantiated set)
+template <class F> hipError_t with_chunk(int chunk, F&& f) {
+    switch (chunk) {
+        case 0: return f(int_c<0>{});
+        case 256: return f(int_c<256>{});
+        case 1024: return f(int_c<1024>{});
+        case 2048: return f(int_c<2048>{});
+        default: return hipErrorInvalidValue;
+    }
+}
 template <int POT, bool GEN, int RPW, bool NC, bool PACKED, bool PACKED4, class COLS>
-__device__ __forceinline__ void tile_forces_cols(const DevModel& m, const DevStep& p, const float* __restrict__ tgt,
-                                                 const float* xs, const float* ys, const float* zs, const COLS& cols, int row0, int lane,
-                                                 float4 (&tv)[RPW], float& Fx, float& Fy, float& Fz) {
+__device__ __forceinline__ void tile_forces(const DevModel& m, const DevStep& p, const float* __restrict__ tgt,
+                                            const float* xs, const float* ys, const float* zs, const COLS& cols, int row0, int lane,
+                                            float4 (&tv)[RPW], float& Fx, float& Fy, float& Fz) {
     static_assert(COLS::kStaged || !NC, "the narrow last block and the left-over columns read the staged arrays");
     float fx[RPW], fy[RPW], fz[RPW];
     float xi[RPW], yi[RPW], zi[RPW];
@@ -614,13 +678,6 @@ __device__ __forceinline__ void tile_forces_cols(const DevModel& m, const DevSte
             pair_quad_w<POT, GEN>(m, p, k, width, pair_b<GEN>(m, tv[r]), pair_a<GEN>(m, p, tv[r]), xi[r], yi[r], zi[r], xj, yj, zj, fx[r], fy[r], fz[r]);
     }
     reduce_and_chain<POT, RPW, GEN, NC>(m, p, tgt, xs, ys, zs, row0, lane, fx, fy, fz, Fx, Fy, Fz);
-}
-// the staged form: rows and columns from the same LDS arrays
-template <int POT, bool GEN, int RPW, bool NC = true, bool PACKED = true, bool PACKED4 = false>
-__device__ __forceinline__ void tile_forces(const DevModel& m, const DevStep& p, const float* __restrict__ tgt,
-                                            const float* xs, const float* ys, const float* zs, int row0, int lane,
-                                            float4 (&tv)[RPW], float& Fx, float& Fy, float& Fz) {
-    tile_forces_cols<POT, GEN, RPW, NC, PACKED, PACKED4>(m, p, tgt, xs, ys, zs, ColsStaged{}, row0, lane, tv, Fx, Fy, Fz);
 }
 
 // clamp form with the per-pair constants resident for a whole launch (cluster kernel, compute waves): tv = pair_b in

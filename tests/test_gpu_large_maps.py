@@ -1,5 +1,5 @@
 """Chromosomes beyond 5120 beads on the fp32 per-step path: the options max_beads / column_chunk, the chunked form of the per-step kernels
-(csrc/c3d_chunked.h) against the staged form bit for bit where both run, and against the oracle past the old limit, up to 16384 beads.
+(k_*_chunked: ColsChunked in csrc/c3d_step_core.h) against the staged form bit for bit where both run, and against the oracle past the old limit, up to 16384 beads.
 
 Every test here runs on a context of its own (module fixture), never the session's: max_beads stays raised on it."""
 import os
