@@ -1575,12 +1575,22 @@ extern "C" int c3d_init_replicas(c3d_ctx* c, int nrep, uint64_t seed, uint32_t f
     return C3D_OK;
 }
 
+// A7: the lower bound of pairs without a restraint, the last stage's repel contact distance (formed in float)
+static float dg_lower(const c3d_ctx* c) {
+    float repel_s = 0.85f;
+    if (!c->stages.empty()) repel_s = c->stages.back().repel_s;
+    return repel_s * c->model.r0_rep;
+}
+
 // A7: replace the replicas' starting coordinates by a metric-matrix distance-geometry embedding
 // (deck :1471-1525 restated for beads; one embed per model, trial distances keyed by replica id)
 extern "C" int c3d_embed_replicas(c3d_ctx* c, int iters) {
     if (!c || iters < 1) return fail(C3D_ERR_INVALID, "c3d_embed_replicas: bad arguments");
     if (!c->have_replicas) return fail(C3D_ERR_INVALID, "c3d_embed_replicas: call c3d_init_replicas first");
-    if ((size_t)9 * c->n + 16 > 160 * 1024 / sizeof(float)) return fail(C3D_ERR_INVALID, "c3d_embed_replicas: too many beads for the embedding kernel");
+    constexpr int kMaxEmbedBeads = (int)((160 * 1024 / sizeof(float) - 16) / 9);   // 4549: k_dg_eig keeps 9 n + 16 floats in LDS
+    if (c->n > kMaxEmbedBeads)
+        return fail(C3D_ERR_INVALID, "c3d_embed_replicas: " + std::to_string(c->n) + " beads; at most " + std::to_string(kMaxEmbedBeads) +
+                                         " (k_dg_eig keeps 9 n + 16 floats in 160 KiB of LDS)");
     C3D_ENTRY(c, unit_bit(UNIT_EMBED));
     const int n = c->n, nrep = c->nrep;
     const size_t nn = (size_t)n * n;
@@ -1597,13 +1607,31 @@ extern "C" int c3d_embed_replicas(c3d_ctx* c, int iters) {
             for (int k = 0; k < 3; ++k) hv[((size_t)r * 3 + k) * n + i] = (float)g[k];
         }
     HIP_TRY(hipMemcpyAsync(v0.p, hv.data(), sizeof(float) * hv.size(), hipMemcpyHostToDevice, c->stream));
-    float repel_s = 0.85f;
-    if (!c->stages.empty()) repel_s = c->stages.back().repel_s;
-    hipError_t e = c3d::launch_dg_embed(c->buf.tgt, n, c->npad, nrep, c->model.b0, repel_s * c->model.r0_rep, c->seed, c->first_rep,
-                                        iters, v0.p, U.p, L.p, D2.p, c->buf.X[0], c->buf.X[1], c->stream);
+    hipError_t e = c3d::launch_dg_smooth(c->buf.tgt, n, c->npad, c->model.b0, dg_lower(c), U.p, L.p, c->stream);
+    if (e == hipSuccess)
+        e = c3d::launch_dg_embed(U.p, L.p, n, c->npad, nrep, c->seed, c->first_rep, iters, v0.p, D2.p, c->buf.X[0], c->buf.X[1],
+                                 c->stream);
     if (e != hipSuccess) return fail(C3D_ERR_HIP, std::string("embed launch: ") + hipGetErrorString(e));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (c->precision == 64) return import64(c);
+    return C3D_OK;
+}
+
+// test hook: the smoothed bounds c3d_embed_replicas embeds from (no LDS limit: the smoothing keeps 32 x 32 tiles)
+extern "C" int c3d_dg_smoothed_bounds(c3d_ctx* c, float* U_out, float* L_out) {
+    if (!c || !U_out || !L_out) return fail(C3D_ERR_INVALID, "c3d_dg_smoothed_bounds: null argument");
+    if (!c->have_targets) return fail(C3D_ERR_INVALID, "c3d_dg_smoothed_bounds: set the IF matrix / restraints first");
+    C3D_ENTRY(c, unit_bit(UNIT_EMBED));
+    const int n = c->n;
+    const size_t nn = (size_t)n * n;
+    DevTmp<float> U, L;
+    HIP_TRY(hipMalloc(&U.p, sizeof(float) * nn));
+    HIP_TRY(hipMalloc(&L.p, sizeof(float) * nn));
+    hipError_t e = c3d::launch_dg_smooth(c->buf.tgt, n, c->npad, c->model.b0, dg_lower(c), U.p, L.p, c->stream);
+    if (e != hipSuccess) return fail(C3D_ERR_HIP, std::string("smoothing launch: ") + hipGetErrorString(e));
+    HIP_TRY(hipMemcpyAsync(U_out, U.p, sizeof(float) * nn, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(L_out, L.p, sizeof(float) * nn, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return C3D_OK;
 }
 

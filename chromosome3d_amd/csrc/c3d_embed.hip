@@ -303,10 +303,8 @@ __global__ __launch_bounds__(kEigBlock) void k_dg_eig(const float* __restrict__ 
     }
 }
 
-// v0: [nrep][3][n] starting vectors (host Philox normals).  U, L: n*n scratch; D2: nrep*n*n scratch.
-hipError_t launch_dg_embed(const float* tgt, int n, int npad, int nrep, float b0, float lower, uint64_t seed,
-                           uint32_t first_replica, int iters, const float* v0, float* U, float* L, float* D2, float* x0,
-                           float* x1, hipStream_t s) {
+// bounds and smoothing: U, L (n*n) <- the smoothed bounds of the targets (tgt: n rows of npad)
+hipError_t launch_dg_smooth(const float* tgt, int n, int npad, float b0, float lower, float* U, float* L, hipStream_t s) {
     hipLaunchKernelGGL(k_dg_bounds, dim3(n), dim3(256), 0, s, tgt, n, npad, b0, lower, U, L);
     const int nb = (n + kFwB - 1) / kFwB;
     for (int kb = 0; kb < nb; ++kb) {
@@ -325,6 +323,12 @@ hipError_t launch_dg_embed(const float* tgt, int n, int npad, int nrep, float b0
     }
     const size_t nn = (size_t)n * n;
     hipLaunchKernelGGL(k_dg_clamp, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, s, L, U, nn);
+    return hipGetLastError();
+}
+
+// trial distances and embedding from smoothed U, L.  v0: [nrep][3][n] starting vectors (host Philox normals); D2: nrep*n*n scratch.
+hipError_t launch_dg_embed(const float* U, const float* L, int n, int npad, int nrep, uint64_t seed, uint32_t first_replica, int iters,
+                           const float* v0, float* D2, float* x0, float* x1, hipStream_t s) {
     hipLaunchKernelGGL(k_dg_trial, dim3(n, nrep), dim3(256), 0, s, U, L, n, (uint32_t)(seed & 0xFFFFFFFFu),
                        (uint32_t)(seed >> 32), first_replica, D2);
     const size_t lds = sizeof(float) * ((size_t)9 * n + 16);

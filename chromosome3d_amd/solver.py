@@ -109,6 +109,13 @@ class Solver:
         """A7: metric-matrix distance-geometry start for every replica."""
         _l.check(self._L.c3d_embed_replicas(self._h, iters))
 
+    def dg_bounds(self):
+        """(U, L), n x n fp32: the smoothed distance bounds embed() draws its trial distances from (c3d_dg_smoothed_bounds)."""
+        U = np.empty((self.n, self.n), dtype=np.float32)
+        L = np.empty((self.n, self.n), dtype=np.float32)
+        _l.check(self._L.c3d_dg_smoothed_bounds(self._h, _l.fptr(U), _l.fptr(L)))
+        return U, L
+
     def set_coords(self, xyz):
         xyz = _l.as_f32(xyz)
         assert xyz.shape == (self.nrep, self.n, 3)

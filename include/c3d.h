@@ -158,7 +158,7 @@ int c3d_set_schedule(c3d_ctx* ctx, const c3d_stage* stages, int n_stages, const 
  *                   256): 0.55 GB at 8192 beads, 2.1 GB at 16384; c3d_set_if_matrix takes 21 n^2 bytes more while it runs (the matrix
  *                   and its powers in fp64, the integer tenths, flags: 5.6 GB at 16384) and the host keeps the n^2 integer tenths (1 GB).
  *                   Beyond 5120 beads the fp32 step kernels run in their chunked form (below).  Not beyond 5120: precision 64 (2560),
- *                   symmetric 1 (c3d_init_replicas refuses it), c3d_embed_replicas (its own LDS limit, about 4550 beads)
+ *                   symmetric 1 (c3d_init_replicas refuses it), c3d_embed_replicas (its own LDS limit: 4549 beads)
  *   column_chunk    0 (default): where the per-step kernels read a column's coordinates — 0 = the library's choice: the replica's whole
  *                   coordinate array staged in LDS while it fits (n <= 5120: exactly the kernels of earlier releases), beyond that the
  *                   chunked form, which streams 1024 columns at a time through two LDS buffers; 256, 1024 or 2048 = the chunked
@@ -218,7 +218,8 @@ int c3d_init_replicas(c3d_ctx* ctx, int n_replicas, uint64_t seed, uint32_t firs
 /* A7 (deck chromosome3D.pl:1471-1525, bead-level restatement): replace the random-coil start of every
  * replica by a metric-matrix distance-geometry embedding — bounds from the restraints, triangle
  * smoothing, random trial distances (Philox, keyed by replica id), 3 leading eigenvectors found with
- * `iters` orthogonal iterations (50 is plenty).  Call between c3d_init_replicas and c3d_run. */
+ * `iters` orthogonal iterations (50 is plenty).  Call between c3d_init_replicas and c3d_run.  At most 4549 beads: the eigen stage
+ * keeps 9 n + 16 floats of a replica in the 160 KiB of LDS of one CU (C3D_ERR_INVALID beyond). */
 int c3d_embed_replicas(c3d_ctx* ctx, int iters);
 /* overwrite coordinates (n_replicas*n*3, xyz interleaved) — tests and restarts */
 int c3d_set_coords(c3d_ctx* ctx, const float* xyz);
@@ -258,6 +259,11 @@ int c3d_get_stat(const c3d_ctx* ctx, const char* key, double* value);
  * workgroup, a consumer workgroup on every other CU, the context's stream) for `iterations` rewrites of 1024 units and returns the number
  * of unit reads, of TORN units (must be 0) and of reads that saw a new value. */
 int c3d_debug_tear16(c3d_ctx* ctx, int iterations, unsigned long long* unit_reads, unsigned long long* torn, unsigned long long* fresh);
+/* Test hook of A7 (c3d_embed_replicas): U, L (n*n each, row-major) = the smoothed distance bounds the embedding draws its trial distances
+ * from — b0 on |i-j| = 1, the target on restrained pairs, [r0_rep x the last stage's repel, 1e30] elsewhere, then all-pairs shortest
+ * paths on U, the inverse triangle inequality on L, L <= U.  The same kernels and arguments as the embedding; no bead limit of its own.
+ * Needs the targets (c3d_set_if_matrix / c3d_set_restraints), not the replicas. */
+int c3d_dg_smoothed_bounds(c3d_ctx* ctx, float* U, float* L);
 /* Name of the kernel the last op of the last range of c3d_run / c3d_run_steps ran on, as a profiler prints it (thread-local string): the
  * choice that op's launch was made from, also when the range was replayed from a captured graph.  After an L-BFGS step the force pass,
  * k_lbfgs_eval<...>; "" before the first range. */
