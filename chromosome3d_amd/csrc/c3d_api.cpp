@@ -601,9 +601,11 @@ int drop_stale_gated(c3d_ctx* c, unsigned stale) {
     return C3D_OK;
 }
 
+// The symmetric-tile kernels evaluate the clamp form only (k_pairs_sym reads rs and mrs, not the tails): decided per op from the model in
+// force, which c3d_set_model may change on a live context; a general tail runs k_step's general form.  The tile list and slabs exist
+// whenever `symmetric` is on (c3d_init_replicas).
 bool use_sym(const c3d_ctx* c) {
-    if (!c->d_sym_scratch) return false;
-    return c->sym > 0;
+    return c->sym > 0 && c->d_sym_scratch && !c3d::general_tail(dev_model(c));
 }
 
 void model_host64(const c3d_ctx* c, double (&mh)[15]) {
@@ -1461,8 +1463,8 @@ extern "C" int c3d_init_replicas(c3d_ctx* c, int nrep, uint64_t seed, uint32_t f
         {
             c3d::DevModel m = dev_model(c);
             m.nrep = nrep; m.nrep_g = nrep; m.rep_base = 0;
-            // symmetric-tile kernels (large N): tile list and the partial-force slabs
-            if (!c3d::general_tail(m) && c->sym > 0) {
+            // symmetric-tile kernels (large N): tile list and the partial-force slabs, whatever the model in force (use_sym)
+            if (c->sym > 0) {
                 int Q, G, od, dg;
                 c3d::sym_geometry(m, &Q, &G, &od, &dg);
                 std::vector<int2> tl((size_t)od + dg);

@@ -164,8 +164,9 @@ int c3d_set_schedule(c3d_ctx* ctx, const c3d_stage* stages, int n_stages, const 
  *                   chunked form, which streams 1024 columns at a time through two LDS buffers; 256, 1024 or 2048 = the chunked
  *                   form with that many columns a pass at every n > 1024 (smaller problems have a narrow last column block and stay
  *                   staged).  Same bits either way (test and measurement knob)
- *   symmetric       1: symmetric-tile kernels for large N (c3d_sym.hip; opt-in); call before c3d_init_replicas.  Not for the L-BFGS steps of
- *                   a kind-8 stage: they run their own kernels.  At most 5120 beads
+ *   symmetric       1: symmetric-tile kernels for large N (c3d_sym.hip; opt-in); call before c3d_init_replicas.  At most 5120 beads.  Not for
+ *                   a general tail (k_step's general form runs; decided per step from the model in force), the L-BFGS steps of a kind-8 stage
+ *                   (their own kernels), or a problem the multi-step kernel takes (at most 768 padded beads) unless resident is 0
  *   eval_rows_per_wave  4 (default) / 2 / -2: form of the forces hook (c3d_eval_forces) — four rows per wave with the scalar pair term; 2 = two
  *                   rows per wave, the step kernels' code (shipped potential: the packed pair term); -2 = two rows per wave, scalar pair
  *                   term.  2 and -2 return the same bits (a -m gpu test); test knob

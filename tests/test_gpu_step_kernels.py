@@ -1,10 +1,14 @@
 """Every step kernel against the fp64 oracle, beyond what the benchmark runs: each NOE potential (and its general-tail form) through
 the three launch forms — k_cluster / k_cluster_tp (many steps per launch), k_step (one launch per step), k64_step (fp64) — the fp64
-kernel's column layouts up to its 2560-bead limit, a model switched on a live context, and device scoring past the rank-prefetch limit.
+kernel's column layouts up to its 2560-bead limit, a model switched on a live context, device scoring past the rank-prefetch limit, and
+the fourth form, the opt-in symmetric tiles (k_pairs_sym + k_update_sym, option symmetric 1): potentials, tile layouts, replica indexing.
 
 Every test asserts through the kernel name and the launch counters that the kernel it claims to test ran.  Tolerances are those of
 test_gpu_parity.py: fp32 coordinates 2e-3 A (5e-3 A once two-point steps are involved), fp64 2e-5 A (the grain of the fp32 read-back).
 """
+import functools
+import time
+
 import numpy as np
 import pytest
 
@@ -78,20 +82,22 @@ def _oracle(O, m, fire, d10, stages, x0, tp, upto):
         O.set_two_point_steps(1000)
 
 
-def _run_form(solver, m, IF, stages, tp, precision, resident, rpw, checkpoints, nrep=2, groups=2):
+def _run_form(solver, m, IF, stages, tp, precision, resident, rpw, checkpoints, nrep=2, groups=2, symmetric=0, use_graph=1, first=0):
     """Runs `stages` in the given form, stopping at each checkpoint: [(steps, coords, velocities, kernel name, cluster launches, step
-    launches)], plus the start coordinates."""
+    launches)], plus the start coordinates.  Replicas first .. first + nrep - 1."""
     from chromosome3d_amd import default_fire, make_stages
     solver.set_option("precision", precision)
     solver.set_option("resident", resident)
     solver.set_option("rows_per_wave", rpw)
     solver.set_option("replica_groups", groups)
     solver.set_option("final_minimiser_steps", tp)
+    solver.set_option("symmetric", symmetric)
+    solver.set_option("use_graph", use_graph)
     try:
         solver.set_model(m)
         solver.set_if_matrix(IF)
         solver.set_schedule(make_stages(stages), default_fire())
-        solver.init_replicas(nrep, 82364, 0)
+        solver.init_replicas(nrep, 82364, first)
         x0 = solver.coords()
         out, done = [], 0
         for k in checkpoints:
@@ -107,6 +113,8 @@ def _run_form(solver, m, IF, stages, tp, precision, resident, rpw, checkpoints, 
         solver.set_option("rows_per_wave", 2)
         solver.set_option("replica_groups", 2)
         solver.set_option("final_minimiser_steps", 1000)
+        solver.set_option("symmetric", 0)
+        solver.set_option("use_graph", 1)
 
 
 def _worst(x, ref):
@@ -334,3 +342,190 @@ def test_device_scoring_beyond_the_rank_prefetch_limit(solver, O, n):
             os_, od = O.assess(xo, rr)
             assert sat[r] == hs == os_, (phase, r, sat[r], hs, os_)
             assert abs(dev[r] - hd) <= 1e-10 * max(1.0, abs(hd)) and abs(dev[r] - od) <= 1e-10 * max(1.0, abs(od)), (phase, r, dev[r], hd, od)
+
+
+# ---------------------------------------------------------------------------------------------
+# F. the symmetric-tile form (c3d_sym.hip, option symmetric 1)
+# ---------------------------------------------------------------------------------------------
+# k_pairs_sym evaluates the clamp form itself (not pair_term): u = 1 - t/d, a clamp per potential, RS1 (rswitch 1: the upper bound is
+# 1/d itself) as its own branch, and repel on every pair, the chain pass taking the |i - j| < rep_sep neighbours back out.  This section's
+# own variants: rep_sep 1 (nothing taken back) and 3 (both chain neighbours; every other variant has the default, 2), RS1 for potentials
+# 0 and 1 (pot3_rs1 has it for potential 3).
+F_VARIANTS = dict(VARIANTS, rep1=(dict(rep_sep=1), 4, False), rep3=(dict(rep_sep=3), 4, False),
+                  pot0_rs1=(dict(noe_pot=0, rswitch=1.0), 0, False), pot1_rs1=(dict(noe_pot=1, rswitch=1.0), 1, False))
+
+
+def _sym_name(m, pot):
+    return f"c3d::k_pairs_sym<{pot}, {'true' if m.rswitch == 1.0 else 'false'}, false>"
+
+
+@functools.lru_cache(maxsize=2)
+def _f_problem(size):
+    if size == "syn1100":                          # beyond the cluster kernel's reach: 5 column blocks x 18 row groups
+        return synthetic_if(1100, seed=1100)[0]
+    return _problem(size)
+
+
+# (potential 2 at syn1100 is held to the oracle by the layout test below instead: see the docstring)
+F_CASES = [(v, size) for v in sorted(F_VARIANTS) for size in ("syn250", "chr4_1mb", "syn1100") if (v, size) != ("pot2", "syn1100")]
+
+
+@pytest.mark.parametrize("variant,size", F_CASES)
+def test_every_potential_through_the_symmetric_tiles_follows_the_oracle(solver, O, variant, size):
+    """The schedule of section A (FIRE; MD at 2000 K: kinds 4 then 0; kind 1; an MD stage with w_all = 0; kind 5 with the hand-over to
+    FIRE after 8 of its steps) with symmetric 1 and resident 0 (the multi-step kernel takes syn250 and chr4_1mb otherwise), against the
+    oracle after the zero-weight stage (34 steps) and at the end (54), and against the per-step path (symmetric 0) of the same case.
+    A clamp-form model runs k_pairs_sym<pot, rs1, false> at every checkpoint — the zero-weight stage and kinds 5 / 6 included, which
+    k_update_sym steps itself; a general tail runs k_step<pot, true, ...>, in the bits of the symmetric 0 run.  The symmetric form sums a
+    row in another order than k_step: the two agree within the oracle tolerances, not bit for bit.  Measured worst of k_pairs_sym over
+    its 35 cases: 9.6e-5 A after the zero-weight stage (pot2, syn250) / 1.0e-4 A at the end (kang0, syn250); the general tails' k_step
+    1.1e-3 / 5.7e-4 A (gen2, syn1100).  Left out: potential 2 at syn1100.  It has no switch, so its force grows with the violation,
+    and syn1100 restrains every pair.  There the stages after step 22 magnify fp32 rounding about a hundredfold in every fp32 form.
+    k_step has it too: 2e-5 A from the oracle after step 22, 2.4e-3 A after step 34.  The oracle cannot see a kernel error through that.  Its
+    k_pairs_sym<2, ...> runs on several column blocks in the layout test below, at 2049 beads."""
+    from chromosome3d_amd import default_fire, default_model
+    kw, pot, gen = F_VARIANTS[variant]
+    m = default_model(**kw)
+    IF = _f_problem(size)
+    cps = [34, 40, 54]
+    forms = {"sym": _run_form(solver, m, IF, S32, TP32, 32, 0, 2, cps, symmetric=1),
+             "step": _run_form(solver, m, IF, S32, TP32, 32, 0, 2, cps)}
+    d10 = solver.dist10()
+    x0 = forms["step"][0]
+    ref = {k: _oracle(O, m, default_fire(), d10, S32, x0, TP32, k) for k in (34, 54)}
+    worst = {}
+    for name, (xs, out) in forms.items():
+        assert np.array_equal(xs, x0), name
+        done = 0
+        for k, x, v, kn, cl, sl in out:
+            assert cl == 0 and sl >= k - done, (name, k, cl, sl)
+            done = k
+            if name == "sym" and not gen:
+                assert kn == _sym_name(m, pot), (name, k, kn)
+            else:                                  # (the zero-weight stage ends at 34: k_step's general form)
+                assert kn.startswith(f"c3d::k_step<{pot}, {'true' if gen or k == 34 else 'false'}, "), (name, k, kn)
+        (_, xa, va, *_), _, (_, xc, vc, *_) = out
+        wa, wc = _worst(xa, ref[34]), _worst(xc, ref[54])
+        assert wa < 2e-3 and wc < 5e-3, (name, wa, wc)
+        for r in range(2):
+            vo = ref[34][r][1]
+            assert np.abs(va[r] - vo).max() < 2e-3 * max(1.0, np.abs(vo).max()), (name, r)
+        worst[name] = (wa, wc)
+    # the symmetric form against the per-step path
+    for (_, xs, vs, *_), (k, xp, vp, *_) in zip(forms["sym"][1], forms["step"][1]):
+        if gen:                                    # the same kernel ran: the same bits
+            assert np.array_equal(xs, xp) and np.array_equal(vs, vp), k
+        else:
+            assert np.abs(xs - xp).max() < (2e-3 if k == 34 else 5e-3), (k, np.abs(xs - xp).max())
+            assert np.abs(vs - vp).max() < 2e-3 * max(1.0, np.abs(vp).max()), k
+    print(f"{variant} {size}: {forms['sym'][1][-1][3]}: worst {worst['sym'][0]:.2e} {worst['sym'][1]:.2e} A "
+          f"(per-step path {worst['step'][0]:.2e} {worst['step'][1]:.2e})")
+
+
+F_GEOMETRY = ([(n, "shipped") for n in (9, 64, 65, 128, 255, 256, 257, 320, 321, 1025, 2049, 5120)]
+              + [(n, v) for v in ("pot3_rs1", "pot0") for n in (257, 2049)] + [(2049, "pot2")])
+
+
+@pytest.mark.parametrize("n,variant", F_GEOMETRY)
+def test_symmetric_tile_layouts_follow_the_oracle(solver, O, n, variant):
+    """k_pairs_sym cuts the pair matrix into tiles of 64 rows (row group g, G = ceil(n / 64) of them) x 256 columns (column block q,
+    Q = npad / 256) and visits a tile only on or above the diagonal: q >= g / 4.  The tile that crosses the diagonal (q = g / 4, G of
+    them) keeps j > i alone (k_pairs_sym<..., true>); the others (od of them) are a launch of their own.  k_update_sym gathers a row's
+    rows-side partials over q >= g / 4 and its column-side partials over the row groups 0 .. gmax = min(4 q + 3, G - 1).  The sizes:
+      9: one diagonal tile, 247 padding columns       64: one full row group        65: a second row group of ONE row
+      128: two row groups, half the block padding     255: four groups, the last of 63 rows, one padding column
+      256: one column block, every tile diagonal (G = 4, od = 0), no padding
+      257: the first off-diagonal tiles (Q = 2, G = 5, od = 4): row group 4 is one row, block 1 one live column, gmax clamped to G - 1
+      320: block 1 of 64 live columns, row group 4 full   321: Q = 2, G = 6, the last group one row
+      1025: Q = 5, G = 17, od = 40, a last group of one row    2049: Q = 9, G = 33, od = 144, a last group of one row
+      5120: the limit (Q = 20, G = 80, od = 760, no padding)
+    The shipped potential at every n, pot3_rs1 (RS1) and potential 0 at 257 and 2049, potential 2 at 2049.  FIRE, MD at 2000 K (kinds 4 then 0), FIRE — 32
+    steps up to 1025, 20 beyond; resident 0 up to 768 (the multi-step kernel's reach), the library's choice beyond; 2 replicas, every one
+    against the oracle.  Measured worst: 7.2e-5 A for the shipped potential (at 5120), 8.2e-5 A (potential 2, 2049).  The oracle takes
+    3.5 s at 5120 (two replicas, 20 steps), the whole case 4.7 s."""
+    from chromosome3d_amd import default_fire, default_model
+    kw, pot, gen = VARIANTS[variant]
+    m = default_model(**kw)
+    IF = synthetic_if(n, seed=n)[0]
+    a, b, d = (10, 12, 10) if n <= 1025 else (6, 8, 6)
+    stages = [(2, a, 0.0, 1.0, 20.0, 0.5, 0.0), (0, b, 0.003, 0.4, 0.003, 0.9, 2000.0), (2, d, 0.0, 1.0, 1.0, 0.85, 0.0)]
+    k = a + b + d
+    x0, out = _run_form(solver, m, IF, stages, 1000, 32, 0 if n <= 768 else -1, 2, [k], symmetric=1)
+    (_, x, v, name, cl, sl) = out[0]
+    assert name == _sym_name(m, pot) and cl == 0 and sl >= k, (name, cl, sl)
+    d10 = solver.dist10()
+    del IF
+    t0 = time.perf_counter()
+    ref = _oracle(O, m, default_fire(), d10, stages, x0, 1000, k)
+    t_oracle = time.perf_counter() - t0
+    worst = _worst(x, ref)
+    assert worst < 2e-3, worst
+    for r in range(2):
+        assert np.abs(v[r] - ref[r][1]).max() < 2e-3 * max(1.0, np.abs(ref[r][1]).max()), r
+    print(f"n={n} {variant}: {name}, worst {worst:.2e} A (oracle {t_oracle:.1f} s)")
+
+
+def test_symmetric_tiles_index_replicas_by_their_global_number(solver):
+    """The slabs of k_pairs_sym / k_update_sym and the FIRE state are indexed by the global replica, rep_base + blockIdx.y: 5 replicas at
+    n = 1100 (S32: every stage kind) give the same bits in replica groups 1, 2, 3 and 4 (uneven groups, rep_base 0 .. 4), eagerly and
+    through graphs, and replica r alone (first_replica r) gives the bits of replica r of the five."""
+    from chromosome3d_amd import default_model
+    m = default_model()
+    IF = _f_problem("syn1100")
+    name = _sym_name(m, 4)
+    runs = {f"groups{g}": _run_form(solver, m, IF, S32, TP32, 32, -1, 2, [54], nrep=5, groups=g, symmetric=1) for g in (1, 2, 3, 4)}
+    runs["eager"] = _run_form(solver, m, IF, S32, TP32, 32, -1, 2, [54], nrep=5, groups=3, symmetric=1, use_graph=0)
+    x0, ((_, x, v, *_),) = runs["groups1"]
+    assert np.isfinite(x).all() and not np.array_equal(x[0], x[1])
+    for key, (xs, ((_, xr, vr, kn, cl, sl),)) in runs.items():
+        assert kn == name and cl == 0 and sl >= 54, (key, kn, cl, sl)
+        assert np.array_equal(xs, x0) and np.array_equal(xr, x) and np.array_equal(vr, v), key
+    for r in range(5):
+        xs, ((_, xr, vr, kn, cl, _),) = _run_form(solver, m, IF, S32, TP32, 32, -1, 2, [54], nrep=1, symmetric=1, first=r)
+        assert kn == name and cl == 0, (r, kn)
+        assert np.array_equal(xs[0], x0[r]) and np.array_equal(xr[0], x[r]) and np.array_equal(vr[0], v[r]), r
+
+
+@pytest.mark.parametrize("start", ["clamp", "general"])
+def test_model_switched_on_a_live_context_takes_the_symmetric_tiles_where_they_apply(solver, O, start):
+    """The walk of test_model_switched_on_a_live_context_follows_the_oracle with symmetric 1 (resident 0, syn250): c3d_set_model alone
+    between runs, after c3d_init_replicas, which ran under the PREVIOUS model.  The symmetric form evaluates the clamp form only: a clamp-form
+    model must run k_pairs_sym<pot, rs1, false>, a general tail k_step<pot, true, ...> — decided per op from the model in force.  Two walks
+    through every device potential, general <-> clamp both ways: one whose first c3d_init_replicas sees a clamp form, one whose first sees a
+    general tail.  Each run against the oracle.  Measured worst: 7.0e-5 A.  Before the choice was made per op, the first walk ran
+    k_pairs_sym on every general tail: gen1, gen3 and gen0 missed the oracle by 1.8, 5.1 and 6.0 A.  The second ran k_step on every
+    clamp form: the symmetric option was silently off."""
+    from chromosome3d_amd import default_fire, default_model, make_stages
+    walk = {"clamp": ["shipped", "gen1", "pot0", "gen3", "pot3_rs1", "gen0", "pot1", "gen2", "pot2", "pot3_clamp", "gen1", "ang0"],
+            "general": ["gen1", "shipped", "gen3", "pot0", "gen0", "pot3_clamp", "gen2", "pot1", "pot2", "pot3_rs1", "gen1", "shipped"]}[start]
+    IF = _problem("syn250")
+    stages = [(2, 10, 0.0, 1.0, 20.0, 0.5, 0.0), (0, 12, 0.003, 0.4, 0.003, 0.9, 2000.0), (1, 8, 0.005, 1.0, 0.05, 1.0, 1500.0)]
+    nsteps = sum(s[1] for s in stages)
+    fire = default_fire()
+    solver.set_option("resident", 0)
+    solver.set_option("symmetric", 1)
+    try:
+        solver.set_model(default_model(**VARIANTS[walk[0]][0]))
+        solver.set_if_matrix(IF)                  # once: the walk below changes the model alone
+        d10 = solver.dist10()
+        seen = []
+        for v in walk:
+            kw, pot, gen = VARIANTS[v]
+            m = default_model(**kw)
+            solver.set_schedule(make_stages(stages), fire)
+            solver.init_replicas(2, 82364, 0)
+            solver.set_model(m)
+            x0 = solver.coords()
+            c0 = solver.stat("cluster_launches")
+            assert solver.run_steps(10 ** 6) == nsteps
+            name = solver.step_kernel_name
+            ok = solver.stat("cluster_launches") == c0 and (name.startswith(f"c3d::k_step<{pot}, true, ") if gen else name == _sym_name(m, pot))
+            ref = _oracle(O, m, fire, d10, stages, x0, 1000, nsteps)
+            seen.append((v, name, ok, _worst(solver.coords(), ref)))
+        # every run first, then the verdict: the message shows the whole walk
+        assert all(ok and w < 2e-3 for _, _, ok, w in seen), "; ".join(f"{v}: {name}{'' if ok else ' (WRONG KERNEL)'} {w:.2e} A"
+                                                                        for v, name, ok, w in seen)
+        print(f"start {start}: worst {max(w for *_, w in seen):.2e} A over {len(walk)} switches")
+    finally:
+        solver.set_option("symmetric", 0)
+        solver.set_option("resident", -1)
