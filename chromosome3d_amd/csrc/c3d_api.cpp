@@ -139,6 +139,10 @@ struct c3d_ctx {
     bool pair_targets = true;              // option "pair_targets": the per-step kernel's resident row-pair constants (measurement knob)
     bool wide_tiles = true;                // option "wide_tiles": beyond the multi-step kernel's reach, 16 rows a workgroup and 4 a wave (measurement knob)
     int max_beads = 5120;                  // option "max_beads": the largest matrix c3d_set_if_matrix / c3d_set_restraints accept (5120..16384)
+    int embed_max_beads = C3D_EMBED_MAX_BEADS_DEFAULT;   // option "embed_max_beads": the largest n c3d_embed_replicas accepts (4549..16384)
+    int embed_form = 0;                    // option "embed_form": 0 = k_dg_eig while it fits, the tiled eigen stage beyond; 1 = tiled at every n
+    int embed_batch = 0;                   // option "embed_batch": 0 = replicas per batch from C3D_EMBED_SCRATCH_BYTES, else that many
+    int last_embed_form = 0, last_embed_batches = 0;   // stats "embed_form", "embed_batches": what the last c3d_embed_replicas ran
     int column_chunk = 0;                  // option "column_chunk": 0 = the library's choice, else the chunked form's CHUNK (c3d::column_chunk_for)
     float* d_feval = nullptr;
     size_t rep_floats = 0;           // 3*npad per replica
@@ -1275,6 +1279,16 @@ extern "C" int c3d_set_option(c3d_ctx* c, const char* key, double value) {
         if (value != (int)value || value < C3D_MAX_BEADS_DEFAULT || value > C3D_MAX_BEADS_LIMIT)
             return fail(C3D_ERR_INVALID, "max_beads must be an integer from 5120 to 16384");
         c->max_beads = (int)value;
+    } else if (!strcmp(key, "embed_max_beads")) {  // the caller's consent to the memory of a large embedding (c3d.h)
+        if (value != (int)value || value < C3D_EMBED_MAX_BEADS_DEFAULT || value > C3D_EMBED_MAX_BEADS_LIMIT)
+            return fail(C3D_ERR_INVALID, "embed_max_beads must be an integer from 4549 to 16384");
+        c->embed_max_beads = (int)value;
+    } else if (!strcmp(key, "embed_form")) {       // test and measurement knob: the eigen stage's form (same bits either way)
+        if (value != 0 && value != 1) return fail(C3D_ERR_INVALID, "embed_form is 0 (k_dg_eig while it fits, tiled beyond) or 1 (tiled)");
+        c->embed_form = (int)value;
+    } else if (!strcmp(key, "embed_batch")) {      // test knob: replicas embedded at a time (same bits whatever it is)
+        if (value != (int)value || value < 0) return fail(C3D_ERR_INVALID, "embed_batch is 0 (by the scratch budget) or a number of replicas");
+        c->embed_batch = (int)value;
     } else if (!strcmp(key, "column_chunk")) {     // test and measurement knob: the per-step kernels' column source (same bits either way)
         if (value != (int)value || (value != 0 && !c3d::column_chunk_valid((int)value)))
             return fail(C3D_ERR_INVALID, "column_chunk must be 0 (the library's choice), 256, 1024 or 2048");
@@ -1589,18 +1603,31 @@ static float dg_lower(const c3d_ctx* c) {
 extern "C" int c3d_embed_replicas(c3d_ctx* c, int iters) {
     if (!c || iters < 1) return fail(C3D_ERR_INVALID, "c3d_embed_replicas: bad arguments");
     if (!c->have_replicas) return fail(C3D_ERR_INVALID, "c3d_embed_replicas: call c3d_init_replicas first");
-    constexpr int kMaxEmbedBeads = (int)((160 * 1024 / sizeof(float) - 16) / 9);   // 4549: k_dg_eig keeps 9 n + 16 floats in LDS
-    if (c->n > kMaxEmbedBeads)
-        return fail(C3D_ERR_INVALID, "c3d_embed_replicas: " + std::to_string(c->n) + " beads; at most " + std::to_string(kMaxEmbedBeads) +
-                                         " (k_dg_eig keeps 9 n + 16 floats in 160 KiB of LDS)");
+    static_assert(c3d::kDgEigMaxBeads == C3D_EMBED_MAX_BEADS_DEFAULT, "the default limit is k_dg_eig's");
+    if (c->n > c->embed_max_beads) {               // on the host, before any launch
+        if (c->embed_max_beads == C3D_EMBED_MAX_BEADS_DEFAULT)
+            return fail(C3D_ERR_INVALID, "c3d_embed_replicas: " + std::to_string(c->n) + " beads; at most " +
+                                             std::to_string(C3D_EMBED_MAX_BEADS_DEFAULT) + " (k_dg_eig keeps 9 n + 16 floats in 160 KiB of LDS)" +
+                                             " unless c3d_set_option(\"embed_max_beads\", n) allows the tiled eigen stage more (up to " +
+                                             std::to_string(C3D_EMBED_MAX_BEADS_LIMIT) + ")");
+        return fail(C3D_ERR_INVALID, "c3d_embed_replicas: " + std::to_string(c->n) + " beads: more than embed_max_beads = " +
+                                         std::to_string(c->embed_max_beads) + " (the option goes up to " +
+                                         std::to_string(C3D_EMBED_MAX_BEADS_LIMIT) + ")");
+    }
     C3D_ENTRY(c, unit_bit(UNIT_EMBED));
     const int n = c->n, nrep = c->nrep;
     const size_t nn = (size_t)n * n;
-    DevTmp<float> U, L, D2, v0;
+    const bool tiled = c->embed_form == 1 || n > c3d::kDgEigMaxBeads;
+    // replicas per batch: as many trial-distance matrices as C3D_EMBED_SCRATCH_BYTES hold, one at least (65535: a grid's y extent)
+    size_t fit = (size_t)C3D_EMBED_SCRATCH_BYTES / (sizeof(float) * nn);
+    if (c->embed_batch > 0) fit = (size_t)c->embed_batch;
+    const int batch = (int)std::min<size_t>(std::max<size_t>(fit, 1), (size_t)std::min(nrep, 65535));
+    DevTmp<float> U, L, D2, v0, wt;
     HIP_TRY(hipMalloc(&U.p, sizeof(float) * nn));
     HIP_TRY(hipMalloc(&L.p, sizeof(float) * nn));
-    HIP_TRY(hipMalloc(&D2.p, sizeof(float) * nn * nrep));
+    HIP_TRY(hipMalloc(&D2.p, sizeof(float) * nn * batch));
     HIP_TRY(hipMalloc(&v0.p, sizeof(float) * 3 * n * nrep));
+    if (tiled) HIP_TRY(hipMalloc(&wt.p, sizeof(float) * 2 * 3 * n * batch));
     std::vector<float> hv((size_t)3 * n * nrep);
     for (int r = 0; r < nrep; ++r)
         for (int i = 0; i < n; ++i) {
@@ -1611,10 +1638,12 @@ extern "C" int c3d_embed_replicas(c3d_ctx* c, int iters) {
     HIP_TRY(hipMemcpyAsync(v0.p, hv.data(), sizeof(float) * hv.size(), hipMemcpyHostToDevice, c->stream));
     hipError_t e = c3d::launch_dg_smooth(c->buf.tgt, n, c->npad, c->model.b0, dg_lower(c), U.p, L.p, c->stream);
     if (e == hipSuccess)
-        e = c3d::launch_dg_embed(U.p, L.p, n, c->npad, nrep, c->seed, c->first_rep, iters, v0.p, D2.p, c->buf.X[0], c->buf.X[1],
-                                 c->stream);
+        e = c3d::launch_dg_embed(U.p, L.p, n, c->npad, nrep, c->seed, c->first_rep, iters, v0.p, D2.p, wt.p, c->buf.X[0], c->buf.X[1],
+                                 tiled, batch, c->stream);
     if (e != hipSuccess) return fail(C3D_ERR_HIP, std::string("embed launch: ") + hipGetErrorString(e));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    c->last_embed_form = tiled ? 1 : 0;
+    c->last_embed_batches = (nrep + batch - 1) / batch;
     if (c->precision == 64) return import64(c);
     return C3D_OK;
 }
@@ -1807,6 +1836,8 @@ extern "C" int c3d_get_stat(const c3d_ctx* c, const char* key, double* value) {
     else if (!strcmp(key, "cluster_helper_waves")) *value = c->cl_ok ? (double)c->cl_plan.helpers : 0.0;
     else if (!strcmp(key, "cluster_wgs_per_cu")) *value = c->cl_ok ? (double)c->cl_plan.wgs_per_cu : 0.0;
     else if (!strcmp(key, "replica_groups")) *value = (double)active_groups(c);
+    else if (!strcmp(key, "embed_form")) *value = (double)c->last_embed_form;
+    else if (!strcmp(key, "embed_batches")) *value = (double)c->last_embed_batches;
     else if (!strcmp(key, "units_loaded")) *value = (double)g_units.loads.load();                       // code objects this PROCESS has loaded (all devices)
     else if (!strcmp(key, "units_loaded_mask")) *value = (double)g_units.loaded[c->device & (kMaxDevices - 1)].load();   // bit per unit, this context's device
     else return fail(C3D_ERR_INVALID, std::string("c3d_get_stat: unknown key ") + key);

@@ -7,7 +7,8 @@
 //                        32 x 32 tiles in LDS, three launches per 32 values of k
 //   k_dg_trial           per replica: d_ij = L + u (U - L), u ~ Philox4x32-10 counter (i, j, 2); stores d^2
 //   k_dg_eig             per replica, one workgroup: orthogonal iteration for the 3 leading eigenpairs of
-//                        B = -1/2 J D2 J (never formed: B v = -1/2 J (D2 (J v))), x = sqrt(lambda) v, centred
+//                        B = -1/2 J D2 J (never formed: B v = -1/2 J (D2 (J v))), x = sqrt(lambda) v, centred (n <= 4549: LDS)
+//   k_dg_matvec / k_dg_orth   the same iteration tiled over the device, vectors in global memory: any n, the same bits
 // Runs once per solve (not part of the SA-step hot loop): O(N^3) smoothing + O(iters N^2) per replica.
 #include "c3d_internal.h"
 
@@ -221,6 +222,118 @@ __device__ __forceinline__ float block_sum(float v, float* scratch, int tid) {
     return s;
 }
 
+// ---- the tiled eigen stage: k_dg_eig's iteration (below) split at its matrix pass, vectors in global memory -----------------------
+// k_dg_eig keeps a replica's nine vectors in the LDS of one CU (n <= 4549) and streams its n x n matrix iters + 1 times from that one
+// CU.  Here V, W, T (3 n floats each per replica) live in global memory, the matrix pass k_dg_matvec is a grid over (row tile, replica)
+// and k_dg_orth does what lies between two matrix passes, one workgroup per replica:
+//     orth(first: T = J V) | matvec | orth(W = -1/2 J W, Gram-Schmidt, T = J V) | matvec | ... | orth(last: W = -1/2 J W, Rayleigh, x)
+// Same bits as k_dg_eig: every sum runs in its order (a row's lanes take j = lane + 64 t as one fmaf chain each, then the butterfly
+// 32..1; a vector sum gives thread tid the elements tid + 1024 t, then block_sum) and every expression is spelled as it is there, so
+// that the compiler contracts the same products into the same fma (a -m gpu test compares the two forms bit for bit).
+constexpr int kMvRows = 4;                         // rows a wave takes together: one load of T's three values serves four rows
+constexpr int kMvBlock = 256;                      // four waves: 16 rows a workgroup
+constexpr int kMvTile = kMvRows * (kMvBlock / 64);
+
+__global__ __launch_bounds__(kMvBlock) void k_dg_matvec(const float* __restrict__ D2all, const float* __restrict__ Tall, int n,
+                                                       float* __restrict__ Wall) {
+    const int rep = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int i0 = blockIdx.x * kMvTile + wave * kMvRows;
+    if (i0 >= n) return;                           // (wave-uniform; no barrier in this kernel)
+    const float* D2 = D2all + (size_t)rep * n * n;
+    const float* T = Tall + (size_t)rep * 3 * n;
+    float* W = Wall + (size_t)rep * 3 * n;
+    const float* row[kMvRows];
+#pragma unroll
+    for (int r = 0; r < kMvRows; ++r) row[r] = D2 + (size_t)(i0 + r < n ? i0 + r : n - 1) * n;   // rows past the end: read the last, store nothing
+    float a0[kMvRows], a1[kMvRows], a2[kMvRows];
+#pragma unroll
+    for (int r = 0; r < kMvRows; ++r) a0[r] = a1[r] = a2[r] = 0.0f;
+#pragma unroll 2
+    for (int j = lane; j < n; j += 64) {
+        const float t0 = T[j], t1 = T[n + j], t2 = T[2 * n + j];
+#pragma unroll
+        for (int r = 0; r < kMvRows; ++r) {
+            const float d = row[r][j];
+            a0[r] = fmaf(d, t0, a0[r]); a1[r] = fmaf(d, t1, a1[r]); a2[r] = fmaf(d, t2, a2[r]);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < kMvRows; ++r) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            a0[r] += __shfl_xor(a0[r], off, 64); a1[r] += __shfl_xor(a1[r], off, 64); a2[r] += __shfl_xor(a2[r], off, 64);
+        }
+        if (lane == 0 && i0 + r < n) { W[i0 + r] = a0[r]; W[n + i0 + r] = a1[r]; W[2 * n + i0 + r] = a2[r]; }
+    }
+}
+
+// stage 0: T = J V (before the first matrix pass); 1: between two matrix passes; 2: after the last (Rayleigh quotients, coordinates).
+// A thread reads back only elements it wrote itself (i = tid + 1024 t in every loop, as in k_dg_eig): what crosses threads goes through
+// block_sum, what crosses workgroups (T, W) through the kernel boundary.
+__global__ __launch_bounds__(kEigBlock) void k_dg_orth(float* __restrict__ Vall, float* __restrict__ Wall, float* __restrict__ Tall, int n,
+                                                      int npad, int stage, float* __restrict__ x0, float* __restrict__ x1) {
+    __shared__ float scratch[kEigBlock / 64];
+    const int rep = blockIdx.x, tid = threadIdx.x;
+    float* V = Vall + (size_t)rep * 3 * n;
+    float* W = Wall + (size_t)rep * 3 * n;
+    float* T = Tall + (size_t)rep * 3 * n;
+    if (stage > 0) {
+        // W = -1/2 J W
+        for (int k = 0; k < 3; ++k) {
+            float s = 0.0f;
+            for (int i = tid; i < n; i += kEigBlock) s += W[k * n + i];
+            const float mean = block_sum(s, scratch, tid) / (float)n;
+            for (int i = tid; i < n; i += kEigBlock) W[k * n + i] = -0.5f * (W[k * n + i] - mean);
+        }
+        __syncthreads();
+    }
+    if (stage == 2) {
+        float lam[3];
+        for (int k = 0; k < 3; ++k) {   // Rayleigh quotients with the current orthonormal V
+            float s = 0.0f;
+            for (int i = tid; i < n; i += kEigBlock) s += V[k * n + i] * W[k * n + i];
+            lam[k] = block_sum(s, scratch, tid);
+        }
+        // coordinates, centred, into both parity buffers (SoA, padding untouched)
+        for (int k = 0; k < 3; ++k) {
+            const float sc = sqrtf(fmaxf(lam[k], 0.0f));
+            float s = 0.0f;
+            for (int i = tid; i < n; i += kEigBlock) s += sc * V[k * n + i];
+            const float mean = block_sum(s, scratch, tid) / (float)n;
+            for (int i = tid; i < n; i += kEigBlock) {
+                const float c = sc * V[k * n + i] - mean;
+                x0[((size_t)rep * 3 + k) * npad + i] = c;
+                x1[((size_t)rep * 3 + k) * npad + i] = c;
+            }
+        }
+        return;
+    }
+    if (stage == 1) {
+        for (int k = 0; k < 3; ++k) {   // modified Gram-Schmidt
+            for (int q = 0; q < k; ++q) {
+                float s = 0.0f;
+                for (int i = tid; i < n; i += kEigBlock) s += W[k * n + i] * V[q * n + i];
+                const float dot = block_sum(s, scratch, tid);
+                for (int i = tid; i < n; i += kEigBlock) W[k * n + i] -= dot * V[q * n + i];
+                __syncthreads();
+            }
+            float s = 0.0f;
+            for (int i = tid; i < n; i += kEigBlock) s += W[k * n + i] * W[k * n + i];
+            const float nrm = sqrtf(fmaxf(block_sum(s, scratch, tid), 1e-30f));
+            for (int i = tid; i < n; i += kEigBlock) V[k * n + i] = W[k * n + i] / nrm;
+            __syncthreads();
+        }
+    }
+    // T = J V  (subtract the mean of each vector)
+    for (int k = 0; k < 3; ++k) {
+        float s = 0.0f;
+        for (int i = tid; i < n; i += kEigBlock) s += V[k * n + i];
+        const float mean = block_sum(s, scratch, tid) / (float)n;
+        for (int i = tid; i < n; i += kEigBlock) T[k * n + i] = V[k * n + i] - mean;
+    }
+}
+
+// ---- the eigen stage of a replica in one workgroup (n <= kDgEigMaxBeads) --------------------------------------------------------
 // LDS: V[3][n] | W[3][n] | T[3][n] | scratch[16]
 __global__ __launch_bounds__(kEigBlock) void k_dg_eig(const float* __restrict__ D2all, const float* __restrict__ v0, int n,
                                                      int npad, int iters, float* __restrict__ x0, float* __restrict__ x1) {
@@ -326,14 +439,35 @@ hipError_t launch_dg_smooth(const float* tgt, int n, int npad, float b0, float l
     return hipGetLastError();
 }
 
-// trial distances and embedding from smoothed U, L.  v0: [nrep][3][n] starting vectors (host Philox normals); D2: nrep*n*n scratch.
+// trial distances and embedding from smoothed U, L, `batch` replicas at a time (1 <= batch; the same stream orders the reuse of D2).
+// v: [nrep][3][n] starting vectors (host Philox normals); D2: min(batch, nrep)*n*n scratch.  tiled = false: k_dg_eig (n <=
+// kDgEigMaxBeads; wt unused); true: the tiled form, which iterates v in place and needs wt = 2*[min(batch, nrep)][3][n] floats (W, T).
+// Trial distances and start vectors are keyed by replica id: the result does not depend on batch.
 hipError_t launch_dg_embed(const float* U, const float* L, int n, int npad, int nrep, uint64_t seed, uint32_t first_replica, int iters,
-                           const float* v0, float* D2, float* x0, float* x1, hipStream_t s) {
-    hipLaunchKernelGGL(k_dg_trial, dim3(n, nrep), dim3(256), 0, s, U, L, n, (uint32_t)(seed & 0xFFFFFFFFu),
-                       (uint32_t)(seed >> 32), first_replica, D2);
-    const size_t lds = sizeof(float) * ((size_t)9 * n + 16);
-    // (above 64 KB of dynamic LDS a kernel needs an allowance: preload_embed_unit set it when the unit was loaded)
-    hipLaunchKernelGGL(k_dg_eig, dim3(nrep), dim3(kEigBlock), lds, s, D2, v0, n, npad, iters, x0, x1);
+                           float* v, float* D2, float* wt, float* x0, float* x1, bool tiled, int batch, hipStream_t s) {
+    if (batch < 1 || (!tiled && n > kDgEigMaxBeads) || (tiled && !wt)) return hipErrorInvalidValue;
+    for (int r0 = 0; r0 < nrep; r0 += batch) {
+        const int nb = nrep - r0 < batch ? nrep - r0 : batch;
+        float* vb = v + (size_t)r0 * 3 * n;
+        float* xb0 = x0 + (size_t)r0 * 3 * npad;
+        float* xb1 = x1 + (size_t)r0 * 3 * npad;
+        hipLaunchKernelGGL(k_dg_trial, dim3(n, nb), dim3(256), 0, s, U, L, n, (uint32_t)(seed & 0xFFFFFFFFu),
+                           (uint32_t)(seed >> 32), first_replica + (uint32_t)r0, D2);
+        if (!tiled) {
+            const size_t lds = sizeof(float) * ((size_t)9 * n + 16);
+            // (above 64 KB of dynamic LDS a kernel needs an allowance: preload_embed_unit set it when the unit was loaded)
+            hipLaunchKernelGGL(k_dg_eig, dim3(nb), dim3(kEigBlock), lds, s, D2, vb, n, npad, iters, xb0, xb1);
+            continue;
+        }
+        float* W = wt;
+        float* T = wt + (size_t)(nrep < batch ? nrep : batch) * 3 * n;
+        const dim3 mv((n + kMvTile - 1) / kMvTile, nb);
+        hipLaunchKernelGGL(k_dg_orth, dim3(nb), dim3(kEigBlock), 0, s, vb, W, T, n, npad, 0, xb0, xb1);
+        for (int it = 0; it <= iters; ++it) {
+            hipLaunchKernelGGL(k_dg_matvec, mv, dim3(kMvBlock), 0, s, D2, T, n, W);
+            hipLaunchKernelGGL(k_dg_orth, dim3(nb), dim3(kEigBlock), 0, s, vb, W, T, n, npad, it == iters ? 2 : 1, xb0, xb1);
+        }
+    }
     return hipGetLastError();
 }
 

@@ -294,10 +294,12 @@ hipError_t launch_if_to_target(const double* IF, int n, int npad, double alpha, 
 
 // A7 (c3d_embed.hip): bead-level metric-matrix distance geometry for every replica, in two halves —
 // launch_dg_smooth: bounds from the targets, triangle smoothing of U and L (n*n each), L <= U;
-// launch_dg_embed: trial distances from the smoothed U, L and the 3 leading eigenvectors, into both parity buffers
+// launch_dg_embed: trial distances from the smoothed U, L and the 3 leading eigenvectors, into both parity buffers, `batch` replicas at a
+// time; the eigen stage as k_dg_eig (one workgroup per replica, 9 n + 16 floats of LDS: n <= kDgEigMaxBeads) or tiled (any n; same bits)
+constexpr int kDgEigMaxBeads = (int)((160 * 1024 / sizeof(float) - 16) / 9);   // 4549
 hipError_t launch_dg_smooth(const float* tgt, int n, int npad, float b0, float lower, float* U, float* L, hipStream_t s);
 hipError_t launch_dg_embed(const float* U, const float* L, int n, int npad, int nrep, uint64_t seed, uint32_t first_replica, int iters,
-                           const float* v0, float* D2, float* x0, float* x1, hipStream_t s);
+                           float* v, float* D2, float* wt, float* x0, float* x1, bool tiled, int batch, hipStream_t s);
 
 // K6 (c3d_score.hip): satisfied / sum-of-deviations / Spearman partial sums for every replica
 hipError_t launch_score(const float* xin, const float* tgt, const double* rankA, int n, int npad, int nrep, int range, int min_sep,

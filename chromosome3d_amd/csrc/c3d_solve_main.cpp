@@ -24,6 +24,7 @@ static void usage() {
             "usage: c3d_solve (--if <IF matrix> | --tbl <contact.tbl> --n <beads>) --out <dir> [--id <ID>]\n"
             "                 [-k <K=11>] [-a <alpha=0.5>] [-m <models=20>] [--seed <82364>] [--first-replica <0>]\n"
             "                 [--device <0>] [--min-steps <3000>] [--gtol <1e-2>] [--final-minimiser <1>] [--lbfgs] [--embed] [--no-graph] [--quiet]\n"
+            "                 [--embed-max-beads <4549>   the largest matrix --embed takes, up to 16384 (memory: 8 n^2 bytes + 4 n^2 per replica of a batch)]\n"
             "                 [--seq <one-letter residue codes | @fasta file>   residue names of the models (default: all MET)]\n"
             "                 [--accepted   also write <ID>a_<k>.pdb beside every <ID>_<k>.pdb, as CNS does for structures it accepts]\n");
 }
@@ -58,7 +59,7 @@ int main(int argc, char** argv) {
     double K = 11, alpha = 0.5, gtol = 1e-2;
     int final_min = 1;
     int lbfgs = 0;
-    int models = 20, device = 0, n_beads = 0, min_steps = 3000, use_graph = 1, quiet = 0, embed = 0, accepted = 0;
+    int models = 20, device = 0, n_beads = 0, min_steps = 3000, use_graph = 1, quiet = 0, embed = 0, embed_max_beads = 0, accepted = 0;
     unsigned long long seed = 82364ULL;
     unsigned first_rep = 0;
     for (int a = 1; a < argc; ++a) {
@@ -83,6 +84,7 @@ int main(int argc, char** argv) {
         else if (s == "--final-minimiser") final_min = atoi(next("--final-minimiser"));   // 0 = FIRE throughout (rounds 1-4), 1 = two-point steps then FIRE (default)
         else if (s == "--lbfgs") lbfgs = 1;   // the final stage as kind 8: L-BFGS, then FIRE (opt-in; the default stays kind 5)
         else if (s == "--embed") embed = 1;   // distance-geometry start (deck :1471-1525) instead of the random coil
+        else if (s == "--embed-max-beads") embed_max_beads = atoi(next("--embed-max-beads"));   // consent to the memory of an embedding beyond 4549 beads
         else if (s == "--no-graph") use_graph = 0;
         else if (s == "--quiet") quiet = 1;
         else if (s == "--accepted") accepted = 1;   // the deck's printaccept writes <ID>a_<k>.pdb for structures CNS accepts, beside the trial file (:1818-1828)
@@ -153,6 +155,7 @@ int main(int argc, char** argv) {
     CHECK(c3d_set_schedule(ctx, stages.data(), (int)stages.size(), &fire, (float)gtol, 250));
     CHECK(c3d_set_option(ctx, "use_graph", use_graph));
     CHECK(c3d_init_replicas(ctx, models, seed, first_rep));
+    if (embed_max_beads) CHECK(c3d_set_option(ctx, "embed_max_beads", embed_max_beads));
     if (embed) CHECK(c3d_embed_replicas(ctx, 50));
     CHECK(c3d_run(ctx));
     const double t_run = now_s();

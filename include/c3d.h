@@ -158,7 +158,19 @@ int c3d_set_schedule(c3d_ctx* ctx, const c3d_stage* stages, int n_stages, const 
  *                   256): 0.55 GB at 8192 beads, 2.1 GB at 16384; c3d_set_if_matrix takes 21 n^2 bytes more while it runs (the matrix
  *                   and its powers in fp64, the integer tenths, flags: 5.6 GB at 16384) and the host keeps the n^2 integer tenths (1 GB).
  *                   Beyond 5120 beads the fp32 step kernels run in their chunked form (below).  Not beyond 5120: precision 64 (2560),
- *                   symmetric 1 (c3d_init_replicas refuses it), c3d_embed_replicas (its own LDS limit: 4549 beads)
+ *                   symmetric 1 (c3d_init_replicas refuses it).  c3d_embed_replicas has a limit of its own (embed_max_beads, next)
+ *   embed_max_beads 4549 (default) .. 16384 (C3D_EMBED_MAX_BEADS_DEFAULT .. C3D_EMBED_MAX_BEADS_LIMIT), an integer (other values:
+ *                   C3D_ERR_INVALID): the largest n c3d_embed_replicas accepts.  Up to 4549 beads the eigen stage of a replica runs in one
+ *                   workgroup (9 n + 16 floats in the 160 KiB of LDS of a CU); beyond, in a tiled form with its vectors in global memory
+ *                   (same bits wherever both run).  Raising it is consent to the memory of a large embedding, freed when the call
+ *                   returns: 8 n^2 bytes for the smoothed bounds U and L, and 4 n^2 bytes of trial distances per replica of a batch —
+ *                   replicas are embedded in batches whose trial distances fit C3D_EMBED_SCRATCH_BYTES (4 GiB), one replica at least.
+ *                   At 16384 beads: 2 GiB + 1 GiB per replica, four replicas a batch, on top of the 2.1 GB such a context holds.
+ *                   (max_beads is needed as well beyond 5120; a precision-64 context embeds with the same fp32 kernels, up to its 2560)
+ *   embed_form      0 (default): the eigen stage of c3d_embed_replicas is k_dg_eig while n <= 4549 and the tiled form beyond; 1 = the
+ *                   tiled form at every n.  Same bits either way (test and measurement knob; stat "embed_form")
+ *   embed_batch     0 (default): replicas per batch of c3d_embed_replicas by the scratch budget; k > 0 = k at a time.  Trial distances
+ *                   and start vectors are keyed by replica id: same bits whatever the batch (test knob; stat "embed_batches")
  *   column_chunk    0 (default): where the per-step kernels read a column's coordinates — 0 = the library's choice: the replica's whole
  *                   coordinate array staged in LDS while it fits (n <= 5120: exactly the kernels of earlier releases), beyond that the
  *                   chunked form, which streams 1024 columns at a time through two LDS buffers; 256, 1024 or 2048 = the chunked
@@ -199,6 +211,10 @@ int c3d_set_option(c3d_ctx* ctx, const char* key, double value);
 /* the option max_beads: its default and its largest value */
 #define C3D_MAX_BEADS_DEFAULT 5120
 #define C3D_MAX_BEADS_LIMIT 16384
+/* the option embed_max_beads: its default and its largest value; the trial-distance scratch a batch of c3d_embed_replicas stays within */
+#define C3D_EMBED_MAX_BEADS_DEFAULT 4549
+#define C3D_EMBED_MAX_BEADS_LIMIT 16384
+#define C3D_EMBED_SCRATCH_BYTES (4ull << 30)
 
 /* Process-wide switches, to be set before the first c3d_create (no environment variable is read by the library):
  *   preload         which code objects c3d_create loads before it returns (the library never leaves a load to the runtime's first-launch
@@ -219,8 +235,9 @@ int c3d_init_replicas(c3d_ctx* ctx, int n_replicas, uint64_t seed, uint32_t firs
 /* A7 (deck chromosome3D.pl:1471-1525, bead-level restatement): replace the random-coil start of every
  * replica by a metric-matrix distance-geometry embedding — bounds from the restraints, triangle
  * smoothing, random trial distances (Philox, keyed by replica id), 3 leading eigenvectors found with
- * `iters` orthogonal iterations (50 is plenty).  Call between c3d_init_replicas and c3d_run.  At most 4549 beads: the eigen stage
- * keeps 9 n + 16 floats of a replica in the 160 KiB of LDS of one CU (C3D_ERR_INVALID beyond). */
+ * `iters` orthogonal iterations (50 is plenty).  Call between c3d_init_replicas and c3d_run.  At most 4549 beads by default (the eigen stage
+ * keeps 9 n + 16 floats of a replica in the 160 KiB of LDS of one CU), up to 16384 after c3d_set_option("embed_max_beads", n), where the eigen
+ * stage runs tiled over the device and the replicas are embedded in batches (memory: see the option); C3D_ERR_INVALID beyond, before any launch. */
 int c3d_embed_replicas(c3d_ctx* ctx, int iters);
 /* overwrite coordinates (n_replicas*n*3, xyz interleaved) — tests and restarts */
 int c3d_set_coords(c3d_ctx* ctx, const float* xyz);
@@ -253,7 +270,8 @@ int c3d_last_timing(const c3d_ctx* ctx, double* ms_total, long* steps, long* lau
  * on the host in the reference's operation order), "k1_patched" (how many of those changed, since c3d_create),
  * "rms_force" (largest RMS force component over the replicas at the last minimiser step: the quantity c3d_run holds
  * against gtol, the stand-in for L-BFGS's convergence test of chromosome3D.pl:1800-1803), "lbfgs_steps" (L-BFGS steps run, kind 8),
- * "lbfgs_resets" (memory drops of the last kind-8 stage since its first step, summed over the replicas: read from the device). */
+ * "lbfgs_resets" (memory drops of the last kind-8 stage since its first step, summed over the replicas: read from the device),
+ * "embed_form" (the eigen stage the last c3d_embed_replicas ran: 0 k_dg_eig, 1 tiled), "embed_batches" (replica batches of that call). */
 int c3d_get_stat(const c3d_ctx* ctx, const char* key, double* value);
 /* Test hook, no reference counterpart: the multi-step kernel's hand-off trusts a 16-byte unit once its tag word matches — i.e. that a
  * 16-byte aligned store is never observed half-written by a 16-byte load on gfx950.  This runs that exact store / load pair (one producer

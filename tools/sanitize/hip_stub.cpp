@@ -184,7 +184,7 @@ hipError_t launch_if_to_target(const double* IF, int n, int npad, double alpha, 
     return hipSuccess;
 }
 hipError_t launch_dg_smooth(const float*, int, int, float, float, float*, float*, hipStream_t) { LaunchScope ls; return hipSuccess; }
-hipError_t launch_dg_embed(const float*, const float*, int, int, int, uint64_t, uint32_t, int, const float*, float*, float*, float*, hipStream_t) { LaunchScope ls; return hipSuccess; }
+hipError_t launch_dg_embed(const float*, const float*, int, int, int, uint64_t, uint32_t, int, float*, float*, float*, float*, float*, bool, int, hipStream_t) { LaunchScope ls; return hipSuccess; }
 hipError_t launch_score(const float*, const float*, const double*, int, int, int, int, int, unsigned, double, double, double, double*, unsigned*, unsigned*,
                         double* partial, int* overflow, hipStream_t) {
     LaunchScope ls;
