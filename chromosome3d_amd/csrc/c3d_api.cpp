@@ -213,6 +213,8 @@ struct c3d_ctx {
     unsigned* h_tmo_dev = nullptr;         // its device address
 
     long rank_prefetch_hits = 0;
+    int device_ranks = 0;                  // option device_ranks: who ranks the IF matrix for c3d_score_replicas (c3d.h)
+    long device_rank_runs = 0, score_wide_runs = 0;   // stats: calls that ranked on the device / that took the sized-histogram re-run
     long k1_recomputed = 0, k1_patched = 0;   // K1: near-tie elements redone on the host in the reference's order / changed by it
     long graph_captures = 0, graph_launches = 0, step_launches = 0, resident_launches = 0, cluster_launches = 0;
     bool has_two_point = false;            // the program holds two-point minimiser steps (run_ops splits ranges at their borders)
@@ -1246,6 +1248,11 @@ extern "C" int c3d_set_option(c3d_ctx* c, const char* key, double value) {
     else if (!strcmp(key, "cluster_inject_incomplete")) c->inject_incomplete = value != 0;   // test hook
     else if (!strcmp(key, "cluster_num_xcc")) { c->num_xcc = (int)value; stale = STALE_REPLICAS; }   // test hook: pretend a partitioned device
     else if (!strcmp(key, "prefetch_ranks")) c->prefetch_ranks = value != 0;
+    else if (!strcmp(key, "device_ranks")) {       // who ranks the IF matrix for c3d_score_replicas
+        if (value != -1 && value != 0 && value != 1)
+            return fail(C3D_ERR_INVALID, "device_ranks is 0 (the device beyond 5120 beads), 1 (the device for every symmetric matrix) or -1 (the host)");
+        c->device_ranks = (int)value;
+    }
     else if (!strcmp(key, "final_minimiser_steps")) {
         if (value < 2) return fail(C3D_ERR_INVALID, "c3d_set_option: final_minimiser_steps >= 2");
         c->bb_steps = (int)value;
@@ -1826,6 +1833,8 @@ extern "C" int c3d_get_stat(const c3d_ctx* c, const char* key, double* value) {
     else if (!strcmp(key, "k1_patched")) *value = (double)c->k1_patched;
     else if (!strcmp(key, "last_path")) *value = (double)c->last_path;
     else if (!strcmp(key, "rank_prefetch_hits")) *value = (double)c->rank_prefetch_hits;
+    else if (!strcmp(key, "device_rank_runs")) *value = (double)c->device_rank_runs;
+    else if (!strcmp(key, "score_wide_runs")) *value = (double)c->score_wide_runs;
     else if (!strcmp(key, "cluster_xcd_count")) *value = (double)c->xcd_count;
     else if (!strcmp(key, "cluster_xcd_base")) *value = (double)c->xcd_base;
     else if (!strcmp(key, "cluster_ok")) *value = c->cl_ok ? 1.0 : 0.0;
@@ -1901,8 +1910,90 @@ extern "C" int c3d_get_energies(c3d_ctx* c, double* e) {
     return c3d_eval(c, 1.0f, 1.0f, repel_s, nullptr, e);
 }
 
+// c3d_score_replicas' scratch inside d_score (byte offsets): the rank matrix (which first holds the matrix itself when the device ranks it),
+// rounded coordinates, per-row sums, the two fixed histograms, the overflow flag, the replicas' bounding boxes (read by the re-run of a
+// wide call only) and, when the device ranks, the sort keys, the per-row sums of squares and the asymmetry flag
+struct ScoreScratch {
+    size_t rank = 0, xr = 0, part = 0, hist = 0, below = 0, ovf = 0, box = 0, keys = 0, saa = 0, asym = 0, total = 0;
+};
+static ScoreScratch score_layout(int n, int nrep, unsigned nbins, size_t key_slots) {
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t b_rank = up(sizeof(double) * (size_t)n * n), b_xr = up(sizeof(double) * 3 * (size_t)n * nrep), b_part = up(sizeof(double) * 4 * (size_t)n * nrep),
+                 b_hist = up(sizeof(unsigned) * (size_t)nbins * nrep);
+    ScoreScratch L;
+    L.xr = b_rank; L.part = L.xr + b_xr; L.hist = L.part + b_part; L.below = L.hist + b_hist; L.ovf = L.below + b_hist;
+    L.box = L.ovf + 256;
+    L.total = L.box + up(sizeof(double) * 6 * (size_t)nrep);
+    if (key_slots) {
+        L.keys = L.total; L.saa = L.keys + up(sizeof(unsigned long long) * key_slots); L.asym = L.saa + up(sizeof(double) * (size_t)n);
+        L.total = L.asym + 256;
+    }
+    return L;
+}
+// one scratch allocation the context keeps (a hipMalloc / hipFree pair of the two 21 MB histograms alone cost about a millisecond per call)
+static int score_scratch(c3d_ctx* c, size_t need) {
+    if (need <= c->d_score_bytes) return C3D_OK;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    dev_free(c->d_score);
+    c->d_score_bytes = 0;
+    HIP_TRY(hipMalloc(&c->d_score, need));
+    c->d_score_bytes = need;
+    return C3D_OK;
+}
+// pairs i < j, j - i >= range, of an n x n matrix: half the ranked multiset
+static size_t rank_half_pairs(int n, int range) {
+    const size_t w = n > range ? (size_t)(n - range) : 0;
+    return w * (w + 1) / 2;
+}
+
+// The IF ranks on the device (c3d_score.hip k_rank_*): the matrix goes into the rank slot of the scratch and is ranked there.  *symmetric =
+// false (and nothing else) when M(i,j) != M(j,i) for a ranked pair: the caller ranks on the host.  saa = the n row sums added in index order.
+static int device_if_ranks(c3d_ctx* c, const double* IF, int range, const ScoreScratch& L, size_t mh, size_t slots, double* saa, bool* symmetric) {
+    const int n = c->n;
+    char* const base = static_cast<char*>(c->d_score);
+    double* const d_rank = reinterpret_cast<double*>(base + L.rank);
+    unsigned long long* const d_keys = reinterpret_cast<unsigned long long*>(base + L.keys);
+    HIP_TRY(hipMemcpyAsync(d_rank, IF, sizeof(double) * (size_t)n * n, hipMemcpyHostToDevice, c->stream));
+    hipError_t e = c3d::launch_if_rank_keys(d_rank, n, range, d_keys, mh, slots, reinterpret_cast<int*>(base + L.asym), c->stream);
+    if (e != hipSuccess) return fail(C3D_ERR_HIP, std::string("rank key launch: ") + hipGetErrorString(e));
+    if (int rc = read_back(c, base + L.asym, sizeof(int))) return rc;
+    *symmetric = *static_cast<const int*>(c->h_stage) == 0;
+    if (!*symmetric) return C3D_OK;
+    const double ma = 0.5 * (2.0 * (double)mh + 1.0);
+    e = c3d::launch_if_rank_sort(d_rank, n, range, d_keys, mh, slots, ma, reinterpret_cast<double*>(base + L.saa), c->stream);
+    if (e != hipSuccess) return fail(C3D_ERR_HIP, std::string("rank sort launch: ") + hipGetErrorString(e));
+    if (int rc = read_back(c, base + L.saa, sizeof(double) * (size_t)n)) return rc;
+    const double* const rows = static_cast<const double*>(c->h_stage);
+    double sum = 0;
+    for (int i = 0; i < n; ++i) sum += rows[i];      // fixed order: deterministic
+    *saa = sum;
+    return C3D_OK;
+}
+
+// test hook: the rank matrix, m and saa as the device computes them for c3d_score_replicas (whatever the option device_ranks says)
+extern "C" int c3d_debug_if_ranks(c3d_ctx* c, const double* IF, int range, double* rank, double* saa, size_t* m) {
+    if (!c || !IF || !rank || !saa || !m || range < 1) return fail(C3D_ERR_INVALID, "c3d_debug_if_ranks: bad arguments");
+    if (!c->have_targets) return fail(C3D_ERR_INVALID, "c3d_debug_if_ranks: set the IF matrix / restraints first");
+    C3D_ENTRY(c, unit_bit(UNIT_SCORE));
+    const int n = c->n;
+    const size_t mh = rank_half_pairs(n, range), slots = c3d::if_rank_key_slots(mh);
+    if (mh < 1) return fail(C3D_ERR_INVALID, "c3d_debug_if_ranks: range leaves no pairs");
+    const ScoreScratch L = score_layout(n, c->have_replicas ? c->nrep : 0, 1u << 18, slots);
+    if (int rc = score_scratch(c, L.total)) return rc;
+    bool symmetric = false;
+    if (int rc = device_if_ranks(c, IF, range, L, mh, slots, saa, &symmetric)) return rc;
+    if (!symmetric) return fail(C3D_ERR_INVALID, "c3d_debug_if_ranks: the matrix is not symmetric over the ranked pairs (the host ranks such a matrix)");
+    HIP_TRY(hipMemcpyAsync(rank, static_cast<char*>(c->d_score) + L.rank, sizeof(double) * (size_t)n * n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    *m = 2 * mh;
+    return C3D_OK;
+}
+
 // K6 on the device: count_satisfied_tbl_rows / sum_noe_dev (:447-485, :581-600) and, when IF is given,
 // spearman_IF_pdb.pl's coefficient for every replica, from the coordinates resident on the GPU.
+// Distances are histogrammed in 2^18 bins of 0.001 A; a call in which a pair is further apart is scored again with a histogram sized to
+// the models (below).  The IF ranks come from the helper thread of c3d_set_if_matrix, from c3d::if_pair_ranks or from the device (option
+// device_ranks; c3d.h).
 extern "C" int c3d_score_replicas(c3d_ctx* c, const double* IF, int range, int32_t* satisfied, double* sum_dev, double* rho) {
     if (!c || range < 1) return fail(C3D_ERR_INVALID, "c3d_score_replicas: bad arguments");
     if (!c->have_replicas) return fail(C3D_ERR_INVALID, "c3d_score_replicas: call c3d_init_replicas first");
@@ -1913,35 +2004,41 @@ extern "C" int c3d_score_replicas(c3d_ctx* c, const double* IF, int range, int32
     std::vector<double> rankA;
     size_t m = 0;
     double ma = 0, saa = 0;
-    // one scratch allocation the context keeps (a hipMalloc / hipFree pair of the two 21 MB histograms alone cost about a millisecond per call)
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t b_rank = up(sizeof(double) * (size_t)n * n), b_xr = up(sizeof(double) * 3 * (size_t)n * nrep), b_part = up(sizeof(double) * 4 * (size_t)n * nrep),
-                 b_hist = up(sizeof(unsigned) * (size_t)nbins * nrep);
-    const size_t need = b_rank + b_xr + b_part + 2 * b_hist + 256;
-    if (need > c->d_score_bytes) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        dev_free(c->d_score);
-        c->d_score_bytes = 0;
-        HIP_TRY(hipMalloc(&c->d_score, need));
-        c->d_score_bytes = need;
-    }
-    char* const base = static_cast<char*>(c->d_score);
-    struct { double* p; } d_rank{reinterpret_cast<double*>(base)}, d_xr{reinterpret_cast<double*>(base + b_rank)}, d_part{reinterpret_cast<double*>(base + b_rank + b_xr)};
-    struct { unsigned* p; } d_hist{reinterpret_cast<unsigned*>(base + b_rank + b_xr + b_part)}, d_below{reinterpret_cast<unsigned*>(base + b_rank + b_xr + b_part + b_hist)};
-    struct { int* p; } d_ovf{reinterpret_cast<int*>(base + b_rank + b_xr + b_part + 2 * b_hist)};
-    if (IF && rho) {
-        // the ranks c3d_set_if_matrix started on its helper thread, if this is the same matrix (same numbers: memcmp) and range
+    const bool spearman = IF && rho;
+    // the ranks c3d_set_if_matrix started on its helper thread, if this is the same matrix (same numbers: memcmp) and range
+    bool prefetched = false;
+    if (spearman) {
         c->ifr.join();
-        const std::vector<double>* ranks = &rankA;
-        if (c->ifr.valid && c->ifr.n == n && c->ifr.range == range && c->ifr.matrix.size() == (size_t)n * n &&
-            memcmp(c->ifr.matrix.data(), IF, sizeof(double) * (size_t)n * n) == 0) {
-            ranks = &c->ifr.rank; m = c->ifr.m; ma = c->ifr.mean; saa = c->ifr.saa;
-            ++c->rank_prefetch_hits;
-        } else {
-            c3d::if_pair_ranks(IF, n, range, rankA, m, ma, saa);
+        prefetched = c->ifr.valid && c->ifr.n == n && c->ifr.range == range && c->ifr.matrix.size() == (size_t)n * n &&
+                     memcmp(c->ifr.matrix.data(), IF, sizeof(double) * (size_t)n * n) == 0;
+    }
+    // device_ranks: 1 = the device ranks every symmetric matrix, 0 = those beyond the default bead limit that no prefetch covers, -1 = none
+    const bool try_device = spearman && (c->device_ranks > 0 || (c->device_ranks == 0 && n > C3D_MAX_BEADS_DEFAULT && !prefetched));
+    const size_t mh = rank_half_pairs(n, range), slots = try_device ? c3d::if_rank_key_slots(mh) : 0;
+    const ScoreScratch L = score_layout(n, nrep, nbins, slots);
+    if (int rc = score_scratch(c, L.total)) return rc;
+    char* const base = static_cast<char*>(c->d_score);
+    struct { double* p; } d_rank{reinterpret_cast<double*>(base + L.rank)}, d_xr{reinterpret_cast<double*>(base + L.xr)}, d_part{reinterpret_cast<double*>(base + L.part)};
+    struct { unsigned* p; } d_hist{reinterpret_cast<unsigned*>(base + L.hist)}, d_below{reinterpret_cast<unsigned*>(base + L.below)};
+    struct { int* p; } d_ovf{reinterpret_cast<int*>(base + L.ovf)};
+    if (spearman) {
+        bool ranked = false;
+        if (try_device) {
+            if (2 * mh < 2) return fail(C3D_ERR_INVALID, "c3d_score_replicas: range leaves no pairs");
+            if (int rc = device_if_ranks(c, IF, range, L, mh, slots, &saa, &ranked)) return rc;
+            if (ranked) { m = 2 * mh; ma = 0.5 * ((double)m + 1.0); ++c->device_rank_runs; }
         }
-        if (m < 2) return fail(C3D_ERR_INVALID, "c3d_score_replicas: range leaves no pairs");
-        HIP_TRY(hipMemcpyAsync(d_rank.p, ranks->data(), sizeof(double) * ranks->size(), hipMemcpyHostToDevice, c->stream));
+        if (!ranked) {
+            const std::vector<double>* ranks = &rankA;
+            if (prefetched && c->device_ranks <= 0) {
+                ranks = &c->ifr.rank; m = c->ifr.m; ma = c->ifr.mean; saa = c->ifr.saa;
+                ++c->rank_prefetch_hits;
+            } else {
+                c3d::if_pair_ranks(IF, n, range, rankA, m, ma, saa);
+            }
+            if (m < 2) return fail(C3D_ERR_INVALID, "c3d_score_replicas: range leaves no pairs");
+            HIP_TRY(hipMemcpyAsync(d_rank.p, ranks->data(), sizeof(double) * ranks->size(), hipMemcpyHostToDevice, c->stream));
+        }
     }
     else d_rank.p = nullptr;
     const double mb = 0.5 * ((double)m + 1.0);     // mean of the ranks 1..m, ties or not
@@ -1950,13 +2047,56 @@ extern "C" int c3d_score_replicas(c3d_ctx* c, const double* IF, int range, int32
     if (e != hipSuccess) return fail(C3D_ERR_HIP, std::string("score launch: ") + hipGetErrorString(e));
     const size_t part_bytes = sizeof(double) * 4 * (size_t)n * nrep;
     if (int rc = ensure_stage(c, part_bytes + 64)) return rc;
-    char* const stage = static_cast<char*>(c->h_stage);
+    char* stage = static_cast<char*>(c->h_stage);
     HIP_TRY(hipMemcpyAsync(stage, d_part.p, part_bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(stage + part_bytes, d_ovf.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    if (*reinterpret_cast<const int*>(stage + part_bytes)) {
+        // A pair lies beyond the fixed histogram: the same kernels again with a histogram that holds the bounding box of the widest
+        // replica's rounded coordinates (the diagonal bounds every pair distance), replicas in batches whose two histograms fit
+        // C3D_SCORE_SCRATCH_BYTES.  Replicas are independent and the histogram is integer: same numbers whatever the batch, and for a
+        // replica that fitted the fixed histogram the numbers of the first pass.  Up to 50 000 A, the limit of c3d_spearman_if_dist_batch:
+        // a box wider than that along one axis holds such a pair for certain (the two beads at its ends) and is refused at once; a box whose
+        // diagonal alone is longer may hold none (the host accepts such a model), so it gets the largest histogram and the pass decides.
+        constexpr unsigned kMaxBins = 50000001u;             // distances 0 .. 50 000.000 A in thousandths
+        const char* const too_far = "c3d_score_replicas: a pair distance exceeds 50000 A (the limit of device and host scoring)";
+        double* const d_box = reinterpret_cast<double*>(base + L.box);
+        e = c3d::launch_score_bbox(d_xr.p, n, nrep, d_box, c->stream);
+        if (e != hipSuccess) return fail(C3D_ERR_HIP, std::string("score launch: ") + hipGetErrorString(e));
+        if (int rc = read_back(c, d_box, sizeof(double) * 6 * (size_t)nrep)) return rc;
+        const double* const hb = static_cast<const double*>(c->h_stage);
+        double widest = 0;
+        for (int r = 0; r < nrep; ++r) {
+            double d2 = 0;
+            for (int k = 0; k < 3; ++k) {
+                const double w = hb[6 * r + 2 * k + 1] - hb[6 * r + 2 * k];
+                if (!(w <= 50000.001)) return fail(C3D_ERR_INVALID, too_far);      // also an infinite coordinate
+                d2 += w * w;
+            }
+            widest = std::max(widest, sqrt(d2));
+        }
+        const double want = ceil(1000.0 * widest) + 2.0;
+        const unsigned wbins = want <= (double)kMaxBins ? (unsigned)want : kMaxBins;
+        const size_t per_rep = 2 * sizeof(unsigned) * (size_t)wbins;
+        const int batch = (int)std::min<size_t>((size_t)nrep, std::max<size_t>(1, (size_t)C3D_SCORE_SCRATCH_BYTES / per_rep));
+        DevTmp<unsigned> wide;
+        HIP_TRY(hipMalloc(&wide.p, per_rep * batch));
+        HIP_TRY(hipMemsetAsync(d_ovf.p, 0, sizeof(int), c->stream));
+        for (int r0 = 0; r0 < nrep; r0 += batch) {
+            const int nb = std::min(batch, nrep - r0);
+            e = c3d::launch_score_wide(d_xr.p + (size_t)r0 * 3 * n, c->buf.tgt, d_rank.p, n, c->npad, nb, range, c->model.min_sep, wbins, ma, mb, 0.5,
+                                       wide.p, wide.p + (size_t)wbins * batch, d_part.p + (size_t)r0 * n * 4, d_ovf.p, c->stream);
+            if (e != hipSuccess) return fail(C3D_ERR_HIP, std::string("score launch: ") + hipGetErrorString(e));
+        }
+        if (int rc = ensure_stage(c, part_bytes + 64)) return rc;
+        stage = static_cast<char*>(c->h_stage);
+        HIP_TRY(hipMemcpyAsync(stage, d_part.p, part_bytes, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(stage + part_bytes, d_ovf.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (*reinterpret_cast<const int*>(stage + part_bytes)) return fail(C3D_ERR_INVALID, too_far);
+        ++c->score_wide_runs;
+    }
     const double* const part = reinterpret_cast<const double*>(stage);
-    const int ovf = *reinterpret_cast<const int*>(stage + part_bytes);
-    if (ovf) return fail(C3D_ERR_INVALID, "c3d_score_replicas: a pair distance exceeds 262 A (device histogram range)");
     for (int r = 0; r < nrep; ++r) {
         double sab = 0, sbb = 0, sat = 0, dev = 0;
         for (int i = 0; i < n; ++i) {    // fixed order: deterministic

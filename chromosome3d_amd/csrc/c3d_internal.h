@@ -305,6 +305,25 @@ hipError_t launch_dg_embed(const float* U, const float* L, int n, int npad, int 
 hipError_t launch_score(const float* xin, const float* tgt, const double* rankA, int n, int npad, int nrep, int range, int min_sep,
                         unsigned nbins, double ma, double mb, double relax, double* xr, unsigned* hist, unsigned* below,
                         double* partial, int* overflow, hipStream_t s);
+// the same histogram, prefix and sums with any `nbins`, for the `nrep` replicas xr and partial start at (c3d_score_replicas runs it in
+// batches when launch_score reported overflow); launch_score_bbox: box[rep][comp][0..1] = min, max of the rounded coordinates
+hipError_t launch_score_bbox(const double* xr, int n, int nrep, double* box, hipStream_t s);
+hipError_t launch_score_wide(const double* xr, const float* tgt, const double* rankA, int n, int npad, int nrep, int range, int min_sep,
+                             unsigned nbins, double ma, double mb, double relax, unsigned* hist, unsigned* below, double* partial,
+                             int* overflow, hipStream_t s);
+// IF ranks of a symmetric matrix on the device.  M (n*n fp64, device) holds the matrix; mh = (n-range)(n-range+1)/2 upper-triangle pairs
+// |i-j| >= range; keys = if_rank_key_slots(mh) 64-bit slots.  launch_if_rank_keys fills the keys and raises *asym if M(i,j) != M(j,i) for
+// one of those pairs; launch_if_rank_sort sorts them, overwrites M with the rank matrix of c3d::if_pair_ranks (0 inside the band) and
+// leaves saa_rows[i] = sum_j (rank(i,j) - ma)^2.
+constexpr int kRankTile = 4096;
+inline size_t if_rank_key_slots(size_t mh) {
+    size_t slots = kRankTile;
+    while (slots < mh) slots <<= 1;
+    return slots;
+}
+hipError_t launch_if_rank_keys(const double* M, int n, int range, unsigned long long* keys, size_t mh, size_t slots, int* asym, hipStream_t s);
+hipError_t launch_if_rank_sort(double* M, int n, int range, unsigned long long* keys, size_t mh, size_t slots, double ma, double* saa_rows,
+                               hipStream_t s);
 
 // Target matrix entry: NOE target in Angstrom, 0 = no restraint (host c3d_set_restraints and K1).
 inline float encode_target_host(float t) { return t > 0 ? t : 0.0f; }

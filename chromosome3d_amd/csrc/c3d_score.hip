@@ -10,7 +10,9 @@
 //   k_score_scan    exclusive prefix of the histogram (one workgroup per replica)
 //   k_score_corr    sum (ra - ma)(rb - mb), sum (rb - mb)^2 with rb = below[dq] + (cnt[dq] + 1)/2, and the
 //                   satisfied / sum-of-deviation tallies over the restrained pairs; per-block fp64 partials
-// The IF ranks ra (one N x N fp64 matrix per input matrix) are computed once on the host.
+// The IF ranks ra (one N x N fp64 matrix per input matrix) come from the host (c3d::if_pair_ranks) or, for large symmetric matrices, from
+// the device (k_rank_*: a key-only bitonic sort of the upper triangle and two binary searches per pair; option device_ranks).
+// A call whose models do not fit the fixed histogram is scored again by launch_score_wide with a histogram sized from k_score_bbox.
 #include "c3d_internal.h"
 
 namespace c3d {
@@ -117,18 +119,175 @@ __global__ __launch_bounds__(256) void k_score_corr(const double* __restrict__ x
     if (tid < 4) partial[((size_t)rep * n + i) * 4 + tid] = red[tid][0];
 }
 
-hipError_t launch_score(const float* xin, const float* tgt, const double* rankA, int n, int npad, int nrep, int range, int min_sep,
-                        unsigned nbins, double ma, double mb, double relax, double* xr, unsigned* hist, unsigned* below,
-                        double* partial, int* overflow, hipStream_t s) {
+// ---- models wider than the fixed histogram --------------------------------------------------------------------------------------------
+// box[rep][comp][0..1] = min, max of the rounded coordinates of a replica
+__global__ __launch_bounds__(256) void k_score_bbox(const double* __restrict__ xr_all, int n, double* __restrict__ box) {
+    __shared__ double lo[256], hi[256];
+    const int rep = blockIdx.x, comp = blockIdx.y, tid = threadIdx.x;
+    const double* x = xr_all + ((size_t)rep * 3 + comp) * n;
+    double a = x[0], b = x[0];
+    for (int i = tid; i < n; i += 256) { a = fmin(a, x[i]); b = fmax(b, x[i]); }
+    lo[tid] = a; hi[tid] = b;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s) { lo[tid] = fmin(lo[tid], lo[tid + s]); hi[tid] = fmax(hi[tid], hi[tid + s]); }
+        __syncthreads();
+    }
+    if (tid == 0) { box[(rep * 3 + comp) * 2] = lo[0]; box[(rep * 3 + comp) * 2 + 1] = hi[0]; }
+}
+
+hipError_t launch_score_bbox(const double* xr, int n, int nrep, double* box, hipStream_t s) {
+    hipLaunchKernelGGL(k_score_bbox, dim3(nrep, 3), dim3(256), 0, s, xr, n, box);
+    return hipGetLastError();
+}
+
+// histogram, prefix and sums for `nrep` replicas whose rounded coordinates xr and sums `partial` start at the first of them, with `nbins`
+// bins per replica; `overflow` is only ever raised (the caller clears it once for all batches)
+hipError_t launch_score_wide(const double* xr, const float* tgt, const double* rankA, int n, int npad, int nrep, int range, int min_sep,
+                             unsigned nbins, double ma, double mb, double relax, unsigned* hist, unsigned* below, double* partial,
+                             int* overflow, hipStream_t s) {
     hipError_t e = hipMemsetAsync(hist, 0, sizeof(unsigned) * (size_t)nbins * nrep, s);
     if (e != hipSuccess) return e;
-    e = hipMemsetAsync(overflow, 0, sizeof(int), s);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_score_round, dim3((3 * n + 255) / 256, nrep), dim3(256), 0, s, xin, n, npad, xr);
     hipLaunchKernelGGL(k_score_hist, dim3(n, nrep), dim3(256), 0, s, xr, n, range, nbins, hist, overflow);
     hipLaunchKernelGGL(k_score_scan, dim3(nrep), dim3(1024), 0, s, hist, nbins, below);
     hipLaunchKernelGGL(k_score_corr, dim3(n, nrep), dim3(256), 0, s, xr, tgt, rankA, n, npad, range, min_sep, nbins, hist, below, ma,
                        mb, relax, partial, overflow);
+    return hipGetLastError();
+}
+
+// the first pass of every call: all replicas, rounded coordinates first, the fixed histogram
+hipError_t launch_score(const float* xin, const float* tgt, const double* rankA, int n, int npad, int nrep, int range, int min_sep,
+                        unsigned nbins, double ma, double mb, double relax, double* xr, unsigned* hist, unsigned* below,
+                        double* partial, int* overflow, hipStream_t s) {
+    hipError_t e = hipMemsetAsync(overflow, 0, sizeof(int), s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_score_round, dim3((3 * n + 255) / 256, nrep), dim3(256), 0, s, xin, n, npad, xr);
+    return launch_score_wide(xr, tgt, rankA, n, npad, nrep, range, min_sep, nbins, ma, mb, relax, hist, below, partial, overflow, s);
+}
+
+// ---- IF ranks on the device -----------------------------------------------------------------------------------------------------------
+// The average ranks of c3d::if_pair_ranks for a symmetric matrix: the multiset in which every upper-triangle value |i-j| >= range appears
+// twice; a tie group at sorted half-list positions k..e has rank k + e + 1.5.  Equal keys are interchangeable, so the keys alone are
+// sorted (order_key of c3d_host.cpp; -0.0 takes the key of +0.0, which the host's value comparison ties it with) and every pair finds
+// its group's bounds by binary search.  The sort is a bitonic network over `slots` keys (a power of two >= kRankTile, padded with the
+// largest key): the strides below kRankTile run in LDS (32 KiB a workgroup), the others one pass over global memory each.
+__device__ __forceinline__ unsigned long long rank_key(double d) {
+    unsigned long long u = (unsigned long long)__double_as_longlong(d);
+    if ((u << 1) == 0) u = 0;
+    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+
+// first key of row i in the key array: rows 0..i-1 hold w, w-1, ... keys (w = n - range)
+__device__ __forceinline__ size_t rank_row_offset(int i, int w) { return (size_t)i * w - (size_t)i * (i - 1) / 2; }
+
+__global__ __launch_bounds__(256) void k_rank_keys(const double* __restrict__ M, int n, int range, unsigned long long* __restrict__ keys,
+                                                  size_t mh, size_t slots, int* __restrict__ asym) {
+    const int i = blockIdx.x, tid = threadIdx.x;
+    if (i + range < n) {
+        unsigned long long* row = keys + rank_row_offset(i, n - range);
+        for (int j = i + range + tid; j < n; j += 256) {
+            const double a = M[(size_t)i * n + j];
+            if (a != M[(size_t)j * n + i]) *asym = 1;
+            row[j - i - range] = rank_key(a);
+        }
+    }
+    for (size_t p = mh + (size_t)i * 256 + tid; p < slots; p += (size_t)gridDim.x * 256) keys[p] = ~0ull;
+}
+
+// one tile of kRankTile keys: the network's stages size_first..size_last, each from stride min(size, kRankTile) / 2 down
+__global__ __launch_bounds__(1024) void k_rank_sort_tile(unsigned long long* __restrict__ keys, size_t size_first, size_t size_last) {
+    __shared__ unsigned long long t[kRankTile];
+    const int tid = threadIdx.x;
+    const size_t base = (size_t)blockIdx.x * kRankTile;
+    for (int p = tid; p < kRankTile; p += 1024) t[p] = keys[base + p];
+    __syncthreads();
+    for (size_t size = size_first; size <= size_last; size <<= 1) {
+        for (unsigned stride = (unsigned)(size < (size_t)kRankTile ? size : (size_t)kRankTile) >> 1; stride > 0; stride >>= 1) {
+            for (unsigned p = tid; p < kRankTile / 2; p += 1024) {
+                const unsigned lo = p & (stride - 1), a = ((p - lo) << 1) | lo, b = a | stride;
+                const bool up = ((base + a) & size) == 0;
+                const unsigned long long x = t[a], y = t[b];
+                if ((x > y) == up) { t[a] = y; t[b] = x; }
+            }
+            __syncthreads();
+        }
+    }
+    for (int p = tid; p < kRankTile; p += 1024) keys[base + p] = t[p];
+}
+
+// one compare-exchange pass of stage `size` at `stride` >= kRankTile over slots / 2 pairs
+__global__ __launch_bounds__(256) void k_rank_sort_step(unsigned long long* __restrict__ keys, size_t size, size_t stride) {
+    const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t lo = p & (stride - 1), a = ((p - lo) << 1) | lo, b = a | stride;
+    const bool up = (a & size) == 0;
+    const unsigned long long x = keys[a], y = keys[b];
+    if ((x > y) == up) { keys[a] = y; keys[b] = x; }
+}
+
+// first position in keys[0..mh) whose key is not below `key`
+__device__ __forceinline__ size_t rank_lower_bound(const unsigned long long* __restrict__ keys, size_t lo, size_t hi, unsigned long long key) {
+    while (lo < hi) {
+        const size_t mid = lo + ((hi - lo) >> 1);
+        if (keys[mid] < key) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// M holds the matrix on entry and the ranks on exit: the thread of (i, j), i < j, is the only reader of (i, j) and the only writer of
+// (i, j) and (j, i); pairs inside the band |i-j| < range get 0 as in the host's rank matrix
+__global__ __launch_bounds__(256) void k_rank_assign(double* __restrict__ M, int n, int range, const unsigned long long* __restrict__ keys, size_t mh) {
+    const int i = blockIdx.x;
+    for (int j = i + threadIdx.x; j < n; j += 256) {
+        double r = 0.0;
+        if (j - i >= range) {
+            const unsigned long long key = rank_key(M[(size_t)i * n + j]);
+            const size_t k = rank_lower_bound(keys, 0, mh, key);
+            const size_t e = key == ~0ull ? mh : rank_lower_bound(keys, k, mh, key + 1);     // one past the group
+            r = ((double)k + (double)(e - 1)) + 1.5;
+        }
+        M[(size_t)i * n + j] = r;
+        M[(size_t)j * n + i] = r;
+    }
+}
+
+// out[i] = sum over j, |i-j| >= range, of (rank(i, j) - ma)^2, summed in a fixed order
+__global__ __launch_bounds__(256) void k_rank_saa(const double* __restrict__ M, int n, int range, double ma, double* __restrict__ out) {
+    __shared__ double red[256];
+    const int i = blockIdx.x, tid = threadIdx.x;
+    double s = 0;
+    for (int j = tid; j < n; j += 256) {
+        const int sep = i > j ? i - j : j - i;
+        if (sep < range) continue;
+        const double d = M[(size_t)i * n + j] - ma;
+        s += d * d;
+    }
+    red[tid] = s;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (tid < w) red[tid] += red[tid + w];
+        __syncthreads();
+    }
+    if (tid == 0) out[i] = red[0];
+}
+
+hipError_t launch_if_rank_keys(const double* M, int n, int range, unsigned long long* keys, size_t mh, size_t slots, int* asym, hipStream_t s) {
+    hipError_t e = hipMemsetAsync(asym, 0, sizeof(int), s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_rank_keys, dim3(n), dim3(256), 0, s, M, n, range, keys, mh, slots, asym);
+    return hipGetLastError();
+}
+
+hipError_t launch_if_rank_sort(double* M, int n, int range, unsigned long long* keys, size_t mh, size_t slots, double ma, double* saa_rows,
+                               hipStream_t s) {
+    const unsigned tiles = (unsigned)(slots / kRankTile), step_blocks = (unsigned)(slots / 2 / 256);
+    hipLaunchKernelGGL(k_rank_sort_tile, dim3(tiles), dim3(1024), 0, s, keys, (size_t)2, (size_t)kRankTile);
+    for (size_t size = 2 * (size_t)kRankTile; size <= slots; size <<= 1) {
+        for (size_t stride = size >> 1; stride >= (size_t)kRankTile; stride >>= 1)
+            hipLaunchKernelGGL(k_rank_sort_step, dim3(step_blocks), dim3(256), 0, s, keys, size, stride);
+        hipLaunchKernelGGL(k_rank_sort_tile, dim3(tiles), dim3(1024), 0, s, keys, size, size);
+    }
+    hipLaunchKernelGGL(k_rank_assign, dim3(n), dim3(256), 0, s, M, n, range, keys, mh);
+    hipLaunchKernelGGL(k_rank_saa, dim3(n), dim3(256), 0, s, M, n, range, ma, saa_rows);
     return hipGetLastError();
 }
 

@@ -189,6 +189,7 @@ int main(int argc, char** argv) {
             if (c3d_score_replicas(ctx, IF, 3, nullptr, nullptr, rho.data()) == C3D_OK)      // on the device, from the resident coordinates (K6)
                 for (int r = 0; r < models; ++r)
                     printf("  model %2u  E_noe %14.2f  Spearman(IF,d) %.4f\n", first_rep + r + 1, en[3 * r], rho[r]);
+            else fprintf(stderr, "c3d_solve: models not scored: %s\n", c3d_last_error());
         }
     }
     if (!quiet)

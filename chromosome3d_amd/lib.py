@@ -72,6 +72,7 @@ SIGNATURES = {
     "c3d_step_kernel_name": (C.c_char_p, [_vp]),
     "c3d_debug_tear16": (_i, [_vp, _i, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
     "c3d_dg_smoothed_bounds": (_i, [_vp, _fp, _fp]),
+    "c3d_debug_if_ranks": (_i, [_vp, _dp, _i, _dp, _dp, C.POINTER(C.c_size_t)]),
     "c3d_eval": (_i, [_vp, _f, _f, _f, _fp, _dp]),
     "c3d_get_energies": (_i, [_vp, _dp]),
     "c3d_score_replicas": (_i, [_vp, _dp, _i, _i32p, _dp, _dp]),

@@ -51,7 +51,9 @@ class Solver:
     resident per context (2.1 GB at 16384) and K1 takes 21 n^2 bytes more while it runs.  precision 64 keeps its 2560-bead limit.
     embed() takes up to 4549 beads by default; set_option("embed_max_beads", n) raises that up to 16384 (the eigen stage then runs tiled
     over the device; 8 n^2 bytes for the bounds + 4 n^2 per replica of a batch while it runs).  embed_form 1 / embed_batch k are test
-    knobs (same bits); stat("embed_form") / stat("embed_batches") say what the last embed() ran."""
+    knobs (same bits); stat("embed_form") / stat("embed_batches") say what the last embed() ran.
+    score() beyond 5120 beads ranks the IF matrix on the device: 8 n^2 bytes for the matrix and ranks plus 8 bytes per sort slot
+    (3 GiB at 16384) in the context's scoring scratch."""
 
     def __init__(self, device=0):
         self._L = _l.load()
@@ -118,6 +120,16 @@ class Solver:
         L = np.empty((self.n, self.n), dtype=np.float32)
         _l.check(self._L.c3d_dg_smoothed_bounds(self._h, _l.fptr(U), _l.fptr(L)))
         return U, L
+
+    def debug_if_ranks(self, IF, rng=3):
+        """(rank matrix n x n fp64, saa, m): the IF side of the Spearman coefficient as the device computes it for score()
+        (c3d_debug_if_ranks; symmetric matrices only)."""
+        IFc = np.ascontiguousarray(IF, dtype=np.float64)
+        assert IFc.shape == (self.n, self.n)
+        rank = np.empty((self.n, self.n), dtype=np.float64)
+        saa, m = C.c_double(), C.c_size_t()
+        _l.check(self._L.c3d_debug_if_ranks(self._h, _l.dptr(IFc), rng, _l.dptr(rank), C.byref(saa), C.byref(m)))
+        return rank, saa.value, m.value
 
     def set_coords(self, xyz):
         xyz = _l.as_f32(xyz)
@@ -187,7 +199,10 @@ class Solver:
         return e
 
     def score(self, IF=None, rng=3):
-        """K6 on the device: (satisfied[M], sum_dev[M], spearman[M] or None) at the current coordinates."""
+        """K6 on the device: (satisfied[M], sum_dev[M], spearman[M] or None) at the current coordinates.  Models of any extent up to
+        50 000 A (stat "score_wide_runs" counts the calls that needed more than the fixed 262 A histogram).  The IF ranks come from the
+        host up to 5120 beads and from the device beyond, for symmetric matrices; set_option("device_ranks", 1 / -1) makes it the device
+        at every size / never (stat "device_rank_runs")."""
         sat = np.empty(self.nrep, dtype=np.int32)
         dev = np.empty(self.nrep, dtype=np.float64)
         rho = np.empty(self.nrep, dtype=np.float64) if IF is not None else None

@@ -195,6 +195,12 @@ int c3d_set_schedule(c3d_ctx* ctx, const c3d_stage* stages, int n_stages, const 
  *                   c3d_score_replicas takes it when its IF argument holds the same numbers, else computes it as before.  Up to 2048 beads
  *                   only (the worker keeps 16 bytes per pair until the context goes: 67 MB there).  Same result either way
  *                   (measurement knob; stat "rank_prefetch_hits")
+ *   device_ranks    0 (default) / 1 / -1 (other values: C3D_ERR_INVALID): who ranks the IF matrix for c3d_score_replicas.  0: the device
+ *                   when n > 5120 (C3D_MAX_BEADS_DEFAULT), the matrix is symmetric over the ranked pairs and no prefetched result
+ *                   covers it, the host otherwise — every n <= 5120 is ranked exactly as before.  1: the device whenever the matrix is
+ *                   symmetric (a prefetched result is ignored and not counted).  -1: the host always.  An asymmetric matrix is ranked
+ *                   on the host whatever this says.  The device's ranks are the host's bit for bit (half-integers below 2^29); the
+ *                   Spearman coefficient differs by the summation order only.  Memory: see c3d_score_replicas (stat "device_rank_runs")
  *   final_minimiser 1 (default) / 0: what a stage of kind 5 (the default schedule's final stage) runs — two-point step sizes handing over to
  *                   FIRE after final_minimiser_steps, or FIRE throughout as in rounds 1-4.  Stages of kind 2 are FIRE whatever this says
  *   final_minimiser_steps   1000 (default): two-point steps of a kind-5 stage, L-BFGS steps of a kind-8 stage, before FIRE takes it over (>= 2)
@@ -215,6 +221,8 @@ int c3d_set_option(c3d_ctx* ctx, const char* key, double value);
 #define C3D_EMBED_MAX_BEADS_DEFAULT 4549
 #define C3D_EMBED_MAX_BEADS_LIMIT 16384
 #define C3D_EMBED_SCRATCH_BYTES (4ull << 30)
+/* the two distance histograms of a replica batch stay within this when c3d_score_replicas re-runs a call whose models are wider than 262 A */
+#define C3D_SCORE_SCRATCH_BYTES (1ull << 30)
 
 /* Process-wide switches, to be set before the first c3d_create (no environment variable is read by the library):
  *   preload         which code objects c3d_create loads before it returns (the library never leaves a load to the runtime's first-launch
@@ -271,7 +279,9 @@ int c3d_last_timing(const c3d_ctx* ctx, double* ms_total, long* steps, long* lau
  * "rms_force" (largest RMS force component over the replicas at the last minimiser step: the quantity c3d_run holds
  * against gtol, the stand-in for L-BFGS's convergence test of chromosome3D.pl:1800-1803), "lbfgs_steps" (L-BFGS steps run, kind 8),
  * "lbfgs_resets" (memory drops of the last kind-8 stage since its first step, summed over the replicas: read from the device),
- * "embed_form" (the eigen stage the last c3d_embed_replicas ran: 0 k_dg_eig, 1 tiled), "embed_batches" (replica batches of that call). */
+ * "embed_form" (the eigen stage the last c3d_embed_replicas ran: 0 k_dg_eig, 1 tiled), "embed_batches" (replica batches of that call),
+ * "device_rank_runs" (calls of c3d_score_replicas that ranked the IF matrix on the device), "score_wide_runs" (calls of it that were
+ * re-run with a histogram sized to the models). */
 int c3d_get_stat(const c3d_ctx* ctx, const char* key, double* value);
 /* Test hook, no reference counterpart: the multi-step kernel's hand-off trusts a 16-byte unit once its tag word matches — i.e. that a
  * 16-byte aligned store is never observed half-written by a 16-byte load on gfx950.  This runs that exact store / load pair (one producer
@@ -283,6 +293,11 @@ int c3d_debug_tear16(c3d_ctx* ctx, int iterations, unsigned long long* unit_read
  * paths on U, the inverse triangle inequality on L, L <= U.  The same kernels and arguments as the embedding; no bead limit of its own.
  * Needs the targets (c3d_set_if_matrix / c3d_set_restraints), not the replicas. */
 int c3d_dg_smoothed_bounds(c3d_ctx* ctx, float* U, float* L);
+/* Test hook of c3d_score_replicas: the IF side of the Spearman coefficient as the DEVICE computes it, whatever the option device_ranks
+ * says.  rank (n*n, row-major) = the average rank of IF(i,j) among the ordered pairs |i-j| >= range, 0 inside that band; *m = the number of
+ * ordered pairs; *saa = sum (rank - (m+1)/2)^2 over them.  IF is n*n with the n of c3d_set_if_matrix / c3d_set_restraints and symmetric over
+ * the ranked pairs (C3D_ERR_INVALID otherwise: c3d_score_replicas ranks such a matrix on the host). */
+int c3d_debug_if_ranks(c3d_ctx* ctx, const double* IF, int range, double* rank, double* saa, size_t* m);
 /* Name of the kernel the last op of the last range of c3d_run / c3d_run_steps ran on, as a profiler prints it (thread-local string): the
  * choice that op's launch was made from, also when the range was replayed from a captured graph.  After an L-BFGS step the force pass,
  * k_lbfgs_eval<...>; "" before the first range. */
@@ -297,7 +312,17 @@ int c3d_get_energies(c3d_ctx* ctx, double* e);
 /* K6 on the device, for every replica at its current coordinates: the restraint-satisfaction count and
  * the sum of deviations of chromosome3D.pl:447-485 / :581-600 (relax 0.5 A, threshold 0.2 A) and, if IF
  * (the n*n matrix given to c3d_set_if_matrix) and rho are non-NULL, Spearman(IF, d) over |i-j| >= range
- * as spearman_IF_pdb.pl:42-70 defines it.  Any output pointer may be NULL. */
+ * as spearman_IF_pdb.pl:42-70 defines it.  Any output pointer may be NULL.
+ * Extent: distances are counted in a histogram of 0.001 A bins, 2^18 of them (262.144 A) in the first place; a call in which any pair of
+ * any replica is further apart is scored again with a histogram sized to the bounding box of the widest replica, replicas in batches
+ * whose two histograms fit C3D_SCORE_SCRATCH_BYTES (one replica at least; allocated for the call) — the same numbers for a replica
+ * either way.  Beyond 50 000 A, the limit of c3d_spearman_if_dist_batch, C3D_ERR_INVALID: at once when the bounding box is wider than
+ * that, else after the pass that finds such a pair (up to 400 MB of histograms per replica).
+ * IF ranks: from the helper thread of c3d_set_if_matrix (up to 2048 beads), else computed by the call — on the host up to 5120 beads and
+ * for asymmetric matrices, on the device beyond (option device_ranks): the matrix is uploaded into the context's scoring scratch, the keys
+ * of its upper triangle are sorted there and every pair looks its rank up; nothing is cached between calls.  That scratch, kept until
+ * the context goes, holds 8 n^2 bytes (matrix, then ranks) at every size, and with device ranks 8 bytes per sort slot — the ranked pairs
+ * i < j, (n-range)(n-range+1)/2, rounded up to a power of two and to 4096 at least: 2 GiB + 1 GiB at 16384 beads, where the host path needs about 10 GB of host memory instead. */
 int c3d_score_replicas(c3d_ctx* ctx, const double* IF, int range, int32_t* satisfied, double* sum_dev, double* rho);
 /* rank[k] = replica index with the k-th lowest int(E_noe) (chromosome3D.pl:796-802,822-828);
  * ties broken by replica id. */
