@@ -215,6 +215,7 @@ struct c3d_ctx {
     long rank_prefetch_hits = 0;
     int device_ranks = 0;                  // option device_ranks: who ranks the IF matrix for c3d_score_replicas (c3d.h)
     long device_rank_runs = 0, score_wide_runs = 0;   // stats: calls that ranked on the device / that took the sized-histogram re-run
+    long compare_runs = 0;                 // stat: completed calls of c3d_compare_replicas
     long k1_recomputed = 0, k1_patched = 0;   // K1: near-tie elements redone on the host in the reference's order / changed by it
     long graph_captures = 0, graph_launches = 0, step_launches = 0, resident_launches = 0, cluster_launches = 0;
     bool has_two_point = false;            // the program holds two-point minimiser steps (run_ops splits ranges at their borders)
@@ -1835,6 +1836,7 @@ extern "C" int c3d_get_stat(const c3d_ctx* c, const char* key, double* value) {
     else if (!strcmp(key, "rank_prefetch_hits")) *value = (double)c->rank_prefetch_hits;
     else if (!strcmp(key, "device_rank_runs")) *value = (double)c->device_rank_runs;
     else if (!strcmp(key, "score_wide_runs")) *value = (double)c->score_wide_runs;
+    else if (!strcmp(key, "compare_runs")) *value = (double)c->compare_runs;
     else if (!strcmp(key, "cluster_xcd_count")) *value = (double)c->xcd_count;
     else if (!strcmp(key, "cluster_xcd_base")) *value = (double)c->xcd_base;
     else if (!strcmp(key, "cluster_ok")) *value = c->cl_ok ? 1.0 : 0.0;
@@ -2107,6 +2109,106 @@ extern "C" int c3d_score_replicas(c3d_ctx* c, const double* IF, int range, int32
         if (sum_dev) sum_dev[r] = dev;
         if (rho) rho[r] = sab / sqrt(saa * sbb);
     }
+    return C3D_OK;
+}
+
+// c3d_compare_replicas' scratch (byte offsets into one allocation of the call): the models' fp64 coordinates, k + e of every pair and model,
+// the sort keys of one model, the row sums of the distances, their totals, the table pass's per-chunk sums and the two tables
+struct CompareScratch {
+    size_t xyz = 0, ke = 0, keys = 0, rowsum = 0, sums = 0, partial = 0, table = 0, total = 0;
+};
+static CompareScratch compare_layout(int n, int K, size_t m, size_t slots) {
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t nb = (size_t)(K + c3d::kCmpModels - 1) / c3d::kCmpModels;
+    CompareScratch L;
+    L.ke = up(sizeof(double) * 3 * (size_t)n * K);
+    L.keys = L.ke + up(sizeof(unsigned) * m * K);
+    L.rowsum = L.keys + up(sizeof(unsigned long long) * slots);
+    L.sums = L.rowsum + up(sizeof(double) * (size_t)n * K);
+    L.partial = L.sums + up(sizeof(double) * (size_t)K);
+    L.table = L.partial + up(sizeof(double) * 512 * nb * nb * (size_t)c3d::compare_table_chunks(m, K));
+    L.total = L.table + up(sizeof(double) * 2 * (size_t)K * K);
+    return L;
+}
+// the call's scratch: freed when `tmp` goes, whatever the exit path
+static int compare_alloc(DevTmp<char>& tmp, size_t bytes, const char* who) {
+    const hipError_t e = hipMalloc(reinterpret_cast<void**>(&tmp.p), bytes);
+    if (e == hipSuccess) return C3D_OK;
+    tmp.p = nullptr;
+    (void)hipGetLastError();
+    char msg[160];
+    snprintf(msg, sizeof msg, "%s: no device memory for %zu bytes of scratch (%s)", who, bytes, hipGetErrorString(e));
+    return fail(e == hipErrorOutOfMemory ? C3D_ERR_NOMEM : C3D_ERR_HIP, msg);
+}
+
+// The replicas (and n_extra models given by the caller) against one another: c3d_model_similarity for every ordered pair, on the device
+// (c3d_score.hip k_cmp_*).  Reads X[parity] only.
+extern "C" int c3d_compare_replicas(c3d_ctx* c, const double* extra_xyz, int n_extra, double* spearman, double* rmsd) {
+    if (!c) return fail(C3D_ERR_INVALID, "c3d_compare_replicas: null context");
+    if (!c->have_replicas) return fail(C3D_ERR_INVALID, "c3d_compare_replicas: call c3d_init_replicas first");
+    if (c->n < 3) return fail(C3D_ERR_INVALID, "c3d_compare_replicas: models of fewer than 3 beads have no distances to rank");
+    if (n_extra < 0 || (n_extra > 0 && !extra_xyz)) return fail(C3D_ERR_INVALID, "c3d_compare_replicas: n_extra < 0, or extra models without coordinates");
+    if ((long)c->nrep + n_extra > C3D_COMPARE_MAX_MODELS) return fail(C3D_ERR_INVALID, "c3d_compare_replicas: more than C3D_COMPARE_MAX_MODELS models");
+    if (!spearman && !rmsd) return fail(C3D_ERR_INVALID, "c3d_compare_replicas: both outputs are NULL");
+    const int n = c->n, nrep = c->nrep, K = nrep + n_extra;
+    if (n_extra > 0)
+        if (int rc = c3d::check_model_coords(extra_xyz, (size_t)3 * n * n_extra, "c3d_compare_replicas")) return rc;
+    C3D_ENTRY(c, unit_bit(UNIT_SCORE));
+    const size_t m = (size_t)n * (n - 1) / 2, slots = c3d::if_rank_key_slots(m);
+    const CompareScratch L = compare_layout(n, K, m, slots);
+    DevTmp<char> tmp;
+    if (int rc = compare_alloc(tmp, L.total, "c3d_compare_replicas")) return rc;
+    double* const d_xyz = reinterpret_cast<double*>(tmp.p + L.xyz);
+    unsigned* const d_ke = reinterpret_cast<unsigned*>(tmp.p + L.ke);
+    double* const d_rowsum = reinterpret_cast<double*>(tmp.p + L.rowsum);
+    double* const d_table = reinterpret_cast<double*>(tmp.p + L.table);
+    hipError_t e = c3d::launch_compare_coords(c->buf.X[c->parity], n, c->npad, nrep, d_xyz, c->stream);
+    if (e != hipSuccess) return fail(C3D_ERR_HIP, std::string("compare launch: ") + hipGetErrorString(e));
+    if (n_extra > 0)
+        HIP_TRY(hipMemcpyAsync(d_xyz + (size_t)3 * n * nrep, extra_xyz, sizeof(double) * 3 * (size_t)n * n_extra, hipMemcpyHostToDevice, c->stream));
+    for (int k = 0; k < K; ++k) {
+        e = c3d::launch_compare_ranks(d_xyz + (size_t)3 * n * k, n, reinterpret_cast<unsigned long long*>(tmp.p + L.keys), m, slots, d_ke + m * k,
+                                      d_rowsum + (size_t)n * k, c->stream);
+        if (e != hipSuccess) return fail(C3D_ERR_HIP, std::string("compare launch: ") + hipGetErrorString(e));
+    }
+    e = c3d::launch_compare_table(d_xyz, d_ke, d_rowsum, n, K, m, reinterpret_cast<double*>(tmp.p + L.sums),
+                                  reinterpret_cast<double*>(tmp.p + L.partial), d_table, c->stream);
+    if (e != hipSuccess) return fail(C3D_ERR_HIP, std::string("compare launch: ") + hipGetErrorString(e));
+    if (int rc = read_back(c, d_table, sizeof(double) * 2 * (size_t)K * K)) return rc;
+    // the centred ranks' sum of squares of a model is its own diagonal entry, summed in the order of every other entry: a model against a
+    // copy of itself gives exactly 1
+    const double* const t = static_cast<const double*>(c->h_stage);
+    for (int a = 0; a < K; ++a)
+        for (int b = 0; b < K; ++b) {
+            const size_t q = (size_t)a * K + b;
+            if (spearman) spearman[q] = t[2 * q] / sqrt(t[2 * ((size_t)a * K + a)] * t[2 * ((size_t)b * K + b)]);
+            if (rmsd) rmsd[q] = sqrt(t[2 * q + 1] / (double)m);
+        }
+    ++c->compare_runs;
+    return C3D_OK;
+}
+
+// test hook: the average ranks of one replica's distances as c3d_compare_replicas' kernels compute them
+extern "C" int c3d_debug_distance_ranks(c3d_ctx* c, int replica, double* rank) {
+    if (!c || !rank) return fail(C3D_ERR_INVALID, "c3d_debug_distance_ranks: null argument");
+    if (!c->have_replicas) return fail(C3D_ERR_INVALID, "c3d_debug_distance_ranks: call c3d_init_replicas first");
+    if (c->n < 3) return fail(C3D_ERR_INVALID, "c3d_debug_distance_ranks: models of fewer than 3 beads have no distances to rank");
+    if (replica < 0 || replica >= c->nrep) return fail(C3D_ERR_INVALID, "c3d_debug_distance_ranks: replica index out of range");
+    C3D_ENTRY(c, unit_bit(UNIT_SCORE));
+    const int n = c->n;
+    const size_t m = (size_t)n * (n - 1) / 2, slots = c3d::if_rank_key_slots(m);
+    const CompareScratch L = compare_layout(n, 1, m, slots);
+    DevTmp<char> tmp;
+    if (int rc = compare_alloc(tmp, L.total, "c3d_debug_distance_ranks")) return rc;
+    double* const d_xyz = reinterpret_cast<double*>(tmp.p + L.xyz);
+    hipError_t e = c3d::launch_compare_coords(c->buf.X[c->parity] + (size_t)replica * c->rep_floats, n, c->npad, 1, d_xyz, c->stream);
+    if (e == hipSuccess)
+        e = c3d::launch_compare_ranks(d_xyz, n, reinterpret_cast<unsigned long long*>(tmp.p + L.keys), m, slots, reinterpret_cast<unsigned*>(tmp.p + L.ke),
+                                      reinterpret_cast<double*>(tmp.p + L.rowsum), c->stream);
+    if (e != hipSuccess) return fail(C3D_ERR_HIP, std::string("compare launch: ") + hipGetErrorString(e));
+    if (int rc = read_back(c, tmp.p + L.ke, sizeof(unsigned) * m)) return rc;
+    const unsigned* const ke = static_cast<const unsigned*>(c->h_stage);
+    for (size_t q = 0; q < m; ++q) rank[q] = 0.5 * (double)ke[q] + 1.0;
     return C3D_OK;
 }
 

@@ -309,6 +309,9 @@ static int check_coords_d(const double* xyz, size_t count, const char* who) {
         if (!(std::fabs(xyz[k]) < 1e6)) return fail(C3D_ERR_INVALID, std::string(who) + ": coordinates not finite or out of range");
     return C3D_OK;
 }
+namespace c3d {
+int check_model_coords(const double* xyz, size_t count, const char* who) { return check_coords_d(xyz, count, who); }
+}
 
 extern "C" int c3d_write_pdb(const char* path, const float* xyz, int n, double e_noe, double e_bond, double e_rep,
                              const char* title) {

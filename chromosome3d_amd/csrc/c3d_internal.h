@@ -324,6 +324,26 @@ inline size_t if_rank_key_slots(size_t mh) {
 hipError_t launch_if_rank_keys(const double* M, int n, int range, unsigned long long* keys, size_t mh, size_t slots, int* asym, hipStream_t s);
 hipError_t launch_if_rank_sort(double* M, int n, int range, unsigned long long* keys, size_t mh, size_t slots, double ma, double* saa_rows,
                                hipStream_t s);
+// The models of a run against one another (c3d_compare_replicas).  A model is n x 3 doubles, xyz interleaved; m = n(n-1)/2 pairs i < j in
+// row order.  launch_compare_coords widens the replicas' floats into `nrep` such models; launch_compare_ranks does one model: keys of its
+// distances (if_rank_key_slots(m) slots), the sort, then ke[pair] = first + last sorted position of the pair's tie group (average rank =
+// ke / 2 + 1) and rowsum[i] = sum_j>i d_ij; launch_compare_table, over K models' ke (K x m) and rowsum (K x n): sums[k] = sum of model k's
+// distances, table[a][b] = { sum (ra - mean)(rb - mean), sum (sums[b] / sums[a] d_a - d_b)^2 } through `partial`, which holds
+// compare_table_chunks(m, K) x nb x nb x 512 doubles, nb = ceil(K / kCmpModels): per-chunk sums, added in chunk order.
+constexpr int kCmpModels = 16;
+inline size_t compare_chunk_pairs(size_t m, int K) {       // a multiple of the 64-pair tile; about 2048 workgroups, 64 chunks at least
+    const size_t nb = (size_t)(K + kCmpModels - 1) / kCmpModels, want = 2048 / (nb * nb) > 64 ? 2048 / (nb * nb) : 64;
+    return ((m + want - 1) / want + 63) / 64 * 64;
+}
+inline int compare_table_chunks(size_t m, int K) {
+    const size_t per = compare_chunk_pairs(m, K);
+    return (int)((m + per - 1) / per);
+}
+hipError_t launch_compare_coords(const float* xin, int n, int npad, int nrep, double* xyz, hipStream_t s);
+hipError_t launch_compare_ranks(const double* x, int n, unsigned long long* keys, size_t m, size_t slots, unsigned* ke, double* rowsum,
+                                hipStream_t s);
+hipError_t launch_compare_table(const double* xyz, const unsigned* ke, const double* rowsum, int n, int K, size_t m, double* sums,
+                                double* partial, double* table, hipStream_t s);
 
 // Target matrix entry: NOE target in Angstrom, 0 = no restraint (host c3d_set_restraints and K1).
 inline float encode_target_host(float t) { return t > 0 ? t : 0.0f; }

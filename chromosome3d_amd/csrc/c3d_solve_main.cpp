@@ -5,6 +5,7 @@
 //       front half on the GPU (K1) + <ID>.dist/.rr/contact.tbl + M models <ID>_<k>.pdb
 //   c3d_solve --tbl contact.tbl --n N --out <dir> --id ID [-m 20] ...
 //       exactly the cns_solve role: restraints in, <ID>_<k>.pdb out
+//   --similarity <path> adds the replicas' similarity table (Spearman and scaled RMSD of the pair distances, on the device)
 //
 // Success convention of the reference: <ID>_<M>.pdb exists, iam.running removed; on failure
 // iam.running is renamed iam.failed and the exit code is non-zero (:266-283).
@@ -26,6 +27,8 @@ static void usage() {
             "                 [--device <0>] [--min-steps <3000>] [--gtol <1e-2>] [--final-minimiser <1>] [--lbfgs] [--embed] [--no-graph] [--quiet]\n"
             "                 [--embed-max-beads <4549>   the largest matrix --embed takes, up to 16384 (memory: 8 n^2 bytes + 4 n^2 per replica of a batch)]\n"
             "                 [--seq <one-letter residue codes | @fasta file>   residue names of the models (default: all MET)]\n"
+            "                 [--similarity <path>   after the solve, the replicas against one another: one row `a b spearman rmsd` per ordered pair of\n"
+            "                                        replica ids (Spearman and scaled RMSD of the pair distances, computed on the device)]\n"
             "                 [--accepted   also write <ID>a_<k>.pdb beside every <ID>_<k>.pdb, as CNS does for structures it accepts]\n");
 }
 
@@ -55,7 +58,7 @@ int main(int argc, char** argv) {
     // (rc -13, "GPU coredump: execvp failed") before the runtime has said WHICH exception — round 5 lost the only evidence of one that way.
     setenv("HSA_DISABLE_COREDUMP_ON_EXCEPTION", "1", 0);          // (0: a user's own setting wins)
     const double t_start = now_s();
-    std::string if_path, tbl_path, out_dir, id, seq_arg;
+    std::string if_path, tbl_path, out_dir, id, seq_arg, similarity_path;
     double K = 11, alpha = 0.5, gtol = 1e-2;
     int final_min = 1;
     int lbfgs = 0;
@@ -89,6 +92,7 @@ int main(int argc, char** argv) {
         else if (s == "--quiet") quiet = 1;
         else if (s == "--accepted") accepted = 1;   // the deck's printaccept writes <ID>a_<k>.pdb for structures CNS accepts, beside the trial file (:1818-1828)
         else if (s == "--seq") seq_arg = next("--seq");
+        else if (s == "--similarity") similarity_path = next("--similarity");   // the ensemble table (c3d_compare_replicas)
         else if (s == "-h" || s == "--help") { usage(); return 0; }
         else { fprintf(stderr, "c3d_solve: unknown option %s\n", s.c_str()); usage(); return 2; }
     }
@@ -176,6 +180,18 @@ int main(int argc, char** argv) {
             CHECK(c3d_write_pdb((out_dir + "/" + name).c_str(), xyz.data() + (size_t)r * n * 3, n, en[3 * r], en[3 * r + 1],
                                 en[3 * r + 2], name));
         }
+    }
+    if (!similarity_path.empty()) {
+        // which replicas share a fold: c3d_model_similarity for every ordered pair, from the resident coordinates
+        std::vector<double> rho((size_t)models * models), rmsd((size_t)models * models);
+        CHECK(c3d_compare_replicas(ctx, nullptr, 0, rho.data(), rmsd.data()));
+        FILE* f = fopen(similarity_path.c_str(), "w");
+        if (!f) { fprintf(stderr, "c3d_solve: cannot write %s\n", similarity_path.c_str()); return fail_exit(out_dir); }
+        fprintf(f, "# replica_a replica_b spearman rmsd   (pair distances of a scaled onto b's; replica r is %s_<r+1>.pdb)\n", id.c_str());
+        for (int a = 0; a < models; ++a)
+            for (int b = 0; b < models; ++b)
+                if (a != b) fprintf(f, "%u %u %.5f %.5f\n", first_rep + (unsigned)a, first_rep + (unsigned)b, rho[(size_t)a * models + b], rmsd[(size_t)a * models + b]);
+        fclose(f);
     }
     double ms = 0;
     long steps = 0, launches = 0;

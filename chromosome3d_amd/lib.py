@@ -76,6 +76,8 @@ SIGNATURES = {
     "c3d_eval": (_i, [_vp, _f, _f, _f, _fp, _dp]),
     "c3d_get_energies": (_i, [_vp, _dp]),
     "c3d_score_replicas": (_i, [_vp, _dp, _i, _i32p, _dp, _dp]),
+    "c3d_compare_replicas": (_i, [_vp, _dp, _i, _dp, _dp]),
+    "c3d_debug_distance_ranks": (_i, [_vp, _i, _dp]),
     "c3d_rank": (_i, [_vp, _i32p]),
     "c3d_reduce_model": (_i, [_dp, _i, _dp]),
     "c3d_model_similarity": (_i, [_dp, _dp, _i, _dp, _dp]),

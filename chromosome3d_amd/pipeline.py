@@ -174,6 +174,12 @@ def model_similarity(xa, xb):
     return rho.value, rmsd.value
 
 
+def compare_models(solver, extra=None):
+    """model_similarity for every ordered pair of the solver's replicas (and the models of `extra`, [E, n, 3]) at once, on the device:
+    (spearman [K, K], rmsd [K, K]), entry [a][b] = model_similarity(model a, model b).  See Solver.compare."""
+    return solver.compare(extra)
+
+
 def build_models(solver, model_count=MODELCOUNT, seed=MD_SEED, first_replica=0, model=None, stages=None, fire=None,
                  gtol=1e-2, check_every=250, final_kind=5):
     """The replacement of `cns_solve < dgsa.inp` (:254-289): runs the whole annealing schedule

@@ -211,6 +211,31 @@ class Solver:
                                             _l.dptr(rho) if IF is not None else None))
         return sat, dev, rho
 
+    def compare(self, extra=None):
+        """(spearman, rmsd), K x K each: pipeline.model_similarity(model a, model b) for every ordered pair of the K = nrep + len(extra)
+        models, on the device (c3d_compare_replicas).  Models 0..nrep-1 are the replicas at their current coordinates; `extra` is a
+        stack [E, n, 3] (or one model [n, 3]) of further models, e.g. a bundled one.  rmsd[a][b] scales a onto b: not symmetric.
+        Scratch for the call: 4 bytes per pair and model plus 8 bytes per sort slot (c3d.h)."""
+        ex = None
+        if extra is not None:
+            ex = np.ascontiguousarray(extra, dtype=np.float64)
+            if ex.ndim == 2:
+                ex = ex[None]
+            assert ex.ndim == 3 and ex.shape[1:] == (self.n, 3)
+        K = self.nrep + (0 if ex is None else ex.shape[0])
+        rho = np.empty((K, K), dtype=np.float64)
+        rmsd = np.empty((K, K), dtype=np.float64)
+        _l.check(self._L.c3d_compare_replicas(self._h, _l.dptr(ex) if ex is not None else None, 0 if ex is None else ex.shape[0],
+                                              _l.dptr(rho), _l.dptr(rmsd)))
+        return rho, rmsd
+
+    def debug_distance_ranks(self, replica):
+        """The average ranks of one replica's n(n-1)/2 distances (pairs i<j in row order) as the device computes them for compare()
+        (c3d_debug_distance_ranks)."""
+        rank = np.empty(max(self.n * (self.n - 1) // 2, 1), dtype=np.float64)
+        _l.check(self._L.c3d_debug_distance_ranks(self._h, int(replica), _l.dptr(rank)))
+        return rank
+
     def rank(self):
         r = np.empty(self.nrep, dtype=np.int32)
         _l.check(self._L.c3d_rank(self._h, _l.i32ptr(r)))

@@ -281,7 +281,7 @@ int c3d_last_timing(const c3d_ctx* ctx, double* ms_total, long* steps, long* lau
  * "lbfgs_resets" (memory drops of the last kind-8 stage since its first step, summed over the replicas: read from the device),
  * "embed_form" (the eigen stage the last c3d_embed_replicas ran: 0 k_dg_eig, 1 tiled), "embed_batches" (replica batches of that call),
  * "device_rank_runs" (calls of c3d_score_replicas that ranked the IF matrix on the device), "score_wide_runs" (calls of it that were
- * re-run with a histogram sized to the models). */
+ * re-run with a histogram sized to the models), "compare_runs" (completed calls of c3d_compare_replicas). */
 int c3d_get_stat(const c3d_ctx* ctx, const char* key, double* value);
 /* Test hook, no reference counterpart: the multi-step kernel's hand-off trusts a 16-byte unit once its tag word matches — i.e. that a
  * 16-byte aligned store is never observed half-written by a 16-byte load on gfx950.  This runs that exact store / load pair (one producer
@@ -324,6 +324,25 @@ int c3d_get_energies(c3d_ctx* ctx, double* e);
  * the context goes, holds 8 n^2 bytes (matrix, then ranks) at every size, and with device ranks 8 bytes per sort slot — the ranked pairs
  * i < j, (n-range)(n-range+1)/2, rounded up to a power of two and to 4096 at least: 2 GiB + 1 GiB at 16384 beads, where the host path needs about 10 GB of host memory instead. */
 int c3d_score_replicas(c3d_ctx* ctx, const double* IF, int range, int32_t* satisfied, double* sum_dev, double* rho);
+/* The models of a run against one another, on the device: the two numbers of the reference's output_models/similarity.txt
+ * (c3d_model_similarity below) for every ordered pair of models, without reading coordinates back.
+ * K = n_replicas + n_extra models of n beads: model k < n_replicas is replica k at its current coordinates (fp32, taken as doubles
+ * unchanged); model n_replicas + e is extra_xyz + 3 n e (xyz interleaved, doubles; e.g. a bundled model).  spearman, rmsd: K x K row-major,
+ * entry [a][b] = what c3d_model_similarity(a, b, n, ...) returns — rmsd[a][b] scales a's distances by mean(d_b)/mean(d_a), so that table
+ * is not symmetric.  Either output may be NULL, not both.
+ * The distances and their tie groups are the host's bit for bit (c3d_debug_distance_ranks); the sums are added in another order, fixed:
+ * entries agree with the host to about m 2^-53 (m = n(n-1)/2), a model against a copy of itself gives exactly 1 and 0, and two calls on
+ * the same coordinates return the same bits.  A model whose distances are all equal gives NaN as the host does.  No state of the solve changes.
+ * C3D_ERR_INVALID: no replicas, n < 3, n_extra < 0, n_extra > 0 without coordinates, K > C3D_COMPARE_MAX_MODELS, both outputs NULL, extra
+ * coordinates that c3d_model_similarity refuses (not finite, |x| >= 1e6).  C3D_ERR_NOMEM: no device memory for the scratch.
+ * Scratch, allocated for the call and freed before it returns: 4 m bytes per model (the pairs' positions in the sorted order), 8 bytes per
+ * sort slot (m rounded up to a power of two, 4096 at least; reused model after model), 24 n bytes per model (fp64 coordinates), 8 n per
+ * model of row sums and at most 64 MB of per-workgroup sums: 10 GiB + 1 GiB at 16384 beads x 20 models, 8 MB + 1 MB at 455 x 20.
+ * Stat "compare_runs" counts the calls that completed. */
+#define C3D_COMPARE_MAX_MODELS 256
+int c3d_compare_replicas(c3d_ctx* ctx, const double* extra_xyz, int n_extra, double* spearman, double* rmsd);
+/* Test hook: rank (n(n-1)/2 doubles, pairs i<j in row order) = the average ranks of replica `replica`'s distances as the device computes them */
+int c3d_debug_distance_ranks(c3d_ctx* ctx, int replica, double* rank);
 /* rank[k] = replica index with the k-th lowest int(E_noe) (chromosome3D.pl:796-802,822-828);
  * ties broken by replica id. */
 int c3d_rank(c3d_ctx* ctx, int32_t* rank);

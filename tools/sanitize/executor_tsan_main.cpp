@@ -89,6 +89,8 @@ static void api_storm(int device_count) {
                 std::vector<int32_t> rank(4), sat(4);
                 ok = ok && c3d_rank(c, rank.data()) == C3D_OK;
                 ok = ok && c3d_score_replicas(c, IF.data(), 3, sat.data(), dev.data(), rho.data()) == C3D_OK;
+                std::vector<double> sim(16), rmsd(16);
+                ok = ok && c3d_compare_replicas(c, nullptr, 0, sim.data(), rmsd.data()) == C3D_OK;
                 if (what == 2) { unsigned long long a, b, d; ok = ok && c3d_debug_tear16(c, 4, &a, &b, &d) == C3D_OK; }
             }
             if (!ok) { fprintf(stderr, "api storm thread %d: %s\n", t, c3d_last_error()); ++failures; }

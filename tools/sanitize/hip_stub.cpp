@@ -9,7 +9,7 @@
 // Beyond what TSan sees by itself, the stub CHECKS the loader's contract (c3d_api.cpp "code objects"): a unit's load function and any HIP
 // call of the library must never overlap in time, whatever the thread.  Every function below counts as device work (LaunchScope) except
 // the device queries and pure look-ups — hipGetDeviceCount, hipSetDevice, hipGetDevicePropertiesR0600, hipDeviceGetAttribute,
-// hipHostGetDevicePointer, hipGetErrorString — so allocation, release, stream / event / graph creation and destruction and synchronisation
+// hipHostGetDevicePointer, hipGetErrorString, hipGetLastError — so allocation, release, stream / event / graph creation and destruction and synchronisation
 // are checked as well as launches, copies and fills; c3d_stub_violations() counts the overlaps, the harness fails on any.
 // Test infrastructure; never linked into the product.
 #include <hip/hip_runtime_api.h>
@@ -80,6 +80,7 @@ hipError_t hipGetDevicePropertiesR0600(hipDeviceProp_tR0600* p, int) {
     return hipSuccess;
 }
 hipError_t hipDeviceGetAttribute(int* v, hipDeviceAttribute_t a, int) { *v = a == hipDeviceAttributeNumberOfXccs ? 8 : 0; return hipSuccess; }
+hipError_t hipGetLastError() { return hipSuccess; }      // (c3d_compare_replicas clears the error of a refused allocation)
 const char* hipGetErrorString(hipError_t e) { return e == hipSuccess ? "no error" : "stub error"; }
 hipError_t hipMalloc(void** p, size_t n) { LaunchScope ls; *p = calloc(n ? n : 1, 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
 hipError_t hipFree(void* p) { LaunchScope ls; free(p); return hipSuccess; }
@@ -231,6 +232,15 @@ hipError_t launch_if_rank_sort(double* M, int n, int range, unsigned long long*,
         for (int j = 0; j < n; ++j)
             if ((i > j ? i - j : j - i) >= range) saa_rows[i] += (M[(size_t)i * n + j] - ma) * (M[(size_t)i * n + j] - ma);
     }
+    return hipSuccess;
+}
+// c3d_compare_replicas: nothing is ranked; the tables come out as the identity's (1 on the diagonal of the centred-rank sums, 0 elsewhere)
+hipError_t launch_compare_coords(const float*, int, int, int, double*, hipStream_t) { LaunchScope ls; return hipSuccess; }
+hipError_t launch_compare_ranks(const double*, int, unsigned long long*, size_t, size_t, unsigned*, double*, hipStream_t) { LaunchScope ls; return hipSuccess; }
+hipError_t launch_compare_table(const double*, const unsigned*, const double*, int, int K, size_t, double*, double*, double* table, hipStream_t) {
+    LaunchScope ls;
+    for (int a = 0; a < K; ++a)
+        for (int b = 0; b < K; ++b) { table[2 * ((size_t)a * K + b)] = a == b ? 1.0 : 0.0; table[2 * ((size_t)a * K + b) + 1] = 0.0; }
     return hipSuccess;
 }
 
