@@ -143,6 +143,9 @@ struct c3d_ctx {
     int embed_form = 0;                    // option "embed_form": 0 = k_dg_eig while it fits, the tiled eigen stage beyond; 1 = tiled at every n
     int embed_batch = 0;                   // option "embed_batch": 0 = replicas per batch from C3D_EMBED_SCRATCH_BYTES, else that many
     int last_embed_form = 0, last_embed_batches = 0;   // stats "embed_form", "embed_batches": what the last c3d_embed_replicas ran
+    int f64_max_beads = C3D_F64_MAX_BEADS_DEFAULT;   // option "f64_max_beads": the largest n a precision-64 context initialises (2560..16384)
+    int f64_column_chunk = 0;              // option "f64_column_chunk": 0 = by size, else k64_step_chunked's CHUNK wherever n > chunk (c3d::column_chunk64_for)
+    std::vector<int32_t> r_i, r_j, r_t10;  // c3d_set_restraints' list (0-based, i < j, one entry a pair): what a precision-64 context builds its tenths from
     int column_chunk = 0;                  // option "column_chunk": 0 = the library's choice, else the chunked form's CHUNK (c3d::column_chunk_for)
     float* d_feval = nullptr;
     size_t rep_floats = 0;           // 3*npad per replica
@@ -665,7 +668,7 @@ KernelRecord op_kernel(const c3d_ctx* c, const c3d::DevModel& m, const Op& op) {
         double mh[15];
         model_host64(c, mh);
         k.family = KernelRecord::STEP64;
-        k.f64 = c3d::form64(m.noe_pot, mh, c->stages[op.stage].w_all);
+        k.f64 = c3d::form64(m.noe_pot, mh, c->stages[op.stage].w_all, c->n, c->f64_column_chunk);
     } else if (!is_lbfgs(op.p.kind) && use_sym(c)) {      // (symmetric tiles do not apply to L-BFGS steps)
         k.family = KernelRecord::PAIRS_SYM;
         k.pot = c3d::device_pot(m.noe_pot);
@@ -686,7 +689,7 @@ int launch_op(c3d_ctx* c, const Op& op, int g, int par) {
         model_host64(c, mh);
         const double fh[7] = {c->fire.dt_start, c->fire.dt_max, c->fire.f_inc, c->fire.f_dec, c->fire.alpha_start, c->fire.f_alpha, c->fire.max_step};
         const double sh[6] = {(double)op.p.kind, st.dt, st.w_all, st.w_vdw, st.repel_s, st.t_bath};
-        hipError_t e64 = c3d::launch_step64(m, mh, sh, fh, c->fire.n_min, c->b64, par, c->gstream[g]);
+        hipError_t e64 = c3d::launch_step64(m, mh, sh, fh, c->fire.n_min, c->b64, par, c->f64_column_chunk, c->gstream[g]);
         if (e64 != hipSuccess) return fail(C3D_ERR_HIP, std::string("fp64 step launch: ") + hipGetErrorString(e64));
         return C3D_OK;
     }
@@ -1291,6 +1294,15 @@ extern "C" int c3d_set_option(c3d_ctx* c, const char* key, double value) {
         if (value != (int)value || value < C3D_EMBED_MAX_BEADS_DEFAULT || value > C3D_EMBED_MAX_BEADS_LIMIT)
             return fail(C3D_ERR_INVALID, "embed_max_beads must be an integer from 4549 to 16384");
         c->embed_max_beads = (int)value;
+    } else if (!strcmp(key, "f64_max_beads")) {    // the caller's consent to the fp64 target matrix, 8 n np bytes (c3d.h); before c3d_init_replicas
+        if (value != (int)value || value < C3D_F64_MAX_BEADS_DEFAULT || value > C3D_F64_MAX_BEADS_LIMIT)
+            return fail(C3D_ERR_INVALID, "f64_max_beads must be an integer from 2560 to 16384");
+        c->f64_max_beads = (int)value;
+    } else if (!strcmp(key, "f64_column_chunk")) { // test and measurement knob: the fp64 step kernel's column source (same bits either way)
+        if (value != (int)value || (value != 0 && !c3d::column_chunk64_valid((int)value)))
+            return fail(C3D_ERR_INVALID, "f64_column_chunk must be 0 (by size), 256, 512 or 1024");
+        c->f64_column_chunk = (int)value;
+        stale = STALE_GRAPHS;
     } else if (!strcmp(key, "embed_form")) {       // test and measurement knob: the eigen stage's form (same bits either way)
         if (value != 0 && value != 1) return fail(C3D_ERR_INVALID, "embed_form is 0 (k_dg_eig while it fits, tiled beyond) or 1 (tiled)");
         c->embed_form = (int)value;
@@ -1380,6 +1392,7 @@ extern "C" int c3d_set_if_matrix(c3d_ctx* c, const double* IF, int n, double alp
                                             npartial, ddist.p, c->buf.tgt, dflags.p, dnflag.p, c->stream);
     if (e != hipSuccess) return fail(C3D_ERR_HIP, std::string("K1 launch: ") + hipGetErrorString(e));
     c->h_dist10.resize(nn);
+    c->r_i.clear(); c->r_j.clear(); c->r_t10.clear();
     unsigned nflag = 0;
     HIP_TRY(hipMemcpyAsync(c->h_dist10.data(), ddist.p, sizeof(int32_t) * nn, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(&nflag, dnflag.p, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
@@ -1446,6 +1459,24 @@ extern "C" int c3d_set_restraints(c3d_ctx* c, int n, int R, const int32_t* ri, c
     int rc = upload_targets(c, enc);
     if (rc) return rc;
     c->h_dist10.clear();
+    // the list itself, for a precision-64 context (c3d_init_replicas): 0-based, i < j, the last entry of a pair as in `enc` above
+    {
+        std::vector<std::pair<uint64_t, int>> key;
+        key.reserve(R);
+        for (int k = 0; k < R; ++k) {
+            const int i = std::min(ri[k], rj[k]) - 1, j = std::max(ri[k], rj[k]) - 1;
+            key.emplace_back((uint64_t)i * n + j, k);
+        }
+        std::sort(key.begin(), key.end());
+        c->r_i.clear(); c->r_j.clear(); c->r_t10.clear();
+        int32_t last = 0;                           // the pair's value in `enc`: the last entry with a positive target
+        for (size_t q = 0; q < key.size(); ++q) {
+            if (rt10[key[q].second] > 0) last = rt10[key[q].second];
+            if (q + 1 < key.size() && key[q + 1].first == key[q].first) continue;
+            if (last > 0) { c->r_i.push_back((int32_t)(key[q].first / n)); c->r_j.push_back((int32_t)(key[q].first % n)); c->r_t10.push_back(last); }
+            last = 0;
+        }
+    }
     c->R = R;
     c->have_targets = true;
     build_program(c);
@@ -1466,6 +1497,17 @@ extern "C" int c3d_init_replicas(c3d_ctx* c, int nrep, uint64_t seed, uint32_t f
     if (!c->have_targets) return fail(C3D_ERR_INVALID, "c3d_init_replicas: set the IF matrix / restraints first");
     if (c->sym > 0 && c->npad > c3d::kMaxStagedCols && c->precision != 64)
         return fail(C3D_ERR_INVALID, "c3d_init_replicas: symmetric tiles stage a replica in LDS and take at most 5120 beads; set symmetric 0");
+    if (c->precision == 64) {              // on the host, before anything is allocated or launched
+        if (c->h_dist10.empty() && c->r_t10.empty())
+            return fail(C3D_ERR_INVALID, "precision 64 needs targets built from an IF matrix (integer tenths)");
+        if (c->n > c->f64_max_beads) {
+            if (c->f64_max_beads == C3D_F64_MAX_BEADS_DEFAULT)
+                return fail(C3D_ERR_INVALID, "precision 64: more than 2560 beads are accepted only after c3d_set_option(\"f64_max_beads\", n) (up to " +
+                                                 std::to_string(C3D_F64_MAX_BEADS_LIMIT) + ")");
+            return fail(C3D_ERR_INVALID, "precision 64: " + std::to_string(c->n) + " beads: more than f64_max_beads = " +
+                                             std::to_string(c->f64_max_beads) + " (the option goes up to " + std::to_string(C3D_F64_MAX_BEADS_LIMIT) + ")");
+        }
+    }
     C3D_ENTRY(c, 0u);
     if (c->have_replicas && nrep != c->nrep) free_replica_buffers(c);
     c->nrep = nrep; c->seed = seed; c->first_rep = first_replica;
@@ -1566,13 +1608,24 @@ extern "C" int c3d_init_replicas(c3d_ctx* c, int nrep, uint64_t seed, uint32_t f
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->pc = 0; c->parity = 0; c->steps_done = 0;
     if (c->precision == 64) {
-        if (c->h_dist10.empty()) return fail(C3D_ERR_INVALID, "precision 64 needs targets built from an IF matrix (integer tenths)");
-        if (n > c3d::kMaxBeads64) return fail(C3D_ERR_INVALID, "precision 64: more than 2560 beads are not supported by this build");
         const int np = c3d::cols64(n);
         const size_t n3 = (size_t)nrep * 3 * np, nP = (size_t)nrep * c->ntiles * 4;
         if (!c->b64.T) {
             HIP_TRY(hipMalloc(&c->b64.t10, sizeof(int32_t) * (size_t)n * n));
-            HIP_TRY(hipMemcpyAsync(c->b64.t10, c->h_dist10.data(), sizeof(int32_t) * (size_t)n * n, hipMemcpyHostToDevice, c->stream));
+            if (!c->h_dist10.empty())
+                HIP_TRY(hipMemcpyAsync(c->b64.t10, c->h_dist10.data(), sizeof(int32_t) * (size_t)n * n, hipMemcpyHostToDevice, c->stream));
+            else {                                  // c3d_set_restraints' list, scattered on the device (no n x n matrix on the host)
+                const size_t R = c->r_t10.size();
+                DevTmp<int32_t> dl;
+                HIP_TRY(hipMalloc(&dl.p, sizeof(int32_t) * 3 * R));
+                HIP_TRY(hipMemcpyAsync(dl.p, c->r_i.data(), sizeof(int32_t) * R, hipMemcpyHostToDevice, c->stream));
+                HIP_TRY(hipMemcpyAsync(dl.p + R, c->r_j.data(), sizeof(int32_t) * R, hipMemcpyHostToDevice, c->stream));
+                HIP_TRY(hipMemcpyAsync(dl.p + 2 * R, c->r_t10.data(), sizeof(int32_t) * R, hipMemcpyHostToDevice, c->stream));
+                HIP_TRY(hipMemsetAsync(c->b64.t10, 0, sizeof(int32_t) * (size_t)n * n, c->stream));
+                hipError_t e = c3d::launch_tenths64(n, (int)R, dl.p, dl.p + R, dl.p + 2 * R, c->b64.t10, c->stream);
+                if (e != hipSuccess) return fail(C3D_ERR_HIP, std::string("fp64 tenths: ") + hipGetErrorString(e));
+                HIP_TRY(hipStreamSynchronize(c->stream));
+            }
             HIP_TRY(hipMalloc(&c->b64.T, sizeof(double) * (size_t)n * np));
             HIP_TRY(hipMalloc(&c->b64.Vinit, sizeof(double) * n3));
             for (int k = 0; k < 2; ++k) {
@@ -1865,7 +1918,10 @@ extern "C" const char* c3d_step_kernel_name(const c3d_ctx* c) {
         case KernelRecord::CLUSTER:
             snprintf(buf, sizeof(buf), "c3d::k_cluster%s<%d, %d, %d, %d, %s>", k.tp ? "_tp" : "", k.pot, k.rpw, k.nb, k.wl, tf(k.late));
             break;
-        case KernelRecord::STEP64: snprintf(buf, sizeof(buf), "c3d::k64_step<%d, %s, %s>", k.f64.pot, tf(k.f64.gen), tf(k.f64.fold)); break;
+        case KernelRecord::STEP64:
+            if (k.f64.chunk) snprintf(buf, sizeof(buf), "c3d::k64_step_chunked<%d, %s, %s, %d>", k.f64.pot, tf(k.f64.gen), tf(k.f64.fold), k.f64.chunk);
+            else snprintf(buf, sizeof(buf), "c3d::k64_step<%d, %s, %s>", k.f64.pot, tf(k.f64.gen), tf(k.f64.fold));
+            break;
         case KernelRecord::PAIRS_SYM: snprintf(buf, sizeof(buf), "c3d::k_pairs_sym<%d, %s, false>", k.pot, tf(k.rs1)); break;
         case KernelRecord::STEP:
         case KernelRecord::LBFGS_EVAL: {      // (after an L-BFGS step: its force pass, k_lbfgs_move follows it)

@@ -219,206 +219,24 @@ __global__ __launch_bounds__(kBlock64) __attribute__((amdgpu_waves_per_eu(5))) v
                                                     const double* __restrict__ pin, const FireState64* __restrict__ sin,
                                                     double* __restrict__ xout, double* __restrict__ vout, double* __restrict__ pout,
                                                     FireState64* __restrict__ sout) {
-    extern __shared__ __attribute__((aligned(16))) double sm64[];
-    const int tile = blockIdx.x, rep = rep_base + blockIdx.y;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n = m.n, np = m.np;
-    double* xs = sm64;
-    double* ys = sm64 + np;
-    double* zs = sm64 + 2 * np;
-    double* rowq = sm64 + 3 * np;                       // [kTileRows][4]
-    const size_t roff = (size_t)rep * 3 * np;
-    // ---- stage the replica's coordinates; the previous step's sums meanwhile ----
-    for (int b = 2 * tid; b < 3 * np; b += 2 * kBlock64) *reinterpret_cast<double2*>(sm64 + b) = *reinterpret_cast<const double2*>(xin + roff + b);
-    // ---- loads whose latency would otherwise be exposed later leave now: the first targets of this wave's rows, the velocities of the two
-    //      rows it finishes ----
-    const int row0 = tile * kTileRows + wave * kRows64;
-    const int ra = min(row0, n - 1), rb = min(row0 + 1, n - 1);
-    const double* Ta = T + (size_t)ra * np + lane;
-    const double* Tb = T + (size_t)rb * np + lane;
-    double ta0 = Ta[0], ta1 = Ta[64], tb0 = Tb[0], tb1 = Tb[64];        // np >= 128: in bounds whatever n is
-    const int row = row0 + lane;
-    double v0x = 0, v0y = 0, v0z = 0;
-    if (lane < kRows64 && row < n && p.kind != 3 && p.kind != 6) {
-        const double* vsrc = p.kind == 4 ? vinit : vin;
-        const size_t ix = roff + row;
-        v0x = vsrc[ix]; v0y = vsrc[ix + np]; v0z = vsrc[ix + 2 * np];
-    }
-    // ---- the replica's scalars of this step: ONE wave forms them (the sums of 57 tiles through four butterflies, six fp64 divisions and
-    //      a square root are ~400 instruction slots — as much as two thirds of a wave's pair loop) and leaves them in LDS before the
-    //      barrier everybody waits at anyway ----
-    double* scal = rowq + 4 * kTileRows;                // [8] lam, cm0, cm1, cm2, keep, mix, dt, (unused)
-    FireState64 st;
-    st.dt = fp.dt_start; st.alpha = fp.alpha_start; st.npos = 0; st.pad = 0;
-    if (wave == 0 && (p.kind == 2 || p.kind == 5)) st = sin[rep];        // (asked for here, used after the sums have arrived)
-    if (wave == 0) {
-        const bool needs = p.kind == 0 || p.kind == 1 || p.kind == 2 || p.kind == 5;
-        double s0 = 0, s1 = 0, s2 = 0, s3 = 0;
-        if (needs) {
-            const double* pp = pin + (size_t)rep * m.ntiles * 4;
-            for (int t = lane; t < m.ntiles; t += 64) { s0 += pp[4 * t]; s1 += pp[4 * t + 1]; s2 += pp[4 * t + 2]; s3 += pp[4 * t + 3]; }
-            s0 = wave_sum64(s0); s1 = wave_sum64(s1); s2 = wave_sum64(s2); s3 = wave_sum64(s3);
-        }
-        // (reciprocals and square roots by seed + two Newton steps, the constant factors folded on the host: the correctly rounded
-        //  divisions and sqrt of the straightforward form are ~230 dependent fp64 operations — a microsecond on every workgroup's
-        //  critical path, more than the launch boundary hides; these are a rounding or two away from them)
-        double lam = 1.0, cm0 = 0, cm1 = 0, cm2 = 0, keep = 0.0, mix = 0.0;
-        if (p.kind == 0 || p.kind == 1) {
-            double tprev = m.t_fac * s0;                // mass / kAccel / (ndf kBoltz) * sum v^2
-            if (tprev < 1e-2) tprev = 1e-2;
-            const double ratio = p.t_bath * rcp64(tprev);
-            if (p.kind == 0) { double l2 = 1.0 + p.dt * m.fbeta * (ratio - 1.0); if (l2 < 0) l2 = 0; lam = sqrt64(l2); }
-            else lam = sqrt64(ratio);
-            cm0 = s1 * m.inv_n; cm1 = s2 * m.inv_n; cm2 = s3 * m.inv_n;
-        } else if (p.kind == 2 || p.kind == 3) {
-            if (s0 > 0) {                               // power of the previous evaluation positive (kind 3: sums are 0)
-                keep = 1.0 - st.alpha;
-                mix = st.alpha * sqrt64(s2 * rcp64(s1 > 1e-30 ? s1 : 1e-30));
-                if (st.npos > fp.n_min) { st.dt = st.dt * fp.f_inc < fp.dt_max ? st.dt * fp.f_inc : fp.dt_max; st.alpha *= fp.f_alpha; }
-                st.npos += 1;
-            } else {
-                st.alpha = fp.alpha_start; st.dt *= fp.f_dec; st.npos = 0;
-            }
-            if (tile == 0 && lane == 0) sout[rep] = st;
-        } else if (p.kind == 5 || p.kind == 6) {        // two-point step size, the length one evaluation late (c3o_bb_step): lam = previous length, mix = this one
-            const int k = p.kind == 6 ? 0 : st.npos;
-            const double a_prev = st.dt;
-            double a = a_prev;
-            if (k == 0) a = fp.dt_start * fp.dt_start * p.kacc;
-            else if (k >= 2) {
-                if (s0 > 0) a = (k & 1) ? s0 * rcp64(s2) : s3 * rcp64(s0);
-                else a = 2.0 * a_prev;
-                if (!(a >= 1e-7)) a = 1e-7;
-                if (a > 1e2) a = 1e2;
-            }
-            lam = a_prev; mix = a;
-            st.dt = a; st.npos = k + 1;
-            if (tile == 0 && lane == 0) sout[rep] = st;
-        }
-        if (lane == 0) { scal[0] = lam; scal[1] = cm0; scal[2] = cm1; scal[3] = cm2; scal[4] = keep; scal[5] = mix; scal[6] = st.dt; }
-    }
-    __syncthreads();
+#define C3D_F64_CHUNKED 0
+#include "c3d_f64_step_body.inc"
+#undef C3D_F64_CHUNKED
+}
 
-    // ---- pair forces of this wave's two rows ----
-    double fxa = 0, fya = 0, fza = 0, fxb = 0, fyb = 0, fzb = 0;
-    const double R2 = p.R2;
-    const double wr4 = p.wr4;
-    if (p.kind != 4) {
-        const double xa = xs[ra], ya = ys[ra], za = zs[ra], xb = xs[rb], yb = ys[rb], zb = zs[rb];
-        // (FOLD: the pair terms carry the repel weight relative to the NOE weight, the row sums get the NOE weight below)
-        const double nws4p = FOLD ? 1.0 : p.nws4, wr4p = FOLD ? p.wq : wr4;
-        // Columns: two per lane and pass (j, j + 64) over the first n & ~127 of them, the next two in flight while these two compute; then
-        // ONE column per lane if 64 or more are left, then the last n % 64 columns — both rows of the wave in one pass where they fit
-        // (lane = (row, column)).  No lane evaluates a padding column pair by pair any more (455 beads: 15 pair terms per lane, not 16);
-        // a lane without a column takes the padding bead n (1e4 A away, no target: an exact zero).
-        const int nmain = n & ~127;
-        if (nmain > 0) {
-            for (int j = lane; j < nmain; j += 128) {
-                const int jn = j + 128 < nmain ? 128 : 0;       // the last pass re-reads itself (in bounds)
-                Ta += jn; Tb += jn;
-                const double na0 = Ta[0], na1 = Ta[64], nb0 = Tb[0], nb1 = Tb[64];
-                const double x0 = xs[j], y0 = ys[j], z0 = zs[j], x1 = xs[j + 64], y1 = ys[j + 64], z1 = zs[j + 64];
-                pair64<POT, GEN, FOLD>(m, nws4p, wr4p, R2, ta0, xa, ya, za, x0, y0, z0, fxa, fya, fza);
-                pair64<POT, GEN, FOLD>(m, nws4p, wr4p, R2, tb0, xb, yb, zb, x0, y0, z0, fxb, fyb, fzb);
-                pair64<POT, GEN, FOLD>(m, nws4p, wr4p, R2, ta1, xa, ya, za, x1, y1, z1, fxa, fya, fza);
-                pair64<POT, GEN, FOLD>(m, nws4p, wr4p, R2, tb1, xb, yb, zb, x1, y1, z1, fxb, fyb, fzb);
-                ta0 = na0; ta1 = na1; tb0 = nb0; tb1 = nb1;
-            }
-        }
-        const double* Tra = T + (size_t)ra * np;
-        const double* Trb = T + (size_t)rb * np;
-        int c0 = nmain;
-        if (n - c0 >= 64) {
-            const int j = c0 + lane;
-            const double x0 = xs[j], y0 = ys[j], z0 = zs[j];
-            pair64<POT, GEN, FOLD>(m, nws4p, wr4p, R2, Tra[j], xa, ya, za, x0, y0, z0, fxa, fya, fza);
-            pair64<POT, GEN, FOLD>(m, nws4p, wr4p, R2, Trb[j], xb, yb, zb, x0, y0, z0, fxb, fyb, fzb);
-            c0 += 64;
-        }
-        const int left = n - c0;                             // 0 .. 63 columns
-        if (left > 0 && 2 * left <= 64) {
-            const bool second = lane >= left;                // lanes [0, left): row a; [left, 2 left): row b; beyond: the padding bead
-            const int c = lane - (second ? left : 0);
-            const int j = c < left ? c0 + c : n;
-            const double xr = second ? xb : xa, yr = second ? yb : ya, zr = second ? zb : za;
-            double tx = 0, ty = 0, tz = 0;
-            pair64<POT, GEN, FOLD>(m, nws4p, wr4p, R2, (second ? Trb : Tra)[j], xr, yr, zr, xs[j], ys[j], zs[j], tx, ty, tz);
-            if (second) { fxb += tx; fyb += ty; fzb += tz; } else { fxa += tx; fya += ty; fza += tz; }
-        } else if (left > 0) {
-            const int j = lane < left ? c0 + lane : n;
-            const double x0 = xs[j], y0 = ys[j], z0 = zs[j];
-            pair64<POT, GEN, FOLD>(m, nws4p, wr4p, R2, Tra[j], xa, ya, za, x0, y0, z0, fxa, fya, fza);
-            pair64<POT, GEN, FOLD>(m, nws4p, wr4p, R2, Trb[j], xb, yb, zb, x0, y0, z0, fxb, fyb, fzb);
-        }
-    }
-    double Fx = reduce_rows64(fxa, fxb, lane), Fy = reduce_rows64(fya, fyb, lane), Fz = reduce_rows64(fza, fzb, lane);
-    if constexpr (FOLD) { Fx *= p.nws4; Fy *= p.nws4; Fz *= p.nws4; }
-    // chain terms: lane 4 r + nb evaluates neighbour nb (offsets -2, -1, +1, +2) of row row0 + r; quad sum; to lane r
-    {
-        const int r = (lane >> 2) & 1, nb = lane & 3;
-        double cx = 0, cy = 0, cz = 0;
-        if (lane < 8 && p.kind != 4) chain64(m, p, wr4, R2, xs, ys, zs, row0 + r, nb < 2 ? nb - 2 : nb - 1, cx, cy, cz);
-        cx += dpp_mov64<0xB1>(cx); cy += dpp_mov64<0xB1>(cy); cz += dpp_mov64<0xB1>(cz);
-        cx += dpp_mov64<0x4E>(cx); cy += dpp_mov64<0x4E>(cy); cz += dpp_mov64<0x4E>(cz);
-        const double ox = dpp_mov64<0x12C>(cx), oy = dpp_mov64<0x12C>(cy), oz = dpp_mov64<0x12C>(cz);   // row_ror:12 = lane + 4
-        if (lane == 0) { Fx += cx; Fy += cy; Fz += cz; }
-        if (lane == 1) { Fx += ox; Fy += oy; Fz += oz; }
-    }
-    // ---- lanes 0, 1 finish one row each (the CPU restatement's update, c3o_md_step / c3o_fire_step) ----
-    const double lam = scal[0], cm0 = scal[1], cm1 = scal[2], cm2 = scal[3], keep = scal[4], mix = scal[5];
-    st.dt = scal[6];
-    double q0 = 0, q1 = 0, q2 = 0, q3 = 0;
-    if (lane < kRows64 && row < n) {
-        const size_t ix = roff + row, iy = ix + np, iz = iy + np;
-        const double x0 = xs[row], y0 = ys[row], z0 = zs[row];
-        double vx, vy, vz, xn, yn, zn;
-        if (p.kind == 4) {                              // MD begin: Maxwell velocities, no move
-            vx = v0x; vy = v0y; vz = v0z; xn = x0; yn = y0; zn = z0;
-            q0 = vx * vx + vy * vy + vz * vz; q1 = vx; q2 = vy; q3 = vz;
-        } else if (p.kind == 0 || p.kind == 1) {
-            const double acc = p.acc;
-            vx = lam * (v0x - cm0) + acc * Fx; vy = lam * (v0y - cm1) + acc * Fy; vz = lam * (v0z - cm2) + acc * Fz;
-            xn = x0 + p.dt * vx; yn = y0 + p.dt * vy; zn = z0 + p.dt * vz;
-            q0 = vx * vx + vy * vy + vz * vz; q1 = vx; q2 = vy; q3 = vz;
-        } else if (p.kind == 5 || p.kind == 6) {
-            const double ms2 = fp.max_step * fp.max_step;
-            auto clamp_scale = [&](double d2) {
-                double scl = 1.0;
-                if (d2 > ms2) { double dd, hh; sqrt_hrsqrt64(d2, dd, hh); hh = fma(fma(-dd, hh, 0.5), hh, hh); scl = fp.max_step * (hh + hh); }
-                return scl;
-            };
-            q1 = Fx * Fx + Fy * Fy + Fz * Fz;
-            if (p.kind == 5) {
-                double sx = lam * v0x, sy = lam * v0y, sz = lam * v0z;
-                const double scp = clamp_scale(sx * sx + sy * sy + sz * sz);
-                sx *= scp; sy *= scp; sz *= scp;
-                const double yx = v0x - Fx, yy = v0y - Fy, yz = v0z - Fz;
-                q0 = sx * yx + sy * yy + sz * yz; q2 = yx * yx + yy * yy + yz * yz; q3 = sx * sx + sy * sy + sz * sz;
-            }
-            const double dxs = mix * Fx, dys = mix * Fy, dzs = mix * Fz;
-            const double scl = clamp_scale(dxs * dxs + dys * dys + dzs * dzs);
-            xn = x0 + scl * dxs; yn = y0 + scl * dys; zn = z0 + scl * dzs;
-            vx = Fx; vy = Fy; vz = Fz;
-        } else {
-            q0 = v0x * Fx + v0y * Fy + v0z * Fz; q1 = Fx * Fx + Fy * Fy + Fz * Fz; q2 = v0x * v0x + v0y * v0y + v0z * v0z;
-            const double acc = st.dt * p.kacc;
-            vx = keep * v0x + mix * Fx; vy = keep * v0y + mix * Fy; vz = keep * v0z + mix * Fz;
-            vx += acc * Fx; vy += acc * Fy; vz += acc * Fz;
-            const double dxs = st.dt * vx, dys = st.dt * vy, dzs = st.dt * vz;
-            const double d2 = dxs * dxs + dys * dys + dzs * dzs;
-            double scl = 1.0;
-            if (d2 > fp.max_step * fp.max_step) { double dd, hh; sqrt_hrsqrt64(d2, dd, hh); hh = fma(fma(-dd, hh, 0.5), hh, hh); scl = fp.max_step * (hh + hh); }
-            xn = x0 + scl * dxs; yn = y0 + scl * dys; zn = z0 + scl * dzs;
-        }
-        xout[ix] = xn; xout[iy] = yn; xout[iz] = zn;
-        vout[ix] = vx; vout[iy] = vy; vout[iz] = vz;
-    }
-    if (lane < kRows64) { double* q = rowq + 4 * (wave * kRows64 + lane); q[0] = q0; q[1] = q1; q[2] = q2; q[3] = q3; }
-    __syncthreads();
-    if (tid < 4) {                                      // tile sums, fixed tree ((q0+q1)+(q2+q3))+((q4+q5)+(q6+q7))
-        const double* q = rowq + tid;
-        pout[((size_t)rep * m.ntiles + tile) * 4 + tid] = ((q[0] + q[4]) + (q[8] + q[12])) + ((q[16] + q[20]) + (q[24] + q[28]));
-    }
+// The same step with the columns staged CHUNK at a time (two LDS buffers of 3 CHUNK doubles: 24 KB at CHUNK 512, 48 KB at 1024, whatever n is) and the row
+// side read from global memory: every n up to 16384, in k64_step's bits (the same passes in the same order).
+template <int POT, bool GEN, bool FOLD, int CHUNK>
+__global__ __launch_bounds__(kBlock64) __attribute__((amdgpu_waves_per_eu(5))) void k64_step_chunked(const Model64 m, const Step64 p, const Fire64 fp, const int rep_base,
+                                                    const double* __restrict__ T, const double* __restrict__ xin,
+                                                    const double* __restrict__ vin, const double* __restrict__ vinit,
+                                                    const double* __restrict__ pin, const FireState64* __restrict__ sin,
+                                                    double* __restrict__ xout, double* __restrict__ vout, double* __restrict__ pout,
+                                                    FireState64* __restrict__ sout) {
+    static_assert(CHUNK % 128 == 0, "a pass of the two-column main loop (j, j + 64, stride 128) never straddles a chunk");
+#define C3D_F64_CHUNKED 1
+#include "c3d_f64_step_body.inc"
+#undef C3D_F64_CHUNKED
 }
 
 // T[i][j] = 0.1 * t10 where a restraint exists (|i-j| >= min_sep, t10 > 0), else 0; np columns per row
@@ -433,6 +251,17 @@ __global__ __launch_bounds__(256) void k64_targets(int n, int np, int min_sep, d
         }
         T[(size_t)i * np + j] = v;
     }
+}
+
+// t10[i][j] = t10[j][i] = the tenths of restraint k (a list with every pair once: no two threads write the same element)
+__global__ __launch_bounds__(256) void k64_tenths(int n, int R, const int32_t* __restrict__ ri, const int32_t* __restrict__ rj,
+                                                 const int32_t* __restrict__ rt10, int32_t* __restrict__ t10) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= R) return;
+    const int i = ri[k], j = rj[k];
+    if (i < 0 || j < 0 || i >= n || j >= n) return;
+    t10[(size_t)i * n + j] = rt10[k];
+    t10[(size_t)j * n + i] = rt10[k];
 }
 
 // fp32 SoA buffers [nrep][3][npad] <-> fp64 SoA state [nrep][3][np] (the solver's read-back, energies and scoring work on the fp32 copy)
@@ -459,6 +288,15 @@ __global__ __launch_bounds__(256) void k64_export(int n, int npad, int np, int n
     for (int t = threadIdx.x; t < 4 * ntiles; t += 256) Pf[(size_t)rep * ntiles * 4 + t] = (float)P[(size_t)rep * ntiles * 4 + t];
 }
 
+template <class F> static hipError_t with_chunk64(int chunk, F&& f) {      // the instantiated set (column_chunk64_valid)
+    switch (chunk) {
+        case 256: return f(int_c<256>{});
+        case 512: return f(int_c<512>{});
+        case 1024: return f(int_c<1024>{});
+        default: return hipErrorInvalidValue;
+    }
+}
+
 // ---- host side ---------------------------------------------------------------------------------------
 int cols64(int n) { return (n + kColPad64 - 1) / kColPad64 * kColPad64; }
 size_t fire_state64_bytes() { return sizeof(FireState64); }
@@ -479,7 +317,7 @@ static Model64 model64(const DevModel& d, const double* host) {
     return m;
 }
 hipError_t launch_step64(const DevModel& d, const double* model_host, const double* step_host, const double* fire_host, int fire_n_min,
-                         const Buffers64& b, int parity, hipStream_t s) {
+                         const Buffers64& b, int parity, int column_chunk, hipStream_t s) {
     const Model64 m = model64(d, model_host);
     Step64 p;   // step_host[]: kind, dt, w_all, w_vdw, repel_s, t_bath
     p.kind = (int)step_host[0]; p.dt = step_host[1]; p.w_all = step_host[2]; p.w_vdw = step_host[3]; p.repel_s = step_host[4]; p.t_bath = step_host[5];
@@ -499,15 +337,23 @@ hipError_t launch_step64(const DevModel& d, const double* model_host, const doub
     const size_t lds = sizeof(double) * ((size_t)3 * m.np + 4 * kTileRows + 8);
     FireState64* sin = reinterpret_cast<FireState64*>(b.S[parity]);
     FireState64* sout = reinterpret_cast<FireState64*>(b.S[q]);
-    const Form64 f = form64(d.noe_pot, model_host, p.w_all);
+    const Form64 f = form64(d.noe_pot, model_host, p.w_all, d.n, column_chunk);
     return with_pot(f.pot, [&](auto P) {
         return with_bool(f.gen, [&](auto G) {
             return with_bool(f.fold, [&](auto F) {
                 constexpr int POT = G && P == 4 ? 2 : P;            // (the general forms have no potential-4 kernel: form64 never asks for one)
                 constexpr bool FOLD = F && POT == 4 && !G;
-                hipLaunchKernelGGL((k64_step<POT, G, FOLD>), grid, blk, lds, s, m, p, fp, d.rep_base, b.T, b.X[parity], b.V[parity], b.Vinit, b.P[parity],
-                                   sin, b.X[q], b.V[q], b.P[q], sout);
-                return hipGetLastError();
+                if (f.chunk == 0) {
+                    hipLaunchKernelGGL((k64_step<POT, G, FOLD>), grid, blk, lds, s, m, p, fp, d.rep_base, b.T, b.X[parity], b.V[parity], b.Vinit, b.P[parity],
+                                       sin, b.X[q], b.V[q], b.P[q], sout);
+                    return hipGetLastError();
+                }
+                return with_chunk64(f.chunk, [&](auto C) {
+                    const size_t ldsc = sizeof(double) * ((size_t)6 * C + 4 * kTileRows + 8);
+                    hipLaunchKernelGGL((k64_step_chunked<POT, G, FOLD, C>), grid, blk, ldsc, s, m, p, fp, d.rep_base, b.T, b.X[parity], b.V[parity], b.Vinit,
+                                       b.P[parity], sin, b.X[q], b.V[q], b.P[q], sout);
+                    return hipGetLastError();
+                });
             });
         });
     });
@@ -516,6 +362,11 @@ hipError_t launch_targets64(const DevModel& d, const double* model_host, int min
     const Form64 f = form64(d.noe_pot, model_host, 0.0);
     const double none = (f.pot == 4 && !f.gen) ? kNoTarget64 : 0.0;        // what pair64 of the kernel that will run expects
     hipLaunchKernelGGL(k64_targets, dim3(d.n), dim3(256), 0, s, d.n, cols64(d.n), min_sep, none, t10, T);
+    return hipGetLastError();
+}
+hipError_t launch_tenths64(int n, int R, const int32_t* ri, const int32_t* rj, const int32_t* rt10, int32_t* t10, hipStream_t s) {
+    if (R <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k64_tenths, dim3((R + 255) / 256), dim3(256), 0, s, n, R, ri, rj, rt10, t10);
     return hipGetLastError();
 }
 hipError_t launch_import64(const DevModel& d, const float* Xf, const Buffers64& b, hipStream_t s) {

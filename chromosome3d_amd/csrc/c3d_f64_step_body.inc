@@ -1,0 +1,281 @@
+// c3d_f64_step_body.inc — the body of the fp64 step kernel, included by its two entry points (c3d_f64.hip):
+//   k64_step          C3D_F64_CHUNKED 0: the replica's coordinates staged whole in LDS, rows and columns read from there
+//   k64_step_chunked  C3D_F64_CHUNKED 1: columns staged CHUNK at a time in two LDS buffers, the row side (a row's own coordinates, its
+//                     chain neighbours, x0 of the update) from global memory; the copy is LDS-DMA (global_load_lds)
+// Everything else — the scalar prologue, the order of every sum, the chain butterfly, the row update, the tile sums — is one text.
+    extern __shared__ __attribute__((aligned(16))) double sm64[];
+    const int tile = blockIdx.x, rep = rep_base + blockIdx.y;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = m.n, np = m.np;
+    const size_t roff = (size_t)rep * 3 * np;
+#if !C3D_F64_CHUNKED
+    double* xs = sm64;
+    double* ys = sm64 + np;
+    double* zs = sm64 + 2 * np;
+    double* rowq = sm64 + 3 * np;                       // [kTileRows][4]
+    const double *rx = xs, *ry = ys, *rz = zs;          // the row side: a row's own coordinates, its chain neighbours
+    // ---- stage the replica's coordinates; the previous step's sums meanwhile ----
+    for (int b = 2 * tid; b < 3 * np; b += 2 * kBlock64) *reinterpret_cast<double2*>(sm64 + b) = *reinterpret_cast<const double2*>(xin + roff + b);
+#else
+    // two buffers [3][CHUNK] of columns, chunk c in buffer c & 1; the row side comes from global memory
+    double* rowq = sm64 + 6 * CHUNK;                    // [kTileRows][4]
+    const double *rx = xin + roff, *ry = rx + np, *rz = ry + np;
+    // chunk c = columns CHUNK c .. min(CHUNK (c + 1), np) - 1 (a multiple of 128: a wave's 16-byte copies are all inside or all outside)
+    auto copy = [&](int c) {
+        const int c0 = CHUNK * c, cnt = min(CHUNK, np - c0);
+        double* dst = sm64 + (c & 1) * 3 * CHUNK;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const double* s = rx + (size_t)k * np + c0;
+            double* d = dst + k * CHUNK;
+#ifndef C3D_F64_PLAIN_COPY
+            // LDS-DMA: no register round trip; LDS address = the wave's base + 16 lane (c3d_step_core.h lds_dma_copy)
+            for (int b = 2 * tid; b < cnt; b += 2 * kBlock64)
+                __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)(s + b),
+                                                 (void __attribute__((address_space(3)))*)(d + (b - 2 * lane)), 16, 0, 0);
+#else       // (measurement build: plain loads and ds_write)
+            for (int b = 2 * tid; b < cnt; b += 2 * kBlock64) *reinterpret_cast<double2*>(d + b) = *reinterpret_cast<const double2*>(s + b);
+#endif
+        }
+    };
+    // ---- start the copy of the first chunk; the previous step's sums meanwhile ----
+    copy(0);
+#endif
+    // ---- loads whose latency would otherwise be exposed later leave now: the first targets of this wave's rows, the velocities of the two
+    //      rows it finishes ----
+    const int row0 = tile * kTileRows + wave * kRows64;
+    const int ra = min(row0, n - 1), rb = min(row0 + 1, n - 1);
+    const double* Ta = T + (size_t)ra * np + lane;
+    const double* Tb = T + (size_t)rb * np + lane;
+    double ta0 = Ta[0], ta1 = Ta[64], tb0 = Tb[0], tb1 = Tb[64];        // np >= 128: in bounds whatever n is
+    const int row = row0 + lane;
+    double v0x = 0, v0y = 0, v0z = 0;
+#if !C3D_F64_CHUNKED
+    if (lane < kRows64 && row < n && p.kind != 3 && p.kind != 6) {
+        const double* vsrc = p.kind == 4 ? vinit : vin;
+        const size_t ix = roff + row;
+        v0x = vsrc[ix]; v0y = vsrc[ix + np]; v0z = vsrc[ix + 2 * np];
+    }
+#endif
+    // ---- the replica's scalars of this step: ONE wave forms them (the sums of 57 tiles through four butterflies, six fp64 divisions and
+    //      a square root are ~400 instruction slots — as much as two thirds of a wave's pair loop) and leaves them in LDS before the
+    //      barrier everybody waits at anyway ----
+    double* scal = rowq + 4 * kTileRows;                // [8] lam, cm0, cm1, cm2, keep, mix, dt, (unused)
+    FireState64 st;
+    st.dt = fp.dt_start; st.alpha = fp.alpha_start; st.npos = 0; st.pad = 0;
+    if (wave == 0 && (p.kind == 2 || p.kind == 5)) st = sin[rep];        // (asked for here, used after the sums have arrived)
+    if (wave == 0) {
+        const bool needs = p.kind == 0 || p.kind == 1 || p.kind == 2 || p.kind == 5;
+        double s0 = 0, s1 = 0, s2 = 0, s3 = 0;
+        if (needs) {
+            const double* pp = pin + (size_t)rep * m.ntiles * 4;
+            for (int t = lane; t < m.ntiles; t += 64) { s0 += pp[4 * t]; s1 += pp[4 * t + 1]; s2 += pp[4 * t + 2]; s3 += pp[4 * t + 3]; }
+            s0 = wave_sum64(s0); s1 = wave_sum64(s1); s2 = wave_sum64(s2); s3 = wave_sum64(s3);
+        }
+        // (reciprocals and square roots by seed + two Newton steps, the constant factors folded on the host: the correctly rounded
+        //  divisions and sqrt of the straightforward form are ~230 dependent fp64 operations — a microsecond on every workgroup's
+        //  critical path, more than the launch boundary hides; these are a rounding or two away from them)
+        double lam = 1.0, cm0 = 0, cm1 = 0, cm2 = 0, keep = 0.0, mix = 0.0;
+        if (p.kind == 0 || p.kind == 1) {
+            double tprev = m.t_fac * s0;                // mass / kAccel / (ndf kBoltz) * sum v^2
+            if (tprev < 1e-2) tprev = 1e-2;
+            const double ratio = p.t_bath * rcp64(tprev);
+            if (p.kind == 0) { double l2 = 1.0 + p.dt * m.fbeta * (ratio - 1.0); if (l2 < 0) l2 = 0; lam = sqrt64(l2); }
+            else lam = sqrt64(ratio);
+            cm0 = s1 * m.inv_n; cm1 = s2 * m.inv_n; cm2 = s3 * m.inv_n;
+        } else if (p.kind == 2 || p.kind == 3) {
+            if (s0 > 0) {                               // power of the previous evaluation positive (kind 3: sums are 0)
+                keep = 1.0 - st.alpha;
+                mix = st.alpha * sqrt64(s2 * rcp64(s1 > 1e-30 ? s1 : 1e-30));
+                if (st.npos > fp.n_min) { st.dt = st.dt * fp.f_inc < fp.dt_max ? st.dt * fp.f_inc : fp.dt_max; st.alpha *= fp.f_alpha; }
+                st.npos += 1;
+            } else {
+                st.alpha = fp.alpha_start; st.dt *= fp.f_dec; st.npos = 0;
+            }
+            if (tile == 0 && lane == 0) sout[rep] = st;
+        } else if (p.kind == 5 || p.kind == 6) {        // two-point step size, the length one evaluation late (c3o_bb_step): lam = previous length, mix = this one
+            const int k = p.kind == 6 ? 0 : st.npos;
+            const double a_prev = st.dt;
+            double a = a_prev;
+            if (k == 0) a = fp.dt_start * fp.dt_start * p.kacc;
+            else if (k >= 2) {
+                if (s0 > 0) a = (k & 1) ? s0 * rcp64(s2) : s3 * rcp64(s0);
+                else a = 2.0 * a_prev;
+                if (!(a >= 1e-7)) a = 1e-7;
+                if (a > 1e2) a = 1e2;
+            }
+            lam = a_prev; mix = a;
+            st.dt = a; st.npos = k + 1;
+            if (tile == 0 && lane == 0) sout[rep] = st;
+        }
+        if (lane == 0) { scal[0] = lam; scal[1] = cm0; scal[2] = cm1; scal[3] = cm2; scal[4] = keep; scal[5] = mix; scal[6] = st.dt; }
+    }
+#if C3D_F64_CHUNKED
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this wave's part of chunk 0 has landed; the barrier: everybody's
+#endif
+    __syncthreads();
+
+    // ---- pair forces of this wave's two rows ----
+    double fxa = 0, fya = 0, fza = 0, fxb = 0, fyb = 0, fzb = 0;
+    const double R2 = p.R2;
+    const double wr4 = p.wr4;
+    if (p.kind != 4) {
+        const double xa = rx[ra], ya = ry[ra], za = rz[ra], xb = rx[rb], yb = ry[rb], zb = rz[rb];
+        // (FOLD: the pair terms carry the repel weight relative to the NOE weight, the row sums get the NOE weight below)
+        const double nws4p = FOLD ? 1.0 : p.nws4, wr4p = FOLD ? p.wq : wr4;
+        // Columns: two per lane and pass (j, j + 64) over the first n & ~127 of them, the next two in flight while these two compute; then
+        // ONE column per lane if 64 or more are left, then the last n % 64 columns — both rows of the wave in one pass where they fit
+        // (lane = (row, column)).  No lane evaluates a padding column pair by pair any more (455 beads: 15 pair terms per lane, not 16);
+        // a lane without a column takes the padding bead n (1e4 A away, no target: an exact zero).
+        const int nmain = n & ~127;
+#if !C3D_F64_CHUNKED
+        const double *cxs = xs, *cys = ys, *czs = zs;       // the columns after the main loop: the staged arrays
+        constexpr int jo = 0;
+        if (nmain > 0) {
+            for (int j = lane; j < nmain; j += 128) {
+                const int jn = j + 128 < nmain ? 128 : 0;       // the last pass re-reads itself (in bounds)
+                Ta += jn; Tb += jn;
+                const double na0 = Ta[0], na1 = Ta[64], nb0 = Tb[0], nb1 = Tb[64];
+                const double x0 = xs[j], y0 = ys[j], z0 = zs[j], x1 = xs[j + 64], y1 = ys[j + 64], z1 = zs[j + 64];
+                pair64<POT, GEN, FOLD>(m, nws4p, wr4p, R2, ta0, xa, ya, za, x0, y0, z0, fxa, fya, fza);
+                pair64<POT, GEN, FOLD>(m, nws4p, wr4p, R2, tb0, xb, yb, zb, x0, y0, z0, fxb, fyb, fzb);
+                pair64<POT, GEN, FOLD>(m, nws4p, wr4p, R2, ta1, xa, ya, za, x1, y1, z1, fxa, fya, fza);
+                pair64<POT, GEN, FOLD>(m, nws4p, wr4p, R2, tb1, xb, yb, zb, x1, y1, z1, fxb, fyb, fzb);
+                ta0 = na0; ta1 = na1; tb0 = nb0; tb1 = nb1;
+            }
+        }
+#else
+        // The main loop's passes in the same ascending order, chunk by chunk (CHUNK is a multiple of 128: a pass never straddles two); the
+        // accumulators and the prefetched targets run straight across.  Before chunk c is computed the copy of chunk c + 1 starts into the
+        // other buffer, which every wave left at the barrier that ended chunk c - 1: one barrier per chunk.  cl = the chunk that holds the
+        // columns after the main loop and, where a lane is left without a column (n % 64 != 0), the padding bead n: they lie in the same
+        // 64-column block, so in the same chunk; all of them are below np.
+        const int cl = ((n & 63) ? n : n - 1) / CHUNK;
+#pragma nounroll
+        for (int c = 0;; ++c) {
+            if (c < cl) copy(c + 1);
+            const double* bx = sm64 + (c & 1) * 3 * CHUNK;
+            const int jb = CHUNK * c, jend = min(jb + CHUNK, nmain);
+#pragma nounroll
+            for (int j = jb + lane; j < jend; j += 128) {
+                const int jn = j + 128 < nmain ? 128 : 0;       // the last pass re-reads itself (in bounds)
+                Ta += jn; Tb += jn;
+                const double na0 = Ta[0], na1 = Ta[64], nb0 = Tb[0], nb1 = Tb[64];
+                const double* q = bx + (j - jb);
+                const double x0 = q[0], y0 = q[CHUNK], z0 = q[2 * CHUNK], x1 = q[64], y1 = q[CHUNK + 64], z1 = q[2 * CHUNK + 64];
+                pair64<POT, GEN, FOLD>(m, nws4p, wr4p, R2, ta0, xa, ya, za, x0, y0, z0, fxa, fya, fza);
+                pair64<POT, GEN, FOLD>(m, nws4p, wr4p, R2, tb0, xb, yb, zb, x0, y0, z0, fxb, fyb, fzb);
+                pair64<POT, GEN, FOLD>(m, nws4p, wr4p, R2, ta1, xa, ya, za, x1, y1, z1, fxa, fya, fza);
+                pair64<POT, GEN, FOLD>(m, nws4p, wr4p, R2, tb1, xb, yb, zb, x1, y1, z1, fxb, fyb, fzb);
+                ta0 = na0; ta1 = na1; tb0 = nb0; tb1 = nb1;
+            }
+            if (c == cl) break;
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+        }
+        const double *cxs = sm64 + (cl & 1) * 3 * CHUNK, *cys = cxs + CHUNK, *czs = cys + CHUNK;   // the last chunk, its first column jo
+        const int jo = CHUNK * cl;
+#endif
+        const double* Tra = T + (size_t)ra * np;
+        const double* Trb = T + (size_t)rb * np;
+        int c0 = nmain;
+        if (n - c0 >= 64) {
+            const int j = c0 + lane;
+            const double x0 = cxs[j - jo], y0 = cys[j - jo], z0 = czs[j - jo];
+            pair64<POT, GEN, FOLD>(m, nws4p, wr4p, R2, Tra[j], xa, ya, za, x0, y0, z0, fxa, fya, fza);
+            pair64<POT, GEN, FOLD>(m, nws4p, wr4p, R2, Trb[j], xb, yb, zb, x0, y0, z0, fxb, fyb, fzb);
+            c0 += 64;
+        }
+        const int left = n - c0;                             // 0 .. 63 columns
+        if (left > 0 && 2 * left <= 64) {
+            const bool second = lane >= left;                // lanes [0, left): row a; [left, 2 left): row b; beyond: the padding bead
+            const int c = lane - (second ? left : 0);
+            const int j = c < left ? c0 + c : n;
+            const double xr = second ? xb : xa, yr = second ? yb : ya, zr = second ? zb : za;
+            double tx = 0, ty = 0, tz = 0;
+            pair64<POT, GEN, FOLD>(m, nws4p, wr4p, R2, (second ? Trb : Tra)[j], xr, yr, zr, cxs[j - jo], cys[j - jo], czs[j - jo], tx, ty, tz);
+            if (second) { fxb += tx; fyb += ty; fzb += tz; } else { fxa += tx; fya += ty; fza += tz; }
+        } else if (left > 0) {
+            const int j = lane < left ? c0 + lane : n;
+            const double x0 = cxs[j - jo], y0 = cys[j - jo], z0 = czs[j - jo];
+            pair64<POT, GEN, FOLD>(m, nws4p, wr4p, R2, Tra[j], xa, ya, za, x0, y0, z0, fxa, fya, fza);
+            pair64<POT, GEN, FOLD>(m, nws4p, wr4p, R2, Trb[j], xb, yb, zb, x0, y0, z0, fxb, fyb, fzb);
+        }
+    }
+#if C3D_F64_CHUNKED
+    // (the velocities of the two rows the wave finishes are asked for here, not ahead of the pair loop: held across the chunk loop, the
+    //  six registers were one more than the kernel has at five waves a SIMD)
+    if (lane < kRows64 && row < n && p.kind != 3 && p.kind != 6) {
+        const double* vsrc = p.kind == 4 ? vinit : vin;
+        const size_t ix = roff + row;
+        v0x = vsrc[ix]; v0y = vsrc[ix + np]; v0z = vsrc[ix + 2 * np];
+    }
+#endif
+    double Fx = reduce_rows64(fxa, fxb, lane), Fy = reduce_rows64(fya, fyb, lane), Fz = reduce_rows64(fza, fzb, lane);
+    if constexpr (FOLD) { Fx *= p.nws4; Fy *= p.nws4; Fz *= p.nws4; }
+    // chain terms: lane 4 r + nb evaluates neighbour nb (offsets -2, -1, +1, +2) of row row0 + r; quad sum; to lane r
+    {
+        const int r = (lane >> 2) & 1, nb = lane & 3;
+        double cx = 0, cy = 0, cz = 0;
+        if (lane < 8 && p.kind != 4) chain64(m, p, wr4, R2, rx, ry, rz, row0 + r, nb < 2 ? nb - 2 : nb - 1, cx, cy, cz);
+        cx += dpp_mov64<0xB1>(cx); cy += dpp_mov64<0xB1>(cy); cz += dpp_mov64<0xB1>(cz);
+        cx += dpp_mov64<0x4E>(cx); cy += dpp_mov64<0x4E>(cy); cz += dpp_mov64<0x4E>(cz);
+        const double ox = dpp_mov64<0x12C>(cx), oy = dpp_mov64<0x12C>(cy), oz = dpp_mov64<0x12C>(cz);   // row_ror:12 = lane + 4
+        if (lane == 0) { Fx += cx; Fy += cy; Fz += cz; }
+        if (lane == 1) { Fx += ox; Fy += oy; Fz += oz; }
+    }
+    // ---- lanes 0, 1 finish one row each (the CPU restatement's update, c3o_md_step / c3o_fire_step) ----
+    const double lam = scal[0], cm0 = scal[1], cm1 = scal[2], cm2 = scal[3], keep = scal[4], mix = scal[5];
+    st.dt = scal[6];
+    double q0 = 0, q1 = 0, q2 = 0, q3 = 0;
+    if (lane < kRows64 && row < n) {
+        const size_t ix = roff + row, iy = ix + np, iz = iy + np;
+        const double x0 = rx[row], y0 = ry[row], z0 = rz[row];
+        double vx, vy, vz, xn, yn, zn;
+        if (p.kind == 4) {                              // MD begin: Maxwell velocities, no move
+            vx = v0x; vy = v0y; vz = v0z; xn = x0; yn = y0; zn = z0;
+            q0 = vx * vx + vy * vy + vz * vz; q1 = vx; q2 = vy; q3 = vz;
+        } else if (p.kind == 0 || p.kind == 1) {
+            const double acc = p.acc;
+            vx = lam * (v0x - cm0) + acc * Fx; vy = lam * (v0y - cm1) + acc * Fy; vz = lam * (v0z - cm2) + acc * Fz;
+            xn = x0 + p.dt * vx; yn = y0 + p.dt * vy; zn = z0 + p.dt * vz;
+            q0 = vx * vx + vy * vy + vz * vz; q1 = vx; q2 = vy; q3 = vz;
+        } else if (p.kind == 5 || p.kind == 6) {
+            const double ms2 = fp.max_step * fp.max_step;
+            auto clamp_scale = [&](double d2) {
+                double scl = 1.0;
+                if (d2 > ms2) { double dd, hh; sqrt_hrsqrt64(d2, dd, hh); hh = fma(fma(-dd, hh, 0.5), hh, hh); scl = fp.max_step * (hh + hh); }
+                return scl;
+            };
+            q1 = Fx * Fx + Fy * Fy + Fz * Fz;
+            if (p.kind == 5) {
+                double sx = lam * v0x, sy = lam * v0y, sz = lam * v0z;
+                const double scp = clamp_scale(sx * sx + sy * sy + sz * sz);
+                sx *= scp; sy *= scp; sz *= scp;
+                const double yx = v0x - Fx, yy = v0y - Fy, yz = v0z - Fz;
+                q0 = sx * yx + sy * yy + sz * yz; q2 = yx * yx + yy * yy + yz * yz; q3 = sx * sx + sy * sy + sz * sz;
+            }
+            const double dxs = mix * Fx, dys = mix * Fy, dzs = mix * Fz;
+            const double scl = clamp_scale(dxs * dxs + dys * dys + dzs * dzs);
+            xn = x0 + scl * dxs; yn = y0 + scl * dys; zn = z0 + scl * dzs;
+            vx = Fx; vy = Fy; vz = Fz;
+        } else {
+            q0 = v0x * Fx + v0y * Fy + v0z * Fz; q1 = Fx * Fx + Fy * Fy + Fz * Fz; q2 = v0x * v0x + v0y * v0y + v0z * v0z;
+            const double acc = st.dt * p.kacc;
+            vx = keep * v0x + mix * Fx; vy = keep * v0y + mix * Fy; vz = keep * v0z + mix * Fz;
+            vx += acc * Fx; vy += acc * Fy; vz += acc * Fz;
+            const double dxs = st.dt * vx, dys = st.dt * vy, dzs = st.dt * vz;
+            const double d2 = dxs * dxs + dys * dys + dzs * dzs;
+            double scl = 1.0;
+            if (d2 > fp.max_step * fp.max_step) { double dd, hh; sqrt_hrsqrt64(d2, dd, hh); hh = fma(fma(-dd, hh, 0.5), hh, hh); scl = fp.max_step * (hh + hh); }
+            xn = x0 + scl * dxs; yn = y0 + scl * dys; zn = z0 + scl * dzs;
+        }
+        xout[ix] = xn; xout[iy] = yn; xout[iz] = zn;
+        vout[ix] = vx; vout[iy] = vy; vout[iz] = vz;
+    }
+    if (lane < kRows64) { double* q = rowq + 4 * (wave * kRows64 + lane); q[0] = q0; q[1] = q1; q[2] = q2; q[3] = q3; }
+    __syncthreads();
+    if (tid < 4) {                                      // tile sums, fixed tree ((q0+q1)+(q2+q3))+((q4+q5)+(q6+q7))
+        const double* q = rowq + tid;
+        pout[((size_t)rep * m.ntiles + tile) * 4 + tid] = ((q[0] + q[4]) + (q[8] + q[12])) + ((q[16] + q[20]) + (q[24] + q[28]));
+    }

@@ -248,7 +248,7 @@ void sym_tile_list(const DevModel& m, int2* out);
 hipError_t launch_step_sym(const DevModel& m, const DevStep& p, const DevFire& fp, const DevBuffers& b, int parity, const void* tiles,
                            float* scratch, hipStream_t s);
 // fp64 step (c3d_f64.hip, option "precision" = 64): the CPU restatement's algorithm in its precision on the GPU, one launch per SA
-// step of a replica group (k64_step), double buffered by step parity like the fp32 per-step path.
+// step of a replica group (k64_step, k64_step_chunked beyond 2560 beads), double buffered by step parity like the fp32 per-step path.
 // model_host[15] = s_noe, rswitch, asym, masym, mrswitch, k_bond, b0, k_ang, a0, r0_rep, k_rep, mass, fbeta, min_sep, msoexp;
 // step_host[6] = kind, dt, w_all, w_vdw, repel_s, t_bath; fire_host[7] = dt_start, dt_max, f_inc, f_dec, alpha_start, f_alpha, max_step.
 // Layouts (np = cols64(n): n rounded up to 128): T [n][np] targets in Angstrom (0.1 * t10, 0 = none); X, V [2][nrep][3][np] SoA;
@@ -263,14 +263,25 @@ struct Buffers64 {
     void* S[2] = {nullptr, nullptr};
 };
 int cols64(int n);
-constexpr int kMaxBeads64 = 2560;     // 3 * 8 * np bytes of LDS must stay below the 64 KB a launch gets without opt-in
-// k64_step<pot, gen, fold>'s form, decided in doubles over the fp64 model (model_host, below) for the launch, the target encoding and
-// c3d_step_kernel_name alike: gen = a general tail, fold = the fast soft lower side (device potential 4) at a restraint weight w_all != 0
+// The staged kernel (k64_step) puts 3 * 8 * np bytes of coordinates in LDS: up to the 64 KB a launch gets without opt-in (n <= 2560,
+// 61 760 B with the tile's own).  Beyond that the chunked form runs (k64_step_chunked), kDefaultColumnChunk64 columns a pass; the option
+// f64_column_chunk forces a chunk wherever n is larger than it, so that both forms can run the same problem.
+constexpr int kMaxStagedBeads64 = 2560;
+constexpr int kDefaultColumnChunk64 = 512;       // the fastest CHUNK at every size measured, 2560 .. 16384 beads (profiles/r14_f64_large_maps.md)
+inline bool column_chunk64_valid(int chunk) { return chunk == 256 || chunk == 512 || chunk == 1024; }   // the instantiated set
+inline int column_chunk64_for(int n, int option) {
+    if (option > 0) return n > option ? option : 0;
+    return n <= kMaxStagedBeads64 ? 0 : kDefaultColumnChunk64;
+}
+// k64_step<pot, gen, fold>'s / k64_step_chunked<pot, gen, fold, chunk>'s form, decided in doubles over the fp64 model (model_host, below)
+// for the launch, the target encoding and c3d_step_kernel_name alike: gen = a general tail, fold = the fast soft lower side (device
+// potential 4) at a restraint weight w_all != 0, chunk = column_chunk64_for(n, the context's f64_column_chunk) (0 = staged)
 struct Form64 {
     int pot;
     bool gen, fold;
+    int chunk;
 };
-inline Form64 form64(int noe_pot, const double* model_host, double w_all) {
+inline Form64 form64(int noe_pot, const double* model_host, double w_all, int n = 0, int column_chunk = 0) {
     const double* h = model_host;
     const int mexp = (int)h[14] == 2 ? 2 : 1;
     const double rs = h[1], tail_c = h[2] * h[1], tail_b = (tail_c - 2.0 * rs) * rs * rs;
@@ -279,11 +290,14 @@ inline Form64 form64(int noe_pot, const double* model_host, double w_all) {
     f.pot = noe_pot == 4 && !(mexp == 2 && mtail_c == 0.0 && tail_b == 0.0 && tail_c == 2.0 * rs) ? 3 : device_pot(noe_pot);   // (cannot happen)
     f.gen = !(tail_b == 0.0 && tail_c == 2.0 * rs) || (f.pot == 3 && !(mtail_b == 0.0 && mtail_c == 2.0 * mrs));     // (potential 4 has a fast form of its own)
     f.fold = f.pot == 4 && !f.gen && w_all != 0.0;
+    f.chunk = column_chunk64_for(n, column_chunk);
     return f;
 }
 hipError_t launch_step64(const DevModel& d, const double* model_host, const double* step_host, const double* fire_host, int fire_n_min,
-                         const Buffers64& b, int parity, hipStream_t s);
+                         const Buffers64& b, int parity, int column_chunk, hipStream_t s);   // column_chunk: the option, 0 = by size
 hipError_t launch_targets64(const DevModel& d, const double* model_host, int min_sep, const int32_t* t10, double* T, hipStream_t s);
+// the integer tenths of a restraint list (R pairs, 0-based, every pair once) into the zeroed n x n matrix t10, both triangles
+hipError_t launch_tenths64(int n, int R, const int32_t* ri, const int32_t* rj, const int32_t* rt10, int32_t* t10, hipStream_t s);
 hipError_t launch_import64(const DevModel& d, const float* Xf, const Buffers64& b, hipStream_t s);
 hipError_t launch_export64(const DevModel& d, const Buffers64& b, int parity, float* Xf, float* Vf, float* Pf, hipStream_t s);
 size_t fire_state64_bytes();

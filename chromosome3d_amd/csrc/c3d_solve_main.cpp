@@ -25,6 +25,8 @@ static void usage() {
             "usage: c3d_solve (--if <IF matrix> | --tbl <contact.tbl> --n <beads>) --out <dir> [--id <ID>]\n"
             "                 [-k <K=11>] [-a <alpha=0.5>] [-m <models=20>] [--seed <82364>] [--first-replica <0>]\n"
             "                 [--device <0>] [--min-steps <3000>] [--gtol <1e-2>] [--final-minimiser <1>] [--lbfgs] [--embed] [--no-graph] [--quiet]\n"
+            "                 [--precision <32>   64: anneal with the fp64 step kernels (the reference's arithmetic; no --lbfgs); beyond 2560 beads the\n"
+            "                                     fp64 target matrix takes 8 n^2 bytes more]\n"
             "                 [--embed-max-beads <4549>   the largest matrix --embed takes, up to 16384 (memory: 8 n^2 bytes + 4 n^2 per replica of a batch)]\n"
             "                 [--seq <one-letter residue codes | @fasta file>   residue names of the models (default: all MET)]\n"
             "                 [--similarity <path>   after the solve, the replicas against one another: one row `a b spearman rmsd` per ordered pair of\n"
@@ -62,7 +64,7 @@ int main(int argc, char** argv) {
     double K = 11, alpha = 0.5, gtol = 1e-2;
     int final_min = 1;
     int lbfgs = 0;
-    int models = 20, device = 0, n_beads = 0, min_steps = 3000, use_graph = 1, quiet = 0, embed = 0, embed_max_beads = 0, accepted = 0;
+    int models = 20, device = 0, n_beads = 0, min_steps = 3000, use_graph = 1, quiet = 0, embed = 0, embed_max_beads = 0, accepted = 0, precision = 32;
     unsigned long long seed = 82364ULL;
     unsigned first_rep = 0;
     for (int a = 1; a < argc; ++a) {
@@ -88,6 +90,7 @@ int main(int argc, char** argv) {
         else if (s == "--lbfgs") lbfgs = 1;   // the final stage as kind 8: L-BFGS, then FIRE (opt-in; the default stays kind 5)
         else if (s == "--embed") embed = 1;   // distance-geometry start (deck :1471-1525) instead of the random coil
         else if (s == "--embed-max-beads") embed_max_beads = atoi(next("--embed-max-beads"));   // consent to the memory of an embedding beyond 4549 beads
+        else if (s == "--precision") precision = atoi(next("--precision"));   // 64: the fp64 step kernels (c3d_f64.hip)
         else if (s == "--no-graph") use_graph = 0;
         else if (s == "--quiet") quiet = 1;
         else if (s == "--accepted") accepted = 1;   // the deck's printaccept writes <ID>a_<k>.pdb for structures CNS accepts, beside the trial file (:1818-1828)
@@ -158,6 +161,11 @@ int main(int argc, char** argv) {
     CHECK(c3d_set_option(ctx, "final_minimiser", final_min));
     CHECK(c3d_set_schedule(ctx, stages.data(), (int)stages.size(), &fire, (float)gtol, 250));
     CHECK(c3d_set_option(ctx, "use_graph", use_graph));
+    if (precision != 32) {
+        CHECK(c3d_set_option(ctx, "precision", precision));
+        // as with max_beads above: the matrix that was read is the user's consent to the fp64 target matrix it needs
+        if (n > C3D_F64_MAX_BEADS_DEFAULT && n <= C3D_F64_MAX_BEADS_LIMIT) CHECK(c3d_set_option(ctx, "f64_max_beads", n));
+    }
     CHECK(c3d_init_replicas(ctx, models, seed, first_rep));
     if (embed_max_beads) CHECK(c3d_set_option(ctx, "embed_max_beads", embed_max_beads));
     if (embed) CHECK(c3d_embed_replicas(ctx, 50));

@@ -48,7 +48,8 @@ class Solver:
 
     Matrices of up to 5120 beads are accepted by default; set_option("max_beads", n) before set_if_matrix / set_restraints raises the
     limit up to 16384 (the per-step kernels then run in their chunked form).  That is consent to the memory: about 8 n npad bytes stay
-    resident per context (2.1 GB at 16384) and K1 takes 21 n^2 bytes more while it runs.  precision 64 keeps its 2560-bead limit.
+    resident per context (2.1 GB at 16384) and K1 takes 21 n^2 bytes more while it runs.  precision 64 takes 2560 beads by default;
+    set_option("f64_max_beads", n) before init_replicas raises that up to 16384 (8 n^2 bytes more for the fp64 target matrix).
     embed() takes up to 4549 beads by default; set_option("embed_max_beads", n) raises that up to 16384 (the eigen stage then runs tiled
     over the device; 8 n^2 bytes for the bounds + 4 n^2 per replica of a batch while it runs).  embed_form 1 / embed_batch k are test
     knobs (same bits); stat("embed_form") / stat("embed_batches") say what the last embed() ran.

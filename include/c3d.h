@@ -148,17 +148,29 @@ int c3d_set_schedule(c3d_ctx* ctx, const c3d_stage* stages, int n_stages, const 
  *   cluster_num_xcc, cluster_inject_incomplete, resident_inject_timeout   test hooks of the cluster kernel's safety net
  *                   (a device that does not expose 8 XCDs gets no cluster plan; a launch that ends without its completion
  *                   mark or with a time-out is re-run on the per-step path)
- *   precision       32 (default) or 64: the fp64 reference kernels (c3d_f64.hip); call before c3d_init_replicas.  The fp64 step stages a
- *                   replica's coordinates in LDS: at most 2560 beads (c3d_init_replicas returns C3D_ERR_INVALID beyond).  The fp32 path takes
- *                   up to 5120 beads by default and up to 16384 behind max_beads (below); c3d_set_if_matrix / c3d_set_restraints refuse more.
+ *   precision       32 (default) or 64: the fp64 reference kernels (c3d_f64.hip); call before c3d_init_replicas.  The fp64 step takes
+ *                   2560 beads by default and up to 16384 behind f64_max_beads (below; c3d_init_replicas returns C3D_ERR_INVALID beyond
+ *                   the limit in force).  The fp32 path takes up to 5120 beads by default and up to 16384 behind max_beads (below);
+ *                   c3d_set_if_matrix / c3d_set_restraints refuse more.  A precision-64 context takes its targets from the integer tenths
+ *                   of c3d_set_if_matrix or from c3d_set_restraints' list (pairs closer than min_sep carry no restraint, as in the matrix).
  *                   64 and a schedule with a stage of kind 8 exclude each other: whichever call comes second returns C3D_ERR_INVALID
  *   max_beads       5120 (default) .. 16384 (C3D_MAX_BEADS_DEFAULT .. C3D_MAX_BEADS_LIMIT): the largest matrix c3d_set_if_matrix and
  *                   c3d_set_restraints accept; set it before them (other values: C3D_ERR_INVALID).  Raising it is consent to the memory of a
  *                   large matrix: about 8 n npad bytes per context stay resident (targets and the pair targets; npad = n rounded up to
  *                   256): 0.55 GB at 8192 beads, 2.1 GB at 16384; c3d_set_if_matrix takes 21 n^2 bytes more while it runs (the matrix
  *                   and its powers in fp64, the integer tenths, flags: 5.6 GB at 16384) and the host keeps the n^2 integer tenths (1 GB).
- *                   Beyond 5120 beads the fp32 step kernels run in their chunked form (below).  Not beyond 5120: precision 64 (2560),
- *                   symmetric 1 (c3d_init_replicas refuses it).  c3d_embed_replicas has a limit of its own (embed_max_beads, next)
+ *                   Beyond 5120 beads the fp32 step kernels run in their chunked form (below).  Not beyond 5120: symmetric 1
+ *                   (c3d_init_replicas refuses it).  precision 64 and c3d_embed_replicas have limits of their own (f64_max_beads,
+ *                   embed_max_beads, next)
+ *   f64_max_beads   2560 (default) .. 16384 (C3D_F64_MAX_BEADS_DEFAULT .. C3D_F64_MAX_BEADS_LIMIT), an integer (other values:
+ *                   C3D_ERR_INVALID): the largest n c3d_init_replicas accepts under precision 64; set it before that call.  Up to 2560
+ *                   beads the fp64 step stages a replica's coordinates in LDS (k64_step: exactly the kernels of earlier releases); beyond,
+ *                   it streams the columns through two LDS buffers, 512 at a time (k64_step_chunked; same bits wherever both run).
+ *                   Raising it is consent to the fp64 target matrix, 8 n np bytes (np = n rounded up to 128): 2.1 GB at 16384, on top of
+ *                   the 1 GB of integer tenths on the device.  max_beads is needed as well beyond 5120.  A kind-8 stage stays refused
+ *   f64_column_chunk 0 (default): the fp64 step's column source by size — staged up to 2560 beads, the chunked form with 512 columns a
+ *                   pass beyond; 256, 512 or 1024 = the chunked form with that many columns a pass wherever n is larger than it.  Same
+ *                   bits either way (test and measurement knob; other values: C3D_ERR_INVALID)
  *   embed_max_beads 4549 (default) .. 16384 (C3D_EMBED_MAX_BEADS_DEFAULT .. C3D_EMBED_MAX_BEADS_LIMIT), an integer (other values:
  *                   C3D_ERR_INVALID): the largest n c3d_embed_replicas accepts.  Up to 4549 beads the eigen stage of a replica runs in one
  *                   workgroup (9 n + 16 floats in the 160 KiB of LDS of a CU); beyond, in a tiled form with its vectors in global memory
@@ -166,7 +178,7 @@ int c3d_set_schedule(c3d_ctx* ctx, const c3d_stage* stages, int n_stages, const 
  *                   returns: 8 n^2 bytes for the smoothed bounds U and L, and 4 n^2 bytes of trial distances per replica of a batch —
  *                   replicas are embedded in batches whose trial distances fit C3D_EMBED_SCRATCH_BYTES (4 GiB), one replica at least.
  *                   At 16384 beads: 2 GiB + 1 GiB per replica, four replicas a batch, on top of the 2.1 GB such a context holds.
- *                   (max_beads is needed as well beyond 5120; a precision-64 context embeds with the same fp32 kernels, up to its 2560)
+ *                   (max_beads is needed as well beyond 5120; a precision-64 context embeds with the same fp32 kernels, up to its f64_max_beads)
  *   embed_form      0 (default): the eigen stage of c3d_embed_replicas is k_dg_eig while n <= 4549 and the tiled form beyond; 1 = the
  *                   tiled form at every n.  Same bits either way (test and measurement knob; stat "embed_form")
  *   embed_batch     0 (default): replicas per batch of c3d_embed_replicas by the scratch budget; k > 0 = k at a time.  Trial distances
@@ -218,6 +230,8 @@ int c3d_set_option(c3d_ctx* ctx, const char* key, double value);
 #define C3D_MAX_BEADS_DEFAULT 5120
 #define C3D_MAX_BEADS_LIMIT 16384
 /* the option embed_max_beads: its default and its largest value; the trial-distance scratch a batch of c3d_embed_replicas stays within */
+#define C3D_F64_MAX_BEADS_DEFAULT 2560
+#define C3D_F64_MAX_BEADS_LIMIT 16384
 #define C3D_EMBED_MAX_BEADS_DEFAULT 4549
 #define C3D_EMBED_MAX_BEADS_LIMIT 16384
 #define C3D_EMBED_SCRATCH_BYTES (4ull << 30)

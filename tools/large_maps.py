@@ -4,7 +4,10 @@ and the chunked form up to 16384 beads.  One child process per size (a fresh con
 timing (c3d_last_timing: the event pair around c3d_run_steps), a warm-up that captures the graphs, then at least 200 timed steps.
 
     python tools/large_maps.py [--sizes 4096,5120,8192,12288,16384] [--chunks 0,256,1024,2048] [--replicas 8] [--steps 200]
-                               [--warmup 30] [--whole 8192] [--json OUT]
+                               [--warmup 30] [--whole 8192] [--json OUT] [--precision 32]
+
+--precision 64 measures the fp64 step instead (k64_step against k64_step_chunked, option f64_column_chunk: chunks 0, 256, 512, 1024;
+chunk 0 is the staged kernel up to 2560 beads and is left out beyond).
 
 Prints one line per (n, chunk, kind) and, with --whole N, the time of the library's default schedule at N x replicas.  Chunk 0 is the
 library's choice (staged up to 5120 beads, chunked beyond): at sizes beyond 5120 it is left out, its kernel is one of the others.
@@ -40,17 +43,22 @@ def synthetic(n, seed=20161015, K=11.0):
     return IF
 
 
-def child(n, chunks, nrep, steps, warmup, whole):
+def child(n, chunks, nrep, steps, warmup, whole, precision=32):
     from chromosome3d_amd import Solver, default_model, default_schedule, make_stages
     s = Solver(0)
     s.set_option("max_beads", max(n, 5120))
+    chunk_option = "column_chunk"
+    if precision == 64:
+        s.set_option("precision", 64)
+        s.set_option("f64_max_beads", max(n, 2560))
+        chunk_option = "f64_column_chunk"
     s.set_model(default_model())
     IF = synthetic(n)
     s.set_if_matrix(IF)
     del IF
     out = []
     for chunk in chunks:
-        s.set_option("column_chunk", chunk)
+        s.set_option(chunk_option, chunk)
         for label, st in (("FIRE", FIRE), ("MD", MD)):
             row = list(st)
             row[1] = warmup + steps
@@ -63,7 +71,7 @@ def child(n, chunks, nrep, steps, warmup, whole):
                             kernel=s.step_kernel_name, pair_terms_per_us=nrep * n * n / (1000.0 * ms / done)))
             print(json.dumps(out[-1]), flush=True)
     if whole:
-        s.set_option("column_chunk", 0)
+        s.set_option(chunk_option, 0)
         sched = default_schedule(3000)
         s.set_schedule(sched, None, 0.0, 250)
         s.init_replicas(nrep, 82364, 0)
@@ -83,18 +91,19 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=30)
     ap.add_argument("--whole", type=int, default=0, help="also run the default schedule at this size")
+    ap.add_argument("--precision", type=int, default=32, choices=(32, 64))
     ap.add_argument("--json")
     ap.add_argument("--child", type=int, help=argparse.SUPPRESS)
     a = ap.parse_args()
     chunks = [int(c) for c in a.chunks.split(",")]
     if a.child:
-        child(a.child, chunks, a.replicas, max(a.steps, 200), a.warmup, a.whole == a.child)
+        child(a.child, chunks, a.replicas, max(a.steps, 200), a.warmup, a.whole == a.child, a.precision)
         return 0
     rows = []
     for n in (int(v) for v in a.sizes.split(",")):
-        cs = [c for c in chunks if c != 0 or n <= 5120]
+        cs = [c for c in chunks if c != 0 or n <= (5120 if a.precision == 32 else 2560)]
         cmd = [sys.executable, os.path.abspath(__file__), "--child", str(n), "--chunks", ",".join(map(str, cs)), "--replicas",
-               str(a.replicas), "--steps", str(a.steps), "--warmup", str(a.warmup), "--whole", str(a.whole)]
+               str(a.replicas), "--steps", str(a.steps), "--warmup", str(a.warmup), "--whole", str(a.whole), "--precision", str(a.precision)]
         p = subprocess.run(cmd, capture_output=True, text=True)
         for line in p.stdout.splitlines():
             if line.startswith("{"):
