@@ -55,9 +55,9 @@ struct Op {
 
 // What the last op of the last range ran: the kernel family and its form, as chosen for the launch (c3d_step_kernel_name formats it)
 struct KernelRecord {
-    enum Family { NONE, STEP, LBFGS_EVAL, PAIRS_SYM, STEP64, CLUSTER } family = NONE;
+    enum Family { NONE, STEP, LBFGS_EVAL, PAIRS_SYM, STEP64, LBFGS_EVAL64, CLUSTER } family = NONE;
     c3d::StepForm step{};                        // STEP, LBFGS_EVAL
-    c3d::Form64 f64{};                           // STEP64
+    c3d::Form64 f64{};                           // STEP64, LBFGS_EVAL64
     int pot = 0, rpw = 0, nb = 0, wl = 0;        // PAIRS_SYM (pot), CLUSTER
     bool rs1 = false, late = false, tp = false;  // PAIRS_SYM (rs1), CLUSTER
 };
@@ -225,6 +225,8 @@ struct c3d_ctx {
     bool has_lbfgs = false;                // the program holds L-BFGS steps (kinds 8 / 9: run_ops splits ranges at their borders, per-step path only)
     int lbfgs_mem = 5;                     // option lbfgs_memory: pairs an L-BFGS stage keeps (1..8), fixed at the stage's first step
     c3d::LbfgsBuffers lb{};                // the L-BFGS history, tile sums and state (ensure_lbfgs), freed with the replica buffers
+    bool f64_lbfgs = false;                // option "f64_lbfgs": the caller's consent to kind-8 stages on a precision-64 context (k64_lbfgs_eval + k64_lbfgs_move)
+    c3d::LbfgsBuffers64 lb64{};            // their history, tile sums and state in doubles (ensure_lbfgs64), freed with the replica buffers
     long lbfgs_steps = 0;                  // L-BFGS steps run (stat "lbfgs_steps")
     int lbfgs_parity = -1;                 // parity the last L-BFGS step left its state in (stat "lbfgs_resets")
     int last_path = 0;                     // 0 per-step, 2 k_cluster, 3 fp64 reference (what the last run_ops used)
@@ -257,6 +259,7 @@ void free_replica_buffers(c3d_ctx* c) {
     dev_free(c->buf.Vinit); dev_free(c->buf.E); dev_free(c->d_feval);
     dev_free(c->d_sym_scratch); dev_free(c->d_sym_tiles);
     dev_free(c->lb.hist); dev_free(c->lb.part); dev_free(c->lb.S[0]); dev_free(c->lb.S[1]);
+    dev_free(c->lb64.hist); dev_free(c->lb64.part); dev_free(c->lb64.S[0]); dev_free(c->lb64.S[1]);
     c->lbfgs_parity = -1;
     dev_free(c->b64.T); dev_free(c->b64.t10); dev_free(c->b64.Vinit);
     for (int k = 0; k < 2; ++k) { dev_free(c->b64.X[k]); dev_free(c->b64.V[k]); dev_free(c->b64.P[k]); dev_free(c->b64.S[k]); }
@@ -652,6 +655,20 @@ int ensure_lbfgs(c3d_ctx* c) {
     return C3D_OK;
 }
 
+// The same for a precision-64 context: doubles, np columns (6.3 MB a replica at 16384 beads)
+int ensure_lbfgs64(c3d_ctx* c) {
+    if (c->lb64.hist) return C3D_OK;
+    const size_t hist = c3d::lbfgs_hist_floats(c3d::cols64(c->n)) * c->nrep, part = (size_t)c->nrep * c->ntiles * c3d::kLbfgsQ;
+    HIP_TRY(hipMalloc(&c->lb64.hist, sizeof(double) * hist));
+    HIP_TRY(hipMalloc(&c->lb64.part, sizeof(double) * part));
+    for (int k = 0; k < 2; ++k) HIP_TRY(hipMalloc(&c->lb64.S[k], sizeof(c3d::LbfgsState) * c->nrep));
+    HIP_TRY(hipMemsetAsync(c->lb64.hist, 0, sizeof(double) * hist, c->stream));
+    HIP_TRY(hipMemsetAsync(c->lb64.part, 0, sizeof(double) * part, c->stream));
+    for (int k = 0; k < 2; ++k) HIP_TRY(hipMemsetAsync(c->lb64.S[k], 0, sizeof(c3d::LbfgsState) * c->nrep, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));          // the step launches run on the group streams
+    return C3D_OK;
+}
+
 int ensure_pair_targets(c3d_ctx* c, const c3d::DevModel& m) {
     if (c->buf.tgs2 || !c->pair_targets || !c3d::pair_targets_fit(m) || c->npad <= 1024 || !c->buf.tgt) return C3D_OK;
     HIP_TRY(hipMalloc(&c->buf.tgs2, sizeof(float) * c3d::pair_targets_floats(c->n, c->npad)));
@@ -667,7 +684,7 @@ KernelRecord op_kernel(const c3d_ctx* c, const c3d::DevModel& m, const Op& op) {
     if (c->precision == 64) {              // launch_step64 makes the same choice from the same doubles
         double mh[15];
         model_host64(c, mh);
-        k.family = KernelRecord::STEP64;
+        k.family = is_lbfgs(op.p.kind) ? KernelRecord::LBFGS_EVAL64 : KernelRecord::STEP64;
         k.f64 = c3d::form64(m.noe_pot, mh, c->stages[op.stage].w_all, c->n, c->f64_column_chunk);
     } else if (!is_lbfgs(op.p.kind) && use_sym(c)) {      // (symmetric tiles do not apply to L-BFGS steps)
         k.family = KernelRecord::PAIRS_SYM;
@@ -689,6 +706,12 @@ int launch_op(c3d_ctx* c, const Op& op, int g, int par) {
         model_host64(c, mh);
         const double fh[7] = {c->fire.dt_start, c->fire.dt_max, c->fire.f_inc, c->fire.f_dec, c->fire.alpha_start, c->fire.f_alpha, c->fire.max_step};
         const double sh[6] = {(double)op.p.kind, st.dt, st.w_all, st.w_vdw, st.repel_s, st.t_bath};
+        if (is_lbfgs(op.p.kind)) {         // two launches, as in fp32: forces + tile sums, then sums + direction + move
+            hipError_t e = c3d::launch_lbfgs_eval64(m, mh, sh, c->b64, c->lb64, par, c->lbfgs_mem, c->f64_column_chunk, c->gstream[g]);
+            if (e == hipSuccess) e = c3d::launch_lbfgs_move64(m, mh, sh, fh, c->fire.n_min, c->b64, c->lb64, par, c->lbfgs_mem, c->gstream[g]);
+            if (e != hipSuccess) return fail(C3D_ERR_HIP, std::string("fp64 L-BFGS step launch: ") + hipGetErrorString(e));
+            return C3D_OK;
+        }
         hipError_t e64 = c3d::launch_step64(m, mh, sh, fh, c->fire.n_min, c->b64, par, c->f64_column_chunk, c->gstream[g]);
         if (e64 != hipSuccess) return fail(C3D_ERR_HIP, std::string("fp64 step launch: ") + hipGetErrorString(e64));
         return C3D_OK;
@@ -847,15 +870,17 @@ int run_ops_segment(c3d_ctx* c, size_t nops, bool zero_w, bool lbfgs = false);
 // also when a caller asks for the whole schedule in one c3d_run_steps.  And where L-BFGS steps (kinds 9 / 8) begin or end: they run on the
 // per-step path only (k_lbfgs_eval + k_lbfgs_move), the MD stages and the FIRE hand-over around them keep the multi-step kernel.
 int run_ops(c3d_ctx* c, size_t nops) {
-    if ((!c->zero_weight && !c->has_two_point && !c->has_lbfgs) || c->precision == 64) return run_ops_segment(c, nops, false);
+    // A precision-64 range (one kernel, k64_step, for every other kind) is split at the L-BFGS borders only.
+    const bool p64 = c->precision == 64;
+    if (p64 ? !c->has_lbfgs : (!c->zero_weight && !c->has_two_point && !c->has_lbfgs)) return run_ops_segment(c, nops, false);
     const size_t end = c->pc + nops;
     while (c->pc < end) {
         const c3d::DevStep& p0 = c->program[c->pc].p;
-        const bool z = p0.w_rs == 0.0f, tp = is_two_point(p0.kind), lb = is_lbfgs(p0.kind);
+        const bool z = !p64 && p0.w_rs == 0.0f, tp = !p64 && is_two_point(p0.kind), lb = is_lbfgs(p0.kind);
         size_t k = 1;
         while (c->pc + k < end) {
             const c3d::DevStep& p = c->program[c->pc + k].p;
-            if ((p.w_rs == 0.0f) != z || is_two_point(p.kind) != tp || is_lbfgs(p.kind) != lb) break;
+            if ((!p64 && p.w_rs == 0.0f) != z || (!p64 && is_two_point(p.kind)) != tp || is_lbfgs(p.kind) != lb) break;
             ++k;
         }
         const int rc = run_ops_segment(c, k, z, lb);
@@ -891,7 +916,7 @@ int run_ops_segment(c3d_ctx* c, size_t nops, bool zero_w, bool lbfgs) {
         if (int rc = ensure_pair_targets(c, dev_model(c))) return rc;
     }
     if (lbfgs)
-        if (int rc = ensure_lbfgs(c)) return rc;
+        if (int rc = c->precision == 64 ? ensure_lbfgs64(c) : ensure_lbfgs(c)) return rc;
     const int G = active_groups(c);
     if (int rc = ensure_group_streams(c, G)) return rc;
     // every replica group advances on its own stream (fork from / join into stream 0 around the range): while one
@@ -1204,7 +1229,7 @@ extern "C" int c3d_set_schedule(c3d_ctx* c, const c3d_stage* st, int n_stages, c
     if (!c || !st || n_stages < 1) return fail(C3D_ERR_INVALID, "c3d_set_schedule: bad arguments");
     for (int k = 0; k < n_stages; ++k) {
         if (st[k].kind < 0 || (st[k].kind > 2 && st[k].kind != 5 && st[k].kind != 8) || st[k].nsteps < 0) return fail(C3D_ERR_INVALID, "c3d_set_schedule: bad stage");
-        if (st[k].kind == 8 && c->precision == 64)
+        if (st[k].kind == 8 && c->precision == 64 && !c->f64_lbfgs)
             return fail(C3D_ERR_INVALID, "c3d_set_schedule: a stage of kind 8 (L-BFGS) has no fp64 form; set precision 32 first");
     }
     c->stages.assign(st, st + n_stages);
@@ -1231,7 +1256,7 @@ extern "C" int c3d_set_option(c3d_ctx* c, const char* key, double value) {
     else if (!strcmp(key, "resident")) { c->resident = value < 0 ? -1 : (value != 0); c->resident_skip = 0; }
     else if (!strcmp(key, "precision")) {  // 32 (the product kernels) or 64 (the fp64 reference step); call before c3d_init_replicas
         if (value != 32 && value != 64) return fail(C3D_ERR_INVALID, "precision must be 32 or 64");
-        if (value == 64)
+        if (value == 64 && !c->f64_lbfgs)
             for (const c3d_stage& st : c->stages)
                 if (st.kind == 8) return fail(C3D_ERR_INVALID, "precision 64: the schedule holds a stage of kind 8 (L-BFGS), which has no fp64 form");
         c->precision = (int)value;
@@ -1298,6 +1323,12 @@ extern "C" int c3d_set_option(c3d_ctx* c, const char* key, double value) {
         if (value != (int)value || value < C3D_F64_MAX_BEADS_DEFAULT || value > C3D_F64_MAX_BEADS_LIMIT)
             return fail(C3D_ERR_INVALID, "f64_max_beads must be an integer from 2560 to 16384");
         c->f64_max_beads = (int)value;
+    } else if (!strcmp(key, "f64_lbfgs")) {        // the caller's consent to kind-8 stages in fp64 (c3d.h); releases nothing on the device
+        if (value != 0 && value != 1) return fail(C3D_ERR_INVALID, "f64_lbfgs must be 0 or 1");
+        if (value == 0 && c->precision == 64)
+            for (const c3d_stage& st : c->stages)
+                if (st.kind == 8) return fail(C3D_ERR_INVALID, "f64_lbfgs: precision is 64 and the schedule holds a stage of kind 8 (L-BFGS); change one of them first");
+        c->f64_lbfgs = value != 0;
     } else if (!strcmp(key, "f64_column_chunk")) { // test and measurement knob: the fp64 step kernel's column source (same bits either way)
         if (value != (int)value || (value != 0 && !c3d::column_chunk64_valid((int)value)))
             return fail(C3D_ERR_INVALID, "f64_column_chunk must be 0 (by size), 256, 512 or 1024");
@@ -1874,9 +1905,10 @@ extern "C" int c3d_get_stat(const c3d_ctx* c, const char* key, double* value) {
     else if (!strcmp(key, "lbfgs_resets")) {
         // memory drops of the last L-BFGS stage, summed over the replicas (device state of the parity its last step wrote)
         *value = 0;
-        if (c->lbfgs_parity >= 0 && c->lb.S[c->lbfgs_parity]) {
+        const c3d::LbfgsState* dev = c->lbfgs_parity < 0 ? nullptr : c->precision == 64 ? c->lb64.S[c->lbfgs_parity] : c->lb.S[c->lbfgs_parity];
+        if (dev) {
             C3D_ENTRY(c, 0u);
-            if (int rc = read_back(const_cast<c3d_ctx*>(c), c->lb.S[c->lbfgs_parity], sizeof(c3d::LbfgsState) * c->nrep)) return rc;
+            if (int rc = read_back(const_cast<c3d_ctx*>(c), dev, sizeof(c3d::LbfgsState) * c->nrep)) return rc;
             const c3d::LbfgsState* h = static_cast<const c3d::LbfgsState*>(c->h_stage);
             long r = 0;
             for (int k = 0; k < c->nrep; ++k) r += h[k].resets;
@@ -1919,9 +1951,12 @@ extern "C" const char* c3d_step_kernel_name(const c3d_ctx* c) {
             snprintf(buf, sizeof(buf), "c3d::k_cluster%s<%d, %d, %d, %d, %s>", k.tp ? "_tp" : "", k.pot, k.rpw, k.nb, k.wl, tf(k.late));
             break;
         case KernelRecord::STEP64:
-            if (k.f64.chunk) snprintf(buf, sizeof(buf), "c3d::k64_step_chunked<%d, %s, %s, %d>", k.f64.pot, tf(k.f64.gen), tf(k.f64.fold), k.f64.chunk);
-            else snprintf(buf, sizeof(buf), "c3d::k64_step<%d, %s, %s>", k.f64.pot, tf(k.f64.gen), tf(k.f64.fold));
+        case KernelRecord::LBFGS_EVAL64: {    // (after an fp64 L-BFGS step: its force pass, k64_lbfgs_move follows it)
+            const char* kernel = k.family == KernelRecord::STEP64 ? "k64_step" : "k64_lbfgs_eval";
+            if (k.f64.chunk) snprintf(buf, sizeof(buf), "c3d::%s_chunked<%d, %s, %s, %d>", kernel, k.f64.pot, tf(k.f64.gen), tf(k.f64.fold), k.f64.chunk);
+            else snprintf(buf, sizeof(buf), "c3d::%s<%d, %s, %s>", kernel, k.f64.pot, tf(k.f64.gen), tf(k.f64.fold));
             break;
+        }
         case KernelRecord::PAIRS_SYM: snprintf(buf, sizeof(buf), "c3d::k_pairs_sym<%d, %s, false>", k.pot, tf(k.rs1)); break;
         case KernelRecord::STEP:
         case KernelRecord::LBFGS_EVAL: {      // (after an L-BFGS step: its force pass, k_lbfgs_move follows it)

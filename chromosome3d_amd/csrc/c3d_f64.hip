@@ -57,6 +57,7 @@ constexpr int kRows64 = 2;                       // rows per wave
 constexpr int kWaves64 = kTileRows / kRows64;    // 4 waves: one tile of 8 rows per workgroup (the fp32 step's tile)
 constexpr int kBlock64 = 64 * kWaves64;
 constexpr int kColPad64 = 128;                   // columns padded to two per lane
+constexpr int kLbfgsMoveRows64 = 256;            // rows per workgroup of k64_lbfgs_move
 constexpr double kNoTarget64 = 1.0e300;          // "no restraint" in the target matrix of the fast soft lower side (pair64)
 
 // ---- 64-bit values through the 32-bit cross-lane paths (DPP, permlane swaps): VALU only, no LDS round trip ----------
@@ -220,7 +221,9 @@ __global__ __launch_bounds__(kBlock64) __attribute__((amdgpu_waves_per_eu(5))) v
                                                     double* __restrict__ xout, double* __restrict__ vout, double* __restrict__ pout,
                                                     FireState64* __restrict__ sout) {
 #define C3D_F64_CHUNKED 0
+#define C3D_F64_LBFGS 0
 #include "c3d_f64_step_body.inc"
+#undef C3D_F64_LBFGS
 #undef C3D_F64_CHUNKED
 }
 
@@ -235,8 +238,199 @@ __global__ __launch_bounds__(kBlock64) __attribute__((amdgpu_waves_per_eu(5))) v
                                                     FireState64* __restrict__ sout) {
     static_assert(CHUNK % 128 == 0, "a pass of the two-column main loop (j, j + 64, stride 128) never straddles a chunk");
 #define C3D_F64_CHUNKED 1
+#define C3D_F64_LBFGS 0
 #include "c3d_f64_step_body.inc"
+#undef C3D_F64_LBFGS
 #undef C3D_F64_CHUNKED
+}
+
+// ---- the L-BFGS stage (kinds 9 / 8) in fp64: the twins of k_lbfgs_eval and k_lbfgs_move (c3d_lbfgs.h), two launches a step ----------
+// fixed tree over the 8 rows of a tile (row_sum8's order)
+__device__ __forceinline__ double row_sum8_64(const double* q, int stride) {
+    return ((q[0] + q[stride]) + (q[2 * stride] + q[3 * stride])) + ((q[4 * stride] + q[5 * stride]) + (q[6 * stride] + q[7 * stride]));
+}
+
+// The evaluation: k64_step's forces of a tile's rows (the same body text: staging, passes, sums and chain terms in its order, so its bits),
+// then vout = F, y = vin - F (vin = the previous evaluation's force) into ring slot nxt of hist, and the tile's kLbfgsQ sums into part.
+// hist [nrep][2: s, y][kLbfgsMaxPairs][3][np], part [nrep][ntiles][kLbfgsQ], both doubles.
+template <int POT, bool GEN, bool FOLD = false>
+__global__ __launch_bounds__(kBlock64) __attribute__((amdgpu_waves_per_eu(5))) void k64_lbfgs_eval(const Model64 m, const Step64 p, const int rep_base,
+                                                    const double* __restrict__ T, const double* __restrict__ xin,
+                                                    const double* __restrict__ vin, double* __restrict__ vout,
+                                                    double* __restrict__ hist, double* __restrict__ part,
+                                                    const LbfgsState* __restrict__ lsin, const int mem0) {
+#define C3D_F64_CHUNKED 0
+#define C3D_F64_LBFGS 1
+#include "c3d_f64_step_body.inc"
+#undef C3D_F64_LBFGS
+#undef C3D_F64_CHUNKED
+}
+template <int POT, bool GEN, bool FOLD, int CHUNK>
+__global__ __launch_bounds__(kBlock64) __attribute__((amdgpu_waves_per_eu(5))) void k64_lbfgs_eval_chunked(const Model64 m, const Step64 p, const int rep_base,
+                                                    const double* __restrict__ T, const double* __restrict__ xin,
+                                                    const double* __restrict__ vin, double* __restrict__ vout,
+                                                    double* __restrict__ hist, double* __restrict__ part,
+                                                    const LbfgsState* __restrict__ lsin, const int mem0) {
+    static_assert(CHUNK % 128 == 0, "a pass of the two-column main loop (j, j + 64, stride 128) never straddles a chunk");
+#define C3D_F64_CHUNKED 1
+#define C3D_F64_LBFGS 1
+#include "c3d_f64_step_body.inc"
+#undef C3D_F64_LBFGS
+#undef C3D_F64_CHUNKED
+}
+
+// The move: k_lbfgs_move in doubles.  Every workgroup of a replica forms the replica sums of the tile partials in one fixed order (lane l
+// takes tiles l, l + 64, ..., then the butterfly), thread 0 the compact form (pair test, gamma, the two triangular solves, the descent test
+// with memory drop); then its rows: direction, the per-bead cap at max_step, the move, s into the ring; P = (move.move, F.F, 0, 0) per tile.
+__global__ __launch_bounds__(kLbfgsMoveRows64) void k64_lbfgs_move(const Model64 m, const Step64 p, const Fire64 fp, const int rep_base,
+                                                                   const double* __restrict__ xin, double* __restrict__ xout,
+                                                                   const double* __restrict__ fcur, double* __restrict__ hist,
+                                                                   const double* __restrict__ part, double* __restrict__ pout,
+                                                                   const LbfgsState* __restrict__ sin, LbfgsState* __restrict__ sout,
+                                                                   const int mem0) {
+    constexpr int Q = kLbfgsQ, M = kLbfgsMaxPairs, ROWS = kLbfgsMoveRows64;
+    __shared__ double sums[Q];
+    __shared__ LbfgsState st;
+    __shared__ double coef[1 + 2 * M];           // gamma, then a_j (of s_j), b_j (of y_j) by slot
+    __shared__ int shi[2];                       // slot mask of the pairs in the direction, slot of the move's s
+    __shared__ double dd[ROWS];
+    const int rep = rep_base + blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const bool first = p.kind == 9;
+    // 1. replica sums of the tile partials: the same order in every workgroup, whatever the replica group
+    const double* pr = part + (size_t)rep * m.ntiles * Q;
+    for (int k = wave; k < Q; k += ROWS / 64) {
+        double a = 0.0;
+        for (int t = lane; t < m.ntiles; t += 64) a += pr[(size_t)t * Q + k];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o);
+        if (lane == 0) sums[k] = a;
+    }
+    if (!first) {
+        const double* src = reinterpret_cast<const double*>(sin + rep);
+        double* dst = reinterpret_cast<double*>(&st);
+        for (int k = tid; k < (int)(sizeof(LbfgsState) / sizeof(double)); k += ROWS) dst[k] = src[k];
+    }
+    __syncthreads();
+    // 2. the compact form, serially (k_lbfgs_move's statements)
+    if (tid == 0) {
+        if (first) {
+            st.cnt = 0; st.mem = mem0; st.head = mem0 - 1; st.resets = 0;
+            st.gamma = fp.dt_start * fp.dt_start * p.kacc;                // kind 6's first step length in k64_step
+        } else {
+            st.mem = min(max(st.mem, 1), M);
+            st.head = min(max(st.head, 0), st.mem - 1);
+            st.cnt = min(max(st.cnt, 0), st.mem);
+            const int mem = st.mem;
+            const int nx = st.head + 1 == mem ? 0 : st.head + 1;
+            const double sy = sums[4 * nx + 2], yy = sums[4 * nx + 3], ss = sums[Q - 4];
+            if (sy > 1e-12 * sqrt(ss * yy)) {
+                st.head = nx;
+                st.cnt = min(st.cnt + 1, mem);
+                for (int i = 0; i < st.cnt; ++i) {
+                    int sl = nx - i; if (sl < 0) sl += mem;
+                    st.SY[sl][nx] = sums[4 * sl + 2];
+                    st.YY[sl][nx] = sums[4 * sl + 3];
+                    st.YY[nx][sl] = sums[4 * sl + 3];
+                }
+                st.gamma = sy / yy;
+            } else {
+                st.cnt = 0;
+                st.resets += 1;
+                st.gamma *= 2.0;
+            }
+            st.gamma = fmin(fmax(st.gamma, 1e-7), 1e2);
+        }
+        const int mem = st.mem, cnt = st.cnt;
+        const double g = st.gamma, ff = sums[Q - 3];
+        int sl[M];
+        double ps[M], py[M], u[M], w[M], top[M];
+        for (int i = 0; i < cnt; ++i) {                  // age order: i = 0 the oldest pair
+            int k = st.head - (cnt - 1) + i; if (k < 0) k += mem;
+            sl[i] = k;
+            ps[i] = -sums[4 * k];                        // S'g, Y'g with g = -F
+            py[i] = -sums[4 * k + 1];
+        }
+        for (int i = cnt - 1; i >= 0; --i) {             // R u = S'g, R = upper triangle of S'Y
+            double a = ps[i];
+            for (int j = i + 1; j < cnt; ++j) a -= st.SY[sl[i]][sl[j]] * u[j];
+            u[i] = a / st.SY[sl[i]][sl[i]];
+        }
+        for (int i = 0; i < cnt; ++i) {                  // w = (D + gamma Y'Y) u - gamma Y'g
+            double a = st.SY[sl[i]][sl[i]] * u[i];
+            for (int j = 0; j < cnt; ++j) a += g * st.YY[sl[i]][sl[j]] * u[j];
+            w[i] = a - g * py[i];
+        }
+        for (int i = 0; i < cnt; ++i) {                  // R' top = w
+            double a = w[i];
+            for (int j = 0; j < i; ++j) a -= st.SY[sl[j]][sl[i]] * top[j];
+            top[i] = a / st.SY[sl[i]][sl[i]];
+        }
+        // d = -H g = gamma F - sum top_i s_i + gamma sum u_i y_i;  F.d > 0 or the memory goes
+        double fd = g * ff;
+        for (int i = 0; i < cnt; ++i) fd += top[i] * ps[i] - g * u[i] * py[i];
+        int mask = 0;
+        for (int j = 0; j < 2 * M; ++j) coef[1 + j] = 0.0;
+        if (fd > 0.0) {
+            for (int i = 0; i < cnt; ++i) { coef[1 + sl[i]] = -top[i]; coef[1 + M + sl[i]] = g * u[i]; mask |= 1 << sl[i]; }
+        } else {
+            st.cnt = 0;
+            st.resets += 1;
+        }
+        coef[0] = g;
+        shi[0] = mask;
+        shi[1] = st.head + 1 == mem ? 0 : st.head + 1;   // where this move's s goes: the slot the next evaluation completes
+    }
+    __syncthreads();
+    // 3. the rows of this workgroup
+    const int i = blockIdx.x * ROWS + tid;
+    const int np = m.np;
+    const size_t roff = (size_t)rep * 3 * np;
+    double d2 = 0.0;
+    if (i < m.n) {
+        const size_t ix = roff + i, iy = ix + np, iz = iy + np;
+        const double c = coef[0];
+        double dx = c * fcur[ix], dy = c * fcur[iy], dz = c * fcur[iz];
+        double* hs = hist + (size_t)rep * lbfgs_hist_floats(np) + i;
+        double* hy = hs + (size_t)3 * M * np;
+        const int mask = shi[0];
+#pragma unroll
+        for (int j = 0; j < M; ++j) {
+            if (!(mask & (1 << j))) continue;
+            const double a = coef[1 + j], b = coef[1 + M + j];
+            const double* s = hs + (size_t)3 * j * np;
+            const double* y = hy + (size_t)3 * j * np;
+            dx = fma(a, s[0], fma(b, y[0], dx));
+            dy = fma(a, s[np], fma(b, y[np], dy));
+            dz = fma(a, s[2 * np], fma(b, y[2 * np], dz));
+        }
+        const double l2 = fma(dx, dx, fma(dy, dy, dz * dz));
+        if (l2 > fp.max_step * fp.max_step) {            // the per-bead cap, 1 / |d| as k64_step's clamp forms it
+            double len, hh;
+            sqrt_hrsqrt64(l2, len, hh);
+            hh = fma(fma(-len, hh, 0.5), hh, hh);
+            const double scl = fp.max_step * (hh + hh);
+            dx *= scl; dy *= scl; dz *= scl;
+        }
+        xout[ix] = xin[ix] + dx; xout[iy] = xin[iy] + dy; xout[iz] = xin[iz] + dz;
+        double* sn = hs + (size_t)3 * shi[1] * np;
+        sn[0] = dx; sn[np] = dy; sn[2 * np] = dz;
+        d2 = fma(dx, dx, fma(dy, dy, dz * dz));
+    }
+    dd[tid] = d2;
+    __syncthreads();
+    // 4. P[parity^1] of this workgroup's tiles: (move.move, F.F of the evaluation, 0, 0) — where k64_export and the exit test look
+    constexpr int WT = ROWS / kTileRows;
+    const int t = blockIdx.x * WT + tid;
+    if (tid < WT && t < m.ntiles) {
+        double* po = pout + ((size_t)rep * m.ntiles + t) * 4;
+        po[0] = row_sum8_64(dd + kTileRows * tid, 1); po[1] = pr[(size_t)t * Q + Q - 3]; po[2] = 0.0; po[3] = 0.0;
+    }
+    // 5. the replica's state: one workgroup writes it
+    if (blockIdx.x == 0) {
+        const double* src = reinterpret_cast<const double*>(&st);
+        double* dst = reinterpret_cast<double*>(sout + rep);
+        for (int k = tid; k < (int)(sizeof(LbfgsState) / sizeof(double)); k += ROWS) dst[k] = src[k];
+    }
 }
 
 // T[i][j] = 0.1 * t10 where a restraint exists (|i-j| >= min_sep, t10 > 0), else 0; np columns per row
@@ -316,9 +510,7 @@ static Model64 model64(const DevModel& d, const double* host) {
     { const int ndf = 3 * d.n - 3; m.t_fac = m.mass / kAccel64 / ((ndf > 0 ? ndf : 1) * kBoltz64); m.inv_n = 1.0 / d.n; }
     return m;
 }
-hipError_t launch_step64(const DevModel& d, const double* model_host, const double* step_host, const double* fire_host, int fire_n_min,
-                         const Buffers64& b, int parity, int column_chunk, hipStream_t s) {
-    const Model64 m = model64(d, model_host);
+static Step64 step64(const Model64& m, const double* step_host) {
     Step64 p;   // step_host[]: kind, dt, w_all, w_vdw, repel_s, t_bath
     p.kind = (int)step_host[0]; p.dt = step_host[1]; p.w_all = step_host[2]; p.w_vdw = step_host[3]; p.repel_s = step_host[4]; p.t_bath = step_host[5];
     p.R2 = (p.repel_s * m.r0_rep) * (p.repel_s * m.r0_rep);
@@ -329,9 +521,19 @@ hipError_t launch_step64(const DevModel& d, const double* model_host, const doub
     p.kb4 = -p.w_all * 4.0 * m.k_bond; p.ka4 = -p.w_all * 4.0 * m.k_ang;
     p.kacc = kAccel64 / m.mass;
     p.a0sq = m.a0 * m.a0;
+    return p;
+}
+static Fire64 fire64(const double* fire_host, int fire_n_min) {
     Fire64 fp;
     fp.dt_start = fire_host[0]; fp.dt_max = fire_host[1]; fp.f_inc = fire_host[2]; fp.f_dec = fire_host[3]; fp.alpha_start = fire_host[4];
     fp.f_alpha = fire_host[5]; fp.max_step = fire_host[6]; fp.n_min = fire_n_min;
+    return fp;
+}
+hipError_t launch_step64(const DevModel& d, const double* model_host, const double* step_host, const double* fire_host, int fire_n_min,
+                         const Buffers64& b, int parity, int column_chunk, hipStream_t s) {
+    const Model64 m = model64(d, model_host);
+    const Step64 p = step64(m, step_host);
+    const Fire64 fp = fire64(fire_host, fire_n_min);
     const int q = parity ^ 1;
     const dim3 grid(d.ntiles, d.nrep_g), blk(kBlock64);
     const size_t lds = sizeof(double) * ((size_t)3 * m.np + 4 * kTileRows + 8);
@@ -357,6 +559,48 @@ hipError_t launch_step64(const DevModel& d, const double* model_host, const doub
             });
         });
     });
+}
+// launch_step64's form (form64: staged up to 2560 beads, chunked beyond or where f64_column_chunk asks), with the kernel of an L-BFGS
+// evaluation: reads X[parity] and the previous force V[parity], writes the force V[parity^1], ring slot and tile sums
+hipError_t launch_lbfgs_eval64(const DevModel& d, const double* model_host, const double* step_host, const Buffers64& b, const LbfgsBuffers64& lb,
+                               int parity, int mem, int column_chunk, hipStream_t s) {
+    if (mem < 1 || mem > kLbfgsMaxPairs) return hipErrorInvalidValue;
+    const Model64 m = model64(d, model_host);
+    const Step64 p = step64(m, step_host);
+    const int q = parity ^ 1;
+    const dim3 grid(d.ntiles, d.nrep_g), blk(kBlock64);
+    const size_t rowq = (size_t)kLbfgsQ * kTileRows;
+    const Form64 f = form64(d.noe_pot, model_host, p.w_all, d.n, column_chunk);
+    return with_pot(f.pot, [&](auto P) {
+        return with_bool(f.gen, [&](auto G) {
+            return with_bool(f.fold, [&](auto F) {
+                constexpr int POT = G && P == 4 ? 2 : P;            // (as launch_step64)
+                constexpr bool FOLD = F && POT == 4 && !G;
+                if (f.chunk == 0) {
+                    hipLaunchKernelGGL((k64_lbfgs_eval<POT, G, FOLD>), grid, blk, sizeof(double) * ((size_t)3 * m.np + rowq), s, m, p, d.rep_base, b.T,
+                                       b.X[parity], b.V[parity], b.V[q], lb.hist, lb.part, lb.S[parity], mem);
+                    return hipGetLastError();
+                }
+                return with_chunk64(f.chunk, [&](auto C) {
+                    hipLaunchKernelGGL((k64_lbfgs_eval_chunked<POT, G, FOLD, C>), grid, blk, sizeof(double) * ((size_t)6 * C + rowq), s, m, p, d.rep_base,
+                                       b.T, b.X[parity], b.V[parity], b.V[q], lb.hist, lb.part, lb.S[parity], mem);
+                    return hipGetLastError();
+                });
+            });
+        });
+    });
+}
+// the move that follows it: X[parity] -> X[parity^1], P[parity^1], the state S[parity] -> S[parity^1]
+hipError_t launch_lbfgs_move64(const DevModel& d, const double* model_host, const double* step_host, const double* fire_host, int fire_n_min,
+                               const Buffers64& b, const LbfgsBuffers64& lb, int parity, int mem, hipStream_t s) {
+    if (mem < 1 || mem > kLbfgsMaxPairs) return hipErrorInvalidValue;
+    const Model64 m = model64(d, model_host);
+    const Step64 p = step64(m, step_host);
+    const Fire64 fp = fire64(fire_host, fire_n_min);
+    const int q = parity ^ 1;
+    hipLaunchKernelGGL(k64_lbfgs_move, dim3((d.n + kLbfgsMoveRows64 - 1) / kLbfgsMoveRows64, d.nrep_g), dim3(kLbfgsMoveRows64), 0, s, m, p, fp,
+                       d.rep_base, b.X[parity], b.X[q], b.V[q], lb.hist, lb.part, b.P[q], lb.S[parity], lb.S[q], mem);
+    return hipGetLastError();
 }
 hipError_t launch_targets64(const DevModel& d, const double* model_host, int min_sep, const int32_t* t10, double* T, hipStream_t s) {
     const Form64 f = form64(d.noe_pot, model_host, 0.0);

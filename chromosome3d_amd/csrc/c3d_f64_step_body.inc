@@ -3,6 +3,9 @@
 //   k64_step_chunked  C3D_F64_CHUNKED 1: columns staged CHUNK at a time in two LDS buffers, the row side (a row's own coordinates, its
 //                     chain neighbours, x0 of the update) from global memory; the copy is LDS-DMA (global_load_lds)
 // Everything else — the scalar prologue, the order of every sum, the chain butterfly, the row update, the tile sums — is one text.
+// C3D_F64_LBFGS 1 makes the same text the body of k64_lbfgs_eval / k64_lbfgs_eval_chunked: staging, pair loop, row reduction and chain terms
+// are these lines (the force has k64_step's bits); the scalar prologue and the row finish are the L-BFGS evaluation's (c3d_lbfgs_eval_body.inc
+// in doubles: F to vout, y = F_prev - F into the ring, the Q dot products per row, the tile sums in the fixed 8-row tree).
     extern __shared__ __attribute__((aligned(16))) double sm64[];
     const int tile = blockIdx.x, rep = rep_base + blockIdx.y;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -50,6 +53,23 @@
     double ta0 = Ta[0], ta1 = Ta[64], tb0 = Tb[0], tb1 = Tb[64];        // np >= 128: in bounds whatever n is
     const int row = row0 + lane;
     double v0x = 0, v0y = 0, v0z = 0;
+#if C3D_F64_LBFGS
+    // ---- the ring of this step (kind 9 = a stage's first step: no pair yet); v0 = the previous evaluation's force, read from vin ----
+    constexpr int Q = kLbfgsQ;
+    const bool first = p.kind == 9;
+    int mem = mem0, nxt = 0;
+    if (!first) {      // (clamped into the ring whatever the state holds: a stage always begins with kind 9, which sets it)
+        mem = min(max(lsin[rep].mem, 1), kLbfgsMaxPairs);
+        nxt = min(max(lsin[rep].head, 0), mem - 1) + 1;
+        if (nxt == mem) nxt = 0;
+    }
+#if !C3D_F64_CHUNKED
+    if (lane < kRows64 && row < n && !first) {
+        const size_t ix = roff + row;
+        v0x = vin[ix]; v0y = vin[ix + np]; v0z = vin[ix + 2 * np];
+    }
+#endif
+#else
 #if !C3D_F64_CHUNKED
     if (lane < kRows64 && row < n && p.kind != 3 && p.kind != 6) {
         const double* vsrc = p.kind == 4 ? vinit : vin;
@@ -110,6 +130,7 @@
         }
         if (lane == 0) { scal[0] = lam; scal[1] = cm0; scal[2] = cm1; scal[3] = cm2; scal[4] = keep; scal[5] = mix; scal[6] = st.dt; }
     }
+#endif   // !C3D_F64_LBFGS
 #if C3D_F64_CHUNKED
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this wave's part of chunk 0 has landed; the barrier: everybody's
 #endif
@@ -202,7 +223,12 @@
             pair64<POT, GEN, FOLD>(m, nws4p, wr4p, R2, Trb[j], xb, yb, zb, x0, y0, z0, fxb, fyb, fzb);
         }
     }
-#if C3D_F64_CHUNKED
+#if C3D_F64_CHUNKED && C3D_F64_LBFGS
+    if (lane < kRows64 && row < n && !first) {          // (here, not ahead of the pair loop: as the velocities of k64_step_chunked below)
+        const size_t ix = roff + row;
+        v0x = vin[ix]; v0y = vin[ix + np]; v0z = vin[ix + 2 * np];
+    }
+#elif C3D_F64_CHUNKED
     // (the velocities of the two rows the wave finishes are asked for here, not ahead of the pair loop: held across the chunk loop, the
     //  six registers were one more than the kernel has at five waves a SIMD)
     if (lane < kRows64 && row < n && p.kind != 3 && p.kind != 6) {
@@ -224,6 +250,45 @@
         if (lane == 0) { Fx += cx; Fy += cy; Fz += cz; }
         if (lane == 1) { Fx += ox; Fy += oy; Fz += oz; }
     }
+#if C3D_F64_LBFGS
+    // ---- lanes 0, 1 finish one row each: F, y into ring slot nxt, the row's Q products (layout: c3d_internal.h "L-BFGS stage") ----
+    if (lane < kRows64) {
+        double* q = rowq + Q * (wave * kRows64 + lane);
+        for (int k = 0; k < Q; ++k) q[k] = 0.0;
+        if (row < n) {
+            const size_t ix = roff + row, iy = ix + np, iz = iy + np;
+            vout[ix] = Fx; vout[iy] = Fy; vout[iz] = Fz;
+            q[Q - 3] = fma(Fx, Fx, fma(Fy, Fy, Fz * Fz));
+            if (!first) {
+                double* hs = hist + (size_t)rep * lbfgs_hist_floats(np) + row;             // slot j, component c: + (3 j + c) np
+                double* hy = hs + (size_t)3 * kLbfgsMaxPairs * np;
+                const double yx = v0x - Fx, yy = v0y - Fy, yz = v0z - Fz;
+                double* yn = hy + (size_t)3 * nxt * np;
+                yn[0] = yx; yn[np] = yy; yn[2 * np] = yz;
+                const double* sn = hs + (size_t)3 * nxt * np;
+                const double sx = sn[0], sy = sn[np], sz = sn[2 * np];
+                q[Q - 4] = fma(sx, sx, fma(sy, sy, sz * sz));
+#pragma unroll
+                for (int j = 0; j < kLbfgsMaxPairs; ++j) {
+                    if (j >= mem) break;
+                    double ax, ay, az, bx, by, bz;
+                    if (j == nxt) { ax = sx; ay = sy; az = sz; bx = yx; by = yy; bz = yz; }
+                    else {
+                        const double* a = hs + (size_t)3 * j * np;
+                        const double* b = hy + (size_t)3 * j * np;
+                        ax = a[0]; ay = a[np]; az = a[2 * np]; bx = b[0]; by = b[np]; bz = b[2 * np];
+                    }
+                    q[4 * j + 0] = fma(Fx, ax, fma(Fy, ay, Fz * az));
+                    q[4 * j + 1] = fma(Fx, bx, fma(Fy, by, Fz * bz));
+                    q[4 * j + 2] = fma(ax, yx, fma(ay, yy, az * yz));
+                    q[4 * j + 3] = fma(bx, yx, fma(by, yy, bz * yz));
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (tid < Q) part[((size_t)rep * m.ntiles + tile) * Q + tid] = row_sum8_64(rowq + tid, Q);     // tile sums, the fixed 8-row tree
+#else
     // ---- lanes 0, 1 finish one row each (the CPU restatement's update, c3o_md_step / c3o_fire_step) ----
     const double lam = scal[0], cm0 = scal[1], cm1 = scal[2], cm2 = scal[3], keep = scal[4], mix = scal[5];
     st.dt = scal[6];
@@ -279,3 +344,4 @@
         const double* q = rowq + tid;
         pout[((size_t)rep * m.ntiles + tile) * 4 + tid] = ((q[0] + q[4]) + (q[8] + q[12])) + ((q[16] + q[20]) + (q[24] + q[28]));
     }
+#endif   // C3D_F64_LBFGS

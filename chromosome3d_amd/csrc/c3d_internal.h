@@ -295,6 +295,19 @@ inline Form64 form64(int noe_pot, const double* model_host, double w_all, int n 
 }
 hipError_t launch_step64(const DevModel& d, const double* model_host, const double* step_host, const double* fire_host, int fire_n_min,
                          const Buffers64& b, int parity, int column_chunk, hipStream_t s);   // column_chunk: the option, 0 = by size
+// The L-BFGS stage in fp64 (option f64_lbfgs on a precision-64 context): k64_lbfgs_eval[_chunked] + k64_lbfgs_move, the layouts of the
+// fp32 stage above in doubles with np columns: hist [nrep][2: s, y][kLbfgsMaxPairs][3][np] (lbfgs_hist_floats(np) doubles a replica),
+// part [nrep][ntiles][kLbfgsQ], S [2][nrep] LbfgsState; V[parity^1] = the force of the evaluation, P[parity^1] = (move.move, F.F, 0, 0).
+// The first step's gamma (kind 9) is dt_start^2 kAccel / mass formed in fp64: kind 6's first length in k64_step.
+struct LbfgsBuffers64 {
+    double* hist = nullptr;
+    double* part = nullptr;
+    LbfgsState* S[2] = {nullptr, nullptr};
+};
+hipError_t launch_lbfgs_eval64(const DevModel& d, const double* model_host, const double* step_host, const Buffers64& b, const LbfgsBuffers64& lb,
+                               int parity, int mem, int column_chunk, hipStream_t s);
+hipError_t launch_lbfgs_move64(const DevModel& d, const double* model_host, const double* step_host, const double* fire_host, int fire_n_min,
+                               const Buffers64& b, const LbfgsBuffers64& lb, int parity, int mem, hipStream_t s);
 hipError_t launch_targets64(const DevModel& d, const double* model_host, int min_sep, const int32_t* t10, double* T, hipStream_t s);
 // the integer tenths of a restraint list (R pairs, 0-based, every pair once) into the zeroed n x n matrix t10, both triangles
 hipError_t launch_tenths64(int n, int R, const int32_t* ri, const int32_t* rj, const int32_t* rt10, int32_t* t10, hipStream_t s);

@@ -25,8 +25,8 @@ static void usage() {
             "usage: c3d_solve (--if <IF matrix> | --tbl <contact.tbl> --n <beads>) --out <dir> [--id <ID>]\n"
             "                 [-k <K=11>] [-a <alpha=0.5>] [-m <models=20>] [--seed <82364>] [--first-replica <0>]\n"
             "                 [--device <0>] [--min-steps <3000>] [--gtol <1e-2>] [--final-minimiser <1>] [--lbfgs] [--embed] [--no-graph] [--quiet]\n"
-            "                 [--precision <32>   64: anneal with the fp64 step kernels (the reference's arithmetic; no --lbfgs); beyond 2560 beads the\n"
-            "                                     fp64 target matrix takes 8 n^2 bytes more]\n"
+            "                 [--precision <32>   64: anneal with the fp64 step kernels (the reference's arithmetic; with --lbfgs the final stage is\n"
+            "                                     L-BFGS in fp64); beyond 2560 beads the fp64 target matrix takes 8 n^2 bytes more]\n"
             "                 [--embed-max-beads <4549>   the largest matrix --embed takes, up to 16384 (memory: 8 n^2 bytes + 4 n^2 per replica of a batch)]\n"
             "                 [--seq <one-letter residue codes | @fasta file>   residue names of the models (default: all MET)]\n"
             "                 [--similarity <path>   after the solve, the replicas against one another: one row `a b spearman rmsd` per ordered pair of\n"
@@ -162,6 +162,7 @@ int main(int argc, char** argv) {
     CHECK(c3d_set_schedule(ctx, stages.data(), (int)stages.size(), &fire, (float)gtol, 250));
     CHECK(c3d_set_option(ctx, "use_graph", use_graph));
     if (precision != 32) {
+        if (lbfgs) CHECK(c3d_set_option(ctx, "f64_lbfgs", 1));        // --lbfgs beside --precision 64 is the consent to the fp64 L-BFGS stage
         CHECK(c3d_set_option(ctx, "precision", precision));
         // as with max_beads above: the matrix that was read is the user's consent to the fp64 target matrix it needs
         if (n > C3D_F64_MAX_BEADS_DEFAULT && n <= C3D_F64_MAX_BEADS_LIMIT) CHECK(c3d_set_option(ctx, "f64_max_beads", n));

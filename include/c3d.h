@@ -80,8 +80,10 @@ typedef struct {
                             move capped at fire.max_step, a pair kept only if its curvature is positive, the memory dropped when the
                             direction is not downhill — for the first `final_minimiser_steps` steps, then FIRE from a fresh state for what
                             is left of nsteps (option final_minimiser does not apply to it).  Per-step path only: two launches a step
-                            (k_lbfgs_eval, k_lbfgs_move), whatever `resident` says; no fp64 form (precision 64 refuses it); symmetric
-                            tiles do not apply to its steps.  About half the force evaluations of kind 5 to the same exit test      */
+                            (k_lbfgs_eval, k_lbfgs_move), whatever `resident` says; symmetric tiles do not apply to its steps.  On a
+                            precision-64 context it runs in fp64 behind the option f64_lbfgs (k64_lbfgs_eval, k64_lbfgs_move: the same
+                            method in doubles, the first length dt_start^2 kAccel / mass formed in fp64); without that option precision
+                            64 and a stage of kind 8 refuse each other.  About half the force evaluations of kind 5 to the same exit test */
     int32_t nsteps;
     float dt;          /* ps (MD)                                                        */
     float w_all;       /* `weights * w`                                                  */
@@ -153,7 +155,8 @@ int c3d_set_schedule(c3d_ctx* ctx, const c3d_stage* stages, int n_stages, const 
  *                   the limit in force).  The fp32 path takes up to 5120 beads by default and up to 16384 behind max_beads (below);
  *                   c3d_set_if_matrix / c3d_set_restraints refuse more.  A precision-64 context takes its targets from the integer tenths
  *                   of c3d_set_if_matrix or from c3d_set_restraints' list (pairs closer than min_sep carry no restraint, as in the matrix).
- *                   64 and a schedule with a stage of kind 8 exclude each other: whichever call comes second returns C3D_ERR_INVALID
+ *                   64 and a schedule with a stage of kind 8 exclude each other unless f64_lbfgs is 1 (below): whichever call comes second
+ *                   returns C3D_ERR_INVALID
  *   max_beads       5120 (default) .. 16384 (C3D_MAX_BEADS_DEFAULT .. C3D_MAX_BEADS_LIMIT): the largest matrix c3d_set_if_matrix and
  *                   c3d_set_restraints accept; set it before them (other values: C3D_ERR_INVALID).  Raising it is consent to the memory of a
  *                   large matrix: about 8 n npad bytes per context stay resident (targets and the pair targets; npad = n rounded up to
@@ -167,7 +170,14 @@ int c3d_set_schedule(c3d_ctx* ctx, const c3d_stage* stages, int n_stages, const 
  *                   beads the fp64 step stages a replica's coordinates in LDS (k64_step: exactly the kernels of earlier releases); beyond,
  *                   it streams the columns through two LDS buffers, 512 at a time (k64_step_chunked; same bits wherever both run).
  *                   Raising it is consent to the fp64 target matrix, 8 n np bytes (np = n rounded up to 128): 2.1 GB at 16384, on top of
- *                   the 1 GB of integer tenths on the device.  max_beads is needed as well beyond 5120.  A kind-8 stage stays refused
+ *                   the 1 GB of integer tenths on the device.  max_beads is needed as well beyond 5120
+ *   f64_lbfgs       0 (default) or 1 (other values: C3D_ERR_INVALID): the caller's consent to stages of kind 8 on a precision-64 context.
+ *                   At 0 c3d_set_schedule refuses a kind-8 stage under precision 64, and precision = 64 refuses a schedule that holds
+ *                   one.  At 1 both are accepted, in either order, and the L-BFGS steps run in fp64 (k64_lbfgs_eval in k64_step's staged
+ *                   or chunked form, then k64_lbfgs_move), up to f64_max_beads; lbfgs_memory, final_minimiser_steps, the stats lbfgs_steps /
+ *                   lbfgs_resets and c3d_step_kernel_name work as in fp32.  Their history, 2 x 8 x 3 x np doubles a replica (6.3 MB at 16384
+ *                   beads), is allocated when the first such step runs and freed with the replicas.  Setting it back to 0 is refused while
+ *                   precision is 64 and the schedule holds a kind-8 stage.  Setting it releases nothing on the device
  *   f64_column_chunk 0 (default): the fp64 step's column source by size — staged up to 2560 beads, the chunked form with 512 columns a
  *                   pass beyond; 256, 512 or 1024 = the chunked form with that many columns a pass wherever n is larger than it.  Same
  *                   bits either way (test and measurement knob; other values: C3D_ERR_INVALID)

@@ -162,6 +162,8 @@ void sym_tile_list(const DevModel&, int2* out) { out[0].x = 0; out[0].y = 0; }
 hipError_t launch_step_sym(const DevModel&, const DevStep&, const DevFire&, const DevBuffers&, int, const void*, float*, hipStream_t) { LaunchScope ls; return hipSuccess; }
 int cols64(int n) { return (n + 127) / 128 * 128; }
 hipError_t launch_step64(const DevModel&, const double*, const double*, const double*, int, const Buffers64&, int, int, hipStream_t) { LaunchScope ls; return hipSuccess; }
+hipError_t launch_lbfgs_eval64(const DevModel&, const double*, const double*, const Buffers64&, const LbfgsBuffers64&, int, int, int, hipStream_t) { LaunchScope ls; return hipSuccess; }
+hipError_t launch_lbfgs_move64(const DevModel&, const double*, const double*, const double*, int, const Buffers64&, const LbfgsBuffers64&, int, int, hipStream_t) { LaunchScope ls; return hipSuccess; }
 hipError_t launch_tenths64(int, int, const int32_t*, const int32_t*, const int32_t*, int32_t*, hipStream_t) { LaunchScope ls; return hipSuccess; }
 hipError_t launch_targets64(const DevModel&, const double*, int, const int32_t*, double*, hipStream_t) { LaunchScope ls; return hipSuccess; }
 hipError_t launch_import64(const DevModel&, const float*, const Buffers64&, hipStream_t) { LaunchScope ls; return hipSuccess; }
