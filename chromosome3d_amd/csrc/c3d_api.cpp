@@ -219,6 +219,7 @@ struct c3d_ctx {
     int device_ranks = 0;                  // option device_ranks: who ranks the IF matrix for c3d_score_replicas (c3d.h)
     long device_rank_runs = 0, score_wide_runs = 0;   // stats: calls that ranked on the device / that took the sized-histogram re-run
     long compare_runs = 0;                 // stat: completed calls of c3d_compare_replicas
+    long f64_evals = 0;                    // stat: completed calls of c3d_eval_f64
     long k1_recomputed = 0, k1_patched = 0;   // K1: near-tie elements redone on the host in the reference's order / changed by it
     long graph_captures = 0, graph_launches = 0, step_launches = 0, resident_launches = 0, cluster_launches = 0;
     bool has_two_point = false;            // the program holds two-point minimiser steps (run_ops splits ranges at their borders)
@@ -261,7 +262,7 @@ void free_replica_buffers(c3d_ctx* c) {
     dev_free(c->lb.hist); dev_free(c->lb.part); dev_free(c->lb.S[0]); dev_free(c->lb.S[1]);
     dev_free(c->lb64.hist); dev_free(c->lb64.part); dev_free(c->lb64.S[0]); dev_free(c->lb64.S[1]);
     c->lbfgs_parity = -1;
-    dev_free(c->b64.T); dev_free(c->b64.t10); dev_free(c->b64.Vinit);
+    dev_free(c->b64.T); dev_free(c->b64.t10); dev_free(c->b64.Vinit); dev_free(c->b64.F);
     for (int k = 0; k < 2; ++k) { dev_free(c->b64.X[k]); dev_free(c->b64.V[k]); dev_free(c->b64.P[k]); dev_free(c->b64.S[k]); }
     c->have_replicas = false;
 }
@@ -1786,6 +1787,69 @@ extern "C" int c3d_get_velocities(c3d_ctx* c, float* v) {
     return get_soa(c, c->buf.V[c->parity], v);
 }
 
+// ---- the boundary of a precision-64 context in doubles ----
+// what its four entries need: the fp64 state, which exists from c3d_init_replicas on a precision-64 context until the replicas are dropped
+static int need_f64_state(const c3d_ctx* c, const char* fn) {
+    if (!c) return fail(C3D_ERR_INVALID, std::string(fn) + ": null context");
+    if (c->precision != 64)
+        return fail(C3D_ERR_INVALID, std::string(fn) + ": the context holds no fp64 state: its precision is 32 (set precision 64 before c3d_init_replicas)");
+    if (!c->have_replicas || !c->b64.X[0])
+        return fail(C3D_ERR_INVALID, std::string(fn) + ": the context holds no fp64 state yet: call c3d_init_replicas first");
+    return C3D_OK;
+}
+// SoA doubles [nrep][3][np] on the device -> [nrep][n][3] of the caller, through the pinned stage: every value as it is
+static int get_soa64(c3d_ctx* c, const double* dev, double* aos) {
+    const int n = c->n, np = c3d::cols64(n);
+    if (int rc = read_back(c, dev, sizeof(double) * (size_t)c->nrep * 3 * np)) return rc;
+    const double* h = static_cast<const double*>(c->h_stage);
+    for (int r = 0; r < c->nrep; ++r)
+        for (int comp = 0; comp < 3; ++comp) {
+            const double* src = h + ((size_t)r * 3 + comp) * np;
+            for (int i = 0; i < n; ++i) aos[((size_t)r * n + i) * 3 + comp] = src[i];
+        }
+    return C3D_OK;
+}
+extern "C" int c3d_get_coords_f64(c3d_ctx* c, double* xyz) {
+    if (int rc = need_f64_state(c, "c3d_get_coords_f64")) return rc;
+    if (!xyz) return fail(C3D_ERR_INVALID, "c3d_get_coords_f64: null buffer");
+    C3D_ENTRY(c, unit_bit(UNIT_F64));
+    return get_soa64(c, c->b64.X[c->parity], xyz);
+}
+extern "C" int c3d_get_velocities_f64(c3d_ctx* c, double* v) {
+    if (int rc = need_f64_state(c, "c3d_get_velocities_f64")) return rc;
+    if (!v) return fail(C3D_ERR_INVALID, "c3d_get_velocities_f64: null buffer");
+    C3D_ENTRY(c, unit_bit(UNIT_F64));
+    return get_soa64(c, c->b64.V[c->parity], v);
+}
+// c3d_set_coords + import64 without the pass through floats: both parities of X = these doubles (padding beads as k64_import places them),
+// both parities of V zero, then the float mirror of the current parity through the existing export
+extern "C" int c3d_set_coords_f64(c3d_ctx* c, const double* xyz) {
+    if (int rc = need_f64_state(c, "c3d_set_coords_f64")) return rc;
+    if (!xyz) return fail(C3D_ERR_INVALID, "c3d_set_coords_f64: null buffer");
+    const int n = c->n, np = c3d::cols64(n);
+    const size_t cnt = (size_t)c->nrep * n * 3, n3 = (size_t)c->nrep * 3 * np;
+    for (size_t k = 0; k < cnt; ++k)
+        if (!std::isfinite(xyz[k])) return fail(C3D_ERR_INVALID, "c3d_set_coords_f64: non-finite coordinate; nothing was copied");
+    C3D_ENTRY(c, unit_bit(UNIT_F64));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (int rc = ensure_stage(c, sizeof(double) * n3)) return rc;
+    double* h = static_cast<double*>(c->h_stage);
+    for (int r = 0; r < c->nrep; ++r)
+        for (int comp = 0; comp < 3; ++comp) {
+            double* dst = h + ((size_t)r * 3 + comp) * np;
+            for (int i = 0; i < n; ++i) dst[i] = xyz[((size_t)r * n + i) * 3 + comp];
+            for (int i = n; i < np; ++i) dst[i] = (double)c3d::kPadCoord * (comp + 1) + 16.0 * (i - n);
+        }
+    for (int k = 0; k < 2; ++k) {
+        HIP_TRY(hipMemcpyAsync(c->b64.X[k], h, sizeof(double) * n3, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemsetAsync(c->b64.V[k], 0, sizeof(double) * n3, c->stream));
+    }
+    hipError_t e = c3d::launch_export64(dev_model(c), c->b64, c->parity, c->buf.X[c->parity], c->buf.V[c->parity], c->buf.P[c->parity], c->stream);
+    if (e != hipSuccess) return fail(C3D_ERR_HIP, std::string("fp64 export: ") + hipGetErrorString(e));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return C3D_OK;
+}
+
 extern "C" long c3d_schedule_length(const c3d_ctx* c) {
     if (!c) return 0;
     long n = 0;
@@ -1922,6 +1986,7 @@ extern "C" int c3d_get_stat(const c3d_ctx* c, const char* key, double* value) {
     else if (!strcmp(key, "device_rank_runs")) *value = (double)c->device_rank_runs;
     else if (!strcmp(key, "score_wide_runs")) *value = (double)c->score_wide_runs;
     else if (!strcmp(key, "compare_runs")) *value = (double)c->compare_runs;
+    else if (!strcmp(key, "f64_evals")) *value = (double)c->f64_evals;
     else if (!strcmp(key, "cluster_xcd_count")) *value = (double)c->xcd_count;
     else if (!strcmp(key, "cluster_xcd_base")) *value = (double)c->xcd_base;
     else if (!strcmp(key, "cluster_ok")) *value = c->cl_ok ? 1.0 : 0.0;
@@ -1993,6 +2058,34 @@ extern "C" int c3d_eval(c3d_ctx* c, float w_all, float w_vdw, float repel_s, flo
         const double* h = static_cast<const double*>(c->h_stage);
         for (int r = 0; r < c->nrep; ++r) for (int k = 0; k < 3; ++k) e[3 * r + k] = h[4 * r + k];
     }
+    return C3D_OK;
+}
+
+// c3d_eval on the fp64 side: the fp64 kernels at the fp64 coordinates, into a buffer of the context's own; reads X[parity] and T, writes b64.F
+extern "C" int c3d_eval_f64(c3d_ctx* c, double w_all, double w_vdw, double repel_s, double* F, double* e) {
+    if (int rc = need_f64_state(c, "c3d_eval_f64")) return rc;
+    if (!F && !e) return fail(C3D_ERR_INVALID, "c3d_eval_f64: F and e are both NULL");
+    C3D_ENTRY(c, unit_bit(UNIT_F64));
+    const size_t n3 = (size_t)c->nrep * 3 * c3d::cols64(c->n);
+    if (!c->b64.F) HIP_TRY(hipMalloc(&c->b64.F, sizeof(double) * (n3 + 4 * (size_t)c->nrep)));
+    const c3d::DevModel m = dev_model(c);
+    double mh[15];
+    model_host64(c, mh);
+    if (F) {
+        const double sh[6] = {3.0, 0.0, w_all, w_vdw, repel_s, 0.0};
+        hipError_t err = c3d::launch_eval_forces64(m, mh, sh, c->b64, c->parity, c->f64_column_chunk, c->b64.F, c->stream);
+        if (err != hipSuccess) return fail(C3D_ERR_HIP, std::string("fp64 eval launch: ") + hipGetErrorString(err));
+        if (int rc = get_soa64(c, c->b64.F, F)) return rc;
+    }
+    if (e) {
+        const double rr = repel_s * (double)c->model.r0_rep;
+        hipError_t err = c3d::launch_energy64(m, mh, rr * rr, c->b64, c->parity, c->b64.F + n3, c->stream);
+        if (err != hipSuccess) return fail(C3D_ERR_HIP, std::string("fp64 energy launch: ") + hipGetErrorString(err));
+        if (int rc = read_back(c, c->b64.F + n3, sizeof(double) * 4 * (size_t)c->nrep)) return rc;
+        const double* h = static_cast<const double*>(c->h_stage);
+        for (int r = 0; r < c->nrep; ++r) for (int k = 0; k < 3; ++k) e[3 * r + k] = h[4 * r + k];
+    }
+    ++c->f64_evals;
     return C3D_OK;
 }
 

@@ -222,7 +222,9 @@ __global__ __launch_bounds__(kBlock64) __attribute__((amdgpu_waves_per_eu(5))) v
                                                     FireState64* __restrict__ sout) {
 #define C3D_F64_CHUNKED 0
 #define C3D_F64_LBFGS 0
+#define C3D_F64_EVAL 0
 #include "c3d_f64_step_body.inc"
+#undef C3D_F64_EVAL
 #undef C3D_F64_LBFGS
 #undef C3D_F64_CHUNKED
 }
@@ -239,7 +241,9 @@ __global__ __launch_bounds__(kBlock64) __attribute__((amdgpu_waves_per_eu(5))) v
     static_assert(CHUNK % 128 == 0, "a pass of the two-column main loop (j, j + 64, stride 128) never straddles a chunk");
 #define C3D_F64_CHUNKED 1
 #define C3D_F64_LBFGS 0
+#define C3D_F64_EVAL 0
 #include "c3d_f64_step_body.inc"
+#undef C3D_F64_EVAL
 #undef C3D_F64_LBFGS
 #undef C3D_F64_CHUNKED
 }
@@ -261,7 +265,9 @@ __global__ __launch_bounds__(kBlock64) __attribute__((amdgpu_waves_per_eu(5))) v
                                                     const LbfgsState* __restrict__ lsin, const int mem0) {
 #define C3D_F64_CHUNKED 0
 #define C3D_F64_LBFGS 1
+#define C3D_F64_EVAL 0
 #include "c3d_f64_step_body.inc"
+#undef C3D_F64_EVAL
 #undef C3D_F64_LBFGS
 #undef C3D_F64_CHUNKED
 }
@@ -274,7 +280,9 @@ __global__ __launch_bounds__(kBlock64) __attribute__((amdgpu_waves_per_eu(5))) v
     static_assert(CHUNK % 128 == 0, "a pass of the two-column main loop (j, j + 64, stride 128) never straddles a chunk");
 #define C3D_F64_CHUNKED 1
 #define C3D_F64_LBFGS 1
+#define C3D_F64_EVAL 0
 #include "c3d_f64_step_body.inc"
+#undef C3D_F64_EVAL
 #undef C3D_F64_LBFGS
 #undef C3D_F64_CHUNKED
 }
@@ -431,6 +439,85 @@ __global__ __launch_bounds__(kLbfgsMoveRows64) void k64_lbfgs_move(const Model64
         double* dst = reinterpret_cast<double*>(sout + rep);
         for (int k = tid; k < (int)(sizeof(LbfgsState) / sizeof(double)); k += ROWS) dst[k] = src[k];
     }
+}
+
+// ---- the forces hook of a precision-64 context (c3d_eval_f64): k64_step's force, nothing else ----------
+// The same body text once more (C3D_F64_EVAL): staging, chunk pipeline, passes, reduce_rows64, the FOLD multiply and the chain butterfly
+// are k64_step's lines, so F has the bits of the force k64_step and k64_lbfgs_eval integrate.  fout [nrep][3][np] is a buffer of the
+// context's own (never the velocity slot); p.kind is 3 (no kind-4 "no force" step here).
+template <int POT, bool GEN, bool FOLD = false>
+__global__ __launch_bounds__(kBlock64) __attribute__((amdgpu_waves_per_eu(5))) void k64_eval_forces(const Model64 m, const Step64 p, const int rep_base,
+                                                    const double* __restrict__ T, const double* __restrict__ xin,
+                                                    double* __restrict__ fout) {
+#define C3D_F64_CHUNKED 0
+#define C3D_F64_LBFGS 0
+#define C3D_F64_EVAL 1
+#include "c3d_f64_step_body.inc"
+#undef C3D_F64_EVAL
+#undef C3D_F64_LBFGS
+#undef C3D_F64_CHUNKED
+}
+template <int POT, bool GEN, bool FOLD, int CHUNK>
+__global__ __launch_bounds__(kBlock64) __attribute__((amdgpu_waves_per_eu(5))) void k64_eval_forces_chunked(const Model64 m, const Step64 p, const int rep_base,
+                                                    const double* __restrict__ T, const double* __restrict__ xin,
+                                                    double* __restrict__ fout) {
+    static_assert(CHUNK % 128 == 0, "a pass of the two-column main loop (j, j + 64, stride 128) never straddles a chunk");
+#define C3D_F64_CHUNKED 1
+#define C3D_F64_LBFGS 0
+#define C3D_F64_EVAL 1
+#include "c3d_f64_step_body.inc"
+#undef C3D_F64_EVAL
+#undef C3D_F64_LBFGS
+#undef C3D_F64_CHUNKED
+}
+
+// k_energy (c3d_device.hip) over the fp64 coordinates and the fp64 targets T [n][np] (Angstrom; "no restraint" is 0, or kNoTarget64 where the
+// fast soft lower side runs): unweighted energies (noe x S, bond + angle, repel x k_rep) of a replica, eout [nrep][4].  One workgroup per
+// replica; thread t takes rows t, t + 256, ... and the pairs j > i in ascending order, the 256 partial sums meet in one fixed LDS tree: two
+// calls return the same bits.  Square roots are the correctly rounded ones (this is not a hot path); rep_r2 = (repel_s r0_rep)^2 in double.
+__global__ __launch_bounds__(256) void k64_energy(const Model64 m, const double rep_r2, const double* __restrict__ T,
+                                                 const double* __restrict__ xin, double* __restrict__ eout) {
+    __shared__ double red[3][256];
+    const int rep = blockIdx.x, tid = threadIdx.x, np = m.np;
+    const double* x = xin + (size_t)rep * 3 * np;
+    const double* y = x + np;
+    const double* z = y + np;
+    double e_noe = 0, e_bond = 0, e_rep = 0;
+    const double rs = m.rs, c = m.tail_c, b = m.tail_b;
+    const double a = rs * rs - b / rs - c * rs;
+    // lower side of potentials 3 / 4: E = ma + mb / D^mexp + mc D beyond mrs (Model64::mtail_b is the force's coefficient: mb x mexp)
+    const bool pot3 = m.noe_pot == 3 || m.noe_pot == 4;
+    const double mrs = m.mrs, mc = m.mtail_c, mb = m.mexp == 2 ? 0.5 * m.mtail_b : m.mtail_b;
+    const double ma = mrs * mrs - (m.mexp == 2 ? mb / (mrs * mrs) : mb / mrs) - mc * mrs;
+    const double a0sq = m.a0 * m.a0;
+    for (int i = tid; i < m.n; i += 256) {
+        const double xi = x[i], yi = y[i], zi = z[i];
+        const double* Ti = T + (size_t)i * np;
+        for (int j = i + 1; j < m.n; ++j) {
+            const double dx = xi - x[j], dy = yi - y[j], dz = zi - z[j];
+            double r2 = dx * dx + dy * dy + dz * dz;
+            if (r2 < 1e-12) r2 = 1e-12;
+            const double t = Ti[j];
+            const int sep = j - i;
+            if (t > 0 && t < 0.5 * kNoTarget64) {
+                const double delta = sqrt(r2) - t, ad = fabs(delta);
+                bool soft;
+                if (m.noe_pot == 0) soft = ad > rs; else if (m.noe_pot == 1 || pot3) soft = delta > rs; else soft = false;
+                if (pot3 && delta < -mrs) e_noe += ma + (m.mexp == 2 ? mb / (ad * ad) : mb / ad) + mc * ad;
+                else e_noe += soft ? (a + b / ad + c * ad) : delta * delta;
+            }
+            if (sep == 1) { const double dl = sqrt(r2) - m.b0; e_bond += m.k_bond * dl * dl; }
+            if (sep == 2 && m.k_ang > 0 && (m.ang_mode == 1 || r2 < a0sq)) { const double dl = sqrt(r2) - m.a0; e_bond += m.k_ang * dl * dl; }
+            if (sep >= m.rep_sep && r2 < rep_r2) { const double q = rep_r2 - r2; e_rep += q * q; }
+        }
+    }
+    red[0][tid] = e_noe * m.s_noe; red[1][tid] = e_bond; red[2][tid] = e_rep * m.k_rep;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s) { red[0][tid] += red[0][tid + s]; red[1][tid] += red[1][tid + s]; red[2][tid] += red[2][tid + s]; }
+        __syncthreads();
+    }
+    if (tid == 0) { eout[rep * 4 + 0] = red[0][0]; eout[rep * 4 + 1] = red[1][0]; eout[rep * 4 + 2] = red[2][0]; eout[rep * 4 + 3] = 0; }
 }
 
 // T[i][j] = 0.1 * t10 where a restraint exists (|i-j| >= min_sep, t10 > 0), else 0; np columns per row
@@ -600,6 +687,38 @@ hipError_t launch_lbfgs_move64(const DevModel& d, const double* model_host, cons
     const int q = parity ^ 1;
     hipLaunchKernelGGL(k64_lbfgs_move, dim3((d.n + kLbfgsMoveRows64 - 1) / kLbfgsMoveRows64, d.nrep_g), dim3(kLbfgsMoveRows64), 0, s, m, p, fp,
                        d.rep_base, b.X[parity], b.X[q], b.V[q], lb.hist, lb.part, b.P[q], lb.S[parity], lb.S[q], mem);
+    return hipGetLastError();
+}
+// c3d_eval_f64's force: launch_step64's form from the doubles launch_step64 would form (step_host's kind is ignored: 3), X[parity] -> Fout
+hipError_t launch_eval_forces64(const DevModel& d, const double* model_host, const double* step_host, const Buffers64& b, int parity,
+                                int column_chunk, double* Fout, hipStream_t s) {
+    const Model64 m = model64(d, model_host);
+    Step64 p = step64(m, step_host);
+    p.kind = 3;
+    const dim3 grid(d.ntiles, d.nrep_g), blk(kBlock64);
+    const Form64 f = form64(d.noe_pot, model_host, p.w_all, d.n, column_chunk);
+    return with_pot(f.pot, [&](auto P) {
+        return with_bool(f.gen, [&](auto G) {
+            return with_bool(f.fold, [&](auto F) {
+                constexpr int POT = G && P == 4 ? 2 : P;            // (as launch_step64)
+                constexpr bool FOLD = F && POT == 4 && !G;
+                if (f.chunk == 0) {
+                    hipLaunchKernelGGL((k64_eval_forces<POT, G, FOLD>), grid, blk, sizeof(double) * (size_t)3 * m.np, s, m, p, d.rep_base, b.T,
+                                       b.X[parity], Fout);
+                    return hipGetLastError();
+                }
+                return with_chunk64(f.chunk, [&](auto C) {
+                    hipLaunchKernelGGL((k64_eval_forces_chunked<POT, G, FOLD, C>), grid, blk, sizeof(double) * (size_t)6 * C, s, m, p, d.rep_base,
+                                       b.T, b.X[parity], Fout);
+                    return hipGetLastError();
+                });
+            });
+        });
+    });
+}
+hipError_t launch_energy64(const DevModel& d, const double* model_host, double rep_r2, const Buffers64& b, int parity, double* Eout, hipStream_t s) {
+    const Model64 m = model64(d, model_host);
+    hipLaunchKernelGGL(k64_energy, dim3(d.nrep), dim3(256), 0, s, m, rep_r2, b.T, b.X[parity], Eout);
     return hipGetLastError();
 }
 hipError_t launch_targets64(const DevModel& d, const double* model_host, int min_sep, const int32_t* t10, double* T, hipStream_t s) {

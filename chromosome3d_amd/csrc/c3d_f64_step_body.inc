@@ -6,6 +6,9 @@
 // C3D_F64_LBFGS 1 makes the same text the body of k64_lbfgs_eval / k64_lbfgs_eval_chunked: staging, pair loop, row reduction and chain terms
 // are these lines (the force has k64_step's bits); the scalar prologue and the row finish are the L-BFGS evaluation's (c3d_lbfgs_eval_body.inc
 // in doubles: F to vout, y = F_prev - F into the ring, the Q dot products per row, the tile sums in the fixed 8-row tree).
+// C3D_F64_EVAL 1 makes it the body of k64_eval_forces / k64_eval_forces_chunked (c3d_eval_f64): the same staging, pair loop, row reduction,
+// FOLD multiply and chain terms, no scalar prologue at all (no sums, no FIRE state, no ring), and the row finish is "lanes 0 and 1 store F
+// of their row" into fout [nrep][3][np].  Nothing of the solve is read but xin and T, nothing is written but fout.
     extern __shared__ __attribute__((aligned(16))) double sm64[];
     const int tile = blockIdx.x, rep = rep_base + blockIdx.y;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -52,8 +55,12 @@
     const double* Tb = T + (size_t)rb * np + lane;
     double ta0 = Ta[0], ta1 = Ta[64], tb0 = Tb[0], tb1 = Tb[64];        // np >= 128: in bounds whatever n is
     const int row = row0 + lane;
+#if !C3D_F64_EVAL
     double v0x = 0, v0y = 0, v0z = 0;
-#if C3D_F64_LBFGS
+#endif
+#if C3D_F64_EVAL
+    // (forces only: no scalar prologue)
+#elif C3D_F64_LBFGS
     // ---- the ring of this step (kind 9 = a stage's first step: no pair yet); v0 = the previous evaluation's force, read from vin ----
     constexpr int Q = kLbfgsQ;
     const bool first = p.kind == 9;
@@ -130,7 +137,7 @@
         }
         if (lane == 0) { scal[0] = lam; scal[1] = cm0; scal[2] = cm1; scal[3] = cm2; scal[4] = keep; scal[5] = mix; scal[6] = st.dt; }
     }
-#endif   // !C3D_F64_LBFGS
+#endif   // the mode's prologue
 #if C3D_F64_CHUNKED
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this wave's part of chunk 0 has landed; the barrier: everybody's
 #endif
@@ -223,7 +230,8 @@
             pair64<POT, GEN, FOLD>(m, nws4p, wr4p, R2, Trb[j], xb, yb, zb, x0, y0, z0, fxb, fyb, fzb);
         }
     }
-#if C3D_F64_CHUNKED && C3D_F64_LBFGS
+#if C3D_F64_EVAL
+#elif C3D_F64_CHUNKED && C3D_F64_LBFGS
     if (lane < kRows64 && row < n && !first) {          // (here, not ahead of the pair loop: as the velocities of k64_step_chunked below)
         const size_t ix = roff + row;
         v0x = vin[ix]; v0y = vin[ix + np]; v0z = vin[ix + 2 * np];
@@ -250,7 +258,14 @@
         if (lane == 0) { Fx += cx; Fy += cy; Fz += cz; }
         if (lane == 1) { Fx += ox; Fy += oy; Fz += oz; }
     }
-#if C3D_F64_LBFGS
+#if C3D_F64_EVAL
+    // ---- lanes 0, 1 store F of their row ----
+    (void)rowq;
+    if (lane < kRows64 && row < n) {
+        const size_t ix = roff + row;
+        fout[ix] = Fx; fout[ix + np] = Fy; fout[ix + 2 * np] = Fz;
+    }
+#elif C3D_F64_LBFGS
     // ---- lanes 0, 1 finish one row each: F, y into ring slot nxt, the row's Q products (layout: c3d_internal.h "L-BFGS stage") ----
     if (lane < kRows64) {
         double* q = rowq + Q * (wave * kRows64 + lane);
@@ -344,4 +359,4 @@
         const double* q = rowq + tid;
         pout[((size_t)rep * m.ntiles + tile) * 4 + tid] = ((q[0] + q[4]) + (q[8] + q[12])) + ((q[16] + q[20]) + (q[24] + q[28]));
     }
-#endif   // C3D_F64_LBFGS
+#endif   // the mode's row finish

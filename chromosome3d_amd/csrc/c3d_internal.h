@@ -261,6 +261,7 @@ struct Buffers64 {
     double* Vinit = nullptr;
     double* P[2] = {nullptr, nullptr};
     void* S[2] = {nullptr, nullptr};
+    double* F = nullptr;           // c3d_eval_f64's force [nrep][3][np], then its energies [nrep][4]; allocated at first use
 };
 int cols64(int n);
 // The staged kernel (k64_step) puts 3 * 8 * np bytes of coordinates in LDS: up to the 64 KB a launch gets without opt-in (n <= 2560,
@@ -313,6 +314,13 @@ hipError_t launch_targets64(const DevModel& d, const double* model_host, int min
 hipError_t launch_tenths64(int n, int R, const int32_t* ri, const int32_t* rj, const int32_t* rt10, int32_t* t10, hipStream_t s);
 hipError_t launch_import64(const DevModel& d, const float* Xf, const Buffers64& b, hipStream_t s);
 hipError_t launch_export64(const DevModel& d, const Buffers64& b, int parity, float* Xf, float* Vf, float* Pf, hipStream_t s);
+// The forces-and-energies hook of a precision-64 context (c3d_eval_f64).  launch_eval_forces64: k64_eval_forces[_chunked] in
+// launch_step64's form (form64 over the same doubles, so a stage's weights select the instantiation family of the stage's step), the total
+// weighted force of X[parity] into Fout [nrep][3][np]: a buffer of the context's own (Buffers64::F), never the velocity slot; step_host as
+// launch_step64's (kind, dt and t_bath unused).  launch_energy64: k64_energy, Eout [nrep][4] = unweighted noe, bond + angle, repel, 0.
+hipError_t launch_eval_forces64(const DevModel& d, const double* model_host, const double* step_host, const Buffers64& b, int parity,
+                                int column_chunk, double* Fout, hipStream_t s);
+hipError_t launch_energy64(const DevModel& d, const double* model_host, double rep_r2, const Buffers64& b, int parity, double* Eout, hipStream_t s);
 size_t fire_state64_bytes();
 // K1: IF (n*n fp64, device) -> dist10 (n*n int32, device) and encoded targets (n*npad, device)
 hipError_t launch_if_to_target(const double* IF, int n, int npad, double alpha, double K, int min_sep, int rep_sep,

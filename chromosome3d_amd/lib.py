@@ -62,6 +62,9 @@ SIGNATURES = {
     "c3d_set_coords": (_i, [_vp, _fp]),
     "c3d_get_coords": (_i, [_vp, _fp]),
     "c3d_get_velocities": (_i, [_vp, _fp]),
+    "c3d_get_coords_f64": (_i, [_vp, _dp]),
+    "c3d_get_velocities_f64": (_i, [_vp, _dp]),
+    "c3d_set_coords_f64": (_i, [_vp, _dp]),
     "c3d_run": (_i, [_vp]),
     "c3d_run_steps": (_i, [_vp, _l, C.POINTER(_l)]),
     "c3d_schedule_length": (_l, [_vp]),
@@ -74,6 +77,7 @@ SIGNATURES = {
     "c3d_dg_smoothed_bounds": (_i, [_vp, _fp, _fp]),
     "c3d_debug_if_ranks": (_i, [_vp, _dp, _i, _dp, _dp, C.POINTER(C.c_size_t)]),
     "c3d_eval": (_i, [_vp, _f, _f, _f, _fp, _dp]),
+    "c3d_eval_f64": (_i, [_vp, _d, _d, _d, _dp, _dp]),
     "c3d_get_energies": (_i, [_vp, _dp]),
     "c3d_score_replicas": (_i, [_vp, _dp, _i, _i32p, _dp, _dp]),
     "c3d_compare_replicas": (_i, [_vp, _dp, _i, _dp, _dp]),

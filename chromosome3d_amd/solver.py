@@ -147,6 +147,22 @@ class Solver:
         _l.check(self._L.c3d_get_velocities(self._h, _l.fptr(v)))
         return v
 
+    # the same three in doubles (precision 64): the fp64 state itself, not its float mirror
+    def set_coords64(self, xyz):
+        xyz = np.ascontiguousarray(xyz, dtype=np.float64)
+        assert xyz.shape == (self.nrep, self.n, 3)
+        _l.check(self._L.c3d_set_coords_f64(self._h, _l.dptr(xyz)))
+
+    def coords64(self):
+        x = np.empty((self.nrep, self.n, 3), dtype=np.float64)
+        _l.check(self._L.c3d_get_coords_f64(self._h, _l.dptr(x)))
+        return x
+
+    def velocities64(self):
+        v = np.empty((self.nrep, self.n, 3), dtype=np.float64)
+        _l.check(self._L.c3d_get_velocities_f64(self._h, _l.dptr(v)))
+        return v
+
     # ---- solve ----
     def run(self):
         _l.check(self._L.c3d_run(self._h))
@@ -192,6 +208,15 @@ class Solver:
         e = np.empty((self.nrep, 3), dtype=np.float64) if energies else None
         _l.check(self._L.c3d_eval(self._h, w_all, w_vdw, repel_s, _l.fptr(F) if forces else None,
                                   _l.dptr(e) if energies else None))
+        return F, e
+
+    def eval64(self, w_all=1.0, w_vdw=1.0, repel_s=0.85, forces=True, energies=True):
+        """(F, e) in doubles from the fp64 kernels at the fp64 coordinates (c3d_eval_f64, precision 64): F has the bits of the force a
+        stage with these weights integrates; changes no state of the solve."""
+        F = np.empty((self.nrep, self.n, 3), dtype=np.float64) if forces else None
+        e = np.empty((self.nrep, 3), dtype=np.float64) if energies else None
+        _l.check(self._L.c3d_eval_f64(self._h, w_all, w_vdw, repel_s, _l.dptr(F) if forces else None,
+                                      _l.dptr(e) if energies else None))
         return F, e
 
     def energies(self):

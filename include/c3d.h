@@ -150,7 +150,12 @@ int c3d_set_schedule(c3d_ctx* ctx, const c3d_stage* stages, int n_stages, const 
  *   cluster_num_xcc, cluster_inject_incomplete, resident_inject_timeout   test hooks of the cluster kernel's safety net
  *                   (a device that does not expose 8 XCDs gets no cluster plan; a launch that ends without its completion
  *                   mark or with a time-out is re-run on the per-step path)
- *   precision       32 (default) or 64: the fp64 reference kernels (c3d_f64.hip); call before c3d_init_replicas.  The fp64 step takes
+ *   precision       32 (default) or 64: the fp64 reference kernels (c3d_f64.hip); call before c3d_init_replicas.  A precision-64 context
+ *                   keeps its state in doubles and has a boundary in doubles: c3d_get_coords_f64, c3d_get_velocities_f64 and
+ *                   c3d_set_coords_f64 move that state bit for bit, c3d_eval_f64 evaluates forces and energies with the fp64 kernels at
+ *                   the fp64 coordinates.  The float entries keep working on such a context through a float mirror of the state that every
+ *                   range of steps (and c3d_set_coords_f64) refreshes: c3d_get_coords, c3d_get_velocities, c3d_eval, c3d_get_energies,
+ *                   scoring and c3d_compare_replicas read the state ROUNDED to float, and c3d_set_coords sets it from floats.  The fp64 step takes
  *                   2560 beads by default and up to 16384 behind f64_max_beads (below; c3d_init_replicas returns C3D_ERR_INVALID beyond
  *                   the limit in force).  The fp32 path takes up to 5120 beads by default and up to 16384 behind max_beads (below);
  *                   c3d_set_if_matrix / c3d_set_restraints refuse more.  A precision-64 context takes its targets from the integer tenths
@@ -279,6 +284,17 @@ int c3d_get_coords(c3d_ctx* ctx, float* xyz);
  *  after MD and FIRE steps it is the velocity in A/ps; the same holds inside the L-BFGS part of a stage of kind 8: the slot holds the force of
  *  the last evaluation) */
 int c3d_get_velocities(c3d_ctx* ctx, float* v);
+/* The same three in doubles, for a precision-64 context with replicas (any other context: C3D_ERR_INVALID, the message names what is
+ * missing); layouts as above, n_replicas*n*3, xyz interleaved.
+ * c3d_get_coords_f64: the fp64 coordinates of the current step parity, bit for bit.  c3d_get_velocities_f64: the fp64 velocity slot (the
+ * remark at c3d_get_velocities applies: inside the two-point and L-BFGS parts it holds the last evaluation's force).
+ * c3d_set_coords_f64: the fp64 state becomes exactly these doubles; everything else is what c3d_set_coords leaves on such a context —
+ * velocities zero in both parities, sums, minimiser state and the position in the schedule untouched — and the float mirror is refreshed
+ * (coordinates rounded to float, velocities zero), so c3d_get_coords, energies and scoring see the new structure.  A non-finite value
+ * anywhere in xyz: C3D_ERR_INVALID before anything is copied. */
+int c3d_get_coords_f64(c3d_ctx* ctx, double* xyz);
+int c3d_get_velocities_f64(c3d_ctx* ctx, double* v);
+int c3d_set_coords_f64(c3d_ctx* ctx, const double* xyz);
 
 /* --- solve -------------------------------------------------------------------------- */
 /* whole schedule, with the gtol exit of the final minimisation; centres the models. */
@@ -305,7 +321,8 @@ int c3d_last_timing(const c3d_ctx* ctx, double* ms_total, long* steps, long* lau
  * "lbfgs_resets" (memory drops of the last kind-8 stage since its first step, summed over the replicas: read from the device),
  * "embed_form" (the eigen stage the last c3d_embed_replicas ran: 0 k_dg_eig, 1 tiled), "embed_batches" (replica batches of that call),
  * "device_rank_runs" (calls of c3d_score_replicas that ranked the IF matrix on the device), "score_wide_runs" (calls of it that were
- * re-run with a histogram sized to the models), "compare_runs" (completed calls of c3d_compare_replicas). */
+ * re-run with a histogram sized to the models), "compare_runs" (completed calls of c3d_compare_replicas),
+ * "f64_evals" (completed calls of c3d_eval_f64). */
 int c3d_get_stat(const c3d_ctx* ctx, const char* key, double* value);
 /* Test hook, no reference counterpart: the multi-step kernel's hand-off trusts a 16-byte unit once its tag word matches — i.e. that a
  * 16-byte aligned store is never observed half-written by a 16-byte load on gfx950.  This runs that exact store / load pair (one producer
@@ -331,6 +348,15 @@ const char* c3d_step_kernel_name(const c3d_ctx* ctx);
  * F (n_replicas*n*3) = total weighted force; e (n_replicas*3) = unweighted (noe, bond+angle,
  * repel) energies in fp64. Either may be NULL. */
 int c3d_eval(c3d_ctx* ctx, float w_all, float w_vdw, float repel_s, float* F, double* e);
+/* One evaluation by the fp64 kernels at the fp64 coordinates of a precision-64 context with replicas (any other context:
+ * C3D_ERR_INVALID).  F (n_replicas*n*3) = the total weighted force, from k64_eval_forces / k64_eval_forces_chunked: the fp64 step's own
+ * pair loop, sums and chain terms in the form (potential, tail, fold, column chunk) a stage with these weights steps in, so F has the bits
+ * of the force that step integrates.  e (3*n_replicas) = the unweighted noe, bond+angle and repel energies with c3d_eval's meaning, from the
+ * fp64 coordinates and the fp64 targets (k64_energy; one workgroup a replica, sums in a fixed order: two calls return the same bits).
+ * Either may be NULL, not both.  Changes no state of the solve: coordinates, velocity slot, sums, minimiser state, step parity, the L-BFGS
+ * history and c3d_step_kernel_name stay as they are.  The force buffer (n_replicas x 3 x np doubles, np = n rounded up to 128) is
+ * allocated by the first call and freed with the replicas.  The stat "f64_evals" counts completed calls. */
+int c3d_eval_f64(c3d_ctx* ctx, double w_all, double w_vdw, double repel_s, double* F, double* e);
 /* per replica: e[3*r + {0,1,2}] = E_noe, E_bond(+angle), E_repel at the final weights */
 int c3d_get_energies(c3d_ctx* ctx, double* e);
 /* K6 on the device, for every replica at its current coordinates: the restraint-satisfaction count and

@@ -168,6 +168,8 @@ hipError_t launch_tenths64(int, int, const int32_t*, const int32_t*, const int32
 hipError_t launch_targets64(const DevModel&, const double*, int, const int32_t*, double*, hipStream_t) { LaunchScope ls; return hipSuccess; }
 hipError_t launch_import64(const DevModel&, const float*, const Buffers64&, hipStream_t) { LaunchScope ls; return hipSuccess; }
 hipError_t launch_export64(const DevModel&, const Buffers64&, int, float*, float*, float*, hipStream_t) { LaunchScope ls; return hipSuccess; }
+hipError_t launch_eval_forces64(const DevModel&, const double*, const double*, const Buffers64&, int, int, double*, hipStream_t) { LaunchScope ls; return hipSuccess; }
+hipError_t launch_energy64(const DevModel&, const double*, double, const Buffers64&, int, double*, hipStream_t) { LaunchScope ls; return hipSuccess; }
 size_t fire_state64_bytes() { return 32; }
 // K1 restated on the host (chromosome3D.pl:110-162 as c3d_api.cpp's own near-tie redo does it): the executor needs real restraints
 hipError_t launch_if_to_target(const double* IF, int n, int npad, double alpha, double K, int min_sep, int, double*, double*, int,
