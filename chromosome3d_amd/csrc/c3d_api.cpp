@@ -220,6 +220,7 @@ struct c3d_ctx {
     long device_rank_runs = 0, score_wide_runs = 0;   // stats: calls that ranked on the device / that took the sized-histogram re-run
     long compare_runs = 0;                 // stat: completed calls of c3d_compare_replicas
     long f64_evals = 0;                    // stat: completed calls of c3d_eval_f64
+    long superpose_runs = 0, rmsd_table_runs = 0;   // stats: completed calls of c3d_superpose_replicas / c3d_rmsd_table
     long k1_recomputed = 0, k1_patched = 0;   // K1: near-tie elements redone on the host in the reference's order / changed by it
     long graph_captures = 0, graph_launches = 0, step_launches = 0, resident_launches = 0, cluster_launches = 0;
     bool has_two_point = false;            // the program holds two-point minimiser steps (run_ops splits ranges at their borders)
@@ -1987,6 +1988,8 @@ extern "C" int c3d_get_stat(const c3d_ctx* c, const char* key, double* value) {
     else if (!strcmp(key, "score_wide_runs")) *value = (double)c->score_wide_runs;
     else if (!strcmp(key, "compare_runs")) *value = (double)c->compare_runs;
     else if (!strcmp(key, "f64_evals")) *value = (double)c->f64_evals;
+    else if (!strcmp(key, "superpose_runs")) *value = (double)c->superpose_runs;
+    else if (!strcmp(key, "rmsd_table_runs")) *value = (double)c->rmsd_table_runs;
     else if (!strcmp(key, "cluster_xcd_count")) *value = (double)c->xcd_count;
     else if (!strcmp(key, "cluster_xcd_base")) *value = (double)c->xcd_base;
     else if (!strcmp(key, "cluster_ok")) *value = c->cl_ok ? 1.0 : 0.0;
@@ -2393,6 +2396,156 @@ extern "C" int c3d_debug_distance_ranks(c3d_ctx* c, int replica, double* rank) {
     if (int rc = read_back(c, tmp.p + L.ke, sizeof(unsigned) * m)) return rc;
     const unsigned* const ke = static_cast<const unsigned*>(c->h_stage);
     for (size_t q = 0; q < m; ++q) rank[q] = 0.5 * (double)ke[q] + 1.0;
+    return C3D_OK;
+}
+
+// ---- the models of a run in one frame (c3d_score.hip k_sup_*) ----
+// the K models of a call as n x 3 doubles each on the device: the replicas' state (the fp64 state itself on a precision-64 context, else the
+// floats widened), then n_extra models of the caller
+static int superpose_models(c3d_ctx* c, double* d_xyz, const double* extra_xyz, int n_extra) {
+    const int n = c->n, nrep = c->nrep;
+    const hipError_t e = c->precision == 64 ? c3d::launch_superpose_gather64(c->b64.X[c->parity], n, c3d::cols64(n), nrep, d_xyz, c->stream)
+                                            : c3d::launch_compare_coords(c->buf.X[c->parity], n, c->npad, nrep, d_xyz, c->stream);
+    if (e != hipSuccess) return fail(C3D_ERR_HIP, std::string("superpose launch: ") + hipGetErrorString(e));
+    if (n_extra > 0)
+        HIP_TRY(hipMemcpyAsync(d_xyz + (size_t)3 * n * nrep, extra_xyz, sizeof(double) * 3 * (size_t)n * n_extra, hipMemcpyHostToDevice, c->stream));
+    return C3D_OK;
+}
+// byte offsets into the one allocation of a call: models (the target of a superposition is model K), centroids, per-chunk sums, the pairs'
+// sums, fits and residuals, two sets of mirror bits, then (superposition only) the fitted models and the block read back in one copy
+struct SuperposeScratch {
+    size_t xyz = 0, cent = 0, partial = 0, cov = 0, fit = 0, res = 0, mir = 0, mir2 = 0, fitted = 0, out = 0, total = 0;
+};
+static SuperposeScratch superpose_layout(int n, int models, int KB, size_t pairs, bool fitted, size_t out_bytes) {
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    SuperposeScratch L;
+    L.cent = up(sizeof(double) * 3 * (size_t)n * models);
+    L.partial = L.cent + up(sizeof(double) * 3 * (size_t)models);
+    L.cov = L.partial + up(sizeof(double) * c3d::superpose_partial_doubles(n, KB));
+    L.fit = L.cov + up(sizeof(double) * c3d::kSupCov * pairs);
+    L.res = L.fit + up(sizeof(double) * c3d::kSupFit * pairs);
+    L.mir = L.res + up(sizeof(double) * pairs);
+    L.mir2 = L.mir + up(sizeof(int) * pairs);
+    L.fitted = L.mir2 + up(sizeof(int) * pairs);
+    L.out = L.fitted + (fitted ? up(sizeof(double) * 3 * (size_t)n * models) : 0);
+    L.total = L.out + up(out_bytes);
+    return L;
+}
+
+extern "C" int c3d_superpose_replicas(c3d_ctx* c, int reference, const double* ref_xyz, int flags, int iters, double* rmsd, int32_t* mirrored,
+                                      double* mean_xyz, double* rmsf) {
+    if (!c) return fail(C3D_ERR_INVALID, "c3d_superpose_replicas: null context");
+    if (!c->have_replicas) return fail(C3D_ERR_INVALID, "c3d_superpose_replicas: call c3d_init_replicas first");
+    if (c->n < 3) return fail(C3D_ERR_INVALID, "c3d_superpose_replicas: models of fewer than 3 beads have no orientation to fit");
+    if (reference < -1 || reference >= c->nrep) return fail(C3D_ERR_INVALID, "c3d_superpose_replicas: reference is neither a replica index nor -1");
+    if (reference == -1 && !ref_xyz) return fail(C3D_ERR_INVALID, "c3d_superpose_replicas: reference -1 without ref_xyz");
+    if (flags & ~(C3D_SUPERPOSE_MIRROR | C3D_SUPERPOSE_APPLY)) return fail(C3D_ERR_INVALID, "c3d_superpose_replicas: unknown flag bits");
+    if (iters < 0 || iters > C3D_SUPERPOSE_MAX_ITERS) return fail(C3D_ERR_INVALID, "c3d_superpose_replicas: iters outside 0..C3D_SUPERPOSE_MAX_ITERS");
+    const bool apply = (flags & C3D_SUPERPOSE_APPLY) != 0;
+    if (!apply && !rmsd && !mirrored && !mean_xyz && !rmsf)
+        return fail(C3D_ERR_INVALID, "c3d_superpose_replicas: every output is NULL and C3D_SUPERPOSE_APPLY is not set");
+    const int n = c->n, K = c->nrep;
+    if (reference == -1)
+        if (int rc = c3d::check_model_coords(ref_xyz, (size_t)3 * n, "c3d_superpose_replicas")) return rc;
+    C3D_ENTRY(c, unit_bit(UNIT_SCORE));
+    // read back in one copy: sum of squares per model (K), mean (3 n), rmsf (n), mirror bits (K ints)
+    const size_t out_doubles = (size_t)K + 4 * (size_t)n, out_bytes = sizeof(double) * out_doubles + sizeof(int) * (size_t)K;
+    const SuperposeScratch L = superpose_layout(n, K + 1, 1, (size_t)K, true, out_bytes);
+    DevTmp<char> tmp;
+    if (int rc = compare_alloc(tmp, L.total, "c3d_superpose_replicas")) return rc;
+    auto dbl = [&](size_t off) { return reinterpret_cast<double*>(tmp.p + off); };
+    double* const d_xyz = dbl(L.xyz);
+    double* const d_target = d_xyz + (size_t)3 * n * K;
+    double* const d_cent = dbl(L.cent);
+    double* const d_fitted = dbl(L.fitted);
+    double* const d_out = dbl(L.out);
+    double* const d_mean = d_out + K;
+    double* const d_rmsf = d_mean + 3 * (size_t)n;
+    int* const d_mir = reinterpret_cast<int*>(d_out + out_doubles);      // the first pass's bits: what the caller gets
+    int* const d_mir2 = reinterpret_cast<int*>(tmp.p + L.mir2);
+    if (int rc = superpose_models(c, d_xyz, ref_xyz, reference == -1 ? 1 : 0)) return rc;
+    if (reference >= 0)
+        HIP_TRY(hipMemcpyAsync(d_target, d_xyz + (size_t)3 * n * reference, sizeof(double) * 3 * (size_t)n, hipMemcpyDeviceToDevice, c->stream));
+    hipError_t e = c3d::launch_superpose_centre(d_xyz, n, K + 1, d_cent, c->stream);
+    if (e == hipSuccess)
+        e = c3d::launch_superpose_fit(d_xyz, K, d_target, 1, n, reference >= 0 ? reference : c3d::kSupNoIdent, (flags & C3D_SUPERPOSE_MIRROR) != 0, nullptr,
+                                      dbl(L.partial), dbl(L.cov), dbl(L.fit), d_mir, d_out, c->stream);
+    if (e == hipSuccess) e = c3d::launch_superpose_apply(d_xyz, K, n, dbl(L.fit), iters == 0 ? d_cent + 3 * (size_t)K : nullptr, d_fitted, c->stream);
+    for (int it = 0; it < iters && e == hipSuccess; ++it) {
+        // the mean of the fitted models is the next target; every model gets a rotation onto it, its handedness as the first pass left it
+        e = c3d::launch_superpose_mean(d_fitted, K, n, d_mean, d_rmsf, nullptr, c->stream);
+        if (e != hipSuccess) break;
+        HIP_TRY(hipMemcpyAsync(d_target, d_mean, sizeof(double) * 3 * (size_t)n, hipMemcpyDeviceToDevice, c->stream));
+        e = c3d::launch_superpose_centre(d_target, n, 1, d_cent + 3 * (size_t)K, c->stream);
+        if (e == hipSuccess)
+            e = c3d::launch_superpose_fit(d_xyz, K, d_target, 1, n, c3d::kSupNoIdent, false, d_mir, dbl(L.partial), dbl(L.cov), dbl(L.fit), d_mir2,
+                                          nullptr, c->stream);
+        if (e == hipSuccess) e = c3d::launch_superpose_apply(d_xyz, K, n, dbl(L.fit), nullptr, d_fitted, c->stream);
+    }
+    // iters = 0: d_out[k] keeps the fit's residual against the target; else it becomes the squared distance from the final mean
+    if (e == hipSuccess) e = c3d::launch_superpose_mean(d_fitted, K, n, d_mean, d_rmsf, iters > 0 ? d_out : nullptr, c->stream);
+    if (e != hipSuccess) return fail(C3D_ERR_HIP, std::string("superpose launch: ") + hipGetErrorString(e));
+    if (int rc = read_back(c, d_out, out_bytes)) return rc;
+    if (apply) {
+        if (c->precision == 64) {
+            const size_t n3 = (size_t)K * 3 * c3d::cols64(n);
+            e = c3d::launch_superpose_store64(d_fitted, n, c3d::cols64(n), K, c->b64.X[0], c->b64.X[1], c->stream);
+            if (e != hipSuccess) return fail(C3D_ERR_HIP, std::string("superpose launch: ") + hipGetErrorString(e));
+            for (int k = 0; k < 2; ++k) HIP_TRY(hipMemsetAsync(c->b64.V[k], 0, sizeof(double) * n3, c->stream));
+            e = c3d::launch_export64(dev_model(c), c->b64, c->parity, c->buf.X[c->parity], c->buf.V[c->parity], c->buf.P[c->parity], c->stream);
+            if (e != hipSuccess) return fail(C3D_ERR_HIP, std::string("fp64 export: ") + hipGetErrorString(e));
+        } else {
+            e = c3d::launch_superpose_store32(d_fitted, n, c->npad, K, c->buf.X[c->parity], c->stream);
+            if (e != hipSuccess) return fail(C3D_ERR_HIP, std::string("superpose launch: ") + hipGetErrorString(e));
+            for (int k = 0; k < 2; ++k) HIP_TRY(hipMemsetAsync(c->buf.V[k], 0, sizeof(float) * c->rep_floats * K, c->stream));
+        }
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    const double* const h = static_cast<const double*>(c->h_stage);
+    const int* const hm = reinterpret_cast<const int*>(h + out_doubles);
+    for (int k = 0; k < K; ++k) {
+        if (rmsd) rmsd[k] = sqrt(h[k] / (double)n);
+        if (mirrored) mirrored[k] = hm[k];
+    }
+    if (mean_xyz) memcpy(mean_xyz, h + K, sizeof(double) * 3 * (size_t)n);
+    if (rmsf) memcpy(rmsf, h + K + 3 * (size_t)n, sizeof(double) * (size_t)n);
+    ++c->superpose_runs;
+    return C3D_OK;
+}
+
+extern "C" int c3d_rmsd_table(c3d_ctx* c, const double* extra_xyz, int n_extra, int flags, double* rmsd, int32_t* mirrored) {
+    if (!c) return fail(C3D_ERR_INVALID, "c3d_rmsd_table: null context");
+    if (!c->have_replicas) return fail(C3D_ERR_INVALID, "c3d_rmsd_table: call c3d_init_replicas first");
+    if (c->n < 3) return fail(C3D_ERR_INVALID, "c3d_rmsd_table: models of fewer than 3 beads have no orientation to fit");
+    if (n_extra < 0 || (n_extra > 0 && !extra_xyz)) return fail(C3D_ERR_INVALID, "c3d_rmsd_table: n_extra < 0, or extra models without coordinates");
+    if ((long)c->nrep + n_extra > C3D_COMPARE_MAX_MODELS) return fail(C3D_ERR_INVALID, "c3d_rmsd_table: more than C3D_COMPARE_MAX_MODELS models");
+    if (flags & ~C3D_SUPERPOSE_MIRROR) return fail(C3D_ERR_INVALID, "c3d_rmsd_table: unknown flag bits (the table moves nothing: C3D_SUPERPOSE_MIRROR alone)");
+    if (!rmsd && !mirrored) return fail(C3D_ERR_INVALID, "c3d_rmsd_table: both outputs are NULL");
+    const int n = c->n, K = c->nrep + n_extra;
+    if (n_extra > 0)
+        if (int rc = c3d::check_model_coords(extra_xyz, (size_t)3 * n * n_extra, "c3d_rmsd_table")) return rc;
+    C3D_ENTRY(c, unit_bit(UNIT_SCORE));
+    const size_t pairs = (size_t)K * K;
+    const SuperposeScratch L = superpose_layout(n, K, K, pairs, false, 0);
+    DevTmp<char> tmp;
+    if (int rc = compare_alloc(tmp, L.total, "c3d_rmsd_table")) return rc;
+    auto dbl = [&](size_t off) { return reinterpret_cast<double*>(tmp.p + off); };
+    double* const d_xyz = dbl(L.xyz);
+    if (int rc = superpose_models(c, d_xyz, extra_xyz, n_extra)) return rc;
+    hipError_t e = c3d::launch_superpose_centre(d_xyz, n, K, dbl(L.cent), c->stream);
+    if (e == hipSuccess)
+        e = c3d::launch_superpose_fit(d_xyz, K, d_xyz, K, n, 0, (flags & C3D_SUPERPOSE_MIRROR) != 0, nullptr, dbl(L.partial), dbl(L.cov), dbl(L.fit),
+                                      reinterpret_cast<int*>(tmp.p + L.mir), dbl(L.res), c->stream);
+    if (e != hipSuccess) return fail(C3D_ERR_HIP, std::string("superpose launch: ") + hipGetErrorString(e));
+    // res and the mirror bits are neighbours in the allocation: one copy
+    if (int rc = read_back(c, tmp.p + L.res, (L.mir - L.res) + sizeof(int) * pairs)) return rc;
+    const double* const h = static_cast<const double*>(c->h_stage);
+    const int* const hm = reinterpret_cast<const int*>(static_cast<const char*>(c->h_stage) + (L.mir - L.res));
+    for (size_t q = 0; q < pairs; ++q) {
+        if (rmsd) rmsd[q] = sqrt(h[q] / (double)n);
+        if (mirrored) mirrored[q] = hm[q];
+    }
+    ++c->rmsd_table_runs;
     return C3D_OK;
 }
 

@@ -5,6 +5,8 @@
 #include <stdint.h>
 #include <type_traits>
 
+#include "c3d_superpose.h"
+
 namespace c3d {
 
 constexpr float kBoltz = 0.0019872f;  // kcal/mol/K (X-PLOR/CNS AKMA)
@@ -379,6 +381,30 @@ hipError_t launch_compare_ranks(const double* x, int n, unsigned long long* keys
                                 hipStream_t s);
 hipError_t launch_compare_table(const double* xyz, const unsigned* ke, const double* rowsum, int n, int K, size_t m, double* sums,
                                 double* partial, double* table, hipStream_t s);
+// The models of a run in one frame (c3d_superpose_replicas, c3d_rmsd_table; k_sup_*).  A model is n x 3 doubles, xyz interleaved.
+// launch_superpose_gather64: the fp64 state X [nrep][3][np] as such models, every value as it is (fp32 state: launch_compare_coords).
+// launch_superpose_centre: cent[k] = the centroid of model k, the model centred on it in place (K models).
+// launch_superpose_fit: every model of A (KA) onto every model of B (KB), both centred: cov[a][b][kSupCov] (c3d_superpose.h), then
+// fit[a][b][kSupFit] = Q, mirror bit, eigenvalue and mirrored[a][b]; res[a][b] = sum |Q a_i - b_i|^2 unless res is null.  ident: the pair
+// a == b + ident gets the identity (kSupNoIdent: no pair).  mirror: the reflected candidate takes part; fixed (KA ints, or null): model a's
+// handedness is given and only rotations are fitted.  partial holds superpose_partial_doubles(n, KB) doubles: per-chunk sums of one row
+// block of sixteen models a, added in chunk order; a chunk is 64 beads at every n and K.
+// launch_superpose_apply: fitted[k] = Q_k a_k + shift (3 doubles on the device, or null), fit holding one entry a model (KB = 1).
+// launch_superpose_mean: mean (n x 3), rmsf (n) over the K fitted models, k in order; dev[k] = sum_i |x_k,i - mean_i|^2 unless null.
+// launch_superpose_store32 / 64: the fitted models into beads 0..n-1 of X [nrep][3][npad] floats / of X0 and X1 [nrep][3][np] doubles.
+constexpr int kSupNoIdent = -(1 << 30);
+inline int superpose_chunks(int n) { return (n + 63) / 64; }
+inline size_t superpose_partial_doubles(int n, int KB) {
+    return (size_t)superpose_chunks(n) * (size_t)((KB + kCmpModels - 1) / kCmpModels) * 256 * kSupCov;
+}
+hipError_t launch_superpose_gather64(const double* X, int n, int np, int nrep, double* xyz, hipStream_t s);
+hipError_t launch_superpose_centre(double* xyz, int n, int K, double* cent, hipStream_t s);
+hipError_t launch_superpose_fit(const double* A, int KA, const double* B, int KB, int n, int ident, bool mirror, const int* fixed, double* partial,
+                                double* cov, double* fit, int* mirrored, double* res, hipStream_t s);
+hipError_t launch_superpose_apply(const double* A, int K, int n, const double* fit, const double* shift, double* fitted, hipStream_t s);
+hipError_t launch_superpose_mean(const double* fitted, int K, int n, double* mean, double* rmsf, double* dev, hipStream_t s);
+hipError_t launch_superpose_store32(const double* fitted, int n, int npad, int nrep, float* X, hipStream_t s);
+hipError_t launch_superpose_store64(const double* fitted, int n, int np, int nrep, double* X0, double* X1, hipStream_t s);
 
 // Target matrix entry: NOE target in Angstrom, 0 = no restraint (host c3d_set_restraints and K1).
 inline float encode_target_host(float t) { return t > 0 ? t : 0.0f; }

@@ -6,6 +6,7 @@
 //   c3d_solve --tbl contact.tbl --n N --out <dir> --id ID [-m 20] ...
 //       exactly the cns_solve role: restraints in, <ID>_<k>.pdb out
 //   --similarity <path> adds the replicas' similarity table (Spearman and scaled RMSD of the pair distances, on the device)
+//   --superpose writes the models in one frame and one hand, the best-ranked model's; --rmsf <path> adds the mean model and per-bead spread
 //
 // Success convention of the reference: <ID>_<M>.pdb exists, iam.running removed; on failure
 // iam.running is renamed iam.failed and the exit code is non-zero (:266-283).
@@ -31,6 +32,10 @@ static void usage() {
             "                 [--seq <one-letter residue codes | @fasta file>   residue names of the models (default: all MET)]\n"
             "                 [--similarity <path>   after the solve, the replicas against one another: one row `a b spearman rmsd` per ordered pair of\n"
             "                                        replica ids (Spearman and scaled RMSD of the pair distances, computed on the device)]\n"
+            "                 [--superpose   write the models superposed on the best-ranked one, mirror images reflected onto its hand: the files overlay;\n"
+            "                                only the coordinates move (rotation, reflection, translation), every REMARK row stays]\n"
+            "                 [--rmsf <path>   mean model and per-bead spread of the superposed ensemble: one row `bead mean_x mean_y mean_z rmsf`\n"
+            "                                  (generalized Procrustes from the best-ranked model, 3 iterations, on the device)]\n"
             "                 [--accepted   also write <ID>a_<k>.pdb beside every <ID>_<k>.pdb, as CNS does for structures it accepts]\n");
 }
 
@@ -60,7 +65,8 @@ int main(int argc, char** argv) {
     // (rc -13, "GPU coredump: execvp failed") before the runtime has said WHICH exception — round 5 lost the only evidence of one that way.
     setenv("HSA_DISABLE_COREDUMP_ON_EXCEPTION", "1", 0);          // (0: a user's own setting wins)
     const double t_start = now_s();
-    std::string if_path, tbl_path, out_dir, id, seq_arg, similarity_path;
+    std::string if_path, tbl_path, out_dir, id, seq_arg, similarity_path, rmsf_path;
+    int superpose = 0;
     double K = 11, alpha = 0.5, gtol = 1e-2;
     int final_min = 1;
     int lbfgs = 0;
@@ -96,6 +102,8 @@ int main(int argc, char** argv) {
         else if (s == "--accepted") accepted = 1;   // the deck's printaccept writes <ID>a_<k>.pdb for structures CNS accepts, beside the trial file (:1818-1828)
         else if (s == "--seq") seq_arg = next("--seq");
         else if (s == "--similarity") similarity_path = next("--similarity");   // the ensemble table (c3d_compare_replicas)
+        else if (s == "--superpose") superpose = 1;   // the models in the best-ranked model's frame and hand before they are written (c3d_superpose_replicas)
+        else if (s == "--rmsf") rmsf_path = next("--rmsf");   // mean model and per-bead spread of the superposed ensemble
         else if (s == "-h" || s == "--help") { usage(); return 0; }
         else { fprintf(stderr, "c3d_solve: unknown option %s\n", s.c_str()); usage(); return 2; }
     }
@@ -175,8 +183,28 @@ int main(int argc, char** argv) {
 
     std::vector<float> xyz((size_t)models * n * 3);
     std::vector<double> en((size_t)models * 3);
-    CHECK(c3d_get_coords(ctx, xyz.data()));
     CHECK(c3d_get_energies(ctx, en.data()));
+    if (superpose || !rmsf_path.empty()) {
+        // the best-ranked model (lowest int(E_noe), the lower index on a tie: c3d_rank's rule) is the frame and the hand of all.  Energies,
+        // assessment and Spearman do not depend on either: they are not computed again.
+        int best = 0;
+        for (int r = 1; r < models; ++r) if ((long)en[3 * r] < (long)en[3 * best]) best = r;
+        if (!rmsf_path.empty()) {
+            std::vector<double> mean((size_t)n * 3), rmsf(n);
+            std::vector<int32_t> mir(models);
+            CHECK(c3d_superpose_replicas(ctx, best, nullptr, C3D_SUPERPOSE_MIRROR, 3, nullptr, mir.data(), mean.data(), rmsf.data()));
+            int nm = 0;
+            for (int r = 0; r < models; ++r) nm += mir[r];
+            FILE* f = fopen(rmsf_path.c_str(), "w");
+            if (!f) { fprintf(stderr, "c3d_solve: cannot write %s\n", rmsf_path.c_str()); return fail_exit(out_dir); }
+            fprintf(f, "# bead mean_x mean_y mean_z rmsf   (%d models superposed on %s_%u.pdb, 3 generalized-Procrustes iterations; %d mirrored)\n", models,
+                    id.c_str(), first_rep + (unsigned)best + 1u, nm);
+            for (int i = 0; i < n; ++i) fprintf(f, "%d %.3f %.3f %.3f %.3f\n", i + 1, mean[3 * (size_t)i], mean[3 * (size_t)i + 1], mean[3 * (size_t)i + 2], rmsf[i]);
+            fclose(f);
+        }
+        if (superpose) CHECK(c3d_superpose_replicas(ctx, best, nullptr, C3D_SUPERPOSE_MIRROR | C3D_SUPERPOSE_APPLY, 0, nullptr, nullptr, nullptr, nullptr));
+    }
+    CHECK(c3d_get_coords(ctx, xyz.data()));
     for (int r = 0; r < models; ++r) {
         char name[64];
         snprintf(name, sizeof name, "%s_%u.pdb", id.c_str(), first_rep + (unsigned)r + 1u);

@@ -82,6 +82,8 @@ SIGNATURES = {
     "c3d_score_replicas": (_i, [_vp, _dp, _i, _i32p, _dp, _dp]),
     "c3d_compare_replicas": (_i, [_vp, _dp, _i, _dp, _dp]),
     "c3d_debug_distance_ranks": (_i, [_vp, _i, _dp]),
+    "c3d_superpose_replicas": (_i, [_vp, _i, _dp, _i, _i, _dp, _i32p, _dp, _dp]),
+    "c3d_rmsd_table": (_i, [_vp, _dp, _i, _i, _dp, _i32p]),
     "c3d_rank": (_i, [_vp, _i32p]),
     "c3d_reduce_model": (_i, [_dp, _i, _dp]),
     "c3d_model_similarity": (_i, [_dp, _dp, _i, _dp, _dp]),
@@ -98,6 +100,8 @@ SIGNATURES = {
     "c3d_spearman_if_dist": (_i, [_dp, _fp, _i, _i, _dp]),
     "c3d_spearman_if_dist_batch": (_i, [_dp, _fp, _i, _i, _i, _dp]),
 }
+
+SUPERPOSE_MIRROR, SUPERPOSE_APPLY = 1, 2      # C3D_SUPERPOSE_MIRROR, C3D_SUPERPOSE_APPLY
 
 _lib = None
 

@@ -180,6 +180,19 @@ def compare_models(solver, extra=None):
     return solver.compare(extra)
 
 
+def superpose_models(solver, reference=0, ref_xyz=None, mirror=True, apply=False, iters=0):
+    """The solver's replicas in one frame and one hand, on the device: (rmsd [M], mirrored [M], mean [n, 3], rmsf [n]) of fitting every
+    replica onto replica `reference` (or the model ref_xyz), reflecting the mirror images; iters > 0 refines against the ensemble mean.
+    rmsf is the per-bead spread of the ensemble.  apply=True leaves the replicas superposed.  See Solver.superpose."""
+    return solver.superpose(reference, ref_xyz, mirror, apply, iters)
+
+
+def rmsd_table(solver, extra=None, mirror=True):
+    """Coordinate RMSD after superposition for every ordered pair of the solver's replicas (and the models of `extra`, [E, n, 3]), on the
+    device: (rmsd [K, K] in Angstrom, mirrored [K, K]).  See Solver.rmsd_table."""
+    return solver.rmsd_table(extra, mirror)
+
+
 def build_models(solver, model_count=MODELCOUNT, seed=MD_SEED, first_replica=0, model=None, stages=None, fire=None,
                  gtol=1e-2, check_every=250, final_kind=5):
     """The replacement of `cns_solve < dgsa.inp` (:254-289): runs the whole annealing schedule

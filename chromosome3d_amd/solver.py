@@ -262,6 +262,48 @@ class Solver:
         _l.check(self._L.c3d_debug_distance_ranks(self._h, int(replica), _l.dptr(rank)))
         return rank
 
+    def _extra_models(self, extra):
+        if extra is None:
+            return None
+        ex = np.ascontiguousarray(extra, dtype=np.float64)
+        if ex.ndim == 2:
+            ex = ex[None]
+        assert ex.ndim == 3 and ex.shape[1:] == (self.n, 3)
+        return ex
+
+    def superpose(self, reference=0, ref_xyz=None, mirror=True, apply=False, iters=0):
+        """(rmsd [nrep], mirrored [nrep], mean [n, 3], rmsf [n]): every replica fitted onto replica `reference` — or onto ref_xyz [n, 3]
+        when that is given (reference is then ignored) — by the least-squares rotation after centring, on the device
+        (c3d_superpose_replicas).  mirror: a replica that fits better reflected through the origin is reflected (mirrored[k] = 1).
+        iters > 0: generalized Procrustes, that many rounds of fitting every replica to the mean of the fitted ones; rmsd is then against
+        the final mean.  mean / rmsf: the mean of the fitted models and the per-bead spread about it.  apply: the fitted coordinates
+        become the replicas' (velocities zero); otherwise nothing of the solve changes.  precision 64: the fp64 state is what is fitted."""
+        ref = None
+        if ref_xyz is not None:
+            ref = np.ascontiguousarray(ref_xyz, dtype=np.float64)
+            assert ref.shape == (self.n, 3)
+            reference = -1
+        flags = (_l.SUPERPOSE_MIRROR if mirror else 0) | (_l.SUPERPOSE_APPLY if apply else 0)
+        rmsd = np.empty(self.nrep, dtype=np.float64)
+        mirrored = np.empty(self.nrep, dtype=np.int32)
+        mean = np.empty((self.n, 3), dtype=np.float64)
+        rmsf = np.empty(self.n, dtype=np.float64)
+        _l.check(self._L.c3d_superpose_replicas(self._h, int(reference), _l.dptr(ref) if ref is not None else None, flags, int(iters),
+                                                _l.dptr(rmsd), _l.i32ptr(mirrored), _l.dptr(mean), _l.dptr(rmsf)))
+        return rmsd, mirrored, mean, rmsf
+
+    def rmsd_table(self, extra=None, mirror=True):
+        """(rmsd, mirrored), K x K each: the superposition of model a onto model b for every ordered pair of the K = nrep + len(extra)
+        models of compare(), on the device (c3d_rmsd_table): coordinate RMSD in Angstrom after the best rotation — and reflection, where
+        that fits strictly better (mirrored[a][b] = 1).  The diagonal is exactly 0."""
+        ex = self._extra_models(extra)
+        K = self.nrep + (0 if ex is None else ex.shape[0])
+        rmsd = np.empty((K, K), dtype=np.float64)
+        mirrored = np.empty((K, K), dtype=np.int32)
+        _l.check(self._L.c3d_rmsd_table(self._h, _l.dptr(ex) if ex is not None else None, 0 if ex is None else ex.shape[0],
+                                        _l.SUPERPOSE_MIRROR if mirror else 0, _l.dptr(rmsd), _l.i32ptr(mirrored)))
+        return rmsd, mirrored
+
     def rank(self):
         r = np.empty(self.nrep, dtype=np.int32)
         _l.check(self._L.c3d_rank(self._h, _l.i32ptr(r)))

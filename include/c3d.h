@@ -322,7 +322,8 @@ int c3d_last_timing(const c3d_ctx* ctx, double* ms_total, long* steps, long* lau
  * "embed_form" (the eigen stage the last c3d_embed_replicas ran: 0 k_dg_eig, 1 tiled), "embed_batches" (replica batches of that call),
  * "device_rank_runs" (calls of c3d_score_replicas that ranked the IF matrix on the device), "score_wide_runs" (calls of it that were
  * re-run with a histogram sized to the models), "compare_runs" (completed calls of c3d_compare_replicas),
- * "f64_evals" (completed calls of c3d_eval_f64). */
+ * "f64_evals" (completed calls of c3d_eval_f64), "superpose_runs" / "rmsd_table_runs" (completed calls of c3d_superpose_replicas /
+ * c3d_rmsd_table). */
 int c3d_get_stat(const c3d_ctx* ctx, const char* key, double* value);
 /* Test hook, no reference counterpart: the multi-step kernel's hand-off trusts a 16-byte unit once its tag word matches — i.e. that a
  * 16-byte aligned store is never observed half-written by a 16-byte load on gfx950.  This runs that exact store / load pair (one producer
@@ -393,6 +394,43 @@ int c3d_score_replicas(c3d_ctx* ctx, const double* IF, int range, int32_t* satis
 int c3d_compare_replicas(c3d_ctx* ctx, const double* extra_xyz, int n_extra, double* spearman, double* rmsd);
 /* Test hook: rank (n(n-1)/2 doubles, pairs i<j in row order) = the average ranks of replica `replica`'s distances as the device computes them */
 int c3d_debug_distance_ranks(c3d_ctx* ctx, int replica, double* rank);
+/* The models of a run in one frame, on the device (c3d_score.hip k_sup_*): a run's replicas come out in arbitrary frames and, mirror images
+ * having equal energy under distance restraints, in both hands.  c3d_superpose_replicas fits every replica onto one target:
+ * replica `reference` (0..n_replicas-1) at its current coordinates, or, with reference = -1, ref_xyz (n x 3 doubles, xyz interleaved, e.g. a
+ * bundled model; checked as the extra models of c3d_compare_replicas are).  The models are the replicas' state: on a precision-64 context the
+ * fp64 state bit for bit, else the floats taken as doubles unchanged.
+ * The fit: model and target are centred on their centroids; the model gets the least-squares rotation R onto the target (Horn's quaternion
+ * matrix of the 3 x 3 covariance, its extreme eigenpairs by 10 cyclic Jacobi sweeps, a fixed count); with C3D_SUPERPOSE_MIRROR it is first
+ * reflected through the origin if the reflected fit is strictly better.  mirrored[k] = 1 for a reflected model (always 0 without the flag),
+ * rmsd[k] = sqrt(sum_i |R a_i - b_i|^2 / n) over the centred coordinates, summed directly (exactly 0 for the reference replica itself).
+ * iters = 0 stops there.  iters > 0 (at most C3D_SUPERPOSE_MAX_ITERS) then repeats `iters` times: the mean of the fitted models becomes the
+ * target and every model gets the rotation onto it (generalized Procrustes; rotations only, the handedness stays as the first pass settled
+ * it); rmsd[k] is then sqrt(sum_i |x_k,i - mean_i|^2 / n) against the final mean.
+ * mean_xyz (n x 3) = the mean of the fitted models, rmsf (n) = sqrt(mean_k |x_k,i - mean_i|^2), the per-bead spread.  The fitted models
+ * are in the target's frame: at the target's centroid with iters = 0, at the origin otherwise.  Any output pointer may be NULL.
+ * Without C3D_SUPERPOSE_APPLY no state of the solve changes (the guarantee of c3d_eval_f64 and c3d_compare_replicas).  With it the
+ * replicas' coordinates become the fitted ones, as c3d_set_coords / c3d_set_coords_f64 would leave them: the current parity's floats
+ * (each the fp64 result rounded once) or both fp64 buffers and the float mirror; velocities zero in both parities; pad beads, sums,
+ * minimiser state, the position in the schedule and c3d_step_kernel_name untouched.
+ * c3d_rmsd_table: rmsd[a][b], mirrored[a][b] (K x K row-major, K = n_replicas + n_extra models as in c3d_compare_replicas) = the fit of
+ * model a onto model b for every ordered pair; flags: C3D_SUPERPOSE_MIRROR or 0.  The diagonal is exactly 0 and not mirrored, the table is
+ * symmetric to rounding.  Either output may be NULL, not both.
+ * All sums have a fixed order that follows from n alone (chunks of 64 beads added in chunk order, no atomics): two calls return the same
+ * bits, and extra models leave the replicas' entries their bits.
+ * C3D_ERR_INVALID, before any launch: no replicas, n < 3, reference outside -1..n_replicas-1 or -1 without ref_xyz, n_extra < 0 or extra
+ * models without coordinates, K > C3D_COMPARE_MAX_MODELS, unknown flag bits (C3D_SUPERPOSE_APPLY is unknown to the table), iters < 0 or
+ * > C3D_SUPERPOSE_MAX_ITERS, every output NULL (without C3D_SUPERPOSE_APPLY), coordinates given by the caller that are not finite or have
+ * |x| >= 1e6.  C3D_ERR_NOMEM: no device memory for the scratch.
+ * Scratch, allocated for the call and freed before it returns: 24 n bytes per model (48 n for a superposition: centred and fitted), 200
+ * bytes per fitted pair (K pairs, K^2 for the table) and the per-chunk sums of one block of sixteen models, 22 528 ceil(n / 64) ceil(Kb / 16)
+ * bytes (Kb = 1, or K for the table): 16 MB + 12 MB at 16384 beads x 20 models, 200 MB + 13 MB + 92 MB at 16384 x 256.
+ * Stats "superpose_runs" and "rmsd_table_runs" count the calls that completed. */
+#define C3D_SUPERPOSE_MIRROR 1   /* a model that fits better reflected is reflected */
+#define C3D_SUPERPOSE_APPLY  2   /* the superposed coordinates become the replicas' state */
+#define C3D_SUPERPOSE_MAX_ITERS 50
+int c3d_superpose_replicas(c3d_ctx* ctx, int reference, const double* ref_xyz, int flags, int iters, double* rmsd, int32_t* mirrored,
+                           double* mean_xyz, double* rmsf);
+int c3d_rmsd_table(c3d_ctx* ctx, const double* extra_xyz, int n_extra, int flags, double* rmsd, int32_t* mirrored);
 /* rank[k] = replica index with the k-th lowest int(E_noe) (chromosome3D.pl:796-802,822-828);
  * ties broken by replica id. */
 int c3d_rank(c3d_ctx* ctx, int32_t* rank);

@@ -1,0 +1,92 @@
+"""fp64 restatement of the superposition of a run's models (c3d_superpose_replicas, c3d_rmsd_table; chromosome3d_amd/csrc/c3d_score.hip
+k_sup_*) in numpy, by another algorithm than the device's: Kabsch's rotation from the SVD of the centred covariance with the determinant
+correction, where the device takes the largest eigenvector of Horn's quaternion matrix by Jacobi sweeps.  The mirror decision compares
+the two candidate fits' residuals, where the device compares two eigenvalues.
+
+A model is [n, 3]; `fit(a, b)` moves a onto b.  Conventions of include/c3d.h: every model is centred on its centroid; the reflection is the
+one through the origin (a -> -a) and is taken only if its fit is strictly better; rmsd = sqrt(sum |Q a_i - b_i|^2 / n) over the centred
+coordinates; with iters = 0 the fitted models sit at the target's centroid, after generalized-Procrustes iterations at the origin."""
+import numpy as np
+
+
+def centred(x):
+    x = np.asarray(x, dtype=np.float64)
+    return x - x.mean(axis=0)
+
+
+def kabsch(a, b):
+    """The proper rotation R (3 x 3, det +1) minimising sum |R a_i - b_i|^2 over two CENTRED models, and that minimum."""
+    H = a.T @ b                                             # sum a_i b_i^T
+    U, _, Vt = np.linalg.svd(H)
+    d = np.sign(np.linalg.det(Vt.T @ U.T))
+    d = 1.0 if d == 0 else d
+    R = Vt.T @ np.diag([1.0, 1.0, d]) @ U.T
+    r = a @ R.T - b
+    return R, float((r * r).sum())
+
+
+def fit(a, b, mirror=True):
+    """(Q, mirrored, rmsd, both residual sums): Q a_centred ~ b_centred, Q orthogonal with det -1 when mirrored."""
+    a, b = centred(a), centred(b)
+    R, e = kabsch(a, b)
+    Rm, em = kabsch(-a, b)
+    mirrored = bool(mirror and em < e)
+    Q = -Rm if mirrored else R
+    r = a @ Q.T - b
+    return Q, int(mirrored), float(np.sqrt((r * r).sum() / len(a))), (e, em)
+
+
+def decision_margins(a, b):
+    """What makes the flag and the rotation well defined (the tests' precondition): the relative gap of the two candidates' residual sums
+    and, for the chosen candidate's covariance, the gap of its two smallest singular values relative to the largest."""
+    a, b = centred(a), centred(b)
+    _, e = kabsch(a, b)
+    _, em = kabsch(-a, b)
+    s = np.linalg.svd(a.T @ b, compute_uv=False)
+    return abs(e - em) / max(e, em, 1e-300), (s[1] - s[2]) / s[0]
+
+
+def unfitted_rmsd(a, b):
+    r = centred(a) - centred(b)
+    return float(np.sqrt((r * r).sum() / len(r)))
+
+
+def superpose(models, target, mirror=True, iters=0):
+    """models [K, n, 3] onto target [n, 3] -> dict(rmsd [K], mirrored [K], mean [n, 3], rmsf [n], fitted [K, n, 3]).
+    iters > 0: then `iters` times the mean of the fitted models becomes the target of a rotation-only fit (the handedness stays as the
+    first pass settled it); rmsd is then the RMS distance of every fitted model from the final mean."""
+    models = np.asarray(models, dtype=np.float64)
+    target = np.asarray(target, dtype=np.float64)
+    K, n = models.shape[0], models.shape[1]
+    cen = np.stack([centred(m) for m in models])
+    tc = centred(target)
+    shift = target.mean(axis=0)
+    rmsd, mirrored, fitted = np.empty(K), np.zeros(K, dtype=np.int32), np.empty_like(cen)
+    for k in range(K):
+        Q, mirrored[k], rmsd[k], _ = fit(cen[k], tc, mirror)
+        fitted[k] = cen[k] @ Q.T + shift
+    if iters > 0:
+        sign = np.where(mirrored == 1, -1.0, 1.0)
+        fitted -= shift
+        for _ in range(iters):
+            tc = centred(fitted.mean(axis=0))
+            for k in range(K):
+                R, _ = kabsch(sign[k] * cen[k], tc)
+                fitted[k] = (sign[k] * cen[k]) @ R.T
+    mean = fitted.mean(axis=0)
+    dev = ((fitted - mean) ** 2).sum(axis=2)                # [K, n]
+    if iters > 0:
+        rmsd = np.sqrt(dev.sum(axis=1) / n)
+    return dict(rmsd=rmsd, mirrored=mirrored, mean=mean, rmsf=np.sqrt(dev.mean(axis=0)), fitted=fitted)
+
+
+def rmsd_table(models, mirror=True):
+    """(rmsd [K, K], mirrored [K, K]): entry [a][b] = the fit of model a onto model b; the diagonal is 0 and not mirrored."""
+    models = np.asarray(models, dtype=np.float64)
+    K = len(models)
+    rmsd, mirrored = np.zeros((K, K)), np.zeros((K, K), dtype=np.int32)
+    for a in range(K):
+        for b in range(K):
+            if a != b:
+                _, mirrored[a, b], rmsd[a, b], _ = fit(models[a], models[b], mirror)
+    return rmsd, mirrored

@@ -57,6 +57,11 @@ def kernels(co):
         ins = re.sub(r"\b0x[0-9a-f]{8,}\b(?= <)", "", ins)             # absolute branch addresses (the relative form stays)
         if ins and ins != "...":                                        # ("...": the padding between functions)
             cur.append(ins)
+    # the assembler pads the end of the text section with s_nop (the instruction prefetch may run past the last s_endpgm): that padding is
+    # listed under whichever kernel comes last in the unit, and moves when a kernel is added behind it
+    for body in funcs.values():
+        while len(body) > 1 and body[-1] == "s_nop 0":
+            body.pop()
     return funcs
 
 

@@ -249,4 +249,33 @@ hipError_t launch_compare_table(const double*, const unsigned*, const double*, i
     return hipSuccess;
 }
 
+// c3d_superpose_replicas / c3d_rmsd_table: nothing is fitted; every pair comes out as the identity's (residual 0, not mirrored), the fitted
+// models as the centred ones and their mean as zero
+hipError_t launch_superpose_gather64(const double*, int, int, int, double*, hipStream_t) { LaunchScope ls; return hipSuccess; }
+hipError_t launch_superpose_centre(double*, int, int K, double* cent, hipStream_t) {
+    LaunchScope ls;
+    for (int k = 0; k < 3 * K; ++k) cent[k] = 0.0;
+    return hipSuccess;
+}
+hipError_t launch_superpose_fit(const double*, int KA, const double*, int KB, int, int, bool, const int*, double*, double*, double* fit, int* mirrored,
+                                double* res, hipStream_t) {
+    LaunchScope ls;
+    for (size_t q = 0; q < (size_t)KA * KB; ++q) {
+        sup_identity(fit + q * kSupFit);
+        mirrored[q] = 0;
+        if (res) res[q] = 0.0;
+    }
+    return hipSuccess;
+}
+hipError_t launch_superpose_apply(const double*, int, int, const double*, const double*, double*, hipStream_t) { LaunchScope ls; return hipSuccess; }
+hipError_t launch_superpose_mean(const double*, int K, int n, double* mean, double* rmsf, double* dev, hipStream_t) {
+    LaunchScope ls;
+    for (int i = 0; i < 3 * n; ++i) mean[i] = 0.0;
+    for (int i = 0; i < n; ++i) rmsf[i] = 0.0;
+    if (dev) for (int k = 0; k < K; ++k) dev[k] = 0.0;
+    return hipSuccess;
+}
+hipError_t launch_superpose_store32(const double*, int, int, int, float*, hipStream_t) { LaunchScope ls; return hipSuccess; }
+hipError_t launch_superpose_store64(const double*, int, int, int, double*, double*, hipStream_t) { LaunchScope ls; return hipSuccess; }
+
 }  // namespace c3d
