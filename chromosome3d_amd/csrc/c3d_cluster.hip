@@ -29,7 +29,7 @@
 //   P == 1      (N <= 64) a replica is one workgroup: no record at all, positions go LDS -> LDS.
 //   completion  every workgroup that finishes its last step bumps a counter; the one that completes replicas x parts writes a mark
 //               into host-mapped memory (no mark -> the host re-runs the range step by step); the host may end its wait on that
-//               mark instead of hipStreamSynchronize (c3d_api.cpp run_cluster, option spin_wait_us).
+//               mark instead of hipStreamSynchronize (c3d_run.cpp run_cluster, option spin_wait_us).
 //
 // Arithmetic: c3d_step_core.h, every row's force and every sum formed in the order k_step forms it, so a range run
 // here ends in the bits of the per-step path.  Every spin is bounded; a workgroup that gives up sets *timeout and the
@@ -683,7 +683,7 @@ static hipError_t cluster_go(const DevModel& m, const DevFire& fp, const Cluster
     // which of the two kernels this translation unit holds: a unit built with -DC3D_CLUSTER_TP carries k_cluster_tp (ranges that hold
     // two-point minimiser steps) and nothing else, the others k_cluster alone; the single-unit build (neither split macro) holds both.
     // Nothing is set up here: the unit was loaded, and every instantiation given its dynamic LDS size, by cluster_prepare_unit below —
-    // before this process's first launch on the device, under the loader's exclusive lock (c3d_api.cpp "code objects")
+    // before this process's first launch on the device, under the loader's exclusive lock (c3d_gate.cpp "code objects")
 #if defined(C3D_CLUSTER_TP)
     constexpr bool kHasLean = false, kHasTp = true;
 #elif defined(C3D_CLUSTER_POT)
@@ -740,7 +740,7 @@ static hipError_t cluster_geom(const DevModel& m, const DevFire& fp, const Clust
 
 // Loads the code object that holds this unit's kernels on the CURRENT device and allows every instantiation in it the dynamic LDS a
 // launch may ask for (more than the 64 KB a kernel gets by default; hipFuncSetAttribute is per function and device).  Called once per
-// (unit, device) by the loader of c3d_api.cpp while it holds its lock exclusively: after it, a launch from this unit changes no state of
+// (unit, device) by the loader of c3d_gate.cpp while it holds its lock exclusively: after it, a launch from this unit changes no state of
 // the runtime.
 template <int POT, bool TP>
 static hipError_t cluster_prepare_unit() {

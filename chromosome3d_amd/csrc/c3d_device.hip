@@ -306,7 +306,7 @@ __device__ __forceinline__ double round_tenths(double v) {
 
 // Elements whose K * mean / P * 10 lies within 1e-10 (relative) of a half-integer are FLAGGED: the device's pow() and its
 // tree sum may differ from the reference's libm pow and row-major running sum (chromosome3D.pl:132-139) by a few ulp,
-// which only such an element can notice.  The host recomputes the flagged ones in the reference's order (c3d_api.cpp).
+// which only such an element can notice.  The host recomputes the flagged ones in the reference's order (c3d_api.cpp c3d_set_if_matrix).
 __global__ __launch_bounds__(256) void k_if_quantise(const double* __restrict__ P, const double* __restrict__ partial,
                                                     int npartial, int n, int npad, double K, int min_sep, int rep_sep,
                                                     int32_t* __restrict__ dist10, float* __restrict__ tgt,

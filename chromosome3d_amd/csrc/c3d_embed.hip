@@ -471,7 +471,7 @@ hipError_t launch_dg_embed(const float* U, const float* L, int n, int npad, int 
     return hipGetLastError();
 }
 
-// loads the unit's code object on the current device and allows k_dg_eig the whole LDS of a CU (c3d_api.cpp "code objects": once per
+// loads the unit's code object on the current device and allows k_dg_eig the whole LDS of a CU (c3d_gate.cpp "code objects": once per
 // device, never beside a launch)
 hipError_t preload_embed_unit() {
     return hipFuncSetAttribute(reinterpret_cast<const void*>(k_dg_eig), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);

@@ -1,4 +1,4 @@
-// c3d_internal.h — shared between the HIP kernels (c3d_device.hip) and the C-ABI host (c3d_api.cpp).
+// c3d_internal.h — shared between the HIP kernels (c3d_device.hip) and the C-ABI host (c3d_api.cpp and the other host units: c3d_ctx.h).
 // Not part of the public boundary (that is include/c3d.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -231,7 +231,7 @@ hipError_t launch_cluster(const DevModel& m, const DevFire& fp, const ClusterPla
                           unsigned* claim, hipStream_t s);
 // Code objects.  The runtime loads a code object at the first use of one of its kernels; libc3d does not leave that to chance: every
 // translation unit that holds kernels exports a function that loads its code object on the current device (and, for the multi-step
-// units, gives every instantiation its dynamic-LDS allowance), and the loader of c3d_api.cpp ("code objects") calls them one at a time,
+// units, gives every instantiation its dynamic-LDS allowance), and the loader of c3d_gate.cpp ("code objects") calls them one at a time,
 // under a lock that every entry of the library holds shared around its HIP calls — no code object is loaded beside any of them.
 hipError_t preload_device_unit();
 hipError_t preload_cluster_base_unit();

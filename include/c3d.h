@@ -255,7 +255,7 @@ int c3d_set_option(c3d_ctx* ctx, const char* key, double value);
 
 /* Process-wide switches, to be set before the first c3d_create (no environment variable is read by the library):
  *   preload         which code objects c3d_create loads before it returns (the library never leaves a load to the runtime's first-launch
- *                   path and never loads beside another HIP call of the library: csrc/c3d_api.cpp "code objects"):
+ *                   path and never loads beside another HIP call of the library: csrc/c3d_gate.cpp "code objects"):
  *                   1 (default)  what a default job launches from — K1 + per-step unit, both multi-step units of the shipped potential,
  *                                scoring — +13 ms on the first c3d_create, once per process and device;
  *                   2            all sixteen units, +24 ms (long-lived executors: nothing is ever loaded after the first c3d_create of a device);

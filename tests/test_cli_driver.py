@@ -299,7 +299,7 @@ def test_batch_executor_per_device_lists_and_threads_rehearsed_on_one_gpu(built,
             assert open(runs["one"][0] / chrom / f"{cid}_model{k}.pdb").read() == open(runs["eight"][0] / chrom / f"{cid}_model{k}.pdb").read(), (chrom, k)
     # (round 5 ran the eight-context start seven times here to see whether its device exception came back; a pass by not reproducing a
     #  race is no evidence.  Round 6 removed what could race — c3d_create loads every code object a default job needs before it returns,
-    #  no helper thread touches the runtime, loads and launches exclude one another: csrc/c3d_api.cpp "code objects" — and checks THAT on
+    #  no helper thread touches the runtime, loads and launches exclude one another: csrc/c3d_gate.cpp "code objects" — and checks THAT on
     #  the CPU under ThreadSanitizer against a fake HIP layer, tests/test_abi_host.py::test_executor_and_loader_under_thread_sanitizer;
     #  the start above runs once, like any other test.)
     # --pair 1 (default), three lanes: the small chromosomes annealed on halves of the device, --pair 0: nobody did

@@ -1000,7 +1000,7 @@ def test_packed_pair_term_has_the_scalar_forms_bits(solver, cid):
 
 
 def test_code_objects_load_in_create_or_at_the_entry_that_needs_them_and_change_no_bit(built):
-    """The loader of csrc/c3d_api.cpp ("code objects", round 6; include/c3d.h c3d_set_process_option "preload"): c3d_create loads the four
+    """The loader of csrc/c3d_gate.cpp ("code objects", round 6; include/c3d.h c3d_set_process_option "preload"): c3d_create loads the four
     units a default job launches from (preload 1), all sixteen (2) or none (0: each at the first entry that needs it); a potential outside
     the default set, the fp64 step and the embedding load at the entry that first needs them — counted by the stat `units_loaded` — and
     none of it touches a result: fresh processes in the three modes end a job — K1, 300 steps of the default schedule through the

@@ -54,16 +54,16 @@ def test_the_cli_lists_the_options(built):
 
 
 def test_the_fake_hip_harness_still_links(built, tmp_path):
-    """tools/sanitize/hip_stub.cpp stands in for every launcher c3d_api.cpp calls: the context code and the stub link into one program
+    """tools/sanitize/hip_stub.cpp stands in for every launcher the host units call: the context code and the stub link into one program
     (no sanitizer here: tools/sanitize/run.sh builds the same objects with them)."""
     cxx = shutil.which("g++") or shutil.which("c++")
     if cxx is None:
         pytest.skip("no host C++ compiler")
     csrc, san = os.path.join(ROOT, "chromosome3d_amd", "csrc"), os.path.join(ROOT, "tools", "sanitize")
     flags = ["-std=c++17", "-O0", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "include"), "-Wno-unused-result"]
-    jobs = [(os.path.join(csrc, "c3d_api.cpp"), "api.o", []), (os.path.join(csrc, "c3d_host.cpp"), "host.o", []),
-            (os.path.join(csrc, "c3d_batch_main.cpp"), "batch.o", ["-Dmain=c3d_batch_main"]), (os.path.join(san, "hip_stub.cpp"), "stub.o", []),
-            (os.path.join(san, "executor_tsan_main.cpp"), "main.o", [])]
+    jobs = [(os.path.join(csrc, "c3d_%s.cpp" % u), u + ".o", []) for u in ("api", "gate", "run", "analysis", "host")] + [
+        (os.path.join(csrc, "c3d_batch_main.cpp"), "batch.o", ["-Dmain=c3d_batch_main"]), (os.path.join(san, "hip_stub.cpp"), "stub.o", []),
+        (os.path.join(san, "executor_tsan_main.cpp"), "main.o", [])]
     procs = [subprocess.Popen([cxx] + flags + extra + ["-c", src, "-o", str(tmp_path / obj)], stderr=subprocess.PIPE, text=True) for src, obj, extra in jobs]
     for p in procs:
         err = p.communicate()[1]

@@ -4,7 +4,7 @@
     python tools/isa_compare.py OLD_LIB_DIR NEW_LIB_DIR [--report FILE]
 
 OLD_LIB_DIR / NEW_LIB_DIR hold the units' object files (chromosome3d_amd/_lib/*.o of two checkouts).  For every unit of the OLD
-build, the device code object is taken out of the object's .hip_fatbin section and, for every kernel of the OLD build, three things are compared with the NEW build:
+build that has device code (the host units' objects have no .hip_fatbin section and are skipped), the device code object is taken out of the object's .hip_fatbin section and, for every kernel of the OLD build, three things are compared with the NEW build:
 the symbol exists, its instruction list (llvm-objdump, without addresses and raw bytes; branch targets as offsets from the kernel's
 start) is the same, and its resource metadata (VGPRs, AGPRs, SGPRs, LDS, scratch, spills, wavefront size) is the same.  Kernels
 only the NEW build has are listed as added.  Exit status 0 when nothing of the OLD build changed.
@@ -27,6 +27,11 @@ META_KEYS = (".vgpr_count", ".agpr_count", ".sgpr_count", ".group_segment_fixed_
 def tool(name):
     p = os.path.join(LLVM, name)
     return p if os.path.exists(p) else name
+
+
+def has_device_code(obj):
+    out = subprocess.run([tool("llvm-readelf"), "-S", obj], check=True, capture_output=True, text=True).stdout
+    return ".hip_fatbin" in out
 
 
 def code_object(obj, tmp):
@@ -113,7 +118,7 @@ def main():
         for old in sorted(glob.glob(os.path.join(a.old, "*.o"))):
             unit = os.path.basename(old)
             new = os.path.join(a.new, unit)
-            if unit in ("c3d_api.o", "c3d_host.o"):
+            if not has_device_code(old):
                 continue
             if not os.path.exists(new):
                 lines.append("%s: missing in the new build" % unit); bad += 1

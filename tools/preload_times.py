@@ -1,4 +1,4 @@
-"""What c3d_create costs with the code objects loaded inside it (round 6: csrc/c3d_api.cpp "code objects"), one fresh process per mode:
+"""What c3d_create costs with the code objects loaded inside it (round 6: csrc/c3d_gate.cpp "code objects"), one fresh process per mode:
 python tools/preload_times.py            (GPU box)
   preload 0   no unit in c3d_create (each at the first entry that needs it)
   preload 1   the default job's four units (default)

@@ -1,12 +1,12 @@
 // hip_stub.cpp — a fake HIP layer for ThreadSanitizer runs of libc3d's HOST code on a box without a GPU (tools/sanitize/run.sh).
 //
-// c3d_api.cpp (context, code-object loader, launch program, executor of c3d_run) and c3d_batch_main.cpp (per-device lists, lanes, the XCD
-// broker) are compiled as they are, with -fsanitize=thread, and linked against THIS file instead of libamdhip64 and the kernels'
+// The host units — c3d_api.cpp (context), c3d_gate.cpp (code-object loader), c3d_run.cpp (launch program, executor of c3d_run),
+// c3d_analysis.cpp (scoring) — and c3d_batch_main.cpp (per-device lists, lanes, the XCD broker) are compiled as they are, with -fsanitize=thread, and linked against THIS file instead of libamdhip64 and the kernels'
 // translation units: "device" memory is host memory, a stream is a counter, a copy is a memcpy, every kernel launcher returns success and
 // computes nothing — except K1, which is restated on the host so that the executor has restraints to write, and the multi-step launcher,
 // which writes the completion mark its kernel would write (every seventh launch does not: the abandoned-launch path runs too).
 //
-// Beyond what TSan sees by itself, the stub CHECKS the loader's contract (c3d_api.cpp "code objects"): a unit's load function and any HIP
+// Beyond what TSan sees by itself, the stub CHECKS the loader's contract (c3d_gate.cpp "code objects"): a unit's load function and any HIP
 // call of the library must never overlap in time, whatever the thread.  Every function below counts as device work (LaunchScope) except
 // the device queries and pure look-ups — hipGetDeviceCount, hipSetDevice, hipGetDevicePropertiesR0600, hipDeviceGetAttribute,
 // hipHostGetDevicePointer, hipGetErrorString, hipGetLastError — so allocation, release, stream / event / graph creation and destruction and synchronisation
