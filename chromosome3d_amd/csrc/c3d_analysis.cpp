@@ -1,6 +1,6 @@
 // c3d_analysis.cpp — host unit of libc3d.so: the output side.  What a run's models are worth and how they relate, from the coordinates
-// resident on the device (kernels: c3d_score.hip): c3d_score_replicas, c3d_compare_replicas, c3d_superpose_replicas, c3d_rmsd_table and
-// the test hooks c3d_debug_if_ranks / c3d_debug_distance_ranks.  Each call carves its device scratch out of one allocation (Carve).
+// resident on the device (kernels: c3d_score.hip): c3d_score_replicas, c3d_compare_replicas, c3d_superpose_replicas, c3d_rmsd_table,
+// c3d_ensemble_map, c3d_ensemble_score and the test hooks c3d_debug_if_ranks / c3d_debug_distance_ranks.  Each call carves its device scratch out of one allocation (Carve).
 #include "c3d_ctx.h"
 
 using namespace c3d::host;
@@ -446,5 +446,146 @@ extern "C" int c3d_rmsd_table(c3d_ctx* c, const double* extra_xyz, int n_extra, 
         if (mirrored) mirrored[q] = hm[q];
     }
     ++c->rmsd_table_runs;
+    return C3D_OK;
+}
+
+// ---- the ensemble's distance map (c3d_score.hip k_ens_*) ----
+// byte offsets into the one allocation of a call: the models, the pick list, up to three n x n matrices (the map's outputs; the score's
+// rank matrix of IF and the map it ranks next) and, for the score, the sort keys, two sets of per-row sums and the asymmetry flag
+struct EnsembleScratch : Carve {
+    size_t xyz = 0, pick = 0, mat[3] = {0, 0, 0}, keys = 0, rows = 0, rows2 = 0, asym = 0;
+};
+static EnsembleScratch ensemble_layout(int n, int K, int Kp, int matrices, size_t key_slots) {
+    EnsembleScratch L;
+    L.xyz = L.take(sizeof(double) * 3 * (size_t)n * K);
+    L.pick = L.take(sizeof(int32_t) * (size_t)Kp);
+    for (int k = 0; k < matrices; ++k) L.mat[k] = L.take(sizeof(double) * (size_t)n * n);
+    if (key_slots) {
+        L.keys = L.take(sizeof(unsigned long long) * key_slots);
+        L.rows = L.take(sizeof(double) * (size_t)n);
+        L.rows2 = L.take(sizeof(double) * (size_t)n);
+        L.asym = L.take(sizeof(int));
+    }
+    return L;
+}
+// what both entries refuse before any launch; on success *list holds the Kp model indices in summation order
+static int ensemble_check(const c3d_ctx* c, const char* who, const double* extra_xyz, int n_extra, const int32_t* pick, int n_pick, std::vector<int32_t>* list) {
+    const std::string w = std::string(who) + ": ";
+    if (!c) return fail(C3D_ERR_INVALID, w + "null context");
+    if (!c->have_replicas) return fail(C3D_ERR_INVALID, w + "call c3d_init_replicas first");
+    if (c->n < 2) return fail(C3D_ERR_INVALID, w + "models of fewer than 2 beads have no pair");
+    if (n_extra < 0 || (n_extra > 0 && !extra_xyz)) return fail(C3D_ERR_INVALID, w + "n_extra < 0, or extra models without coordinates");
+    if ((long)c->nrep + n_extra > C3D_COMPARE_MAX_MODELS) return fail(C3D_ERR_INVALID, w + "more than C3D_COMPARE_MAX_MODELS models");
+    if (n_pick < 0) return fail(C3D_ERR_INVALID, w + "n_pick < 0");
+    if ((n_pick > 0) != (pick != nullptr)) return fail(C3D_ERR_INVALID, w + "a pick list without a length, or a length without a list (all models: NULL and 0)");
+    if (n_pick > c3d::kEnsMaxPicks) return fail(C3D_ERR_INVALID, w + "more than 4096 picks");
+    const int K = c->nrep + n_extra;
+    for (int k = 0; k < n_pick; ++k)
+        if (pick[k] < 0 || pick[k] >= K) return fail(C3D_ERR_INVALID, w + "a pick index outside 0..K-1");
+    if (n_pick > 0) list->assign(pick, pick + n_pick);
+    else {
+        list->resize((size_t)K);
+        for (int k = 0; k < K; ++k) (*list)[(size_t)k] = k;
+    }
+    return C3D_OK;
+}
+static bool ensemble_cutoff_ok(double cutoff) { return std::isfinite(cutoff) && cutoff > 0.0; }
+
+// the matrix at d_M ranked in place (launch_if_rank_keys, launch_if_rank_sort): *sum = its n row sums of (rank - ma)^2 added in index order;
+// *symmetric = false, and nothing ranked, when M(i,j) != M(j,i) for a ranked pair
+static int ensemble_rank(c3d_ctx* c, double* d_M, int range, void* base, const EnsembleScratch& L, size_t mh, size_t slots, double* sum, bool* symmetric) {
+    const int n = c->n;
+    unsigned long long* const d_keys = at<unsigned long long>(base, L.keys);
+    LAUNCH_TRY("rank key launch", c3d::launch_if_rank_keys(d_M, n, range, d_keys, mh, slots, at<int>(base, L.asym), c->stream));
+    if (int rc = read_back(c, at<int>(base, L.asym), sizeof(int))) return rc;
+    *symmetric = *static_cast<const int*>(c->h_stage) == 0;
+    if (!*symmetric) return C3D_OK;
+    const double ma = 0.5 * (2.0 * (double)mh + 1.0);
+    LAUNCH_TRY("rank sort launch", c3d::launch_if_rank_sort(d_M, n, range, d_keys, mh, slots, ma, at<double>(base, L.rows), c->stream));
+    if (int rc = read_back(c, at<double>(base, L.rows), sizeof(double) * (size_t)n)) return rc;
+    const double* const rows = static_cast<const double*>(c->h_stage);
+    double s = 0;
+    for (int i = 0; i < n; ++i) s += rows[i];        // fixed order: deterministic
+    *sum = s;
+    return C3D_OK;
+}
+
+extern "C" int c3d_ensemble_map(c3d_ctx* c, const double* extra_xyz, int n_extra, const int32_t* pick, int n_pick, double cutoff, double* mean, double* sd,
+                                double* contact) {
+    std::vector<int32_t> list;
+    if (int rc = ensemble_check(c, "c3d_ensemble_map", extra_xyz, n_extra, pick, n_pick, &list)) return rc;
+    if (!mean && !sd && !contact) return fail(C3D_ERR_INVALID, "c3d_ensemble_map: every output is NULL");
+    if (contact && !ensemble_cutoff_ok(cutoff)) return fail(C3D_ERR_INVALID, "c3d_ensemble_map: the contact map needs a finite cutoff > 0");
+    const int n = c->n, K = c->nrep + n_extra, Kp = (int)list.size();
+    if (n_extra > 0)
+        if (int rc = c3d::check_model_coords(extra_xyz, (size_t)3 * n * n_extra, "c3d_ensemble_map")) return rc;
+    C3D_ENTRY(c, unit_bit(UNIT_SCORE));
+    double* const outs[3] = {mean, sd, contact};
+    const int matrices = (mean ? 1 : 0) + (sd ? 1 : 0) + (contact ? 1 : 0);
+    const EnsembleScratch L = ensemble_layout(n, K, Kp, matrices, 0);
+    DevTmp<char> tmp;
+    if (int rc = compare_alloc(tmp, L.total, "c3d_ensemble_map")) return rc;
+    double* const d_xyz = at<double>(tmp.p, L.xyz);
+    int* const d_pick = at<int>(tmp.p, L.pick);
+    double* d_out[3] = {nullptr, nullptr, nullptr};
+    for (int k = 0, slot = 0; k < 3; ++k)
+        if (outs[k]) d_out[k] = at<double>(tmp.p, L.mat[slot++]);
+    if (int rc = superpose_models(c, d_xyz, extra_xyz, n_extra)) return rc;
+    HIP_TRY(hipMemcpyAsync(d_pick, list.data(), sizeof(int32_t) * (size_t)Kp, hipMemcpyHostToDevice, c->stream));
+    LAUNCH_TRY("ensemble launch", c3d::launch_ensemble_map(d_xyz, n, d_pick, Kp, contact ? cutoff : 0.0, d_out[0], d_out[1], d_out[2], c->stream));
+    // straight into the caller's matrices: the pinned stage would have to grow to their size
+    for (int k = 0; k < 3; ++k)
+        if (outs[k]) HIP_TRY(hipMemcpyAsync(outs[k], d_out[k], sizeof(double) * (size_t)n * n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    ++c->ensemble_map_runs;
+    return C3D_OK;
+}
+
+extern "C" int c3d_ensemble_score(c3d_ctx* c, const double* IF, int range, const double* extra_xyz, int n_extra, const int32_t* pick, int n_pick, double cutoff,
+                                  double* rho_mean, double* rho_contact) {
+    std::vector<int32_t> list;
+    if (int rc = ensemble_check(c, "c3d_ensemble_score", extra_xyz, n_extra, pick, n_pick, &list)) return rc;
+    if (!rho_mean && !rho_contact) return fail(C3D_ERR_INVALID, "c3d_ensemble_score: both outputs are NULL");
+    if (!IF) return fail(C3D_ERR_INVALID, "c3d_ensemble_score: the Spearman coefficient needs the IF matrix");
+    if (range < 1) return fail(C3D_ERR_INVALID, "c3d_ensemble_score: range < 1");
+    if (rho_contact && !ensemble_cutoff_ok(cutoff)) return fail(C3D_ERR_INVALID, "c3d_ensemble_score: the contact map needs a finite cutoff > 0");
+    const int n = c->n, K = c->nrep + n_extra, Kp = (int)list.size();
+    const size_t mh = rank_half_pairs(n, range), slots = c3d::if_rank_key_slots(mh);
+    if (mh < 1) return fail(C3D_ERR_INVALID, "c3d_ensemble_score: range leaves no pairs");
+    if (n_extra > 0)
+        if (int rc = c3d::check_model_coords(extra_xyz, (size_t)3 * n * n_extra, "c3d_ensemble_score")) return rc;
+    C3D_ENTRY(c, unit_bit(UNIT_SCORE));
+    // two matrices: IF, ranked once, and the map that is ranked against it — the mean first, then the contact frequencies in the same slot
+    const EnsembleScratch L = ensemble_layout(n, K, Kp, 2, slots);
+    DevTmp<char> tmp;
+    if (int rc = compare_alloc(tmp, L.total, "c3d_ensemble_score")) return rc;
+    double* const d_xyz = at<double>(tmp.p, L.xyz);
+    int* const d_pick = at<int>(tmp.p, L.pick);
+    double* const d_A = at<double>(tmp.p, L.mat[0]);
+    double* const d_B = at<double>(tmp.p, L.mat[1]);
+    HIP_TRY(hipMemcpyAsync(d_A, IF, sizeof(double) * (size_t)n * n, hipMemcpyHostToDevice, c->stream));
+    double saa = 0;
+    bool symmetric = false;
+    if (int rc = ensemble_rank(c, d_A, range, tmp.p, L, mh, slots, &saa, &symmetric)) return rc;
+    if (!symmetric) return fail(C3D_ERR_INVALID, "c3d_ensemble_score: the matrix is not symmetric over the ranked pairs (no host ranking here)");
+    if (int rc = superpose_models(c, d_xyz, extra_xyz, n_extra)) return rc;
+    HIP_TRY(hipMemcpyAsync(d_pick, list.data(), sizeof(int32_t) * (size_t)Kp, hipMemcpyHostToDevice, c->stream));
+    const double ma = 0.5 * (2.0 * (double)mh + 1.0);
+    double* const want[2] = {rho_mean, rho_contact};
+    for (int k = 0; k < 2; ++k) {
+        if (!want[k]) continue;
+        // the kernel and arguments of c3d_ensemble_map for this output alone: the same bits
+        LAUNCH_TRY("ensemble launch", c3d::launch_ensemble_map(d_xyz, n, d_pick, Kp, k ? cutoff : 0.0, k ? nullptr : d_B, nullptr, k ? d_B : nullptr, c->stream));
+        double sbb = 0;
+        if (int rc = ensemble_rank(c, d_B, range, tmp.p, L, mh, slots, &sbb, &symmetric)) return rc;
+        if (!symmetric) return fail(C3D_ERR_HIP, "c3d_ensemble_score: the device's map is not symmetric (cannot happen)");
+        LAUNCH_TRY("ensemble launch", c3d::launch_ensemble_corr(d_A, d_B, n, range, ma, at<double>(tmp.p, L.rows2), c->stream));
+        if (int rc = read_back(c, at<double>(tmp.p, L.rows2), sizeof(double) * (size_t)n)) return rc;
+        const double* const rows = static_cast<const double*>(c->h_stage);
+        double sab = 0;
+        for (int i = 0; i < n; ++i) sab += rows[i];      // fixed order: deterministic
+        *want[k] = sab / sqrt(saa * sbb);
+    }
+    ++c->ensemble_score_runs;
     return C3D_OK;
 }

@@ -1040,6 +1040,8 @@ extern "C" int c3d_get_stat(const c3d_ctx* c, const char* key, double* value) {
     else if (!strcmp(key, "f64_evals")) *value = (double)c->f64_evals;
     else if (!strcmp(key, "superpose_runs")) *value = (double)c->superpose_runs;
     else if (!strcmp(key, "rmsd_table_runs")) *value = (double)c->rmsd_table_runs;
+    else if (!strcmp(key, "ensemble_map_runs")) *value = (double)c->ensemble_map_runs;
+    else if (!strcmp(key, "ensemble_score_runs")) *value = (double)c->ensemble_score_runs;
     else if (!strcmp(key, "cluster_xcd_count")) *value = (double)c->xcd_count;
     else if (!strcmp(key, "cluster_xcd_base")) *value = (double)c->xcd_base;
     else if (!strcmp(key, "cluster_ok")) *value = c->cl_ok ? 1.0 : 0.0;

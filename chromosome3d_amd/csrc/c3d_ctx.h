@@ -222,6 +222,7 @@ struct c3d_ctx {
     long compare_runs = 0;                 // stat: completed calls of c3d_compare_replicas
     long f64_evals = 0;                    // stat: completed calls of c3d_eval_f64
     long superpose_runs = 0, rmsd_table_runs = 0;   // stats: completed calls of c3d_superpose_replicas / c3d_rmsd_table
+    long ensemble_map_runs = 0, ensemble_score_runs = 0;   // stats: completed calls of c3d_ensemble_map / c3d_ensemble_score
     long k1_recomputed = 0, k1_patched = 0;   // K1: near-tie elements redone on the host in the reference's order / changed by it
     long graph_captures = 0, graph_launches = 0, step_launches = 0, resident_launches = 0, cluster_launches = 0;
     bool has_two_point = false;            // the program holds two-point minimiser steps (run_ops splits ranges at their borders)

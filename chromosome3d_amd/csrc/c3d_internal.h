@@ -405,6 +405,17 @@ hipError_t launch_superpose_apply(const double* A, int K, int n, const double* f
 hipError_t launch_superpose_mean(const double* fitted, int K, int n, double* mean, double* rmsf, double* dev, hipStream_t s);
 hipError_t launch_superpose_store32(const double* fitted, int n, int npad, int nrep, float* X, hipStream_t s);
 hipError_t launch_superpose_store64(const double* fitted, int n, int np, int nrep, double* X0, double* X1, hipStream_t s);
+// The ensemble's distance map (c3d_ensemble_map, c3d_ensemble_score; k_ens_*).  xyz holds K models of n x 3 doubles, xyz interleaved; pick
+// (device) lists Kp model indices in 0..K-1, the summation order.  launch_ensemble_map: mean, sd, contact (n x n row-major doubles on the
+// device, any of them null) = per pair the mean of d_k, sqrt(sum (d_k - mean)^2 / Kp) and #{d_k < cutoff} / Kp, both triangles from one
+// value; one workgroup a 64 x 64 tile of the upper triangle, the picked models staged in blocks of kEnsModels.
+// launch_ensemble_corr: rows[i] = sum over j, |i-j| >= range, of (A(i,j) - ma)(B(i,j) - ma) for two rank matrices launch_if_rank_sort left.
+constexpr int kEnsModels = 16;
+constexpr int kEnsMaxPicks = 4096;
+inline int ensemble_tiles(int n) { return (n + 63) / 64; }
+hipError_t launch_ensemble_map(const double* xyz, int n, const int* pick, int Kp, double cutoff, double* mean, double* sd, double* contact,
+                               hipStream_t s);
+hipError_t launch_ensemble_corr(const double* A, const double* B, int n, int range, double ma, double* rows, hipStream_t s);
 
 // Target matrix entry: NOE target in Angstrom, 0 = no restraint (host c3d_set_restraints and K1).
 inline float encode_target_host(float t) { return t > 0 ? t : 0.0f; }

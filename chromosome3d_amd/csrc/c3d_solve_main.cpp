@@ -7,6 +7,8 @@
 //       exactly the cns_solve role: restraints in, <ID>_<k>.pdb out
 //   --similarity <path> adds the replicas' similarity table (Spearman and scaled RMSD of the pair distances, on the device)
 //   --superpose writes the models in one frame and one hand, the best-ranked model's; --rmsf <path> adds the mean model and per-bead spread
+//   --ensemble <prefix> writes the ensemble's distance map — <prefix>_mean.txt, _sd.txt, _contact.txt: mean, spread and contact frequency of
+//       every bead pair over the models (or the --ensemble-top best) — and prints how that map follows the input matrix
 //
 // Success convention of the reference: <ID>_<M>.pdb exists, iam.running removed; on failure
 // iam.running is renamed iam.failed and the exit code is non-zero (:266-283).
@@ -36,6 +38,14 @@ static void usage() {
             "                                only the coordinates move (rotation, reflection, translation), every REMARK row stays]\n"
             "                 [--rmsf <path>   mean model and per-bead spread of the superposed ensemble: one row `bead mean_x mean_y mean_z rmsf`\n"
             "                                  (generalized Procrustes from the best-ranked model, 3 iterations, on the device)]\n"
+            "                 [--ensemble <prefix>   the ensemble's distance map, computed on the device: <prefix>_mean.txt and <prefix>_sd.txt hold the mean of\n"
+            "                                        every bead pair's distance over the models and its standard deviation from model to model (%%.3f),\n"
+            "                                        <prefix>_contact.txt the share of models with the pair closer than the cutoff (%%.4f); n lines of n\n"
+            "                                        numbers, the layout of the input matrix.  With --if one line `ensemble: ...` gives Spearman(IF, mean d)\n"
+            "                                        and Spearman(IF, contact); a run started from --tbl has no matrix and writes the maps alone]\n"
+            "                 [--ensemble-top <M>   the map of the M best-ranked models only (lowest int(E_noe) first; default: all models)]\n"
+            "                 [--ensemble-cutoff <A>   contact distance in Angstrom; default 2 x the model's bond length b0 — a convention, not a\n"
+            "                                          measured value; 0: no contact map]\n"
             "                 [--accepted   also write <ID>a_<k>.pdb beside every <ID>_<k>.pdb, as CNS does for structures it accepts]\n");
 }
 
@@ -65,8 +75,9 @@ int main(int argc, char** argv) {
     // (rc -13, "GPU coredump: execvp failed") before the runtime has said WHICH exception — round 5 lost the only evidence of one that way.
     setenv("HSA_DISABLE_COREDUMP_ON_EXCEPTION", "1", 0);          // (0: a user's own setting wins)
     const double t_start = now_s();
-    std::string if_path, tbl_path, out_dir, id, seq_arg, similarity_path, rmsf_path;
-    int superpose = 0;
+    std::string if_path, tbl_path, out_dir, id, seq_arg, similarity_path, rmsf_path, ensemble_prefix;
+    int superpose = 0, ensemble_top = 0;
+    double ensemble_cutoff = -1;      // < 0: 2 x b0
     double K = 11, alpha = 0.5, gtol = 1e-2;
     int final_min = 1;
     int lbfgs = 0;
@@ -104,6 +115,9 @@ int main(int argc, char** argv) {
         else if (s == "--similarity") similarity_path = next("--similarity");   // the ensemble table (c3d_compare_replicas)
         else if (s == "--superpose") superpose = 1;   // the models in the best-ranked model's frame and hand before they are written (c3d_superpose_replicas)
         else if (s == "--rmsf") rmsf_path = next("--rmsf");   // mean model and per-bead spread of the superposed ensemble
+        else if (s == "--ensemble") ensemble_prefix = next("--ensemble");   // mean / sd / contact maps of the ensemble (c3d_ensemble_map, c3d_ensemble_score)
+        else if (s == "--ensemble-top") ensemble_top = atoi(next("--ensemble-top"));
+        else if (s == "--ensemble-cutoff") ensemble_cutoff = atof(next("--ensemble-cutoff"));
         else if (s == "-h" || s == "--help") { usage(); return 0; }
         else { fprintf(stderr, "c3d_solve: unknown option %s\n", s.c_str()); usage(); return 2; }
     }
@@ -229,6 +243,35 @@ int main(int argc, char** argv) {
             for (int b = 0; b < models; ++b)
                 if (a != b) fprintf(f, "%u %u %.5f %.5f\n", first_rep + (unsigned)a, first_rep + (unsigned)b, rho[(size_t)a * models + b], rmsd[(size_t)a * models + b]);
         fclose(f);
+    }
+    if (!ensemble_prefix.empty()) {
+        // the models that count: all of them, or the best-ranked few in c3d_rank's order (which is then the summation order)
+        std::vector<int32_t> order(models);
+        CHECK(c3d_rank(ctx, order.data()));
+        const int top = ensemble_top > 0 && ensemble_top < models ? ensemble_top : 0, Kp = top ? top : models;
+        const double cutoff = ensemble_cutoff < 0 ? 2.0 * (double)model.b0 : ensemble_cutoff;
+        const bool with_contact = cutoff > 0;
+        const size_t nn = (size_t)n * n;
+        std::vector<double> maps((with_contact ? 3 : 2) * nn);
+        CHECK(c3d_ensemble_map(ctx, nullptr, 0, top ? order.data() : nullptr, top, cutoff, maps.data(), maps.data() + nn, with_contact ? maps.data() + 2 * nn : nullptr));
+        const char* const names[3] = {"_mean.txt", "_sd.txt", "_contact.txt"};
+        for (int k = 0; k < (with_contact ? 3 : 2); ++k) {
+            const std::string path = ensemble_prefix + names[k];
+            FILE* f = fopen(path.c_str(), "w");
+            if (!f) { fprintf(stderr, "c3d_solve: cannot write %s\n", path.c_str()); return fail_exit(out_dir); }
+            const double* M = maps.data() + (size_t)k * nn;
+            for (int i = 0; i < n; ++i)
+                for (int j = 0; j < n; ++j) fprintf(f, k == 2 ? "%.4f%s" : "%.3f%s", M[(size_t)i * n + j], j + 1 < n ? " " : "\n");
+            fclose(f);
+        }
+        if (IF) {
+            double rho_mean = 0, rho_contact = 0;
+            CHECK(c3d_ensemble_score(ctx, IF, 3, nullptr, 0, top ? order.data() : nullptr, top, cutoff, &rho_mean, with_contact ? &rho_contact : nullptr));
+            if (with_contact) printf("ensemble: %d models, Spearman(IF, mean d) = %.4f, Spearman(IF, contact) = %.4f\n", Kp, rho_mean, rho_contact);
+            else printf("ensemble: %d models, Spearman(IF, mean d) = %.4f, Spearman(IF, contact) = none (no cutoff)\n", Kp, rho_mean);
+        } else {
+            printf("ensemble: %d models, maps written; no Spearman line: a run started from --tbl has no IF matrix to compare them with\n", Kp);
+        }
     }
     double ms = 0;
     long steps = 0, launches = 0;

@@ -84,6 +84,8 @@ SIGNATURES = {
     "c3d_debug_distance_ranks": (_i, [_vp, _i, _dp]),
     "c3d_superpose_replicas": (_i, [_vp, _i, _dp, _i, _i, _dp, _i32p, _dp, _dp]),
     "c3d_rmsd_table": (_i, [_vp, _dp, _i, _i, _dp, _i32p]),
+    "c3d_ensemble_map": (_i, [_vp, _dp, _i, _i32p, _i, _d, _dp, _dp, _dp]),
+    "c3d_ensemble_score": (_i, [_vp, _dp, _i, _dp, _i, _i32p, _i, _d, _dp, _dp]),
     "c3d_rank": (_i, [_vp, _i32p]),
     "c3d_reduce_model": (_i, [_dp, _i, _dp]),
     "c3d_model_similarity": (_i, [_dp, _dp, _i, _dp, _dp]),

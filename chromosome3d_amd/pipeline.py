@@ -193,6 +193,18 @@ def rmsd_table(solver, extra=None, mirror=True):
     return solver.rmsd_table(extra, mirror)
 
 
+def ensemble_maps(solver, IF=None, rng=3, extra=None, pick=None, cutoff=None):
+    """The ensemble's distance map on the device: a dict with "mean" and "sd" [n, n] — the mean of every pair distance over the solver's
+    replicas (and the models of `extra`) and its spread from model to model — and, with a cutoff in Angstrom, "contact", the share of
+    models in which the pair is closer than that (2 x the model's b0 is a common convention).  With IF also "rho_mean" and "rho_contact":
+    Spearman(IF, mean distance) and Spearman(IF, contact frequency) over |i-j| >= rng.  pick: the models that count, e.g. the best-ranked
+    few of solver.rank().  See Solver.ensemble_map / Solver.ensemble_score."""
+    out = solver.ensemble_map(extra, pick, cutoff)
+    if IF is not None:
+        out["rho_mean"], out["rho_contact"] = solver.ensemble_score(IF, rng, extra, pick, cutoff)
+    return out
+
+
 def build_models(solver, model_count=MODELCOUNT, seed=MD_SEED, first_replica=0, model=None, stages=None, fire=None,
                  gtol=1e-2, check_every=250, final_kind=5):
     """The replacement of `cns_solve < dgsa.inp` (:254-289): runs the whole annealing schedule

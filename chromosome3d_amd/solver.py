@@ -304,6 +304,46 @@ class Solver:
                                         _l.SUPERPOSE_MIRROR if mirror else 0, _l.dptr(rmsd), _l.i32ptr(mirrored)))
         return rmsd, mirrored
 
+    def _picked(self, pick):
+        if pick is None:
+            return None, 0
+        p = np.ascontiguousarray(pick, dtype=np.int32)
+        if p.ndim != 1 or p.size == 0:
+            raise ValueError("pick is a non-empty list of model indices (None: all models)")
+        return p, int(p.size)
+
+    def ensemble_map(self, extra=None, pick=None, cutoff=None, mean=True, sd=True, contact=None):
+        """{"mean", "sd", "contact"} -> [n, n] float64, the maps that were asked for: per bead pair the mean distance over the ensemble,
+        its population standard deviation from model to model, and the share of models in which the pair is closer than `cutoff`, on the
+        device (c3d_ensemble_map).  The models are those of compare(): the replicas at their current coordinates (precision 64: the fp64
+        state), then `extra` [E, n, 3].  pick: the model indices that count, in summation order, repeats allowed (None: all).  contact
+        defaults to whether a cutoff was given.  The matrices are symmetric bit for bit; nothing of the solve changes."""
+        contact = (cutoff is not None) if contact is None else bool(contact)
+        if contact and cutoff is None:
+            raise ValueError("the contact map needs a cutoff")
+        ex = self._extra_models(extra)
+        p, n_pick = self._picked(pick)
+        out = {k: np.empty((self.n, self.n), dtype=np.float64) for k, on in (("mean", mean), ("sd", sd), ("contact", contact)) if on}
+        ptr = lambda k: _l.dptr(out[k]) if k in out else None
+        _l.check(self._L.c3d_ensemble_map(self._h, _l.dptr(ex) if ex is not None else None, 0 if ex is None else ex.shape[0],
+                                          _l.i32ptr(p) if p is not None else None, n_pick, 0.0 if cutoff is None else float(cutoff),
+                                          ptr("mean"), ptr("sd"), ptr("contact")))
+        return out
+
+    def ensemble_score(self, IF, rng=3, extra=None, pick=None, cutoff=None):
+        """(rho_mean, rho_contact or None): Spearman(IF, mean distance) and, with a cutoff, Spearman(IF, contact frequency) of the
+        ensemble's maps over the ordered pairs |i-j| >= rng, ranked on the device (c3d_ensemble_score).  The maps are ensemble_map's for
+        the same arguments, bit for bit.  A good ensemble has rho_mean < 0 and rho_contact > 0.  IF must be symmetric."""
+        IFc = np.ascontiguousarray(IF, dtype=np.float64)
+        assert IFc.shape == (self.n, self.n)
+        ex = self._extra_models(extra)
+        p, n_pick = self._picked(pick)
+        rm, rc = C.c_double(), C.c_double()
+        _l.check(self._L.c3d_ensemble_score(self._h, _l.dptr(IFc), int(rng), _l.dptr(ex) if ex is not None else None,
+                                            0 if ex is None else ex.shape[0], _l.i32ptr(p) if p is not None else None, n_pick,
+                                            0.0 if cutoff is None else float(cutoff), C.byref(rm), C.byref(rc) if cutoff is not None else None))
+        return rm.value, (rc.value if cutoff is not None else None)
+
     def rank(self):
         r = np.empty(self.nrep, dtype=np.int32)
         _l.check(self._L.c3d_rank(self._h, _l.i32ptr(r)))

@@ -323,7 +323,7 @@ int c3d_last_timing(const c3d_ctx* ctx, double* ms_total, long* steps, long* lau
  * "device_rank_runs" (calls of c3d_score_replicas that ranked the IF matrix on the device), "score_wide_runs" (calls of it that were
  * re-run with a histogram sized to the models), "compare_runs" (completed calls of c3d_compare_replicas),
  * "f64_evals" (completed calls of c3d_eval_f64), "superpose_runs" / "rmsd_table_runs" (completed calls of c3d_superpose_replicas /
- * c3d_rmsd_table). */
+ * c3d_rmsd_table), "ensemble_map_runs" / "ensemble_score_runs" (completed calls of c3d_ensemble_map / c3d_ensemble_score). */
 int c3d_get_stat(const c3d_ctx* ctx, const char* key, double* value);
 /* Test hook, no reference counterpart: the multi-step kernel's hand-off trusts a 16-byte unit once its tag word matches — i.e. that a
  * 16-byte aligned store is never observed half-written by a 16-byte load on gfx950.  This runs that exact store / load pair (one producer
@@ -431,6 +431,42 @@ int c3d_debug_distance_ranks(c3d_ctx* ctx, int replica, double* rank);
 int c3d_superpose_replicas(c3d_ctx* ctx, int reference, const double* ref_xyz, int flags, int iters, double* rmsd, int32_t* mirrored,
                            double* mean_xyz, double* rmsf);
 int c3d_rmsd_table(c3d_ctx* ctx, const double* extra_xyz, int n_extra, int flags, double* rmsd, int32_t* mirrored);
+/* The ensemble itself, on the device (c3d_score.hip k_ens_*): what the models say about every bead pair together.  A mean of superposed
+ * coordinates shrinks wherever the models disagree; the quantity that stays meaningful for a population is the distance map.
+ * Models: K = n_replicas + n_extra, numbered as in c3d_compare_replicas; the replicas are taken as c3d_superpose_replicas takes them (on a
+ * precision-64 context the fp64 state bit for bit, else the floats taken as doubles unchanged); extra models are n x 3 doubles, xyz
+ * interleaved, checked as there.  pick: n_pick model indices in 0..K-1 — the models that count, in the order they are summed; an index may
+ * repeat and then counts twice; NULL with n_pick = 0 means all K in index order.  Kp is the length of that list (at most 4096).
+ * The distance d_k(i,j) is the one of c3d_compare_replicas, sqrt(((ux ux) + uy uy) + uz uz) in fp64 with every operation rounded on its
+ * own: it has the bits of the host's.
+ * c3d_ensemble_map: mean, sd, contact — n x n row-major doubles, any of them NULL, not all three:
+ *   mean(i,j)    = sum_k d_k / Kp, summed in list order;
+ *   sd(i,j)      = sqrt(sum_k (d_k - mean)^2 / Kp), the population form, from the deviations in a second walk over the models (never as
+ *                  sum d^2 - Kp mean^2, which loses about 1e-6 A where the models agree);
+ *   contact(i,j) = #{k : d_k(i,j) < cutoff} / Kp: an exact count, divided once.
+ * The diagonal is mean 0, sd 0, contact 1.  Every pair i < j is computed once and stored to both halves: the matrices equal their
+ * transposes bit for bit.  No atomics and one fixed order: two calls on the same state return the same bits.  The matrices are copied
+ * straight into the caller's buffers.
+ * c3d_ensemble_score: how the ensemble's map — not one model's — follows the input: rho_mean = Spearman(IF, mean distance), rho_contact =
+ * Spearman(IF, contact frequency), both over the ordered pairs |i-j| >= range with average ranks on ties, either NULL, not both.  A good
+ * ensemble has rho_mean < 0 and rho_contact > 0; a constant map gives NaN as a host computation would.  The two maps are the ones
+ * c3d_ensemble_map returns for the same arguments, bit for bit (the same kernel); they and IF (n x n with the context's n) are ranked on the
+ * device by the kernels that rank IF for c3d_score_replicas.  IF must be symmetric over the ranked pairs: there is NO host ranking to fall
+ * back on here, an asymmetric matrix is C3D_ERR_INVALID.
+ * No state of the solve changes in either call (the guarantee of c3d_compare_replicas).
+ * C3D_ERR_INVALID, before any launch: no replicas, n < 2, n_extra < 0 or extra models without coordinates, K > C3D_COMPARE_MAX_MODELS,
+ * n_pick < 0, a list without a length or a length without a list, a pick index outside 0..K-1, more than 4096 picks, every output NULL,
+ * extra coordinates that are not finite or have |x| >= 1e6, contact / rho_contact wanted with a cutoff that is not finite or <= 0,
+ * range < 1 or a range that leaves no pairs, no IF.  C3D_ERR_NOMEM: no device memory for the scratch.
+ * Scratch, one allocation per call, freed before it returns: 24 n bytes per model, 4 bytes per pick and 8 n^2 bytes for each matrix the
+ * call needs — the map those that were asked for: 5 MB + 0.2 MB at 455 beads x 20 models, 6 GiB + 8 MB at 16384 x 20 with all three; the
+ * score two at every size (IF's ranks, and one slot that holds the mean and then the contact map), and 8 bytes per sort slot (the ranked
+ * pairs i < j rounded up to a power of two, 4096 at least): 3.3 MB + 1 MB + 0.2 MB at 455 x 20, 4 GiB + 1 GiB + 8 MB at 16384 x 20.
+ * Stats "ensemble_map_runs" and "ensemble_score_runs" count the calls that completed. */
+int c3d_ensemble_map(c3d_ctx* ctx, const double* extra_xyz, int n_extra, const int32_t* pick, int n_pick, double cutoff,
+                     double* mean, double* sd, double* contact);
+int c3d_ensemble_score(c3d_ctx* ctx, const double* IF, int range, const double* extra_xyz, int n_extra,
+                       const int32_t* pick, int n_pick, double cutoff, double* rho_mean, double* rho_contact);
 /* rank[k] = replica index with the k-th lowest int(E_noe) (chromosome3D.pl:796-802,822-828);
  * ties broken by replica id. */
 int c3d_rank(c3d_ctx* ctx, int32_t* rank);

@@ -91,6 +91,12 @@ static void api_storm(int device_count) {
                 ok = ok && c3d_score_replicas(c, IF.data(), 3, sat.data(), dev.data(), rho.data()) == C3D_OK;
                 std::vector<double> sim(16), rmsd(16);
                 ok = ok && c3d_compare_replicas(c, nullptr, 0, sim.data(), rmsd.data()) == C3D_OK;
+                std::vector<double> emap(3 * (size_t)n * n);
+                const int32_t picked[3] = {3, 0, 0};
+                double erho[2];
+                ok = ok && c3d_ensemble_map(c, nullptr, 0, picked, 3, 7.6, emap.data(), emap.data() + (size_t)n * n, emap.data() + 2 * (size_t)n * n) == C3D_OK;
+                ok = ok && c3d_ensemble_score(c, IF.data(), 3, nullptr, 0, nullptr, 0, 7.6, &erho[0], &erho[1]) == C3D_OK;
+                ok = ok && c3d_ensemble_map(c, nullptr, 0, picked, 0, 7.6, emap.data(), nullptr, nullptr) == C3D_ERR_INVALID;
                 if (what == 2) { unsigned long long a, b, d; ok = ok && c3d_debug_tear16(c, 4, &a, &b, &d) == C3D_OK; }
             }
             if (!ok) { fprintf(stderr, "api storm thread %d: %s\n", t, c3d_last_error()); ++failures; }

@@ -278,4 +278,38 @@ hipError_t launch_superpose_mean(const double*, int K, int n, double* mean, doub
 hipError_t launch_superpose_store32(const double*, int, int, int, float*, hipStream_t) { LaunchScope ls; return hipSuccess; }
 hipError_t launch_superpose_store64(const double*, int, int, int, double*, double*, hipStream_t) { LaunchScope ls; return hipSuccess; }
 
+// c3d_ensemble_map / c3d_ensemble_score: the map restated on the host over the "device" memory, which is the host's here
+hipError_t launch_ensemble_map(const double* xyz, int n, const int* pick, int Kp, double cutoff, double* mean, double* sd, double* contact, hipStream_t) {
+    LaunchScope ls;
+    std::vector<double> d((size_t)Kp);
+    for (int i = 0; i < n; ++i)
+        for (int j = i; j < n; ++j) {
+            double sum = 0, dev = 0;
+            int cnt = 0;
+            for (int k = 0; k < Kp; ++k) {
+                const double* x = xyz + (size_t)pick[k] * 3 * n;
+                const double ux = x[3 * i] - x[3 * j], uy = x[3 * i + 1] - x[3 * j + 1], uz = x[3 * i + 2] - x[3 * j + 2];
+                d[(size_t)k] = sqrt(((ux * ux) + uy * uy) + uz * uz);
+                sum += d[(size_t)k];
+                cnt += d[(size_t)k] < cutoff ? 1 : 0;
+            }
+            const double mu = sum / (double)Kp;
+            for (int k = 0; k < Kp; ++k) dev += (d[(size_t)k] - mu) * (d[(size_t)k] - mu);
+            const size_t a = (size_t)i * n + j, b = (size_t)j * n + i;
+            if (mean) mean[a] = mean[b] = mu;
+            if (sd) sd[a] = sd[b] = sqrt(dev / (double)Kp);
+            if (contact) contact[a] = contact[b] = (double)cnt / (double)Kp;
+        }
+    return hipSuccess;
+}
+hipError_t launch_ensemble_corr(const double* A, const double* B, int n, int range, double ma, double* rows, hipStream_t) {
+    LaunchScope ls;
+    for (int i = 0; i < n; ++i) {
+        rows[i] = 0;
+        for (int j = 0; j < n; ++j)
+            if ((i > j ? i - j : j - i) >= range) rows[i] += (A[(size_t)i * n + j] - ma) * (B[(size_t)i * n + j] - ma);
+    }
+    return hipSuccess;
+}
+
 }  // namespace c3d
