@@ -124,9 +124,8 @@ int drop_stale_gated(c3d_ctx* c, unsigned stale) {
 
 // fp64 target matrix from the resident integer tenths, in the encoding the current model's kernel expects (c3d_f64.hip pair64)
 int build_targets64(c3d_ctx* c) {
-    double mh[15];
-    model_host64(c, mh);
-    LAUNCH_TRY("fp64 targets", c3d::launch_targets64(dev_model(c), mh, c->model.min_sep, c->b64.t10, c->b64.T, c->stream));
+    const c3d::Model64 m = c3d::model64(dev_model(c), c->model);
+    LAUNCH_TRY("fp64 targets", c3d::launch_targets64(m, c3d::form64(m, 0.0, 0), c->b64.t10, c->b64.T, c->stream));   // (the encoding follows pot and gen alone)
     HIP_TRY(hipStreamSynchronize(c->stream));
     return C3D_OK;
 }
@@ -200,13 +199,6 @@ c3d::DevStep dev_step(const c3d_ctx* c, int kind, float dt, float w_all, float w
     p.kq = p.w_rs != 0.0f ? p.w_rep4r2 / p.w_rs : 0.0f;
     p.t_bath = t_bath;
     return p;
-}
-
-void model_host64(const c3d_ctx* c, double (&mh)[15]) {
-    const c3d_model& h = c->model;
-    const double v[15] = {h.s_noe, h.rswitch, h.asym, h.masym, h.mrswitch, h.k_bond, h.b0, h.k_ang, h.a0, h.r0_rep, h.k_rep, h.mass, h.fbeta,
-                          (double)h.min_sep, (double)h.msoexp};
-    for (int k = 0; k < 15; ++k) mh[k] = v[k];
 }
 
 // Read-backs (exit test of the minimiser, coordinates, energies, scoring sums) land in a pinned buffer the context owns: the runtime does not
@@ -1088,16 +1080,15 @@ extern "C" int c3d_eval_f64(c3d_ctx* c, double w_all, double w_vdw, double repel
     const size_t n3 = (size_t)c->nrep * 3 * c3d::cols64(c->n);
     if (!c->b64.F) HIP_TRY(hipMalloc(&c->b64.F, sizeof(double) * (n3 + 4 * (size_t)c->nrep)));
     const c3d::DevModel m = dev_model(c);
-    double mh[15];
-    model_host64(c, mh);
+    const c3d::Model64 m64 = c3d::model64(m, c->model);
     if (F) {
-        const double sh[6] = {3.0, 0.0, w_all, w_vdw, repel_s, 0.0};
-        LAUNCH_TRY("fp64 eval launch", c3d::launch_eval_forces64(m, mh, sh, c->b64, c->parity, c->f64_column_chunk, c->b64.F, c->stream));
+        const c3d::Step64 p = c3d::step64(m64, 3, 0.0, w_all, w_vdw, repel_s, 0.0);
+        LAUNCH_TRY("fp64 eval launch", c3d::launch_eval_forces64(m, m64, p, c3d::form64(m64, w_all, c->f64_column_chunk), c->b64, c->parity, c->b64.F, c->stream));
         if (int rc = get_soa64(c, c->b64.F, F)) return rc;
     }
     if (e) {
         const double rr = repel_s * (double)c->model.r0_rep;
-        LAUNCH_TRY("fp64 energy launch", c3d::launch_energy64(m, mh, rr * rr, c->b64, c->parity, c->b64.F + n3, c->stream));
+        LAUNCH_TRY("fp64 energy launch", c3d::launch_energy64(m, m64, rr * rr, c->b64, c->parity, c->b64.F + n3, c->stream));
         if (int rc = read_back(c, c->b64.F + n3, sizeof(double) * 4 * (size_t)c->nrep)) return rc;
         const double* h = static_cast<const double*>(c->h_stage);
         for (int r = 0; r < c->nrep; ++r) for (int k = 0; k < 3; ++k) e[3 * r + k] = h[4 * r + k];

@@ -63,7 +63,6 @@ void dev_free(T*& p) {
 // ---- c3d_api.cpp: the context's configuration as the kernels take it, the pinned stage of the read-backs
 c3d::DevModel dev_model(const c3d_ctx* c);
 c3d::DevStep dev_step(const c3d_ctx* c, int kind, float dt, float w_all, float w_vdw, float repel_s, float t_bath);
-void model_host64(const c3d_ctx* c, double (&mh)[15]);
 int ensure_stage(c3d_ctx* c, size_t bytes);
 int read_back(c3d_ctx* c, const void* dev, size_t bytes);        // device -> c->h_stage, synchronised
 

@@ -26,28 +26,6 @@
 
 namespace c3d {
 
-struct Model64 {
-    int n, np, ntiles, min_sep, noe_pot, rep_sep, ang_mode, mexp;      // noe_pot as DevModel's (4 = the fast soft lower side)
-    double s_noe, rs, tail_c, tail_b, mrs, mtail_c, mtail_b;
-    double k_bond, b0, k_ang, a0, r0_rep, k_rep, mass, fbeta;
-    double nmrs4;                                  // -mrs^4 (the fast soft lower side's bound is nmrs4 / D^3)
-    double t_fac, inv_n;                           // T = t_fac * sum v^2; 1 / n
-};
-struct Step64 {
-    int kind;
-    double dt, w_all, w_vdw, repel_s, t_bath;
-    // uniform factors of a step, formed on the host (fp64 has no scalar ALU: formed in the kernel they are vector registers every wave
-    // holds through its pair loop): R2 = (repel_s r0_rep)^2, wr4 = 4 w_vdw k_rep, nws4 = -4 w_all S, wq = wr4 / nws4 (0 where nws4 = 0)
-    double R2, wr4, nws4, wq;
-    double acc;        // MD: dt kAccel / mass (the kernel's own division was ~30 fp64 operations on every wave's path after its pair loop)
-    double kb4, ka4;   // chain terms: -4 w_all k_bond, -4 w_all k_ang
-    double kacc;       // kAccel / mass (FIRE: times the step's dt)
-    double a0sq;       // a0^2
-};
-struct Fire64 {
-    double dt_start, dt_max, f_inc, f_dec, alpha_start, f_alpha, max_step;
-    int n_min;
-};
 struct FireState64 {
     double dt, alpha;
     int npos, pad;
@@ -569,37 +547,29 @@ __global__ __launch_bounds__(256) void k64_export(int n, int npad, int np, int n
     for (int t = threadIdx.x; t < 4 * ntiles; t += 256) Pf[(size_t)rep * ntiles * 4 + t] = (float)P[(size_t)rep * ntiles * 4 + t];
 }
 
-template <class F> static hipError_t with_chunk64(int chunk, F&& f) {      // the instantiated set (column_chunk64_valid)
-    switch (chunk) {
-        case 256: return f(int_c<256>{});
-        case 512: return f(int_c<512>{});
-        case 1024: return f(int_c<1024>{});
-        default: return hipErrorInvalidValue;
-    }
-}
-
 // ---- host side ---------------------------------------------------------------------------------------
 int cols64(int n) { return (n + kColPad64 - 1) / kColPad64 * kColPad64; }
 size_t fire_state64_bytes() { return sizeof(FireState64); }
 
-static Model64 model64(const DevModel& d, const double* host) {
-    // host[]: s_noe, rswitch, asym, masym, mrswitch, k_bond, b0, k_ang, a0, r0_rep, k_rep, mass, fbeta, min_sep, msoexp
+// The builders of the kernel arguments (c3d_internal.h): the only place a derived fp64 parameter is formed.
+Model64 model64(const DevModel& d, const c3d_model& h) {
     Model64 m;
     m.n = d.n; m.np = cols64(d.n); m.ntiles = d.ntiles;
-    m.min_sep = (int)host[13]; m.noe_pot = d.noe_pot; m.rep_sep = d.rep_sep; m.ang_mode = d.ang_mode; m.mexp = (int)host[14] == 2 ? 2 : 1;
-    m.s_noe = host[0]; m.rs = host[1];
-    m.tail_c = host[2] * host[1]; m.tail_b = (m.tail_c - 2.0 * m.rs) * m.rs * m.rs;
+    m.min_sep = h.min_sep; m.rep_sep = d.rep_sep; m.ang_mode = d.ang_mode; m.mexp = h.msoexp == 2 ? 2 : 1;
+    m.s_noe = h.s_noe; m.rs = h.rswitch;
+    m.tail_c = (double)h.asym * m.rs; m.tail_b = (m.tail_c - 2.0 * m.rs) * m.rs * m.rs;
     // lower side beyond mrs: dE/dD = mtail_c - mtail_b / D^(mexp + 1)
-    m.mrs = host[4]; m.mtail_c = host[3]; m.mtail_b = (m.mtail_c - 2.0 * m.mrs) * m.mrs * m.mrs * (m.mexp == 2 ? m.mrs : 1.0);
+    m.mrs = h.mrswitch; m.mtail_c = h.masym; m.mtail_b = (m.mtail_c - 2.0 * m.mrs) * m.mrs * m.mrs * (m.mexp == 2 ? m.mrs : 1.0);
     m.nmrs4 = -(m.mrs * m.mrs) * (m.mrs * m.mrs);
-    m.noe_pot = form64(d.noe_pot, host, 0.0).pot;
-    m.k_bond = host[5]; m.b0 = host[6]; m.k_ang = host[7]; m.a0 = host[8]; m.r0_rep = host[9]; m.k_rep = host[10]; m.mass = host[11]; m.fbeta = host[12];
+    // the device potential that runs (form64 reads it); a potential 4 whose doubles are not the fast form's would run as 3 (cannot happen)
+    m.noe_pot = d.noe_pot == 4 && !(m.mexp == 2 && m.mtail_c == 0.0 && m.tail_b == 0.0 && m.tail_c == 2.0 * m.rs) ? 3 : device_pot(d.noe_pot);
+    m.k_bond = h.k_bond; m.b0 = h.b0; m.k_ang = h.k_ang; m.a0 = h.a0; m.r0_rep = h.r0_rep; m.k_rep = h.k_rep; m.mass = h.mass; m.fbeta = h.fbeta;
     { const int ndf = 3 * d.n - 3; m.t_fac = m.mass / kAccel64 / ((ndf > 0 ? ndf : 1) * kBoltz64); m.inv_n = 1.0 / d.n; }
     return m;
 }
-static Step64 step64(const Model64& m, const double* step_host) {
-    Step64 p;   // step_host[]: kind, dt, w_all, w_vdw, repel_s, t_bath
-    p.kind = (int)step_host[0]; p.dt = step_host[1]; p.w_all = step_host[2]; p.w_vdw = step_host[3]; p.repel_s = step_host[4]; p.t_bath = step_host[5];
+Step64 step64(const Model64& m, int kind, double dt, double w_all, double w_vdw, double repel_s, double t_bath) {
+    Step64 p;
+    p.kind = kind; p.dt = dt; p.w_all = w_all; p.w_vdw = w_vdw; p.repel_s = repel_s; p.t_bath = t_bath;
     p.R2 = (p.repel_s * m.r0_rep) * (p.repel_s * m.r0_rep);
     p.wr4 = p.w_vdw * m.k_rep * 4.0;
     p.nws4 = -4.0 * p.w_all * m.s_noe;
@@ -610,121 +580,98 @@ static Step64 step64(const Model64& m, const double* step_host) {
     p.a0sq = m.a0 * m.a0;
     return p;
 }
-static Fire64 fire64(const double* fire_host, int fire_n_min) {
+Fire64 fire64(const c3d_fire_params& f) {
     Fire64 fp;
-    fp.dt_start = fire_host[0]; fp.dt_max = fire_host[1]; fp.f_inc = fire_host[2]; fp.f_dec = fire_host[3]; fp.alpha_start = fire_host[4];
-    fp.f_alpha = fire_host[5]; fp.max_step = fire_host[6]; fp.n_min = fire_n_min;
+    fp.dt_start = f.dt_start; fp.dt_max = f.dt_max; fp.f_inc = f.f_inc; fp.f_dec = f.f_dec; fp.alpha_start = f.alpha_start;
+    fp.f_alpha = f.f_alpha; fp.max_step = f.max_step; fp.n_min = f.n_min;
     return fp;
 }
-hipError_t launch_step64(const DevModel& d, const double* model_host, const double* step_host, const double* fire_host, int fire_n_min,
-                         const Buffers64& b, int parity, int column_chunk, hipStream_t s) {
-    const Model64 m = model64(d, model_host);
-    const Step64 p = step64(m, step_host);
-    const Fire64 fp = fire64(fire_host, fire_n_min);
-    const int q = parity ^ 1;
-    const dim3 grid(d.ntiles, d.nrep_g), blk(kBlock64);
-    const size_t lds = sizeof(double) * ((size_t)3 * m.np + 4 * kTileRows + 8);
-    FireState64* sin = reinterpret_cast<FireState64*>(b.S[parity]);
-    FireState64* sout = reinterpret_cast<FireState64*>(b.S[q]);
-    const Form64 f = form64(d.noe_pot, model_host, p.w_all, d.n, column_chunk);
+
+// The one runtime -> template dispatch of the force kernels (k64_step, k64_lbfgs_eval, k64_eval_forces and their chunked forms): fn is
+// called with POT, GEN, FOLD, CHUNK as integral constants, CHUNK 0 = staged, else one of the instantiated set (column_chunk64_valid).
+// The general forms have no potential-4 kernel (form64 never asks for one), and FOLD exists for the fast soft lower side only.
+template <class Fn> static hipError_t with_form64(const Form64& f, Fn&& fn) {
     return with_pot(f.pot, [&](auto P) {
         return with_bool(f.gen, [&](auto G) {
             return with_bool(f.fold, [&](auto F) {
-                constexpr int POT = G && P == 4 ? 2 : P;            // (the general forms have no potential-4 kernel: form64 never asks for one)
+                constexpr int POT = G && P == 4 ? 2 : P;
                 constexpr bool FOLD = F && POT == 4 && !G;
-                if (f.chunk == 0) {
-                    hipLaunchKernelGGL((k64_step<POT, G, FOLD>), grid, blk, lds, s, m, p, fp, d.rep_base, b.T, b.X[parity], b.V[parity], b.Vinit, b.P[parity],
-                                       sin, b.X[q], b.V[q], b.P[q], sout);
-                    return hipGetLastError();
+                switch (f.chunk) {
+                    case 0: return fn(int_c<POT>{}, G, bool_c<FOLD>{}, int_c<0>{});
+                    case 256: return fn(int_c<POT>{}, G, bool_c<FOLD>{}, int_c<256>{});
+                    case 512: return fn(int_c<POT>{}, G, bool_c<FOLD>{}, int_c<512>{});
+                    case 1024: return fn(int_c<POT>{}, G, bool_c<FOLD>{}, int_c<1024>{});
+                    default: return hipErrorInvalidValue;
                 }
-                return with_chunk64(f.chunk, [&](auto C) {
-                    const size_t ldsc = sizeof(double) * ((size_t)6 * C + 4 * kTileRows + 8);
-                    hipLaunchKernelGGL((k64_step_chunked<POT, G, FOLD, C>), grid, blk, ldsc, s, m, p, fp, d.rep_base, b.T, b.X[parity], b.V[parity], b.Vinit,
-                                       b.P[parity], sin, b.X[q], b.V[q], b.P[q], sout);
-                    return hipGetLastError();
-                });
             });
         });
     });
 }
-// launch_step64's form (form64: staged up to 2560 beads, chunked beyond or where f64_column_chunk asks), with the kernel of an L-BFGS
-// evaluation: reads X[parity] and the previous force V[parity], writes the force V[parity^1], ring slot and tile sums
-hipError_t launch_lbfgs_eval64(const DevModel& d, const double* model_host, const double* step_host, const Buffers64& b, const LbfgsBuffers64& lb,
-                               int parity, int mem, int column_chunk, hipStream_t s) {
-    if (mem < 1 || mem > kLbfgsMaxPairs) return hipErrorInvalidValue;
-    const Model64 m = model64(d, model_host);
-    const Step64 p = step64(m, step_host);
+// doubles of LDS the columns take: the replica's three coordinate rows staged whole, or two buffers of 3 CHUNK
+static size_t cols_lds64(const Model64& m, int chunk) { return chunk ? (size_t)6 * chunk : (size_t)3 * m.np; }
+
+hipError_t launch_step64(const DevModel& d, const Model64& m, const Step64& p, const Fire64& fp, const Form64& f, const Buffers64& b, int parity,
+                         hipStream_t s) {
     const int q = parity ^ 1;
     const dim3 grid(d.ntiles, d.nrep_g), blk(kBlock64);
-    const size_t rowq = (size_t)kLbfgsQ * kTileRows;
-    const Form64 f = form64(d.noe_pot, model_host, p.w_all, d.n, column_chunk);
-    return with_pot(f.pot, [&](auto P) {
-        return with_bool(f.gen, [&](auto G) {
-            return with_bool(f.fold, [&](auto F) {
-                constexpr int POT = G && P == 4 ? 2 : P;            // (as launch_step64)
-                constexpr bool FOLD = F && POT == 4 && !G;
-                if (f.chunk == 0) {
-                    hipLaunchKernelGGL((k64_lbfgs_eval<POT, G, FOLD>), grid, blk, sizeof(double) * ((size_t)3 * m.np + rowq), s, m, p, d.rep_base, b.T,
-                                       b.X[parity], b.V[parity], b.V[q], lb.hist, lb.part, lb.S[parity], mem);
-                    return hipGetLastError();
-                }
-                return with_chunk64(f.chunk, [&](auto C) {
-                    hipLaunchKernelGGL((k64_lbfgs_eval_chunked<POT, G, FOLD, C>), grid, blk, sizeof(double) * ((size_t)6 * C + rowq), s, m, p, d.rep_base,
-                                       b.T, b.X[parity], b.V[parity], b.V[q], lb.hist, lb.part, lb.S[parity], mem);
-                    return hipGetLastError();
-                });
-            });
-        });
+    const size_t lds = sizeof(double) * (cols_lds64(m, f.chunk) + 4 * kTileRows + 8);
+    FireState64* sin = reinterpret_cast<FireState64*>(b.S[parity]);
+    FireState64* sout = reinterpret_cast<FireState64*>(b.S[q]);
+    return with_form64(f, [&](auto POT, auto GEN, auto FOLD, auto CHUNK) {
+        if constexpr (CHUNK == 0)
+            hipLaunchKernelGGL((k64_step<POT, GEN, FOLD>), grid, blk, lds, s, m, p, fp, d.rep_base, b.T, b.X[parity], b.V[parity], b.Vinit, b.P[parity],
+                               sin, b.X[q], b.V[q], b.P[q], sout);
+        else
+            hipLaunchKernelGGL((k64_step_chunked<POT, GEN, FOLD, CHUNK>), grid, blk, lds, s, m, p, fp, d.rep_base, b.T, b.X[parity], b.V[parity], b.Vinit,
+                               b.P[parity], sin, b.X[q], b.V[q], b.P[q], sout);
+        return hipGetLastError();
+    });
+}
+// The kernel of an L-BFGS evaluation in the step's form (staged up to 2560 beads, chunked beyond or where f64_column_chunk asks): reads
+// X[parity] and the previous force V[parity], writes the force V[parity^1], ring slot and tile sums
+hipError_t launch_lbfgs_eval64(const DevModel& d, const Model64& m, const Step64& p, const Form64& f, const Buffers64& b, const LbfgsBuffers64& lb,
+                               int parity, int mem, hipStream_t s) {
+    if (mem < 1 || mem > kLbfgsMaxPairs) return hipErrorInvalidValue;
+    const int q = parity ^ 1;
+    const dim3 grid(d.ntiles, d.nrep_g), blk(kBlock64);
+    const size_t lds = sizeof(double) * (cols_lds64(m, f.chunk) + (size_t)kLbfgsQ * kTileRows);
+    return with_form64(f, [&](auto POT, auto GEN, auto FOLD, auto CHUNK) {
+        if constexpr (CHUNK == 0)
+            hipLaunchKernelGGL((k64_lbfgs_eval<POT, GEN, FOLD>), grid, blk, lds, s, m, p, d.rep_base, b.T, b.X[parity], b.V[parity], b.V[q], lb.hist,
+                               lb.part, lb.S[parity], mem);
+        else
+            hipLaunchKernelGGL((k64_lbfgs_eval_chunked<POT, GEN, FOLD, CHUNK>), grid, blk, lds, s, m, p, d.rep_base, b.T, b.X[parity], b.V[parity], b.V[q],
+                               lb.hist, lb.part, lb.S[parity], mem);
+        return hipGetLastError();
     });
 }
 // the move that follows it: X[parity] -> X[parity^1], P[parity^1], the state S[parity] -> S[parity^1]
-hipError_t launch_lbfgs_move64(const DevModel& d, const double* model_host, const double* step_host, const double* fire_host, int fire_n_min,
-                               const Buffers64& b, const LbfgsBuffers64& lb, int parity, int mem, hipStream_t s) {
+hipError_t launch_lbfgs_move64(const DevModel& d, const Model64& m, const Step64& p, const Fire64& fp, const Buffers64& b, const LbfgsBuffers64& lb,
+                               int parity, int mem, hipStream_t s) {
     if (mem < 1 || mem > kLbfgsMaxPairs) return hipErrorInvalidValue;
-    const Model64 m = model64(d, model_host);
-    const Step64 p = step64(m, step_host);
-    const Fire64 fp = fire64(fire_host, fire_n_min);
     const int q = parity ^ 1;
     hipLaunchKernelGGL(k64_lbfgs_move, dim3((d.n + kLbfgsMoveRows64 - 1) / kLbfgsMoveRows64, d.nrep_g), dim3(kLbfgsMoveRows64), 0, s, m, p, fp,
                        d.rep_base, b.X[parity], b.X[q], b.V[q], lb.hist, lb.part, b.P[q], lb.S[parity], lb.S[q], mem);
     return hipGetLastError();
 }
-// c3d_eval_f64's force: launch_step64's form from the doubles launch_step64 would form (step_host's kind is ignored: 3), X[parity] -> Fout
-hipError_t launch_eval_forces64(const DevModel& d, const double* model_host, const double* step_host, const Buffers64& b, int parity,
-                                int column_chunk, double* Fout, hipStream_t s) {
-    const Model64 m = model64(d, model_host);
-    Step64 p = step64(m, step_host);
-    p.kind = 3;
+// c3d_eval_f64's force in the step's form (p of kind 3), X[parity] -> Fout
+hipError_t launch_eval_forces64(const DevModel& d, const Model64& m, const Step64& p, const Form64& f, const Buffers64& b, int parity, double* Fout,
+                                hipStream_t s) {
     const dim3 grid(d.ntiles, d.nrep_g), blk(kBlock64);
-    const Form64 f = form64(d.noe_pot, model_host, p.w_all, d.n, column_chunk);
-    return with_pot(f.pot, [&](auto P) {
-        return with_bool(f.gen, [&](auto G) {
-            return with_bool(f.fold, [&](auto F) {
-                constexpr int POT = G && P == 4 ? 2 : P;            // (as launch_step64)
-                constexpr bool FOLD = F && POT == 4 && !G;
-                if (f.chunk == 0) {
-                    hipLaunchKernelGGL((k64_eval_forces<POT, G, FOLD>), grid, blk, sizeof(double) * (size_t)3 * m.np, s, m, p, d.rep_base, b.T,
-                                       b.X[parity], Fout);
-                    return hipGetLastError();
-                }
-                return with_chunk64(f.chunk, [&](auto C) {
-                    hipLaunchKernelGGL((k64_eval_forces_chunked<POT, G, FOLD, C>), grid, blk, sizeof(double) * (size_t)6 * C, s, m, p, d.rep_base,
-                                       b.T, b.X[parity], Fout);
-                    return hipGetLastError();
-                });
-            });
-        });
+    const size_t lds = sizeof(double) * cols_lds64(m, f.chunk);
+    return with_form64(f, [&](auto POT, auto GEN, auto FOLD, auto CHUNK) {
+        if constexpr (CHUNK == 0) hipLaunchKernelGGL((k64_eval_forces<POT, GEN, FOLD>), grid, blk, lds, s, m, p, d.rep_base, b.T, b.X[parity], Fout);
+        else hipLaunchKernelGGL((k64_eval_forces_chunked<POT, GEN, FOLD, CHUNK>), grid, blk, lds, s, m, p, d.rep_base, b.T, b.X[parity], Fout);
+        return hipGetLastError();
     });
 }
-hipError_t launch_energy64(const DevModel& d, const double* model_host, double rep_r2, const Buffers64& b, int parity, double* Eout, hipStream_t s) {
-    const Model64 m = model64(d, model_host);
+hipError_t launch_energy64(const DevModel& d, const Model64& m, double rep_r2, const Buffers64& b, int parity, double* Eout, hipStream_t s) {
     hipLaunchKernelGGL(k64_energy, dim3(d.nrep), dim3(256), 0, s, m, rep_r2, b.T, b.X[parity], Eout);
     return hipGetLastError();
 }
-hipError_t launch_targets64(const DevModel& d, const double* model_host, int min_sep, const int32_t* t10, double* T, hipStream_t s) {
-    const Form64 f = form64(d.noe_pot, model_host, 0.0);
+hipError_t launch_targets64(const Model64& m, const Form64& f, const int32_t* t10, double* T, hipStream_t s) {
     const double none = (f.pot == 4 && !f.gen) ? kNoTarget64 : 0.0;        // what pair64 of the kernel that will run expects
-    hipLaunchKernelGGL(k64_targets, dim3(d.n), dim3(256), 0, s, d.n, cols64(d.n), min_sep, none, t10, T);
+    hipLaunchKernelGGL(k64_targets, dim3(m.n), dim3(256), 0, s, m.n, m.np, m.min_sep, none, t10, T);
     return hipGetLastError();
 }
 hipError_t launch_tenths64(int n, int R, const int32_t* ri, const int32_t* rj, const int32_t* rt10, int32_t* t10, hipStream_t s) {

@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <type_traits>
 
+#include "../../include/c3d.h"
 #include "c3d_superpose.h"
 
 namespace c3d {
@@ -251,8 +252,6 @@ hipError_t launch_step_sym(const DevModel& m, const DevStep& p, const DevFire& f
                            float* scratch, hipStream_t s);
 // fp64 step (c3d_f64.hip, option "precision" = 64): the CPU restatement's algorithm in its precision on the GPU, one launch per SA
 // step of a replica group (k64_step, k64_step_chunked beyond 2560 beads), double buffered by step parity like the fp32 per-step path.
-// model_host[15] = s_noe, rswitch, asym, masym, mrswitch, k_bond, b0, k_ang, a0, r0_rep, k_rep, mass, fbeta, min_sep, msoexp;
-// step_host[6] = kind, dt, w_all, w_vdw, repel_s, t_bath; fire_host[7] = dt_start, dt_max, f_inc, f_dec, alpha_start, f_alpha, max_step.
 // Layouts (np = cols64(n): n rounded up to 128): T [n][np] targets in Angstrom (0.1 * t10, 0 = none); X, V [2][nrep][3][np] SoA;
 // Vinit [nrep][3][np]; P [2][nrep][ntiles][4] per-tile sums; S [2][nrep] x fire_state64_bytes().
 struct Buffers64 {
@@ -276,28 +275,53 @@ inline int column_chunk64_for(int n, int option) {
     if (option > 0) return n > option ? option : 0;
     return n <= kMaxStagedBeads64 ? 0 : kDefaultColumnChunk64;
 }
-// k64_step<pot, gen, fold>'s / k64_step_chunked<pot, gen, fold, chunk>'s form, decided in doubles over the fp64 model (model_host, below)
-// for the launch, the target encoding and c3d_step_kernel_name alike: gen = a general tail, fold = the fast soft lower side (device
-// potential 4) at a restraint weight w_all != 0, chunk = column_chunk64_for(n, the context's f64_column_chunk) (0 = staged)
+// The kernel arguments of the fp64 path, built once per op by the host units (launch_op, c3d_eval_f64, build_targets64) and passed on as they
+// are.  The builders are defined in c3d_f64.hip, the unit compiled with -ffp-contract=off: every derived double (the tails, nmrs4, t_fac; a
+// step's R2, wr4, nws4, wq, acc, kb4, ka4, ...) is formed there, in one expression order.  d carries the geometry and the device potential.
+struct Model64 {
+    int n, np, ntiles, min_sep, noe_pot, rep_sep, ang_mode, mexp;      // noe_pot as DevModel's (4 = the fast soft lower side)
+    double s_noe, rs, tail_c, tail_b, mrs, mtail_c, mtail_b;
+    double k_bond, b0, k_ang, a0, r0_rep, k_rep, mass, fbeta;
+    double nmrs4;                                  // -mrs^4 (the fast soft lower side's bound is nmrs4 / D^3)
+    double t_fac, inv_n;                           // T = t_fac * sum v^2; 1 / n
+};
+struct Step64 {
+    int kind;
+    double dt, w_all, w_vdw, repel_s, t_bath;
+    // uniform factors of a step, formed on the host (fp64 has no scalar ALU: formed in the kernel they are vector registers every wave
+    // holds through its pair loop): R2 = (repel_s r0_rep)^2, wr4 = 4 w_vdw k_rep, nws4 = -4 w_all S, wq = wr4 / nws4 (0 where nws4 = 0)
+    double R2, wr4, nws4, wq;
+    double acc;        // MD: dt kAccel / mass (the kernel's own division was ~30 fp64 operations on every wave's path after its pair loop)
+    double kb4, ka4;   // chain terms: -4 w_all k_bond, -4 w_all k_ang
+    double kacc;       // kAccel / mass (FIRE: times the step's dt)
+    double a0sq;       // a0^2
+};
+struct Fire64 {
+    double dt_start, dt_max, f_inc, f_dec, alpha_start, f_alpha, max_step;
+    int n_min;
+};
+Model64 model64(const DevModel& d, const c3d_model& h);
+Step64 step64(const Model64& m, int kind, double dt, double w_all, double w_vdw, double repel_s, double t_bath);   // a stage's values, as doubles
+Fire64 fire64(const c3d_fire_params& f);
+// k64_step<pot, gen, fold>'s / k64_step_chunked<pot, gen, fold, chunk>'s form, decided once per op from the built Model64 (op_kernel,
+// c3d_eval_f64, build_targets64): the launch, the target encoding and c3d_step_kernel_name all read this one value.  pot = the model's
+// device potential, gen = a general tail, fold = the fast soft lower side (potential 4) at a restraint weight w_all != 0, chunk =
+// column_chunk64_for(n, the context's f64_column_chunk) (0 = staged)
 struct Form64 {
     int pot;
     bool gen, fold;
     int chunk;
 };
-inline Form64 form64(int noe_pot, const double* model_host, double w_all, int n = 0, int column_chunk = 0) {
-    const double* h = model_host;
-    const int mexp = (int)h[14] == 2 ? 2 : 1;
-    const double rs = h[1], tail_c = h[2] * h[1], tail_b = (tail_c - 2.0 * rs) * rs * rs;
-    const double mrs = h[4], mtail_c = h[3], mtail_b = (mtail_c - 2.0 * mrs) * mrs * mrs * (mexp == 2 ? mrs : 1.0);
+inline Form64 form64(const Model64& m, double w_all, int column_chunk) {
     Form64 f;
-    f.pot = noe_pot == 4 && !(mexp == 2 && mtail_c == 0.0 && tail_b == 0.0 && tail_c == 2.0 * rs) ? 3 : device_pot(noe_pot);   // (cannot happen)
-    f.gen = !(tail_b == 0.0 && tail_c == 2.0 * rs) || (f.pot == 3 && !(mtail_b == 0.0 && mtail_c == 2.0 * mrs));     // (potential 4 has a fast form of its own)
+    f.pot = m.noe_pot;
+    f.gen = !(m.tail_b == 0.0 && m.tail_c == 2.0 * m.rs) || (f.pot == 3 && !(m.mtail_b == 0.0 && m.mtail_c == 2.0 * m.mrs));     // (potential 4 has a fast form of its own)
     f.fold = f.pot == 4 && !f.gen && w_all != 0.0;
-    f.chunk = column_chunk64_for(n, column_chunk);
+    f.chunk = column_chunk64_for(m.n, column_chunk);
     return f;
 }
-hipError_t launch_step64(const DevModel& d, const double* model_host, const double* step_host, const double* fire_host, int fire_n_min,
-                         const Buffers64& b, int parity, int column_chunk, hipStream_t s);   // column_chunk: the option, 0 = by size
+hipError_t launch_step64(const DevModel& d, const Model64& m, const Step64& p, const Fire64& fp, const Form64& f, const Buffers64& b, int parity,
+                         hipStream_t s);
 // The L-BFGS stage in fp64 (option f64_lbfgs on a precision-64 context): k64_lbfgs_eval[_chunked] + k64_lbfgs_move, the layouts of the
 // fp32 stage above in doubles with np columns: hist [nrep][2: s, y][kLbfgsMaxPairs][3][np] (lbfgs_hist_floats(np) doubles a replica),
 // part [nrep][ntiles][kLbfgsQ], S [2][nrep] LbfgsState; V[parity^1] = the force of the evaluation, P[parity^1] = (move.move, F.F, 0, 0).
@@ -307,22 +331,22 @@ struct LbfgsBuffers64 {
     double* part = nullptr;
     LbfgsState* S[2] = {nullptr, nullptr};
 };
-hipError_t launch_lbfgs_eval64(const DevModel& d, const double* model_host, const double* step_host, const Buffers64& b, const LbfgsBuffers64& lb,
-                               int parity, int mem, int column_chunk, hipStream_t s);
-hipError_t launch_lbfgs_move64(const DevModel& d, const double* model_host, const double* step_host, const double* fire_host, int fire_n_min,
-                               const Buffers64& b, const LbfgsBuffers64& lb, int parity, int mem, hipStream_t s);
-hipError_t launch_targets64(const DevModel& d, const double* model_host, int min_sep, const int32_t* t10, double* T, hipStream_t s);
+hipError_t launch_lbfgs_eval64(const DevModel& d, const Model64& m, const Step64& p, const Form64& f, const Buffers64& b, const LbfgsBuffers64& lb,
+                               int parity, int mem, hipStream_t s);
+hipError_t launch_lbfgs_move64(const DevModel& d, const Model64& m, const Step64& p, const Fire64& fp, const Buffers64& b, const LbfgsBuffers64& lb,
+                               int parity, int mem, hipStream_t s);
+hipError_t launch_targets64(const Model64& m, const Form64& f, const int32_t* t10, double* T, hipStream_t s);   // in the encoding f's kernel expects
 // the integer tenths of a restraint list (R pairs, 0-based, every pair once) into the zeroed n x n matrix t10, both triangles
 hipError_t launch_tenths64(int n, int R, const int32_t* ri, const int32_t* rj, const int32_t* rt10, int32_t* t10, hipStream_t s);
 hipError_t launch_import64(const DevModel& d, const float* Xf, const Buffers64& b, hipStream_t s);
 hipError_t launch_export64(const DevModel& d, const Buffers64& b, int parity, float* Xf, float* Vf, float* Pf, hipStream_t s);
-// The forces-and-energies hook of a precision-64 context (c3d_eval_f64).  launch_eval_forces64: k64_eval_forces[_chunked] in
-// launch_step64's form (form64 over the same doubles, so a stage's weights select the instantiation family of the stage's step), the total
-// weighted force of X[parity] into Fout [nrep][3][np]: a buffer of the context's own (Buffers64::F), never the velocity slot; step_host as
-// launch_step64's (kind, dt and t_bath unused).  launch_energy64: k64_energy, Eout [nrep][4] = unweighted noe, bond + angle, repel, 0.
-hipError_t launch_eval_forces64(const DevModel& d, const double* model_host, const double* step_host, const Buffers64& b, int parity,
-                                int column_chunk, double* Fout, hipStream_t s);
-hipError_t launch_energy64(const DevModel& d, const double* model_host, double rep_r2, const Buffers64& b, int parity, double* Eout, hipStream_t s);
+// The forces-and-energies hook of a precision-64 context (c3d_eval_f64).  launch_eval_forces64: k64_eval_forces[_chunked] in the form f (a
+// stage's weights select the instantiation family of the stage's step), the total weighted force of X[parity] into Fout [nrep][3][np]: a
+// buffer of the context's own (Buffers64::F), never the velocity slot; p of kind 3 (dt and t_bath unused).  launch_energy64: k64_energy,
+// Eout [nrep][4] = unweighted noe, bond + angle, repel, 0.
+hipError_t launch_eval_forces64(const DevModel& d, const Model64& m, const Step64& p, const Form64& f, const Buffers64& b, int parity, double* Fout,
+                                hipStream_t s);
+hipError_t launch_energy64(const DevModel& d, const Model64& m, double rep_r2, const Buffers64& b, int parity, double* Eout, hipStream_t s);
 size_t fire_state64_bytes();
 // K1: IF (n*n fp64, device) -> dist10 (n*n int32, device) and encoded targets (n*npad, device)
 hipError_t launch_if_to_target(const double* IF, int n, int npad, double alpha, double K, int min_sep, int rep_sep,

@@ -159,13 +159,12 @@ int ensure_pair_targets(c3d_ctx* c, const c3d::DevModel& m) {
 }
 // The kernel an op runs on the per-step path and its form: launch_op launches what this says, run_ops_segment records it for the range's
 // last op (a graph replay does not pass through launch_op)
-KernelRecord op_kernel(const c3d_ctx* c, const c3d::DevModel& m, const Op& op) {
+// (m64: the op's fp64 model where the caller has built it, precision 64 only)
+KernelRecord op_kernel(const c3d_ctx* c, const c3d::DevModel& m, const Op& op, const c3d::Model64* m64 = nullptr) {
     KernelRecord k;
-    if (c->precision == 64) {              // launch_step64 makes the same choice from the same doubles
-        double mh[15];
-        model_host64(c, mh);
+    if (c->precision == 64) {
         k.family = is_lbfgs(op.p.kind) ? KernelRecord::LBFGS_EVAL64 : KernelRecord::STEP64;
-        k.f64 = c3d::form64(m.noe_pot, mh, c->stages[op.stage].w_all, c->n, c->f64_column_chunk);
+        k.f64 = c3d::form64(m64 ? *m64 : c3d::model64(m, c->model), c->stages[op.stage].w_all, c->f64_column_chunk);
     } else if (!is_lbfgs(op.p.kind) && use_sym(c)) {      // (symmetric tiles do not apply to L-BFGS steps)
         k.family = KernelRecord::PAIRS_SYM;
         k.pot = c3d::device_pot(m.noe_pot);
@@ -182,15 +181,15 @@ int launch_op(c3d_ctx* c, const Op& op, int g, int par) {
     group_range(c, g, m.rep_base, m.nrep_g);
     if (c->precision == 64) {              // the stage's own doubles, not the floats of DevStep
         const c3d_stage& st = c->stages[op.stage];
-        double mh[15];
-        model_host64(c, mh);
-        const double fh[7] = {c->fire.dt_start, c->fire.dt_max, c->fire.f_inc, c->fire.f_dec, c->fire.alpha_start, c->fire.f_alpha, c->fire.max_step};
-        const double sh[6] = {(double)op.p.kind, st.dt, st.w_all, st.w_vdw, st.repel_s, st.t_bath};
+        const c3d::Model64 m64 = c3d::model64(m, c->model);
+        const c3d::Step64 p = c3d::step64(m64, op.p.kind, st.dt, st.w_all, st.w_vdw, st.repel_s, st.t_bath);
+        const c3d::Fire64 fp = c3d::fire64(c->fire);
+        const c3d::Form64 f = op_kernel(c, m, op, &m64).f64;
         if (is_lbfgs(op.p.kind)) {         // two launches, as in fp32: forces + tile sums, then sums + direction + move
-            hipError_t e = c3d::launch_lbfgs_eval64(m, mh, sh, c->b64, c->lb64, par, c->lbfgs_mem, c->f64_column_chunk, c->gstream[g]);
-            if (e == hipSuccess) e = c3d::launch_lbfgs_move64(m, mh, sh, fh, c->fire.n_min, c->b64, c->lb64, par, c->lbfgs_mem, c->gstream[g]);
+            hipError_t e = c3d::launch_lbfgs_eval64(m, m64, p, f, c->b64, c->lb64, par, c->lbfgs_mem, c->gstream[g]);
+            if (e == hipSuccess) e = c3d::launch_lbfgs_move64(m, m64, p, fp, c->b64, c->lb64, par, c->lbfgs_mem, c->gstream[g]);
             LAUNCH_TRY("fp64 L-BFGS step launch", e);
-        } else LAUNCH_TRY("fp64 step launch", c3d::launch_step64(m, mh, sh, fh, c->fire.n_min, c->b64, par, c->f64_column_chunk, c->gstream[g]));
+        } else LAUNCH_TRY("fp64 step launch", c3d::launch_step64(m, m64, p, fp, f, c->b64, par, c->gstream[g]));
         return C3D_OK;
     }
     const KernelRecord k = op_kernel(c, m, op);

@@ -161,15 +161,18 @@ size_t sym_scratch_floats(const DevModel& m) { return (size_t)m.npad * 8; }
 void sym_tile_list(const DevModel&, int2* out) { out[0].x = 0; out[0].y = 0; }
 hipError_t launch_step_sym(const DevModel&, const DevStep&, const DevFire&, const DevBuffers&, int, const void*, float*, hipStream_t) { LaunchScope ls; return hipSuccess; }
 int cols64(int n) { return (n + 127) / 128 * 128; }
-hipError_t launch_step64(const DevModel&, const double*, const double*, const double*, int, const Buffers64&, int, int, hipStream_t) { LaunchScope ls; return hipSuccess; }
-hipError_t launch_lbfgs_eval64(const DevModel&, const double*, const double*, const Buffers64&, const LbfgsBuffers64&, int, int, int, hipStream_t) { LaunchScope ls; return hipSuccess; }
-hipError_t launch_lbfgs_move64(const DevModel&, const double*, const double*, const double*, int, const Buffers64&, const LbfgsBuffers64&, int, int, hipStream_t) { LaunchScope ls; return hipSuccess; }
+Model64 model64(const DevModel& d, const c3d_model&) { Model64 m{}; m.n = d.n; m.noe_pot = device_pot(d.noe_pot); return m; }   // (what form64 reads; no kernel runs here)
+Step64 step64(const Model64&, int, double, double, double, double, double) { return Step64{}; }
+Fire64 fire64(const c3d_fire_params&) { return Fire64{}; }
+hipError_t launch_step64(const DevModel&, const Model64&, const Step64&, const Fire64&, const Form64&, const Buffers64&, int, hipStream_t) { LaunchScope ls; return hipSuccess; }
+hipError_t launch_lbfgs_eval64(const DevModel&, const Model64&, const Step64&, const Form64&, const Buffers64&, const LbfgsBuffers64&, int, int, hipStream_t) { LaunchScope ls; return hipSuccess; }
+hipError_t launch_lbfgs_move64(const DevModel&, const Model64&, const Step64&, const Fire64&, const Buffers64&, const LbfgsBuffers64&, int, int, hipStream_t) { LaunchScope ls; return hipSuccess; }
 hipError_t launch_tenths64(int, int, const int32_t*, const int32_t*, const int32_t*, int32_t*, hipStream_t) { LaunchScope ls; return hipSuccess; }
-hipError_t launch_targets64(const DevModel&, const double*, int, const int32_t*, double*, hipStream_t) { LaunchScope ls; return hipSuccess; }
+hipError_t launch_targets64(const Model64&, const Form64&, const int32_t*, double*, hipStream_t) { LaunchScope ls; return hipSuccess; }
 hipError_t launch_import64(const DevModel&, const float*, const Buffers64&, hipStream_t) { LaunchScope ls; return hipSuccess; }
 hipError_t launch_export64(const DevModel&, const Buffers64&, int, float*, float*, float*, hipStream_t) { LaunchScope ls; return hipSuccess; }
-hipError_t launch_eval_forces64(const DevModel&, const double*, const double*, const Buffers64&, int, int, double*, hipStream_t) { LaunchScope ls; return hipSuccess; }
-hipError_t launch_energy64(const DevModel&, const double*, double, const Buffers64&, int, double*, hipStream_t) { LaunchScope ls; return hipSuccess; }
+hipError_t launch_eval_forces64(const DevModel&, const Model64&, const Step64&, const Form64&, const Buffers64&, int, double*, hipStream_t) { LaunchScope ls; return hipSuccess; }
+hipError_t launch_energy64(const DevModel&, const Model64&, double, const Buffers64&, int, double*, hipStream_t) { LaunchScope ls; return hipSuccess; }
 size_t fire_state64_bytes() { return 32; }
 // K1 restated on the host (chromosome3D.pl:110-162 as c3d_api.cpp's own near-tie redo does it): the executor needs real restraints
 hipError_t launch_if_to_target(const double* IF, int n, int npad, double alpha, double K, int min_sep, int, double*, double*, int,
