@@ -241,18 +241,13 @@ class Solver:
         """(spearman, rmsd), K x K each: pipeline.model_similarity(model a, model b) for every ordered pair of the K = nrep + len(extra)
         models, on the device (c3d_compare_replicas).  Models 0..nrep-1 are the replicas at their current coordinates; `extra` is a
         stack [E, n, 3] (or one model [n, 3]) of further models, e.g. a bundled one.  rmsd[a][b] scales a onto b: not symmetric.
-        Scratch for the call: 4 bytes per pair and model plus 8 bytes per sort slot (c3d.h)."""
-        ex = None
-        if extra is not None:
-            ex = np.ascontiguousarray(extra, dtype=np.float64)
-            if ex.ndim == 2:
-                ex = ex[None]
-            assert ex.ndim == 3 and ex.shape[1:] == (self.n, 3)
-        K = self.nrep + (0 if ex is None else ex.shape[0])
+        Scratch for the call: 4 bytes per pair and model plus 8 bytes per sort slot (c3d.h).  precision 64: the replicas compared are the
+        float mirror of the fp64 state, what coords() returns (the other model-set methods read the fp64 state itself)."""
+        ptr, E = self._extra_models(extra)
+        K = self.nrep + E
         rho = np.empty((K, K), dtype=np.float64)
         rmsd = np.empty((K, K), dtype=np.float64)
-        _l.check(self._L.c3d_compare_replicas(self._h, _l.dptr(ex) if ex is not None else None, 0 if ex is None else ex.shape[0],
-                                              _l.dptr(rho), _l.dptr(rmsd)))
+        _l.check(self._L.c3d_compare_replicas(self._h, ptr, E, _l.dptr(rho), _l.dptr(rmsd)))
         return rho, rmsd
 
     def debug_distance_ranks(self, replica):
@@ -263,13 +258,14 @@ class Solver:
         return rank
 
     def _extra_models(self, extra):
+        """(pointer or None, count) of `extra` as the C entries take their extra models; the pointer keeps its array alive"""
         if extra is None:
-            return None
+            return None, 0
         ex = np.ascontiguousarray(extra, dtype=np.float64)
         if ex.ndim == 2:
             ex = ex[None]
         assert ex.ndim == 3 and ex.shape[1:] == (self.n, 3)
-        return ex
+        return _l.dptr(ex), ex.shape[0]
 
     def superpose(self, reference=0, ref_xyz=None, mirror=True, apply=False, iters=0):
         """(rmsd [nrep], mirrored [nrep], mean [n, 3], rmsf [n]): every replica fitted onto replica `reference` — or onto ref_xyz [n, 3]
@@ -296,12 +292,11 @@ class Solver:
         """(rmsd, mirrored), K x K each: the superposition of model a onto model b for every ordered pair of the K = nrep + len(extra)
         models of compare(), on the device (c3d_rmsd_table): coordinate RMSD in Angstrom after the best rotation — and reflection, where
         that fits strictly better (mirrored[a][b] = 1).  The diagonal is exactly 0."""
-        ex = self._extra_models(extra)
-        K = self.nrep + (0 if ex is None else ex.shape[0])
+        ptr, E = self._extra_models(extra)
+        K = self.nrep + E
         rmsd = np.empty((K, K), dtype=np.float64)
         mirrored = np.empty((K, K), dtype=np.int32)
-        _l.check(self._L.c3d_rmsd_table(self._h, _l.dptr(ex) if ex is not None else None, 0 if ex is None else ex.shape[0],
-                                        _l.SUPERPOSE_MIRROR if mirror else 0, _l.dptr(rmsd), _l.i32ptr(mirrored)))
+        _l.check(self._L.c3d_rmsd_table(self._h, ptr, E, _l.SUPERPOSE_MIRROR if mirror else 0, _l.dptr(rmsd), _l.i32ptr(mirrored)))
         return rmsd, mirrored
 
     def _picked(self, pick):
@@ -321,12 +316,11 @@ class Solver:
         contact = (cutoff is not None) if contact is None else bool(contact)
         if contact and cutoff is None:
             raise ValueError("the contact map needs a cutoff")
-        ex = self._extra_models(extra)
+        xptr, E = self._extra_models(extra)
         p, n_pick = self._picked(pick)
         out = {k: np.empty((self.n, self.n), dtype=np.float64) for k, on in (("mean", mean), ("sd", sd), ("contact", contact)) if on}
         ptr = lambda k: _l.dptr(out[k]) if k in out else None
-        _l.check(self._L.c3d_ensemble_map(self._h, _l.dptr(ex) if ex is not None else None, 0 if ex is None else ex.shape[0],
-                                          _l.i32ptr(p) if p is not None else None, n_pick, 0.0 if cutoff is None else float(cutoff),
+        _l.check(self._L.c3d_ensemble_map(self._h, xptr, E, _l.i32ptr(p) if p is not None else None, n_pick, 0.0 if cutoff is None else float(cutoff),
                                           ptr("mean"), ptr("sd"), ptr("contact")))
         return out
 
@@ -336,11 +330,10 @@ class Solver:
         the same arguments, bit for bit.  A good ensemble has rho_mean < 0 and rho_contact > 0.  IF must be symmetric."""
         IFc = np.ascontiguousarray(IF, dtype=np.float64)
         assert IFc.shape == (self.n, self.n)
-        ex = self._extra_models(extra)
+        xptr, E = self._extra_models(extra)
         p, n_pick = self._picked(pick)
         rm, rc = C.c_double(), C.c_double()
-        _l.check(self._L.c3d_ensemble_score(self._h, _l.dptr(IFc), int(rng), _l.dptr(ex) if ex is not None else None,
-                                            0 if ex is None else ex.shape[0], _l.i32ptr(p) if p is not None else None, n_pick,
+        _l.check(self._L.c3d_ensemble_score(self._h, _l.dptr(IFc), int(rng), xptr, E, _l.i32ptr(p) if p is not None else None, n_pick,
                                             0.0 if cutoff is None else float(cutoff), C.byref(rm), C.byref(rc) if cutoff is not None else None))
         return rm.value, (rc.value if cutoff is not None else None)
 

@@ -11,6 +11,7 @@ Shapes, the smallest at which each part can still go wrong (m = n(n-1)/2 pairs, 
   k17      64 beads x 17    K crosses a sixteen-model block of the table pass
   lattice  130 beads x 4    integer coordinates in [0, 6)^3: coincident beads (distance 0), heavy ties, all arithmetic exact; replica 1 is a
            copy of replica 0, replica 2 is 3 x replica 0
+  f64      64 beads x 3     a precision-64 context, lattice [1, 7)^3 plus noise that no float holds: the float mirror is what is compared
 
 Tolerances (from the arithmetic, not from the device's numbers): the ranks are equal bit for bit.  rho and rmsd differ from the host's by
 the order of summation alone: a few m 2^-53, about 1e-11 at the largest m here, so |rho_dev - rho_host| <= 1e-10 and |rmsd_dev - rmsd_host|
@@ -21,13 +22,12 @@ import subprocess
 import numpy as np
 import pytest
 
-from tests.util import GOLD, load_if, load_pdb_xyz, model_pdb, random_coil
+from tests.util import GOLD, SHORT, load_if, load_pdb_xyz, model_pdb, random_coil, restrained, shared_models
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOL = 1e-10
-SHORT = [(2, 15, 0.0, 1.0, 20.0, 0.5, 0.0), (0, 15, 0.003, 0.4, 0.003, 0.9, 2000.0), (2, 15, 0.0, 1.0, 1.0, 0.85, 0.0)]
 CASES = ["n64", "n92", "n257", "k17", "lattice"]
 
 
@@ -39,34 +39,14 @@ def ctx():
     s.close()
 
 
-def _restrained(s, n, nrep, seed=7):
-    """a context of n beads with a small random restraint set and nrep replicas"""
-    from chromosome3d_amd import default_model, make_stages
-    rng = np.random.default_rng(seed)
-    R = max(1, min(3 * n, n * (n - 1) // 2 // 2))
-    i = rng.integers(1, n, size=R)
-    j = np.minimum(i + rng.integers(1, 12, size=R), n)
-    keep = j > i
-    s.set_model(default_model())
-    s.set_schedule(make_stages(SHORT))
-    s.set_restraints(n, i[keep].astype(np.int32), j[keep].astype(np.int32), rng.integers(30, 120, size=int(keep.sum())).astype(np.int32))
-    s.init_replicas(nrep)
-
-
 def _models(name):
     """(replica coordinates [M, n, 3] float32, extra models [E, n, 3] float64 or None)"""
     if name == "n64":
         return np.stack([random_coil(64, 100 + r) for r in range(3)]), None
     if name == "n92":
         return np.stack([random_coil(92, 200 + r) for r in range(2)]), None
-    if name == "n257":
-        x = np.stack([random_coil(257, 300 + r) for r in range(5)])
-        rng = np.random.default_rng(257)
-        extra = np.stack([random_coil(257, 310 + e).astype(np.float64) * (1.5 + e) + rng.normal(scale=1e-3, size=(257, 3)) for e in range(2)])
-        assert not np.array_equal(extra, extra.astype(np.float32))
-        return x, extra
-    if name == "k17":
-        return np.stack([random_coil(64, 400 + r) for r in range(17)]), None
+    if name in ("n257", "k17"):
+        return shared_models(name)
     rng = np.random.default_rng(130)
     a, b = rng.integers(0, 6, size=(130, 3)), rng.integers(0, 6, size=(130, 3))
     assert len(np.unique(a, axis=0)) < 130                                     # coincident beads
@@ -105,7 +85,7 @@ def _host_tables(name, models):
 def _load(ctx, name):
     """the context holding the case's replicas; returns (x, extra, all K models as doubles)"""
     x, extra = _models(name)
-    _restrained(ctx, x.shape[1], x.shape[0])
+    restrained(ctx, x.shape[1], x.shape[0])
     ctx.set_coords(x)
     models = [m.astype(np.float64) for m in x] + ([] if extra is None else list(extra))
     return x, extra, models
@@ -154,6 +134,38 @@ def test_lattice_copies_are_exact(ctx):
         assert rho[a, b] == hrho[a, b] == 1.0, (a, b, rho[a, b], hrho[a, b])
         assert rmsd[a, b] <= 1e-9, (a, b, rmsd[a, b])
     assert rho[0, 3] < 0.9 and rmsd[0, 3] > 0.1                                 # and an unrelated lattice is unrelated
+
+
+def test_precision64_context_compares_its_float_mirror():
+    """compare() and its hook read the floats on every context: on a precision-64 one the float mirror of the fp64 state, which is what
+    coords() returns and what the host twin is fed.  64 beads x 3 (one sort tile, one table block) on the lattice [1, 7)^3 plus 1e-9 of
+    noise: a float's spacing at 1 is 1.2e-7, so the mirror is the bare lattice with heavy ties (43 to 44 distinct ranks a model), while the
+    doubles have none (2016 distinct ranks) and 1992 to 1994 of the 2016 ranks differ between the two."""
+    from chromosome3d_amd import Solver
+    s = Solver(0)
+    try:
+        s.set_option("precision", 64)
+        restrained(s, 64, 3)
+        rng = np.random.default_rng(64)
+        lattice, x = [], []
+        for _ in range(3):
+            lattice.append(rng.integers(1, 7, size=(64, 3)).astype(np.float64))
+            x.append(lattice[-1] + 1e-9 * rng.normal(size=(64, 3)))
+        s.set_coords64(np.stack(x))
+        mirror, state = s.coords(), s.coords64()
+        assert np.array_equal(mirror, np.stack(lattice)) and np.array_equal(state, np.stack(x))
+        for r in range(3):
+            dev, of_mirror, of_state = s.debug_distance_ranks(r), _host_ranks(mirror[r]), _host_ranks(state[r])
+            differ = int((dev != of_state).sum())
+            print(f"replica {r}: ranks off the mirror's {int((dev != of_mirror).sum())}, off the fp64 state's {differ} of {dev.size}, "
+                  f"distinct ranks {len(np.unique(of_mirror))} / {len(np.unique(of_state))}")
+            assert np.array_equal(dev, of_mirror)
+            assert differ > dev.size // 2
+        models = [m.astype(np.float64) for m in mirror]
+        rho, rmsd = s.compare()
+        _check_tables(rho, rmsd, *_host_tables("f64 mirror", models), "f64 mirror")
+    finally:
+        s.close()
 
 
 def test_rmsd_is_not_symmetric_and_each_side_is_the_hosts(ctx):

@@ -26,12 +26,11 @@ import numpy as np
 import pytest
 
 from tests import ensemble_ref as R
-from tests.util import GOLD, load_pdb_xyz, random_coil
+from tests.util import GOLD, SHORT, load_pdb_xyz, random_coil, restrained, shared_models
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SHORT = [(2, 15, 0.0, 1.0, 20.0, 0.5, 0.0), (0, 15, 0.003, 0.4, 0.003, 0.9, 2000.0), (2, 15, 0.0, 1.0, 1.0, 0.85, 0.0)]
 CASES = ["n64", "n65", "n130", "n257", "k17", "lattice"]
 PICK257 = [6, 4, 2, 2, 0]
 CUTOFF = {"lattice": 3.0}                                                       # an integer: pairs at exactly the cutoff are no contact
@@ -45,33 +44,13 @@ def ctx():
     s.close()
 
 
-def _restrained(s, n, nrep, seed=7):
-    """a context of n beads with a small random restraint set and nrep replicas"""
-    from chromosome3d_amd import default_model, make_stages
-    rng = np.random.default_rng(seed)
-    R_ = max(1, min(3 * n, n * (n - 1) // 2 // 2))
-    i = rng.integers(1, n, size=R_)
-    j = np.minimum(i + rng.integers(1, 12, size=R_), n)
-    keep = j > i
-    s.set_model(default_model())
-    s.set_schedule(make_stages(SHORT))
-    s.set_restraints(n, i[keep].astype(np.int32), j[keep].astype(np.int32), rng.integers(30, 120, size=int(keep.sum())).astype(np.int32))
-    s.init_replicas(nrep)
-
-
 def _models(name):
     """(replica coordinates [M, n, 3] float32, extra models [E, n, 3] float64 or None)"""
     if name in ("n64", "n65", "n130", "n92", "n95"):
         n, M = {"n64": (64, 3), "n65": (65, 2), "n130": (130, 4), "n92": (92, 2), "n95": (95, 2)}[name]
         return np.stack([random_coil(n, 10 * n + r) for r in range(M)]), None
-    if name == "n257":
-        x = np.stack([random_coil(257, 300 + r) for r in range(5)])
-        rng = np.random.default_rng(257)
-        extra = np.stack([random_coil(257, 310 + e).astype(np.float64) * (1.5 + e) + rng.normal(scale=1e-3, size=(257, 3)) for e in range(2)])
-        assert not np.array_equal(extra, extra.astype(np.float32))
-        return x, extra
-    if name == "k17":
-        return np.stack([random_coil(64, 400 + r) for r in range(17)]), None
+    if name in ("n257", "k17"):
+        return shared_models(name)
     rng = np.random.default_rng(130)
     a, b, c = (rng.integers(0, 6, size=(130, 3)) for _ in range(3))
     assert len(np.unique(a, axis=0)) < 130                                      # coincident beads
@@ -81,7 +60,7 @@ def _models(name):
 def _load(ctx, name):
     """the context holding the case's replicas; returns (extra, all K models as doubles)"""
     x, extra = _models(name)
-    _restrained(ctx, x.shape[1], x.shape[0])
+    restrained(ctx, x.shape[1], x.shape[0])
     ctx.set_coords(x)
     return extra, [m.astype(np.float64) for m in x] + ([] if extra is None else list(extra))
 
@@ -146,7 +125,7 @@ def test_maps_equal_the_restatement(ctx, name):
 @pytest.mark.parametrize("K", [3, 7])
 def test_copies_of_one_model_have_no_spread(ctx, K):
     x = random_coil(64, 77) * np.float32(25.0)
-    _restrained(ctx, 64, K)
+    restrained(ctx, 64, K)
     ctx.set_coords(np.stack([x] * K))
     got = ctx.ensemble_map(cutoff=60.0)
     d = R.distances(ctx.coords()[0])
@@ -159,7 +138,7 @@ def test_copies_of_one_model_have_no_spread(ctx, K):
 def test_one_model_is_its_own_map_and_scores_as_its_distances(ctx):
     """K = 1 at n = 92: mean = d bit for bit, sd = 0 exactly, and rho_mean = Spearman(IF, exact distances) of the restatement."""
     x = random_coil(92, 920)
-    _restrained(ctx, 92, 1)
+    restrained(ctx, 92, 1)
     ctx.set_coords(x[None])
     got = ctx.ensemble_map(cutoff=7.6)
     d = R.distances(x)
@@ -217,7 +196,7 @@ def test_f64_state_is_mapped_in_doubles():
     s = Solver(0)
     try:
         s.set_option("precision", 64)
-        _restrained(s, 96, 3)
+        restrained(s, 96, 3)
         rng = np.random.default_rng(96)
         x = np.stack([random_coil(96, 960 + r).astype(np.float64) for r in range(3)]) + rng.normal(scale=1e-3, size=(3, 96, 3))
         assert not np.array_equal(x, x.astype(np.float32).astype(np.float64))
@@ -348,7 +327,7 @@ def test_from_the_command_line(ctx, tmp_path):
         rows = open(f"{prefix}_{k}.txt").read().split("\n")
         assert len(rows) == 38 and rows[-1] == "" and all(len(r.split(" ")) == 37 for r in rows[:-1])     # n lines of n numbers, single spaces
     x = np.stack([load_pdb_xyz(tmp_path / "a" / f"{cid}_matrix_{r + 1}.pdb") for r in range(M)])
-    _restrained(ctx, 37, M)
+    restrained(ctx, 37, M)
     ctx.set_coords(x)
     got = ctx.ensemble_map(cutoff=2 * 3.8)
     gap = np.abs(maps["mean"] - got["mean"]).max()

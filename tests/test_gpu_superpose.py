@@ -19,7 +19,7 @@ import numpy as np
 import pytest
 
 from tests import superpose_ref as R
-from tests.util import GOLD, load_if, load_pdb_xyz, model_pdb, random_coil
+from tests.util import GOLD, SHORT, load_if, load_pdb_xyz, model_pdb, random_coil, restrained
 
 pytestmark = pytest.mark.gpu
 
@@ -29,7 +29,6 @@ CAP = 1e-9
 BOUND = {k: 1e-10 for k in ("rmsd", "mean", "rmsf", "coords", "table", "energy")}
 assert all(v <= CAP for v in BOUND.values())
 
-SHORT = [(2, 15, 0.0, 1.0, 20.0, 0.5, 0.0), (0, 15, 0.003, 0.4, 0.003, 0.9, 2000.0), (2, 15, 0.0, 1.0, 1.0, 0.85, 0.0)]
 CASES = {"n4k2": (4, 2), "n37k20": (37, 20), "n255k1": (255, 1), "n256k2": (256, 2), "n257k20": (257, 20), "n455k20": (455, 20)}
 CASES64 = {"n37k20": (37, 20), "n455k2": (455, 2), "n2561k2": (2561, 2)}
 SEED = {4: 1, 37: 4, 255: 1, 256: 1, 257: 1, 455: 1, 2561: 1}        # chosen on the CPU: every case passes `precondition`
@@ -93,20 +92,6 @@ def expected(n, K, f64, iters, external):
     for v in out.values():
         v.setflags(write=False)
     return out
-
-
-def restrained(s, n, nrep, seed=7):
-    """a context of n beads with a small random restraint set and nrep replicas"""
-    from chromosome3d_amd import default_model, make_stages
-    rng = np.random.default_rng(seed)
-    R_ = max(1, min(3 * n, n * (n - 1) // 2 // 2))
-    i = rng.integers(1, n, size=R_)
-    j = np.minimum(i + rng.integers(1, 12, size=R_), n)
-    keep = j > i
-    s.set_model(default_model())
-    s.set_schedule(make_stages(SHORT))
-    s.set_restraints(n, i[keep].astype(np.int32), j[keep].astype(np.int32), rng.integers(30, 120, size=int(keep.sum())).astype(np.int32))
-    s.init_replicas(nrep)
 
 
 def load32(s, n, K):

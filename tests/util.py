@@ -72,6 +72,38 @@ def random_coil(n, seed, step=3.8):
     return (x - x.mean(0)).astype(np.float32)
 
 
+# ---- what the GPU tests of the output side (compare, superpose, ensemble) share ----
+# a schedule of 45 steps: enough for a context that only has to hold replicas
+SHORT = [(2, 15, 0.0, 1.0, 20.0, 0.5, 0.0), (0, 15, 0.003, 0.4, 0.003, 0.9, 2000.0), (2, 15, 0.0, 1.0, 1.0, 0.85, 0.0)]
+
+
+def restrained(s, n, nrep, seed=7):
+    """a context of n beads with a small random restraint set and nrep replicas"""
+    from chromosome3d_amd import default_model, make_stages
+    rng = np.random.default_rng(seed)
+    R = max(1, min(3 * n, n * (n - 1) // 2 // 2))
+    i = rng.integers(1, n, size=R)
+    j = np.minimum(i + rng.integers(1, 12, size=R), n)
+    keep = j > i
+    s.set_model(default_model())
+    s.set_schedule(make_stages(SHORT))
+    s.set_restraints(n, i[keep].astype(np.int32), j[keep].astype(np.int32), rng.integers(30, 120, size=int(keep.sum())).astype(np.int32))
+    s.init_replicas(nrep)
+
+
+def shared_models(name):
+    """(replica coordinates [M, n, 3] float32, extra models [E, n, 3] float64 or None) of the cases the compare and ensemble modules share:
+    n257 = 257 beads x 5 + 2 extra models that no float holds, k17 = 64 beads x 17"""
+    if name == "k17":
+        return np.stack([random_coil(64, 400 + r) for r in range(17)]), None
+    assert name == "n257"
+    x = np.stack([random_coil(257, 300 + r) for r in range(5)])
+    rng = np.random.default_rng(257)
+    extra = np.stack([random_coil(257, 310 + e).astype(np.float64) * (1.5 + e) + rng.normal(scale=1e-3, size=(257, 3)) for e in range(2)])
+    assert not np.array_equal(extra, extra.astype(np.float32))
+    return x, extra
+
+
 def synthetic_if(n, seed=20161015, K=11.0, alpha=0.5, sigma=0.2, radius=None):
     """Config-5 style synthetic Hi-C matrix: ground truth = confined random walk with
     3.8 A steps; IF_ij = (K / d_ij)^(1/alpha) * lognormal noise, symmetric, diagonal = 10 x row max.
