@@ -1,6 +1,6 @@
 // c3d_analysis.cpp — host unit of libc3d.so: the output side.  What a run's models are worth and how they relate, from the coordinates
 // resident on the device (kernels: c3d_score.hip): c3d_score_replicas, c3d_compare_replicas, c3d_superpose_replicas, c3d_rmsd_table,
-// c3d_ensemble_map, c3d_ensemble_score and the test hooks c3d_debug_if_ranks / c3d_debug_distance_ranks.  What they share comes first: typed
+// c3d_ensemble_map, c3d_ensemble_score, c3d_geometry_replicas, c3d_separation_profile and the test hooks c3d_debug_if_ranks / c3d_debug_distance_ranks.  What they share comes first: typed
 // scratch slots (Slot, Block, Carve, CallScratch), the ranker (rank_matrix) and the models of a call (model_set_check, model_set_coords, gather_models).
 #include "c3d_ctx.h"
 
@@ -614,5 +614,88 @@ extern "C" int c3d_ensemble_score(c3d_ctx* c, const double* IF, int range, const
         *want[k] = sab / sqrt(saa * sbb);
     }
     ++c->ensemble_score_runs;
+    return C3D_OK;
+}
+
+// ---- a model's geometry and the distance against separation (c3d_score.hip k_geo_*, k_sep_*) ----
+// c3d_geometry_replicas' one allocation: the models, per bead the clash partners, the nearest counted partner and the furthest bead, per
+// model the clash count and the chain fields
+struct GeometryScratch : Carve {
+    Slot<double> xyz, nearest, furthest, chain;
+    Slot<int32_t> bead;
+    Slot<long long> clashes;
+    GeometryScratch(int n, int K) {
+        xyz = take<double>(3 * (size_t)n * K);
+        bead = take<int32_t>((size_t)n * K);
+        nearest = take<double>((size_t)n * K);
+        furthest = take<double>((size_t)n * K);
+        clashes = take<long long>((size_t)K);
+        chain = take<double>((size_t)C3D_GEOMETRY_FIELDS * K);
+    }
+};
+
+extern "C" int c3d_geometry_replicas(c3d_ctx* c, const double* extra_xyz, int n_extra, double cutoff, int sep, int64_t* clashes, int32_t* bead_clashes,
+                                     double* nearest, double* chain) {
+    if (int rc = model_set_check(c, "c3d_geometry_replicas", 3, "no (i,i+2) distance", extra_xyz, n_extra)) return rc;
+    if (!clashes && !bead_clashes && !nearest && !chain) return fail(C3D_ERR_INVALID, "c3d_geometry_replicas: every output is NULL");
+    if (sep < 1 || sep > c->n - 1) return fail(C3D_ERR_INVALID, "c3d_geometry_replicas: sep outside 1..n-1");
+    const bool counting = clashes || bead_clashes;
+    if (counting && !ensemble_cutoff_ok(cutoff)) return fail(C3D_ERR_INVALID, "c3d_geometry_replicas: the clash count needs a finite cutoff > 0");
+    if (int rc = model_set_coords(c, "c3d_geometry_replicas", extra_xyz, n_extra)) return rc;
+    const int n = c->n, K = c->nrep + n_extra;
+    C3D_ENTRY(c, unit_bit(UNIT_SCORE));
+    const GeometryScratch L(n, K);
+    CallScratch tmp;
+    if (int rc = tmp.alloc(L.total, "c3d_geometry_replicas")) return rc;
+    double* const d_xyz = L.xyz.at(tmp.p);
+    if (int rc = gather_models(c, ModelSource::STATE, 0, c->nrep, d_xyz, extra_xyz, n_extra, "superpose launch")) return rc;
+    static_assert(sizeof(long long) == sizeof(int64_t), "the device's counts are the caller's int64_t");
+    LAUNCH_TRY("geometry launch", c3d::launch_geometry(d_xyz, n, K, counting ? cutoff : -1.0, sep, L.bead.at(tmp.p), L.nearest.at(tmp.p), L.furthest.at(tmp.p),
+                                                       L.clashes.at(tmp.p), L.chain.at(tmp.p), c->stream));
+    // straight into the caller's arrays: the per-bead ones are 8 n K bytes, which the pinned stage would have to grow to
+    if (clashes) HIP_TRY(hipMemcpyAsync(clashes, L.clashes.at(tmp.p), L.clashes.bytes(), hipMemcpyDeviceToHost, c->stream));
+    if (bead_clashes) HIP_TRY(hipMemcpyAsync(bead_clashes, L.bead.at(tmp.p), L.bead.bytes(), hipMemcpyDeviceToHost, c->stream));
+    if (nearest) HIP_TRY(hipMemcpyAsync(nearest, L.nearest.at(tmp.p), L.nearest.bytes(), hipMemcpyDeviceToHost, c->stream));
+    if (chain) HIP_TRY(hipMemcpyAsync(chain, L.chain.at(tmp.p), L.chain.bytes(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    ++c->geometry_runs;
+    return C3D_OK;
+}
+
+// c3d_separation_profile's one allocation: the models, the pick list and the three profiles
+struct SeparationScratch : Carve {
+    Slot<double> xyz, out[3];
+    Slot<int32_t> pick;
+    SeparationScratch(int n, int K, int Kp) {
+        xyz = take<double>(3 * (size_t)n * K);
+        pick = take<int32_t>((size_t)Kp);
+        for (int k = 0; k < 3; ++k) out[k] = take<double>((size_t)n);
+    }
+};
+
+extern "C" int c3d_separation_profile(c3d_ctx* c, const double* extra_xyz, int n_extra, const int32_t* pick, int n_pick, double cutoff, double* mean, double* sd,
+                                      double* contact) {
+    std::vector<int32_t> list;
+    if (int rc = ensemble_check(c, "c3d_separation_profile", extra_xyz, n_extra, pick, n_pick, &list)) return rc;
+    if (!mean && !sd && !contact) return fail(C3D_ERR_INVALID, "c3d_separation_profile: every output is NULL");
+    if (contact && !ensemble_cutoff_ok(cutoff)) return fail(C3D_ERR_INVALID, "c3d_separation_profile: the contact profile needs a finite cutoff > 0");
+    if (int rc = model_set_coords(c, "c3d_separation_profile", extra_xyz, n_extra)) return rc;
+    const int n = c->n, K = c->nrep + n_extra, Kp = (int)list.size();
+    C3D_ENTRY(c, unit_bit(UNIT_SCORE));
+    const SeparationScratch L(n, K, Kp);
+    CallScratch tmp;
+    if (int rc = tmp.alloc(L.total, "c3d_separation_profile")) return rc;
+    double* const d_xyz = L.xyz.at(tmp.p);
+    int* const d_pick = L.pick.at(tmp.p);
+    double* const outs[3] = {mean, sd, contact};
+    if (int rc = gather_models(c, ModelSource::STATE, 0, c->nrep, d_xyz, extra_xyz, n_extra, "superpose launch")) return rc;
+    HIP_TRY(hipMemcpyAsync(d_pick, list.data(), sizeof(int32_t) * (size_t)Kp, hipMemcpyHostToDevice, c->stream));
+    // the mean is formed whatever was asked for: the sd is taken about it
+    LAUNCH_TRY("separation launch", c3d::launch_separation_profile(d_xyz, n, d_pick, Kp, contact ? cutoff : 0.0, L.out[0].at(tmp.p), sd ? L.out[1].at(tmp.p) : nullptr,
+                                                                   contact ? L.out[2].at(tmp.p) : nullptr, c->stream));
+    for (int k = 0; k < 3; ++k)
+        if (outs[k]) HIP_TRY(hipMemcpyAsync(outs[k], L.out[k].at(tmp.p), L.out[k].bytes(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    ++c->separation_runs;
     return C3D_OK;
 }

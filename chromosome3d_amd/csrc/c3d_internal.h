@@ -440,6 +440,16 @@ inline int ensemble_tiles(int n) { return (n + 63) / 64; }
 hipError_t launch_ensemble_map(const double* xyz, int n, const int* pick, int Kp, double cutoff, double* mean, double* sd, double* contact,
                                hipStream_t s);
 hipError_t launch_ensemble_corr(const double* A, const double* B, int n, int range, double ma, double* rows, hipStream_t s);
+// A model's geometry and the distance against separation (c3d_geometry_replicas, c3d_separation_profile; k_geo_*, k_sep_*).  xyz as above.
+// launch_geometry, for each of the K models: bead_clashes, nearest, furthest (K x n on the device) = per bead the number of partners j,
+// |i-j| >= sep, with d <= cutoff, the smallest such d (+inf without a partner) and the largest d over all j; clashes (K) = half the sum of
+// a model's bead_clashes, chain (K x C3D_GEOMETRY_FIELDS) = bond mean / sd, (i,i+2) mean / sd, radius of gyration, extent.  A cutoff < 0
+// counts nothing.  launch_separation_profile: mean, sd, contact (n doubles on the device, indexed by s; mean is always written, sd and
+// contact may be null) over the Kp picked models' d(i, i+s); the sd is a second launch that reads the finished mean.
+hipError_t launch_geometry(const double* xyz, int n, int K, double cutoff, int sep, int* bead_clashes, double* nearest, double* furthest,
+                           long long* clashes, double* chain, hipStream_t s);
+hipError_t launch_separation_profile(const double* xyz, int n, const int* pick, int Kp, double cutoff, double* mean, double* sd, double* contact,
+                                     hipStream_t s);
 
 // Target matrix entry: NOE target in Angstrom, 0 = no restraint (host c3d_set_restraints and K1).
 inline float encode_target_host(float t) { return t > 0 ? t : 0.0f; }

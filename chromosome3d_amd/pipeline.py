@@ -205,6 +205,17 @@ def ensemble_maps(solver, IF=None, rng=3, extra=None, pick=None, cutoff=None):
     return out
 
 
+def geometry_report(solver, extra=None, pick=None, clash_cutoff=3.5, sep=1, contact_cutoff=None):
+    """Model quality and polymer diagnostics of a run's models on the device: Solver.geometry's dict ("clashes", "bead_clashes", "nearest",
+    "chain" per model; clash_cutoff 3.5 A and sep 1 are the reference's clash count) with "separation_mean", "separation_sd" [n] and, with
+    a contact_cutoff, "separation_contact" [n] of Solver.separation_profile over the models of `pick` (None: all)."""
+    out = solver.geometry(extra, clash_cutoff, sep)
+    out["separation_mean"], out["separation_sd"], contact = solver.separation_profile(extra, pick, contact_cutoff)
+    if contact is not None:
+        out["separation_contact"] = contact
+    return out
+
+
 def build_models(solver, model_count=MODELCOUNT, seed=MD_SEED, first_replica=0, model=None, stages=None, fire=None,
                  gtol=1e-2, check_every=250, final_kind=5):
     """The replacement of `cns_solve < dgsa.inp` (:254-289): runs the whole annealing schedule

@@ -337,6 +337,32 @@ class Solver:
                                             0.0 if cutoff is None else float(cutoff), C.byref(rm), C.byref(rc) if cutoff is not None else None))
         return rm.value, (rc.value if cutoff is not None else None)
 
+    def geometry(self, extra=None, cutoff=3.5, sep=1):
+        """A dict of arrays over the K models of compare() — the replicas at their current coordinates (precision 64: the fp64 state), then
+        `extra` [E, n, 3] — computed on the device (c3d_geometry_replicas): "clashes" [K] int64, the pairs i < j, j - i >= sep, no further
+        apart than `cutoff` (sep = 1: the reference's clash_count, bonded neighbours and `<=` included); "bead_clashes" [K, n] int32, every
+        bead's partners in those pairs; "nearest" [K, n], its closest partner at |i-j| >= sep (inf where it has none); "chain" [K, 6]:
+        bond mean, bond sd, (i,i+2) mean, (i,i+2) sd, radius of gyration, extent.  Nothing of the solve changes."""
+        xptr, E = self._extra_models(extra)
+        K = self.nrep + E
+        out = {"clashes": np.empty(K, dtype=np.int64), "bead_clashes": np.empty((K, self.n), dtype=np.int32),
+               "nearest": np.empty((K, self.n), dtype=np.float64), "chain": np.empty((K, _l.GEOMETRY_FIELDS), dtype=np.float64)}
+        _l.check(self._L.c3d_geometry_replicas(self._h, xptr, E, float(cutoff), int(sep), out["clashes"].ctypes.data_as(C.POINTER(C.c_int64)),
+                                               _l.i32ptr(out["bead_clashes"]), _l.dptr(out["nearest"]), _l.dptr(out["chain"])))
+        return out
+
+    def separation_profile(self, extra=None, pick=None, cutoff=None):
+        """(mean [n], sd [n], contact [n] or None), indexed by the separation s = |i-j|: mean and population sd of the distances d(i, i+s)
+        over all i and the picked models, and, with a cutoff, the share of them below it — R(s) and P(s), the diagonal averages of
+        ensemble_map()'s matrices for the same arguments without forming the matrices (c3d_separation_profile).  s = 0: 0, 0, 1."""
+        xptr, E = self._extra_models(extra)
+        p, n_pick = self._picked(pick)
+        mean, sd = np.empty(self.n, dtype=np.float64), np.empty(self.n, dtype=np.float64)
+        contact = np.empty(self.n, dtype=np.float64) if cutoff is not None else None
+        _l.check(self._L.c3d_separation_profile(self._h, xptr, E, _l.i32ptr(p) if p is not None else None, n_pick, 0.0 if cutoff is None else float(cutoff),
+                                                _l.dptr(mean), _l.dptr(sd), _l.dptr(contact) if contact is not None else None))
+        return mean, sd, contact
+
     def rank(self):
         r = np.empty(self.nrep, dtype=np.int32)
         _l.check(self._L.c3d_rank(self._h, _l.i32ptr(r)))

@@ -323,7 +323,8 @@ int c3d_last_timing(const c3d_ctx* ctx, double* ms_total, long* steps, long* lau
  * "device_rank_runs" (calls of c3d_score_replicas that ranked the IF matrix on the device), "score_wide_runs" (calls of it that were
  * re-run with a histogram sized to the models), "compare_runs" (completed calls of c3d_compare_replicas),
  * "f64_evals" (completed calls of c3d_eval_f64), "superpose_runs" / "rmsd_table_runs" (completed calls of c3d_superpose_replicas /
- * c3d_rmsd_table), "ensemble_map_runs" / "ensemble_score_runs" (completed calls of c3d_ensemble_map / c3d_ensemble_score). */
+ * c3d_rmsd_table), "ensemble_map_runs" / "ensemble_score_runs" (completed calls of c3d_ensemble_map / c3d_ensemble_score),
+ * "geometry_runs" / "separation_runs" (completed calls of c3d_geometry_replicas / c3d_separation_profile). */
 int c3d_get_stat(const c3d_ctx* ctx, const char* key, double* value);
 /* Test hook, no reference counterpart: the multi-step kernel's hand-off trusts a 16-byte unit once its tag word matches — i.e. that a
  * 16-byte aligned store is never observed half-written by a 16-byte load on gfx950.  This runs that exact store / load pair (one producer
@@ -467,6 +468,49 @@ int c3d_ensemble_map(c3d_ctx* ctx, const double* extra_xyz, int n_extra, const i
                      double* mean, double* sd, double* contact);
 int c3d_ensemble_score(c3d_ctx* ctx, const double* IF, int range, const double* extra_xyz, int n_extra,
                        const int32_t* pick, int n_pick, double cutoff, double* rho_mean, double* rho_contact);
+/* A model's geometry and the distance against genomic separation, on the device (c3d_score.hip k_geo_*, k_sep_*): all-pairs reductions over
+ * the models of the ensemble entries above — K = n_replicas + n_extra, numbered as in c3d_compare_replicas, the replicas taken as
+ * c3d_superpose_replicas takes them (precision 64: the fp64 state bit for bit, else the floats taken as doubles unchanged), extra models n x 3
+ * doubles checked as there; pick / n_pick with exactly the meaning and limits they have in c3d_ensemble_map.  The distance d(i,j) is
+ * theirs too, sqrt(((ux ux) + uy uy) + uz uz) in fp64 with every operation rounded on its own: the host's bits, and those of the reference's
+ * sqrt(($x1-$x2)**2+($y1-$y2)**2+($z1-$z2)**2).
+ * c3d_geometry_replicas, per model k; any output may be NULL, not all four:
+ *   clashes[k]          = #{i < j, j - i >= sep : d(i,j) <= cutoff}.  With sep = 1 this is the reference's clash_count(pdb, cutoff)
+ *                         (chromosome3D.pl:693-714) exactly: bonded neighbours are included and the comparison is `<=`, as at :708 — the
+ *                         "clash(<=3.5 A)" of BASELINE.md §3, by which a bead model under distance-only restraints is checked for
+ *                         collapse.  Integers only: the count is exact.
+ *   bead_clashes[k n+i] = the number of such partners of bead i, on both sides; their sum over i is exactly 2 clashes[k].
+ *   nearest[k n+i]      = min over j, |i-j| >= sep, of d(i,j): a minimum has no summation order, so it has the host's bits.  +infinity
+ *                         for a bead without such a partner (sep > max(i, n-1-i)).
+ *   chain[6 k+f]        : f = 0, 1 mean and population sd of the n-1 bond lengths d(i,i+1); f = 2, 3 those of the n-2 distances d(i,i+2);
+ *                         f = 4 the radius of gyration sqrt(mean_i |x_i - centroid|^2); f = 5 the model's extent, max over i < j of d(i,j),
+ *                         which has exact bits.  Every sd is the two-pass form — the mean, then the squared deviations in a second walk —
+ *                         never sum d^2 - n mean^2, for the reason given at c3d_ensemble_map.  (C3D_GEOMETRY_FIELDS = 6.)
+ *   cutoff must be finite and > 0 when clashes or bead_clashes is asked for; 1 <= sep <= n-1; n >= 3.
+ * c3d_separation_profile: mean, sd, contact — n doubles each, indexed by s = 0 .. n-1, any of them NULL, not all three.  For s >= 1, over
+ * the (n-s) Kp values d_k(i, i+s), k in list order:
+ *   mean[s]    = their mean: R(s), the polymer's distance against separation;
+ *   sd[s]      = their population sd about that mean, from the deviations in a second walk over the same values;
+ *   contact[s] = #{d < cutoff} / ((n-s) Kp): P(s); an exact 64-bit count, divided once.  The `<` is strict as in c3d_ensemble_map, so the
+ *                profile is the diagonal average of that map — ON PURPOSE not the `<=` of the clash count above, which is the reference's.
+ *   s = 0 gives mean 0, sd 0, contact 1, as the map's diagonal does.  cutoff is needed (finite, > 0) for contact only; n >= 2.
+ * Both: no state of the solve changes (the guarantee of c3d_compare_replicas).  Floating-point sums take no atomics and their order follows
+ * from n and the pick list alone (strided partial sums met in a fixed tree; per separation, bead chunks ascending and models in list
+ * order): two calls on the same state return the same bits, and extra models leave the replicas' entries their bits.  Counts, minima
+ * and maxima are order-free and exact.  The results agree with a host computation of the same definitions to about T 2^-53 relative,
+ * T the number of terms of the sum (n, or (n-s) Kp).
+ * C3D_ERR_INVALID, before any launch: no replicas, n < 3 (profile: n < 2), n_extra < 0 or extra models without coordinates, K >
+ * C3D_COMPARE_MAX_MODELS, every output NULL, sep outside 1..n-1, a cutoff that is not finite or <= 0 where one is needed, the pick list's
+ * refusals of c3d_ensemble_map, extra coordinates that are not finite or have |x| >= 1e6.  C3D_ERR_NOMEM: no device memory for the scratch.
+ * Scratch, one allocation per call, freed before it returns.  Geometry: 44 n K + 56 K bytes (24 n a model of coordinates, 4 + 8 + 8 a bead
+ * of counts, nearest and furthest partners, 8 + 48 a model of results): 0.4 MB at 455 beads x 20 models, 14.4 MB at 16384 x 20.  Profile:
+ * 24 n K + 4 Kp + 24 n bytes: 0.23 MB at 455 x 20, 8.3 MB at 16384 x 20 — where the three n x n maps would be 6 GiB.
+ * Stats "geometry_runs" and "separation_runs" count the calls that completed. */
+#define C3D_GEOMETRY_FIELDS 6
+int c3d_geometry_replicas(c3d_ctx* ctx, const double* extra_xyz, int n_extra, double cutoff, int sep,
+                          int64_t* clashes, int32_t* bead_clashes, double* nearest, double* chain);
+int c3d_separation_profile(c3d_ctx* ctx, const double* extra_xyz, int n_extra, const int32_t* pick, int n_pick,
+                           double cutoff, double* mean, double* sd, double* contact);
 /* rank[k] = replica index with the k-th lowest int(E_noe) (chromosome3D.pl:796-802,822-828);
  * ties broken by replica id. */
 int c3d_rank(c3d_ctx* ctx, int32_t* rank);

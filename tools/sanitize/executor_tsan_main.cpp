@@ -97,6 +97,12 @@ static void api_storm(int device_count) {
                 ok = ok && c3d_ensemble_map(c, nullptr, 0, picked, 3, 7.6, emap.data(), emap.data() + (size_t)n * n, emap.data() + 2 * (size_t)n * n) == C3D_OK;
                 ok = ok && c3d_ensemble_score(c, IF.data(), 3, nullptr, 0, nullptr, 0, 7.6, &erho[0], &erho[1]) == C3D_OK;
                 ok = ok && c3d_ensemble_map(c, nullptr, 0, picked, 0, 7.6, emap.data(), nullptr, nullptr) == C3D_ERR_INVALID;
+                std::vector<int64_t> clashes(4);
+                std::vector<int32_t> bead(4 * (size_t)n);
+                std::vector<double> nearest(4 * (size_t)n), chain(4 * C3D_GEOMETRY_FIELDS), prof(3 * (size_t)n);
+                ok = ok && c3d_geometry_replicas(c, nullptr, 0, 3.5, 1, clashes.data(), bead.data(), nearest.data(), chain.data()) == C3D_OK;
+                ok = ok && c3d_separation_profile(c, nullptr, 0, picked, 3, 7.6, prof.data(), prof.data() + n, prof.data() + 2 * (size_t)n) == C3D_OK;
+                ok = ok && c3d_geometry_replicas(c, nullptr, 0, 3.5, n, clashes.data(), nullptr, nullptr, nullptr) == C3D_ERR_INVALID;
                 if (what == 2) { unsigned long long a, b, d; ok = ok && c3d_debug_tear16(c, 4, &a, &b, &d) == C3D_OK; }
             }
             if (!ok) { fprintf(stderr, "api storm thread %d: %s\n", t, c3d_last_error()); ++failures; }

@@ -315,4 +315,68 @@ hipError_t launch_ensemble_corr(const double* A, const double* B, int n, int ran
     return hipSuccess;
 }
 
+// c3d_geometry_replicas / c3d_separation_profile: restated on the host over the "device" memory as well
+static double stub_dist(const double* x, int i, int j) {
+    const double ux = x[3 * i] - x[3 * j], uy = x[3 * i + 1] - x[3 * j + 1], uz = x[3 * i + 2] - x[3 * j + 2];
+    return sqrt(((ux * ux) + uy * uy) + uz * uz);
+}
+hipError_t launch_geometry(const double* xyz, int n, int K, double cutoff, int sep, int* bead_clashes, double* nearest, double* furthest, long long* clashes,
+                           double* chain, hipStream_t) {
+    LaunchScope ls;
+    for (int k = 0; k < K; ++k) {
+        const double* x = xyz + (size_t)k * 3 * n;
+        long long both = 0;
+        double extent = 0, cen[3] = {0, 0, 0}, g = 0;
+        for (int i = 0; i < n; ++i) {
+            int cnt = 0;
+            double lo = INFINITY, hi = 0;
+            for (int j = 0; j < n; ++j) {
+                const double d = stub_dist(x, i, j);
+                if ((i > j ? i - j : j - i) >= sep) { cnt += d <= cutoff ? 1 : 0; lo = d < lo ? d : lo; }
+                hi = d > hi ? d : hi;
+            }
+            bead_clashes[(size_t)k * n + i] = cnt; nearest[(size_t)k * n + i] = lo; furthest[(size_t)k * n + i] = hi;
+            both += cnt;
+            extent = hi > extent ? hi : extent;
+            for (int q = 0; q < 3; ++q) cen[q] += x[3 * i + q];
+        }
+        clashes[k] = both / 2;
+        double* f = chain + (size_t)6 * k;
+        for (int gap = 1; gap <= 2; ++gap) {
+            double s = 0, v = 0;
+            for (int i = 0; i + gap < n; ++i) s += stub_dist(x, i, i + gap);
+            const double mu = s / (double)(n - gap);
+            for (int i = 0; i + gap < n; ++i) v += (stub_dist(x, i, i + gap) - mu) * (stub_dist(x, i, i + gap) - mu);
+            f[2 * gap - 2] = mu; f[2 * gap - 1] = sqrt(v / (double)(n - gap));
+        }
+        for (int i = 0; i < n; ++i)
+            for (int q = 0; q < 3; ++q) g += (x[3 * i + q] - cen[q] / n) * (x[3 * i + q] - cen[q] / n);
+        f[4] = sqrt(g / n); f[5] = extent;
+    }
+    return hipSuccess;
+}
+hipError_t launch_separation_profile(const double* xyz, int n, const int* pick, int Kp, double cutoff, double* mean, double* sd, double* contact, hipStream_t) {
+    LaunchScope ls;
+    for (int s = 0; s < n; ++s) {
+        const double terms = (double)(n - s) * (double)Kp;
+        double sum = 0, dev = 0;
+        long long cnt = 0;
+        for (int k = 0; k < Kp; ++k)
+            for (int i = 0; i + s < n; ++i) {
+                const double d = stub_dist(xyz + (size_t)pick[k] * 3 * n, i, i + s);
+                sum += d;
+                cnt += d < cutoff ? 1 : 0;
+            }
+        mean[s] = sum / terms;
+        for (int k = 0; k < Kp; ++k)
+            for (int i = 0; i + s < n; ++i) {
+                const double e = stub_dist(xyz + (size_t)pick[k] * 3 * n, i, i + s) - mean[s];
+                dev += e * e;
+            }
+        if (sd) sd[s] = sqrt(dev / terms);
+        if (contact) contact[s] = (double)cnt / terms;
+    }
+    return hipSuccess;
+}
+
 }  // namespace c3d
