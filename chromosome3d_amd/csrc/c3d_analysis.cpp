@@ -315,7 +315,7 @@ struct CompareScratch : Carve {
     Slot<unsigned> ke;
     Slot<unsigned long long> keys;
     CompareScratch(int n, int K, size_t m, size_t slots) {
-        const size_t nb = (size_t)(K + c3d::kCmpModels - 1) / c3d::kCmpModels;
+        const size_t nb = (size_t)c3d::model_blocks(K);
         xyz = take<double>(3 * (size_t)n * K);
         ke = take<unsigned>(m * K);
         keys = take<unsigned long long>(slots);

@@ -390,10 +390,16 @@ hipError_t launch_if_rank_sort(double* M, int n, int range, unsigned long long* 
 // distances (if_rank_key_slots(m) slots), the sort, then ke[pair] = first + last sorted position of the pair's tie group (average rank =
 // ke / 2 + 1) and rowsum[i] = sum_j>i d_ij; launch_compare_table, over K models' ke (K x m) and rowsum (K x n): sums[k] = sum of model k's
 // distances, table[a][b] = { sum (ra - mean)(rb - mean), sum (sums[b] / sums[a] d_a - d_b)^2 } through `partial`, which holds
-// compare_table_chunks(m, K) x nb x nb x 512 doubles, nb = ceil(K / kCmpModels): per-chunk sums, added in chunk order.
+// compare_table_chunks(m, K) x nb x nb x 512 doubles, nb = model_blocks(K): per-chunk sums, added in chunk order.
 constexpr int kCmpModels = 16;
+// Model blocks: a workgroup of 256 threads takes kCmpModels models a and kCmpModels models b, thread t the pair of a's model pair_row(t)
+// and b's model pair_col(t) (k_cmp_table, k_sup_cov, k_sup_residual); K models are model_blocks(K) blocks a side.
+constexpr int model_blocks(int K) { return (K + kCmpModels - 1) / kCmpModels; }
+static_assert(kCmpModels == 16, "pair_row shifts by log2(kCmpModels), and a block of pairs is one 256-thread workgroup");
+constexpr int pair_row(int tid) { return tid >> 4; }
+constexpr int pair_col(int tid) { return tid & (kCmpModels - 1); }
 inline size_t compare_chunk_pairs(size_t m, int K) {       // a multiple of the 64-pair tile; about 2048 workgroups, 64 chunks at least
-    const size_t nb = (size_t)(K + kCmpModels - 1) / kCmpModels, want = 2048 / (nb * nb) > 64 ? 2048 / (nb * nb) : 64;
+    const size_t nb = (size_t)model_blocks(K), want = 2048 / (nb * nb) > 64 ? 2048 / (nb * nb) : 64;
     return ((m + want - 1) / want + 63) / 64 * 64;
 }
 inline int compare_table_chunks(size_t m, int K) {
@@ -406,7 +412,8 @@ hipError_t launch_compare_ranks(const double* x, int n, unsigned long long* keys
 hipError_t launch_compare_table(const double* xyz, const unsigned* ke, const double* rowsum, int n, int K, size_t m, double* sums,
                                 double* partial, double* table, hipStream_t s);
 // The models of a run in one frame (c3d_superpose_replicas, c3d_rmsd_table; k_sup_*).  A model is n x 3 doubles, xyz interleaved.
-// launch_superpose_gather64: the fp64 state X [nrep][3][np] as such models, every value as it is (fp32 state: launch_compare_coords).
+// launch_superpose_gather64: the fp64 state X [nrep][3][np] as such models, every value as it is (fp32 state: launch_compare_coords; both
+// are k_models_gather, and the two stores below k_models_scatter: c3d_score_core.h).
 // launch_superpose_centre: cent[k] = the centroid of model k, the model centred on it in place (K models).
 // launch_superpose_fit: every model of A (KA) onto every model of B (KB), both centred: cov[a][b][kSupCov] (c3d_superpose.h), then
 // fit[a][b][kSupFit] = Q, mirror bit, eigenvalue and mirrored[a][b]; res[a][b] = sum |Q a_i - b_i|^2 unless res is null.  ident: the pair
@@ -419,7 +426,7 @@ hipError_t launch_compare_table(const double* xyz, const unsigned* ke, const dou
 constexpr int kSupNoIdent = -(1 << 30);
 inline int superpose_chunks(int n) { return (n + 63) / 64; }
 inline size_t superpose_partial_doubles(int n, int KB) {
-    return (size_t)superpose_chunks(n) * (size_t)((KB + kCmpModels - 1) / kCmpModels) * 256 * kSupCov;
+    return (size_t)superpose_chunks(n) * (size_t)model_blocks(KB) * 256 * kSupCov;
 }
 hipError_t launch_superpose_gather64(const double* X, int n, int np, int nrep, double* xyz, hipStream_t s);
 hipError_t launch_superpose_centre(double* xyz, int n, int K, double* cent, hipStream_t s);

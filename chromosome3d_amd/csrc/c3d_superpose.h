@@ -1,4 +1,4 @@
-// c3d_superpose.h — the per-pair arithmetic of the superposition kernels (c3d_score.hip k_sup_solve), free of the HIP runtime so that the
+// c3d_superpose.h — the per-pair arithmetic of the superposition kernels (c3d_score_superpose.inc k_sup_solve), free of the HIP runtime so that the
 // same lines compile for the host: the least-squares rotation of one centred model onto another from their 3 x 3 covariance.
 //
 // Horn (J. Opt. Soc. Am. A 4, 629, 1987): with S = sum a_i b_i^T, the unit quaternion of the rotation R that minimises sum |R a_i - b_i|^2

@@ -376,7 +376,7 @@ int c3d_get_energies(c3d_ctx* ctx, double* e);
  * the context goes, holds 8 n^2 bytes (matrix, then ranks) at every size, and with device ranks 8 bytes per sort slot — the ranked pairs
  * i < j, (n-range)(n-range+1)/2, rounded up to a power of two and to 4096 at least: 2 GiB + 1 GiB at 16384 beads, where the host path needs about 10 GB of host memory instead. */
 int c3d_score_replicas(c3d_ctx* ctx, const double* IF, int range, int32_t* satisfied, double* sum_dev, double* rho);
-/* The models of a run against one another, on the device: the two numbers of the reference's output_models/similarity.txt
+/* The models of a run against one another, on the device (c3d_score_compare.inc k_cmp_*): the two numbers of the reference's output_models/similarity.txt
  * (c3d_model_similarity below) for every ordered pair of models, without reading coordinates back.
  * K = n_replicas + n_extra models of n beads: model k < n_replicas is replica k at its current coordinates (fp32, taken as doubles
  * unchanged); model n_replicas + e is extra_xyz + 3 n e (xyz interleaved, doubles; e.g. a bundled model).  spearman, rmsd: K x K row-major,
@@ -395,7 +395,7 @@ int c3d_score_replicas(c3d_ctx* ctx, const double* IF, int range, int32_t* satis
 int c3d_compare_replicas(c3d_ctx* ctx, const double* extra_xyz, int n_extra, double* spearman, double* rmsd);
 /* Test hook: rank (n(n-1)/2 doubles, pairs i<j in row order) = the average ranks of replica `replica`'s distances as the device computes them */
 int c3d_debug_distance_ranks(c3d_ctx* ctx, int replica, double* rank);
-/* The models of a run in one frame, on the device (c3d_score.hip k_sup_*): a run's replicas come out in arbitrary frames and, mirror images
+/* The models of a run in one frame, on the device (c3d_score_superpose.inc k_sup_*): a run's replicas come out in arbitrary frames and, mirror images
  * having equal energy under distance restraints, in both hands.  c3d_superpose_replicas fits every replica onto one target:
  * replica `reference` (0..n_replicas-1) at its current coordinates, or, with reference = -1, ref_xyz (n x 3 doubles, xyz interleaved, e.g. a
  * bundled model; checked as the extra models of c3d_compare_replicas are).  The models are the replicas' state: on a precision-64 context the
@@ -432,7 +432,7 @@ int c3d_debug_distance_ranks(c3d_ctx* ctx, int replica, double* rank);
 int c3d_superpose_replicas(c3d_ctx* ctx, int reference, const double* ref_xyz, int flags, int iters, double* rmsd, int32_t* mirrored,
                            double* mean_xyz, double* rmsf);
 int c3d_rmsd_table(c3d_ctx* ctx, const double* extra_xyz, int n_extra, int flags, double* rmsd, int32_t* mirrored);
-/* The ensemble itself, on the device (c3d_score.hip k_ens_*): what the models say about every bead pair together.  A mean of superposed
+/* The ensemble itself, on the device (c3d_score_ensemble.inc k_ens_*): what the models say about every bead pair together.  A mean of superposed
  * coordinates shrinks wherever the models disagree; the quantity that stays meaningful for a population is the distance map.
  * Models: K = n_replicas + n_extra, numbered as in c3d_compare_replicas; the replicas are taken as c3d_superpose_replicas takes them (on a
  * precision-64 context the fp64 state bit for bit, else the floats taken as doubles unchanged); extra models are n x 3 doubles, xyz
@@ -468,7 +468,7 @@ int c3d_ensemble_map(c3d_ctx* ctx, const double* extra_xyz, int n_extra, const i
                      double* mean, double* sd, double* contact);
 int c3d_ensemble_score(c3d_ctx* ctx, const double* IF, int range, const double* extra_xyz, int n_extra,
                        const int32_t* pick, int n_pick, double cutoff, double* rho_mean, double* rho_contact);
-/* A model's geometry and the distance against genomic separation, on the device (c3d_score.hip k_geo_*, k_sep_*): all-pairs reductions over
+/* A model's geometry and the distance against genomic separation, on the device (c3d_score_geometry.inc k_geo_*, k_sep_*): all-pairs reductions over
  * the models of the ensemble entries above — K = n_replicas + n_extra, numbered as in c3d_compare_replicas, the replicas taken as
  * c3d_superpose_replicas takes them (precision 64: the fp64 state bit for bit, else the floats taken as doubles unchanged), extra models n x 3
  * doubles checked as there; pick / n_pick with exactly the meaning and limits they have in c3d_ensemble_map.  The distance d(i,j) is

@@ -1,4 +1,4 @@
-"""fp64 restatement of the superposition of a run's models (c3d_superpose_replicas, c3d_rmsd_table; chromosome3d_amd/csrc/c3d_score.hip
+"""fp64 restatement of the superposition of a run's models (c3d_superpose_replicas, c3d_rmsd_table; chromosome3d_amd/csrc/c3d_score_superpose.inc
 k_sup_*) in numpy, by another algorithm than the device's: Kabsch's rotation from the SVD of the centred covariance with the determinant
 correction, where the device takes the largest eigenvector of Horn's quaternion matrix by Jacobi sweeps.  The mirror decision compares
 the two candidate fits' residuals, where the device compares two eigenvalues.

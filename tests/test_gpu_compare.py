@@ -1,4 +1,4 @@
-"""The models of a run against one another on the device (c3d_compare_replicas, csrc/c3d_score.hip k_cmp_*; hook c3d_debug_distance_ranks).
+"""The models of a run against one another on the device (c3d_compare_replicas, csrc/c3d_score_compare.inc k_cmp_*; hook c3d_debug_distance_ranks).
 
 The host side of every table is pipeline.model_similarity (c3d_model_similarity, fp64) on the replicas' float coordinates cast to double;
 the host side of the hook is a numpy restatement of the average ranks over sqrt(((ux ux) + uy uy) + uz uz) in float64.

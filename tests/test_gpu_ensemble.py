@@ -1,4 +1,4 @@
-"""The ensemble's distance map on the device (c3d_ensemble_map, c3d_ensemble_score; csrc/c3d_score.hip k_ens_*) against its numpy
+"""The ensemble's distance map on the device (c3d_ensemble_map, c3d_ensemble_score; csrc/c3d_score_ensemble.inc k_ens_*) against its numpy
 restatement tests/ensemble_ref.py, which tests/test_ensemble_ref.py holds to scipy and to the host helper.
 
 Shapes, the smallest at which each part can still go wrong.  k_ens_map gives a workgroup a 64 x 64 tile of the upper triangle and stages

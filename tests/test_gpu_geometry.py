@@ -1,4 +1,4 @@
-"""Model geometry on the device (c3d_geometry_replicas, c3d_separation_profile; csrc/c3d_score.hip k_geo_*, k_sep_*) against the numpy
+"""Model geometry on the device (c3d_geometry_replicas, c3d_separation_profile; csrc/c3d_score_geometry.inc k_geo_*, k_sep_*) against the numpy
 restatement tests/geometry_ref.py, which tests/test_geometry_ref.py holds to the reference's clash counts, to tests/util.chain_stats and
 to tests/ensemble_ref.
 

@@ -1,4 +1,4 @@
-"""Device scoring of large maps (csrc/c3d_score.hip): the IF ranks on the GPU (k_rank_*, option device_ranks, stat device_rank_runs, hook
+"""Device scoring of large maps (csrc/c3d_score.hip, shared helpers in c3d_score_core.h): the IF ranks on the GPU (k_rank_*, option device_ranks, stat device_rank_runs, hook
 c3d_debug_if_ranks) and models of any extent (the sized-histogram re-run, stat score_wide_runs).
 
   1. the device's ranks are the average ranks, bit for bit          2. the same scores from either rank source

@@ -1,4 +1,4 @@
-"""The models of a run in one frame on the device (c3d_superpose_replicas, c3d_rmsd_table; csrc/c3d_score.hip k_sup_*) against the numpy
+"""The models of a run in one frame on the device (c3d_superpose_replicas, c3d_rmsd_table; csrc/c3d_score_superpose.inc k_sup_*) against the numpy
 restatement tests/superpose_ref.py, which fits by SVD where the device diagonalises Horn's quaternion matrix.
 
 Shapes (a staged chunk is 64 beads, a table block 16 x 16 models): n = 4, 37, 255, 256, 257, 455 with K = 1, 2, 20 replicas; 2561 beads x 2
