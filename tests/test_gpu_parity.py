@@ -746,11 +746,29 @@ def test_cluster_launch_without_completion_mark_is_not_accepted(solver, cid, nre
     or CU-masked device, an uneven dispatch — must not hand stale state back as a result.  The kernel counts the workgroups
     that reach their last step and the last one writes a mark the host checks; here the host expects one workgroup more than
     exist (test hook), so the mark never comes: the range is re-run step by step and ends in the per-step path's bits.
-    chr21_1mb: one workgroup per replica (P == 1, nobody waits for anybody: the case a time-out cannot catch)."""
+    Both problems run as several workgroups per replica (chr21_1mb x 4, 37 beads: five parts of 4 x 2 rows since the planner's round 4
+    cost model; it was the single-workgroup case before).  The single workgroup has the test below."""
     xa, va, ea, ta = _anneal(solver, cid, nrep, 0)
     before = solver.stat("cluster_incomplete"), solver.stat("resident_fallbacks")
     solver.set_option("cluster_inject_incomplete", 1)
     xb, vb, eb, tb = _anneal(solver, cid, nrep, 1)
+    assert solver.stat("cluster_incomplete") == before[0] + 1 and solver.stat("resident_fallbacks") == before[1] + 1
+    assert tb[2] > 40                           # ran step by step after the rejected launch
+    assert np.array_equal(xa, xb) and np.array_equal(va, vb) and np.array_equal(ea, eb)
+
+
+def test_cluster_launch_of_one_workgroup_without_completion_mark_is_not_accepted(solver):
+    """The case a time-out cannot catch: one workgroup per replica (P == 1), where nobody waits for anybody.  chr21_1mb x 4 under a
+    forced 12 x 4 geometry (48 rows for its 37 beads); otherwise as the test above."""
+    xa, va, ea, ta = _anneal(solver, "chr21_1mb", 4, 0)
+    before = solver.stat("cluster_incomplete"), solver.stat("resident_fallbacks")
+    solver.set_option("cluster_geometry", 1244)
+    try:
+        solver.set_option("cluster_inject_incomplete", 1)
+        xb, vb, eb, tb = _anneal(solver, "chr21_1mb", 4, 1)
+        assert solver.stat("cluster_ok") == 1 and solver.stat("cluster_parts") == 1 and solver.stat("cluster_compute_waves") == 12
+    finally:
+        solver.set_option("cluster_geometry", 0)
     assert solver.stat("cluster_incomplete") == before[0] + 1 and solver.stat("resident_fallbacks") == before[1] + 1
     assert tb[2] > 40                           # ran step by step after the rejected launch
     assert np.array_equal(xa, xb) and np.array_equal(va, vb) and np.array_equal(ea, eb)
