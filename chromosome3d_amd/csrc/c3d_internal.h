@@ -250,6 +250,10 @@ size_t sym_scratch_floats(const DevModel& m);
 void sym_tile_list(const DevModel& m, int2* out);
 hipError_t launch_step_sym(const DevModel& m, const DevStep& p, const DevFire& fp, const DevBuffers& b, int parity, const void* tiles,
                            float* scratch, hipStream_t s);
+// step_scalars<true> on `rows` rows of (psum[4], FireState), a thread a row (c3d_sym.hip k_step_scalars; c3d_debug_step_scalars):
+// scalars [rows][6] = lam, cmx, cmy, cmz, keep, mix; out = the state it leaves
+hipError_t launch_step_scalars(const DevModel& m, const DevStep& p, const DevFire& fp, int rows, const float* psum, const FireState* in,
+                               float* scalars, FireState* out, hipStream_t s);
 // fp64 step (c3d_f64.hip, option "precision" = 64): the CPU restatement's algorithm in its precision on the GPU, one launch per SA
 // step of a replica group (k64_step, k64_step_chunked beyond 2560 beads), double buffered by step parity like the fp32 per-step path.
 // Layouts (np = cols64(n): n rounded up to 128): T [n][np] targets in Angstrom (0.1 * t10, 0 = none); X, V [2][nrep][3][np] SoA;

@@ -519,9 +519,11 @@ extern "C" int c3d_run(c3d_ctx* c) {
     }
     if (int rc = run_ops(c, nfixed)) return rc;
     if (early) {
-        // chunks of check_every steps until every replica's RMS force < gtol
+        // chunks of exactly check_every steps (> 0: c3d_set_schedule) until every replica's RMS force < gtol: the test falls after the steps
+        // c3o_run_schedule tests, (it + 1) % check_every == 0 counted from the stage's start.  Odd or even: a range of any length runs from
+        // either parity, and the sums read here and the graph keys follow c->parity.
         while (c->pc < c->program.size()) {
-            const size_t chunk = std::min<size_t>((size_t)(c->check_every & ~1), c->program.size() - c->pc);
+            const size_t chunk = std::min<size_t>((size_t)c->check_every, c->program.size() - c->pc);
             if (int rc = run_ops(c, chunk)) return rc;
             double rms = 0;
             if (int rc = max_rms_force(c, &rms)) return rc;
@@ -544,6 +546,35 @@ extern "C" int c3d_last_timing(const c3d_ctx* c, double* ms_total, long* steps, 
     if (ms_total) *ms_total = c->last_ms;
     if (steps) *steps = c->last_steps;
     if (launches) *launches = c->last_launches;
+    return C3D_OK;
+}
+
+// Test hook: step_scalars<true> on a table of rows (c3d.h).  The model, the FIRE values and the step are built by the functions every
+// launch uses (dev_model, dev_fire, dev_step), so the table also covers what the host folds into them (acc, t_fac, inv_n).
+extern "C" int c3d_debug_step_scalars(c3d_ctx* c, int kind, float dt, float t_bath, int rows, const float* psum, const float* state_in,
+                                      const int32_t* npos_in, float* scalars, float* state_out, int32_t* npos_out) {
+    if (!c || !psum || !state_in || !npos_in || !scalars || !state_out || !npos_out || rows < 1 || rows > (1 << 20))
+        return fail(C3D_ERR_INVALID, "c3d_debug_step_scalars: bad arguments");
+    if (!(kind == 0 || kind == 1 || kind == 2 || kind == 3 || kind == 5 || kind == 6))
+        return fail(C3D_ERR_INVALID, "c3d_debug_step_scalars: kind is 0, 1, 2, 3, 5 or 6");
+    if (c->n < 1) return fail(C3D_ERR_INVALID, "c3d_debug_step_scalars: set the targets first (the bead count enters the temperature)");
+    C3D_ENTRY(c, unit_bit(UNIT_SYM));
+    std::vector<c3d::FireState> st((size_t)rows);
+    for (int r = 0; r < rows; ++r) st[r] = c3d::FireState{state_in[2 * r], state_in[2 * r + 1], npos_in[r], 0};
+    DevTmp<float> d_psum, d_out;
+    DevTmp<c3d::FireState> d_in, d_st;
+    HIP_TRY(hipMalloc(&d_psum.p, sizeof(float) * 4 * (size_t)rows));
+    HIP_TRY(hipMalloc(&d_out.p, sizeof(float) * 6 * (size_t)rows));
+    HIP_TRY(hipMalloc(&d_in.p, sizeof(c3d::FireState) * (size_t)rows));
+    HIP_TRY(hipMalloc(&d_st.p, sizeof(c3d::FireState) * (size_t)rows));
+    HIP_TRY(hipMemcpyAsync(d_psum.p, psum, sizeof(float) * 4 * (size_t)rows, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_in.p, st.data(), sizeof(c3d::FireState) * (size_t)rows, hipMemcpyHostToDevice, c->stream));
+    LAUNCH_TRY("step scalars launch", c3d::launch_step_scalars(dev_model(c), dev_step(c, kind, dt, 1.0f, 1.0f, 0.85f, t_bath), dev_fire(c), rows,
+                                                               d_psum.p, d_in.p, d_out.p, d_st.p, c->stream));
+    HIP_TRY(hipMemcpyAsync(scalars, d_out.p, sizeof(float) * 6 * (size_t)rows, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(st.data(), d_st.p, sizeof(c3d::FireState) * (size_t)rows, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int r = 0; r < rows; ++r) { state_out[2 * r] = st[r].dt; state_out[2 * r + 1] = st[r].alpha; npos_out[r] = st[r].npos; }
     return C3D_OK;
 }
 

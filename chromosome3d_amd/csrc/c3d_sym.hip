@@ -241,6 +241,25 @@ hipError_t launch_step_sym(const DevModel& m, const DevStep& p, const DevFire& f
     return with_pot(m.noe_pot, [&](auto POT) { return with_bool(sym_rs1(m), [&](auto RS1) { return sym_go<POT, RS1>(m, p, fp, b, parity, t, scratch, s); }); });
 }
 
+// ---- the controller as a table (c3d_debug_step_scalars) ----------------------------------------------------------------------------
+// step_scalars<true> — what k_update_sym above, k_step and k_cluster_tp call once per replica and step — on `rows` independent
+// (sums, state) pairs, a thread a row: the scalars and the state it leaves, stored as they are.
+__global__ void k_step_scalars(DevModel m, DevStep p, DevFire fp, int rows, const float4* __restrict__ psum, const FireState* __restrict__ in,
+                               StepScalars* __restrict__ out, FireState* __restrict__ st_out) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= rows) return;
+    FireState st = in[r];
+    out[r] = step_scalars<true>(m, p, fp, psum[r], st);
+    st_out[r] = st;
+}
+static_assert(sizeof(StepScalars) == 6 * sizeof(float), "c3d_debug_step_scalars returns six floats a row");
+hipError_t launch_step_scalars(const DevModel& m, const DevStep& p, const DevFire& fp, int rows, const float* psum, const FireState* in,
+                               float* scalars, FireState* out, hipStream_t s) {
+    hipLaunchKernelGGL(k_step_scalars, dim3((rows + 63) / 64), dim3(64), 0, s, m, p, fp, rows, reinterpret_cast<const float4*>(psum), in,
+                       reinterpret_cast<StepScalars*>(scalars), out);
+    return hipGetLastError();
+}
+
 hipError_t preload_sym_unit() {
     hipFuncAttributes a;
     return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_update_sym<0>));

@@ -74,6 +74,7 @@ SIGNATURES = {
     "c3d_get_stat": (_i, [_vp, C.c_char_p, _dp]),
     "c3d_step_kernel_name": (C.c_char_p, [_vp]),
     "c3d_debug_tear16": (_i, [_vp, _i, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
+    "c3d_debug_step_scalars": (_i, [_vp, _i, _f, _f, _i, _fp, _fp, _i32p, _fp, _fp, _i32p]),
     "c3d_dg_smoothed_bounds": (_i, [_vp, _fp, _fp]),
     "c3d_debug_if_ranks": (_i, [_vp, _dp, _i, _dp, _dp, C.POINTER(C.c_size_t)]),
     "c3d_eval": (_i, [_vp, _f, _f, _f, _fp, _dp]),

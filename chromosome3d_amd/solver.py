@@ -199,6 +199,18 @@ class Solver:
         _l.check(self._L.c3d_debug_tear16(self._h, iterations, C.byref(a), C.byref(b), C.byref(c)))
         return a.value, b.value, c.value
 
+    def debug_step_scalars(self, kind, dt, t_bath, psum, state, npos):
+        """The fp32 step controller as a table (c3d_debug_step_scalars): psum [K, 4], state [K, 2] = (dt, alpha), npos [K] ->
+        (scalars [K, 6] = lambda, v_cm x y z, keep, mix; state out [K, 2]; npos out [K]) under the context's model and FIRE values."""
+        psum, state = _l.as_f32(psum), _l.as_f32(state)
+        npos = np.ascontiguousarray(npos, dtype=np.int32)
+        K = npos.shape[0]
+        assert psum.shape == (K, 4) and state.shape == (K, 2)
+        sc, so, no = np.empty((K, 6), dtype=np.float32), np.empty((K, 2), dtype=np.float32), np.empty(K, dtype=np.int32)
+        _l.check(self._L.c3d_debug_step_scalars(self._h, int(kind), float(dt), float(t_bath), K, _l.fptr(psum), _l.fptr(state), _l.i32ptr(npos),
+                                                _l.fptr(sc), _l.fptr(so), _l.i32ptr(no)))
+        return sc, so, no
+
     @property
     def step_kernel_name(self):
         return self._L.c3d_step_kernel_name(self._h).decode()

@@ -331,6 +331,14 @@ int c3d_get_stat(const c3d_ctx* ctx, const char* key, double* value);
  * workgroup, a consumer workgroup on every other CU, the context's stream) for `iterations` rewrites of 1024 units and returns the number
  * of unit reads, of TORN units (must be 0) and of reads that saw a new value. */
 int c3d_debug_tear16(c3d_ctx* ctx, int iterations, unsigned long long* unit_reads, unsigned long long* torn, unsigned long long* fresh);
+/* Test hook: the fp32 step controller as a table.  One step of `kind` (0 / 1 MD, 2 / 3 FIRE, 5 / 6 two-point step length; dt and t_bath as
+ * a stage gives them) is decided for `rows` independent rows by the function every fp32 step kernel calls once per replica, with the
+ * context's own model (mass, fbeta, bead count) and FIRE values.  Row r: psum[4 r ..] = the previous evaluation's four replica sums (MD:
+ * sum v^2, sum vx, vy, vz; FIRE: v.F, F.F, v.v, -; two-point: s.y, F.F, y.y, s.s), state_in[2 r ..] = (dt, alpha), npos_in[r].  Returns
+ * scalars[6 r ..] = (lambda, v_cm x, y, z, keep, mix) and the state the step leaves in state_out / npos_out.  Needs the bead count (targets set);
+ * touches nothing of the solve. */
+int c3d_debug_step_scalars(c3d_ctx* ctx, int kind, float dt, float t_bath, int rows, const float* psum, const float* state_in,
+                           const int32_t* npos_in, float* scalars, float* state_out, int32_t* npos_out);
 /* Test hook of A7 (c3d_embed_replicas): U, L (n*n each, row-major) = the smoothed distance bounds the embedding draws its trial distances
  * from — b0 on |i-j| = 1, the target on restrained pairs, [r0_rep x the last stage's repel, 1e30] elsewhere, then all-pairs shortest
  * paths on U, the inverse triangle inequality on L, L <= U.  The same kernels and arguments as the embedding; no bead limit of its own.

@@ -1,0 +1,438 @@
+"""A Python twin of the oracle's schedule runner (c3o_run_schedule with c3o_md_step, c3o_fire_step, c3o_bb_step: oracle/c3d_oracle.c) that
+says, step by step, which branch of the step controller it took — and a table of named cases built so that every branch is taken, with a
+margin, on a trajectory float32 can follow.  The forces are the oracle's own (O.energy_force), the Maxwell start its own
+(O.init_velocities); the statements around them are restated here one for one, so that each can be MUTATED: a case is only worth running
+on the GPU if a subtly wrong controller would end far from it (MUTATIONS, tests/test_controller_ref.py).
+
+branch names   fire: reset | hold | grow | cap        (power test failed | npos <= n_min | dt grows | dt held at dt_max)
+               md:   plain | floor | clamp0           (T floored at 1e-2 | Berendsen lambda^2 clamped at 0; both: floor+clamp0)
+               bb:   first | bb | negcurv, + "+lo" / "+hi" where the length was bounded by 1e-7 / 1e2
+"""
+import functools
+
+import numpy as np
+
+from oracle import oracle as O
+from tests.util import oracle_fire_from, oracle_model_from, synthetic_if
+
+KBOLTZ, ACCEL = 0.0019872, 418.4
+SEED = 82364
+
+# name -> what the mutated twin does differently (the list the GPU test's sensitivity rests on)
+MUTATIONS = {
+    "nmin_ge": "the n_min gate reads npos >= n_min",
+    "no_dt_max": "dt grows without the dt_max cap",
+    "reset_keeps_dt": "an uphill reset leaves dt as it was",
+    "reset_keeps_alpha": "an uphill reset leaves alpha as it was",
+    "reset_keeps_v": "an uphill reset leaves the velocities as they were",
+    "alpha_not_decayed": "alpha is not multiplied by f_alpha",
+    "no_max_step_fire": "FIRE moves without the per-bead max_step cap",
+    "floor_1e3": "the temperature floor is 1e-3",
+    "sqrt_abs_clamp": "lambda = sqrt(|lambda^2|) instead of the clamp at 0",
+    "bb_parity_swapped": "the two two-point lengths on each other's parity",
+    "bb_first_no_mass": "the first two-point length without / mass",
+    "fbeta_10": "fbeta is a literal 10",
+    "mass_100": "the mass is a literal 100",
+    "s_noe_10": "s_noe is a literal 10",
+}
+
+
+def _copy_model(m, **kw):
+    c = O.Model.from_buffer_copy(m)
+    for k, v in kw.items():
+        setattr(c, k, v)
+    return c
+
+
+class Step:
+    """stage, step of the stage, kind that ran (0 / 1 / 2 / 5), branch, beads the max_step cap acted on, margin of the step's discontinuous
+    decision (None: it has none), steps since the controller's state was fresh (stage start or hand-over), RMS force of the evaluation"""
+    __slots__ = ("stage", "it", "kind", "branch", "ncap", "margin", "since", "rms")
+
+    def __init__(self, stage, it, kind, branch, ncap=0, margin=None, since=0, rms=None):
+        self.stage, self.it, self.kind, self.branch, self.ncap, self.margin, self.since, self.rms = stage, it, kind, branch, ncap, margin, since, rms
+
+
+def _capped(dr, max_step):
+    d2 = (dr * dr).sum(1)
+    over = d2 > max_step * max_step
+    sc = np.where(over, max_step / np.sqrt(np.where(over, d2, 1.0)), 1.0)
+    return sc[:, None] * dr, int(over.sum())
+
+
+def run_twin(om, d10, stages, fire, replica, x0, tp=1000, checkpoints=(), round32=False, mut=None, seed=SEED):
+    """c3o_run_schedule restated.  om / fire: oracle Model / FireParams; stages: rows (kind, nsteps, dt, w_all, w_vdw, repel_s, t_bath);
+    tp: final_minimiser_steps.  Returns (x centred, v, log [Step per step], {k: (x centred, v) after k steps for k in checkpoints}).
+    round32: coordinates and velocities rounded to float32 after every step (the conditioning probe).  mut: one name of MUTATIONS."""
+    n = om.n
+    mass = 100.0 if mut == "mass_100" else om.mass
+    fbeta = 10.0 if mut == "fbeta_10" else om.fbeta
+    fm = _copy_model(om, s_noe=10.0) if mut == "s_noe_10" else om
+    x = np.array(x0, dtype=np.float64)
+    v = np.zeros_like(x)
+    log, cps, done, prev_kind = [], {}, 0, -1
+    tp = max(int(tp), 2)
+
+    def after_step():
+        nonlocal x, v, done
+        if round32:
+            x, v = x.astype(np.float32).astype(np.float64), v.astype(np.float32).astype(np.float64)
+        done += 1
+        if done in checkpoints:
+            cps[done] = (x - x.mean(0), v.copy())
+
+    for s, (kind, nsteps, dt, w_all, w_vdw, repel_s, t_bath) in enumerate(stages):
+        force = lambda: O.energy_force(fm, d10, x, w_all, w_vdw, repel_s)[0]
+        if kind in (2, 5):
+            fdt, alpha, npos = fire.dt_start, fire.alpha_start, 0
+            L = [0.0, 0.0, 0.0, 0.0]
+            nbb = min(nsteps, tp) if kind == 5 else 0
+            v[:] = 0.0
+            for it in range(nsteps):
+                if it == nbb and nbb > 0:
+                    fdt, alpha, npos, L = fire.dt_start, fire.alpha_start, 0, [0.0, 0.0, 0.0, 0.0]
+                    v[:] = 0.0
+                F = force()
+                if it >= nbb:                                   # c3o_fire_step
+                    vf, ff, vv = float((v * F).sum()), float((F * F).sum()), float((v * v).sum())
+                    margin = L[0] / np.sqrt(L[1] * L[2]) if L[1] * L[2] > 0 else 0.0
+                    if L[0] > 0:
+                        mix = alpha * np.sqrt(L[2] / (L[1] if L[1] > 1e-30 else 1e-30))
+                        v = (1.0 - alpha) * v + mix * F
+                        branch = "hold"
+                        if (npos >= fire.n_min) if mut == "nmin_ge" else (npos > fire.n_min):
+                            grown = fdt * fire.f_inc
+                            branch = "grow" if grown < fire.dt_max else "cap"
+                            fdt = grown if (grown < fire.dt_max or mut == "no_dt_max") else fire.dt_max
+                            if mut != "alpha_not_decayed":
+                                alpha *= fire.f_alpha
+                        npos += 1
+                    else:
+                        branch = "reset"
+                        if mut != "reset_keeps_v":
+                            v[:] = 0.0
+                        if mut != "reset_keeps_alpha":
+                            alpha = fire.alpha_start
+                        if mut != "reset_keeps_dt":
+                            fdt *= fire.f_dec
+                        npos = 0
+                    v = v + (fdt * ACCEL / mass) * F
+                    dr = fdt * v
+                    if mut == "no_max_step_fire":
+                        ncap = 0
+                    else:
+                        dr, ncap = _capped(dr, fire.max_step)
+                    x = x + dr
+                    L = [vf, ff, vv, 0.0]
+                    log.append(Step(s, it, 2, branch, ncap, margin, it - nbb, np.sqrt(ff / (3.0 * n))))
+                else:                                           # c3o_bb_step
+                    k, a_prev = npos, fdt
+                    a, branch, margin = a_prev, "first", None
+                    if k == 0:
+                        a = fire.dt_start * fire.dt_start * ACCEL / (1.0 if mut == "bb_first_no_mass" else mass)
+                    elif k >= 2:
+                        sy = L[0]
+                        margin = sy / np.sqrt(L[3] * L[2]) if L[3] * L[2] > 0 else 0.0
+                        if sy > 0:
+                            even = (k % 2 == 0) != (mut == "bb_parity_swapped")
+                            a, branch = (L[3] / sy if even else sy / L[2]), "bb"
+                        else:
+                            a, branch = 2.0 * a_prev, "negcurv"
+                        if not (a >= 1e-7):
+                            a, branch = 1e-7, branch + "+lo"
+                        if a > 1e2:
+                            a, branch = 1e2, branch + "+hi"
+                    q = [0.0, float((F * F).sum()), 0.0, 0.0]
+                    if k > 0:
+                        sv, _ = _capped(a_prev * v, fire.max_step)
+                        y = v - F
+                        q[0], q[2], q[3] = float((sv * y).sum()), float((y * y).sum()), float((sv * sv).sum())
+                    dr, ncap = _capped(a * F, fire.max_step)
+                    x = x + dr
+                    v = F.copy()
+                    fdt, npos, L = a, k + 1, q
+                    log.append(Step(s, it, 5, branch, ncap, margin, it, np.sqrt(q[1] / (3.0 * n))))
+                after_step()
+        else:                                                   # c3o_md_step
+            if prev_kind in (2, 5, -1):
+                v = O.init_velocities(_copy_model(om, mass=mass), seed, replica, 0.5)
+            ndf = max(3 * n - 3, 1)
+            for it in range(nsteps):
+                F = force()
+                tprev = mass * float((v * v).sum()) / ACCEL / (ndf * KBOLTZ)
+                floor = 1e-3 if mut == "floor_1e3" else 1e-2
+                branch = "plain"
+                if tprev < floor:
+                    tprev, branch = floor, "floor"
+                if kind == 0:
+                    l2 = 1.0 + dt * fbeta * (t_bath / tprev - 1.0)
+                    if l2 < 0:
+                        l2 = abs(l2) if mut == "sqrt_abs_clamp" else 0.0
+                        branch = "clamp0" if branch == "plain" else "floor+clamp0"
+                    lam = np.sqrt(l2)
+                else:
+                    lam = np.sqrt(t_bath / tprev)
+                v = lam * (v - v.mean(0)) + (dt * ACCEL / mass) * F
+                x = x + dt * v
+                log.append(Step(s, it, kind, branch, since=it))
+                after_step()
+        prev_kind = kind
+    return x - x.mean(0), v, log, cps
+
+
+# ---------------------------------------------------------------------------------------------
+# the cases
+# ---------------------------------------------------------------------------------------------
+# the off-default scalars (every one of them enters a number the host derives: acc, t_fac, w_noe2n, w_rep4, rep_r2, kq, k_bond2, ...)
+OFF = dict(mass=37.0, s_noe=6.0, k_bond=220.0, b0=3.6, k_ang=30.0, a0=5.1, k_rep=2.5, r0_rep=4.4, fbeta=400.0)
+FIRE_A = dict(f_inc=1.3, dt_max=0.02, n_min=2, f_dec=0.4, alpha_start=0.2, f_alpha=0.95, max_step=2.0, dt_start=0.008)
+FIRE_B = dict(f_inc=1.6, dt_max=0.025, n_min=0, f_dec=0.25, alpha_start=0.3, f_alpha=0.85, max_step=0.05, dt_start=0.012)
+COLD = [(1, 2, 0.005, 1e-4, 1e-4, 0.85, 0.0), (0, 3, 0.003, 1e-4, 1e-4, 0.85, 3.0), (0, 4, 0.003, 1.0, 1.0, 0.85, 300.0),
+        (0, 6, 0.003, 0.4, 0.003, 0.9, 0.02), (1, 4, 0.005, 1.0, 0.05, 1.0, 1500.0)]
+
+
+class Case:
+    """model / fire: fields off the library's defaults; start: "relaxed" (the oracle's result after 200 default FIRE steps from the coil
+    under the case's model, rounded to float) or "coil"; ids: {beads: the two coils the starts are made from} (default 0 and 1 — a start
+    is data, passed in through set_coords: which coil it came from is chosen per size for conditioning); first: the first replica number on
+    the device (it keys the Maxwell velocities of an MD stage); checkpoints: step counts at which run_steps is split and everything is
+    compared; vrel: checkpoints whose velocities are compared relative to the oracle's own max |v|; pot / gen: device potential and
+    general tail, for the kernel names (a general tail has no multi-step form); two_point: kind-5 steps are in the range (5e-3 A)."""
+
+    def __init__(self, model, fire, stages, checkpoints, start="relaxed", tp=1000, vrel=(), pot=4, gen=False, two_point=False, ids=None,
+                 first=0):
+        # (a stage's dt, weights and bath temperature as the C ABI holds them: floats)
+        stages = [tuple(s[:2]) + tuple(float(np.float32(a)) for a in s[2:]) for s in stages]
+        self.model, self.fire, self.stages, self.checkpoints, self.start, self.tp = model, fire, stages, tuple(checkpoints), start, tp
+        self.vrel, self.pot, self.gen, self.two_point, self.ids, self.first = tuple(vrel), pot, gen, two_point, ids or {}, first
+        self.nsteps = sum(s[1] for s in stages)
+        assert self.checkpoints[-1] == self.nsteps
+
+    def tol(self, precision=32):
+        """the suite's coordinate tolerance for the case (Angstrom)"""
+        return 2e-5 if precision == 64 else (5e-3 if self.two_point else 2e-3)
+
+    def key(self):
+        return tuple(sorted(self.model.items()))
+
+
+_MIN = (0.0, 1.0, 1.0, 0.85, 0.0)          # a minimiser stage at the final stage's weights
+_HOT = (0, 8, 0.003, 0.4, 0.003, 0.9, 2000.0)
+_BIG = {1100: (4, 5)}                      # the coils whose relaxed starts are quiet at 1100 beads (coils 0 and 1 are not: SIZES below)
+CASES = {
+    # 7 mid-run resets, the dt_max cap, n_min 2, every bead below max_step; split directly after a mid-run reset (17: slot 0 at 250 beads);
+    # then an MD stage without repel weight (w_vdw = 0: kq = 0)
+    "fire_resets": Case({}, FIRE_A, [(2, 48) + _MIN, (0, 8, 0.003, 0.4, 0.0, 0.9, 2000.0)], [17, 48, 56], ids=_BIG),
+    # n_min 0, a max_step that cuts some beads on some steps and none on others, every scalar off default
+    "fire_partial_cap": Case(OFF, FIRE_B, [(2, 40) + _MIN], [40], ids={250: (0, 5)}),
+    # the same over its first 14 steps, for 1100 beads (see SIZES)
+    "fire_partial_cap_short": Case(OFF, FIRE_B, [(2, 14) + _MIN], [14], ids=_BIG),
+    # floor (kinds 1 and 0), lambda^2 < 0, plain before and after; w_all = 1e-4 (kq large); a checkpoint right after the floor steps
+    "md_cold": Case(OFF, {}, COLD, [4, 9, 19], vrel=(4,), ids=_BIG),
+    # two-point steps, the hand-over to FIRE inside the window (step 13), split inside the two-point part (7) and in the FIRE part (17: the
+    # range 8 .. 17 is five two-point ops and five FIRE ops, each segment long enough for a multi-step launch)
+    "two_point": Case(OFF, dict(dt_start=0.006, max_step=2.0, n_min=3), [(5, 30) + _MIN], [7, 17, 30], tp=12, two_point=True, ids=_BIG),
+    # every scalar off default on the shipped fast form, FIRE_A, then hot MD from the Maxwell velocities of replicas 5 and 6 (the mass)
+    "off_default": Case(OFF, FIRE_A, [(2, 40) + _MIN, _HOT], [40, 48], ids=_BIG, first=5),
+    "pot3_rs1_off": Case(dict(OFF, noe_pot=3, rswitch=1.0, mrswitch=11.0, masym=22.0, msoexp=1), FIRE_A, [(2, 30) + _MIN, _HOT], [30, 38],
+                         pot=3, ids={250: (5, 7), 1100: (4, 5)}),
+    "gen1_off": Case(dict(OFF, noe_pot=1, asym=1.0, rswitch=0.5), FIRE_A, [(2, 30) + _MIN, _HOT], [30, 38], pot=1, gen=True, ids=_BIG),
+    # default FIRE values from the coil, then hot MD with full repel weight
+    "rep_sep1": Case(dict(rep_sep=1), {}, [(2, 12) + _MIN, (0, 10, 0.003, 0.4, 1.0, 0.9, 2000.0)], [22], start="coil"),
+    "rep_sep3": Case(dict(rep_sep=3), {}, [(2, 12) + _MIN, (0, 10, 0.003, 0.4, 1.0, 0.9, 2000.0)], [22], start="coil"),
+}
+# The sizes a case runs at.  At 1100 beads 200 relaxation steps leave more of the chain unsettled: under FIRE_B (max_step 0.05, dt up to
+# 0.025) every start tried (coils 0 .. 5) either caps every bead for 30 steps or, within 40 steps, magnifies float32 rounding beyond a
+# quarter of the tolerance in the velocities after a reset (0.25 .. 35 tolerances).  Its first 14 steps from coils 4 and 5 are quiet
+# (0.04 / 0.07) and still cut some beads on 8 steps and hold dt at dt_max on 4: that window is the case at 1100 beads.
+SIZES = {name: (250, 1100) for name in CASES}
+SIZES["fire_partial_cap"] = (250,)
+SIZES["fire_partial_cap_short"] = (1100,)
+
+
+@functools.lru_cache(maxsize=None)
+def problem(n):
+    """(IF, dist10) of the synthetic matrix of n beads the GPU suite uses at that size"""
+    IF = synthetic_if(n, seed=n)[0]
+    return IF, O.if_to_dist10(IF)
+
+
+def models(case, n):
+    """(c3d_model, c3d_fire_params, oracle Model, oracle FireParams) of a case: the oracle's hold the float32 values of the library's"""
+    from chromosome3d_amd import default_fire, default_model
+    m, f = default_model(**case.model), default_fire(**case.fire)
+    return m, f, oracle_model_from(m, n), oracle_fire_from(f)
+
+
+@functools.lru_cache(maxsize=None)
+def _start(model_key, kind, n, coil):
+    from chromosome3d_amd import default_model
+    om = oracle_model_from(default_model(**dict(model_key)), n)
+    x = O.init_coords(om, SEED, coil)
+    if kind != "coil":                     # "relaxed": 200 default FIRE steps; "fire30": 30 (forces still large)
+        x = O.run_schedule(om, problem(n)[1], O.make_stages([(2, 200 if kind == "relaxed" else 30) + _MIN]), O.default_fire(), SEED, coil, x0=x)[0]
+    return x.astype(np.float32)
+
+
+def start_of(case, n, slot):
+    return _start(case.key(), case.start, n, case.ids.get(n, (0, 1))[slot])
+
+
+def start(name, n, slot):
+    """float32 start coordinates of slot 0 / 1 of a case at n beads (cases of one model share their starts)"""
+    return start_of(CASES[name], n, slot)
+
+
+@functools.lru_cache(maxsize=None)
+def reference(name, n, slot, round32=False, mut=None):
+    """run_twin of a case's slot: (x, v, log, checkpoints)"""
+    case = CASES[name]
+    _, _, om, of = models(case, n)
+    return run_twin(om, problem(n)[1], case.stages, of, case.first + slot, start(name, n, slot).astype(np.float64), tp=case.tp,
+                    checkpoints=case.checkpoints, round32=round32, mut=mut)
+
+
+def gap(a, b, case, precision=32):
+    """how far two runs of a case are apart at their checkpoints, in units of the GPU tolerance there: coordinates against case.tol(),
+    velocities against tol_v * max(1, max|v|) — at a checkpoint of case.vrel against tol_v * max|v| itself"""
+    worst = 0.0
+    tol_x = case.tol(precision)
+    tol_v = 2e-5 if precision == 64 else 2e-3
+    for k in case.checkpoints:
+        (xa, va), (xb, vb) = a[3][k], b[3][k]
+        vmax = np.abs(va).max()
+        worst = max(worst, np.abs(xa - xb).max() / tol_x, np.abs(va - vb).max() / (tol_v * (vmax if k in case.vrel else max(1.0, vmax))))
+    return float(worst)
+
+
+# ---------------------------------------------------------------------------------------------
+# the gradient exit and the L-BFGS case
+# ---------------------------------------------------------------------------------------------
+GTOL_CHECK_EVERY = 7
+GTOL_STAGE = (2, 84) + _MIN
+
+
+def gtol_stage():
+    return tuple(GTOL_STAGE[:2]) + tuple(float(np.float32(a)) for a in GTOL_STAGE[2:])
+
+
+@functools.lru_cache(maxsize=None)
+def gradient_exit(name, n):
+    """(gtol, steps): a final FIRE stage GTOL_STAGE of case `name`'s model, FIRE values and starts, its exit test looked at every
+    GTOL_CHECK_EVERY steps.  gtol = the geometric mean of the largest-over-replicas RMS forces at the first two consecutive checks that
+    differ by at least 10 % (the second lower, every earlier check above gtol); steps = where c3o_run_schedule then stops: the second."""
+    case = CASES[name]
+    _, _, om, of = models(case, n)
+    logs = [run_twin(om, problem(n)[1], [gtol_stage()], of, slot, start(name, n, slot).astype(np.float64))[2] for slot in (0, 1)]
+    checks = range(GTOL_CHECK_EVERY, GTOL_STAGE[1] + 1, GTOL_CHECK_EVERY)
+    worst = [max(log[k - 1].rms for log in logs) for k in checks]
+    for j in range(len(worst) - 1):
+        gtol = float(np.sqrt(worst[j] * worst[j + 1]))
+        if worst[j + 1] <= 0.9 * worst[j] and min(worst[:j + 1]) > gtol:
+            return gtol, checks[j + 1]
+    raise AssertionError(f"no two consecutive checks 10 % apart: {worst}")
+
+
+# dt_start, max_step, mass and lbfgs_memory off default; 20 L-BFGS steps from 30 FIRE steps off the coil (tests/test_gpu_lbfgs.py's kind of start)
+LBFGS_CASE = Case(dict(mass=37.0), dict(dt_start=0.004, max_step=0.2), [(8, 20) + _MIN], [20], start="fire30")
+LBFGS_MEMORY = 3
+
+
+# ---------------------------------------------------------------------------------------------
+# the controller as a table: the statements of run_twin's three step kinds on one row of sums and state, in float64
+# ---------------------------------------------------------------------------------------------
+F32 = np.float32
+
+
+def step_scalars_ref(kind, dt, t_bath, psum, state, npos, consts, fire):
+    """One row of c3d_debug_step_scalars.  psum (4), state (dt, alpha), npos: the row; consts = (t_fac, inv_n, acc, fbeta) as the host holds
+    them (floats, widened); fire = c3d_fire_params.  Every constant of the oracle that the device holds as a float (1e-2, 1e-30, 1e-7, 1e2)
+    is that float.  Returns ((lambda, cmx, cmy, cmz, keep, mix), (dt, alpha), npos) in float64 — the statements of c3o_md_step,
+    c3o_fire_step and c3o_bb_step that decide a step, with their comparisons as the oracle writes them (a NaN fails every one)."""
+    t_fac, inv_n, acc, fbeta = (float(a) for a in consts)
+    p = [float(a) for a in psum]
+    sdt, alpha = float(state[0]), float(state[1])
+    lam, cm, keep, mix = 1.0, [0.0, 0.0, 0.0], 0.0, 0.0
+    with np.errstate(all="ignore"):
+        if kind in (0, 1):
+            tprev = t_fac * p[0]
+            if tprev < float(F32(1e-2)):
+                tprev = float(F32(1e-2))
+            if kind == 0:
+                l2 = 1.0 + float(F32(dt) * F32(fbeta)) * (t_bath / tprev - 1.0)
+                lam = float(np.sqrt(np.float64(l2 if l2 >= 0 else 0.0)))
+            else:
+                lam = float(np.sqrt(np.float64(t_bath) / tprev))
+            cm = [p[1] * inv_n, p[2] * inv_n, p[3] * inv_n]
+        elif kind in (5, 6):
+            k = 0 if kind == 6 else npos
+            a_prev = sdt
+            a = a_prev
+            if k == 0:
+                a = float(fire.dt_start) ** 2 * acc
+            elif k >= 2:
+                sy = p[0]
+                if sy > 0:
+                    a = float(np.float64(p[3]) / sy) if k % 2 == 0 else float(np.float64(sy) / np.float64(p[2]))
+                else:
+                    a = 2.0 * a_prev
+                if not (a >= float(F32(1e-7))):
+                    a = float(F32(1e-7))
+                if a > 1e2:
+                    a = 1e2
+            lam, mix, sdt, npos = a_prev, a, a, k + 1
+        else:
+            if p[0] > 0:
+                keep = 1.0 - alpha
+                mix = alpha * float(np.sqrt(np.float64(p[2]) / (p[1] if p[1] > float(F32(1e-30)) else float(F32(1e-30)))))
+                if npos > fire.n_min:
+                    grown = sdt * float(fire.f_inc)
+                    sdt = grown if grown < float(fire.dt_max) else float(fire.dt_max)
+                    alpha *= float(fire.f_alpha)
+                npos += 1
+            else:
+                alpha, sdt, npos = float(fire.alpha_start), sdt * float(fire.f_dec), 0
+    return (lam, cm[0], cm[1], cm[2], keep, mix), (sdt, alpha), npos
+
+
+# The table's model and FIRE values: products that float holds exactly, so that "at" is at (dt fbeta = 1/2, 1, 3/2; dt f_inc = dt_max)
+TABLE_MODEL = dict(mass=37.0, fbeta=256.0)
+TABLE_FIRE = dict(dt_start=0.006, dt_max=0.046875, f_inc=1.5, f_dec=0.25, alpha_start=0.3, f_alpha=0.875, n_min=3)
+TABLE_N = 37
+
+
+def table_consts(m, n):
+    """(t_fac, inv_n, acc, fbeta) in the host's float arithmetic (dev_model)"""
+    ndf = max(3 * n - 3, 1)
+    mass = F32(m.mass)
+    return (mass / F32(418.4) / (F32(ndf) * F32(0.0019872)), F32(1.0) / F32(n), F32(418.4) / mass, F32(m.fbeta))
+
+
+def table_rows(kind, t_fac):
+    """[(dt, t_bath, psum, state, npos)] of a kind: the grid of the issue"""
+    nan, rows = float("nan"), []
+    if kind in (0, 1):
+        x_floor = float(F32(1e-2)) / float(t_fac)                      # sum v^2 at which T is the floor
+        xs = [0.0, 0.5 * x_floor, float(np.nextafter(F32(x_floor), F32(0))), float(F32(x_floor)), float(np.nextafter(F32(x_floor), F32(1e9))),
+              2.0 * x_floor, 300.0 / float(t_fac), 3.0e4 * x_floor]
+        for dt in (2.0 ** -9, 2.0 ** -8, 3 * 2.0 ** -9):                # dt fbeta = 1/2, 1, 3/2: lambda^2 at t_bath 0 = 1/2, 0, -1/2
+            for t_bath in ((0.0, 300.0, 2000.0) if kind == 0 else (0.0, 0.02, 300.0)):
+                for x in xs:
+                    if kind == 0 and 0.0 < t_bath < float(t_fac) * x * 1.001:      # cooling towards lambda^2 = 0 cancels: not a 4-ulp row
+                        continue
+                    rows.append((dt, t_bath, (x, 0.37 * (1 + len(rows) % 5), -1.25, 0.0), (0.01, 0.1), 4))
+    elif kind in (2, 3):
+        for vf in (3.0, 1e-30, 0.0, -0.0, -2.5, nan):
+            for npos in (2, 3, 4):                                       # n_min - 1, n_min, n_min + 1
+                for sdt in (0.03, 0.03125, 0.04):                        # dt f_inc below, at, above dt_max
+                    for ff, vv in ((7.0, 0.3), (0.0, 0.3), (1e-35, 1e-20), (7.0, 0.0)):
+                        rows.append((0.0, 0.0, (vf, ff, vv, 0.0), (sdt, 0.3 * 0.875 ** (npos % 3)), npos))
+        rows.append((0.0, 0.0, (3.0, nan, 0.3, 0.0), (0.03, 0.3), 4))
+        rows.append((0.0, 0.0, (3.0, 7.0, nan, 0.0), (0.03, 0.3), 4))
+    else:
+        for npos in (0, 1, 2, 3, 7, 8):
+            for a_prev in (1e-5, 3e-8, 80.0):                            # the doubling leaves [1e-7, 1e2] on both sides
+                for sy, yy, ss in ((2.0, 5.0, 3.0), (2.0, 5e9, 3e-9), (2.0, 1e-3, 9e2), (0.0, 5.0, 3.0), (-0.0, 5.0, 3.0), (-1.5, 5.0, 3.0),
+                                   (nan, 5.0, 3.0), (2.0, nan, nan), (2.0, 0.0, 3.0), (1e-30, 5.0, 3.0)):
+                    rows.append((0.0, 0.0, (sy, 11.0, yy, ss), (a_prev, 0.2), npos))
+    return rows

@@ -160,6 +160,7 @@ void sym_geometry(const DevModel&, int* Q, int* G, int* od, int* dg) { *Q = 1; *
 size_t sym_scratch_floats(const DevModel& m) { return (size_t)m.npad * 8; }
 void sym_tile_list(const DevModel&, int2* out) { out[0].x = 0; out[0].y = 0; }
 hipError_t launch_step_sym(const DevModel&, const DevStep&, const DevFire&, const DevBuffers&, int, const void*, float*, hipStream_t) { LaunchScope ls; return hipSuccess; }
+hipError_t launch_step_scalars(const DevModel&, const DevStep&, const DevFire&, int, const float*, const FireState*, float*, FireState*, hipStream_t) { LaunchScope ls; return hipSuccess; }
 int cols64(int n) { return (n + 127) / 128 * 128; }
 Model64 model64(const DevModel& d, const c3d_model&) { Model64 m{}; m.n = d.n; m.noe_pot = device_pot(d.noe_pot); return m; }   // (what form64 reads; no kernel runs here)
 Step64 step64(const Model64&, int, double, double, double, double, double) { return Step64{}; }
