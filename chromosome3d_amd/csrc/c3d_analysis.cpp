@@ -1,7 +1,9 @@
 // c3d_analysis.cpp — host unit of libc3d.so: the output side.  What a run's models are worth and how they relate, from the coordinates
 // resident on the device (kernels: c3d_score.hip): c3d_score_replicas, c3d_compare_replicas, c3d_superpose_replicas, c3d_rmsd_table,
-// c3d_ensemble_map, c3d_ensemble_score, c3d_geometry_replicas, c3d_separation_profile and the test hooks c3d_debug_if_ranks / c3d_debug_distance_ranks.  What they share comes first: typed
+// c3d_ensemble_map, c3d_ensemble_score, c3d_geometry_replicas, c3d_separation_profile, c3d_stratified_score and the test hooks c3d_debug_if_ranks / c3d_debug_distance_ranks.  What they share comes first: typed
 // scratch slots (Slot, Block, Carve, CallScratch), the ranker (rank_matrix) and the models of a call (model_set_check, model_set_coords, gather_models).
+#include <limits>
+
 #include "c3d_ctx.h"
 
 using namespace c3d::host;
@@ -697,5 +699,99 @@ extern "C" int c3d_separation_profile(c3d_ctx* c, const double* extra_xyz, int n
         if (outs[k]) HIP_TRY(hipMemcpyAsync(outs[k], L.out[k].at(tmp.p), L.out[k].bytes(), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     ++c->separation_runs;
+    return C3D_OK;
+}
+
+// ---- IF against model distance inside every genomic separation (c3d_score.hip k_str_*) ----
+// c3d_stratified_score's one allocation: the models, the doubled IF ranks of every stratum (packed, diagonal-major), their sums of squares,
+// C, A, B of every model and stratum, and the flag words.  IF itself lies in the context's d_score.
+struct StratifiedScratch : Carve {
+    Slot<double> xyz;
+    Slot<unsigned> a;
+    Slot<long long> saa, sums;
+    Slot<int> flags;
+    StratifiedScratch(int n, int K, int lo, int hi) {
+        xyz = take<double>(3 * (size_t)n * K);
+        a = take<unsigned>(c3d::stratified_pairs(n, lo, hi));
+        saa = take<long long>((size_t)(hi - lo + 1));
+        sums = take<long long>((size_t)C3D_STRATUM_FIELDS * n * K);
+        flags = take<int>(c3d::kStrFlags);
+    }
+};
+// the device time of the two passes (stats "stratified_if_ms", "stratified_models_ms"): four events of the call, destroyed when it goes
+struct PassEvents {
+    hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
+    ~PassEvents() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+};
+
+extern "C" int c3d_stratified_score(c3d_ctx* c, const double* IF, int range, int max_sep, const double* extra_xyz, int n_extra, double* rho, double* scc,
+                                    int64_t* sums) {
+    const char* const who = "c3d_stratified_score";
+    if (int rc = model_set_check(c, who, 2, "no pair", extra_xyz, n_extra)) return rc;
+    const int n = c->n, K = c->nrep + n_extra;
+    if (!IF) return fail(C3D_ERR_INVALID, "c3d_stratified_score: the coefficient needs the IF matrix");
+    if (range < 1) return fail(C3D_ERR_INVALID, "c3d_stratified_score: range < 1");
+    if (max_sep < 0 || max_sep > n - 1 || (max_sep > 0 && max_sep < range)) return fail(C3D_ERR_INVALID, "c3d_stratified_score: max_sep is 0 (for n-1) or in range..n-1");
+    if (range > n - 1) return fail(C3D_ERR_INVALID, "c3d_stratified_score: range leaves no stratum (range > n-1)");
+    if (!rho && !scc && !sums) return fail(C3D_ERR_INVALID, "c3d_stratified_score: every output is NULL");
+    if (int rc = model_set_coords(c, who, extra_xyz, n_extra)) return rc;
+    C3D_ENTRY(c, unit_bit(UNIT_SCORE));
+    const int lo = range, hi = max_sep ? max_sep : n - 1;
+    if (int rc = score_scratch(c, sizeof(double) * (size_t)n * n)) return rc;
+    double* const d_IF = static_cast<double*>(c->d_score);
+    const StratifiedScratch L(n, K, lo, hi);
+    CallScratch tmp;
+    if (int rc = tmp.alloc(L.total, who)) return rc;
+    PassEvents ev;
+    for (hipEvent_t& x : ev.e) HIP_TRY(hipEventCreate(&x));
+    static_assert(sizeof(long long) == sizeof(int64_t), "the device's sums are the caller's int64_t");
+    HIP_TRY(hipMemcpyAsync(d_IF, IF, sizeof(double) * (size_t)n * n, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipEventRecord(ev.e[0], c->stream));
+    LAUNCH_TRY("stratified launch", c3d::launch_stratified_if(d_IF, n, lo, hi, L.a.at(tmp.p), L.saa.at(tmp.p), L.flags.at(tmp.p), c->stream));
+    HIP_TRY(hipEventRecord(ev.e[1], c->stream));
+    if (int rc = read_back(c, L.flags.at(tmp.p), L.flags.bytes())) return rc;
+    const int* const flags = static_cast<const int*>(c->h_stage);
+    if (flags[1]) return fail(C3D_ERR_INVALID, "c3d_stratified_score: an IF entry of the strata asked for is not finite");
+    if (flags[0]) return fail(C3D_ERR_INVALID, "c3d_stratified_score: the matrix is not symmetric over the strata asked for");
+    if (flags[3]) return fail(C3D_ERR_HIP, "c3d_stratified_score: internal: the ranks of a stratum do not add up to N(N+1)");
+    double* const d_xyz = L.xyz.at(tmp.p);
+    if (int rc = gather_models(c, ModelSource::STATE, 0, c->nrep, d_xyz, extra_xyz, n_extra, "superpose launch")) return rc;
+    HIP_TRY(hipEventRecord(ev.e[2], c->stream));
+    LAUNCH_TRY("stratified launch", c3d::launch_stratified_models(d_xyz, n, K, lo, hi, L.a.at(tmp.p), L.saa.at(tmp.p), L.sums.at(tmp.p), L.flags.at(tmp.p), c->stream));
+    HIP_TRY(hipEventRecord(ev.e[3], c->stream));
+    if (int rc = read_back(c, L.flags.at(tmp.p), L.flags.bytes())) return rc;
+    if (static_cast<const int*>(c->h_stage)[2]) return fail(C3D_ERR_INVALID, "c3d_stratified_score: a pair distance exceeds 50000 A (the limit of device and host scoring)");
+    // the sums straight into the caller's array, or into one of the call: 24 n K bytes, which the pinned stage would have to grow to
+    std::vector<int64_t> own;
+    if (!sums) own.resize(L.sums.count);
+    int64_t* const h = sums ? sums : own.data();
+    HIP_TRY(hipMemcpyAsync(h, L.sums.at(tmp.p), L.sums.bytes(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    float ms_if = 0, ms_models = 0;
+    HIP_TRY(hipEventElapsedTime(&ms_if, ev.e[0], ev.e[1]));
+    HIP_TRY(hipEventElapsedTime(&ms_models, ev.e[2], ev.e[3]));
+    c->stratified_if_ms = ms_if;
+    c->stratified_models_ms = ms_models;
+    // rho and scc on the host, from the integers, with the header's expressions in the header's order
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    for (int k = 0; k < K && (rho || scc); ++k) {
+        double num = 0, den = 0;
+        bool any = false;
+        for (int s = 0; s < n; ++s) {
+            double r = nan;
+            const int64_t* const q = h + ((size_t)k * n + s) * C3D_STRATUM_FIELDS;
+            if (s >= lo && s <= hi && q[1] > 0 && q[2] > 0) {
+                const double N = (double)(n - s), cN = N * N * N;
+                const double root = sqrt((double)q[1] * (double)q[2]);
+                r = (double)q[0] / root;
+                num += (double)q[0] / cN;
+                den += root / cN;
+                any = true;
+            }
+            if (rho) rho[(size_t)k * n + s] = r;
+        }
+        if (scc) scc[k] = any ? num / den : nan;
+    }
+    ++c->stratified_runs;
     return C3D_OK;
 }

@@ -223,6 +223,8 @@ struct c3d_ctx {
     long superpose_runs = 0, rmsd_table_runs = 0;   // stats: completed calls of c3d_superpose_replicas / c3d_rmsd_table
     long ensemble_map_runs = 0, ensemble_score_runs = 0;   // stats: completed calls of c3d_ensemble_map / c3d_ensemble_score
     long geometry_runs = 0, separation_runs = 0;   // stats: completed calls of c3d_geometry_replicas / c3d_separation_profile
+    long stratified_runs = 0;                      // stat: completed calls of c3d_stratified_score
+    double stratified_if_ms = 0, stratified_models_ms = 0;   // stats: device time of the last completed call's two passes (HIP events)
     long k1_recomputed = 0, k1_patched = 0;   // K1: near-tie elements redone on the host in the reference's order / changed by it
     long graph_captures = 0, graph_launches = 0, step_launches = 0, resident_launches = 0, cluster_launches = 0;
     bool has_two_point = false;            // the program holds two-point minimiser steps (run_ops splits ranges at their borders)

@@ -461,6 +461,16 @@ hipError_t launch_geometry(const double* xyz, int n, int K, double cutoff, int s
                            long long* clashes, double* chain, hipStream_t s);
 hipError_t launch_separation_profile(const double* xyz, int n, const int* pick, int Kp, double cutoff, double* mean, double* sd, double* contact,
                                      hipStream_t s);
+// IF against model distance per genomic separation (c3d_stratified_score; k_str_*).  Strata lo <= s <= hi, stratum s the n - s pairs (i, i + s).
+// launch_stratified_if: a = the doubled average ranks of IF inside every stratum, packed diagonal-major from stratum lo (stratified_pairs
+// values), saa[s - lo] = their sum of squares; flags (kStrFlags ints on the device, cleared here): [0] IF(i, j) != IF(j, i) in a stratum,
+// [1] a value there that is not finite, [3] a stratum whose ranks do not add up to N (N + 1): an internal error.  launch_stratified_models: sums (K x n x C3D_STRATUM_FIELDS, cleared here) = C, A, B of every
+// stratum and model from the models' "%.3f" distances ranked the same way; flags[2]: a pair further apart than 50 000 A (or not a number).
+constexpr int kStrFlags = 4;
+inline size_t stratified_pairs(int n, int lo, int hi) { return (size_t)(hi - lo + 1) * (size_t)n - ((size_t)hi * (hi + 1) / 2 - (size_t)lo * (lo - 1) / 2); }
+hipError_t launch_stratified_if(const double* IF, int n, int lo, int hi, unsigned* a, long long* saa, int* flags, hipStream_t s);
+hipError_t launch_stratified_models(const double* xyz, int n, int K, int lo, int hi, const unsigned* a, const long long* saa, long long* sums, int* flags,
+                                    hipStream_t s);
 
 // Target matrix entry: NOE target in Angstrom, 0 = no restraint (host c3d_set_restraints and K1).
 inline float encode_target_host(float t) { return t > 0 ? t : 0.0f; }

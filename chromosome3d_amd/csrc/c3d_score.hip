@@ -24,6 +24,8 @@
 //                             of those maps with IF (c3d_ensemble_map, c3d_ensemble_score)
 //   c3d_score_geometry.inc    k_geo_*    a model's clash count, nearest partners and chain envelope (c3d_geometry_replicas);
 //                             k_sep_*    the distance against the genomic separation (c3d_separation_profile)
+//   c3d_score_stratified.inc  k_str_*    IF against model distance inside every genomic separation: one LDS sort a (stratum, model) and
+//                             integer sums (c3d_stratified_score)
 #include "c3d_score_core.h"
 
 namespace c3d {
@@ -257,10 +259,14 @@ hipError_t launch_if_rank_sort(double* M, int n, int range, unsigned long long* 
 #include "c3d_score_superpose.inc"
 #include "c3d_score_ensemble.inc"
 #include "c3d_score_geometry.inc"
+#include "c3d_score_stratified.inc"
 
+// loads the unit's code object on the current device and gives the k_str_* kernels their dynamic-LDS allowance (c3d_gate.cpp "code objects":
+// once per device, never beside a launch)
 hipError_t preload_score_unit() {
     hipFuncAttributes a;
-    return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_score_round));
+    const hipError_t e = hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_score_round));
+    return e == hipSuccess ? str_prepare_unit() : e;
 }
 
 }  // namespace c3d

@@ -11,12 +11,15 @@
 //       every bead pair over the models (or the --ensemble-top best) — and prints how that map follows the input matrix
 //   --geometry <prefix> writes <prefix>_geometry.txt — per model the reference's clash count, closest counted pair and chain envelope — and
 //       <prefix>_separation.txt, distance and contact share against genomic separation over the models (or the --ensemble-top best)
+//   --stratified <prefix> writes <prefix>_scc.txt — per model the stratum-adjusted rank correlation of IF and distance — and
+//       <prefix>_strata.txt, the Spearman coefficient inside every genomic separation, one column a model
 //
 // Success convention of the reference: <ID>_<M>.pdb exists, iam.running removed; on failure
 // iam.running is renamed iam.failed and the exit code is non-zero (:266-283).
 #include <sys/stat.h>
 
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -57,6 +60,13 @@ static void usage() {
             "                                        pairs closer than --ensemble-cutoff (`s mean sd` when that is 0)]\n"
             "                 [--clash-cutoff <A>   clash distance in Angstrom, `<=` as the reference compares; default 3.5]\n"
             "                 [--clash-sep <k>   smallest |i-j| of a counted pair; default 1: bonded neighbours count, as in the reference]\n"
+            "                 [--stratified <prefix>   IF against model distance inside every genomic separation s = |i-j| >= 3 (the reference's range), sorted\n"
+            "                                          and summed on the device; needs --if.  <prefix>_scc.txt: one row `rank model scc` per model in rank\n"
+            "                                          order (lowest int(E_noe) first), scc the strata's Spearman coefficients combined with HiCRep's weights:\n"
+            "                                          the rank correlation with the distance decay taken out, negative for a good model (%%.6f).\n"
+            "                                          <prefix>_strata.txt: one row `s N rho_1 ... rho_M` per separation, N = n - s pairs, the models' columns\n"
+            "                                          in rank order (%%.6f; `nan` where IF or the distances of the stratum are constant)]\n"
+            "                 [--stratified-max-sep <S>   the largest separation of --stratified; default 0: n-1]\n"
             "                 [--accepted   also write <ID>a_<k>.pdb beside every <ID>_<k>.pdb, as CNS does for structures it accepts]\n");
 }
 
@@ -86,8 +96,8 @@ int main(int argc, char** argv) {
     // (rc -13, "GPU coredump: execvp failed") before the runtime has said WHICH exception — round 5 lost the only evidence of one that way.
     setenv("HSA_DISABLE_COREDUMP_ON_EXCEPTION", "1", 0);          // (0: a user's own setting wins)
     const double t_start = now_s();
-    std::string if_path, tbl_path, out_dir, id, seq_arg, similarity_path, rmsf_path, ensemble_prefix, geometry_prefix;
-    int superpose = 0, ensemble_top = 0;
+    std::string if_path, tbl_path, out_dir, id, seq_arg, similarity_path, rmsf_path, ensemble_prefix, geometry_prefix, stratified_prefix;
+    int superpose = 0, ensemble_top = 0, stratified_max_sep = 0;
     double ensemble_cutoff = -1;      // < 0: 2 x b0
     double clash_cutoff = 3.5;        // the figure of the reference's assessment
     int clash_sep = 1;
@@ -132,12 +142,15 @@ int main(int argc, char** argv) {
         else if (s == "--ensemble-top") ensemble_top = atoi(next("--ensemble-top"));
         else if (s == "--ensemble-cutoff") ensemble_cutoff = atof(next("--ensemble-cutoff"));
         else if (s == "--geometry") geometry_prefix = next("--geometry");   // clashes, chain envelope, distance against separation (c3d_geometry_replicas, c3d_separation_profile)
+        else if (s == "--stratified") stratified_prefix = next("--stratified");   // per-separation Spearman and their combination (c3d_stratified_score)
+        else if (s == "--stratified-max-sep") stratified_max_sep = atoi(next("--stratified-max-sep"));
         else if (s == "--clash-cutoff") clash_cutoff = atof(next("--clash-cutoff"));
         else if (s == "--clash-sep") clash_sep = atoi(next("--clash-sep"));
         else if (s == "-h" || s == "--help") { usage(); return 0; }
         else { fprintf(stderr, "c3d_solve: unknown option %s\n", s.c_str()); usage(); return 2; }
     }
     if (out_dir.empty() || (if_path.empty() == tbl_path.empty()) || models < 1) { usage(); return 2; }
+    if (!stratified_prefix.empty() && if_path.empty()) { fprintf(stderr, "c3d_solve: --stratified needs --if: a run started from --tbl has no IF matrix\n"); return 2; }
     if (id.empty()) {
         std::string base = if_path.empty() ? std::string("model") : if_path.substr(if_path.find_last_of('/') + 1);
         if (base.size() > 4 && base.substr(base.size() - 4) == ".txt") base.resize(base.size() - 4);
@@ -322,6 +335,34 @@ int main(int argc, char** argv) {
         for (int s = 0; s < n; ++s) {
             if (with_contact) fprintf(f, "%d %.3f %.3f %.6f\n", s, prof[s], prof[(size_t)n + s], prof[2 * (size_t)n + s]);
             else fprintf(f, "%d %.3f %.3f\n", s, prof[s], prof[(size_t)n + s]);
+        }
+        fclose(f);
+    }
+    if (!stratified_prefix.empty()) {
+        std::vector<int32_t> order(models);
+        CHECK(c3d_rank(ctx, order.data()));
+        const int range = 3, hi = stratified_max_sep ? stratified_max_sep : n - 1;       // spearman_IF_pdb.pl's range
+        std::vector<double> rho((size_t)models * n), scc(models);
+        CHECK(c3d_stratified_score(ctx, IF, range, stratified_max_sep, nullptr, 0, rho.data(), scc.data(), nullptr));
+        auto put = [](FILE* f, double v) { if (std::isnan(v)) fprintf(f, " nan"); else fprintf(f, " %.6f", v); };
+        std::string path = stratified_prefix + "_scc.txt";
+        FILE* f = fopen(path.c_str(), "w");
+        if (!f) { fprintf(stderr, "c3d_solve: cannot write %s\n", path.c_str()); return fail_exit(out_dir); }
+        fprintf(f, "# rank model scc   (separations %d..%d; model r is %s_<r>.pdb)\n", range, hi, id.c_str());
+        for (int k = 0; k < models; ++k) {
+            fprintf(f, "%d %u", k + 1, first_rep + (unsigned)order[k] + 1u);
+            put(f, scc[order[k]]);
+            fprintf(f, "\n");
+        }
+        fclose(f);
+        path = stratified_prefix + "_strata.txt";
+        f = fopen(path.c_str(), "w");
+        if (!f) { fprintf(stderr, "c3d_solve: cannot write %s\n", path.c_str()); return fail_exit(out_dir); }
+        fprintf(f, "# s N rho_1 ... rho_%d   (columns: the models in rank order)\n", models);
+        for (int s = range; s <= hi; ++s) {
+            fprintf(f, "%d %d", s, n - s);
+            for (int k = 0; k < models; ++k) put(f, rho[(size_t)order[k] * n + s]);
+            fprintf(f, "\n");
         }
         fclose(f);
     }

@@ -216,6 +216,18 @@ def geometry_report(solver, extra=None, pick=None, clash_cutoff=3.5, sep=1, cont
     return out
 
 
+def stratified_report(solver, IF, rng=3, max_sep=0, extra=None, sums=False):
+    """A quality number that the distance decay does not dominate, on the device: {"rho" [K, n], "scc" [K][, "sums" [K, n, 3]]} of
+    Solver.stratified_score — per model the Spearman coefficient of IF against distance inside every separation s = |i-j| (rng <= s <=
+    max_sep, 0: n-1) and their combination with HiCRep's weights — with "strata" [n], the number of pairs n - s of every separation
+    (0 outside the strata asked for).  rng 3 is the reference's range."""
+    out = solver.stratified_score(IF, rng, max_sep, extra, sums)
+    n = out["rho"].shape[1]
+    s = np.arange(n)
+    out["strata"] = np.where((s >= rng) & (s <= (max_sep if max_sep else n - 1)), n - s, 0)
+    return out
+
+
 def build_models(solver, model_count=MODELCOUNT, seed=MD_SEED, first_replica=0, model=None, stages=None, fire=None,
                  gtol=1e-2, check_every=250, final_kind=5):
     """The replacement of `cns_solve < dgsa.inp` (:254-289): runs the whole annealing schedule

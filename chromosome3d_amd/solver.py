@@ -375,6 +375,24 @@ class Solver:
                                                 _l.dptr(mean), _l.dptr(sd), _l.dptr(contact) if contact is not None else None))
         return mean, sd, contact
 
+    def stratified_score(self, IF, range=3, max_sep=0, extra=None, sums=False):
+        """{"rho" [K, n], "scc" [K]} and, with sums=True, "sums" [K, n, 3] int64: IF against the "%.3f" model distance inside every genomic
+        separation s = |i-j|, range <= s <= max_sep (0: n-1), for the K models of compare(), the sorting and the integer sums on the
+        device (c3d_stratified_score).  rho[k, s] is the Spearman coefficient of the n - s pairs (i, i+s) of model k, NaN where a side
+        is constant (and outside the strata asked for); scc[k] combines the strata with HiCRep's weights — the rank correlation with the
+        distance decay taken out, negative for a good model.  sums[k, s] = (C, A, B), the exact integers rho and scc are formed from
+        (include/c3d.h), from which a band-limited scc follows without another call.  IF must be symmetric; nothing of the solve changes."""
+        IFc = np.ascontiguousarray(IF, dtype=np.float64)
+        assert IFc.shape == (self.n, self.n)
+        xptr, E = self._extra_models(extra)
+        K = self.nrep + E
+        out = {"rho": np.empty((K, self.n), dtype=np.float64), "scc": np.empty(K, dtype=np.float64)}
+        if sums:
+            out["sums"] = np.empty((K, self.n, _l.STRATUM_FIELDS), dtype=np.int64)
+        _l.check(self._L.c3d_stratified_score(self._h, _l.dptr(IFc), int(range), int(max_sep), xptr, E, _l.dptr(out["rho"]), _l.dptr(out["scc"]),
+                                              out["sums"].ctypes.data_as(C.POINTER(C.c_int64)) if sums else None))
+        return out
+
     def rank(self):
         r = np.empty(self.nrep, dtype=np.int32)
         _l.check(self._L.c3d_rank(self._h, _l.i32ptr(r)))

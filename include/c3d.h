@@ -324,7 +324,9 @@ int c3d_last_timing(const c3d_ctx* ctx, double* ms_total, long* steps, long* lau
  * re-run with a histogram sized to the models), "compare_runs" (completed calls of c3d_compare_replicas),
  * "f64_evals" (completed calls of c3d_eval_f64), "superpose_runs" / "rmsd_table_runs" (completed calls of c3d_superpose_replicas /
  * c3d_rmsd_table), "ensemble_map_runs" / "ensemble_score_runs" (completed calls of c3d_ensemble_map / c3d_ensemble_score),
- * "geometry_runs" / "separation_runs" (completed calls of c3d_geometry_replicas / c3d_separation_profile). */
+ * "geometry_runs" / "separation_runs" (completed calls of c3d_geometry_replicas / c3d_separation_profile),
+ * "stratified_runs" (completed calls of c3d_stratified_score), "stratified_if_ms" / "stratified_models_ms" (device time of the two passes
+ * of the last completed one, from HIP events: measurement). */
 int c3d_get_stat(const c3d_ctx* ctx, const char* key, double* value);
 /* Test hook, no reference counterpart: the multi-step kernel's hand-off trusts a 16-byte unit once its tag word matches — i.e. that a
  * 16-byte aligned store is never observed half-written by a 16-byte load on gfx950.  This runs that exact store / load pair (one producer
@@ -519,6 +521,65 @@ int c3d_geometry_replicas(c3d_ctx* ctx, const double* extra_xyz, int n_extra, do
                           int64_t* clashes, int32_t* bead_clashes, double* nearest, double* chain);
 int c3d_separation_profile(c3d_ctx* ctx, const double* extra_xyz, int n_extra, const int32_t* pick, int n_pick,
                            double cutoff, double* mean, double* sd, double* contact);
+/* IF against model distance per genomic separation, on the device (c3d_score_stratified.inc k_str_*).  The Spearman coefficient of
+ * c3d_score_replicas runs over all pairs |i-j| >= range; IF falls and distance rises with |i-j| in every chain-like model, so the
+ * distance-decay curve dominates it.  This entry correlates inside each stratum s = |i-j| and combines the strata with variance-stabilising
+ * weights: HiCRep's stratum-adjusted correlation (Yang et al. 2017), with a rank correlation inside each stratum to match the reference's
+ * metric.
+ *
+ * Models.  K = n_replicas + n_extra, numbered and taken as c3d_geometry_replicas takes them.  On a precision-64 context that is the fp64
+ *   state bit for bit.  Otherwise the floats are taken as doubles.  Extra models are n x 3 doubles, checked as there.
+ * Distance.  d_k(i,j) is the unit's cmp_dist, with the host's bits, rounded to integer thousandths of an A as the reference's
+ *   sprintf "%.3f" does (round_milli_dev, spearman_IF_pdb.pl:47).
+ * Stratum.  Stratum s is lo <= s <= hi, with lo = range >= 1 and hi = max_sep, or n-1 when max_sep is 0.
+ *   - It holds the N = n - s pairs (i, i+s), i = 0 .. N-1.
+ *   - It pairs IF[i][i+s] with that rounded distance.
+ *   - IF must be symmetric over the strata asked for.  A stratum of the ordered pairs (both triangles, as the reference walks them) then
+ *     has every observation twice.  That leaves a correlation of average ranks unchanged.
+ *   - Zeros of IF count, as in the reference.
+ *   - -0.0 equals 0.0 (rank_key).
+ * Doubled ranks.
+ *   - a_i = 2 x (average rank of IF[i][i+s] within the stratum).
+ *   - b_i = 2 x (average rank of the rounded distance within the stratum).
+ *   - Both are integers: #{smaller} + #{not larger} + 1.
+ * Integer sums.
+ *   - T = N(N+1).
+ *   - C = N sum a_i b_i - T^2.
+ *   - A = N sum a_i^2 - T^2.
+ *   - B = N sum b_i^2 - T^2.
+ *   - All are exact in int64.  The largest term is 4 N^4 < 2.9e17 at N = 16383.
+ * Per-stratum coefficient.
+ *   - rho[k][s] = (double)C / sqrt((double)A * (double)B) when A > 0 and B > 0.
+ *   - Otherwise it is NaN.  That covers a constant stratum and N = 1.
+ *   - It is also NaN for s outside [lo, hi].
+ * Combined coefficient per model.
+ *   - With cN = (double)N*(double)N*(double)N, num = sum_s (double)C / cN.
+ *   - den = sum_s sqrt((double)A*(double)B) / cN.
+ *   - Both sums run over the strata with A > 0 and B > 0, in ascending s, each sum one sequential chain.
+ *   - scc[k] = num / den, or NaN when no stratum counts.
+ *   - This is sum w_s rho_s / sum w_s with HiCRep's weights w_s = N_s sqrt(var(a/2N) var(b/2N)).
+ *   - It is negative for a good model, as rho_mean of c3d_ensemble_score is.
+ *
+ * Outputs: rho is K x n, row-major; scc holds K values; sums is K x n x C3D_STRATUM_FIELDS and holds C, A, B per stratum, 0 outside
+ * [lo, hi].  Any output may be NULL, not all three.  A caller can form a band-limited SCC from sums without another call.  rho and scc are
+ * formed on the host from the integer sums read back, with exactly the expressions above; the integer sums are the device's work: one LDS
+ * sort per stratum of IF (k_str_if) and per (stratum, model) of the distances (k_str_model), two binary searches an element, int64 sums.
+ * Every quantity before the last division is an exact integer: the result has no summation order and takes no atomics.
+ * No state of the solve changes (the guarantee of c3d_compare_replicas); two calls return the same bits; extra models leave the replicas'
+ * entries their bits.
+ * C3D_ERR_INVALID with the function's name, before any launch: no replicas, n < 2, no IF, range < 1, max_sep < 0, max_sep > n-1 or
+ * 0 < max_sep < range, range > n-1, every output NULL, and the model-set refusals of c3d_geometry_replicas (n_extra < 0 or extra models
+ * without coordinates, K > C3D_COMPARE_MAX_MODELS, extra coordinates that are not finite or have |x| >= 1e6).  C3D_ERR_INVALID after the pass
+ * that finds it, with nothing written to the outputs: IF not symmetric over the strata asked for, a non-finite IF entry there, a pair of a
+ * model further apart than 50 000 A (the limit of c3d_score_replicas and of the host twin).  C3D_ERR_NOMEM: no device memory for the scratch.
+ * Memory: IF goes into the context's scoring scratch as c3d_score_replicas uploads it (8 n^2 bytes, kept: 1.7 MB at 455 beads, 2 GiB at
+ * 16384).  Everything else is one allocation per call, freed before it returns: 48 n K bytes (24 n a model of coordinates, 24 n of sums)
+ * + 4 bytes a pair of the strata (the IF ranks) + 8 bytes a stratum: 0.85 MB at 455 x 20 and range 3, 0.55 GB at 16384 x 20 (0.54 GB of it
+ * the IF ranks of all 1.3e8 pairs).
+ * Stat "stratified_runs" counts the calls that completed. */
+#define C3D_STRATUM_FIELDS 3
+int c3d_stratified_score(c3d_ctx* ctx, const double* IF, int range, int max_sep, const double* extra_xyz, int n_extra,
+                         double* rho, double* scc, int64_t* sums);
 /* rank[k] = replica index with the k-th lowest int(E_noe) (chromosome3D.pl:796-802,822-828);
  * ties broken by replica id. */
 int c3d_rank(c3d_ctx* ctx, int32_t* rank);

@@ -5,7 +5,9 @@ solver evidence the reference holds): per matrix
   * structure-level similarity of our model with the bundled one: Spearman of the pairwise distances and the scaled
     dRMSD, the two numbers of output_models/similarity.txt (c3d_model_similarity); for scale, the same between our two
     best replicas, and the reference's own 500 kb vs 1 Mb agreement is 0.855-0.967;
-  * the chain envelope: bond mean/sd, |i-j| = 2 mean/sd, radius of gyration ratio.
+  * the chain envelope (SURVEY 8a/8c): bond mean/sd, |i-j| = 2 mean/sd, radius of gyration ratio;
+  * SCC, the stratum-adjusted rank correlation of IF and distance (c3d_stratified_score, range 3: Spearman inside every |i-j|, combined
+    with HiCRep's weights, so the distance decay does not carry it): our lowest-energy replica beside the bundled model.
 
     python tools/parity_sweep.py ['{json model overrides}'] [replicas=20] [subset regex]
 Extra keys in the overrides: min_steps, quiet, embed (DG-embed start, chromosome3D.pl:1471-1525), start (1 = extended strand, :2413-2416), seed, dump (path of an .npz receiving every replica's coordinates).
@@ -66,20 +68,20 @@ def solve(s, IF, over, nrep=20, seed=82364, min_steps=3000, embed=0, start=0):
 
 HEADER = ("| matrix | N | R | rho best | rho rank-matched (rank) | rho mean | rho max | rho reference | d best | d matched | d max | ref pct | "
           "dist-Spearman best / matched / own | dRMSD best / own | bond ours | bond ref | i+2 ours | i+2 ref | Rg ours/ref | ratio | "
-          "satisfied ours / ref (%) | deviation sum ours / ref | ms | bundled relaxed under our energy: int(E_noe) (ours best .. worst) | its rank in our 20 | file rank | moved: dist-Spearman / dRMSD | d max top10 |\n"
-          "|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|")
+          "satisfied ours / ref (%) | deviation sum ours / ref | ms | bundled relaxed under our energy: int(E_noe) (ours best .. worst) | its rank in our 20 | file rank | moved: dist-Spearman / dRMSD | d max top10 | SCC ours best / bundled |\n"
+          "|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|")
 
 
 def row(cid, n, R, rep, rank, ms):
     c, cr = rep["chain"], rep["chain_ref"]
     return ("| %-12s | %4d | %6d | %.4f | %.4f (%d) | %.4f | %.4f | %.4f | %+.4f | %+.4f | %+.4f | %.2f | %.3f / %.3f / %.3f | %.2f / %.2f | "
-            "%.2f±%.2f | %.2f±%.2f | %.2f±%.2f | %.2f±%.2f | %.1f / %.1f | %.3f | %.1f / %.1f | %.4g / %.4g | %.0f | %d (%d .. %d) | %d | %d | %.4f / %.2f | %+.4f |" % (
+            "%.2f±%.2f | %.2f±%.2f | %.2f±%.2f | %.2f±%.2f | %.1f / %.1f | %.3f | %.1f / %.1f | %.4g / %.4g | %.0f | %d (%d .. %d) | %d | %d | %.4f / %.2f | %+.4f | %.4f / %.4f |" % (
                 cid, n, R, rep["rho_best"], rep["rho_matched"], rank, rep["rho_mean"], rep["rho"].max(), rep["rho_ref"], rep["delta"], rep["delta_matched"],
                 rep["delta_max"], rep["ref_percentile"], rep["sim_best"][0], rep["sim_matched"][0], rep["sim_own"][0], rep["sim_best"][1], rep["sim_own"][1],
                 c[0], c[1], cr[0], cr[1], c[2], c[3], cr[2], cr[3], c[4], cr[4], rep["rg_ratio"],
                 100.0 * rep["assess"]["best"][0] / R, 100.0 * rep["assess"]["ref"][0] / R, rep["assess"]["best"][1], rep["assess"]["ref"][1], ms,
                 int(rep["relaxed"]["e_noe"]), int(rep["e_sorted"][0]), int(rep["e_sorted"][-1]), rep["relaxed"]["rank_in_ours"], rank,
-                rep["relaxed"]["moved"][0], rep["relaxed"]["moved"][1], rep["delta_max_top10"]))
+                rep["relaxed"]["moved"][0], rep["relaxed"]["moved"][1], rep["delta_max_top10"], rep["scc"][0], rep["scc"][1]))
 
 
 def summary(reps):
@@ -88,6 +90,7 @@ def summary(reps):
     bsd = np.array([r["chain"][1] - r["chain_ref"][1] for r in reps]); a2 = np.array([r["chain"][2] - r["chain_ref"][2] for r in reps])
     a2s = np.array([r["chain"][3] - r["chain_ref"][3] for r in reps]); q05 = np.array([r["chain"][5] - r["chain_ref"][5] for r in reps]); q95 = np.array([r["chain"][6] - r["chain_ref"][6] for r in reps])
     dx = np.array([r["delta_max"] for r in reps]); dc = np.array([r["delta_closest"] for r in reps])
+    ds = np.array([r["scc"][0] - r["scc"][1] for r in reps])
     pct = np.array([r["ref_percentile"] for r in reps])
     sat = np.array([r["assess"]["best"][0] / r["assess"]["ref"][0] for r in reps]); dev = np.array([r["assess"]["best"][1] / r["assess"]["ref"][1] for r in reps])
     rk = np.array([r["relaxed"]["rank_in_ours"] for r in reps]); fr = np.array([r["file_rank"] for r in reps]); dt = np.array([r["delta_max_top10"] for r in reps])
@@ -109,7 +112,8 @@ def summary(reps):
             f"bond sd ours-ref mean {bsd.mean():+.3f}; i+2 mean ours-ref {a2.mean():+.3f}, i+2 sd ours-ref mean {a2s.mean():+.3f} (within 0.25: {(np.abs(a2s) <= 0.25).sum()}), "
             f"i+2 5% / 95% quantile ours-ref {q05.mean():+.2f} / {q95.mean():+.2f}; "
             f"reference's assessment, ours / bundled: satisfied restraints ratio mean {sat.mean():.3f} range {sat.min():.3f}-{sat.max():.3f}, "
-            f"deviation sum ratio mean {dev.mean():.3f} range {dev.min():.3f}-{dev.max():.3f}")
+            f"deviation sum ratio mean {dev.mean():.3f} range {dev.min():.3f}-{dev.max():.3f}; "
+            f"SCC (stratum-adjusted, range 3) ours best - bundled: mean {ds.mean():+.4f}, mean |d| {np.abs(ds).mean():.4f}, max |d| {np.abs(ds).max():.4f}")
 
 
 def main():
@@ -138,6 +142,10 @@ def main():
         ms = s.last_timing()[0]
         rank = bundled_rank(ref[0])
         rep = structure_report(IF, x, e[:, 0], Xr, rank, rows)
+        # the stratum-adjusted coefficient (c3d_stratified_score, range 3): our lowest-energy replica beside the bundled model, which rides
+        # along as an extra model.  Before the relaxation below replaces the replicas.
+        scc = s.stratified_score(IF, 3, 0, Xr)["scc"]
+        rep["scc"] = (scc[int(s.rank()[0])], scc[nrep])
         rep["relaxed"] = relax_reference_model(s, Xr, e[:, 0])
         rep["e_sorted"] = np.sort(e[:, 0].astype(np.int64)); rep["file_rank"] = rank
         rep["cid"] = cid

@@ -103,6 +103,10 @@ static void api_storm(int device_count) {
                 ok = ok && c3d_geometry_replicas(c, nullptr, 0, 3.5, 1, clashes.data(), bead.data(), nearest.data(), chain.data()) == C3D_OK;
                 ok = ok && c3d_separation_profile(c, nullptr, 0, picked, 3, 7.6, prof.data(), prof.data() + n, prof.data() + 2 * (size_t)n) == C3D_OK;
                 ok = ok && c3d_geometry_replicas(c, nullptr, 0, 3.5, n, clashes.data(), nullptr, nullptr, nullptr) == C3D_ERR_INVALID;
+                std::vector<double> srho(4 * (size_t)n), sscc(4);
+                std::vector<int64_t> ssums(4 * (size_t)n * C3D_STRATUM_FIELDS);
+                ok = ok && c3d_stratified_score(c, IF.data(), 3, 0, nullptr, 0, srho.data(), sscc.data(), ssums.data()) == C3D_OK;
+                ok = ok && c3d_stratified_score(c, IF.data(), 3, 2, nullptr, 0, srho.data(), nullptr, nullptr) == C3D_ERR_INVALID;
                 if (what == 2) { unsigned long long a, b, d; ok = ok && c3d_debug_tear16(c, 4, &a, &b, &d) == C3D_OK; }
             }
             if (!ok) { fprintf(stderr, "api storm thread %d: %s\n", t, c3d_last_error()); ++failures; }

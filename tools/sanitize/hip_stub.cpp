@@ -380,4 +380,56 @@ hipError_t launch_separation_profile(const double* xyz, int n, const int* pick, 
     return hipSuccess;
 }
 
+// c3d_stratified_score: the doubled average ranks inside every stratum by counting, over the "device" memory
+hipError_t launch_stratified_if(const double* IF, int n, int lo, int hi, unsigned* a, long long* saa, int* flags, hipStream_t) {
+    LaunchScope ls;
+    for (int q = 0; q < kStrFlags; ++q) flags[q] = 0;
+    size_t off = 0;
+    for (int s = lo; s <= hi; off += (size_t)(n - s), ++s) {
+        const int N = n - s;
+        saa[s - lo] = 0;
+        for (int i = 0; i < N; ++i) {
+            const double v = IF[(size_t)i * n + i + s];
+            if (!(v == IF[(size_t)(i + s) * n + i])) flags[0] = 1;
+            if (!std::isfinite(v)) flags[1] = 1;
+            long long r = 1;
+            for (int j = 0; j < N; ++j) {
+                const double w = IF[(size_t)j * n + j + s];
+                r += (w < v ? 1 : 0) + (w <= v ? 1 : 0);
+            }
+            a[off + i] = (unsigned)r;
+            saa[s - lo] += r * r;
+        }
+    }
+    return hipSuccess;
+}
+hipError_t launch_stratified_models(const double* xyz, int n, int K, int lo, int hi, const unsigned* a, const long long* saa, long long* sums, int* flags,
+                                    hipStream_t) {
+    LaunchScope ls;
+    memset(sums, 0, sizeof(long long) * 3 * (size_t)n * K);
+    for (int k = 0; k < K; ++k) {
+        const double* x = xyz + (size_t)k * 3 * n;
+        size_t off = 0;
+        for (int s = lo; s <= hi; off += (size_t)(n - s), ++s) {
+            const long long N = n - s, T = N * (N + 1);
+            std::vector<long long> q((size_t)N);
+            for (int i = 0; i < N; ++i) {
+                const double d = stub_dist(x, i, i + s);
+                if (!(d <= 50000.0)) flags[2] = 1;
+                q[(size_t)i] = d <= 50000.0 ? llround(d * 1000.0) : 0;      // (ties of the "%.3f" rounding: of no account to the harness)
+            }
+            long long sab = 0, sbb = 0;
+            for (int i = 0; i < N; ++i) {
+                long long r = 1;
+                for (int j = 0; j < N; ++j) r += (q[(size_t)j] < q[(size_t)i] ? 1 : 0) + (q[(size_t)j] <= q[(size_t)i] ? 1 : 0);
+                sab += (long long)a[off + i] * r;
+                sbb += r * r;
+            }
+            long long* const out = sums + ((size_t)k * n + s) * 3;
+            out[0] = N * sab - T * T; out[1] = N * saa[s - lo] - T * T; out[2] = N * sbb - T * T;
+        }
+    }
+    return hipSuccess;
+}
+
 }  // namespace c3d
