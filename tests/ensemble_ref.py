@@ -10,8 +10,8 @@ import numpy as np
 def distances(x):
     """[n, n] float64: the pair distances of one model [n, 3]"""
     x = np.asarray(x, dtype=np.float64)
-    u = x[:, None, :] - x[None, :, :]
-    return np.sqrt(((u[..., 0] * u[..., 0]) + u[..., 1] * u[..., 1]) + u[..., 2] * u[..., 2])
+    ux, uy, uz = (x[:, None, c] - x[None, :, c] for c in range(3))          # a component at a time: contiguous n x n arrays, the same operations
+    return np.sqrt(((ux * ux) + uy * uy) + uz * uz)
 
 
 def ensemble_map(models, pick=None, cutoff=None):

@@ -23,6 +23,7 @@ import numpy as np
 import pytest
 
 from tests.util import GOLD, SHORT, load_if, load_pdb_xyz, model_pdb, random_coil, restrained, shared_models
+from tests.util import host_ranks as _host_ranks
 
 pytestmark = pytest.mark.gpu
 
@@ -51,17 +52,6 @@ def _models(name):
     a, b = rng.integers(0, 6, size=(130, 3)), rng.integers(0, 6, size=(130, 3))
     assert len(np.unique(a, axis=0)) < 130                                     # coincident beads
     return np.stack([a, a, 3 * a, b]).astype(np.float32), None
-
-
-def _host_ranks(x):
-    """average ranks of the i<j distances of one model, pairs in row order: the host's avg_ranks over the host's distances"""
-    x = np.asarray(x, dtype=np.float64)
-    i, j = np.triu_indices(len(x), 1)
-    u = x[i] - x[j]
-    d = np.sqrt(((u[:, 0] * u[:, 0]) + u[:, 1] * u[:, 1]) + u[:, 2] * u[:, 2])
-    _, inv, cnt = np.unique(d, return_inverse=True, return_counts=True)
-    below = np.cumsum(cnt) - cnt
-    return (0.5 * (below + (below + cnt - 1)) + 1.0)[inv]
 
 
 _HOST = {}

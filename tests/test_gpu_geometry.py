@@ -8,6 +8,12 @@ Shapes, the smallest at which each part can still go wrong.  k_geo_pairs gives a
   n257                      257 beads x 5 + 2 extra fp64 models that no float holds: five row blocks / separation blocks, K = 7
   k17                       64 beads x 17: three staged model blocks in the profile, the last of one model
   the seven bundled models  n = 35 .. 455: zero to seven tile edges, against the reference's own counts
+  n6000                     6000 beads x 1 + 1 extra fp64 model on a context of its own with max_beads raised: 94 row blocks of which the last
+                            has 48 beads, past the 5120 beads a context holds by default; coils at 0.5 and 0.6 of the usual step, so that
+                            tens of thousands of pairs clash; cutoff 3.5 and sep 2 (one sep: the numpy side takes 2 s a model and sep), the
+                            profile at cutoff 7.6 over all 6000 separations.  Printed on an MI355X: 45974 and 33006 clashes, counts,
+                            nearest and extent equal, largest chain gap 4.4e-16 under a bound of 1.0e-9, largest profile gap 0.016 of
+                            its bound (mean) and 0.002 (sd)
 
 Bounds.  Distances have the host's bits, so counts, minima and maxima are compared with ==.  A sum of T same-sign fp64 terms taken in two
 orders differs by at most 2 T 2^-53 relative; the tests assert 8 T 2^-53 x the largest magnitude entering the sum (the factor 4 covers
@@ -172,6 +178,41 @@ def test_profile_equals_the_restatement_and_the_maps_diagonals(ctx, name):
         assert 0.0 < got[2][3] < 1.0                                            # the cutoff separates something
     mean, sd, contact = ctx.separation_profile(extra)                           # no cutoff: no contact profile
     assert contact is None and mean.tobytes() == ctx.separation_profile(extra, None, 7.6)[0].tobytes()
+
+
+@pytest.fixture(scope="module")
+def ctx6000():
+    """a context of 6000 beads (max_beads raised) holding the case n6000; yields (solver, extra, models)"""
+    from chromosome3d_amd import Solver
+    n = 6000
+    x = (random_coil(n, 60000) * np.float32(0.5))[None]
+    extra = (random_coil(n, 60001).astype(np.float64) * 0.6 + np.random.default_rng(6000).normal(scale=1e-3, size=(n, 3)))[None]
+    assert not np.array_equal(extra, extra.astype(np.float32))
+    s = Solver(0)
+    try:
+        s.set_option("max_beads", n)
+        restrained(s, n, 1)
+        s.set_coords(x)
+        yield s, extra, [x[0].astype(np.float64), extra[0]]
+    finally:
+        s.close()
+
+
+def test_geometry_of_6000_beads_equals_the_restatement(ctx6000):
+    """c3d_geometry_replicas beyond the default bead limit: counts, nearest and extent equal, the chain fields within 8 n 2^-53."""
+    s, extra, models = ctx6000
+    got = s.geometry(extra, 3.5, 2)
+    assert got["clashes"].shape == (2,) and got["bead_clashes"].shape == got["nearest"].shape == (2, 6000)
+    _check_geometry(got, [G.geometry(m, 3.5, 2) for m in models], models, "n6000 sep 2")
+    assert got["clashes"].min() > 10000                                         # the cutoff counts something in both models
+
+
+def test_profile_of_6000_beads_equals_the_restatement(ctx6000):
+    """c3d_separation_profile over all 6000 separations, both models, within 8 (n - s) Kp 2^-53 x the largest distance at s."""
+    s, extra, models = ctx6000
+    got = s.separation_profile(extra, None, 7.6)
+    _check_profile(got, G.separation_profile(models, None, 7.6), 6000, 2, "n6000")
+    assert 0.0 < got[2][5] < 1.0 and got[2][5999] == 0.0                        # the cutoff separates something
 
 
 def test_f64_state_is_measured_in_doubles():

@@ -1,8 +1,11 @@
 """The models of a run in one frame on the device (c3d_superpose_replicas, c3d_rmsd_table; csrc/c3d_score_superpose.inc k_sup_*) against the numpy
 restatement tests/superpose_ref.py, which fits by SVD where the device diagonalises Horn's quaternion matrix.
 
-Shapes (a staged chunk is 64 beads, a table block 16 x 16 models): n = 4, 37, 255, 256, 257, 455 with K = 1, 2, 20 replicas; 2561 beads x 2
-on a precision-64 context; one table of 17 replicas + 16 extra models (a block partial on both sides).  A case's models are three random
+Shapes (a staged chunk is 64 beads, a table block 16 x 16 models): n = 4, 37, 255, 256, 257, 455 with K = 1, 2, 20 replicas; 2049 beads x 3
+(33 chunks, the last of one bead) on the precision-32 context, whose path (the gather from floats, the padded row of the float state) is
+otherwise run to 455 beads only: three unrelated coils, two of them fitted as mirror images (largest gaps printed on an MI355X: rmsd
+3.6e-14, mean 2.9e-13, rmsf 2.3e-13, under BOUND = 1e-10); 2561 beads x 2 on a precision-64 context; one
+table of 17 replicas + 16 extra models (a block partial on both sides).  A case's models are three random
 coils and copies of them moved by random rotations, reflections (every odd model) and translations, with 0.3 A of noise, so that the
 handedness of every pair is decided by a wide margin: `precondition` asserts it on the restatement for every pair whose flag is compared.
 
@@ -29,9 +32,9 @@ CAP = 1e-9
 BOUND = {k: 1e-10 for k in ("rmsd", "mean", "rmsf", "coords", "table", "energy")}
 assert all(v <= CAP for v in BOUND.values())
 
-CASES = {"n4k2": (4, 2), "n37k20": (37, 20), "n255k1": (255, 1), "n256k2": (256, 2), "n257k20": (257, 20), "n455k20": (455, 20)}
+CASES = {"n4k2": (4, 2), "n37k20": (37, 20), "n255k1": (255, 1), "n256k2": (256, 2), "n257k20": (257, 20), "n455k20": (455, 20), "n2049k3": (2049, 3)}
 CASES64 = {"n37k20": (37, 20), "n455k2": (455, 2), "n2561k2": (2561, 2)}
-SEED = {4: 1, 37: 4, 255: 1, 256: 1, 257: 1, 455: 1, 2561: 1}        # chosen on the CPU: every case passes `precondition`
+SEED = {4: 1, 37: 4, 255: 1, 256: 1, 257: 1, 455: 1, 2049: 1, 2561: 1}        # chosen on the CPU: every case passes `precondition`
 GAPS = {}                                                            # figure -> largest gap seen by this process (tools/superpose.py prints it)
 
 

@@ -91,6 +91,26 @@ def restrained(s, n, nrep, seed=7):
     s.init_replicas(nrep)
 
 
+def pair_distances(x):
+    """the i<j distances of one model [n, 3] in row order, sqrt(((ux ux) + uy uy) + uz uz) in float64: the host's, operation for operation"""
+    x = np.asarray(x, dtype=np.float64)
+    i, j = np.triu_indices(len(x), 1)
+    u = x[i] - x[j]
+    return np.sqrt(((u[:, 0] * u[:, 0]) + u[:, 1] * u[:, 1]) + u[:, 2] * u[:, 2])
+
+
+def average_ranks(d):
+    """average ranks 1..m of a vector, ties sharing the mean of their first and last position: the host's avg_ranks"""
+    _, inv, cnt = np.unique(d, return_inverse=True, return_counts=True)
+    below = np.cumsum(cnt) - cnt
+    return (0.5 * (below + (below + cnt - 1)) + 1.0)[inv]
+
+
+def host_ranks(x):
+    """average ranks of the i<j distances of one model, pairs in row order: the host's avg_ranks over the host's distances"""
+    return average_ranks(pair_distances(x))
+
+
 def shared_models(name):
     """(replica coordinates [M, n, 3] float32, extra models [E, n, 3] float64 or None) of the cases the compare and ensemble modules share:
     n257 = 257 beads x 5 + 2 extra models that no float holds, k17 = 64 beads x 17"""
