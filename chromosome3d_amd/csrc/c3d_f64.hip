@@ -297,74 +297,13 @@ __global__ __launch_bounds__(kLbfgsMoveRows64) void k64_lbfgs_move(const Model64
         for (int k = tid; k < (int)(sizeof(LbfgsState) / sizeof(double)); k += ROWS) dst[k] = src[k];
     }
     __syncthreads();
-    // 2. the compact form, serially (k_lbfgs_move's statements)
+    // 2. the compact form, serially: c3d_lbfgs_serial.inc, k_lbfgs_move's text
     if (tid == 0) {
-        if (first) {
-            st.cnt = 0; st.mem = mem0; st.head = mem0 - 1; st.resets = 0;
-            st.gamma = fp.dt_start * fp.dt_start * p.kacc;                // kind 6's first step length in k64_step
-        } else {
-            st.mem = min(max(st.mem, 1), M);
-            st.head = min(max(st.head, 0), st.mem - 1);
-            st.cnt = min(max(st.cnt, 0), st.mem);
-            const int mem = st.mem;
-            const int nx = st.head + 1 == mem ? 0 : st.head + 1;
-            const double sy = sums[4 * nx + 2], yy = sums[4 * nx + 3], ss = sums[Q - 4];
-            if (sy > 1e-12 * sqrt(ss * yy)) {
-                st.head = nx;
-                st.cnt = min(st.cnt + 1, mem);
-                for (int i = 0; i < st.cnt; ++i) {
-                    int sl = nx - i; if (sl < 0) sl += mem;
-                    st.SY[sl][nx] = sums[4 * sl + 2];
-                    st.YY[sl][nx] = sums[4 * sl + 3];
-                    st.YY[nx][sl] = sums[4 * sl + 3];
-                }
-                st.gamma = sy / yy;
-            } else {
-                st.cnt = 0;
-                st.resets += 1;
-                st.gamma *= 2.0;
-            }
-            st.gamma = fmin(fmax(st.gamma, 1e-7), 1e2);
-        }
-        const int mem = st.mem, cnt = st.cnt;
-        const double g = st.gamma, ff = sums[Q - 3];
-        int sl[M];
-        double ps[M], py[M], u[M], w[M], top[M];
-        for (int i = 0; i < cnt; ++i) {                  // age order: i = 0 the oldest pair
-            int k = st.head - (cnt - 1) + i; if (k < 0) k += mem;
-            sl[i] = k;
-            ps[i] = -sums[4 * k];                        // S'g, Y'g with g = -F
-            py[i] = -sums[4 * k + 1];
-        }
-        for (int i = cnt - 1; i >= 0; --i) {             // R u = S'g, R = upper triangle of S'Y
-            double a = ps[i];
-            for (int j = i + 1; j < cnt; ++j) a -= st.SY[sl[i]][sl[j]] * u[j];
-            u[i] = a / st.SY[sl[i]][sl[i]];
-        }
-        for (int i = 0; i < cnt; ++i) {                  // w = (D + gamma Y'Y) u - gamma Y'g
-            double a = st.SY[sl[i]][sl[i]] * u[i];
-            for (int j = 0; j < cnt; ++j) a += g * st.YY[sl[i]][sl[j]] * u[j];
-            w[i] = a - g * py[i];
-        }
-        for (int i = 0; i < cnt; ++i) {                  // R' top = w
-            double a = w[i];
-            for (int j = 0; j < i; ++j) a -= st.SY[sl[j]][sl[i]] * top[j];
-            top[i] = a / st.SY[sl[i]][sl[i]];
-        }
-        // d = -H g = gamma F - sum top_i s_i + gamma sum u_i y_i;  F.d > 0 or the memory goes
-        double fd = g * ff;
-        for (int i = 0; i < cnt; ++i) fd += top[i] * ps[i] - g * u[i] * py[i];
-        int mask = 0;
-        for (int j = 0; j < 2 * M; ++j) coef[1 + j] = 0.0;
-        if (fd > 0.0) {
-            for (int i = 0; i < cnt; ++i) { coef[1 + sl[i]] = -top[i]; coef[1 + M + sl[i]] = g * u[i]; mask |= 1 << sl[i]; }
-        } else {
-            st.cnt = 0;
-            st.resets += 1;
-        }
-        coef[0] = g;
-        shi[0] = mask;
-        shi[1] = st.head + 1 == mem ? 0 : st.head + 1;   // where this move's s goes: the slot the next evaluation completes
+#define C3D_LBFGS_COEF double
+#define C3D_LBFGS_GAMMA0 (fp.dt_start * fp.dt_start * p.kacc)                /* kind 6's first step length in k64_step */
+#include "c3d_lbfgs_serial.inc"
+#undef C3D_LBFGS_GAMMA0
+#undef C3D_LBFGS_COEF
     }
     __syncthreads();
     // 3. the rows of this workgroup
@@ -652,6 +591,36 @@ hipError_t launch_lbfgs_move64(const DevModel& d, const Model64& m, const Step64
     const int q = parity ^ 1;
     hipLaunchKernelGGL(k64_lbfgs_move, dim3((d.n + kLbfgsMoveRows64 - 1) / kLbfgsMoveRows64, d.nrep_g), dim3(kLbfgsMoveRows64), 0, s, m, p, fp,
                        d.rep_base, b.X[parity], b.X[q], b.V[q], lb.hist, lb.part, b.P[q], lb.S[parity], lb.S[q], mem);
+    return hipGetLastError();
+}
+// The serial section of k64_lbfgs_move as a table (c3d_debug_lbfgs_direction on a precision-64 context): k_lbfgs_direction in doubles.
+__global__ void k64_lbfgs_direction(const Step64 p, const Fire64 fp, const int rows, const double* __restrict__ sums_in,
+                                    const LbfgsState* __restrict__ sin, const int* __restrict__ flags, LbfgsState* __restrict__ sout,
+                                    double* __restrict__ coef_out, int* __restrict__ shi_out) {
+    constexpr int Q = kLbfgsQ, M = kLbfgsMaxPairs;
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= rows) return;
+    double sums[Q];
+    for (int k = 0; k < Q; ++k) sums[k] = sums_in[(size_t)r * Q + k];
+    LbfgsState st = sin[r];
+    double coef[1 + 2 * M];
+    int shi[2];
+    const bool first = flags[2 * r] != 0;
+    const int mem0 = flags[2 * r + 1];
+    {
+#define C3D_LBFGS_COEF double
+#define C3D_LBFGS_GAMMA0 (fp.dt_start * fp.dt_start * p.kacc)
+#include "c3d_lbfgs_serial.inc"
+#undef C3D_LBFGS_GAMMA0
+#undef C3D_LBFGS_COEF
+    }
+    sout[r] = st;
+    for (int k = 0; k < 1 + 2 * M; ++k) coef_out[(size_t)r * (1 + 2 * M) + k] = coef[k];
+    shi_out[2 * r] = shi[0]; shi_out[2 * r + 1] = shi[1];
+}
+hipError_t launch_lbfgs_direction64(const Step64& p, const Fire64& fp, int rows, const double* sums, const LbfgsState* in, const int* flags,
+                                    LbfgsState* out, double* coef, int* shi, hipStream_t s) {
+    hipLaunchKernelGGL(k64_lbfgs_direction, dim3((rows + 63) / 64), dim3(64), 0, s, p, fp, rows, sums, in, flags, out, coef, shi);
     return hipGetLastError();
 }
 // c3d_eval_f64's force in the step's form (p of kind 3), X[parity] -> Fout

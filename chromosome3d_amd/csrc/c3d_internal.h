@@ -192,6 +192,10 @@ hipError_t launch_lbfgs_eval(const DevModel& m, const DevStep& p, const DevBuffe
                              const StepForm& f, hipStream_t s);
 hipError_t launch_lbfgs_move(const DevModel& m, const DevStep& p, const DevFire& fp, const DevBuffers& b, const LbfgsBuffers& lb, int parity,
                              int mem, hipStream_t s);
+// c3d_lbfgs_serial.inc (the serial section of k_lbfgs_move) on `rows` rows of (sums[kLbfgsQ], LbfgsState, flags = (first, mem0)), a thread a
+// row (c3d_debug_lbfgs_direction): out = the state left, coef[1 + 2 kLbfgsMaxPairs] widened to doubles, shi[2] = (slot mask, slot of s)
+hipError_t launch_lbfgs_direction(const DevModel& m, const DevFire& fp, int rows, const double* sums, const LbfgsState* in, const int* flags,
+                                  LbfgsState* out, double* coef, int* shi, hipStream_t s);
 size_t pair_targets_floats(int n, int npad);           // size of DevBuffers::tgs2
 hipError_t launch_pair_targets(const DevModel& m, const float* tgt, float* tgs2, hipStream_t s);
 struct StepRun {    // `count` consecutive steps with the same parameters
@@ -339,6 +343,8 @@ hipError_t launch_lbfgs_eval64(const DevModel& d, const Model64& m, const Step64
                                int parity, int mem, hipStream_t s);
 hipError_t launch_lbfgs_move64(const DevModel& d, const Model64& m, const Step64& p, const Fire64& fp, const Buffers64& b, const LbfgsBuffers64& lb,
                                int parity, int mem, hipStream_t s);
+hipError_t launch_lbfgs_direction64(const Step64& p, const Fire64& fp, int rows, const double* sums, const LbfgsState* in, const int* flags,
+                                    LbfgsState* out, double* coef, int* shi, hipStream_t s);      // the same of k64_lbfgs_move
 hipError_t launch_targets64(const Model64& m, const Form64& f, const int32_t* t10, double* T, hipStream_t s);   // in the encoding f's kernel expects
 // the integer tenths of a restraint list (R pairs, 0-based, every pair once) into the zeroed n x n matrix t10, both triangles
 hipError_t launch_tenths64(int n, int R, const int32_t* ri, const int32_t* rj, const int32_t* rt10, int32_t* t10, hipStream_t s);

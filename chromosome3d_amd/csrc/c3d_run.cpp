@@ -578,6 +578,64 @@ extern "C" int c3d_debug_step_scalars(c3d_ctx* c, int kind, float dt, float t_ba
     return C3D_OK;
 }
 
+// Test hook: the serial section of the L-BFGS move (c3d_lbfgs_serial.inc) on a table of rows (c3d.h) — k_lbfgs_direction, or
+// k64_lbfgs_direction on a precision-64 context.  DevModel / DevFire, Step64 / Fire64 come from the functions every launch uses, so the
+// first step's gamma is formed from what the host folds into them (acc, kacc).
+static_assert(C3D_LBFGS_MAX_PAIRS == c3d::kLbfgsMaxPairs && C3D_LBFGS_SUMS == c3d::kLbfgsQ, "c3d.h states the L-BFGS stage's sizes");
+static_assert(sizeof(c3d::LbfgsState) == 4 * sizeof(int32_t) + C3D_LBFGS_STATE_DOUBLES * sizeof(double), "LbfgsState is 4 ints, then doubles");
+extern "C" int c3d_debug_lbfgs_direction(c3d_ctx* c, int rows, const double* sums, const int32_t* state_int_in, const double* state_dbl_in,
+                                         const int32_t* first, const int32_t* mem0, int32_t* state_int_out, double* state_dbl_out,
+                                         double* coef, int32_t* mask_slot) {
+    if (!c || !sums || !state_int_in || !state_dbl_in || !first || !mem0 || !state_int_out || !state_dbl_out || !coef || !mask_slot ||
+        rows < 1 || rows > (1 << 16))
+        return fail(C3D_ERR_INVALID, "c3d_debug_lbfgs_direction: bad arguments");
+    for (int r = 0; r < rows; ++r)
+        if (mem0[r] < 1 || mem0[r] > c3d::kLbfgsMaxPairs) return fail(C3D_ERR_INVALID, "c3d_debug_lbfgs_direction: mem0 is 1 .. 8 (lbfgs_memory)");
+    if (c->n < 1) return fail(C3D_ERR_INVALID, "c3d_debug_lbfgs_direction: set the targets first (the model is built for a bead count)");
+    const bool f64 = c->precision == 64;
+    C3D_ENTRY(c, f64 ? unit_bit(UNIT_F64) : 0u);
+    constexpr int ND = C3D_LBFGS_STATE_DOUBLES, NC = C3D_LBFGS_COEFS;
+    std::vector<c3d::LbfgsState> st((size_t)rows);
+    std::vector<int> flags(2 * (size_t)rows);
+    for (int r = 0; r < rows; ++r) {
+        c3d::LbfgsState& s = st[r];
+        s.cnt = state_int_in[4 * r]; s.head = state_int_in[4 * r + 1]; s.mem = state_int_in[4 * r + 2]; s.resets = state_int_in[4 * r + 3];
+        memcpy(reinterpret_cast<char*>(&s) + 4 * sizeof(int32_t), state_dbl_in + (size_t)ND * r, sizeof(double) * ND);     // gamma, SY, YY
+        flags[2 * r] = first[r] != 0; flags[2 * r + 1] = mem0[r];
+    }
+    DevTmp<double> d_sums, d_coef;
+    DevTmp<c3d::LbfgsState> d_in, d_out;
+    DevTmp<int> d_flags, d_shi;
+    HIP_TRY(hipMalloc(&d_sums.p, sizeof(double) * C3D_LBFGS_SUMS * (size_t)rows));
+    HIP_TRY(hipMalloc(&d_coef.p, sizeof(double) * NC * (size_t)rows));
+    HIP_TRY(hipMalloc(&d_in.p, sizeof(c3d::LbfgsState) * (size_t)rows));
+    HIP_TRY(hipMalloc(&d_out.p, sizeof(c3d::LbfgsState) * (size_t)rows));
+    HIP_TRY(hipMalloc(&d_flags.p, sizeof(int) * 2 * (size_t)rows));
+    HIP_TRY(hipMalloc(&d_shi.p, sizeof(int) * 2 * (size_t)rows));
+    HIP_TRY(hipMemcpyAsync(d_sums.p, sums, sizeof(double) * C3D_LBFGS_SUMS * (size_t)rows, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_in.p, st.data(), sizeof(c3d::LbfgsState) * (size_t)rows, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_flags.p, flags.data(), sizeof(int) * 2 * (size_t)rows, hipMemcpyHostToDevice, c->stream));
+    if (f64) {
+        const c3d::Model64 m64 = c3d::model64(dev_model(c), c->model);
+        LAUNCH_TRY("fp64 L-BFGS direction launch", c3d::launch_lbfgs_direction64(c3d::step64(m64, 9, 0.0, 1.0, 1.0, 0.85, 0.0), c3d::fire64(c->fire), rows,
+                                                                                 d_sums.p, d_in.p, d_flags.p, d_out.p, d_coef.p, d_shi.p, c->stream));
+    } else {
+        LAUNCH_TRY("L-BFGS direction launch", c3d::launch_lbfgs_direction(dev_model(c), dev_fire(c), rows, d_sums.p, d_in.p, d_flags.p, d_out.p,
+                                                                          d_coef.p, d_shi.p, c->stream));
+    }
+    HIP_TRY(hipMemcpyAsync(coef, d_coef.p, sizeof(double) * NC * (size_t)rows, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(st.data(), d_out.p, sizeof(c3d::LbfgsState) * (size_t)rows, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(flags.data(), d_shi.p, sizeof(int) * 2 * (size_t)rows, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int r = 0; r < rows; ++r) {
+        const c3d::LbfgsState& s = st[r];
+        state_int_out[4 * r] = s.cnt; state_int_out[4 * r + 1] = s.head; state_int_out[4 * r + 2] = s.mem; state_int_out[4 * r + 3] = s.resets;
+        memcpy(state_dbl_out + (size_t)ND * r, reinterpret_cast<const char*>(&s) + 4 * sizeof(int32_t), sizeof(double) * ND);
+        mask_slot[2 * r] = flags[2 * r]; mask_slot[2 * r + 1] = flags[2 * r + 1];
+    }
+    return C3D_OK;
+}
+
 // name of the kernel the last op of the last range ran on, as rocprofv3 prints it (without the argument list): the record its launch was made from
 extern "C" const char* c3d_step_kernel_name(const c3d_ctx* c) {
     static thread_local char buf[96];

@@ -75,6 +75,7 @@ SIGNATURES = {
     "c3d_step_kernel_name": (C.c_char_p, [_vp]),
     "c3d_debug_tear16": (_i, [_vp, _i, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
     "c3d_debug_step_scalars": (_i, [_vp, _i, _f, _f, _i, _fp, _fp, _i32p, _fp, _fp, _i32p]),
+    "c3d_debug_lbfgs_direction": (_i, [_vp, _i, _dp, _i32p, _dp, _i32p, _i32p, _i32p, _dp, _dp, _i32p]),
     "c3d_dg_smoothed_bounds": (_i, [_vp, _fp, _fp]),
     "c3d_debug_if_ranks": (_i, [_vp, _dp, _i, _dp, _dp, C.POINTER(C.c_size_t)]),
     "c3d_eval": (_i, [_vp, _f, _f, _f, _fp, _dp]),
@@ -110,6 +111,7 @@ SIGNATURES = {
 SUPERPOSE_MIRROR, SUPERPOSE_APPLY = 1, 2      # C3D_SUPERPOSE_MIRROR, C3D_SUPERPOSE_APPLY
 GEOMETRY_FIELDS = 6                           # C3D_GEOMETRY_FIELDS
 STRATUM_FIELDS = 3                            # C3D_STRATUM_FIELDS
+LBFGS_MAX_PAIRS, LBFGS_SUMS, LBFGS_STATE_DOUBLES, LBFGS_COEFS = 8, 36, 129, 17      # C3D_LBFGS_*
 
 _lib = None
 

@@ -211,6 +211,20 @@ class Solver:
                                                 _l.fptr(sc), _l.fptr(so), _l.i32ptr(no)))
         return sc, so, no
 
+    def debug_lbfgs_direction(self, sums, state_int, state_dbl, first, mem0):
+        """The serial section of the L-BFGS move as a table (c3d_debug_lbfgs_direction), in the context's precision: sums [K, 36], state_int
+        [K, 4] = (cnt, head, mem, resets), state_dbl [K, 129] = (gamma, S'Y [8, 8], Y'Y [8, 8]), first [K], mem0 [K] -> (state_int out,
+        state_dbl out, coef [K, 17] = gamma, a by slot, b by slot; mask_slot [K, 2]) under the context's model and FIRE values."""
+        sums, state_dbl = np.ascontiguousarray(sums, dtype=np.float64), np.ascontiguousarray(state_dbl, dtype=np.float64)
+        state_int, first, mem0 = (np.ascontiguousarray(a, dtype=np.int32) for a in (state_int, first, mem0))
+        K = first.shape[0]
+        assert sums.shape == (K, _l.LBFGS_SUMS) and state_int.shape == (K, 4) and state_dbl.shape == (K, _l.LBFGS_STATE_DOUBLES) and mem0.shape == (K,)
+        si, sd = np.empty((K, 4), dtype=np.int32), np.empty((K, _l.LBFGS_STATE_DOUBLES), dtype=np.float64)
+        coef, ms = np.empty((K, _l.LBFGS_COEFS), dtype=np.float64), np.empty((K, 2), dtype=np.int32)
+        _l.check(self._L.c3d_debug_lbfgs_direction(self._h, K, _l.dptr(sums), _l.i32ptr(state_int), _l.dptr(state_dbl), _l.i32ptr(first),
+                                                   _l.i32ptr(mem0), _l.i32ptr(si), _l.dptr(sd), _l.dptr(coef), _l.i32ptr(ms)))
+        return si, sd, coef, ms
+
     @property
     def step_kernel_name(self):
         return self._L.c3d_step_kernel_name(self._h).decode()

@@ -341,6 +341,26 @@ int c3d_debug_tear16(c3d_ctx* ctx, int iterations, unsigned long long* unit_read
  * touches nothing of the solve. */
 int c3d_debug_step_scalars(c3d_ctx* ctx, int kind, float dt, float t_bath, int rows, const float* psum, const float* state_in,
                            const int32_t* npos_in, float* scalars, float* state_out, int32_t* npos_out);
+/* Test hook: the serial section of an L-BFGS move (stage kind 8) as a table.  Between its two barriers one thread of every workgroup of
+ * the move kernel decides the step from the replica's sums: the pair test s.y > 1e-12 sqrt(s.s y.y), the ring of lbfgs_memory slots,
+ * gamma (s.y / y.y after a kept pair, doubled after a rejected one, clamped to [1e-7, 1e2]), the two triangular solves of the compact form
+ * and the descent test F.d > 0.  This runs those very statements (one source text, shared with the kernels) for `rows` independent rows,
+ * in the precision of the context: the fp32 kernels' section (coefficients rounded to float) or, on a precision-64 context, the fp64
+ * kernels'; the first step's gamma is dt_start^2 * 418.4 / mass from the context's model and FIRE values, as that precision forms it.
+ * Row r in: sums[36 r ..] = per ring slot j (F.s_j, F.y_j, s_j.y, y_j.y) at 4 j, then s.s, F.F, 0, 0 — (s, y) the pair this step completes,
+ * F the force just evaluated; the state of the previous step as state_int_in[4 r ..] = (cnt pairs held, head = slot of the newest, mem =
+ * ring size, resets) and state_dbl_in[129 r ..] = (gamma, S'Y [8][8], Y'Y [8][8], both indexed by slot); first[r] != 0: the stage's first
+ * step (the state is then not read); mem0[r] = lbfgs_memory, 1 .. 8.  A state out of range is clamped first: mem to [1, 8], head to
+ * [0, mem - 1], cnt to [0, mem].  Row r out: the state the step leaves, coef[17 r ..] = (gamma, a_j by slot, b_j by slot) of the direction
+ * gamma F + sum a_j s_j + sum b_j y_j (0 for a slot outside it), mask_slot[2 r ..] = (bit j set: slot j is in the direction, the slot this
+ * move's s goes to).  Needs the bead count (targets set); touches nothing of the solve. */
+#define C3D_LBFGS_MAX_PAIRS 8
+#define C3D_LBFGS_SUMS (4 * C3D_LBFGS_MAX_PAIRS + 4)
+#define C3D_LBFGS_STATE_DOUBLES (1 + 2 * C3D_LBFGS_MAX_PAIRS * C3D_LBFGS_MAX_PAIRS)
+#define C3D_LBFGS_COEFS (1 + 2 * C3D_LBFGS_MAX_PAIRS)
+int c3d_debug_lbfgs_direction(c3d_ctx* ctx, int rows, const double* sums, const int32_t* state_int_in, const double* state_dbl_in,
+                              const int32_t* first, const int32_t* mem0, int32_t* state_int_out, double* state_dbl_out, double* coef,
+                              int32_t* mask_slot);
 /* Test hook of A7 (c3d_embed_replicas): U, L (n*n each, row-major) = the smoothed distance bounds the embedding draws its trial distances
  * from — b0 on |i-j| = 1, the target on restrained pairs, [r0_rep x the last stage's repel, 1e30] elsewhere, then all-pairs shortest
  * paths on U, the inverse triangle inequality on L, L <= U.  The same kernels and arguments as the embedding; no bead limit of its own.

@@ -131,6 +131,7 @@ size_t pair_targets_floats(int n, int npad) { return (size_t)n * npad; }
 hipError_t launch_pair_targets(const DevModel&, const float*, float*, hipStream_t) { LaunchScope ls; return hipSuccess; }
 hipError_t launch_lbfgs_eval(const DevModel&, const DevStep&, const DevBuffers&, const LbfgsBuffers&, int, int, const StepForm&, hipStream_t) { LaunchScope ls; return hipSuccess; }
 hipError_t launch_lbfgs_move(const DevModel&, const DevStep&, const DevFire&, const DevBuffers&, const LbfgsBuffers&, int, int, hipStream_t) { LaunchScope ls; return hipSuccess; }
+hipError_t launch_lbfgs_direction(const DevModel&, const DevFire&, int, const double*, const LbfgsState*, const int*, LbfgsState*, double*, int*, hipStream_t) { LaunchScope ls; return hipSuccess; }
 AnnealIO anneal_io(const DevBuffers& b, int parity) {
     const int q = parity ^ 1;
     AnnealIO io;
@@ -168,6 +169,7 @@ Fire64 fire64(const c3d_fire_params&) { return Fire64{}; }
 hipError_t launch_step64(const DevModel&, const Model64&, const Step64&, const Fire64&, const Form64&, const Buffers64&, int, hipStream_t) { LaunchScope ls; return hipSuccess; }
 hipError_t launch_lbfgs_eval64(const DevModel&, const Model64&, const Step64&, const Form64&, const Buffers64&, const LbfgsBuffers64&, int, int, hipStream_t) { LaunchScope ls; return hipSuccess; }
 hipError_t launch_lbfgs_move64(const DevModel&, const Model64&, const Step64&, const Fire64&, const Buffers64&, const LbfgsBuffers64&, int, int, hipStream_t) { LaunchScope ls; return hipSuccess; }
+hipError_t launch_lbfgs_direction64(const Step64&, const Fire64&, int, const double*, const LbfgsState*, const int*, LbfgsState*, double*, int*, hipStream_t) { LaunchScope ls; return hipSuccess; }
 hipError_t launch_tenths64(int, int, const int32_t*, const int32_t*, const int32_t*, int32_t*, hipStream_t) { LaunchScope ls; return hipSuccess; }
 hipError_t launch_targets64(const Model64&, const Form64&, const int32_t*, double*, hipStream_t) { LaunchScope ls; return hipSuccess; }
 hipError_t launch_import64(const DevModel&, const float*, const Buffers64&, hipStream_t) { LaunchScope ls; return hipSuccess; }
