@@ -1,6 +1,6 @@
 // c3d_analysis.cpp — host unit of libc3d.so: the output side.  What a run's models are worth and how they relate, from the coordinates
 // resident on the device (kernels: c3d_score.hip): c3d_score_replicas, c3d_compare_replicas, c3d_superpose_replicas, c3d_rmsd_table,
-// c3d_ensemble_map, c3d_ensemble_score, c3d_geometry_replicas, c3d_separation_profile, c3d_stratified_score and the test hooks c3d_debug_if_ranks / c3d_debug_distance_ranks.  What they share comes first: typed
+// c3d_ensemble_map, c3d_ensemble_score, c3d_geometry_replicas, c3d_separation_profile, c3d_stratified_score, c3d_bead_scores and the test hooks c3d_debug_if_ranks / c3d_debug_distance_ranks.  What they share comes first: typed
 // scratch slots (Slot, Block, Carve, CallScratch), the ranker (rank_matrix) and the models of a call (model_set_check, model_set_coords, gather_models).
 #include <limits>
 
@@ -793,5 +793,112 @@ extern "C" int c3d_stratified_score(c3d_ctx* c, const double* IF, int range, int
         if (scc) scc[k] = any ? num / den : nan;
     }
     ++c->stratified_runs;
+    return C3D_OK;
+}
+
+// ---- a model's fit to the data bead by bead (c3d_score.hip k_bead_*) ----
+// c3d_bead_scores' one allocation: the models, the bead list (if one was given), the doubled IF ranks of the rows asked for (B x n, only
+// where a coefficient was asked for), their sums of squares, C, A, B and the tallies of every model and row, and the flag words.  IF itself
+// lies in the context's d_score.
+struct BeadScratch : Carve {
+    Slot<double> xyz;
+    Slot<int32_t> list, restrained, satisfied;
+    Slot<unsigned> a;
+    Slot<long long> saa, sums, dev;
+    Slot<int> flags;
+    BeadScratch(int n, int K, int B, bool listed, bool ranked) {
+        xyz = take<double>(3 * (size_t)n * K);
+        if (listed) list = take<int32_t>((size_t)B);
+        if (ranked) a = take<unsigned>((size_t)B * n);
+        saa = take<long long>((size_t)B);
+        sums = take<long long>((size_t)C3D_BEAD_FIELDS * B * K);
+        restrained = take<int32_t>((size_t)B);
+        satisfied = take<int32_t>((size_t)B * K);
+        dev = take<long long>((size_t)B * K);
+        flags = take<int>(c3d::kStrFlags);
+    }
+};
+
+extern "C" int c3d_bead_scores(c3d_ctx* c, const double* IF, int range, const int32_t* beads, int n_beads, const double* extra_xyz, int n_extra, double* rho,
+                               int64_t* sums, int32_t* restrained, int32_t* satisfied, int64_t* dev_milli) {
+    const char* const who = "c3d_bead_scores";
+    if (int rc = model_set_check(c, who, 2, "no pair", extra_xyz, n_extra)) return rc;
+    const int n = c->n, K = c->nrep + n_extra;
+    const bool ranked = rho || sums, tallied = restrained || satisfied || dev_milli;
+    if (range < 1) return fail(C3D_ERR_INVALID, "c3d_bead_scores: range < 1");
+    if (range > n - 1) return fail(C3D_ERR_INVALID, "c3d_bead_scores: range leaves no row a partner (range > n-1)");
+    if (ranked && !IF) return fail(C3D_ERR_INVALID, "c3d_bead_scores: the coefficient needs the IF matrix");
+    if (!ranked && !tallied) return fail(C3D_ERR_INVALID, "c3d_bead_scores: every output is NULL");
+    if (!beads && n_beads != 0) return fail(C3D_ERR_INVALID, "c3d_bead_scores: n_beads without a bead list (NULL and 0 ask for every bead)");
+    if (beads) {
+        if (n_beads <= 0) return fail(C3D_ERR_INVALID, "c3d_bead_scores: a bead list with n_beads <= 0");
+        for (int b = 0; b < n_beads; ++b)
+            if (beads[b] < 0 || beads[b] >= n || (b > 0 && beads[b] <= beads[b - 1]))
+                return fail(C3D_ERR_INVALID, "c3d_bead_scores: the bead list holds indices 0..n-1, strictly ascending");
+    }
+    if (int rc = model_set_coords(c, who, extra_xyz, n_extra)) return rc;
+    C3D_ENTRY(c, unit_bit(UNIT_SCORE));
+    // the targets of the tallies: the float matrix every context fills; the integer tenths of a precision-64 context where it is not there
+    const float* const d_tgt = c->buf.tgt;
+    const int* const d_t10 = d_tgt ? nullptr : c->b64.t10;
+    if (tallied && !d_tgt && !d_t10) return fail(C3D_ERR_INVALID, "c3d_bead_scores: the tallies need the context's target matrix");
+    const int B = beads ? n_beads : n;
+    double* d_IF = nullptr;
+    if (ranked) {
+        if (int rc = score_scratch(c, sizeof(double) * (size_t)n * n)) return rc;
+        d_IF = static_cast<double*>(c->d_score);
+    }
+    const BeadScratch L(n, K, B, beads != nullptr, ranked);
+    CallScratch tmp;
+    if (int rc = tmp.alloc(L.total, who)) return rc;
+    PassEvents ev;
+    for (hipEvent_t& x : ev.e) HIP_TRY(hipEventCreate(&x));
+    static_assert(sizeof(long long) == sizeof(int64_t) && sizeof(int) == sizeof(int32_t), "the device's sums and counts are the caller's int64_t and int32_t");
+    const int* const d_list = beads ? L.list.at(tmp.p) : nullptr;
+    int* const d_flags = L.flags.at(tmp.p);
+    HIP_TRY(hipMemsetAsync(d_flags, 0, L.flags.bytes(), c->stream));
+    if (beads) HIP_TRY(hipMemcpyAsync(L.list.at(tmp.p), beads, L.list.bytes(), hipMemcpyHostToDevice, c->stream));
+    float ms_if = 0, ms_models = 0;
+    if (ranked) {
+        HIP_TRY(hipMemcpyAsync(d_IF, IF, sizeof(double) * (size_t)n * n, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipEventRecord(ev.e[0], c->stream));
+        LAUNCH_TRY("bead launch", c3d::launch_bead_if(d_IF, n, range, d_list, B, L.a.at(tmp.p), L.saa.at(tmp.p), d_flags, c->stream));
+        HIP_TRY(hipEventRecord(ev.e[1], c->stream));
+        if (int rc = read_back(c, d_flags, L.flags.bytes())) return rc;
+        const int* const flags = static_cast<const int*>(c->h_stage);
+        if (flags[1]) return fail(C3D_ERR_INVALID, "c3d_bead_scores: an IF entry of the rows asked for is not finite");
+        if (flags[3]) return fail(C3D_ERR_HIP, "c3d_bead_scores: internal: the ranks of a row do not add up to N(N+1)");
+        HIP_TRY(hipEventElapsedTime(&ms_if, ev.e[0], ev.e[1]));
+    }
+    double* const d_xyz = L.xyz.at(tmp.p);
+    if (int rc = gather_models(c, ModelSource::STATE, 0, c->nrep, d_xyz, extra_xyz, n_extra, "superpose launch")) return rc;
+    HIP_TRY(hipEventRecord(ev.e[2], c->stream));
+    LAUNCH_TRY("bead launch", c3d::launch_bead_models(d_xyz, n, K, range, d_list, B, ranked ? L.a.at(tmp.p) : nullptr, L.saa.at(tmp.p), tallied ? d_tgt : nullptr, c->npad,
+                                                      tallied ? d_t10 : nullptr, c->model.min_sep, L.sums.at(tmp.p), L.restrained.at(tmp.p), L.satisfied.at(tmp.p),
+                                                      L.dev.at(tmp.p), d_flags, c->stream));
+    HIP_TRY(hipEventRecord(ev.e[3], c->stream));
+    if (int rc = read_back(c, d_flags, L.flags.bytes())) return rc;
+    if (static_cast<const int*>(c->h_stage)[2]) return fail(C3D_ERR_INVALID, "c3d_bead_scores: a pair distance exceeds 50000 A (the limit of device and host scoring)");
+    // straight into the caller's arrays (the sums into one of the call where only rho was asked for), as c3d_stratified_score does
+    std::vector<int64_t> own;
+    if (rho && !sums) own.resize(L.sums.count);
+    int64_t* const h = sums ? sums : own.data();
+    if (ranked) HIP_TRY(hipMemcpyAsync(h, L.sums.at(tmp.p), L.sums.bytes(), hipMemcpyDeviceToHost, c->stream));
+    if (restrained) HIP_TRY(hipMemcpyAsync(restrained, L.restrained.at(tmp.p), L.restrained.bytes(), hipMemcpyDeviceToHost, c->stream));
+    if (satisfied) HIP_TRY(hipMemcpyAsync(satisfied, L.satisfied.at(tmp.p), L.satisfied.bytes(), hipMemcpyDeviceToHost, c->stream));
+    if (dev_milli) HIP_TRY(hipMemcpyAsync(dev_milli, L.dev.at(tmp.p), L.dev.bytes(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipEventElapsedTime(&ms_models, ev.e[2], ev.e[3]));
+    c->bead_if_ms = ms_if;
+    c->bead_models_ms = ms_models;
+    // rho on the host, from the integers, with the header's expression
+    if (rho) {
+        const double nan = std::numeric_limits<double>::quiet_NaN();
+        for (size_t r = 0; r < (size_t)K * B; ++r) {
+            const int64_t* const q = h + r * C3D_BEAD_FIELDS;
+            rho[r] = q[1] > 0 && q[2] > 0 ? (double)q[0] / sqrt((double)q[1] * (double)q[2]) : nan;
+        }
+    }
+    ++c->bead_runs;
     return C3D_OK;
 }

@@ -1039,6 +1039,9 @@ extern "C" int c3d_get_stat(const c3d_ctx* c, const char* key, double* value) {
     else if (!strcmp(key, "stratified_runs")) *value = (double)c->stratified_runs;
     else if (!strcmp(key, "stratified_if_ms")) *value = c->stratified_if_ms;
     else if (!strcmp(key, "stratified_models_ms")) *value = c->stratified_models_ms;
+    else if (!strcmp(key, "bead_runs")) *value = (double)c->bead_runs;
+    else if (!strcmp(key, "bead_if_ms")) *value = c->bead_if_ms;
+    else if (!strcmp(key, "bead_models_ms")) *value = c->bead_models_ms;
     else if (!strcmp(key, "cluster_xcd_count")) *value = (double)c->xcd_count;
     else if (!strcmp(key, "cluster_xcd_base")) *value = (double)c->xcd_base;
     else if (!strcmp(key, "cluster_ok")) *value = c->cl_ok ? 1.0 : 0.0;

@@ -225,6 +225,8 @@ struct c3d_ctx {
     long geometry_runs = 0, separation_runs = 0;   // stats: completed calls of c3d_geometry_replicas / c3d_separation_profile
     long stratified_runs = 0;                      // stat: completed calls of c3d_stratified_score
     double stratified_if_ms = 0, stratified_models_ms = 0;   // stats: device time of the last completed call's two passes (HIP events)
+    long bead_runs = 0;                            // stat: completed calls of c3d_bead_scores
+    double bead_if_ms = 0, bead_models_ms = 0;     // stats: device time of the last completed call's two passes (the first 0 where no IF was ranked)
     long k1_recomputed = 0, k1_patched = 0;   // K1: near-tie elements redone on the host in the reference's order / changed by it
     long graph_captures = 0, graph_launches = 0, step_launches = 0, resident_launches = 0, cluster_launches = 0;
     bool has_two_point = false;            // the program holds two-point minimiser steps (run_ops splits ranges at their borders)

@@ -477,6 +477,19 @@ inline size_t stratified_pairs(int n, int lo, int hi) { return (size_t)(hi - lo 
 hipError_t launch_stratified_if(const double* IF, int n, int lo, int hi, unsigned* a, long long* saa, int* flags, hipStream_t s);
 hipError_t launch_stratified_models(const double* xyz, int n, int K, int lo, int hi, const unsigned* a, const long long* saa, long long* sums, int* flags,
                                     hipStream_t s);
+// A model's fit to the data bead by bead (c3d_bead_scores; k_bead_*).  beads (device): nb ascending bead indices, or null for every bead
+// (nb = n); row b is bead i = beads[b], its partners J(i) = { j : |i-j| >= range }.  flags: the kStrFlags ints above, cleared by the caller.
+// launch_bead_if: a (nb x n) = at column j in J(i) the doubled average rank of IF(i, j) inside the row (other columns are not written),
+// saa[b] = their sum of squares (0 for a row of fewer than two partners); flags[1]: a value of an asked row is not finite, [3] internal.
+// launch_bead_models: sums (K x nb x C3D_BEAD_FIELDS) = C, A, B of every model and row (0 for fewer than two partners; not written when
+// a is null: no ranking); over the partners j with a target t10 > 0 tenths and |i-j| >= min_sep — tgt (n x npad floats, t10 / 10) or,
+// where that is null, t10 (n x n ints) — restrained (nb), satisfied and dev_milli (K x nb): their number, the reference's net
+// satisfaction count and deviation in thousandths of an A (not written when tgt and t10 are both null).  flags[2]: a pair of an asked bead
+// further apart than 50 000 A (or not a number).
+hipError_t launch_bead_if(const double* IF, int n, int range, const int* beads, int nb, unsigned* a, long long* saa, int* flags, hipStream_t s);
+hipError_t launch_bead_models(const double* xyz, int n, int K, int range, const int* beads, int nb, const unsigned* a, const long long* saa, const float* tgt,
+                              int npad, const int* t10, int min_sep, long long* sums, int* restrained, int* satisfied, long long* dev_milli, int* flags,
+                              hipStream_t s);
 
 // Target matrix entry: NOE target in Angstrom, 0 = no restraint (host c3d_set_restraints and K1).
 inline float encode_target_host(float t) { return t > 0 ? t : 0.0f; }

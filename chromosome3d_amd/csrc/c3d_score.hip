@@ -26,6 +26,8 @@
 //                             k_sep_*    the distance against the genomic separation (c3d_separation_profile)
 //   c3d_score_stratified.inc  k_str_*    IF against model distance inside every genomic separation: one LDS sort a (stratum, model) and
 //                             integer sums (c3d_stratified_score)
+//   c3d_score_bead.inc        k_bead_*   the same ranking inside every row of IF — a Spearman coefficient a bead — and the reference's
+//                             restraint tallies a bead (c3d_bead_scores)
 #include "c3d_score_core.h"
 
 namespace c3d {
@@ -260,13 +262,16 @@ hipError_t launch_if_rank_sort(double* M, int n, int range, unsigned long long* 
 #include "c3d_score_ensemble.inc"
 #include "c3d_score_geometry.inc"
 #include "c3d_score_stratified.inc"
+#include "c3d_score_bead.inc"
 
-// loads the unit's code object on the current device and gives the k_str_* kernels their dynamic-LDS allowance (c3d_gate.cpp "code objects":
+// loads the unit's code object on the current device and gives the k_str_* and k_bead_* kernels their dynamic-LDS allowance (c3d_gate.cpp "code objects":
 // once per device, never beside a launch)
 hipError_t preload_score_unit() {
     hipFuncAttributes a;
     const hipError_t e = hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_score_round));
-    return e == hipSuccess ? str_prepare_unit() : e;
+    if (e != hipSuccess) return e;
+    const hipError_t es = str_prepare_unit();
+    return es == hipSuccess ? bead_prepare_unit() : es;
 }
 
 }  // namespace c3d

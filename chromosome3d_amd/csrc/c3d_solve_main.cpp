@@ -13,6 +13,8 @@
 //       <prefix>_separation.txt, distance and contact share against genomic separation over the models (or the --ensemble-top best)
 //   --stratified <prefix> writes <prefix>_scc.txt — per model the stratum-adjusted rank correlation of IF and distance — and
 //       <prefix>_strata.txt, the Spearman coefficient inside every genomic separation, one column a model
+//   --per-bead <prefix> writes <prefix>_beads.txt — per bead and model the Spearman coefficient of the bead's row of IF against its distances,
+//       and how many of the bead's restraints the model satisfies and by how much it misses them
 //
 // Success convention of the reference: <ID>_<M>.pdb exists, iam.running removed; on failure
 // iam.running is renamed iam.failed and the exit code is non-zero (:266-283).
@@ -67,6 +69,12 @@ static void usage() {
             "                                          <prefix>_strata.txt: one row `s N rho_1 ... rho_M` per separation, N = n - s pairs, the models' columns\n"
             "                                          in rank order (%%.6f; `nan` where IF or the distances of the stratum are constant)]\n"
             "                 [--stratified-max-sep <S>   the largest separation of --stratified; default 0: n-1]\n"
+            "                 [--per-bead <prefix>   which bins are placed badly, computed on the device; needs --if.  <prefix>_beads.txt: one row per bead,\n"
+            "                                        `bead restrained rho_1 satisfied_1 dev_1 ... rho_M satisfied_M dev_M`, the models' columns in rank order\n"
+            "                                        (lowest int(E_noe) first): the bead's 1-based index, the number of its restraints, and per model the\n"
+            "                                        Spearman coefficient of the bead's row of IF against its distances over |i-j| >= 3 (%%.6f; `nan` where a\n"
+            "                                        side is constant, e.g. an unmappable bin), the reference's net count of satisfied restraints of the bead\n"
+            "                                        and the summed deviation of the others in A (%%.3f)]\n"
             "                 [--accepted   also write <ID>a_<k>.pdb beside every <ID>_<k>.pdb, as CNS does for structures it accepts]\n");
 }
 
@@ -96,7 +104,7 @@ int main(int argc, char** argv) {
     // (rc -13, "GPU coredump: execvp failed") before the runtime has said WHICH exception — round 5 lost the only evidence of one that way.
     setenv("HSA_DISABLE_COREDUMP_ON_EXCEPTION", "1", 0);          // (0: a user's own setting wins)
     const double t_start = now_s();
-    std::string if_path, tbl_path, out_dir, id, seq_arg, similarity_path, rmsf_path, ensemble_prefix, geometry_prefix, stratified_prefix;
+    std::string if_path, tbl_path, out_dir, id, seq_arg, similarity_path, rmsf_path, ensemble_prefix, geometry_prefix, stratified_prefix, per_bead_prefix;
     int superpose = 0, ensemble_top = 0, stratified_max_sep = 0;
     double ensemble_cutoff = -1;      // < 0: 2 x b0
     double clash_cutoff = 3.5;        // the figure of the reference's assessment
@@ -144,6 +152,7 @@ int main(int argc, char** argv) {
         else if (s == "--geometry") geometry_prefix = next("--geometry");   // clashes, chain envelope, distance against separation (c3d_geometry_replicas, c3d_separation_profile)
         else if (s == "--stratified") stratified_prefix = next("--stratified");   // per-separation Spearman and their combination (c3d_stratified_score)
         else if (s == "--stratified-max-sep") stratified_max_sep = atoi(next("--stratified-max-sep"));
+        else if (s == "--per-bead") per_bead_prefix = next("--per-bead");   // per-bead Spearman and restraint tallies (c3d_bead_scores)
         else if (s == "--clash-cutoff") clash_cutoff = atof(next("--clash-cutoff"));
         else if (s == "--clash-sep") clash_sep = atoi(next("--clash-sep"));
         else if (s == "-h" || s == "--help") { usage(); return 0; }
@@ -151,6 +160,7 @@ int main(int argc, char** argv) {
     }
     if (out_dir.empty() || (if_path.empty() == tbl_path.empty()) || models < 1) { usage(); return 2; }
     if (!stratified_prefix.empty() && if_path.empty()) { fprintf(stderr, "c3d_solve: --stratified needs --if: a run started from --tbl has no IF matrix\n"); return 2; }
+    if (!per_bead_prefix.empty() && if_path.empty()) { fprintf(stderr, "c3d_solve: --per-bead needs --if: a run started from --tbl has no IF matrix\n"); return 2; }
     if (id.empty()) {
         std::string base = if_path.empty() ? std::string("model") : if_path.substr(if_path.find_last_of('/') + 1);
         if (base.size() > 4 && base.substr(base.size() - 4) == ".txt") base.resize(base.size() - 4);
@@ -362,6 +372,33 @@ int main(int argc, char** argv) {
         for (int s = range; s <= hi; ++s) {
             fprintf(f, "%d %d", s, n - s);
             for (int k = 0; k < models; ++k) put(f, rho[(size_t)order[k] * n + s]);
+            fprintf(f, "\n");
+        }
+        fclose(f);
+    }
+    if (!per_bead_prefix.empty()) {
+        std::vector<int32_t> order(models);
+        CHECK(c3d_rank(ctx, order.data()));
+        const int range = 3;                                                              // spearman_IF_pdb.pl's range
+        std::vector<double> rho((size_t)models * n);
+        std::vector<int32_t> restrained(n), satisfied((size_t)models * n);
+        std::vector<int64_t> dev((size_t)models * n);
+        CHECK(c3d_bead_scores(ctx, IF, range, nullptr, 0, nullptr, 0, rho.data(), nullptr, restrained.data(), satisfied.data(), dev.data()));
+        const std::string path = per_bead_prefix + "_beads.txt";
+        FILE* f = fopen(path.c_str(), "w");
+        if (!f) { fprintf(stderr, "c3d_solve: cannot write %s\n", path.c_str()); return fail_exit(out_dir); }
+        fprintf(f, "# bead restrained rho_1 satisfied_1 dev_1 ... rho_%d satisfied_%d dev_%d   (columns: the models in rank order; model r is %s_<r>.pdb)\n", models, models,
+                models, id.c_str());
+        fprintf(f, "# models:");
+        for (int k = 0; k < models; ++k) fprintf(f, " %u", first_rep + (unsigned)order[k] + 1u);
+        fprintf(f, "\n# rho: Spearman(IF[i][j], d(i,j)) over |i-j| >= %d; satisfied: net count within 0.5 A; dev: summed deviation beyond 0.2 A, in A\n", range);
+        for (int i = 0; i < n; ++i) {
+            fprintf(f, "%d %d", i + 1, restrained[i]);
+            for (int k = 0; k < models; ++k) {
+                const size_t at = (size_t)order[k] * n + i;
+                if (std::isnan(rho[at])) fprintf(f, " nan"); else fprintf(f, " %.6f", rho[at]);
+                fprintf(f, " %d %.3f", satisfied[at], (double)dev[at] / 1000.0);
+            }
             fprintf(f, "\n");
         }
         fclose(f);

@@ -91,6 +91,7 @@ SIGNATURES = {
     "c3d_geometry_replicas": (_i, [_vp, _dp, _i, _d, _i, C.POINTER(C.c_int64), _i32p, _dp, _dp]),
     "c3d_separation_profile": (_i, [_vp, _dp, _i, _i32p, _i, _d, _dp, _dp, _dp]),
     "c3d_stratified_score": (_i, [_vp, _dp, _i, _i, _dp, _i, _dp, _dp, C.POINTER(C.c_int64)]),
+    "c3d_bead_scores": (_i, [_vp, _dp, _i, _i32p, _i, _dp, _i, _dp, C.POINTER(C.c_int64), _i32p, _i32p, C.POINTER(C.c_int64)]),
     "c3d_rank": (_i, [_vp, _i32p]),
     "c3d_reduce_model": (_i, [_dp, _i, _dp]),
     "c3d_model_similarity": (_i, [_dp, _dp, _i, _dp, _dp]),
@@ -111,6 +112,7 @@ SIGNATURES = {
 SUPERPOSE_MIRROR, SUPERPOSE_APPLY = 1, 2      # C3D_SUPERPOSE_MIRROR, C3D_SUPERPOSE_APPLY
 GEOMETRY_FIELDS = 6                           # C3D_GEOMETRY_FIELDS
 STRATUM_FIELDS = 3                            # C3D_STRATUM_FIELDS
+BEAD_FIELDS = 3                               # C3D_BEAD_FIELDS
 LBFGS_MAX_PAIRS, LBFGS_SUMS, LBFGS_STATE_DOUBLES, LBFGS_COEFS = 8, 36, 129, 17      # C3D_LBFGS_*
 
 _lib = None

@@ -228,6 +228,20 @@ def stratified_report(solver, IF, rng=3, max_sep=0, extra=None, sums=False):
     return out
 
 
+def bead_report(solver, IF, rng=3, beads=None, extra=None):
+    """Which bins are placed badly, on the device: Solver.bead_scores' dict — per model and bead "rho" (the Spearman coefficient of the
+    bead's row of IF against its distances over |i-j| >= rng; 3 is the reference's range), "sums", "restrained", "satisfied" and
+    "dev_milli" — with "beads" [B], the 0-based indices the columns stand for, "partners" [B], the number of pairs N_i of every row, and
+    "dev" [K, B], the deviation in Angstrom."""
+    out = solver.bead_scores(IF, rng, beads, extra)
+    n = solver.n
+    i = np.arange(n) if beads is None else np.asarray(beads, dtype=np.int64)
+    out["beads"] = i
+    out["partners"] = np.maximum(0, i - rng + 1) + np.maximum(0, n - i - rng)
+    out["dev"] = out["dev_milli"] / 1000.0
+    return out
+
+
 def build_models(solver, model_count=MODELCOUNT, seed=MD_SEED, first_replica=0, model=None, stages=None, fire=None,
                  gtol=1e-2, check_every=250, final_kind=5):
     """The replacement of `cns_solve < dgsa.inp` (:254-289): runs the whole annealing schedule

@@ -407,6 +407,31 @@ class Solver:
                                               out["sums"].ctypes.data_as(C.POINTER(C.c_int64)) if sums else None))
         return out
 
+    def bead_scores(self, IF, range=3, beads=None, extra=None):
+        """A dict of arrays over the K models of compare() and the B beads asked for (beads: ascending indices, None: every bead), on the
+        device (c3d_bead_scores): "rho" [K, B], the Spearman coefficient of row i of IF against the "%.3f" distances of bead i to every bead
+        at least `range` away (NaN where a side is constant: an all-zero row of IF, a row of fewer than two partners); "sums" [K, B, 3]
+        int64, the exact integers C, A, B it is formed from; "restrained" [B], the number of the bead's restraints (targets of the context,
+        |i-j| >= min_sep, both sides); "satisfied" [K, B], the reference's net count of them within 0.5 A; "dev_milli" [K, B] int64, the
+        summed deviation of those beyond 0.2 A in thousandths of an A.  IF None: the tallies alone.  Nothing of the solve changes."""
+        xptr, E = self._extra_models(extra)
+        K = self.nrep + E
+        b = None if beads is None else np.ascontiguousarray(beads, dtype=np.int32)
+        B = self.n if b is None else int(b.size)
+        i64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))
+        out = {"restrained": np.empty(B, dtype=np.int32), "satisfied": np.empty((K, B), dtype=np.int32), "dev_milli": np.empty((K, B), dtype=np.int64)}
+        IFc = None
+        if IF is not None:
+            IFc = np.ascontiguousarray(IF, dtype=np.float64)
+            assert IFc.shape == (self.n, self.n)
+            out["rho"] = np.empty((K, B), dtype=np.float64)
+            out["sums"] = np.empty((K, B, _l.BEAD_FIELDS), dtype=np.int64)
+        _l.check(self._L.c3d_bead_scores(self._h, _l.dptr(IFc) if IFc is not None else None, int(range), _l.i32ptr(b) if b is not None else None,
+                                         0 if b is None else B, xptr, E, _l.dptr(out["rho"]) if IFc is not None else None,
+                                         i64(out["sums"]) if IFc is not None else None, _l.i32ptr(out["restrained"]), _l.i32ptr(out["satisfied"]),
+                                         i64(out["dev_milli"])))
+        return out
+
     def rank(self):
         r = np.empty(self.nrep, dtype=np.int32)
         _l.check(self._L.c3d_rank(self._h, _l.i32ptr(r)))

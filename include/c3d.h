@@ -326,7 +326,8 @@ int c3d_last_timing(const c3d_ctx* ctx, double* ms_total, long* steps, long* lau
  * c3d_rmsd_table), "ensemble_map_runs" / "ensemble_score_runs" (completed calls of c3d_ensemble_map / c3d_ensemble_score),
  * "geometry_runs" / "separation_runs" (completed calls of c3d_geometry_replicas / c3d_separation_profile),
  * "stratified_runs" (completed calls of c3d_stratified_score), "stratified_if_ms" / "stratified_models_ms" (device time of the two passes
- * of the last completed one, from HIP events: measurement). */
+ * of the last completed one, from HIP events: measurement), "bead_runs" (completed calls of c3d_bead_scores), "bead_if_ms" /
+ * "bead_models_ms" (device time of its two passes in the last completed call, the first 0 where no IF was ranked: measurement). */
 int c3d_get_stat(const c3d_ctx* ctx, const char* key, double* value);
 /* Test hook, no reference counterpart: the multi-step kernel's hand-off trusts a 16-byte unit once its tag word matches — i.e. that a
  * 16-byte aligned store is never observed half-written by a 16-byte load on gfx950.  This runs that exact store / load pair (one producer
@@ -600,6 +601,56 @@ int c3d_separation_profile(c3d_ctx* ctx, const double* extra_xyz, int n_extra, c
 #define C3D_STRATUM_FIELDS 3
 int c3d_stratified_score(c3d_ctx* ctx, const double* IF, int range, int max_sep, const double* extra_xyz, int n_extra,
                          double* rho, double* scc, int64_t* sums);
+/* A model's fit to the data bead by bead, on the device (c3d_score_bead.inc k_bead_*): which bins are placed badly.  Two tracks a bead,
+ * both the reference's own metrics restricted to one first index: the Spearman coefficient of row i of IF against the distances of bead i
+ * (spearman_IF_pdb.pl:42-70 with r1 = i), and the restraint tallies of bead i (count_satisfied_tbl_rows, sum_noe_dev;
+ * chromosome3D.pl:447-485, 581-600).
+ *
+ * Models.  K = n_replicas + n_extra, numbered and taken exactly as c3d_stratified_score takes them: on a precision-64 context the fp64
+ *   state bit for bit, otherwise the floats taken as doubles; extra models are n x 3 doubles, checked as there.
+ * Beads.  beads = NULL with n_beads = 0 means every bead: B = n.  Otherwise beads holds n_beads indices in 0..n-1, strictly ascending, and
+ *   B = n_beads.  Every output is indexed [k][b] in list order, b the position in the list.
+ * Distance.  q_k(i,j) = the unit's cmp_dist, with the host's bits, rounded to integer thousandths of an A as the reference's "%.3f" does
+ *   (round_milli_dev).  A pair (i, j), j != i, of an asked bead beyond 50 000 A (or not a number) refuses the call after the pass that
+ *   finds it, as in c3d_stratified_score.
+ * Row.  Row i is J(i) = { j : |i-j| >= range }, N_i = max(0, i-range+1) + max(0, n-i-range) members.  It pairs IF[i][j] with q_k(i,j).
+ *   - IF is read from row i only: no symmetry is required.
+ *   - Zeros of IF count, as in the reference.  -0.0 equals 0.0 (rank_key).
+ *   - A value of a row asked for that is not finite refuses the call.
+ * Doubled ranks and integer sums, exactly as in c3d_stratified_score.
+ *   - a_j and b_j are #{smaller} + #{not larger} + 1 within the row: 2 x the average ranks, integers.
+ *   - T = N(N+1), C = N sum a_j b_j - T^2, A = N sum a_j^2 - T^2, B = N sum b_j^2 - T^2.
+ *   - All are exact in int64: 4 N^4 < 2.9e17 at N = 16383.
+ *   - sums[(k*B + b)*C3D_BEAD_FIELDS + 0..2] holds C, A, B.  The three are 0 when N_i <= 1.
+ * Coefficient.  rho[k*B + b] = (double)C / sqrt((double)A * (double)B) when A > 0 and B > 0, otherwise NaN; formed on the host from the
+ *   integers that were read back.  An all-zero IF row (an unmappable bin) is therefore NaN, not an error.
+ * Tallies.  A partner j of bead i counts iff the context's target matrix holds a target t10 > 0 (in tenths of an A) for (i,j) and
+ *   |i-j| >= model.min_sep (the rule of c3d_score_replicas' kernel); partners on both sides of i.  With d = (double)q / 1000.0 and
+ *   t = (double)t10 / 10.0 the comparisons are the reference's, in doubles:
+ *   - satisfied: +1 if d < t + 0.5, -1 if d < t - 0.5.
+ *   - dev_milli: + (q - 100 t10) if d > t + 0.2, + (100 t10 - q) if d < t - 0.2: an exact integer of thousandths.
+ *   - restrained[b] is the number of such partners (it does not depend on the model), satisfied[k*B + b] the net count,
+ *     dev_milli[k*B + b] the deviation.  Summed over all beads each is twice the whole model's figure (every pair has two ends).
+ *   - The targets are read from the float matrix every context fills (t10 = lrintf(10 t), as c3d_score_replicas reads it); a precision-64
+ *     context whose float matrix is not filled is read from the integer tenths it keeps: the same integers.
+ *
+ * Any output may be NULL, not all five.  IF may be NULL when neither rho nor sums is asked for (IF is not read then).
+ * C3D_ERR_INVALID with the function's name, before any launch and with nothing written: no context or no replicas, n < 2, range < 1 or
+ * range > n-1, rho or sums asked for without IF, every output NULL, a bead list that is out of range, not strictly ascending or given with
+ * n_beads <= 0, beads = NULL with n_beads != 0, and the model-set refusals of c3d_geometry_replicas.  C3D_ERR_INVALID after the pass that
+ * finds it, with nothing written: a non-finite IF value in a row asked for, a model too wide.  C3D_ERR_NOMEM: no device memory.
+ * No state of the solve changes; two calls return the same bytes; extra models leave the replicas' entries their bits.  No atomics and no
+ * floating-point sum on the device: k_bead_if sorts a row of IF in LDS, k_bead_model a row of distances a (bead, model) and, in the same
+ * pass over j, tallies the bead's restrained partners; every sum is an int64 block reduction.
+ * Memory: IF goes into the context's scoring scratch as c3d_stratified_score uploads it (8 n^2 bytes, kept; not where only tallies are
+ * asked for).  Everything else is one allocation per call, freed before it returns: 24 n K (models) + 4 B n (IF ranks of the rows asked
+ * for, where a coefficient is asked for) + 16 B (sums of squares, bead list, restrained) + (24 + 4 + 8) B K (sums, satisfied, dev_milli)
+ * + flags: 1.2 MB at 455 x 20 with every bead, about 1 GiB of ranks at 16384 beads with every bead (a bead list cuts that to its rows).
+ * Stat "bead_runs" counts the calls that completed; "bead_if_ms" / "bead_models_ms" are the device time of the two passes. */
+#define C3D_BEAD_FIELDS 3
+int c3d_bead_scores(c3d_ctx* ctx, const double* IF, int range, const int32_t* beads, int n_beads,
+                    const double* extra_xyz, int n_extra,
+                    double* rho, int64_t* sums, int32_t* restrained, int32_t* satisfied, int64_t* dev_milli);
 /* rank[k] = replica index with the k-th lowest int(E_noe) (chromosome3D.pl:796-802,822-828);
  * ties broken by replica id. */
 int c3d_rank(c3d_ctx* ctx, int32_t* rank);

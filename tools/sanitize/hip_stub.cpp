@@ -434,4 +434,70 @@ hipError_t launch_stratified_models(const double* xyz, int n, int K, int lo, int
     return hipSuccess;
 }
 
+// c3d_bead_scores: the doubled average ranks inside every asked row by counting, and the tallies, over the "device" memory
+hipError_t launch_bead_if(const double* IF, int n, int range, const int* beads, int nb, unsigned* a, long long* saa, int* flags, hipStream_t) {
+    LaunchScope ls;
+    for (int b = 0; b < nb; ++b) {
+        const int i = beads ? beads[b] : b;
+        const double* row = IF + (size_t)i * n;
+        saa[b] = 0;
+        for (int j = 0; j < n; ++j) {
+            if ((i > j ? i - j : j - i) < range) continue;
+            if (!std::isfinite(row[j])) flags[1] = 1;
+            long long r = 1;
+            for (int m = 0; m < n; ++m)
+                if ((i > m ? i - m : m - i) >= range) r += (row[m] < row[j] ? 1 : 0) + (row[m] <= row[j] ? 1 : 0);
+            a[(size_t)b * n + j] = (unsigned)r;
+            saa[b] += r * r;
+        }
+    }
+    return hipSuccess;
+}
+hipError_t launch_bead_models(const double* xyz, int n, int K, int range, const int* beads, int nb, const unsigned* a, const long long* saa, const float* tgt,
+                              int npad, const int* t10, int min_sep, long long* sums, int* restrained, int* satisfied, long long* dev_milli, int* flags,
+                              hipStream_t) {
+    LaunchScope ls;
+    std::vector<long long> q((size_t)n);
+    for (int k = 0; k < K; ++k) {
+        const double* x = xyz + (size_t)k * 3 * n;
+        for (int b = 0; b < nb; ++b) {
+            const int i = beads ? beads[b] : b;
+            long long N = 0, sab = 0, sbb = 0, cnt = 0, sat = 0, dev = 0;
+            for (int j = 0; j < n; ++j) {
+                const double d = stub_dist(x, i, j);
+                if (!(d <= 50000.0)) flags[2] = 1;
+                q[(size_t)j] = d <= 50000.0 ? llround(d * 1000.0) : 0;      // (ties of the "%.3f" rounding: of no account to the harness)
+                N += (i > j ? i - j : j - i) >= range ? 1 : 0;
+            }
+            for (int j = 0; j < n; ++j) {
+                const int sep = i > j ? i - j : j - i;
+                if (a && sep >= range) {
+                    long long r = 1;
+                    for (int m = 0; m < n; ++m)
+                        if ((i > m ? i - m : m - i) >= range) r += (q[(size_t)m] < q[(size_t)j] ? 1 : 0) + (q[(size_t)m] <= q[(size_t)j] ? 1 : 0);
+                    sab += (long long)a[(size_t)b * n + j] * r;
+                    sbb += r * r;
+                }
+                if ((tgt || t10) && sep >= min_sep && sep > 0) {
+                    const long long t = tgt ? (long long)lrintf(tgt[(size_t)i * npad + j] * 10.0f) : (long long)t10[(size_t)i * n + j];
+                    if (t <= 0) continue;
+                    const double dd = (double)q[(size_t)j] / 1000.0, tv = (double)t / 10.0;
+                    ++cnt;
+                    sat += (dd < tv + 0.5 ? 1 : 0) - (dd < tv - 0.5 ? 1 : 0);
+                    if (dd > tv + 0.2) dev += q[(size_t)j] - 100 * t;
+                    if (dd < tv - 0.2) dev += 100 * t - q[(size_t)j];
+                }
+            }
+            const size_t at = (size_t)k * nb + b;
+            if (a) {
+                const long long T = N * (N + 1);
+                const bool on = N > 1;
+                sums[3 * at] = on ? N * sab - T * T : 0; sums[3 * at + 1] = on ? N * saa[b] - T * T : 0; sums[3 * at + 2] = on ? N * sbb - T * T : 0;
+            }
+            if (tgt || t10) { if (k == 0) restrained[b] = (int)cnt; satisfied[at] = (int)sat; dev_milli[at] = dev; }
+        }
+    }
+    return hipSuccess;
+}
+
 }  // namespace c3d
