@@ -1,7 +1,7 @@
-// c3d_api.cpp — C-ABI host of libc3d.so: the context and its configuration (model, schedule, options, stats), device buffers, targets
-// (K1), start structures and the embedding, coordinates in floats and doubles, c3d_eval*.  Compiled with hipcc (-x hip) for the HIP runtime
-// API only, like the other three host units: c3d_gate.cpp (code objects, the gate every entry runs under), c3d_run.cpp (schedule -> launch
-// program, its executor) and c3d_analysis.cpp (score, compare, superpose); c3d_ctx.h holds what they share.  The kernels live in
+// c3d_api.cpp — C-ABI host of libc3d.so: the context's lifetime, device buffers, targets (K1), start structures and the embedding,
+// coordinates in floats and doubles, c3d_eval*.  Compiled with hipcc (-x hip) for the HIP runtime API only, like the other four host units:
+// c3d_config.cpp (model, schedule, options, stats), c3d_gate.cpp (code objects, the gate every entry runs under), c3d_run.cpp (schedule ->
+// launch program, its executor) and c3d_analysis.cpp (score, compare, superpose); c3d_ctx.h holds what they share.  The kernels live in
 // c3d_device.hip (per-step), c3d_cluster.hip (multi-step), c3d_embed.hip, c3d_score.hip, c3d_f64.hip, c3d_sym.hip.
 #include <cstdlib>
 
@@ -28,11 +28,15 @@ inline void philox4x32(const uint32_t ctr_in[4], const uint32_t key_in[2], uint3
     memcpy(out, c, sizeof(c));
 }
 inline double u01(uint32_t u) { return ((double)u + 0.5) * (1.0 / 4294967296.0); }
-void normals4(uint64_t seed, uint32_t replica, uint32_t bead, uint32_t purpose, double g[4]) {
+// four random words of (seed, replica) for one bead and purpose: the key is the pair, the counter what it is drawn for
+void philox_draw(uint64_t seed, uint32_t replica, uint32_t bead, uint32_t purpose, uint32_t out[4]) {
     const uint32_t ctr[4] = {bead, purpose, 0u, 0u};
     const uint32_t key[2] = {(uint32_t)(seed & 0xFFFFFFFFu) ^ (replica * 0x9E3779B9u), (uint32_t)(seed >> 32) + replica};
+    philox4x32(ctr, key, out);
+}
+void normals4(uint64_t seed, uint32_t replica, uint32_t bead, uint32_t purpose, double g[4]) {
     uint32_t r[4];
-    philox4x32(ctr, key, r);
+    philox_draw(seed, replica, bead, purpose, r);
     const double two_pi = 6.283185307179586476925286766559;
     double a = sqrt(-2.0 * log(u01(r[0]))), b = two_pi * u01(r[1]);
     g[0] = a * cos(b); g[1] = a * sin(b);
@@ -40,21 +44,6 @@ void normals4(uint64_t seed, uint32_t replica, uint32_t bead, uint32_t purpose, 
     g[2] = a * cos(b); g[3] = a * sin(b);
 }
 
-void free_replica_buffers(c3d_ctx* c) {
-    for (int k = 0; k < 2; ++k) {
-        dev_free(c->buf.X[k]); dev_free(c->buf.V[k]); dev_free(c->buf.P[k]); dev_free(c->buf.S[k]);
-    }
-    dev_free(c->d_crec);
-    c->crec_bytes = 0; c->cl_ok = false;
-    dev_free(c->buf.Vinit); dev_free(c->buf.E); dev_free(c->d_feval);
-    dev_free(c->d_sym_scratch); dev_free(c->d_sym_tiles);
-    dev_free(c->lb.hist); dev_free(c->lb.part); dev_free(c->lb.S[0]); dev_free(c->lb.S[1]);
-    dev_free(c->lb64.hist); dev_free(c->lb64.part); dev_free(c->lb64.S[0]); dev_free(c->lb64.S[1]);
-    c->lbfgs_parity = -1;
-    dev_free(c->b64.T); dev_free(c->b64.t10); dev_free(c->b64.Vinit); dev_free(c->b64.F);
-    for (int k = 0; k < 2; ++k) { dev_free(c->b64.X[k]); dev_free(c->b64.V[k]); dev_free(c->b64.P[k]); dev_free(c->b64.S[k]); }
-    c->have_replicas = false;
-}
 // Everything else a context holds, once its streams have drained: graphs, replica state, targets, the program, claim sets, staging, score
 // scratch, events, streams.  c3d_destroy's alone; the caller holds the gate.
 void release_context(c3d_ctx* c) {
@@ -71,25 +60,16 @@ void release_context(c3d_ctx* c) {
     if (c->stream) (void)hipStreamDestroy(c->stream);
 }
 
-// the length the clamp form divides (d - t) by: rswitch, or mrswitch for device potential 4 (1 / DevModel::inv_rs in either case)
-float clamp_scale(const c3d_ctx* c) { return dev_model(c).noe_pot == 4 ? c->model.mrswitch : c->model.rswitch; }
-
-// What a change of configuration (c3d_set_model / c3d_set_schedule / c3d_set_option) makes stale
-enum Stale : unsigned { STALE_REPLICAS = 1, STALE_GRAPHS = 2, STALE_PAIR_TARGETS = 4, STALE_PROGRAM = 8 };
-// the caller holds the gate when this releases anything device-side (drop_stale_gated)
-void drop_stale(c3d_ctx* c, unsigned stale) {
-    if (stale & STALE_REPLICAS) free_replica_buffers(c);
-    if (stale & STALE_PAIR_TARGETS) dev_free(c->buf.tgs2);
-    if (stale & STALE_PROGRAM) build_program(c);       // drops the graphs
-    else if (stale & STALE_GRAPHS) drop_graphs(c);
-}
-
 void set_dims(c3d_ctx* c, int n) {
     c->n = n;
     c->npad = (n + 255) / 256 * 256;   // one column block of the pair kernel = 256 columns
     c->ntiles = (n + c3d::kTileRows - 1) / c3d::kTileRows;
     c->rep_floats = (size_t)3 * c->npad;
 }
+
+// Coordinate `comp` of the k-th padding bead behind a replica's beads: far from the chain and from one another (k64_import places them
+// the same way).  Whole numbers of at most 34080 (kPadCoord = 1e4, k < 256): exact in float, so the doubles of c3d_set_coords_f64 are these.
+float pad_coord(int comp, int k) { return c3d::kPadCoord * (float)(comp + 1) + 16.0f * (float)k; }
 
 // AoS host (nrep*n*3) -> SoA padded device layout
 void pack(const c3d_ctx* c, const float* aos, std::vector<float>& soa, bool pad_far) {
@@ -99,7 +79,7 @@ void pack(const c3d_ctx* c, const float* aos, std::vector<float>& soa, bool pad_
         for (int comp = 0; comp < 3; ++comp) {
             for (int i = 0; i < c->n; ++i) base[(size_t)comp * c->npad + i] = aos[((size_t)r * c->n + i) * 3 + comp];
             if (pad_far)
-                for (int i = c->n; i < c->npad; ++i) base[(size_t)comp * c->npad + i] = c3d::kPadCoord * (float)(comp + 1) + 16.0f * (float)(i - c->n);
+                for (int i = c->n; i < c->npad; ++i) base[(size_t)comp * c->npad + i] = pad_coord(comp, i - c->n);
         }
     }
 }
@@ -111,24 +91,13 @@ void unpack(const c3d_ctx* c, const float* soa, float* aos) {
     }
 }
 
-// c3d_set_schedule / c3d_set_option: drops what a change made stale, inside the gate when that releases anything device-side (the replica
-// state is allocated from X[0] and t10 on: c3d_init_replicas)
-int drop_stale_gated(c3d_ctx* c, unsigned stale) {
-    const bool device_side = ((stale & STALE_REPLICAS) && (c->buf.X[0] || c->b64.t10)) || ((stale & STALE_PAIR_TARGETS) && c->buf.tgs2) ||
-                             ((stale & (STALE_GRAPHS | STALE_PROGRAM)) && !c->graphs.empty());
-    if (!device_side) { drop_stale(c, stale); return C3D_OK; }
-    C3D_GATE(c);
-    drop_stale(c, stale);
-    return C3D_OK;
+// the three energies of a replica (NOE, bond + angle, repel) out of the four sums a replica's energy kernel leaves in the stage
+void copy_energies(const c3d_ctx* c, double* e) {
+    const double* h = static_cast<const double*>(c->h_stage);
+    for (int r = 0; r < c->nrep; ++r) for (int k = 0; k < 3; ++k) e[3 * r + k] = h[4 * r + k];
 }
-
-// fp64 target matrix from the resident integer tenths, in the encoding the current model's kernel expects (c3d_f64.hip pair64)
-int build_targets64(c3d_ctx* c) {
-    const c3d::Model64 m = c3d::model64(dev_model(c), c->model);
-    LAUNCH_TRY("fp64 targets", c3d::launch_targets64(m, c3d::form64(m, 0.0, 0), c->b64.t10, c->b64.T, c->stream));   // (the encoding follows pot and gen alone)
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return C3D_OK;
-}
+// the last stage's repel contact scale (0.85 without a schedule): what the embedding's lower bound and c3d_get_energies evaluate at
+float final_repel_s(const c3d_ctx* c) { return c->stages.empty() ? 0.85f : c->stages.back().repel_s; }
 
 // fp64 state <- the fp32 coordinates of the current parity (start structures, c3d_set_coords, the DG embedding); velocities zero
 int import64(c3d_ctx* c) {
@@ -139,66 +108,27 @@ int import64(c3d_ctx* c) {
 }  // namespace
 
 namespace c3d::host {
-c3d::DevModel dev_model(const c3d_ctx* c) {
-    c3d::DevModel m{};
-    const c3d_model& h = c->model;
-    m.n = c->n; m.npad = c->npad; m.ntiles = c->ntiles; m.nrep = c->nrep;
-    m.rep_base = 0; m.nrep_g = c->nrep;
-    m.rpw = c->rpw;
-    m.stage_dma = c->stage_dma;
-    m.noe_pot = h.noe_pot; m.ang_mode = h.ang_mode; m.rep_sep = h.rep_sep;
-    m.mexp = h.msoexp == 2 ? 2 : 1;
-    m.rs = h.rswitch;
-    m.tail_c = h.asym * h.rswitch;
-    m.tail_b = (m.tail_c - 2.0f * h.rswitch) * h.rswitch * h.rswitch;
-    m.mrs = h.mrswitch; m.nmrs = -h.mrswitch;
-    m.inv_rs = 1.0f / h.rswitch; m.nm_rs = -h.mrswitch / h.rswitch;
-    // the shipped lower side (square up to mrswitch, then soft with exponent 2 and no asymptote) has a fast form of its own in
-    // the clamp-form kernels: device potential 4 (pair_term); it needs the upper tail in clamp form too (slope 2 rswitch)
-    if (h.noe_pot == 3 && h.msoexp == 2 && h.masym == 0.0f && m.tail_b == 0.0f && m.tail_c == 2.0f * m.rs) {
-        m.noe_pot = 4;
-        // its pair term works on (d - t) / MRS (pair_term): the per-pair constants are t / mrs and 1 / mrs, the third run constant is
-        // the upper bound rs / mrs, and the factor applied once per row is W mrs (dev_step: clamp_scale)
-        m.inv_rs = 1.0f / h.mrswitch; m.nm_rs = h.rswitch / h.mrswitch;
+void free_replica_buffers(c3d_ctx* c) {
+    for (int k = 0; k < 2; ++k) {
+        dev_free(c->buf.X[k]); dev_free(c->buf.V[k]); dev_free(c->buf.P[k]); dev_free(c->buf.S[k]);
     }
-    // column layout of the pair loop (c3d_internal.h): lanes of the last 256-column block own wl consecutive columns, up to 8
-    // columns behind it are left over; both follow from n alone, so every launch form sums the same terms in the same order
-    {
-        const int cols_last = c->n - (c->npad - 256);
-        int wl = cols_last / 64, nleft = cols_last - 64 * wl;
-        if (wl == 0 || nleft > 8) { wl = std::min(4, wl + 1); nleft = 0; }
-        // beyond the cluster kernel's reach (npad > 1024: the per-step kernel streams the targets) one column slot in 40 is not worth
-        // the narrow block's scalar loads and the left-over pass: 28.0 against 27.0 us per step at N = 2500
-        if (!c->narrow_columns || c->npad > 1024) { wl = 4; nleft = 0; }
-        m.wl = wl; m.nleft = nleft; m.jl0 = c->npad - 256 + 64 * wl;
-    }
-    m.mtail_c = h.masym;
-    // lower side beyond mrswitch: dE/dD = mtail_c - mtail_b / D^(mexp + 1), continuous with 2 D at D = mrswitch
-    m.mtail_b = (m.mtail_c - 2.0f * h.mrswitch) * h.mrswitch * h.mrswitch * (m.mexp == 2 ? h.mrswitch : 1.0f);
-    m.k_bond2 = 2.0f * h.k_bond; m.b0 = h.b0;
-    m.k_ang2 = 2.0f * h.k_ang; m.a0 = h.a0;
-    m.acc = c3d::kAccel / h.mass;
-    const int ndf = std::max(3 * c->n - 3, 1);
-    m.t_fac = h.mass / c3d::kAccel / ((float)ndf * c3d::kBoltz);
-    m.fbeta = h.fbeta;
-    m.inv_n = 1.0f / (float)c->n;
-    return m;
+    dev_free(c->d_crec);
+    c->crec_bytes = 0; c->cl_ok = false;
+    dev_free(c->buf.Vinit); dev_free(c->buf.E); dev_free(c->d_feval);
+    dev_free(c->d_sym_scratch); dev_free(c->d_sym_tiles);
+    dev_free(c->lb.hist); dev_free(c->lb.part); dev_free(c->lb.S[0]); dev_free(c->lb.S[1]);
+    dev_free(c->lb64.hist); dev_free(c->lb64.part); dev_free(c->lb64.S[0]); dev_free(c->lb64.S[1]);
+    c->lbfgs_parity = -1;
+    dev_free(c->b64.T); dev_free(c->b64.t10); dev_free(c->b64.Vinit); dev_free(c->b64.F);
+    for (int k = 0; k < 2; ++k) { dev_free(c->b64.X[k]); dev_free(c->b64.V[k]); dev_free(c->b64.P[k]); dev_free(c->b64.S[k]); }
+    c->have_replicas = false;
 }
-c3d::DevStep dev_step(const c3d_ctx* c, int kind, float dt, float w_all, float w_vdw, float repel_s, float t_bath) {
-    c3d::DevStep p;
-    p.kind = kind; p.dt = dt; p.w_all = w_all;
-    p.w_noe2n = -2.0f * w_all * c->model.s_noe;
-    p.w_rep4 = 4.0f * w_vdw * c->model.k_rep;
-    const float rr = repel_s * c->model.r0_rep;
-    p.rep_r2 = rr * rr;
-    p.inv_rep_r2 = rr > 0.0f ? 1.0f / p.rep_r2 : 0.0f;
-    p.w_rep4r2 = p.w_rep4 * p.rep_r2;
-    // clamp form (c3d_step_core.h pair_term): the NOE weight times rswitch is applied once per row, the repel weight rides
-    // relative to it.  A stage without restraint weight (w_all = 0) cannot be written that way: general kernels (zero_weight).
-    p.w_rs = p.w_noe2n * clamp_scale(c);
-    p.kq = p.w_rs != 0.0f ? p.w_rep4r2 / p.w_rs : 0.0f;
-    p.t_bath = t_bath;
-    return p;
+// fp64 target matrix from the resident integer tenths, in the encoding the current model's kernel expects (c3d_f64.hip pair64)
+int build_targets64(c3d_ctx* c) {
+    const c3d::Model64 m = c3d::model64(dev_model(c), c->model);
+    LAUNCH_TRY("fp64 targets", c3d::launch_targets64(m, c3d::form64(m, 0.0, 0), c->b64.t10, c->b64.T, c->stream));   // (the encoding follows pot and gen alone)
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return C3D_OK;
 }
 
 // Read-backs (exit test of the minimiser, coordinates, energies, scoring sums) land in a pinned buffer the context owns: the runtime does not
@@ -225,63 +155,6 @@ extern "C" int c3d_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
     return n;
-}
-
-extern "C" void c3d_default_model(c3d_model* m) {
-    if (!m) return;
-    // Round 3: every number below comes from the reference's 45 bundled models, in two independent steps:
-    // (1) inverse force matching (tools/calib/force_match.py, profiles/r03_force_matching.txt): which restraint potential
-    //     leaves every bead of a bundled model force-free.  Answer, the same at 1 Mb and at 500 kb: the soft-square switches
-    //     to its linear tail 0.5 A above the target with slope 2 S 0.5 = 10 (CNS terms: rswitch 0.5, asymptote 1.0 — half of
-    //     round 2's 1.0 / 2.0), the lower side is square for a few Angstrom and saturates, pseudo-bonds ~300-400 kcal/mol/A^2
-    //     around 3.95 A, (i,i+2) ~45 around 6 A, repel contact ~4.6 A with k ~2-4;
-    // (2) refit on the 23 one-megabase matrices against the structure-level metrics of the parity table (Rg ratio,
-    //     distance-matrix similarity, bond and (i,i+2) statistics, Spearman), the 22 matrices at 500 kb held out
-    //     (tools/calib/fit_structure.py, profiles/r03_structure_fit.txt): a plateau around the values below.
-    m->min_sep = 5; m->noe_pot = 3; m->rep_sep = 2; m->ang_mode = 1;
-    m->s_noe = 10.0f; m->rswitch = 0.5f; m->asym = 2.0f;   // tail slope = asym x rswitch x S = 10
-    m->k_bond = 500.0f; m->b0 = 3.93f;
-    m->k_ang = 15.0f; m->a0 = 5.55f;
-    m->r0_rep = 5.25f; m->k_rep = 4.0f;
-    m->mass = 100.0f; m->fbeta = 10.0f;
-    // lower side of the NOE term (round 4): square up to mrswitch inside the target, then the soft form with exponent 2 and no
-    // asymptote — the push on a pair far inside its target DECAYS as D^-3 beyond 10 A.  These are X-PLOR's own defaults for the soft
-    // potential (rswitch 10, asymptote 0, soexponent 2), which CNS keeps for the minus side because the deck's modules only set the
-    // plus side [CNS-UNVERIFIED]; the relaxation fit finds mrswitch = 9.9-10.0 on its own (profiles/r04_relax_fit.txt)
-    m->mrswitch = 10.0f; m->masym = 0.0f; m->msoexp = 2;
-}
-extern "C" void c3d_default_fire(c3d_fire_params* f) {
-    if (!f) return;
-    f->dt_start = 0.002f; f->dt_max = 0.02f; f->f_inc = 1.1f; f->f_dec = 0.5f;
-    f->alpha_start = 0.1f; f->f_alpha = 0.99f; f->max_step = 0.5f; f->n_min = 5;
-}
-extern "C" int c3d_default_schedule(c3d_stage* st, int cap, int min_steps) {
-    std::vector<c3d_stage> v;
-    // regularisation (deck :1631-1645: 100 + 100 minimiser steps, weights * 1, vdw 20, repel 0.5)
-    v.push_back({2, 200, 0.0f, 1.0f, 20.0f, 0.5f, 0.0f});
-    // hot stages (deck :1649-1700): 1000 steps at 2000 K, dt 0.003
-    const float hot_t = 2000.0f, hot_dt = 0.003f;
-    const int hot_n[5] = {125, 125, 125, 500, 125};
-    const float hot_w[5] = {0.1f, 0.2f, 0.2f, 0.4f, 1.0f};
-    const float hot_v[5] = {20.0f, 20.0f, 0.01f, 0.003f, 0.003f};
-    const float hot_r[5] = {0.5f, 0.5f, 0.9f, 0.9f, 0.9f};
-    for (int k = 0; k < 5; ++k) v.push_back({0, hot_n[k], hot_dt, hot_w[k], hot_v[k], hot_r[k], hot_t});
-    // slow cool (deck :1740-1782): ncycle = 80, 81 passes of int(1000/80) = 12 steps, dt 0.005
-    const int ncycle = (int)(hot_t / 25.0f);
-    const int nstep = 1000 / ncycle;
-    const double vdw_step = pow(4.0 / 0.003, 1.0 / ncycle);
-    const double rad_step = (1.0 - 0.85) / ncycle;
-    double radius = 1.0, kv = 0.003, bath = hot_t;
-    for (int i = 0; i <= ncycle; ++i) {
-        v.push_back({1, nstep, 0.005f, 1.0f, (float)kv, (float)radius, (float)bath});
-        radius = std::max(0.85, radius - rad_step);
-        kv = std::min(4.0, kv * vdw_step);
-        bath -= 25.0;
-    }
-    // final minimisation (deck :1790-1803): weights * 1; kind 5 = two-point step-size minimiser, FIRE after final_minimiser_steps (round 5)
-    v.push_back({5, min_steps, 0.0f, 1.0f, 1.0f, 0.85f, 0.0f});
-    if (st) for (int k = 0; k < (int)v.size() && k < cap; ++k) st[k] = v[k];
-    return (int)v.size();
 }
 
 extern "C" int c3d_create(int device, c3d_ctx** out) {
@@ -340,157 +213,6 @@ extern "C" void c3d_destroy(c3d_ctx* c) {
         release_context(c);
     }
     delete c;
-}
-
-extern "C" int c3d_set_model(c3d_ctx* c, const c3d_model* m) {
-    if (!c || !m) return fail(C3D_ERR_INVALID, "c3d_set_model: null argument");
-    // msoexp (the struct's last member, added in round 4) = 0 means "the default, 2": a caller that zero-initialises the struct and
-    // fills in what it knows keeps working ("ABI notes")
-    const int msoexp = m->msoexp == 0 ? 2 : m->msoexp;
-    if (m->mass <= 0 || m->rswitch <= 0 || m->min_sep < 1 || m->rep_sep < 1 || m->rep_sep > 3 || m->noe_pot < 0 || m->noe_pot > 3 || m->mrswitch <= 0 || (msoexp != 1 && msoexp != 2))
-        return fail(C3D_ERR_INVALID, "c3d_set_model: parameter out of range");
-    if (c->have_targets && m->min_sep != c->model.min_sep)
-        return fail(C3D_ERR_INVALID, "c3d_set_model: min_sep must be set before the targets are built");
-    // the fp64 target matrix encodes "no restraint" per potential: rebuilt by a launch (fp64 contexts load no potential-specific unit)
-    const bool targets64 = c->precision == 64 && c->b64.T;
-    Entry entry(c, 0u, targets64);
-    if (entry.rc != C3D_OK) return entry.rc;
-    c->model = *m;
-    c->model.msoexp = msoexp;
-    drop_stale(c, STALE_PAIR_TARGETS | STALE_PROGRAM);   // the pre-scaled pair targets of the per-step kernel carry 1 / mrs: rebuilt on demand
-    if (c->have_replicas)                  // the multi-step kernel's plan depends on the potential
-        if (int rc = plan_cluster(c)) return rc;
-    return targets64 ? build_targets64(c) : C3D_OK;
-}
-
-extern "C" int c3d_set_schedule(c3d_ctx* c, const c3d_stage* st, int n_stages, const c3d_fire_params* fire, float gtol,
-                                int check_every) {
-    if (!c || !st || n_stages < 1) return fail(C3D_ERR_INVALID, "c3d_set_schedule: bad arguments");
-    for (int k = 0; k < n_stages; ++k) {
-        if (st[k].kind < 0 || (st[k].kind > 2 && st[k].kind != 5 && st[k].kind != 8) || st[k].nsteps < 0) return fail(C3D_ERR_INVALID, "c3d_set_schedule: bad stage");
-        if (st[k].kind == 8 && c->precision == 64 && !c->f64_lbfgs)
-            return fail(C3D_ERR_INVALID, "c3d_set_schedule: a stage of kind 8 (L-BFGS) has no fp64 form; set precision 32 first");
-    }
-    c->stages.assign(st, st + n_stages);
-    if (fire) c->fire = *fire;
-    c->gtol = gtol;
-    if (check_every > 0) c->check_every = check_every;
-    return drop_stale_gated(c, STALE_PROGRAM);
-}
-
-extern "C" int c3d_set_option(c3d_ctx* c, const char* key, double value) {
-    if (!c || !key) return fail(C3D_ERR_INVALID, "c3d_set_option: null argument");
-    unsigned stale = 0;                    // what the new value invalidates: dropped below, in one place
-    if (!strcmp(key, "use_graph")) c->use_graph = value != 0;
-    else if (!strcmp(key, "rows_per_wave")) {
-        if (value != 1 && value != 2 && value != 4) return fail(C3D_ERR_INVALID, "rows_per_wave must be 1, 2 or 4");
-        c->rpw = (int)value;
-        stale = STALE_GRAPHS;
-    } else if (!strcmp(key, "replica_groups")) {   // groups stepped concurrently on separate streams
-        if (value < 1 || value > c3d_ctx::kMaxGroups) return fail(C3D_ERR_INVALID, "replica_groups must be 1..4");
-        c->ngroups = (int)value;
-        stale = STALE_GRAPHS;
-    } else if (!strcmp(key, "event_timing")) c->event_timing = value != 0;
-    else if (!strcmp(key, "kernel_timing")) c->kernel_timing = value != 0;
-    else if (!strcmp(key, "resident")) { c->resident = value < 0 ? -1 : (value != 0); c->resident_skip = 0; }
-    else if (!strcmp(key, "precision")) {  // 32 (the product kernels) or 64 (the fp64 reference step); call before c3d_init_replicas
-        if (value != 32 && value != 64) return fail(C3D_ERR_INVALID, "precision must be 32 or 64");
-        if (value == 64 && !c->f64_lbfgs)
-            for (const c3d_stage& st : c->stages)
-                if (st.kind == 8) return fail(C3D_ERR_INVALID, "precision 64: the schedule holds a stage of kind 8 (L-BFGS), which has no fp64 form");
-        c->precision = (int)value;
-        stale = STALE_REPLICAS | STALE_GRAPHS;
-    } else if (!strcmp(key, "eval_rows_per_wave")) {
-        if (value != 2 && value != 4 && value != -2) return fail(C3D_ERR_INVALID, "eval_rows_per_wave must be 4, 2 (packed pair term) or -2 (two rows per wave, scalar pair term)");
-        c->eval_rpw = (int)value;
-    } else if (!strcmp(key, "pair_targets")) { c->pair_targets = value != 0; stale = STALE_PAIR_TARGETS | STALE_GRAPHS; }
-    else if (!strcmp(key, "wide_tiles")) { c->wide_tiles = value != 0; stale = STALE_GRAPHS; }
-    else if (!strcmp(key, "symmetric")) { c->sym = value > 0; stale = STALE_REPLICAS | STALE_GRAPHS; }   // takes effect at the next c3d_init_replicas with a new replica count / matrix
-    else if (!strcmp(key, "start")) {      // A5: 0 = Philox random coil, 1 = extended strand as extn.inp lays it out (:2413-2416)
-        if (value != 0 && value != 1) return fail(C3D_ERR_INVALID, "start must be 0 (random coil) or 1 (extended strand)");
-        c->start_mode = (int)value;
-    } else if (!strcmp(key, "cluster")) c->cluster = value < 0 ? -1 : (value != 0);
-    else if (!strcmp(key, "resident_inject_timeout")) c->inject_timeout = value != 0;   // test hook
-    else if (!strcmp(key, "narrow_columns")) { c->narrow_columns = value != 0; stale = STALE_REPLICAS | STALE_GRAPHS; }
-    else if (!strcmp(key, "cluster_static_placement")) { c->static_place = value != 0; c->inject_misplaced = value == 2; }   // 0: per-XCD atomic slot counters; 2: test hook
-    else if (!strcmp(key, "cluster_inject_incomplete")) c->inject_incomplete = value != 0;   // test hook
-    else if (!strcmp(key, "cluster_num_xcc")) { c->num_xcc = (int)value; stale = STALE_REPLICAS; }   // test hook: pretend a partitioned device
-    else if (!strcmp(key, "prefetch_ranks")) c->prefetch_ranks = value != 0;
-    else if (!strcmp(key, "device_ranks")) {       // who ranks the IF matrix for c3d_score_replicas
-        if (value != -1 && value != 0 && value != 1)
-            return fail(C3D_ERR_INVALID, "device_ranks is 0 (the device beyond 5120 beads), 1 (the device for every symmetric matrix) or -1 (the host)");
-        c->device_ranks = (int)value;
-    }
-    else if (!strcmp(key, "final_minimiser_steps")) {
-        if (value < 2) return fail(C3D_ERR_INVALID, "c3d_set_option: final_minimiser_steps >= 2");
-        c->bb_steps = (int)value;
-        stale = STALE_PROGRAM;
-    } else if (!strcmp(key, "final_minimiser")) {  // what a stage of kind 5 runs: 1 (default) two-point step size then FIRE, 0 FIRE throughout
-        if (value != 0 && value != 1) return fail(C3D_ERR_INVALID, "c3d_set_option: final_minimiser is 0 (FIRE) or 1 (two-point step size)");
-        c->final_bb = value != 0;
-        stale = STALE_PROGRAM;
-    } else if (!strcmp(key, "lbfgs_memory")) {     // pairs a kind-8 stage keeps; takes effect at the next stage's first step
-        if (value != (int)value || value < 1 || value > c3d::kLbfgsMaxPairs) return fail(C3D_ERR_INVALID, "c3d_set_option: lbfgs_memory is 1..8");
-        c->lbfgs_mem = (int)value;
-        stale = STALE_GRAPHS;
-    } else if (!strcmp(key, "cluster_xcd_count")) {   // 1..8 XCDs for this context's multi-step launches; re-plans: before c3d_init_replicas
-        const int v = (int)value;
-        if (v < 1 || v > 8 || c->xcd_base + v > 8) return fail(C3D_ERR_INVALID, "cluster_xcd_count: 1..8, and cluster_xcd_base + cluster_xcd_count <= 8");
-        c->xcd_count = v;
-        stale = STALE_REPLICAS;
-    } else if (!strcmp(key, "cluster_xcd_base")) {    // first XCD of the set; may change between launches (the plan depends on the count only)
-        const int v = (int)value;
-        if (v < 0 || v + c->xcd_count > 8) return fail(C3D_ERR_INVALID, "cluster_xcd_base: 0 .. 8 - cluster_xcd_count");
-        c->xcd_base = v;
-    } else if (!strcmp(key, "cluster_late_tiles")) { c->cluster_late = value != 0 ? -1 : 0; stale = STALE_REPLICAS; }   // measurement knob: 0 = never; before c3d_init_replicas
-    else if (!strcmp(key, "cluster_geometry")) {   // measurement knob: 100 CW + 10 RPW + helpers (0 = planner); before c3d_init_replicas
-        if (value < 0 || value > 1699) return fail(C3D_ERR_INVALID, "cluster_geometry = 100 compute waves + 10 rows per wave + helper waves");
-        c->cluster_geom = (int)value;
-        stale = STALE_REPLICAS;
-    } else if (!strcmp(key, "spin_wait_us")) c->spin_wait_us = value < 0 ? 0 : value;
-    else if (!strcmp(key, "resident_min_ops")) c->resident_min_ops = value < 1 ? 1 : (int)value;
-    else if (!strcmp(key, "stage_dma")) { c->stage_dma = value != 0; stale = STALE_GRAPHS; }
-    else if (!strcmp(key, "max_beads")) {          // the caller's consent to the memory of a large matrix (c3d.h); before c3d_set_if_matrix
-        if (value != (int)value || value < C3D_MAX_BEADS_DEFAULT || value > C3D_MAX_BEADS_LIMIT)
-            return fail(C3D_ERR_INVALID, "max_beads must be an integer from 5120 to 16384");
-        c->max_beads = (int)value;
-    } else if (!strcmp(key, "embed_max_beads")) {  // the caller's consent to the memory of a large embedding (c3d.h)
-        if (value != (int)value || value < C3D_EMBED_MAX_BEADS_DEFAULT || value > C3D_EMBED_MAX_BEADS_LIMIT)
-            return fail(C3D_ERR_INVALID, "embed_max_beads must be an integer from 4549 to 16384");
-        c->embed_max_beads = (int)value;
-    } else if (!strcmp(key, "f64_max_beads")) {    // the caller's consent to the fp64 target matrix, 8 n np bytes (c3d.h); before c3d_init_replicas
-        if (value != (int)value || value < C3D_F64_MAX_BEADS_DEFAULT || value > C3D_F64_MAX_BEADS_LIMIT)
-            return fail(C3D_ERR_INVALID, "f64_max_beads must be an integer from 2560 to 16384");
-        c->f64_max_beads = (int)value;
-    } else if (!strcmp(key, "f64_lbfgs")) {        // the caller's consent to kind-8 stages in fp64 (c3d.h); releases nothing on the device
-        if (value != 0 && value != 1) return fail(C3D_ERR_INVALID, "f64_lbfgs must be 0 or 1");
-        if (value == 0 && c->precision == 64)
-            for (const c3d_stage& st : c->stages)
-                if (st.kind == 8) return fail(C3D_ERR_INVALID, "f64_lbfgs: precision is 64 and the schedule holds a stage of kind 8 (L-BFGS); change one of them first");
-        c->f64_lbfgs = value != 0;
-    } else if (!strcmp(key, "f64_column_chunk")) { // test and measurement knob: the fp64 step kernel's column source (same bits either way)
-        if (value != (int)value || (value != 0 && !c3d::column_chunk64_valid((int)value)))
-            return fail(C3D_ERR_INVALID, "f64_column_chunk must be 0 (by size), 256, 512 or 1024");
-        c->f64_column_chunk = (int)value;
-        stale = STALE_GRAPHS;
-    } else if (!strcmp(key, "embed_form")) {       // test and measurement knob: the eigen stage's form (same bits either way)
-        if (value != 0 && value != 1) return fail(C3D_ERR_INVALID, "embed_form is 0 (k_dg_eig while it fits, tiled beyond) or 1 (tiled)");
-        c->embed_form = (int)value;
-    } else if (!strcmp(key, "embed_batch")) {      // test knob: replicas embedded at a time (same bits whatever it is)
-        if (value != (int)value || value < 0) return fail(C3D_ERR_INVALID, "embed_batch is 0 (by the scratch budget) or a number of replicas");
-        c->embed_batch = (int)value;
-    } else if (!strcmp(key, "column_chunk")) {     // test and measurement knob: the per-step kernels' column source (same bits either way)
-        if (value != (int)value || (value != 0 && !c3d::column_chunk_valid((int)value)))
-            return fail(C3D_ERR_INVALID, "column_chunk must be 0 (the library's choice), 256, 1024 or 2048");
-        c->column_chunk = (int)value;
-        stale = STALE_GRAPHS;
-    }
-    else if (!strcmp(key, "graph_chunk")) {
-        if (value < 8) return fail(C3D_ERR_INVALID, "graph_chunk must be >= 8");
-        c->graph_chunk = (int)value & ~1;   // even: a chunk returns to the starting parity
-        stale = STALE_GRAPHS;
-    } else return fail(C3D_ERR_INVALID, std::string("unknown option ") + key);
-    return drop_stale_gated(c, stale);
 }
 
 // The largest matrix a context accepts: kDefaultMaxBeads unless the option max_beads raises it, up to kMaxBeadsLimit.  Up to
@@ -727,10 +449,8 @@ extern "C" int c3d_init_replicas(c3d_ctx* c, int nrep, uint64_t seed, uint32_t f
                 // extended strand: the reference's template runs along x with small random y, z (`do (x=x/5.)`,
                 // `do (y=random(0.5))`, `do (z=random(0.5))`, :2413-2416) and is regularised to chain geometry; for
                 // beads: b0 apart along x, y and z uniform in [0, 0.5), keyed by (seed, replica, bead)
-                const uint32_t ctr[4] = {(uint32_t)i, 2u, 0u, 0u};
-                const uint32_t key[2] = {(uint32_t)(seed & 0xFFFFFFFFu) ^ (rid * 0x9E3779B9u), (uint32_t)(seed >> 32) + rid};
                 uint32_t u[4];
-                philox4x32(ctr, key, u);
+                philox_draw(seed, rid, (uint32_t)i, 2u, u);
                 xd[3 * i] = (double)c->model.b0 * i; xd[3 * i + 1] = 0.5 * u01(u[0]); xd[3 * i + 2] = 0.5 * u01(u[1]);
                 continue;
             }
@@ -821,11 +541,7 @@ extern "C" int c3d_init_replicas(c3d_ctx* c, int nrep, uint64_t seed, uint32_t f
 }
 
 // A7: the lower bound of pairs without a restraint, the last stage's repel contact distance (formed in float)
-static float dg_lower(const c3d_ctx* c) {
-    float repel_s = 0.85f;
-    if (!c->stages.empty()) repel_s = c->stages.back().repel_s;
-    return repel_s * c->model.r0_rep;
-}
+static float dg_lower(const c3d_ctx* c) { return final_repel_s(c) * c->model.r0_rep; }
 
 // A7: replace the replicas' starting coordinates by a metric-matrix distance-geometry embedding
 // (deck :1471-1525 restated for beads; one embed per model, trial distances keyed by replica id)
@@ -971,7 +687,7 @@ extern "C" int c3d_set_coords_f64(c3d_ctx* c, const double* xyz) {
         for (int comp = 0; comp < 3; ++comp) {
             double* dst = h + ((size_t)r * 3 + comp) * np;
             for (int i = 0; i < n; ++i) dst[i] = xyz[((size_t)r * n + i) * 3 + comp];
-            for (int i = n; i < np; ++i) dst[i] = (double)c3d::kPadCoord * (comp + 1) + 16.0 * (i - n);
+            for (int i = n; i < np; ++i) dst[i] = pad_coord(comp, i - n);
         }
     for (int k = 0; k < 2; ++k) {
         HIP_TRY(hipMemcpyAsync(c->b64.X[k], h, sizeof(double) * n3, hipMemcpyHostToDevice, c->stream));
@@ -979,84 +695,6 @@ extern "C" int c3d_set_coords_f64(c3d_ctx* c, const double* xyz) {
     }
     LAUNCH_TRY("fp64 export", c3d::launch_export64(dev_model(c), c->b64, c->parity, c->buf.X[c->parity], c->buf.V[c->parity], c->buf.P[c->parity], c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    return C3D_OK;
-}
-
-extern "C" int c3d_get_stat(const c3d_ctx* c, const char* key, double* value) {
-    if (!c || !key || !value) return fail(C3D_ERR_INVALID, "c3d_get_stat: null argument");
-    if (!strcmp(key, "graph_captures")) *value = (double)c->graph_captures;
-    else if (!strcmp(key, "last_kernel_us")) *value = 1e3 * c->last_kernel_ms;
-    else if (!strcmp(key, "last_host_launch_us")) *value = c->last_host_launch_us;
-    else if (!strcmp(key, "last_host_sync_us")) *value = c->last_host_sync_us;
-    else if (!strcmp(key, "graph_launches")) *value = (double)c->graph_launches;
-    else if (!strcmp(key, "graphs_cached")) *value = (double)c->graphs.size();
-    else if (!strcmp(key, "step_launches")) *value = (double)c->step_launches;
-    else if (!strcmp(key, "resident_launches")) *value = (double)c->resident_launches;
-    else if (!strcmp(key, "cluster_launches")) *value = (double)c->cluster_launches;
-    else if (!strcmp(key, "resident_fallbacks")) *value = (double)c->resident_fallbacks;
-    else if (!strcmp(key, "cluster_incomplete")) *value = (double)c->cluster_incomplete;
-    else if (!strcmp(key, "spin_completions")) *value = (double)c->spin_completions;
-    else if (!strcmp(key, "cluster_static_placement")) *value = c->static_place ? 1.0 : 0.0;
-    else if (!strcmp(key, "cluster_placement_mismatches")) *value = (double)c->placement_mismatches;
-    else if (!strcmp(key, "num_xcc")) *value = (double)c->num_xcc;
-    else if (!strcmp(key, "rms_force")) {
-        // max over the replicas of the RMS force component at the last minimiser evaluation (what c3d_run compares with
-        // gtol); meaningful after a FIRE step only
-        double rms = 0;
-        if (!c->have_replicas) return fail(C3D_ERR_INVALID, "c3d_get_stat: rms_force needs replicas");
-        C3D_ENTRY(c, 0u);
-        if (int rc = max_rms_force(const_cast<c3d_ctx*>(c), &rms)) return rc;
-        *value = rms;
-    }
-    else if (!strcmp(key, "lbfgs_steps")) *value = (double)c->lbfgs_steps;
-    else if (!strcmp(key, "lbfgs_resets")) {
-        // memory drops of the last L-BFGS stage, summed over the replicas (device state of the parity its last step wrote)
-        *value = 0;
-        const c3d::LbfgsState* dev = c->lbfgs_parity < 0 ? nullptr : c->precision == 64 ? c->lb64.S[c->lbfgs_parity] : c->lb.S[c->lbfgs_parity];
-        if (dev) {
-            C3D_ENTRY(c, 0u);
-            if (int rc = read_back(const_cast<c3d_ctx*>(c), dev, sizeof(c3d::LbfgsState) * c->nrep)) return rc;
-            const c3d::LbfgsState* h = static_cast<const c3d::LbfgsState*>(c->h_stage);
-            long r = 0;
-            for (int k = 0; k < c->nrep; ++k) r += h[k].resets;
-            *value = (double)r;
-        }
-    }
-    else if (!strcmp(key, "k1_recomputed")) *value = (double)c->k1_recomputed;
-    else if (!strcmp(key, "k1_patched")) *value = (double)c->k1_patched;
-    else if (!strcmp(key, "last_path")) *value = (double)c->last_path;
-    else if (!strcmp(key, "rank_prefetch_hits")) *value = (double)c->rank_prefetch_hits;
-    else if (!strcmp(key, "device_rank_runs")) *value = (double)c->device_rank_runs;
-    else if (!strcmp(key, "score_wide_runs")) *value = (double)c->score_wide_runs;
-    else if (!strcmp(key, "compare_runs")) *value = (double)c->compare_runs;
-    else if (!strcmp(key, "f64_evals")) *value = (double)c->f64_evals;
-    else if (!strcmp(key, "superpose_runs")) *value = (double)c->superpose_runs;
-    else if (!strcmp(key, "rmsd_table_runs")) *value = (double)c->rmsd_table_runs;
-    else if (!strcmp(key, "ensemble_map_runs")) *value = (double)c->ensemble_map_runs;
-    else if (!strcmp(key, "ensemble_score_runs")) *value = (double)c->ensemble_score_runs;
-    else if (!strcmp(key, "geometry_runs")) *value = (double)c->geometry_runs;
-    else if (!strcmp(key, "separation_runs")) *value = (double)c->separation_runs;
-    else if (!strcmp(key, "stratified_runs")) *value = (double)c->stratified_runs;
-    else if (!strcmp(key, "stratified_if_ms")) *value = c->stratified_if_ms;
-    else if (!strcmp(key, "stratified_models_ms")) *value = c->stratified_models_ms;
-    else if (!strcmp(key, "bead_runs")) *value = (double)c->bead_runs;
-    else if (!strcmp(key, "bead_if_ms")) *value = c->bead_if_ms;
-    else if (!strcmp(key, "bead_models_ms")) *value = c->bead_models_ms;
-    else if (!strcmp(key, "cluster_xcd_count")) *value = (double)c->xcd_count;
-    else if (!strcmp(key, "cluster_xcd_base")) *value = (double)c->xcd_base;
-    else if (!strcmp(key, "cluster_ok")) *value = c->cl_ok ? 1.0 : 0.0;
-    else if (!strcmp(key, "cluster_parts")) *value = c->cl_ok ? (double)c->cl_plan.parts : 0.0;
-    else if (!strcmp(key, "cluster_rows_per_wave")) *value = c->cl_ok ? (double)c->cl_plan.rpw : 0.0;
-    else if (!strcmp(key, "cluster_late_tiles")) *value = c->cl_ok ? (double)c->cl_plan.late_tiles : 0.0;
-    else if (!strcmp(key, "cluster_compute_waves")) *value = c->cl_ok ? (double)c->cl_plan.cw : 0.0;
-    else if (!strcmp(key, "cluster_helper_waves")) *value = c->cl_ok ? (double)c->cl_plan.helpers : 0.0;
-    else if (!strcmp(key, "cluster_wgs_per_cu")) *value = c->cl_ok ? (double)c->cl_plan.wgs_per_cu : 0.0;
-    else if (!strcmp(key, "replica_groups")) *value = (double)active_groups(c);
-    else if (!strcmp(key, "embed_form")) *value = (double)c->last_embed_form;
-    else if (!strcmp(key, "embed_batches")) *value = (double)c->last_embed_batches;
-    else if (!strcmp(key, "units_loaded")) *value = (double)units_loaded();                        // code objects this PROCESS has loaded (all devices)
-    else if (!strcmp(key, "units_loaded_mask")) *value = (double)units_loaded_mask(c->device);     // bit per unit, this context's device
-    else return fail(C3D_ERR_INVALID, std::string("c3d_get_stat: unknown key ") + key);
     return C3D_OK;
 }
 
@@ -1074,8 +712,7 @@ extern "C" int c3d_eval(c3d_ctx* c, float w_all, float w_vdw, float repel_s, flo
         const double rr = (double)repel_s * (double)c->model.r0_rep;
         LAUNCH_TRY("energy launch", c3d::launch_energy(m, p, c->buf, c->parity, c->model.s_noe, c->model.k_rep, rr * rr, c->stream));
         if (int rc = read_back(c, c->buf.E, sizeof(double) * 4 * (size_t)c->nrep)) return rc;
-        const double* h = static_cast<const double*>(c->h_stage);
-        for (int r = 0; r < c->nrep; ++r) for (int k = 0; k < 3; ++k) e[3 * r + k] = h[4 * r + k];
+        copy_energies(c, e);
     }
     return C3D_OK;
 }
@@ -1098,8 +735,7 @@ extern "C" int c3d_eval_f64(c3d_ctx* c, double w_all, double w_vdw, double repel
         const double rr = repel_s * (double)c->model.r0_rep;
         LAUNCH_TRY("fp64 energy launch", c3d::launch_energy64(m, m64, rr * rr, c->b64, c->parity, c->b64.F + n3, c->stream));
         if (int rc = read_back(c, c->b64.F + n3, sizeof(double) * 4 * (size_t)c->nrep)) return rc;
-        const double* h = static_cast<const double*>(c->h_stage);
-        for (int r = 0; r < c->nrep; ++r) for (int k = 0; k < 3; ++k) e[3 * r + k] = h[4 * r + k];
+        copy_energies(c, e);
     }
     ++c->f64_evals;
     return C3D_OK;
@@ -1107,9 +743,7 @@ extern "C" int c3d_eval_f64(c3d_ctx* c, double w_all, double w_vdw, double repel
 
 extern "C" int c3d_get_energies(c3d_ctx* c, double* e) {
     if (!c || !e) return fail(C3D_ERR_INVALID, "c3d_get_energies: null argument");
-    float repel_s = 0.85f;
-    if (!c->stages.empty()) repel_s = c->stages.back().repel_s;
-    return c3d_eval(c, 1.0f, 1.0f, repel_s, nullptr, e);
+    return c3d_eval(c, 1.0f, 1.0f, final_repel_s(c), nullptr, e);
 }
 
 extern "C" int c3d_rank(c3d_ctx* c, int32_t* rank) {

@@ -128,6 +128,8 @@ int c3d_set_schedule(c3d_ctx* ctx, const c3d_stage* stages, int n_stages, const 
  * of the knobs below except `precision`, `symmetric` and `start` end in the same bits.
  *   resident        -1 (default) / 0 / 1: run step ranges as ONE multi-step launch of the cluster kernel (c3d_cluster.hip)
  *                   wherever a geometry exists / never / as -1, without the back-off after an abandoned launch
+ *   resident_min_ops  4 (default): a range of fewer program steps than this runs step by step, not as a multi-step launch (values
+ *                   below 1 count as 1; a fraction is dropped); measurement knob
  *   cluster         0: never use the cluster kernel (test knob)
  *   cluster_geometry  100 x compute waves + 10 x rows per wave + helper waves (e.g. 1244): force that geometry of the cluster
  *                   kernel instead of the planner's choice (measurement knob; 0 = planner); before c3d_init_replicas
@@ -313,7 +315,9 @@ int c3d_last_timing(const c3d_ctx* ctx, double* ms_total, long* steps, long* lau
  * "cluster_launches", "resident_fallbacks" (multi-step launches abandoned for the per-step path), "cluster_incomplete"
  * (those of them that ended without every (replica, part) workgroup reporting), "cluster_static_placement",
  * "cluster_placement_mismatches", "cluster_xcd_count", "cluster_xcd_base", "cluster_ok" (1: a multi-step geometry exists for the replicas as initialised), "spin_completions" (multi-step launches whose end was seen on the completion mark), "num_xcc", "last_path"
- * (0 per-step, 2 k_cluster), "cluster_parts", "cluster_rows_per_wave", "cluster_late_tiles", "last_host_launch_us", "last_host_sync_us" (host time inside the launch / synchronise call of the last c3d_run_steps, cluster launches), "cluster_compute_waves", "replica_groups",
+ * (0 per-step, 2 k_cluster), "cluster_parts", "cluster_rows_per_wave", "cluster_late_tiles", "last_host_launch_us", "last_host_sync_us" (host time inside the launch / synchronise call of the last c3d_run_steps, cluster launches), "cluster_compute_waves",
+ * "cluster_helper_waves", "cluster_wgs_per_cu" (the other two numbers of the multi-step geometry in force, 0 without one), "replica_groups",
+ * "units_loaded" (code objects this process has loaded, all devices), "units_loaded_mask" (bit per unit, this context's device),
  * "k1_recomputed" (elements of the last c3d_set_if_matrix that sat within 1e-10 of a "%.1f" rounding tie and were redone
  * on the host in the reference's operation order), "k1_patched" (how many of those changed, since c3d_create),
  * "rms_force" (largest RMS force component over the replicas at the last minimiser step: the quantity c3d_run holds

@@ -1,5 +1,5 @@
 """Which forms of the multi-step cluster kernel can be launched, and at which bead count: a plain-Python restatement of the ACCEPTANCE
-rules of cluster_plan (c3d_cluster.hip) and of the column layout of dev_model (c3d_api.cpp), for an unpartitioned MI355X (256 CUs, 8 XCDs,
+rules of cluster_plan (c3d_cluster.hip) and of the column layout of dev_model (c3d_config.cpp), for an unpartitioned MI355X (256 CUs, 8 XCDs,
 every XCD in the launch's set).  The table is built from the acceptance rules alone: every case forces its geometry with the option
 cluster_geometry, so what the planner would have preferred does not matter.  The cost model is restated beside it (planner_choice), only
 to say which keys a problem reaches without the option.

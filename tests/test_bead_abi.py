@@ -60,9 +60,9 @@ def test_without_a_context_it_refuses_and_names_itself(built):
     assert b"c3d_bead_scores" in L.c3d_last_error() and (out == 7.0).all()
     v = C.c_double()
     assert L.c3d_get_stat(None, b"bead_runs", C.byref(v)) == C3D_ERR_INVALID
-    src = open(os.path.join(ROOT, "chromosome3d_amd", "csrc", "c3d_api.cpp")).read()
+    from tests.util import stub_context_knows_stat
     for key in ("bead_runs", "bead_if_ms", "bead_models_ms"):
-        assert '!strcmp(key, "%s")' % key in src                                 # and c3d_get_stat knows the keys
+        assert stub_context_knows_stat(key)                                      # and c3d_get_stat knows the keys
     assert "bead_runs" in open(os.path.join(ROOT, "chromosome3d_amd", "csrc", "c3d_ctx.h")).read()
 
 

@@ -1,7 +1,11 @@
 """Shared helpers of the test-suite (fixtures live in tests/golden)."""
+import functools
 import glob
 import json
 import os
+import shutil
+import subprocess
+import tempfile
 
 import numpy as np
 
@@ -238,3 +242,71 @@ def relax_reference_model(solver, ref_xyz, e_noe_ours, min_steps=3000, gtol=1e-2
     ours = np.asarray(e_noe_ours).astype(np.int64)
     return dict(e_noe=e, rank_in_ours=int(1 + (ours < int(e)).sum()), moved=pipeline.model_similarity(x, ref_xyz), xyz=x,
                 rel_gap=float((e - ours.min()) / ours.min()), e3=e3)
+
+
+# ---- the host units on the CPU, against the fake HIP layer of tools/sanitize (plain g++ -O0: no sanitizer, nothing preloaded) ----
+HOST_UNITS = ("api", "config", "gate", "run", "analysis", "host")     # every translation unit of libc3d without device code
+
+
+def link_fake_hip(out_dir, mains, exe):
+    """Compiles the host units of csrc/, tools/sanitize/hip_stub.cpp and `mains` [(source, object name, extra flags)] side by side and
+    links them into out_dir/exe.  Returns the program's path, or None where there is no host C++ compiler; a compiler or linker error fails."""
+    cxx = shutil.which("g++") or shutil.which("c++")
+    if cxx is None:
+        return None
+    root = os.path.dirname(HERE)
+    csrc, san = os.path.join(root, "chromosome3d_amd", "csrc"), os.path.join(root, "tools", "sanitize")
+    flags = ["-std=c++17", "-O0", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "include"), "-Wno-unused-result"]
+    jobs = [(os.path.join(csrc, "c3d_%s.cpp" % u), u + ".o", []) for u in HOST_UNITS] + [(os.path.join(san, "hip_stub.cpp"), "stub.o", [])] + list(mains)
+    procs = [subprocess.Popen([cxx] + flags + extra + ["-c", src, "-o", os.path.join(out_dir, obj)], stderr=subprocess.PIPE, text=True) for src, obj, extra in jobs]
+    for p in procs:
+        err = p.communicate()[1]
+        assert p.returncode == 0, err[-2000:]
+    out = os.path.join(out_dir, exe)
+    link = subprocess.run([cxx] + [os.path.join(out_dir, obj) for _, obj, _ in jobs] + ["-o", out, "-lpthread"], capture_output=True, text=True)
+    assert link.returncode == 0, link.stderr[-2000:]
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def config_transcript():
+    """(transcript, key lists) as tests/harness/config_transcript.cpp prints them, built and run once per session; None without a compiler."""
+    tmp = tempfile.mkdtemp(prefix="c3d_config_transcript_")
+    try:
+        exe = link_fake_hip(tmp, [(os.path.join(HERE, "harness", "config_transcript.cpp"), "main.o", [])], "config_transcript")
+        if exe is None:
+            return None
+        runs = [subprocess.run([exe] + args, capture_output=True, text=True, timeout=120) for args in ([], ["keys"])]
+        for r in runs:
+            assert r.returncode == 0, r.stderr[-2000:]
+        return runs[0].stdout, runs[1].stdout
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+
+
+def transcript_calls(text):
+    """[(context, state, what, call, return code, refusal, what changed)] of a transcript's call lines: `context` counts the `# <state> <what>`
+    lines, each of which opens a fresh context in state "A" / "B" / "C"; `"` is resolved to the refusal of the line before."""
+    out, ctx, state, what, last = [], -1, None, None, ""
+    for line in text.splitlines():
+        if line.startswith("# "):
+            ctx, state, what, last = ctx + 1, line[2], line[4:], ""
+            continue
+        f = line.split("\t") + ["", "", ""]
+        if f[0] == "default" or f[0] == "set-up differs":
+            continue
+        rc = int(f[1])
+        if rc and f[2] != '"':
+            last = f[2]
+        out.append((ctx, state, what, f[0], rc, last if rc else "", f[3]))
+    return out
+
+
+def stub_context_knows_stat(key):
+    """c3d_get_stat(key) returned C3D_OK on a live context of the harness (state A and state B); skips without a host compiler"""
+    import pytest
+    got = config_transcript()
+    if got is None:
+        pytest.skip("no host C++ compiler")
+    rcs = [c[4] for c in transcript_calls(got[0]) if c[3] == "get_stat " + key]
+    return len(rcs) == 2 and rcs == [0, 0]
