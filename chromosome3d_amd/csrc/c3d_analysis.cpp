@@ -1,6 +1,6 @@
 // c3d_analysis.cpp — host unit of libc3d.so: the output side.  What a run's models are worth and how they relate, from the coordinates
 // resident on the device (kernels: c3d_score.hip): c3d_score_replicas, c3d_compare_replicas, c3d_superpose_replicas, c3d_rmsd_table,
-// c3d_ensemble_map, c3d_ensemble_score, c3d_geometry_replicas, c3d_separation_profile, c3d_stratified_score, c3d_bead_scores and the test hooks c3d_debug_if_ranks / c3d_debug_distance_ranks.  What they share comes first: typed
+// c3d_ensemble_map, c3d_ensemble_score, c3d_geometry_replicas, c3d_separation_profile, c3d_stratified_score, c3d_bead_scores, c3d_accessibility (with the host-only c3d_sphere_points) and the test hooks c3d_debug_if_ranks / c3d_debug_distance_ranks.  What they share comes first: typed
 // scratch slots (Slot, Block, Carve, CallScratch), the ranker (rank_matrix) and the models of a call (model_set_check, model_set_coords, gather_models).
 #include <limits>
 
@@ -900,5 +900,87 @@ extern "C" int c3d_bead_scores(c3d_ctx* c, const double* IF, int range, const in
         }
     }
     ++c->bead_runs;
+    return C3D_OK;
+}
+
+// ---- a bead's exposed surface (c3d_score.hip k_access) ----
+// c3d_accessibility's one allocation: the models, the points, the K x n counts and the flag word
+struct AccessScratch : Carve {
+    Slot<double> xyz, points;
+    Slot<int32_t> exposed;
+    Slot<int> flags;
+    AccessScratch(int n, int K, int P) {
+        xyz = take<double>(3 * (size_t)n * K);
+        points = take<double>(3 * (size_t)P);
+        exposed = take<int32_t>((size_t)n * K);
+        flags = take<int>(1);
+    }
+};
+
+extern "C" int c3d_sphere_points(int n_points, double* u) {
+    if (n_points < 1 || n_points > C3D_ACCESS_MAX_POINTS) return fail(C3D_ERR_INVALID, "c3d_sphere_points: n_points outside 1..C3D_ACCESS_MAX_POINTS");
+    if (!u) return fail(C3D_ERR_INVALID, "c3d_sphere_points: null buffer");
+    const double pi = 3.14159265358979323846, golden = pi * (3.0 - sqrt(5.0));
+    for (int k = 0; k < n_points; ++k) {
+        const double z = 1.0 - (double)(2 * k + 1) / (double)n_points, r = sqrt(1.0 - z * z), phi = (double)k * golden;
+        u[3 * k] = r * cos(phi);
+        u[3 * k + 1] = r * sin(phi);
+        u[3 * k + 2] = z;
+    }
+    return C3D_OK;
+}
+
+extern "C" int c3d_accessibility(c3d_ctx* c, const double* extra_xyz, int n_extra, double radius, double probe, const double* points, int n_points, int32_t* exposed,
+                                 double* device_ms) {
+    const char* const who = "c3d_accessibility";
+    if (int rc = model_set_check(c, who, 2, "no other bead to bury a point", extra_xyz, n_extra)) return rc;
+    if (!exposed) return fail(C3D_ERR_INVALID, "c3d_accessibility: exposed is NULL");
+    if (n_points < 1 || n_points > C3D_ACCESS_MAX_POINTS) return fail(C3D_ERR_INVALID, "c3d_accessibility: n_points outside 1..C3D_ACCESS_MAX_POINTS");
+    if (!std::isfinite(radius) || radius <= 0.0) return fail(C3D_ERR_INVALID, "c3d_accessibility: radius is not finite or <= 0");
+    if (!std::isfinite(probe) || probe < 0.0) return fail(C3D_ERR_INVALID, "c3d_accessibility: probe is not finite or < 0");
+    const double R = radius + probe;
+    if (!(R >= 0.01 && R <= 1e5)) return fail(C3D_ERR_INVALID, "c3d_accessibility: radius + probe outside 0.01 .. 1e5 A");
+    std::vector<double> lattice;
+    if (points) {
+        for (int p = 0; p < n_points; ++p) {
+            const double* const u = points + 3 * (size_t)p;
+            const double norm2 = (u[0] * u[0] + u[1] * u[1]) + u[2] * u[2];
+            if (!(fabs(norm2 - 1.0) <= 1e-9))      // (a component that is not finite fails the comparison too)
+                return fail(C3D_ERR_INVALID, "c3d_accessibility: point " + std::to_string(p) + " is not a unit vector (squared norm within 1e-9 of 1)");
+        }
+    } else {
+        lattice.resize(3 * (size_t)n_points);
+        if (int rc = c3d_sphere_points(n_points, lattice.data())) return rc;
+    }
+    if (int rc = model_set_coords(c, who, extra_xyz, n_extra)) return rc;
+    const int n = c->n, K = c->nrep + n_extra;
+    C3D_ENTRY(c, unit_bit(UNIT_SCORE));
+    const AccessScratch L(n, K, n_points);
+    CallScratch tmp;
+    if (int rc = tmp.alloc(L.total, who)) return rc;
+    PassEvents ev;
+    for (int k = 0; k < 2; ++k) HIP_TRY(hipEventCreate(&ev.e[k]));
+    static_assert(sizeof(int) == sizeof(int32_t), "the device's counts are the caller's int32_t");
+    double* const d_xyz = L.xyz.at(tmp.p);
+    int* const d_flags = L.flags.at(tmp.p);
+    // the products of the definition's constants, formed here once: R2 as the kernel compares with it, and the neighbour bound
+    const double R2 = R * R, keep2 = 4.0 * R2 * (1.0 + 0x1p-20);
+    HIP_TRY(hipMemsetAsync(d_flags, 0, L.flags.bytes(), c->stream));
+    HIP_TRY(hipMemcpyAsync(L.points.at(tmp.p), points ? points : lattice.data(), L.points.bytes(), hipMemcpyHostToDevice, c->stream));
+    if (int rc = gather_models(c, ModelSource::STATE, 0, c->nrep, d_xyz, extra_xyz, n_extra, "superpose launch")) return rc;
+    HIP_TRY(hipEventRecord(ev.e[0], c->stream));
+    LAUNCH_TRY("accessibility launch", c3d::launch_accessibility(d_xyz, n, K, L.points.at(tmp.p), n_points, R, R2, keep2, L.exposed.at(tmp.p), d_flags, c->stream));
+    HIP_TRY(hipEventRecord(ev.e[1], c->stream));
+    if (int rc = read_back(c, d_flags, L.flags.bytes())) return rc;
+    if (static_cast<const int*>(c->h_stage)[0])
+        return fail(C3D_ERR_INVALID, "c3d_accessibility: a replica's coordinate is not finite or has |x| >= 1e6 (the limit of the extra models, and of the neighbour bound)");
+    // straight into the caller's array, as c3d_geometry_replicas copies its per-bead counts
+    HIP_TRY(hipMemcpyAsync(exposed, L.exposed.at(tmp.p), L.exposed.bytes(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (device_ms) {
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+        *device_ms = ms;
+    }
     return C3D_OK;
 }

@@ -490,6 +490,12 @@ hipError_t launch_bead_if(const double* IF, int n, int range, const int* beads, 
 hipError_t launch_bead_models(const double* xyz, int n, int K, int range, const int* beads, int nb, const unsigned* a, const long long* saa, const float* tgt,
                               int npad, const int* t10, int min_sep, long long* sums, int* restrained, int* satisfied, long long* dev_milli, int* flags,
                               hipStream_t s);
+// A bead's exposed surface (c3d_accessibility; k_access).  xyz as above; points (device): P x 3 doubles, unit vectors; R = radius + probe,
+// R2 = R R, keep2 = 4 R2 (1 + 2^-20), the neighbour bound (c3d_score_access.inc), all three formed by the caller.  exposed (K x n on the
+// device) = per bead the number of its points x_i + R u_p that lie strictly inside the sphere of radius R of no other bead of the model.
+// flags (one int, cleared by the caller): [0] a coordinate of a model is not finite or has |x| >= 1e6, outside the bound's proof.
+hipError_t launch_accessibility(const double* xyz, int n, int K, const double* points, int P, double R, double R2, double keep2, int* exposed, int* flags,
+                                hipStream_t s);
 
 // Target matrix entry: NOE target in Angstrom, 0 = no restraint (host c3d_set_restraints and K1).
 inline float encode_target_host(float t) { return t > 0 ? t : 0.0f; }

@@ -15,6 +15,8 @@
 //       <prefix>_strata.txt, the Spearman coefficient inside every genomic separation, one column a model
 //   --per-bead <prefix> writes <prefix>_beads.txt — per bead and model the Spearman coefficient of the bead's row of IF against its distances,
 //       and how many of the bead's restraints the model satisfies and by how much it misses them
+//   --accessibility <prefix> writes <prefix>_accessibility.txt — per bead and model the share of the bead's sphere that a probe can reach:
+//       which loci lie on the surface of the fold and which are buried in it
 //
 // Success convention of the reference: <ID>_<M>.pdb exists, iam.running removed; on failure
 // iam.running is renamed iam.failed and the exit code is non-zero (:266-283).
@@ -75,6 +77,14 @@ static void usage() {
             "                                        Spearman coefficient of the bead's row of IF against its distances over |i-j| >= 3 (%%.6f; `nan` where a\n"
             "                                        side is constant, e.g. an unmappable bin), the reference's net count of satisfied restraints of the bead\n"
             "                                        and the summed deviation of the others in A (%%.3f)]\n"
+            "                 [--accessibility <prefix>   where every locus sits in the fold, computed on the device.  <prefix>_accessibility.txt: one row per bead,\n"
+            "                                             `bead mean f_1 ... f_M`: the bead's 1-based index, the mean over the models and per model, in rank order\n"
+            "                                             (lowest int(E_noe) first), the exposed share of the P points on the sphere of radius R = bead radius +\n"
+            "                                             probe radius about the bead — those inside no other bead's sphere of that radius (%%.4f; Shrake-Rupley).\n"
+            "                                             A header line gives R, P and every model's accessible area 4 pi R^2 sum f in A^2]\n"
+            "                 [--bead-radius <A>   radius of a bead; default half the model's bond length b0: touching beads — a convention]\n"
+            "                 [--probe-radius <A>   radius of the probe; default half of b0: a probe of a bead's size — a convention]\n"
+            "                 [--sphere-points <P>   points on a bead's sphere, 1..1024; default 96]\n"
             "                 [--accepted   also write <ID>a_<k>.pdb beside every <ID>_<k>.pdb, as CNS does for structures it accepts]\n");
 }
 
@@ -104,7 +114,9 @@ int main(int argc, char** argv) {
     // (rc -13, "GPU coredump: execvp failed") before the runtime has said WHICH exception — round 5 lost the only evidence of one that way.
     setenv("HSA_DISABLE_COREDUMP_ON_EXCEPTION", "1", 0);          // (0: a user's own setting wins)
     const double t_start = now_s();
-    std::string if_path, tbl_path, out_dir, id, seq_arg, similarity_path, rmsf_path, ensemble_prefix, geometry_prefix, stratified_prefix, per_bead_prefix;
+    std::string if_path, tbl_path, out_dir, id, seq_arg, similarity_path, rmsf_path, ensemble_prefix, geometry_prefix, stratified_prefix, per_bead_prefix, accessibility_prefix;
+    double bead_radius = -1, probe_radius = -1;      // < 0: half of b0
+    int sphere_points = 96;
     int superpose = 0, ensemble_top = 0, stratified_max_sep = 0;
     double ensemble_cutoff = -1;      // < 0: 2 x b0
     double clash_cutoff = 3.5;        // the figure of the reference's assessment
@@ -153,6 +165,10 @@ int main(int argc, char** argv) {
         else if (s == "--stratified") stratified_prefix = next("--stratified");   // per-separation Spearman and their combination (c3d_stratified_score)
         else if (s == "--stratified-max-sep") stratified_max_sep = atoi(next("--stratified-max-sep"));
         else if (s == "--per-bead") per_bead_prefix = next("--per-bead");   // per-bead Spearman and restraint tallies (c3d_bead_scores)
+        else if (s == "--accessibility") accessibility_prefix = next("--accessibility");   // exposed share of every bead's sphere (c3d_accessibility)
+        else if (s == "--bead-radius") bead_radius = atof(next("--bead-radius"));
+        else if (s == "--probe-radius") probe_radius = atof(next("--probe-radius"));
+        else if (s == "--sphere-points") sphere_points = atoi(next("--sphere-points"));
         else if (s == "--clash-cutoff") clash_cutoff = atof(next("--clash-cutoff"));
         else if (s == "--clash-sep") clash_sep = atoi(next("--clash-sep"));
         else if (s == "-h" || s == "--help") { usage(); return 0; }
@@ -399,6 +415,35 @@ int main(int argc, char** argv) {
                 if (std::isnan(rho[at])) fprintf(f, " nan"); else fprintf(f, " %.6f", rho[at]);
                 fprintf(f, " %d %.3f", satisfied[at], (double)dev[at] / 1000.0);
             }
+            fprintf(f, "\n");
+        }
+        fclose(f);
+    }
+    if (!accessibility_prefix.empty()) {
+        std::vector<int32_t> order(models);
+        CHECK(c3d_rank(ctx, order.data()));
+        const double radius = bead_radius < 0 ? 0.5 * (double)model.b0 : bead_radius, probe = probe_radius < 0 ? 0.5 * (double)model.b0 : probe_radius;
+        const double R = radius + probe, sphere = 4.0 * 3.14159265358979323846 * R * R;
+        std::vector<int32_t> exposed((size_t)models * n);
+        CHECK(c3d_accessibility(ctx, nullptr, 0, radius, probe, nullptr, sphere_points, exposed.data(), nullptr));
+        const std::string path = accessibility_prefix + "_accessibility.txt";
+        FILE* f = fopen(path.c_str(), "w");
+        if (!f) { fprintf(stderr, "c3d_solve: cannot write %s\n", path.c_str()); return fail_exit(out_dir); }
+        fprintf(f, "# bead mean f_1 ... f_%d   (exposed share of a bead's sphere points; columns: the models in rank order; model r is %s_<r>.pdb)\n", models, id.c_str());
+        fprintf(f, "# models:");
+        for (int k = 0; k < models; ++k) fprintf(f, " %u", first_rep + (unsigned)order[k] + 1u);
+        fprintf(f, "\n# R = %g A (bead radius %g + probe radius %g), P = %d points, accessible area of every model in A^2:", R, radius, probe, sphere_points);
+        for (int k = 0; k < models; ++k) {
+            long long open = 0;
+            for (int i = 0; i < n; ++i) open += exposed[(size_t)order[k] * n + i];
+            fprintf(f, " %.1f", sphere * (double)open / (double)sphere_points);
+        }
+        fprintf(f, "\n");
+        for (int i = 0; i < n; ++i) {
+            long long open = 0;
+            for (int k = 0; k < models; ++k) open += exposed[(size_t)k * n + i];
+            fprintf(f, "%d %.4f", i + 1, (double)open / ((double)sphere_points * models));
+            for (int k = 0; k < models; ++k) fprintf(f, " %.4f", (double)exposed[(size_t)order[k] * n + i] / (double)sphere_points);
             fprintf(f, "\n");
         }
         fclose(f);

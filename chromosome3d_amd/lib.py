@@ -92,6 +92,8 @@ SIGNATURES = {
     "c3d_separation_profile": (_i, [_vp, _dp, _i, _i32p, _i, _d, _dp, _dp, _dp]),
     "c3d_stratified_score": (_i, [_vp, _dp, _i, _i, _dp, _i, _dp, _dp, C.POINTER(C.c_int64)]),
     "c3d_bead_scores": (_i, [_vp, _dp, _i, _i32p, _i, _dp, _i, _dp, C.POINTER(C.c_int64), _i32p, _i32p, C.POINTER(C.c_int64)]),
+    "c3d_sphere_points": (_i, [_i, _dp]),
+    "c3d_accessibility": (_i, [_vp, _dp, _i, _d, _d, _dp, _i, _i32p, _dp]),
     "c3d_rank": (_i, [_vp, _i32p]),
     "c3d_reduce_model": (_i, [_dp, _i, _dp]),
     "c3d_model_similarity": (_i, [_dp, _dp, _i, _dp, _dp]),
@@ -113,6 +115,7 @@ SUPERPOSE_MIRROR, SUPERPOSE_APPLY = 1, 2      # C3D_SUPERPOSE_MIRROR, C3D_SUPERP
 GEOMETRY_FIELDS = 6                           # C3D_GEOMETRY_FIELDS
 STRATUM_FIELDS = 3                            # C3D_STRATUM_FIELDS
 BEAD_FIELDS = 3                               # C3D_BEAD_FIELDS
+ACCESS_MAX_POINTS = 1024                      # C3D_ACCESS_MAX_POINTS
 LBFGS_MAX_PAIRS, LBFGS_SUMS, LBFGS_STATE_DOUBLES, LBFGS_COEFS = 8, 36, 129, 17      # C3D_LBFGS_*
 
 _lib = None

@@ -242,6 +242,19 @@ def bead_report(solver, IF, rng=3, beads=None, extra=None):
     return out
 
 
+def accessibility_report(solver, extra=None, radius=None, probe=None, n_points=96, points=None):
+    """Where every locus sits in the fold, on the device: Solver.accessibility's dict ("exposed", "fraction", "area" per model and bead,
+    "model_area" per model, "mean_fraction" per bead, "device_ms") with "radius" and "probe", the values the call used (each defaults to half
+    the model's bond length b0: a convention), "points", the number of sphere points P, and "buried" [K], the number of a model's beads
+    without an exposed point."""
+    out = solver.accessibility(extra, radius, probe, n_points, points)
+    out["radius"] = 0.5 * solver.b0 if radius is None else float(radius)
+    out["probe"] = 0.5 * solver.b0 if probe is None else float(probe)
+    out["points"] = int(n_points) if points is None else int(np.asarray(points).shape[0])
+    out["buried"] = (out["exposed"] == 0).sum(axis=1)
+    return out
+
+
 def build_models(solver, model_count=MODELCOUNT, seed=MD_SEED, first_replica=0, model=None, stages=None, fire=None,
                  gtol=1e-2, check_every=250, final_kind=5):
     """The replacement of `cns_solve < dgsa.inp` (:254-289): runs the whole annealing schedule

@@ -63,6 +63,7 @@ class Solver:
         self.device = device
         self.n = 0
         self.nrep = 0
+        self._b0 = None      # the bond length of the model last set (None: the library's default model)
 
     def close(self):
         if self._h:
@@ -78,6 +79,7 @@ class Solver:
     # ---- problem ----
     def set_model(self, model):
         _l.check(self._L.c3d_set_model(self._h, C.byref(model)))
+        self._b0 = float(model.b0)
 
     def set_schedule(self, stages, fire=None, gtol=0.0, check_every=250):
         fire = fire if fire is not None else default_fire()
@@ -101,6 +103,11 @@ class Solver:
         d = np.empty((self.n, self.n), dtype=np.int32)
         _l.check(self._L.c3d_get_dist10(self._h, _l.i32ptr(d)))
         return d
+
+    @property
+    def b0(self):
+        """the bond length of the model last set (the library's default model before any set_model)"""
+        return self._b0 if self._b0 is not None else float(default_model().b0)
 
     @property
     def num_restraints(self):
@@ -431,6 +438,32 @@ class Solver:
                                          i64(out["sums"]) if IFc is not None else None, _l.i32ptr(out["restrained"]), _l.i32ptr(out["satisfied"]),
                                          i64(out["dev_milli"])))
         return out
+
+    def accessibility(self, extra=None, radius=None, probe=None, n_points=96, points=None):
+        """A dict of arrays over the K models of compare() — the replicas at their current coordinates (precision 64: the fp64 state), then
+        `extra` [E, n, 3] — computed on the device (c3d_accessibility): "exposed" [K, n] int32, of the P points x_i + R u_p on the sphere of
+        radius R = radius + probe about bead i the number that lie strictly inside no other bead's sphere of that radius (Shrake-Rupley);
+        "fraction" [K, n] = exposed / P; "area" [K, n] = 4 pi R^2 fraction, the bead's accessible area in A^2; "model_area" [K], its sum
+        over a model's beads; "mean_fraction" [n], the fraction's mean over the models; "device_ms", the device time of the call's kernel.
+        points: [P, 3] unit vectors, used as given (None: the Fibonacci lattice of n_points points, c3d_sphere_points).  radius and probe
+        default to half the model's bond length b0 each — touching beads, and a probe of a bead's size: a convention, not a measured
+        value.  Nothing of the solve changes."""
+        radius = 0.5 * self.b0 if radius is None else float(radius)
+        probe = 0.5 * self.b0 if probe is None else float(probe)
+        u = None
+        if points is not None:
+            u = np.ascontiguousarray(points, dtype=np.float64)
+            assert u.ndim == 2 and u.shape[1] == 3
+            n_points = u.shape[0]
+        xptr, E = self._extra_models(extra)
+        K, P = self.nrep + E, int(n_points)
+        exposed = np.empty((K, self.n), dtype=np.int32)
+        ms = C.c_double()
+        _l.check(self._L.c3d_accessibility(self._h, xptr, E, radius, probe, _l.dptr(u) if u is not None else None, P, _l.i32ptr(exposed), C.byref(ms)))
+        fraction = exposed / float(P)
+        area = 4.0 * np.pi * (radius + probe) ** 2 * fraction
+        return {"exposed": exposed, "fraction": fraction, "area": area, "model_area": area.sum(axis=1), "mean_fraction": fraction.mean(axis=0),
+                "device_ms": ms.value}
 
     def rank(self):
         r = np.empty(self.nrep, dtype=np.int32)

@@ -655,6 +655,47 @@ int c3d_stratified_score(c3d_ctx* ctx, const double* IF, int range, int max_sep,
 int c3d_bead_scores(c3d_ctx* ctx, const double* IF, int range, const int32_t* beads, int n_beads,
                     const double* extra_xyz, int n_extra,
                     double* rho, int64_t* sums, int32_t* restrained, int32_t* satisfied, int64_t* dev_milli);
+/* Bead accessibility on the device (c3d_score_access.inc k_access): where a locus sits in the fold — buried in the interior, or on the
+ * surface where a probe of a given size reaches it.  The Shrake-Rupley construction over uniform spheres: the track bead-model packages
+ * call "accessibility" (TADbit), the quantity that relates a model to accessibility assays.  A neighbour count (bead_clashes, nearest of
+ * c3d_geometry_replicas) does not say it: six partners on one side leave a bead half open, six around it close it.
+ *
+ * Models.  K = n_replicas + n_extra, numbered and taken exactly as c3d_geometry_replicas takes them: on a precision-64 context the fp64
+ *   state bit for bit, otherwise the floats taken as doubles; extra models are n x 3 doubles, checked as there.
+ * Points.  points = n_points x 3 doubles, unit vectors u_p, used as given; NULL asks for the lattice of c3d_sphere_points(n_points).
+ *   P = n_points, 1 <= P <= C3D_ACCESS_MAX_POINTS.  A caller's point is refused unless it is finite and its squared norm
+ *   (ux ux + uy uy) + uz uz lies within 1e-9 of 1.
+ * Definition.  For model k, bead i and point p, in doubles, every product and every sum rounded on its own (no fma):
+ *   - R = radius + probe, R2 = R * R.
+ *   - c = x_i + R u_p, a component as one product and one sum.
+ *   - point p of bead i is buried if some bead j != i of the same model has ((ex ex) + ey ey) + ez ez < R2 with e = c - x_j; the
+ *     comparison is strict.  j = i is left out by index, not by distance: a second bead at the same coordinates does bury.
+ *   - exposed[k n + i] = the number of points of bead i that are not buried, 0 .. P.
+ *   The accessible area follows on the host as 4 pi R^2 exposed / P.  With uniform spheres `radius` and `probe` enter through their sum
+ *   alone; they are two arguments because they are two physical quantities.
+ * c3d_sphere_points, host only, no device needed: the Fibonacci lattice of n_points unit vectors into u (n_points x 3 doubles),
+ *   z = 1 - (2k+1)/P, r = sqrt(1 - z z), phi = k pi (3 - sqrt 5), u_k = (r cos phi, r sin phi, z), k = 0 .. P-1.  C3D_ERR_INVALID for
+ *   n_points outside 1..C3D_ACCESS_MAX_POINTS or u NULL.
+ * exposed is K x n, row-major, required.  device_ms, optional: one double, the device time of the call's kernel from HIP events (there is
+ * no stat key for it).
+ * The result is a set of integers that depends on no summation order: no atomics on floating-point data, two calls return the same bytes,
+ * extra models leave the replicas' entries their bytes, and the integers are those of a host loop over all j written with the operations
+ * above.  The device does not test all j: only beads closer to bead i than 2 R can bury a point of i, so a workgroup first lists a bead's
+ * neighbours — d(i,j)^2 <= 4 R2 (1 + 2^-20), a bound that is proved conservative under the limits below (c3d_score_access.inc) — and
+ * tests points against the list.
+ * No state of the solve changes (the guarantee of c3d_compare_replicas).
+ * C3D_ERR_INVALID with the function's name, before any launch and with nothing written: no context or no replicas, n < 2, n_extra < 0 or
+ * extra models without coordinates, K > C3D_COMPARE_MAX_MODELS, exposed NULL, n_points outside 1..C3D_ACCESS_MAX_POINTS, radius not finite
+ * or <= 0, probe not finite or < 0, radius + probe outside [0.01, 1e5] A (the range in which the neighbour bound is proved for |x| < 1e6),
+ * a bad point, extra coordinates that are not finite or have |x| >= 1e6.  C3D_ERR_INVALID after the pass that finds it, with nothing
+ * written: a replica's coordinate that is not finite or has |x| >= 1e6 (a solve that has diverged; the bound's proof does not cover it).
+ * C3D_ERR_NOMEM: no device memory for the scratch.
+ * Scratch, one allocation per call, freed before it returns: 28 n K + 24 P bytes and a flag word (24 n a model of coordinates, 4 a bead of
+ * counts, 24 a point): 0.26 MB at 455 beads x 20 models, 9.2 MB at 16384 x 20, both with 96 points. */
+#define C3D_ACCESS_MAX_POINTS 1024
+int c3d_sphere_points(int n_points, double* u);
+int c3d_accessibility(c3d_ctx* ctx, const double* extra_xyz, int n_extra, double radius, double probe,
+                      const double* points, int n_points, int32_t* exposed, double* device_ms);
 /* rank[k] = replica index with the k-th lowest int(E_noe) (chromosome3D.pl:796-802,822-828);
  * ties broken by replica id. */
 int c3d_rank(c3d_ctx* ctx, int32_t* rank);

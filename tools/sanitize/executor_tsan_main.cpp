@@ -111,6 +111,9 @@ static void api_storm(int device_count) {
                 std::vector<int64_t> bsums(4 * (size_t)n * C3D_BEAD_FIELDS), bdev(4 * (size_t)n);
                 ok = ok && c3d_bead_scores(c, IF.data(), 3, nullptr, 0, nullptr, 0, srho.data(), bsums.data(), brestr.data(), bsat.data(), bdev.data()) == C3D_OK;
                 ok = ok && c3d_bead_scores(c, nullptr, 3, picked, 3, nullptr, 0, srho.data(), nullptr, nullptr, nullptr, nullptr) == C3D_ERR_INVALID;
+                double access_ms = -1;
+                ok = ok && c3d_accessibility(c, nullptr, 0, 1.965, 1.965, nullptr, 24, bead.data(), &access_ms) == C3D_OK && access_ms >= 0;
+                ok = ok && c3d_accessibility(c, nullptr, 0, 1.965, 1.965, nullptr, C3D_ACCESS_MAX_POINTS + 1, bead.data(), nullptr) == C3D_ERR_INVALID;
                 if (what == 2) { unsigned long long a, b, d; ok = ok && c3d_debug_tear16(c, 4, &a, &b, &d) == C3D_OK; }
             }
             if (!ok) { fprintf(stderr, "api storm thread %d: %s\n", t, c3d_last_error()); ++failures; }

@@ -500,4 +500,33 @@ hipError_t launch_bead_models(const double* xyz, int n, int K, int range, const 
     return hipSuccess;
 }
 
+// c3d_accessibility: plain brute force over all j, over the "device" memory (no neighbour list: keep2 is not used)
+hipError_t launch_accessibility(const double* xyz, int n, int K, const double* points, int P, double R, double R2, double, int* exposed, int* flags, hipStream_t) {
+    LaunchScope ls;
+    for (int k = 0; k < K; ++k) {
+        const double* x = xyz + (size_t)k * 3 * n;
+        for (int i = 0; i < n; ++i) {
+            int open = 0;
+            for (int q = 0; q < 3; ++q)
+                if (!(std::fabs(x[3 * i + q]) < 1e6)) flags[0] = 1;
+            for (int p = 0; p < P; ++p) {
+                volatile double c[3];                                        // (volatile: every product and sum rounded on its own)
+                for (int q = 0; q < 3; ++q) { volatile double t = R * points[3 * p + q]; c[q] = x[3 * i + q] + t; }
+                bool buried = false;
+                for (int j = 0; j < n && !buried; ++j) {
+                    if (j == i) continue;
+                    const double e0 = c[0] - x[3 * j], e1 = c[1] - x[3 * j + 1], e2 = c[2] - x[3 * j + 2];
+                    volatile double s = e0 * e0, t1 = e1 * e1, t2 = e2 * e2;
+                    s = s + t1;
+                    s = s + t2;
+                    buried = s < R2;
+                }
+                open += buried ? 0 : 1;
+            }
+            exposed[(size_t)k * n + i] = open;
+        }
+    }
+    return hipSuccess;
+}
+
 }  // namespace c3d
