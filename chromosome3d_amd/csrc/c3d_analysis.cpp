@@ -1,6 +1,6 @@
 // c3d_analysis.cpp — host unit of libc3d.so: the output side.  What a run's models are worth and how they relate, from the coordinates
 // resident on the device (kernels: c3d_score.hip): c3d_score_replicas, c3d_compare_replicas, c3d_superpose_replicas, c3d_rmsd_table,
-// c3d_ensemble_map, c3d_ensemble_score, c3d_geometry_replicas, c3d_separation_profile, c3d_stratified_score, c3d_bead_scores, c3d_accessibility (with the host-only c3d_sphere_points) and the test hooks c3d_debug_if_ranks / c3d_debug_distance_ranks.  What they share comes first: typed
+// c3d_ensemble_map, c3d_ensemble_score, c3d_geometry_replicas, c3d_separation_profile, c3d_stratified_score, c3d_bead_scores, c3d_accessibility (with the host-only c3d_sphere_points), c3d_compartments (with the host-only c3d_compartment_start) and the test hooks c3d_debug_if_ranks / c3d_debug_distance_ranks.  What they share comes first: typed
 // scratch slots (Slot, Block, Carve, CallScratch), the ranker (rank_matrix) and the models of a call (model_set_check, model_set_coords, gather_models).
 #include <limits>
 
@@ -977,6 +977,148 @@ extern "C" int c3d_accessibility(c3d_ctx* c, const double* extra_xyz, int n_extr
     // straight into the caller's array, as c3d_geometry_replicas copies its per-bead counts
     HIP_TRY(hipMemcpyAsync(exposed, L.exposed.at(tmp.p), L.exposed.bytes(), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    if (device_ms) {
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+        *device_ms = ms;
+    }
+    return C3D_OK;
+}
+
+// ---- compartment eigenvectors (c3d_score.hip k_cpt_*) ----
+// c3d_compartments' one allocation: the models, the pick list, the start vectors, IF's finished vectors and, per map in flight (slots), X,
+// E, m, D, the four vector sets of a round, c and the results; the two flag words
+struct CompartmentScratch : Carve {
+    Slot<double> xyz, start, F, X, E, m, D, V, U, W, P, c, stats;
+    Slot<int32_t> pick;
+    Slot<int> flags;
+    CompartmentScratch(int n, int K, int Kp, int nv, int slots) {
+        const size_t S = (size_t)slots, vec = S * nv * n;
+        xyz = take<double>(3 * (size_t)n * K);
+        pick = take<int32_t>((size_t)Kp);
+        start = take<double>((size_t)nv * n);
+        F = take<double>((size_t)nv * n);
+        X = take<double>(S * n * n);
+        E = take<double>(S * n);
+        m = take<double>(S * n);
+        D = take<double>(S * n);
+        V = take<double>(vec);
+        U = take<double>(vec);
+        W = take<double>(vec);
+        P = take<double>(vec);
+        c = take<double>(S * c3d::kCptVecs);
+        stats = take<double>(S * c3d::kCptStats);
+        flags = take<int>(2);
+    }
+};
+
+static bool compartment_vectors_ok(int n, int n_vec) { return n_vec >= 1 && n_vec <= C3D_COMPARTMENT_MAX_VECTORS && n_vec <= n - 1; }
+
+extern "C" int c3d_compartment_start(int n, int n_vec, double* start) {
+    if (n < 3) return fail(C3D_ERR_INVALID, "c3d_compartment_start: n < 3");
+    if (!compartment_vectors_ok(n, n_vec)) return fail(C3D_ERR_INVALID, "c3d_compartment_start: n_vec outside 1..min(3, n-1)");
+    if (!start) return fail(C3D_ERR_INVALID, "c3d_compartment_start: null buffer");
+    for (int a = 0; a < n_vec; ++a)
+        for (int i = 0; i < n; ++i) {
+            uint32_t h = 4u * (uint32_t)i + (uint32_t)a + 0x9E3779B9u;
+            h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
+            start[(size_t)a * n + i] = ((double)h + 0.5) / 4294967296.0 - 0.5;      // every step exact in fp64
+        }
+    return C3D_OK;
+}
+
+extern "C" int c3d_compartments(c3d_ctx* c, const double* IF, const double* extra_xyz, int n_extra, const int32_t* pick, int n_pick, int flags, int min_sep,
+                                int n_vec, int iters, const double* start, double* expected, double* vectors, double* share, double* residual, double* agreement,
+                                double* same_side, double* device_ms) {
+    const char* const who = "c3d_compartments";
+    std::vector<int32_t> list;
+    if (int rc = ensemble_check(c, who, extra_xyz, n_extra, pick, n_pick, &list)) return rc;
+    const int n = c->n, K = c->nrep + n_extra, Kp = (int)list.size(), nv = n_vec;
+    if (n < 3) return fail(C3D_ERR_INVALID, "c3d_compartments: maps of fewer than 3 beads have no correlation to diagonalise (n < 3)");
+    if (Kp > C3D_COMPARE_MAX_MODELS) return fail(C3D_ERR_INVALID, "c3d_compartments: more than 256 picks");
+    if (!compartment_vectors_ok(n, n_vec)) return fail(C3D_ERR_INVALID, "c3d_compartments: n_vec outside 1..min(3, n-1)");
+    if (iters < 0 || iters > C3D_COMPARTMENT_MAX_ITERS) return fail(C3D_ERR_INVALID, "c3d_compartments: iters outside 0..C3D_COMPARTMENT_MAX_ITERS");
+    if (min_sep < 1 || min_sep > n - 1) return fail(C3D_ERR_INVALID, "c3d_compartments: min_sep outside 1..n-1");
+    if (flags & ~C3D_COMPARTMENT_CONSENSUS) return fail(C3D_ERR_INVALID, "c3d_compartments: unknown flag bits");
+    const bool consensus = (flags & C3D_COMPARTMENT_CONSENSUS) != 0;
+    if (consensus && Kp < 1) return fail(C3D_ERR_INVALID, "c3d_compartments: the consensus of an empty list");
+    if (!expected && !vectors && !share && !agreement && !same_side)
+        return fail(C3D_ERR_INVALID, "c3d_compartments: expected, vectors, share, agreement and same_side are all NULL");
+    if ((agreement || same_side) && !IF) return fail(C3D_ERR_INVALID, "c3d_compartments: agreement and same_side need the IF matrix");
+    std::vector<double> own;
+    if (start) {
+        for (size_t q = 0; q < (size_t)nv * n; ++q)
+            if (!std::isfinite(start[q])) return fail(C3D_ERR_INVALID, "c3d_compartments: a start vector is not finite");
+    } else {
+        own.resize((size_t)nv * n);
+        if (int rc = c3d_compartment_start(n, nv, own.data())) return rc;
+    }
+    if (int rc = model_set_coords(c, who, extra_xyz, n_extra)) return rc;
+    const int has_if = IF ? 1 : 0, Q = has_if + Kp + (consensus ? 1 : 0);
+    C3D_ENTRY(c, unit_bit(UNIT_SCORE));
+    // maps in flight: as many X slots as fit the budget, one at least
+    const size_t map_bytes = sizeof(double) * (size_t)n * n;
+    const int slots = (int)std::min<size_t>((size_t)Q, std::max<size_t>(1, (size_t)C3D_SCORE_SCRATCH_BYTES / map_bytes));
+    const CompartmentScratch L(n, K, Kp, nv, slots);
+    CallScratch tmp;
+    if (int rc = tmp.alloc(L.total, who)) return rc;
+    PassEvents ev;
+    for (int k = 0; k < 2; ++k) HIP_TRY(hipEventCreate(&ev.e[k]));
+    c3d::CptWork w;
+    w.X = L.X.at(tmp.p); w.E = L.E.at(tmp.p); w.m = L.m.at(tmp.p); w.D = L.D.at(tmp.p);
+    w.V = L.V.at(tmp.p); w.U = L.U.at(tmp.p); w.W = L.W.at(tmp.p); w.P = L.P.at(tmp.p);
+    w.c = L.c.at(tmp.p); w.stats = L.stats.at(tmp.p); w.F = L.F.at(tmp.p); w.flags = L.flags.at(tmp.p);
+    const size_t vec_bytes = sizeof(double) * (size_t)nv * n;
+    HIP_TRY(hipEventRecord(ev.e[0], c->stream));
+    HIP_TRY(hipMemsetAsync(w.flags, 0, L.flags.bytes(), c->stream));
+    HIP_TRY(hipMemcpyAsync(L.start.at(tmp.p), start ? start : own.data(), vec_bytes, hipMemcpyHostToDevice, c->stream));
+    if (int rc = gather_models(c, ModelSource::STATE, 0, c->nrep, L.xyz.at(tmp.p), extra_xyz, n_extra, "superpose launch")) return rc;
+    HIP_TRY(hipMemcpyAsync(L.pick.at(tmp.p), list.data(), sizeof(int32_t) * (size_t)Kp, hipMemcpyHostToDevice, c->stream));
+    // the results of every batch gather here: the caller's arrays are written once the last batch is through
+    std::vector<double> hE(expected ? (size_t)Q * n : 0), hV(vectors ? (size_t)Q * nv * n : 0), hS((size_t)Q * c3d::kCptStats);
+    for (int q0 = 0; q0 < Q; q0 += slots) {
+        const int nb = std::min(slots, Q - q0);
+        const c3d::CptMaps maps{n, q0, nb, has_if, Kp, L.xyz.at(tmp.p), L.pick.at(tmp.p)};
+        if (has_if && q0 == 0) {
+            HIP_TRY(hipMemcpyAsync(w.X, IF, map_bytes, hipMemcpyHostToDevice, c->stream));
+            LAUNCH_TRY("compartment launch", c3d::launch_compartment_if_check(w.X, n, w.flags, c->stream));
+            if (int rc = read_back(c, w.flags, L.flags.bytes())) return rc;
+            const int bad = static_cast<const int*>(c->h_stage)[0];
+            if (bad & 2) return fail(C3D_ERR_INVALID, "c3d_compartments: an IF entry is not finite");
+            if (bad & 4) return fail(C3D_ERR_INVALID, "c3d_compartments: an IF entry is negative");
+            if (bad & 1) return fail(C3D_ERR_INVALID, "c3d_compartments: the IF matrix is not symmetric");
+        }
+        for (int b = 0; b < nb; ++b)
+            HIP_TRY(hipMemcpyAsync(w.V + (size_t)b * nv * n, L.start.at(tmp.p), vec_bytes, hipMemcpyDeviceToDevice, c->stream));
+        LAUNCH_TRY("compartment launch", c3d::launch_compartment_build(maps, w, min_sep, c->stream));
+        for (int r = 0; r <= iters; ++r) LAUNCH_TRY("compartment launch", c3d::launch_compartment_round(maps, w, nv, r == 0, c->stream));
+        LAUNCH_TRY("compartment launch", c3d::launch_compartment_finish(maps, w, nv, c->stream));
+        if (has_if) {
+            if (q0 == 0) HIP_TRY(hipMemcpyAsync(w.F, w.V, vec_bytes, hipMemcpyDeviceToDevice, c->stream));
+            LAUNCH_TRY("compartment launch", c3d::launch_compartment_fit(maps, w, nv, c->stream));
+        }
+        if (expected) HIP_TRY(hipMemcpyAsync(hE.data() + (size_t)q0 * n, w.E, sizeof(double) * (size_t)nb * n, hipMemcpyDeviceToHost, c->stream));
+        if (vectors) HIP_TRY(hipMemcpyAsync(hV.data() + (size_t)q0 * nv * n, w.V, vec_bytes * nb, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(hS.data() + (size_t)q0 * c3d::kCptStats, w.stats, sizeof(double) * (size_t)nb * c3d::kCptStats, hipMemcpyDeviceToHost, c->stream));
+        if (int rc = read_back(c, w.flags, L.flags.bytes())) return rc;
+        if (static_cast<const int*>(c->h_stage)[1]) return fail(C3D_ERR_INVALID, "c3d_compartments: dependent start vectors (a vector projected to exactly 0)");
+    }
+    HIP_TRY(hipEventRecord(ev.e[1], c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (expected) memcpy(expected, hE.data(), sizeof(double) * hE.size());
+    if (vectors) memcpy(vectors, hV.data(), sizeof(double) * hV.size());
+    for (int q = 0; q < Q; ++q) {
+        const double* const st = hS.data() + (size_t)q * c3d::kCptStats;
+        for (int a = 0; a < nv; ++a) {
+            if (share) share[(size_t)q * nv + a] = st[a];
+            if (residual) residual[(size_t)q * nv + a] = st[3 + a];
+            if (q >= has_if && has_if) {
+                const size_t r = (size_t)(q - 1) * nv + a;
+                if (same_side) same_side[r] = st[6 + a];
+                for (int f = 0; f < nv && agreement; ++f) agreement[r * nv + f] = st[9 + 3 * a + f];
+            }
+        }
+    }
     if (device_ms) {
         float ms = 0;
         HIP_TRY(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));

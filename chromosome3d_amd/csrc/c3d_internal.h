@@ -496,6 +496,34 @@ hipError_t launch_bead_models(const double* xyz, int n, int K, int range, const 
 // flags (one int, cleared by the caller): [0] a coordinate of a model is not finite or has |x| >= 1e6, outside the bound's proof.
 hipError_t launch_accessibility(const double* xyz, int n, int K, const double* points, int P, double R, double R2, double keep2, int* exposed, int* flags,
                                 hipStream_t s);
+// Compartment eigenvectors (c3d_compartments; k_cpt_*, c3d_score_compartment.inc).  A batch is nb maps in flight, map b of it the call's map
+// q0 + b: map 0 is IF when has_if (uploaded into slot 0 of X by the caller), the n_models maps after it one picked model each — pick
+// (device) lists them, indices into the K models of xyz — and the map after those the consensus, the list's mean distance map.  Every
+// array of CptWork is on the device and indexed by b: X nb x n x n, E, m, D nb x n, V, U, W, P nb x nv x n, c nb x kCptVecs, stats
+// nb x kCptStats (share, residual, same_side at 0, 3, 6 + a; agreement at 9 + 3 a + b2); F (nv x n, one for the call) holds IF's finished
+// vectors; flags (2 ints, cleared by the caller): [0] IF is asymmetric (1), not finite (2) or negative (4) somewhere, [1] a vector
+// projected to 0 in some round.
+// launch_compartment_if_check: flags[0] of the n x n matrix M.  launch_compartment_build: E, X (in place for IF), m and D of the batch.
+// launch_compartment_round: one round — V <- Y unless `first`, Gram-Schmidt, U = D V, W = X U - c, P = X W.  launch_compartment_finish:
+// Y of the last round, share, residual and, for IF or where the call has no IF, the sign rule of the largest entry.
+// launch_compartment_fit: the maps other than IF against F — sign, agreement, same_side.
+constexpr int kCptVecs = 3;       // C3D_COMPARTMENT_MAX_VECTORS
+constexpr int kCptRows = 8;       // rows of X a workgroup of the product kernel owns
+constexpr int kCptStats = 24;
+struct CptMaps {
+    int n, q0, nb, has_if, n_models;
+    const double* xyz;
+    const int* pick;
+};
+struct CptWork {
+    double *X, *E, *m, *D, *V, *U, *W, *P, *c, *stats, *F;
+    int* flags;
+};
+hipError_t launch_compartment_if_check(const double* M, int n, int* flags, hipStream_t s);
+hipError_t launch_compartment_build(const CptMaps& maps, const CptWork& w, int min_sep, hipStream_t s);
+hipError_t launch_compartment_round(const CptMaps& maps, const CptWork& w, int nv, bool first, hipStream_t s);
+hipError_t launch_compartment_finish(const CptMaps& maps, const CptWork& w, int nv, hipStream_t s);
+hipError_t launch_compartment_fit(const CptMaps& maps, const CptWork& w, int nv, hipStream_t s);
 
 // Target matrix entry: NOE target in Angstrom, 0 = no restraint (host c3d_set_restraints and K1).
 inline float encode_target_host(float t) { return t > 0 ? t : 0.0f; }

@@ -17,6 +17,8 @@
 //       and how many of the bead's restraints the model satisfies and by how much it misses them
 //   --accessibility <prefix> writes <prefix>_accessibility.txt — per bead and model the share of the bead's sphere that a probe can reach:
 //       which loci lie on the surface of the fold and which are buried in it
+//   --compartments <prefix> writes <prefix>_compartments.txt — the first compartment eigenvector (PC1 of the correlation of the observed/expected
+//       map) of IF, of the models' consensus distance map and of every model, and how well each agrees with IF's
 //
 // Success convention of the reference: <ID>_<M>.pdb exists, iam.running removed; on failure
 // iam.running is renamed iam.failed and the exit code is non-zero (:266-283).
@@ -85,6 +87,15 @@ static void usage() {
             "                 [--bead-radius <A>   radius of a bead; default half the model's bond length b0: touching beads — a convention]\n"
             "                 [--probe-radius <A>   radius of the probe; default half of b0: a probe of a bead's size — a convention]\n"
             "                 [--sphere-points <P>   points on a bead's sphere, 1..1024; default 96]\n"
+            "                 [--compartments <prefix>   do the models reproduce the A/B compartment pattern of the data?  Computed on the device.\n"
+            "                                            <prefix>_compartments.txt: header lines `# IF|consensus|model <r>: share residual agreement same_side` (the first\n"
+            "                                            eigenvector's share of the correlation's trace, |C v - lambda v|, |Pearson r| against IF's first eigenvector and\n"
+            "                                            the share of beads on IF's side of zero; with more vectors one such group per vector), then one row per bead,\n"
+            "                                            `bead IF consensus pc1_1 ... pc1_M`: the bead's 1-based index and the entry of the first eigenvector (%%.6f) of IF,\n"
+            "                                            of the models' mean distance map and of every model in rank order; its sign is the compartment call]\n"
+            "                 [--compartment-vectors <1..3>   eigenvectors computed and reported in the header lines; default 1]\n"
+            "                 [--compartment-iters <k>   rounds of orthogonal iteration, 0..10000; default 200]\n"
+            "                 [--compartment-min-sep <s>   pairs closer than s bins along the chain count as 1 in the observed/expected map; default 1]\n"
             "                 [--accepted   also write <ID>a_<k>.pdb beside every <ID>_<k>.pdb, as CNS does for structures it accepts]\n");
 }
 
@@ -114,7 +125,8 @@ int main(int argc, char** argv) {
     // (rc -13, "GPU coredump: execvp failed") before the runtime has said WHICH exception — round 5 lost the only evidence of one that way.
     setenv("HSA_DISABLE_COREDUMP_ON_EXCEPTION", "1", 0);          // (0: a user's own setting wins)
     const double t_start = now_s();
-    std::string if_path, tbl_path, out_dir, id, seq_arg, similarity_path, rmsf_path, ensemble_prefix, geometry_prefix, stratified_prefix, per_bead_prefix, accessibility_prefix;
+    std::string if_path, tbl_path, out_dir, id, seq_arg, similarity_path, rmsf_path, ensemble_prefix, geometry_prefix, stratified_prefix, per_bead_prefix, accessibility_prefix, compartments_prefix;
+    int compartment_vectors = 1, compartment_iters = 200, compartment_min_sep = 1;
     double bead_radius = -1, probe_radius = -1;      // < 0: half of b0
     int sphere_points = 96;
     int superpose = 0, ensemble_top = 0, stratified_max_sep = 0;
@@ -166,6 +178,10 @@ int main(int argc, char** argv) {
         else if (s == "--stratified-max-sep") stratified_max_sep = atoi(next("--stratified-max-sep"));
         else if (s == "--per-bead") per_bead_prefix = next("--per-bead");   // per-bead Spearman and restraint tallies (c3d_bead_scores)
         else if (s == "--accessibility") accessibility_prefix = next("--accessibility");   // exposed share of every bead's sphere (c3d_accessibility)
+        else if (s == "--compartments") compartments_prefix = next("--compartments");   // compartment eigenvectors of IF, consensus and models (c3d_compartments)
+        else if (s == "--compartment-vectors") compartment_vectors = atoi(next("--compartment-vectors"));
+        else if (s == "--compartment-iters") compartment_iters = atoi(next("--compartment-iters"));
+        else if (s == "--compartment-min-sep") compartment_min_sep = atoi(next("--compartment-min-sep"));
         else if (s == "--bead-radius") bead_radius = atof(next("--bead-radius"));
         else if (s == "--probe-radius") probe_radius = atof(next("--probe-radius"));
         else if (s == "--sphere-points") sphere_points = atoi(next("--sphere-points"));
@@ -177,6 +193,7 @@ int main(int argc, char** argv) {
     if (out_dir.empty() || (if_path.empty() == tbl_path.empty()) || models < 1) { usage(); return 2; }
     if (!stratified_prefix.empty() && if_path.empty()) { fprintf(stderr, "c3d_solve: --stratified needs --if: a run started from --tbl has no IF matrix\n"); return 2; }
     if (!per_bead_prefix.empty() && if_path.empty()) { fprintf(stderr, "c3d_solve: --per-bead needs --if: a run started from --tbl has no IF matrix\n"); return 2; }
+    if (!compartments_prefix.empty() && if_path.empty()) { fprintf(stderr, "c3d_solve: --compartments needs --if: a run started from --tbl has no IF matrix\n"); return 2; }
     if (id.empty()) {
         std::string base = if_path.empty() ? std::string("model") : if_path.substr(if_path.find_last_of('/') + 1);
         if (base.size() > 4 && base.substr(base.size() - 4) == ".txt") base.resize(base.size() - 4);
@@ -444,6 +461,39 @@ int main(int argc, char** argv) {
             for (int k = 0; k < models; ++k) open += exposed[(size_t)k * n + i];
             fprintf(f, "%d %.4f", i + 1, (double)open / ((double)sphere_points * models));
             for (int k = 0; k < models; ++k) fprintf(f, " %.4f", (double)exposed[(size_t)order[k] * n + i] / (double)sphere_points);
+            fprintf(f, "\n");
+        }
+        fclose(f);
+    }
+    if (!compartments_prefix.empty()) {
+        std::vector<int32_t> order(models);
+        CHECK(c3d_rank(ctx, order.data()));
+        // the maps: IF, the models in rank order, their consensus
+        const int nv = compartment_vectors, Q = models + 2;
+        const size_t vec = (size_t)(nv > 0 ? nv : 1);
+        std::vector<double> vectors((size_t)Q * vec * n), share((size_t)Q * vec), residual((size_t)Q * vec), agreement((size_t)(Q - 1) * vec * vec), side((size_t)(Q - 1) * vec);
+        CHECK(c3d_compartments(ctx, IF, nullptr, 0, order.data(), models, C3D_COMPARTMENT_CONSENSUS, compartment_min_sep, nv, compartment_iters, nullptr, nullptr,
+                               vectors.data(), share.data(), residual.data(), agreement.data(), side.data(), nullptr));
+        const std::string path = compartments_prefix + "_compartments.txt";
+        FILE* f = fopen(path.c_str(), "w");
+        if (!f) { fprintf(stderr, "c3d_solve: cannot write %s\n", path.c_str()); return fail_exit(out_dir); }
+        fprintf(f, "# bead IF consensus pc1_1 ... pc1_%d   (the first compartment eigenvector; columns: the models in rank order; model r is %s_<r>.pdb)\n", models, id.c_str());
+        fprintf(f, "# models:");
+        for (int k = 0; k < models; ++k) fprintf(f, " %u", first_rep + (unsigned)order[k] + 1u);
+        fprintf(f, "\n# %d vector(s), %d rounds, min_sep %d; per vector: share residual agreement same_side\n", nv, compartment_iters, compartment_min_sep);
+        for (int q = 0; q < Q; ++q) {
+            if (q == 0) fprintf(f, "# IF:");
+            else if (q == Q - 1) fprintf(f, "# consensus:");
+            else fprintf(f, "# model %d:", q);
+            for (int a = 0; a < nv; ++a) {
+                fprintf(f, " %.6f %.3e", share[(size_t)q * nv + a], residual[(size_t)q * nv + a]);
+                if (q > 0) fprintf(f, " %.6f %.6f", agreement[((size_t)(q - 1) * nv + a) * nv + a], side[(size_t)(q - 1) * nv + a]);
+            }
+            fprintf(f, "\n");
+        }
+        for (int i = 0; i < n; ++i) {
+            fprintf(f, "%d %.6f %.6f", i + 1, vectors[(size_t)i], vectors[(size_t)(Q - 1) * nv * n + i]);
+            for (int k = 1; k <= models; ++k) fprintf(f, " %.6f", vectors[(size_t)k * nv * n + i]);
             fprintf(f, "\n");
         }
         fclose(f);

@@ -94,6 +94,8 @@ SIGNATURES = {
     "c3d_bead_scores": (_i, [_vp, _dp, _i, _i32p, _i, _dp, _i, _dp, C.POINTER(C.c_int64), _i32p, _i32p, C.POINTER(C.c_int64)]),
     "c3d_sphere_points": (_i, [_i, _dp]),
     "c3d_accessibility": (_i, [_vp, _dp, _i, _d, _d, _dp, _i, _i32p, _dp]),
+    "c3d_compartment_start": (_i, [_i, _i, _dp]),
+    "c3d_compartments": (_i, [_vp, _dp, _dp, _i, _i32p, _i, _i, _i, _i, _i, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "c3d_rank": (_i, [_vp, _i32p]),
     "c3d_reduce_model": (_i, [_dp, _i, _dp]),
     "c3d_model_similarity": (_i, [_dp, _dp, _i, _dp, _dp]),
@@ -116,6 +118,7 @@ GEOMETRY_FIELDS = 6                           # C3D_GEOMETRY_FIELDS
 STRATUM_FIELDS = 3                            # C3D_STRATUM_FIELDS
 BEAD_FIELDS = 3                               # C3D_BEAD_FIELDS
 ACCESS_MAX_POINTS = 1024                      # C3D_ACCESS_MAX_POINTS
+COMPARTMENT_MAX_VECTORS, COMPARTMENT_MAX_ITERS, COMPARTMENT_CONSENSUS = 3, 10000, 1      # C3D_COMPARTMENT_*
 LBFGS_MAX_PAIRS, LBFGS_SUMS, LBFGS_STATE_DOUBLES, LBFGS_COEFS = 8, 36, 129, 17      # C3D_LBFGS_*
 
 _lib = None

@@ -255,6 +255,18 @@ def accessibility_report(solver, extra=None, radius=None, probe=None, n_points=9
     return out
 
 
+def compartment_report(solver, IF, extra=None, pick=None, min_sep=1, n_vec=1, iters=200):
+    """Do the models reproduce the A/B compartment pattern of the data?  Solver.compartments' dict for IF, every picked model and the
+    consensus map, with "calls" [Q, n] int8, the sign of every map's first vector (the compartment call; 0 for a bead without spread),
+    "converged" [Q], whether every residual is below 1e-9, and "best" — the index into "maps" of the model map (not the consensus) whose
+    first vector agrees best with IF's."""
+    out = solver.compartments(IF, extra, pick, True, min_sep, n_vec, iters)
+    out["calls"] = np.sign(out["vectors"][:, 0, :]).astype(np.int8)
+    out["converged"] = (out["residual"] < 1e-9).all(axis=1)
+    out["best"] = 1 + int(np.argmax(out["agreement"][:-1, 0, 0]))
+    return out
+
+
 def build_models(solver, model_count=MODELCOUNT, seed=MD_SEED, first_replica=0, model=None, stages=None, fire=None,
                  gtol=1e-2, check_every=250, final_kind=5):
     """The replacement of `cns_solve < dgsa.inp` (:254-289): runs the whole annealing schedule

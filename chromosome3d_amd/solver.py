@@ -465,6 +465,45 @@ class Solver:
         return {"exposed": exposed, "fraction": fraction, "area": area, "model_area": area.sum(axis=1), "mean_fraction": fraction.mean(axis=0),
                 "device_ms": ms.value}
 
+    def compartments(self, IF=None, extra=None, pick=None, consensus=False, min_sep=1, n_vec=1, iters=200, start=None):
+        """Compartment eigenvectors on the device (c3d_compartments): the leading n_vec eigenvectors of the Pearson correlation of the rows
+        of the observed/expected map, by `iters` rounds of orthogonal iteration, for Q maps in this order: IF [n, n] if given, the
+        distance map of every picked model (pick: indices into the K models of compare(), None: all; precision 64: the fp64 state), and
+        with consensus=True the pick list's mean distance map.  A dict: "expected" [Q, n] (the mean of every diagonal), "vectors"
+        [Q, n_vec, n] (unit vectors; the sign of vector 0 is the compartment call), "share" [Q, n_vec] (the eigenvalue's share of the
+        correlation's trace), "residual" [Q, n_vec] (|C v - lambda v|: how far the iteration is from converged), "maps" (the names of
+        the Q maps: "IF", "model <k>", "consensus"), "device_ms", and with IF "agreement" [Q-1, n_vec, n_vec] (|Pearson r| of a map's
+        vector a against IF's vector b) and "same_side" [Q-1, n_vec] (the share of beads on IF's side of zero).  start: [n_vec, n]
+        start vectors (None: c3d_compartment_start's).  Nothing of the solve changes."""
+        n, nv = self.n, int(n_vec)
+        m = None
+        if IF is not None:
+            m = np.ascontiguousarray(IF, dtype=np.float64)
+            assert m.shape == (n, n)
+        s0 = None
+        if start is not None:
+            s0 = np.ascontiguousarray(start, dtype=np.float64)
+            assert s0.shape == (nv, n)
+        xptr, E = self._extra_models(extra)
+        p, n_pick = self._picked(pick)
+        Kp = n_pick if p is not None else self.nrep + E
+        has_if = 1 if m is not None else 0
+        Q = has_if + Kp + (1 if consensus else 0)
+        rows = max(nv, 1)
+        out = {"expected": np.empty((Q, n)), "vectors": np.empty((Q, rows, n)), "share": np.empty((Q, rows)), "residual": np.empty((Q, rows))}
+        if has_if:
+            out["agreement"] = np.empty((Q - 1, rows, rows))
+            out["same_side"] = np.empty((Q - 1, rows))
+        ms = C.c_double()
+        ptr = lambda k: _l.dptr(out[k]) if k in out else None
+        _l.check(self._L.c3d_compartments(self._h, _l.dptr(m) if has_if else None, xptr, E, _l.i32ptr(p) if p is not None else None, n_pick,
+                                          _l.COMPARTMENT_CONSENSUS if consensus else 0, int(min_sep), nv, int(iters), _l.dptr(s0) if s0 is not None else None,
+                                          ptr("expected"), ptr("vectors"), ptr("share"), ptr("residual"), ptr("agreement"), ptr("same_side"), C.byref(ms)))
+        models = [int(k) for k in p] if p is not None else list(range(Kp))
+        out["maps"] = (["IF"] if has_if else []) + ["model %d" % k for k in models] + (["consensus"] if consensus else [])
+        out["device_ms"] = ms.value
+        return out
+
     def rank(self):
         r = np.empty(self.nrep, dtype=np.int32)
         _l.check(self._L.c3d_rank(self._h, _l.i32ptr(r)))

@@ -696,6 +696,61 @@ int c3d_bead_scores(c3d_ctx* ctx, const double* IF, int range, const int32_t* be
 int c3d_sphere_points(int n_points, double* u);
 int c3d_accessibility(c3d_ctx* ctx, const double* extra_xyz, int n_extra, double radius, double probe,
                       const double* points, int n_points, int32_t* exposed, double* device_ms);
+/* Compartment eigenvectors on the device (c3d_score_compartment.inc k_cpt_*): do the models reproduce the A/B compartment pattern of the
+ * data?  At 500 kb and 1 Mb compartments are the large-scale feature of a contact map; the standard read-out is the leading eigenvector of
+ * the correlation matrix of the observed/expected (O/E) map, and the sign of PC1 is the compartment call.
+ *
+ * Maps, in order, Q in all: IF if non-NULL (n x n with the context's n; refused if asymmetric, not finite or holding a negative entry);
+ *   then one map per picked model, its distance map (the distance of c3d_compare_replicas: ((ux ux) + uy uy) + uz uz, every operation
+ *   rounded on its own, then sqrt); then, with C3D_COMPARTMENT_CONSENSUS in flags, the consensus: the pick list's mean distance map, summed
+ *   in list order as c3d_ensemble_map defines `mean`.
+ * Models.  K = n_replicas + n_extra, numbered and taken as in c3d_ensemble_map (the fp64 state bit for bit on a precision-64 context).
+ *   pick = the models analysed, in order; NULL with 0 = all K; at most 256 entries.
+ * Definitions, for a symmetric n x n map M:
+ *   1. Expected.  For s = 1..n-1, E[s] = mean over i of M(i, i+s), i ascending.  E[0] = 0.
+ *   2. O/E.  X(i,j) = M(i,j) / E[|i-j|] where |i-j| >= min_sep and E[|i-j|] != 0, and X(i,j) = 1 elsewhere (min_sep = 1: the diagonal is
+ *      1).  Every pair i < j is computed once and stored to both halves: X equals its transpose bit for bit.
+ *   3. Row statistics.  m_i = mean_j X(i,j); q_i = sqrt(mean_j (X(i,j) - m_i)^2), the two-pass form; D_i = 1/q_i, or 0 for a row without
+ *      spread, which gets 0 in every vector.  live = the number of rows with q_i > 0.
+ *   4. The operator.  C = Z Z^T / n with Z = D (X - m 1^T): the Pearson correlation of the rows of X.  It is never formed; X being
+ *      symmetric, both passes are matrix-vector products with X:  w = X (D v) - (m^T D v) 1,  C v = D (X w - m (1^T w)) / n.
+ *   5. Iteration.  V (n_vec x n) starts from `start`, or from c3d_compartment_start's vectors if start is NULL.  One round
+ *      orthonormalises V by modified Gram-Schmidt in index order (v_a -= (v_b . v_a) v_b for b < a, then v_a /= |v_a|) and sets
+ *      Y_a = C v_a.  After `iters` rounds (V <- Y), V is orthonormalised once more and Y computed once more; then lambda_a = v_a . y_a,
+ *      share = lambda_a / live (0 where live is 0) and residual = |y_a - lambda_a v_a|_2.  A vector that projects to exactly 0 makes the
+ *      call C3D_ERR_INVALID ("dependent start vectors"), with nothing written.
+ *   6. Sign.  IF's vectors, and every map's vectors when no IF is given: the entry of largest magnitude is positive (lowest index on
+ *      ties).  Vector a of a model or consensus map, when IF is given: its dot product with IF's vector a is made non-negative; an exact
+ *      0 falls back to the first rule.
+ *   7. Fit to the data (only with IF), per map other than IF: agreement[a][b] = |Pearson r| of the map's vector a against IF's vector b
+ *      (a table, because PC1 of one map may be PC2 of the other; means first, then the centred sums); same_side[a] =
+ *      #{i : v_map,a(i) v_IF,a(i) > 0} / n, an exact count divided once.
+ * c3d_compartment_start, host only, exact in fp64: start[a n + i] = ((double)h + 0.5) / 2^32 - 0.5 with the 32-bit integer hash
+ *   h = k + 0x9E3779B9; h ^= h >> 16; h *= 0x85EBCA6B; h ^= h >> 13; h *= 0xC2B2AE35; h ^= h >> 16 of k = 4 i + a: no libm, one division
+ *   by a power of two.  C3D_ERR_INVALID for n < 3, n_vec outside 1..min(3, n-1) or start NULL.
+ * Outputs, any may be NULL but not all of expected, vectors, share, agreement, same_side; agreement and same_side are refused without
+ *   IF.  expected Q x n; vectors Q x n_vec x n; share, residual Q x n_vec; agreement (Q - 1) x n_vec x n_vec and same_side
+ *   (Q - 1) x n_vec, the maps after IF; device_ms, optional: the HIP-event time of the call (there is no stat key for it).
+ * Every floating-point sum has an order that follows from n, n_vec and the pick list alone, through the scoring unit's one block
+ * reduction: no atomics, two calls return the same bytes, and a model's results are the same bytes whether it is analysed alone or among
+ * others.  No state of the solve changes.
+ * C3D_ERR_INVALID with the function's name, before any launch and with nothing written: no context or no replicas, n < 3, n_vec outside
+ * 1..min(3, n-1), iters outside 0..C3D_COMPARTMENT_MAX_ITERS, min_sep outside 1..n-1, unknown flag bits, consensus with an empty list,
+ * the pick and extra-model refusals of c3d_ensemble_map (and more than 256 picks), the outputs as above, start vectors that are not
+ * finite.  After the pass that finds it, with nothing written: a bad IF, dependent start vectors.  C3D_ERR_NOMEM: no device memory for
+ * the scratch.
+ * Scratch, one allocation per call, freed before it returns: 8 n^2 bytes per map in flight (IF is uploaded and turned into X in place, a
+ * model's X is written straight from coordinates) + (24 + 32 n_vec) n bytes of row statistics and vectors per map in flight + 24 n K of
+ * coordinates + 16 n_vec n.  Maps run in batches whose X slots fit C3D_SCORE_SCRATCH_BYTES, at least one a batch: one 2 GiB slot at 16384
+ * beads, and all 22 maps at once (36.4 MB of X) at 455 beads x 20 models with IF and the consensus. */
+#define C3D_COMPARTMENT_MAX_VECTORS 3
+#define C3D_COMPARTMENT_MAX_ITERS   10000
+#define C3D_COMPARTMENT_CONSENSUS   1      /* flags: one more map after the models: the pick list's mean distance map */
+int c3d_compartment_start(int n, int n_vec, double* start);   /* the library's start vectors, n_vec x n */
+int c3d_compartments(c3d_ctx* ctx, const double* IF, const double* extra_xyz, int n_extra, const int32_t* pick, int n_pick,
+                     int flags, int min_sep, int n_vec, int iters, const double* start,
+                     double* expected, double* vectors, double* share, double* residual,
+                     double* agreement, double* same_side, double* device_ms);
 /* rank[k] = replica index with the k-th lowest int(E_noe) (chromosome3D.pl:796-802,822-828);
  * ties broken by replica id. */
 int c3d_rank(c3d_ctx* ctx, int32_t* rank);

@@ -114,6 +114,13 @@ static void api_storm(int device_count) {
                 double access_ms = -1;
                 ok = ok && c3d_accessibility(c, nullptr, 0, 1.965, 1.965, nullptr, 24, bead.data(), &access_ms) == C3D_OK && access_ms >= 0;
                 ok = ok && c3d_accessibility(c, nullptr, 0, 1.965, 1.965, nullptr, C3D_ACCESS_MAX_POINTS + 1, bead.data(), nullptr) == C3D_ERR_INVALID;
+                // (the stub's models are all zeros, maps without spread: iters = 0 keeps the start vectors independent)
+                std::vector<double> cvec(6 * 2 * (size_t)n), cexp(6 * (size_t)n), cshare(12), cres(12), cagree(5 * 4), cside(5 * 2);
+                double cpt_ms = -1;
+                ok = ok && c3d_compartments(c, IF.data(), nullptr, 0, nullptr, 0, C3D_COMPARTMENT_CONSENSUS, 1, 2, 0, nullptr, cexp.data(), cvec.data(), cshare.data(),
+                                            cres.data(), cagree.data(), cside.data(), &cpt_ms) == C3D_OK && cpt_ms >= 0;
+                ok = ok && c3d_compartments(c, nullptr, nullptr, 0, picked, 3, 0, 1, C3D_COMPARTMENT_MAX_VECTORS + 1, 0, nullptr, nullptr, cvec.data(), nullptr, nullptr,
+                                            nullptr, nullptr, nullptr) == C3D_ERR_INVALID;
                 if (what == 2) { unsigned long long a, b, d; ok = ok && c3d_debug_tear16(c, 4, &a, &b, &d) == C3D_OK; }
             }
             if (!ok) { fprintf(stderr, "api storm thread %d: %s\n", t, c3d_last_error()); ++failures; }

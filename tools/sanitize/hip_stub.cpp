@@ -529,4 +529,164 @@ hipError_t launch_accessibility(const double* xyz, int n, int K, const double* p
     return hipSuccess;
 }
 
+// c3d_compartments: the five launchers restated on the host with plain loops in index order (the definitions of include/c3d.h; no tiles,
+// no block reduction: the sums' orders are not the device's)
+static double stub_cpt_entry(const CptMaps& S, const double* Xb, int b, int i, int j) {
+    const int q = S.q0 + b, mi = q - S.has_if, n = S.n;
+    if (S.has_if && q == 0) return Xb[(size_t)i * n + j];
+    const int* pick = mi < S.n_models ? S.pick + mi : S.pick;
+    const int cnt = mi < S.n_models ? 1 : S.n_models;
+    double sum = 0.0;
+    for (int k = 0; k < cnt; ++k) sum += stub_dist(S.xyz + (size_t)pick[k] * 3 * n, i, j);
+    return sum / (double)cnt;
+}
+static void stub_cpt_sign_largest(double* v, int n) {
+    int at = 0;
+    for (int j = 1; j < n; ++j)
+        if (std::fabs(v[j]) > std::fabs(v[at])) at = j;
+    if (v[at] < 0.0)
+        for (int j = 0; j < n; ++j) v[j] = -v[j];
+}
+// out = X u - sub 1, one map
+static void stub_cpt_product(const double* X, int n, const double* u, double sub, double* out) {
+    for (int i = 0; i < n; ++i) {
+        double s = 0.0;
+        for (int j = 0; j < n; ++j) s += X[(size_t)i * n + j] * u[j];
+        out[i] = s - sub;
+    }
+}
+static void stub_cpt_take_y(const CptWork& w, int b, int n, int nv, double* out) {
+    for (int a = 0; a < nv; ++a) {
+        const double* W = w.W + ((size_t)b * nv + a) * n;
+        const double* P = w.P + ((size_t)b * nv + a) * n;
+        double s = 0.0;
+        for (int j = 0; j < n; ++j) s += W[j];
+        for (int j = 0; j < n; ++j) out[(size_t)a * n + j] = w.D[(size_t)b * n + j] * (P[j] - w.m[(size_t)b * n + j] * s) / (double)n;
+    }
+}
+hipError_t launch_compartment_if_check(const double* M, int n, int* flags, hipStream_t) {
+    LaunchScope ls;
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j) {
+            const double v = M[(size_t)i * n + j];
+            if (v != M[(size_t)j * n + i]) flags[0] |= 1;
+            if (!std::isfinite(v)) flags[0] |= 2;
+            if (v < 0.0) flags[0] |= 4;
+        }
+    return hipSuccess;
+}
+hipError_t launch_compartment_build(const CptMaps& S, const CptWork& w, int min_sep, hipStream_t) {
+    LaunchScope ls;
+    const int n = S.n;
+    for (int b = 0; b < S.nb; ++b) {
+        double* X = w.X + (size_t)b * n * n;
+        double* E = w.E + (size_t)b * n;
+        E[0] = 0.0;
+        for (int s = 1; s < n; ++s) {
+            double sum = 0.0;
+            for (int i = 0; i + s < n; ++i) sum += stub_cpt_entry(S, X, b, i, i + s);
+            E[s] = sum / (double)(n - s);
+        }
+        for (int i = 0; i < n; ++i) {
+            for (int j = i + 1; j < n; ++j) {
+                const double e = E[j - i];
+                X[(size_t)i * n + j] = X[(size_t)j * n + i] = j - i >= min_sep && e != 0.0 ? stub_cpt_entry(S, X, b, i, j) / e : 1.0;
+            }
+            X[(size_t)i * n + i] = 1.0;
+        }
+        for (int i = 0; i < n; ++i) {
+            double sum = 0.0, dev = 0.0;
+            for (int j = 0; j < n; ++j) sum += X[(size_t)i * n + j];
+            const double mean = sum / (double)n;
+            for (int j = 0; j < n; ++j) dev += (X[(size_t)i * n + j] - mean) * (X[(size_t)i * n + j] - mean);
+            const double q = sqrt(dev / (double)n);
+            w.m[(size_t)b * n + i] = mean;
+            w.D[(size_t)b * n + i] = q > 0.0 ? 1.0 / q : 0.0;
+        }
+    }
+    return hipSuccess;
+}
+hipError_t launch_compartment_round(const CptMaps& S, const CptWork& w, int nv, bool first, hipStream_t) {
+    LaunchScope ls;
+    const int n = S.n;
+    for (int b = 0; b < S.nb; ++b) {
+        double* V = w.V + (size_t)b * nv * n;
+        if (!first) stub_cpt_take_y(w, b, n, nv, V);
+        for (int a = 0; a < nv; ++a) {
+            double* va = V + (size_t)a * n;
+            for (int p = 0; p < a; ++p) {
+                const double* vp = V + (size_t)p * n;
+                double d = 0.0;
+                for (int j = 0; j < n; ++j) d += vp[j] * va[j];
+                for (int j = 0; j < n; ++j) va[j] -= d * vp[j];
+            }
+            double nn = 0.0;
+            for (int j = 0; j < n; ++j) nn += va[j] * va[j];
+            if (!(nn > 0.0)) w.flags[1] = 1;
+            const double norm = sqrt(nn);
+            for (int j = 0; j < n; ++j) va[j] /= norm;
+            double* u = w.U + ((size_t)b * nv + a) * n;
+            double c = 0.0;
+            for (int j = 0; j < n; ++j) { u[j] = w.D[(size_t)b * n + j] * va[j]; c += w.m[(size_t)b * n + j] * u[j]; }
+            w.c[(size_t)b * kCptVecs + a] = c;
+        }
+        for (int a = 0; a < nv; ++a) {
+            stub_cpt_product(w.X + (size_t)b * n * n, n, w.U + ((size_t)b * nv + a) * n, w.c[(size_t)b * kCptVecs + a], w.W + ((size_t)b * nv + a) * n);
+            stub_cpt_product(w.X + (size_t)b * n * n, n, w.W + ((size_t)b * nv + a) * n, 0.0, w.P + ((size_t)b * nv + a) * n);
+        }
+    }
+    return hipSuccess;
+}
+hipError_t launch_compartment_finish(const CptMaps& S, const CptWork& w, int nv, hipStream_t) {
+    LaunchScope ls;
+    const int n = S.n;
+    for (int b = 0; b < S.nb; ++b) {
+        double* V = w.V + (size_t)b * nv * n;
+        double* Y = w.U + (size_t)b * nv * n;
+        stub_cpt_take_y(w, b, n, nv, Y);
+        double live = 0.0;
+        for (int j = 0; j < n; ++j) live += w.D[(size_t)b * n + j] > 0.0 ? 1.0 : 0.0;
+        for (int a = 0; a < nv; ++a) {
+            double* va = V + (size_t)a * n;
+            const double* ya = Y + (size_t)a * n;
+            double lam = 0.0, res = 0.0;
+            for (int j = 0; j < n; ++j) lam += va[j] * ya[j];
+            for (int j = 0; j < n; ++j) res += (ya[j] - lam * va[j]) * (ya[j] - lam * va[j]);
+            w.stats[(size_t)b * kCptStats + a] = live > 0.0 ? lam / live : 0.0;
+            w.stats[(size_t)b * kCptStats + 3 + a] = sqrt(res);
+            if (!S.has_if || S.q0 + b == 0) stub_cpt_sign_largest(va, n);
+        }
+    }
+    return hipSuccess;
+}
+hipError_t launch_compartment_fit(const CptMaps& S, const CptWork& w, int nv, hipStream_t) {
+    LaunchScope ls;
+    const int n = S.n;
+    for (int b = 0; b < S.nb; ++b) {
+        if (S.q0 + b == 0) continue;
+        double* V = w.V + (size_t)b * nv * n;
+        for (int a = 0; a < nv; ++a) {
+            double* va = V + (size_t)a * n;
+            const double* fa = w.F + (size_t)a * n;
+            double d = 0.0, same = 0.0;
+            for (int j = 0; j < n; ++j) d += va[j] * fa[j];
+            if (d < 0.0) { for (int j = 0; j < n; ++j) va[j] = -va[j]; }
+            else if (!(d > 0.0)) stub_cpt_sign_largest(va, n);
+            for (int j = 0; j < n; ++j) same += va[j] * fa[j] > 0.0 ? 1.0 : 0.0;
+            w.stats[(size_t)b * kCptStats + 6 + a] = same / (double)n;
+        }
+        for (int a = 0; a < nv; ++a)
+            for (int f = 0; f < nv; ++f) {
+                const double* va = V + (size_t)a * n;
+                const double* ff = w.F + (size_t)f * n;
+                double sv = 0.0, sf = 0.0, sxy = 0.0, sxx = 0.0, syy = 0.0;
+                for (int j = 0; j < n; ++j) { sv += va[j]; sf += ff[j]; }
+                const double mv = sv / (double)n, mf = sf / (double)n;
+                for (int j = 0; j < n; ++j) { sxy += (va[j] - mv) * (ff[j] - mf); sxx += (va[j] - mv) * (va[j] - mv); syy += (ff[j] - mf) * (ff[j] - mf); }
+                w.stats[(size_t)b * kCptStats + 9 + 3 * a + f] = std::fabs(sxy / sqrt(sxx * syy));
+            }
+    }
+    return hipSuccess;
+}
+
 }  // namespace c3d
