@@ -92,23 +92,37 @@ __device__ __forceinline__ void sqrt_hrsqrt64(double r2, double& d, double& h) {
     d = fma(g, r, g); h = fma(h, r, h);
 }
 
-// 1 / x and sqrt(x) to a rounding or two (fp32 seed, two Newton steps each): the per-workgroup scalars; x > 0 (sqrt64: 0 allowed)
+// 1 / x and sqrt(x) to a rounding or two (fp32 seed, two Newton steps each): the per-workgroup scalars.  The seed is a float's: outside
+// 2^-120 <= x < 2^120 (where x and 1 / x are both normal floats) — a sum that underflowed, a zero, a negative number, an infinity, a
+// NaN — the operand takes the correctly rounded division / square root instead: a path no sane trajectory enters, but finite doubles
+// must not come out as NaN or on the wrong side of a bound (the seed of 1e-40 is inf and the Newton steps make NaN of it; that of 1e40 is
+// 0 and stays 0).  The range test is one addition and one unsigned compare on the high word (sign and exponent), and the branch is
+// the WAVE's (any lane outside: every lane computes the wide form, each keeps the one its operand asks for): one scalar branch on the
+// step kernels' critical path instead of two exec-mask regions (a per-lane branch cost 0.06 us of a 10.1 us step).
+__device__ __forceinline__ bool seed_range64(double x) {
+    return (unsigned)(__double_as_longlong(x) >> 32) - 0x38700000u < 0x0F000000u;      // biased exponents 903 .. 1142, sign 0
+}
 __device__ __forceinline__ double rcp64(double x) {
     double y = (double)__builtin_amdgcn_rcpf((float)x);
     double e = fma(-x, y, 1.0);
     y = fma(y, e, y);
     e = fma(-x, y, 1.0);
-    return fma(y, e, y);
+    y = fma(y, e, y);
+    const bool wide = !seed_range64(x);
+    if (__builtin_expect(__builtin_amdgcn_ballot_w64(wide) != 0, 0)) y = wide ? 1.0 / x : y;
+    return y;
 }
 __device__ __forceinline__ double sqrt64(double x) {
-    if (!(x > 0.0)) return 0.0;
     const double y = (double)__builtin_amdgcn_rsqf((float)x);
     double g = x * y, h = 0.5 * y;
     double r = fma(-g, h, 0.5);
     g = fma(g, r, g); h = fma(h, r, h);
     r = fma(-g, h, 0.5);
     g = fma(g, r, g); h = fma(h, r, h);
-    return fma(fma(-g, g, x), h, g);                // one more correction of g alone
+    g = fma(fma(-g, g, x), h, g);                   // one more correction of g alone
+    const bool wide = !seed_range64(x);
+    if (__builtin_expect(__builtin_amdgcn_ballot_w64(wide) != 0, 0)) g = wide ? __builtin_sqrt(x) : g;      // (0 -> 0, NaN -> NaN: the CPU restatement's sqrt)
+    return g;
 }
 
 // HALF of dE/dDelta of the NOE term without S and w.  GEN = tails with a 1/D^2 part.
@@ -621,6 +635,50 @@ __global__ void k64_lbfgs_direction(const Step64 p, const Fire64 fp, const int r
 hipError_t launch_lbfgs_direction64(const Step64& p, const Fire64& fp, int rows, const double* sums, const LbfgsState* in, const int* flags,
                                     LbfgsState* out, double* coef, int* shi, hipStream_t s) {
     hipLaunchKernelGGL(k64_lbfgs_direction, dim3((rows + 63) / 64), dim3(64), 0, s, p, fp, rows, sums, in, flags, out, coef, shi);
+    return hipGetLastError();
+}
+// The controller of k64_step as a table (c3d_debug_step_scalars_f64): c3d_f64_scalars.inc — the text wave 0 of every k64_step workgroup
+// runs on the replica's sums — a thread a row, on (psum[4], FireState64) as given whatever the kind.  out [rows][6] = lam, cm0 .. cm2, keep, mix.
+__global__ void k64_step_scalars(const Model64 m, const Step64 p, const Fire64 fp, const int rows, const double* __restrict__ psum,
+                                 const FireState64* __restrict__ sin, double* __restrict__ out, FireState64* __restrict__ sout) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= rows) return;
+    const double s0 = psum[4 * (size_t)r], s1 = psum[4 * (size_t)r + 1], s2 = psum[4 * (size_t)r + 2], s3 = psum[4 * (size_t)r + 3];
+    FireState64 st = sin[r];
+    {
+#define C3D_F64_STATE_OUT
+#include "c3d_f64_scalars.inc"
+#undef C3D_F64_STATE_OUT
+        double* o = out + 6 * (size_t)r;
+        o[0] = lam; o[1] = cm0; o[2] = cm1; o[3] = cm2; o[4] = keep; o[5] = mix;
+    }
+    sout[r] = st;
+}
+hipError_t launch_step_scalars64(const Model64& m, const Step64& p, const Fire64& fp, int rows, const double* psum, const void* in, double* scalars,
+                                 void* out, hipStream_t s) {
+    hipLaunchKernelGGL(k64_step_scalars, dim3((rows + 63) / 64), dim3(64), 0, s, m, p, fp, rows, psum, static_cast<const FireState64*>(in), scalars,
+                       static_cast<FireState64*>(out));
+    return hipGetLastError();
+}
+// The row update of k64_step as a table (c3d_debug_row_finish_f64): c3d_f64_row_finish.inc — the text lanes 0 and 1 of every k64_step wave
+// run on their row — a thread a row.  in [rows][16] = x0[3], v0[3], F[3], lam, cm0 .. cm2, keep, mix, st.dt; out [rows][10] = xn[3], vn[3], q0 .. q3.
+__global__ void k64_row_finish(const Step64 p, const Fire64 fp, const int rows, const double* __restrict__ in, double* __restrict__ out) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= rows) return;
+    const double* a = in + kRowFinish64In * (size_t)r;
+    const double x0 = a[0], y0 = a[1], z0 = a[2], v0x = a[3], v0y = a[4], v0z = a[5], Fx = a[6], Fy = a[7], Fz = a[8];
+    const double lam = a[9], cm0 = a[10], cm1 = a[11], cm2 = a[12], keep = a[13], mix = a[14];
+    FireState64 st;
+    st.dt = a[15]; st.alpha = 0.0; st.npos = 0; st.pad = 0;
+    double q0 = 0, q1 = 0, q2 = 0, q3 = 0;
+    {
+#include "c3d_f64_row_finish.inc"
+        double* o = out + kRowFinish64Out * (size_t)r;
+        o[0] = xn; o[1] = yn; o[2] = zn; o[3] = vx; o[4] = vy; o[5] = vz; o[6] = q0; o[7] = q1; o[8] = q2; o[9] = q3;
+    }
+}
+hipError_t launch_row_finish64(const Step64& p, const Fire64& fp, int rows, const double* in, double* out, hipStream_t s) {
+    hipLaunchKernelGGL(k64_row_finish, dim3((rows + 63) / 64), dim3(64), 0, s, p, fp, rows, in, out);
     return hipGetLastError();
 }
 // c3d_eval_f64's force in the step's form (p of kind 3), X[parity] -> Fout

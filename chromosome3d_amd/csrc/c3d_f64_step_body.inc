@@ -99,42 +99,9 @@
             for (int t = lane; t < m.ntiles; t += 64) { s0 += pp[4 * t]; s1 += pp[4 * t + 1]; s2 += pp[4 * t + 2]; s3 += pp[4 * t + 3]; }
             s0 = wave_sum64(s0); s1 = wave_sum64(s1); s2 = wave_sum64(s2); s3 = wave_sum64(s3);
         }
-        // (reciprocals and square roots by seed + two Newton steps, the constant factors folded on the host: the correctly rounded
-        //  divisions and sqrt of the straightforward form are ~230 dependent fp64 operations — a microsecond on every workgroup's
-        //  critical path, more than the launch boundary hides; these are a rounding or two away from them)
-        double lam = 1.0, cm0 = 0, cm1 = 0, cm2 = 0, keep = 0.0, mix = 0.0;
-        if (p.kind == 0 || p.kind == 1) {
-            double tprev = m.t_fac * s0;                // mass / kAccel / (ndf kBoltz) * sum v^2
-            if (tprev < 1e-2) tprev = 1e-2;
-            const double ratio = p.t_bath * rcp64(tprev);
-            if (p.kind == 0) { double l2 = 1.0 + p.dt * m.fbeta * (ratio - 1.0); if (l2 < 0) l2 = 0; lam = sqrt64(l2); }
-            else lam = sqrt64(ratio);
-            cm0 = s1 * m.inv_n; cm1 = s2 * m.inv_n; cm2 = s3 * m.inv_n;
-        } else if (p.kind == 2 || p.kind == 3) {
-            if (s0 > 0) {                               // power of the previous evaluation positive (kind 3: sums are 0)
-                keep = 1.0 - st.alpha;
-                mix = st.alpha * sqrt64(s2 * rcp64(s1 > 1e-30 ? s1 : 1e-30));
-                if (st.npos > fp.n_min) { st.dt = st.dt * fp.f_inc < fp.dt_max ? st.dt * fp.f_inc : fp.dt_max; st.alpha *= fp.f_alpha; }
-                st.npos += 1;
-            } else {
-                st.alpha = fp.alpha_start; st.dt *= fp.f_dec; st.npos = 0;
-            }
-            if (tile == 0 && lane == 0) sout[rep] = st;
-        } else if (p.kind == 5 || p.kind == 6) {        // two-point step size, the length one evaluation late (c3o_bb_step): lam = previous length, mix = this one
-            const int k = p.kind == 6 ? 0 : st.npos;
-            const double a_prev = st.dt;
-            double a = a_prev;
-            if (k == 0) a = fp.dt_start * fp.dt_start * p.kacc;
-            else if (k >= 2) {
-                if (s0 > 0) a = (k & 1) ? s0 * rcp64(s2) : s3 * rcp64(s0);
-                else a = 2.0 * a_prev;
-                if (!(a >= 1e-7)) a = 1e-7;
-                if (a > 1e2) a = 1e2;
-            }
-            lam = a_prev; mix = a;
-            st.dt = a; st.npos = k + 1;
-            if (tile == 0 && lane == 0) sout[rep] = st;
-        }
+#define C3D_F64_STATE_OUT if (tile == 0 && lane == 0) sout[rep] = st;
+#include "c3d_f64_scalars.inc"                  // the controller: lam, cm0 .. cm2, keep, mix, st from s0 .. s3 (one text with k64_step_scalars)
+#undef C3D_F64_STATE_OUT
         if (lane == 0) { scal[0] = lam; scal[1] = cm0; scal[2] = cm1; scal[3] = cm2; scal[4] = keep; scal[5] = mix; scal[6] = st.dt; }
     }
 #endif   // the mode's prologue
@@ -311,45 +278,7 @@
     if (lane < kRows64 && row < n) {
         const size_t ix = roff + row, iy = ix + np, iz = iy + np;
         const double x0 = rx[row], y0 = ry[row], z0 = rz[row];
-        double vx, vy, vz, xn, yn, zn;
-        if (p.kind == 4) {                              // MD begin: Maxwell velocities, no move
-            vx = v0x; vy = v0y; vz = v0z; xn = x0; yn = y0; zn = z0;
-            q0 = vx * vx + vy * vy + vz * vz; q1 = vx; q2 = vy; q3 = vz;
-        } else if (p.kind == 0 || p.kind == 1) {
-            const double acc = p.acc;
-            vx = lam * (v0x - cm0) + acc * Fx; vy = lam * (v0y - cm1) + acc * Fy; vz = lam * (v0z - cm2) + acc * Fz;
-            xn = x0 + p.dt * vx; yn = y0 + p.dt * vy; zn = z0 + p.dt * vz;
-            q0 = vx * vx + vy * vy + vz * vz; q1 = vx; q2 = vy; q3 = vz;
-        } else if (p.kind == 5 || p.kind == 6) {
-            const double ms2 = fp.max_step * fp.max_step;
-            auto clamp_scale = [&](double d2) {
-                double scl = 1.0;
-                if (d2 > ms2) { double dd, hh; sqrt_hrsqrt64(d2, dd, hh); hh = fma(fma(-dd, hh, 0.5), hh, hh); scl = fp.max_step * (hh + hh); }
-                return scl;
-            };
-            q1 = Fx * Fx + Fy * Fy + Fz * Fz;
-            if (p.kind == 5) {
-                double sx = lam * v0x, sy = lam * v0y, sz = lam * v0z;
-                const double scp = clamp_scale(sx * sx + sy * sy + sz * sz);
-                sx *= scp; sy *= scp; sz *= scp;
-                const double yx = v0x - Fx, yy = v0y - Fy, yz = v0z - Fz;
-                q0 = sx * yx + sy * yy + sz * yz; q2 = yx * yx + yy * yy + yz * yz; q3 = sx * sx + sy * sy + sz * sz;
-            }
-            const double dxs = mix * Fx, dys = mix * Fy, dzs = mix * Fz;
-            const double scl = clamp_scale(dxs * dxs + dys * dys + dzs * dzs);
-            xn = x0 + scl * dxs; yn = y0 + scl * dys; zn = z0 + scl * dzs;
-            vx = Fx; vy = Fy; vz = Fz;
-        } else {
-            q0 = v0x * Fx + v0y * Fy + v0z * Fz; q1 = Fx * Fx + Fy * Fy + Fz * Fz; q2 = v0x * v0x + v0y * v0y + v0z * v0z;
-            const double acc = st.dt * p.kacc;
-            vx = keep * v0x + mix * Fx; vy = keep * v0y + mix * Fy; vz = keep * v0z + mix * Fz;
-            vx += acc * Fx; vy += acc * Fy; vz += acc * Fz;
-            const double dxs = st.dt * vx, dys = st.dt * vy, dzs = st.dt * vz;
-            const double d2 = dxs * dxs + dys * dys + dzs * dzs;
-            double scl = 1.0;
-            if (d2 > fp.max_step * fp.max_step) { double dd, hh; sqrt_hrsqrt64(d2, dd, hh); hh = fma(fma(-dd, hh, 0.5), hh, hh); scl = fp.max_step * (hh + hh); }
-            xn = x0 + scl * dxs; yn = y0 + scl * dys; zn = z0 + scl * dzs;
-        }
+#include "c3d_f64_row_finish.inc"               // the update: xn, vn, q0 .. q3 (one text with k64_row_finish)
         xout[ix] = xn; xout[iy] = yn; xout[iz] = zn;
         vout[ix] = vx; vout[iy] = vy; vout[iz] = vz;
     }

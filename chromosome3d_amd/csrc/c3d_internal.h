@@ -358,6 +358,14 @@ hipError_t launch_eval_forces64(const DevModel& d, const Model64& m, const Step6
                                 hipStream_t s);
 hipError_t launch_energy64(const DevModel& d, const Model64& m, double rep_r2, const Buffers64& b, int parity, double* Eout, hipStream_t s);
 size_t fire_state64_bytes();
+// The fp64 controller and row update as tables, a thread a row (k64_step_scalars / k64_row_finish run the two texts k64_step includes,
+// c3d_f64_scalars.inc and c3d_f64_row_finish.inc; c3d_debug_step_scalars_f64 / c3d_debug_row_finish_f64).  State rows in / out are
+// fire_state64_bytes() each: (double dt, double alpha, int32 npos, int32 pad).  scalars [rows][6] = lam, cm0 .. cm2, keep, mix.
+// Row finish: in [rows][16] = x0[3], v0[3], F[3], lam, cm0 .. cm2, keep, mix, dt of the state; out [rows][10] = xn[3], vn[3], q0 .. q3.
+constexpr int kRowFinish64In = 16, kRowFinish64Out = 10;
+hipError_t launch_step_scalars64(const Model64& m, const Step64& p, const Fire64& fp, int rows, const double* psum, const void* in, double* scalars,
+                                 void* out, hipStream_t s);
+hipError_t launch_row_finish64(const Step64& p, const Fire64& fp, int rows, const double* in, double* out, hipStream_t s);
 // K1: IF (n*n fp64, device) -> dist10 (n*n int32, device) and encoded targets (n*npad, device)
 hipError_t launch_if_to_target(const double* IF, int n, int npad, double alpha, double K, int min_sep, int rep_sep,
                                double* scratchP, double* partial, int npartial, int32_t* dist10, float* tgt,

@@ -578,6 +578,64 @@ extern "C" int c3d_debug_step_scalars(c3d_ctx* c, int kind, float dt, float t_ba
     return C3D_OK;
 }
 
+// Test hooks: the fp64 controller (c3d_f64_scalars.inc) and the fp64 row update (c3d_f64_row_finish.inc) on tables of rows (c3d.h).
+// Model64 / Step64 / Fire64 come from the builders every fp64 launch uses, so the tables also cover t_fac, inv_n, acc and kacc as the host
+// forms them.  The stage weights of the Step64 (1, 1, 0.85) enter neither text.
+namespace {
+struct FireRow64 { double dt, alpha; int32_t npos, pad; };       // a FireState64 (c3d_f64.hip) as the host packs it
+bool f64_table_kind(int kind, bool row_finish) {
+    return kind == 0 || kind == 1 || kind == 2 || kind == 3 || kind == 5 || kind == 6 || (row_finish && kind == 4);
+}
+}  // namespace
+extern "C" int c3d_debug_step_scalars_f64(c3d_ctx* c, int kind, double dt, double t_bath, int rows, const double* psum, const double* state_in,
+                                          const int32_t* npos_in, double* scalars, double* state_out, int32_t* npos_out) {
+    if (!c || !psum || !state_in || !npos_in || !scalars || !state_out || !npos_out)
+        return fail(C3D_ERR_INVALID, "c3d_debug_step_scalars_f64: bad arguments");
+    if (rows < 1 || rows > (1 << 20)) return fail(C3D_ERR_INVALID, "c3d_debug_step_scalars_f64: rows is 1 .. 2^20");
+    if (!f64_table_kind(kind, false)) return fail(C3D_ERR_INVALID, "c3d_debug_step_scalars_f64: kind is 0, 1, 2, 3, 5 or 6");
+    if (c->precision != 64) return fail(C3D_ERR_INVALID, "c3d_debug_step_scalars_f64: the context's precision is not 64");
+    if (c->n < 1) return fail(C3D_ERR_INVALID, "c3d_debug_step_scalars_f64: set the targets first (the bead count enters the temperature)");
+    if (sizeof(FireRow64) != c3d::fire_state64_bytes()) return fail(C3D_ERR_INVALID, "c3d_debug_step_scalars_f64: the state's layout is not the one this entry packs");
+    C3D_ENTRY(c, unit_bit(UNIT_F64));
+    std::vector<FireRow64> st((size_t)rows);
+    for (int r = 0; r < rows; ++r) st[r] = FireRow64{state_in[2 * r], state_in[2 * r + 1], npos_in[r], 0};
+    DevTmp<double> d_psum, d_out;
+    DevTmp<FireRow64> d_in, d_st;
+    HIP_TRY(hipMalloc(&d_psum.p, sizeof(double) * 4 * (size_t)rows));
+    HIP_TRY(hipMalloc(&d_out.p, sizeof(double) * 6 * (size_t)rows));
+    HIP_TRY(hipMalloc(&d_in.p, sizeof(FireRow64) * (size_t)rows));
+    HIP_TRY(hipMalloc(&d_st.p, sizeof(FireRow64) * (size_t)rows));
+    HIP_TRY(hipMemcpyAsync(d_psum.p, psum, sizeof(double) * 4 * (size_t)rows, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_in.p, st.data(), sizeof(FireRow64) * (size_t)rows, hipMemcpyHostToDevice, c->stream));
+    const c3d::Model64 m64 = c3d::model64(dev_model(c), c->model);
+    LAUNCH_TRY("fp64 step scalars launch", c3d::launch_step_scalars64(m64, c3d::step64(m64, kind, dt, 1.0, 1.0, 0.85, t_bath), c3d::fire64(c->fire), rows,
+                                                                     d_psum.p, d_in.p, d_out.p, d_st.p, c->stream));
+    HIP_TRY(hipMemcpyAsync(scalars, d_out.p, sizeof(double) * 6 * (size_t)rows, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(st.data(), d_st.p, sizeof(FireRow64) * (size_t)rows, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int r = 0; r < rows; ++r) { state_out[2 * r] = st[r].dt; state_out[2 * r + 1] = st[r].alpha; npos_out[r] = st[r].npos; }
+    return C3D_OK;
+}
+static_assert(C3D_ROW_FINISH_IN == c3d::kRowFinish64In && C3D_ROW_FINISH_OUT == c3d::kRowFinish64Out, "c3d.h states the row table's sizes");
+extern "C" int c3d_debug_row_finish_f64(c3d_ctx* c, int kind, double dt, int rows, const double* in, double* out) {
+    if (!c || !in || !out) return fail(C3D_ERR_INVALID, "c3d_debug_row_finish_f64: bad arguments");
+    if (rows < 1 || rows > (1 << 20)) return fail(C3D_ERR_INVALID, "c3d_debug_row_finish_f64: rows is 1 .. 2^20");
+    if (!f64_table_kind(kind, true)) return fail(C3D_ERR_INVALID, "c3d_debug_row_finish_f64: kind is 0, 1, 2, 3, 4, 5 or 6");
+    if (c->precision != 64) return fail(C3D_ERR_INVALID, "c3d_debug_row_finish_f64: the context's precision is not 64");
+    if (c->n < 1) return fail(C3D_ERR_INVALID, "c3d_debug_row_finish_f64: set the targets first (the model is built for a bead count)");
+    C3D_ENTRY(c, unit_bit(UNIT_F64));
+    DevTmp<double> d_in, d_out;
+    HIP_TRY(hipMalloc(&d_in.p, sizeof(double) * C3D_ROW_FINISH_IN * (size_t)rows));
+    HIP_TRY(hipMalloc(&d_out.p, sizeof(double) * C3D_ROW_FINISH_OUT * (size_t)rows));
+    HIP_TRY(hipMemcpyAsync(d_in.p, in, sizeof(double) * C3D_ROW_FINISH_IN * (size_t)rows, hipMemcpyHostToDevice, c->stream));
+    const c3d::Model64 m64 = c3d::model64(dev_model(c), c->model);
+    LAUNCH_TRY("fp64 row finish launch", c3d::launch_row_finish64(c3d::step64(m64, kind, dt, 1.0, 1.0, 0.85, 0.0), c3d::fire64(c->fire), rows, d_in.p,
+                                                                 d_out.p, c->stream));
+    HIP_TRY(hipMemcpyAsync(out, d_out.p, sizeof(double) * C3D_ROW_FINISH_OUT * (size_t)rows, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return C3D_OK;
+}
+
 // Test hook: the serial section of the L-BFGS move (c3d_lbfgs_serial.inc) on a table of rows (c3d.h) — k_lbfgs_direction, or
 // k64_lbfgs_direction on a precision-64 context.  DevModel / DevFire, Step64 / Fire64 come from the functions every launch uses, so the
 // first step's gamma is formed from what the host folds into them (acc, kacc).

@@ -218,6 +218,27 @@ class Solver:
                                                 _l.fptr(sc), _l.fptr(so), _l.i32ptr(no)))
         return sc, so, no
 
+    def debug_step_scalars_f64(self, kind, dt, t_bath, psum, state, npos):
+        """The fp64 step controller as a table (c3d_debug_step_scalars_f64, precision-64 contexts): debug_step_scalars in doubles."""
+        psum, state = np.ascontiguousarray(psum, dtype=np.float64), np.ascontiguousarray(state, dtype=np.float64)
+        npos = np.ascontiguousarray(npos, dtype=np.int32)
+        K = npos.shape[0]
+        assert psum.shape == (K, 4) and state.shape == (K, 2)
+        sc, so, no = np.empty((K, 6), dtype=np.float64), np.empty((K, 2), dtype=np.float64), np.empty(K, dtype=np.int32)
+        _l.check(self._L.c3d_debug_step_scalars_f64(self._h, int(kind), float(dt), float(t_bath), K, _l.dptr(psum), _l.dptr(state),
+                                                    _l.i32ptr(npos), _l.dptr(sc), _l.dptr(so), _l.i32ptr(no)))
+        return sc, so, no
+
+    def debug_row_finish_f64(self, kind, dt, rows):
+        """The fp64 row update as a table (c3d_debug_row_finish_f64, precision-64 contexts): rows [K, 16] = x[3], v[3], F[3], lambda,
+        v_cm[3], keep, mix, state dt -> [K, 10] = new x[3], new v[3], the bead's terms of the four sums."""
+        rows = np.ascontiguousarray(rows, dtype=np.float64)
+        K = rows.shape[0]
+        assert rows.shape == (K, _l.ROW_FINISH_IN)
+        out = np.empty((K, _l.ROW_FINISH_OUT), dtype=np.float64)
+        _l.check(self._L.c3d_debug_row_finish_f64(self._h, int(kind), float(dt), K, _l.dptr(rows), _l.dptr(out)))
+        return out
+
     def debug_lbfgs_direction(self, sums, state_int, state_dbl, first, mem0):
         """The serial section of the L-BFGS move as a table (c3d_debug_lbfgs_direction), in the context's precision: sums [K, 36], state_int
         [K, 4] = (cnt, head, mem, resets), state_dbl [K, 129] = (gamma, S'Y [8, 8], Y'Y [8, 8]), first [K], mem0 [K] -> (state_int out,

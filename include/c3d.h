@@ -346,6 +346,22 @@ int c3d_debug_tear16(c3d_ctx* ctx, int iterations, unsigned long long* unit_read
  * touches nothing of the solve. */
 int c3d_debug_step_scalars(c3d_ctx* ctx, int kind, float dt, float t_bath, int rows, const float* psum, const float* state_in,
                            const int32_t* npos_in, float* scalars, float* state_out, int32_t* npos_out);
+/* Test hooks: the fp64 step controller and the fp64 row update as tables (precision-64 contexts only; every value crosses in doubles, the
+ * state's counter as int32_t).  The statements run are the two source texts every k64_step kernel includes, a thread a row, under the
+ * context's own model and FIRE values as the fp64 path derives them (t_fac, 1 / n, dt 418.4 / mass, 418.4 / mass).
+ * c3d_debug_step_scalars_f64: kinds and rows as c3d_debug_step_scalars — psum[4 r ..], state_in[2 r ..] = (dt, alpha), npos_in[r] ->
+ * scalars[6 r ..] = (lambda, v_cm x, y, z, keep, mix), state_out[2 r ..], npos_out[r].
+ * c3d_debug_row_finish_f64: one bead's update of a step of `kind` (0 / 1 MD with the stage's dt, 4 MD begin, 2 / 3 FIRE, 5 / 6 two-point).
+ * Row r in: in[16 r ..] = x[3], v[3] (kinds 5: the force of the previous evaluation; 4: the Maxwell velocity), F[3], lambda, v_cm[3], keep,
+ * mix, dt of the FIRE state — the scalars as c3d_debug_step_scalars_f64 returns them.  Row r out: out[10 r ..] = new x[3], new v[3], the
+ * bead's terms of the four sums the next step reads.
+ * Both refuse (C3D_ERR_INVALID) a context whose precision is not 64, other kinds, rows outside 1 .. 2^20; both need the bead count
+ * (targets set) and touch nothing of the solve. */
+#define C3D_ROW_FINISH_IN 16
+#define C3D_ROW_FINISH_OUT 10
+int c3d_debug_step_scalars_f64(c3d_ctx* ctx, int kind, double dt, double t_bath, int rows, const double* psum, const double* state_in,
+                               const int32_t* npos_in, double* scalars, double* state_out, int32_t* npos_out);
+int c3d_debug_row_finish_f64(c3d_ctx* ctx, int kind, double dt, int rows, const double* in, double* out);
 /* Test hook: the serial section of an L-BFGS move (stage kind 8) as a table.  Between its two barriers one thread of every workgroup of
  * the move kernel decides the step from the replica's sums: the pair test s.y > 1e-12 sqrt(s.s y.y), the ring of lbfgs_memory slots,
  * gamma (s.y / y.y after a kept pair, doubled after a rejected one, clamped to [1e-7, 1e2]), the two triangular solves of the compact form

@@ -4,6 +4,9 @@ margin, on a trajectory float32 can follow.  The forces are the oracle's own (O.
 (O.init_velocities); the statements around them are restated here one for one, so that each can be MUTATED: a case is only worth running
 on the GPU if a subtly wrong controller would end far from it (MUTATIONS, tests/test_controller_ref.py).
 
+The last two sections restate the controller as TABLES (one row of sums and state in, the step's scalars out; one bead in, its update
+out): step_scalars_ref for the fp32 and fp64 controllers, row_finish_ref for the fp64 row update, with the rows the GPU tests run.
+
 branch names   fire: reset | hold | grow | cap        (power test failed | npos <= n_min | dt grows | dt held at dt_max)
                md:   plain | floor | clamp0           (T floored at 1e-2 | Berendsen lambda^2 clamped at 0; both: floor+clamp0)
                bb:   first | bb | negcurv, + "+lo" / "+hi" where the length was bounded by 1e-7 / 1e2
@@ -344,22 +347,36 @@ LBFGS_MEMORY = 3
 F32 = np.float32
 
 
-def step_scalars_ref(kind, dt, t_bath, psum, state, npos, consts, fire):
-    """One row of c3d_debug_step_scalars.  psum (4), state (dt, alpha), npos: the row; consts = (t_fac, inv_n, acc, fbeta) as the host holds
-    them (floats, widened); fire = c3d_fire_params.  Every constant of the oracle that the device holds as a float (1e-2, 1e-30, 1e-7, 1e2)
-    is that float.  Returns ((lambda, cmx, cmy, cmz, keep, mix), (dt, alpha), npos) in float64 — the statements of c3o_md_step,
-    c3o_fire_step and c3o_bb_step that decide a step, with their comparisons as the oracle writes them (a NaN fails every one)."""
-    t_fac, inv_n, acc, fbeta = (float(a) for a in consts)
+def step_scalars_ref(kind, dt, t_bath, psum, state, npos, consts, fire, precision=32, mut=None, hits=None):
+    """One row of c3d_debug_step_scalars (precision 32) or c3d_debug_step_scalars_f64 (64).  psum (4), state (dt, alpha), npos: the row;
+    consts = (t_fac, inv_n, acc, fbeta) as the host holds them (precision 32: floats, widened, table_consts; 64: doubles formed as
+    model64 / step64 form them, table_consts64); fire = c3d_fire_params (floats, widened).  The oracle's constants 1e-2, 1e-30, 1e-7, 1e2
+    are the floats the fp32 device holds, or the doubles themselves.  Returns ((lambda, cmx, cmy, cmz, keep, mix), (dt, alpha), npos) in
+    float64 — the statements of c3o_md_step, c3o_fire_step and c3o_bb_step that decide a step, one correctly rounded operation per oracle
+    operation, with their comparisons as the oracle writes them (a NaN fails every one).  mut: one name of TABLE_MUTATIONS; hits: a
+    Counter that receives the name of every branch the row takes."""
+    t_fac, inv_n, acc, fbeta = (float(a) for a in consts[:4])
+    c = (lambda v: float(F32(v))) if precision == 32 else float
     p = [float(a) for a in psum]
     sdt, alpha = float(state[0]), float(state[1])
     lam, cm, keep, mix = 1.0, [0.0, 0.0, 0.0], 0.0, 0.0
+
+    def hit(name):
+        if hits is not None:
+            hits[name] += 1
+
     with np.errstate(all="ignore"):
         if kind in (0, 1):
             tprev = t_fac * p[0]
-            if tprev < float(F32(1e-2)):
-                tprev = float(F32(1e-2))
+            hit("T_at_floor" if tprev == c(1e-2) else ("T_below_floor" if tprev < c(1e-2) else "T_above_floor"))
+            if tprev < c(1e-2):
+                tprev = c(1e-2)
             if kind == 0:
-                l2 = 1.0 + float(F32(dt) * F32(fbeta)) * (t_bath / tprev - 1.0)
+                dtfb = float(F32(dt) * F32(fbeta)) if precision == 32 else dt * fbeta
+                l2 = 1.0 + dtfb * (float(np.float64(t_bath) / tprev) - 1.0)
+                hit("l2_at_0" if l2 == 0 else ("l2_below_0" if l2 < 0 else "l2_above_0"))
+                if mut == "sqrt_abs_clamp":
+                    l2 = abs(l2)
                 lam = float(np.sqrt(np.float64(l2 if l2 >= 0 else 0.0)))
             else:
                 lam = float(np.sqrt(np.float64(t_bath) / tprev))
@@ -370,28 +387,48 @@ def step_scalars_ref(kind, dt, t_bath, psum, state, npos, consts, fire):
             a = a_prev
             if k == 0:
                 a = float(fire.dt_start) ** 2 * acc
+                hit("bb_first")
             elif k >= 2:
                 sy = p[0]
+                hit("bb_sy_nan" if sy != sy else ("bb_sy_zero" if sy == 0 else ("bb_sy_pos" if sy > 0 else "bb_sy_neg")))
                 if sy > 0:
-                    a = float(np.float64(p[3]) / sy) if k % 2 == 0 else float(np.float64(sy) / np.float64(p[2]))
+                    even = (k % 2 == 0) != (mut == "bb_parity_swapped")
+                    hit("bb_even" if k % 2 == 0 else "bb_odd")
+                    a = float(np.float64(p[3]) / sy) if even else float(np.float64(sy) / np.float64(p[2]))
                 else:
                     a = 2.0 * a_prev
-                if not (a >= float(F32(1e-7))):
-                    a = float(F32(1e-7))
+                    hit("bb_negcurv")
+                if (a < c(1e-7)) if mut == "lo_lt" else (not (a >= c(1e-7))):
+                    hit("bb_lo_nan" if a != a else "bb_lo")
+                    a = c(1e-7)
                 if a > 1e2:
                     a = 1e2
+                    hit("bb_hi")
+            else:
+                hit("bb_second")
             lam, mix, sdt, npos = a_prev, a, a, k + 1
         else:
+            hit("fire_vf_nan" if p[0] != p[0] else ("fire_vf_zero" if p[0] == 0 else ("fire_vf_pos" if p[0] > 0 else "fire_vf_neg")))
             if p[0] > 0:
                 keep = 1.0 - alpha
-                mix = alpha * float(np.sqrt(np.float64(p[2]) / (p[1] if p[1] > float(F32(1e-30)) else float(F32(1e-30)))))
-                if npos > fire.n_min:
+                hit("fire_ff_floor" if not (p[1] > c(1e-30)) else "fire_ff")
+                if p[1] == c(1e-30):
+                    hit("fire_ff_at_floor")
+                mix = alpha * float(np.sqrt(np.float64(p[2]) / (p[1] if p[1] > c(1e-30) else c(1e-30))))
+                hit("npos_at_nmin" if npos == fire.n_min else ("npos_below_nmin" if npos < fire.n_min else "npos_above_nmin"))
+                if (npos >= fire.n_min) if mut == "nmin_ge" else (npos > fire.n_min):
                     grown = sdt * float(fire.f_inc)
-                    sdt = grown if grown < float(fire.dt_max) else float(fire.dt_max)
+                    hit("dt_at_max" if grown == float(fire.dt_max) else ("dt_grow" if grown < float(fire.dt_max) else "dt_cap"))
+                    sdt = grown if (grown < float(fire.dt_max) or mut == "no_dt_max") else float(fire.dt_max)
                     alpha *= float(fire.f_alpha)
                 npos += 1
             else:
-                alpha, sdt, npos = float(fire.alpha_start), sdt * float(fire.f_dec), 0
+                hit("fire_reset")
+                if mut != "reset_keeps_alpha":
+                    alpha = float(fire.alpha_start)
+                if mut != "reset_keeps_dt":
+                    sdt = sdt * float(fire.f_dec)
+                npos = 0
     return (lam, cm[0], cm[1], cm[2], keep, mix), (sdt, alpha), npos
 
 
@@ -435,4 +472,293 @@ def table_rows(kind, t_fac):
                 for sy, yy, ss in ((2.0, 5.0, 3.0), (2.0, 5e9, 3e-9), (2.0, 1e-3, 9e2), (0.0, 5.0, 3.0), (-0.0, 5.0, 3.0), (-1.5, 5.0, 3.0),
                                    (nan, 5.0, 3.0), (2.0, nan, nan), (2.0, 0.0, 3.0), (1e-30, 5.0, 3.0)):
                     rows.append((0.0, 0.0, (sy, 11.0, yy, ss), (a_prev, 0.2), npos))
+    return rows
+
+
+# ---------------------------------------------------------------------------------------------
+# the fp64 controller and the fp64 row update as tables (c3d_debug_step_scalars_f64, c3d_debug_row_finish_f64)
+# ---------------------------------------------------------------------------------------------
+# name -> what the mutated restatement does differently (tests/test_controller_ref.py: each moves some row by >= 1000 double ulps or an integer)
+TABLE_MUTATIONS = {
+    "nmin_ge": "the n_min gate reads npos >= n_min",
+    "no_dt_max": "dt grows without the dt_max cap",
+    "reset_keeps_dt": "an uphill reset leaves dt as it was",
+    "reset_keeps_alpha": "an uphill reset leaves alpha as it was",
+    "bb_parity_swapped": "the two two-point lengths on each other's parity",
+    "lo_lt": "the lower bound reads a < 1e-7 (a NaN length passes)",
+    "cap_ge": "the per-bead cap reads d2 >= max_step^2",
+    "cap_no_sqrt": "the cap scales by max_step / d2",
+    "sqrt_abs_clamp": "lambda = sqrt(|lambda^2|) instead of the clamp at 0",
+    "no_cm": "the centre-of-mass velocity is not subtracted",
+}
+SCALAR_KINDS, ROW_KINDS = (0, 1, 2, 3, 5, 6), (0, 1, 2, 3, 4, 5, 6)
+NAN = float("nan")
+
+
+def table_consts64(m, n):
+    """(t_fac, inv_n, kacc, fbeta, mass) as model64 / step64 form them: doubles from the model's floats"""
+    ndf = 3 * n - 3
+    mass = float(m.mass)
+    return (mass / 418.4 / ((ndf if ndf > 0 else 1) * 0.0019872), 1.0 / n, 418.4 / mass, float(m.fbeta), mass)
+
+
+def ulps(got, want):
+    """|got - want| in units of the spacing of doubles at want (inf where one of them is not finite and they differ)"""
+    if got == want:
+        return 0.0
+    if not (np.isfinite(got) and np.isfinite(want)):
+        return float("inf")
+    return abs(got - want) / float(np.spacing(np.float64(abs(want))))
+
+
+def _next(x, up=True):
+    return float(np.nextafter(np.float64(x), np.float64(np.inf if up else -np.inf)))
+
+
+def _floor_edge(t_fac):
+    """sum v^2 one double below, at, and one double above the place where t_fac * x is the double 1e-2"""
+    x = 1e-2 / t_fac
+    while t_fac * x > 1e-2:
+        x = _next(x, False)
+    while t_fac * x < 1e-2:
+        x = _next(x)
+    assert t_fac * x == 1e-2
+    lo = x
+    while t_fac * lo == 1e-2:
+        lo = _next(lo, False)
+    hi = x
+    while t_fac * hi == 1e-2:
+        hi = _next(hi)
+    return lo, x, hi
+
+
+def table_rows64(kind, t_fac):
+    """[(dt, t_bath, psum, state, npos)] of a kind for the fp64 controller: table_rows' grid with every "one float either side" one double
+    either side, and the rows on which a reciprocal or square root seeded in float can go wrong (sums and ratios outside float's range)."""
+    rows = []
+    if kind in (0, 1):
+        lo, at, hi = _floor_edge(t_fac)
+        xs = [0.0, 0.5 * at, lo, at, hi, 2.0 * at, 300.0 / t_fac, 3.0e4 * at, 1e30 / t_fac, 1e37 / t_fac]
+        for dt in (2.0 ** -9, 2.0 ** -8, 3 * 2.0 ** -9):                # dt fbeta = 1/2, 1, 3/2: lambda^2 at t_bath 0 = 1/2, 0, -1/2
+            for t_bath in ((0.0, 300.0, 2000.0) if kind == 0 else (0.0, 0.02, 300.0)):
+                for x in xs:
+                    if kind == 0 and 0.0 < t_bath < t_fac * x * 1.001:   # cooling towards lambda^2 = 0 cancels: no ulp bound holds
+                        continue
+                    rows.append((dt, t_bath, (x, 0.37 * (1 + len(rows) % 5), -1.25, 0.0), (0.01, 0.1), 4))
+    elif kind in (2, 3):
+        at = 0.03125                                                     # dt f_inc = dt_max
+        for vf in (3.0, 1e-30, 5e-324, 0.0, -0.0, -2.5, NAN):
+            for npos in (2, 3, 4):                                       # n_min - 1, n_min, n_min + 1
+                for sdt in (0.03, _next(at, False), at, _next(at), 0.04):
+                    for ff, vv in ((7.0, 0.3), (0.0, 0.3), (1e-35, 1e-20), (7.0, 0.0)):
+                        rows.append((0.0, 0.0, (vf, ff, vv, 0.0), (sdt, 0.3 * 0.875 ** (npos % 3)), npos))
+        rows.append((0.0, 0.0, (3.0, NAN, 0.3, 0.0), (0.03, 0.3), 4))
+        rows.append((0.0, 0.0, (3.0, 7.0, NAN, 0.0), (0.03, 0.3), 4))
+        # v.v / F.F outside float's range, by a sum that is itself outside it and by two that are inside
+        for ratio in (1e-36, 1e-40, 1e-300, 1e36, 1e40):
+            r2 = float(np.sqrt(ratio))
+            for ff, vv in ((1.0, ratio), (1.0 / r2, r2), (3e-29, 3e-29 * ratio)):
+                rows.append((0.0, 0.0, (3.0, ff, vv, 0.0), (0.03, 0.3), 4))
+        for ff in (_next(1e-30, False), 1e-30, _next(1e-30)):            # F.F at the floor
+            rows.append((0.0, 0.0, (3.0, ff, 0.3, 0.0), (0.03, 0.3), 4))
+    else:
+        for npos in (0, 1, 2, 3, 7, 8):
+            for a_prev in (1e-5, 3e-8, 80.0):                            # the doubling leaves [1e-7, 1e2] on both sides
+                for sy, yy, ss in ((2.0, 5.0, 3.0), (2.0, 5e9, 3e-9), (2.0, 1e-3, 9e2), (0.0, 5.0, 3.0), (-0.0, 5.0, 3.0), (-1.5, 5.0, 3.0),
+                                   (NAN, 5.0, 3.0), (2.0, NAN, NAN), (2.0, 0.0, 3.0), (1e-30, 5.0, 3.0)):
+                    rows.append((0.0, 0.0, (sy, 11.0, yy, ss), (a_prev, 0.2), npos))
+        for npos in (2, 3):
+            for sy in (1e-30, 1e-37, 1e-40, 1e-300, 5e-324):             # s.y below float's range: s.s / s.y is the upper bound's side
+                rows.append((0.0, 0.0, (sy, 11.0, 5.0, 3.0), (1e-5, 0.2), npos))
+            for yy in (1e-40, 1e-300):
+                rows.append((0.0, 0.0, (2.0, 11.0, yy, 3.0), (1e-5, 0.2), npos))
+            # lengths at both bounds and one double either side: s.y / y.y with y.y = 1, s.s / s.y with s.y = 1
+            for a in (_next(1e-7, False), 1e-7, _next(1e-7), _next(1e2, False), 1e2, _next(1e2)):
+                rows.append((0.0, 0.0, (a, 11.0, 1.0, a * a), (1e-5, 0.2), npos) if npos % 2 else (0.0, 0.0, (1.0, 11.0, 1.0, a), (1e-5, 0.2), npos))
+    return rows
+
+
+def row_finish_ref(kind, dt, row, consts, fire, mut=None, hits=None):
+    """One row of c3d_debug_row_finish_f64: the per-bead statements of c3o_md_step, c3o_fire_step and c3o_bb_step (oracle/c3d_oracle.c) and the
+    bead's terms of the four sums the next step reads, in float64, one correctly rounded operation per oracle operation.  row (16) = x[3], v[3],
+    F[3], lambda, cm[3], keep, mix, state dt; consts = table_consts64 (acc = dt 418.4 / mass and dt_state (418.4 / mass) as step64 and the
+    kernel form them).  Returns [x'[3], v'[3], q[4]].  mut: one name of TABLE_MUTATIONS; hits: a Counter of the branches taken."""
+    kacc, mass = float(consts[2]), float(consts[4])
+    r = [float(a) for a in row]
+    x, v, F = r[0:3], r[3:6], r[6:9]
+    lam, cm, keep, mix, sdt = r[9], r[10:13], r[13], r[14], r[15]
+    ms = float(fire.max_step)
+    ms2 = ms * ms
+
+    def hit(name):
+        if hits is not None:
+            hits[name] += 1
+
+    def cap(d, which):
+        d2 = d[0] * d[0] + d[1] * d[1] + d[2] * d[2]
+        over = (d2 >= ms2) if mut == "cap_ge" else (d2 > ms2)
+        hit(which + ("_at_cap" if d2 == ms2 else ("_capped" if d2 > ms2 else "_uncapped")))
+        if not over:
+            return 1.0
+        hit(which + "_acted")                       # (an integer of the row: the only place ">=" for ">" at the cap shows — the scale there is 1)
+        return float(np.float64(ms) / (np.float64(d2) if mut == "cap_no_sqrt" else np.sqrt(np.float64(d2))))
+
+    with np.errstate(all="ignore"):
+        if kind == 4:
+            hit("md_begin")
+            vn, xn = list(v), list(x)
+            q = [vn[0] * vn[0] + vn[1] * vn[1] + vn[2] * vn[2], vn[0], vn[1], vn[2]]
+        elif kind in (0, 1):
+            hit("md")
+            acc = dt * 418.4 / mass
+            vn = [lam * ((v[k] - cm[k]) if mut != "no_cm" else v[k]) + acc * F[k] for k in range(3)]
+            xn = [x[k] + dt * vn[k] for k in range(3)]
+            q = [vn[0] * vn[0] + vn[1] * vn[1] + vn[2] * vn[2], vn[0], vn[1], vn[2]]
+        elif kind in (5, 6):
+            q = [0.0, F[0] * F[0] + F[1] * F[1] + F[2] * F[2], 0.0, 0.0]
+            if kind == 5:
+                s = [lam * v[k] for k in range(3)]
+                sc = cap(s, "s")
+                s = [a * sc for a in s]
+                y = [v[k] - F[k] for k in range(3)]
+                q[0] = s[0] * y[0] + s[1] * y[1] + s[2] * y[2]
+                q[2] = y[0] * y[0] + y[1] * y[1] + y[2] * y[2]
+                q[3] = s[0] * s[0] + s[1] * s[1] + s[2] * s[2]
+            dr = [mix * F[k] for k in range(3)]
+            sc = cap(dr, "move")
+            xn = [x[k] + sc * dr[k] for k in range(3)]
+            vn = list(F)
+        else:
+            q = [v[0] * F[0] + v[1] * F[1] + v[2] * F[2], F[0] * F[0] + F[1] * F[1] + F[2] * F[2], v[0] * v[0] + v[1] * v[1] + v[2] * v[2], 0.0]
+            acc = sdt * kacc
+            vn = [keep * v[k] + mix * F[k] for k in range(3)]
+            vn = [vn[k] + acc * F[k] for k in range(3)]
+            dr = [sdt * vn[k] for k in range(3)]
+            sc = cap(dr, "move")
+            xn = [x[k] + sc * dr[k] for k in range(3)]
+    return xn + vn + q
+
+
+_U = (0.6, -0.64, 0.48)                     # the direction of the tuned rows: every component in play, |u| = 1 to a rounding
+_X0 = (1.5, -2.5, 3.5)                      # coordinates on the displacement's side of 0: x + (capped move) does not cancel
+
+
+def _bisect(fn, lo, hi, target):
+    """the double z in [lo, hi] (positive, fn non-decreasing there) with fn(z) == target"""
+    a, b = int(np.float64(lo).view(np.int64)), int(np.float64(hi).view(np.int64))
+    assert fn(lo) < target <= fn(hi), (fn(lo), target, fn(hi))
+    while b - a > 1:
+        mid = (a + b) // 2
+        if fn(float(np.int64(mid).view(np.float64))) >= target:
+            b = mid
+        else:
+            a = mid
+    z = float(np.int64(b).view(np.float64))
+    assert fn(z) == target, (fn(z), target)
+    return z
+
+
+def _d2(d):
+    return d[0] * d[0] + d[1] * d[1] + d[2] * d[2]
+
+
+def row_finish_rows(kind, dt, consts, fire):
+    """[(row16, tag)] of a kind for c3d_debug_row_finish_f64.  tag: "plain" (no cap acted: products and sums) or "capped".
+    The capped quantity of a kind (FIRE: dt v'; two-point: mix F, and lambda v of the previous move) is put at max_step^2 and one double
+    either side by a search on one component, and at 0, 1e-300, 4 and 1e16 max_step^2; F = 0, F with a -0, F with a NaN; lambda in {0, 1},
+    keep / mix in {0, 0.7}; kind 5: both caps on either side independently; kinds 0, 1, 4 have no cap: the same moves uncapped."""
+    kacc = float(consts[2])
+    ms = float(fire.max_step)
+    ms2 = ms * ms
+    sdt = 0.03125
+    rows = []
+
+    def row(x, v, F, lam=1.0, cm=(0.0, 0.0, 0.0), keep=0.0, mix=0.0, st=sdt):
+        return list(x) + list(v) + list(F) + [lam] + list(cm) + [keep, mix, st]
+
+    def tag_of(r):
+        from collections import Counter
+        h = Counter()
+        row_finish_ref(kind, dt, r, consts, fire, hits=h)
+        return "capped" if (h["move_capped"] or h["s_capped"]) else "plain"
+
+    def add(r):
+        rows.append((r, tag_of(r)))
+
+    if kind in (2, 3):
+        # dr = st (keep v + mix F + st kacc F): v, F along _U; F's third component tuned
+        for keep, mix in ((0.0, 0.0), (0.7, 0.7), (0.7, 0.0), (0.0, 0.7)):
+            gain = mix + sdt * kacc
+
+            def move_d2(fz, S, keep=keep, mix=mix):
+                r = row(_X0, [0.5 * S * u for u in _U], [S * _U[0], S * _U[1], fz], keep=keep, mix=mix)
+                acc = sdt * kacc
+                vn = [keep * r[3 + k] + mix * r[6 + k] for k in range(3)]
+                vn = [vn[k] + acc * r[6 + k] for k in range(3)]
+                return _d2([sdt * a for a in vn]), r
+
+            for target in (_next(ms2, False), ms2, _next(ms2)):
+                S = 0.98 * ms / (sdt * (0.5 * keep + gain))
+                fz = _bisect(lambda z: move_d2(z, S)[0], 0.5 * S * _U[2], 4.0 * S * _U[2], target)
+                d2, r = move_d2(fz, S)
+                assert d2 == target
+                add(r)
+            for f2 in (1e-300, 4.0, 1e16):
+                S = float(np.sqrt(f2)) * ms / (sdt * (0.5 * keep + gain))
+                add(row(_X0, [0.5 * S * u for u in _U], [S * u for u in _U], keep=keep, mix=mix))
+            add(row(_X0, (0.3, -0.2, 0.1), (0.0, 0.0, 0.0), keep=keep, mix=mix))
+            add(row(_X0, (0.0, 0.0, 0.0), (0.0, 0.0, 0.0), keep=keep, mix=mix))                       # d2 = 0
+            add(row(_X0, (0.3, -0.2, 0.1), (1.5, -0.0, 2.5), keep=keep, mix=mix))
+            add(row(_X0, (0.3, -0.2, 0.1), (1.5, NAN, 2.5), keep=keep, mix=mix))
+    elif kind in (5, 6):
+        # move = mix F; kind 5: s = lambda v.  Each on either side of, and at, the cap, independently
+        sides = [("edge", t) for t in (_next(ms2, False), ms2, _next(ms2))] + [("free", f2) for f2 in (1e-300, 0.25, 4.0, 1e16)]
+
+        def tuned(length, what):
+            """a vector w along _U with |length w|^2 == what[1] exactly ("edge") or about what[1] max_step^2 ("free")"""
+            if what[0] == "free":
+                S = float(np.sqrt(what[1])) * ms / length
+                return [S * u for u in _U]
+            S = 0.98 * ms / length
+            fn = lambda z: _d2([length * S * _U[0], length * S * _U[1], length * z])
+            z = _bisect(fn, 0.5 * S * _U[2], 4.0 * S * _U[2], what[1])
+            return [S * _U[0], S * _U[1], z]
+
+        for a_prev, a in ((1e-5, 3e-5), (0.7, 0.7), (1.0, 1e2), (0.0, 1e-7)):
+            for mv in sides:
+                F = [-c for c in tuned(a, mv)]                            # the move is along -_U, x0 on that side of 0
+                x0 = [-c for c in _X0]
+                if kind == 6:
+                    add(row(x0, (0.0, 0.0, 0.0), F, lam=a_prev, mix=a))
+                    continue
+                for sv in (sides if a_prev > 0 else [("free", 4.0)]):
+                    v = tuned(a_prev, sv) if a_prev > 0 else [3.0 * u for u in _U]
+                    add(row(x0, v, F, lam=a_prev, mix=a))
+        for a_prev, a in ((1e-5, 3e-5), (0.7, 0.7)):
+            v = (0.0, 0.0, 0.0) if kind == 6 else (0.3, -0.2, 0.1)
+            add(row(_X0, v, (0.0, 0.0, 0.0), lam=a_prev, mix=a))
+            add(row(_X0, v, (1.5, -0.0, 2.5), lam=a_prev, mix=a))
+            add(row(_X0, v, (1.5, NAN, 2.5), lam=a_prev, mix=a))
+    else:
+        # MD: v' = lambda (v - cm) + acc F, x' = x + dt v' (kind 4: v' = v, x' = x); no cap whatever the move
+        step = dt if kind != 4 else sdt
+        for lam in (0.0, 1.0, 0.93):
+            for cm in ((0.0, 0.0, 0.0), (0.01, -0.02, 0.03)):
+                for f2 in (0.0, 1e-300, 1.0, 4.0, 1e16):
+                    S = float(np.sqrt(f2)) * ms / step
+                    add(row(_X0, [S * u for u in _U], [0.5 * S * u for u in _U], lam=lam, cm=cm))
+                add(row(_X0, (0.3, -0.2, 0.1), (0.0, 0.0, 0.0), lam=lam, cm=cm))
+                add(row(_X0, (0.3, -0.2, 0.1), (1.5, -0.0, 2.5), lam=lam, cm=cm))
+                add(row(_X0, (0.3, -0.2, 0.1), (1.5, NAN, 2.5), lam=lam, cm=cm))
+    # vectors that are not parallel (a swapped component shows), in one sign pattern so that no sum of a capped row cancels: plain and capped
+    rng = np.random.default_rng(3100 + kind)
+    sg = np.array([1.0, -1.0, 1.0])
+    for big in (False, True):
+        for _ in range(8):
+            v = sg * rng.uniform(0.2, 1.0, 3) * (40.0 * ms / sdt if big else 0.01)
+            F = -sg * rng.uniform(0.2, 1.0, 3) * (40.0 * ms / sdt if big else 0.01)
+            if kind in (2, 3):
+                v = -v                                                    # v' = keep v + (mix + acc) F: one sign
+            add(row(-sg * rng.uniform(1.0, 4.0, 3), v if kind not in (3, 6) else 0.0 * v, F, lam=0.9 if kind < 5 else 0.02, cm=(0.01, -0.02, 0.03) if kind < 2 else (0.0, 0.0, 0.0),
+                    keep=0.7, mix=0.02 if kind >= 5 else 0.1))
     return rows

@@ -158,3 +158,210 @@ def test_lbfgs_first_length_without_mass_is_caught(built):
     xa, _ = L.lbfgs_run(force, x0, case.nsteps, m=R.LBFGS_MEMORY, g0=L.gamma0(om, of), max_step=float(of.max_step))
     xb, _ = L.lbfgs_run(force, x0, case.nsteps, m=R.LBFGS_MEMORY, g0=L.gamma0(om, of) * float(om.mass), max_step=float(of.max_step))
     assert np.abs(xa - xb).max() > 10 * 1e-2, np.abs(xa - xb).max()
+
+
+# ---------------------------------------------------------------------------------------------
+# the fp64 tables (tests/test_gpu_f64_controller_table.py runs them on the device): admitted here, without one
+# ---------------------------------------------------------------------------------------------
+ROW_DT = 2.0 ** -9          # the MD step of the row-finish table (kinds 0, 1)
+
+
+def _table64():
+    from chromosome3d_amd import default_fire, default_model
+    m, fire = default_model(**R.TABLE_MODEL), default_fire(**R.TABLE_FIRE)
+    return R.table_consts64(m, R.TABLE_N), fire
+
+
+def _scalar_hits(kind):
+    from collections import Counter
+    consts, fire = _table64()
+    h = Counter()
+    for dt, t_bath, psum, state, npos in R.table_rows64(kind, consts[0]):
+        R.step_scalars_ref(kind, dt, t_bath, psum, state, npos, consts, fire, precision=64, hits=h)
+    return h
+
+
+def _row_hits(kind):
+    from collections import Counter
+    consts, fire = _table64()
+    h = Counter()
+    rows = R.row_finish_rows(kind, ROW_DT, consts, fire)
+    for r, _ in rows:
+        R.row_finish_ref(kind, ROW_DT, r, consts, fire, hits=h)
+    return h, rows
+
+
+def test_fp64_table_takes_every_branch(built):
+    """every branch and edge the fp64 tables are there for is taken by at least one row, counted by the restatement itself"""
+    for kind in (0, 1):
+        h = _scalar_hits(kind)
+        for name in ("T_below_floor", "T_at_floor", "T_above_floor"):
+            assert h[name] >= 1, (kind, name, dict(h))
+    h = _scalar_hits(0)
+    for name in ("l2_below_0", "l2_at_0", "l2_above_0"):
+        assert h[name] >= 1, (name, dict(h))
+    for kind in (2, 3):
+        h = _scalar_hits(kind)
+        for name in ("fire_vf_pos", "fire_vf_zero", "fire_vf_neg", "fire_vf_nan", "fire_reset", "fire_ff", "fire_ff_floor", "fire_ff_at_floor",
+                     "npos_below_nmin", "npos_at_nmin", "npos_above_nmin", "dt_grow", "dt_at_max", "dt_cap"):
+            assert h[name] >= 1, (kind, name, dict(h))
+    h = _scalar_hits(5)
+    for name in ("bb_first", "bb_second", "bb_even", "bb_odd", "bb_negcurv", "bb_lo", "bb_lo_nan", "bb_hi", "bb_sy_pos", "bb_sy_zero", "bb_sy_neg",
+                 "bb_sy_nan"):
+        assert h[name] >= 1, (name, dict(h))
+    assert _scalar_hits(6)["bb_first"] == len(R.table_rows64(6, _table64()[0][0]))
+    for kind in (2, 3, 6):
+        h, rows = _row_hits(kind)
+        for name in ("move_uncapped", "move_at_cap", "move_capped"):
+            assert h[name] >= 1, (kind, name, dict(h))
+    h, rows = _row_hits(5)
+    for name in ("move_uncapped", "move_at_cap", "move_capped", "s_uncapped", "s_at_cap", "s_capped"):
+        assert h[name] >= 1, (name, dict(h))
+    # kind 5: the two caps independently — each of the four combinations on some row
+    from collections import Counter
+    consts, fire = _table64()
+    combos = set()
+    for r, _ in rows:
+        c = Counter()
+        R.row_finish_ref(5, ROW_DT, r, consts, fire, hits=c)
+        combos.add((bool(c["s_capped"]), bool(c["move_capped"])))
+    assert combos == {(False, False), (False, True), (True, False), (True, True)}
+    for kind in (0, 1):
+        assert _row_hits(kind)[0]["md"] >= 1
+    h, rows = _row_hits(4)
+    assert h["md_begin"] == len(rows)
+    for r, _ in rows:                                          # kind 4: v = vinit, x unchanged
+        out = R.row_finish_ref(4, ROW_DT, r, consts, fire)
+        assert all(a == b or (a != a and b != b) for a, b in zip(out[:6], r[:6]))
+
+
+def test_fp64_table_edges_are_at_the_edge(built):
+    """exact equality in float64 where a row is meant to sit at an edge, and one double either side where it is meant to sit beside it"""
+    consts, fire = _table64()
+    t_fac = consts[0]
+    lo, at, hi = R._floor_edge(t_fac)
+    assert t_fac * at == 1e-2 and t_fac * lo < 1e-2 < t_fac * hi
+    assert t_fac * lo == float(np.nextafter(1e-2, 0.0)) and t_fac * hi == float(np.nextafter(1e-2, 1.0))
+    xs = {r[2][0] for r in R.table_rows64(0, t_fac)}
+    assert {lo, at, hi} <= xs
+    # lambda^2 = 0 exactly: dt fbeta = 1 at t_bath 0; and the products of the FIRE values that are "at"
+    assert 2.0 ** -8 * consts[3] == 1.0 and 1.0 + 2.0 ** -8 * consts[3] * (0.0 / 1e-2 - 1.0) == 0.0
+    assert 0.03125 * float(fire.f_inc) == float(fire.dt_max)
+    assert float(np.nextafter(0.03125, 0.0)) * float(fire.f_inc) < float(fire.dt_max) < float(np.nextafter(0.03125, 1.0)) * float(fire.f_inc)
+    sdts = {r[3][0] for r in R.table_rows64(2, t_fac)}
+    assert {float(np.nextafter(0.03125, 0.0)), 0.03125, float(np.nextafter(0.03125, 1.0))} <= sdts
+    assert fire.n_min == 3 and {r[4] for r in R.table_rows64(2, t_fac)} >= {2, 3, 4}
+    ffs = {r[2][1] for r in R.table_rows64(2, t_fac)}
+    assert {float(np.nextafter(1e-30, 0.0)), 1e-30, float(np.nextafter(1e-30, 1.0))} <= ffs
+    # two-point lengths at both bounds and one double either side
+    got = set()
+    for dt, t_bath, psum, state, npos in R.table_rows64(5, t_fac):
+        if npos in (2, 3) and psum[0] > 0 and psum[2] == 1.0:
+            a = psum[0] / psum[2] if npos % 2 else psum[3] / psum[0]
+            got.add((npos % 2, a))
+    for par in (0, 1):
+        for b in (1e-7, 1e2):
+            assert {(par, float(np.nextafter(b, 0.0))), (par, b), (par, float(np.nextafter(b, 1e3)))} <= got, (par, b)
+    # the capped quantity at max_step^2 and one double either side, per kind and per cap
+    ms = float(fire.max_step)
+    ms2 = ms * ms
+    want = {float(np.nextafter(ms2, 0.0)), ms2, float(np.nextafter(ms2, 1.0))}
+    for kind in (2, 3, 5, 6):
+        seen_move, seen_s = set(), set()
+        for r, _ in R.row_finish_rows(kind, ROW_DT, consts, fire):
+            x, v, F, lam, keep, mix, sdt = r[0:3], r[3:6], r[6:9], r[9], r[13], r[14], r[15]
+            if kind in (2, 3):
+                acc = sdt * consts[2]
+                vn = [keep * v[k] + mix * F[k] for k in range(3)]
+                vn = [vn[k] + acc * F[k] for k in range(3)]
+                seen_move.add(R._d2([sdt * a for a in vn]))
+            else:
+                seen_move.add(R._d2([mix * a for a in F]))
+                seen_s.add(R._d2([lam * a for a in v]))
+        assert want <= seen_move, kind
+        if kind == 5:
+            assert want <= seen_s
+
+
+def _rows_differ(a, b):
+    """largest difference of two result rows in double ulps (inf: NaN against a number, or an integer that differs)"""
+    worst = 0.0
+    for g, w in zip(a, b):
+        if isinstance(w, int) or isinstance(g, int):
+            if g != w:
+                return float("inf")
+        elif (g != g) != (w != w):
+            return float("inf")
+        elif w == w:
+            worst = max(worst, R.ulps(g, w))
+    return worst
+
+
+@pytest.mark.parametrize("mut", sorted(R.TABLE_MUTATIONS))
+def test_fp64_table_catches_every_mutation(built, mut):
+    """each mutation of the restatement moves some row of the fp64 tables by at least 1000 double ulps, or changes an integer"""
+    consts, fire = _table64()
+    worst = 0.0
+    for kind in R.SCALAR_KINDS:
+        for dt, t_bath, psum, state, npos in R.table_rows64(kind, consts[0]):
+            a = R.step_scalars_ref(kind, dt, t_bath, psum, state, npos, consts, fire, precision=64)
+            b = R.step_scalars_ref(kind, dt, t_bath, psum, state, npos, consts, fire, precision=64, mut=mut)
+            worst = max(worst, _rows_differ(list(b[0]) + list(b[1]) + [b[2]], list(a[0]) + list(a[1]) + [a[2]]))
+    from collections import Counter
+    for kind in R.ROW_KINDS:
+        for r, _ in R.row_finish_rows(kind, ROW_DT, consts, fire):
+            ha, hb = Counter(), Counter()
+            a, b = R.row_finish_ref(kind, ROW_DT, r, consts, fire, hits=ha), R.row_finish_ref(kind, ROW_DT, r, consts, fire, mut=mut, hits=hb)
+            # (the row's integers: whether each cap acted.  ">=" for ">" in the cap test changes nothing else — at d2 = max_step^2 the scale
+            #  max_step / sqrt(d2) is 1 to a rounding — so no table of outputs, on the CPU or on the device, can tell the two apart)
+            acted = [ha["move_acted"], ha["s_acted"]], [hb["move_acted"], hb["s_acted"]]
+            worst = max(worst, _rows_differ(b + acted[1], a + acted[0]))
+    print(f"{mut} ({R.TABLE_MUTATIONS[mut]}): {worst:.3g} double ulps")
+    assert worst >= 1000.0, worst
+
+
+def test_fp64_row_restatement_is_the_oracles_step(built):
+    """row_finish_ref against the oracle's own step functions through O.run_schedule: one bead cannot be run alone, so a short FIRE and a short
+    two-point stage of the 37-bead model are followed bead by bead with the restatement (forces from O.energy_force) to 1e-12 A"""
+    from chromosome3d_amd import default_fire, default_model
+    from tests.util import load_if, oracle_fire_from, oracle_model_from
+    m, fire = default_model(**R.TABLE_MODEL), default_fire(**R.TABLE_FIRE, max_step=0.01)
+    IF = load_if("chr21_1mb")
+    n = IF.shape[0]
+    om, of, d10 = oracle_model_from(m, n), oracle_fire_from(fire), O.if_to_dist10(IF)
+    consts = R.table_consts64(m, n)
+    x0 = O.init_coords(om, R.SEED, 0)
+    for stage_kind, nsteps in ((2, 9), (5, 9)):
+        stage = (stage_kind, nsteps) + tuple(float(np.float32(a)) for a in (0.0, 1.0, 1.0, 0.85, 0.0))
+        xo = O.run_schedule(om, d10, O.make_stages([stage]), of, R.SEED, 0, x0=x0)[0]
+        x, v = np.array(x0, dtype=np.float64), np.zeros((n, 3))
+        sums, state, npos = (0.0, 0.0, 0.0, 0.0), (float(of.dt_start), float(of.alpha_start)), 0
+        capped = 0
+        for it in range(nsteps):
+            F = O.energy_force(om, d10, x, *stage[3:6])[0]
+            kind = stage_kind if it else stage_kind + 1
+            sc, state, npos = R.step_scalars_ref(kind, 0.0, 0.0, sums, state, npos, consts, fire, precision=64)
+            from collections import Counter
+            h = Counter()
+            out = np.array([R.row_finish_ref(kind, 0.0, list(x[i]) + list(v[i]) + list(F[i]) + list(sc) + [state[0]], consts, fire, hits=h) for i in range(n)])
+            capped += h["move_capped"]
+            x, v = out[:, 0:3], out[:, 3:6]
+            sums = tuple(out[:, 6 + k].sum() for k in range(4))
+        assert capped > 0, stage_kind
+        x = x - x.mean(0)
+        assert np.abs(x - xo).max() < 1e-12, (stage_kind, np.abs(x - xo).max())
+    # MD: the Maxwell start (kind 4: no move, the sums of its velocities), then Berendsen / rescaling steps
+    for stage_kind in (0, 1):
+        stage = (stage_kind, 6) + tuple(float(np.float32(a)) for a in (0.003, 0.4, 0.003, 0.9, 300.0))
+        dt, t_bath = stage[2], stage[6]
+        xo, vo, _ = O.run_schedule(om, d10, O.make_stages([stage]), of, R.SEED, 0, x0=x0)
+        x, v = np.array(x0, dtype=np.float64), O.init_velocities(om, R.SEED, 0, 0.5)
+        sc = (1.0, 0.0, 0.0, 0.0, 0.0, 0.0)
+        for kind in (4,) + (stage_kind,) * 6:
+            F = O.energy_force(om, d10, x, *stage[3:6])[0]
+            if kind != 4:
+                sc = R.step_scalars_ref(kind, dt, t_bath, sums, (0.0, 0.0), 0, consts, fire, precision=64)[0]
+            out = np.array([R.row_finish_ref(kind, dt, list(x[i]) + list(v[i]) + list(F[i]) + list(sc) + [0.0], consts, fire) for i in range(n)])
+            x, v = out[:, 0:3], out[:, 3:6]
+            sums = tuple(out[:, 6 + k].sum() for k in range(4))
+        assert np.abs(x - x.mean(0) - xo).max() < 1e-12 and np.abs(v - vo).max() < 1e-12 * np.abs(vo).max(), stage_kind
