@@ -125,6 +125,16 @@ __device__ __forceinline__ double sqrt64(double x) {
     return g;
 }
 
+// The per-bead cap's scale max_step / |d| beyond the seed's range.  sqrt_hrsqrt64 seeds from a float: for d.d >= 2^128 the seed is 0, the
+// Newton steps keep 0, and a bead the CPU restatement moves by max_step would stay where it is.  A capped d.d outside seed_range64 takes the
+// correctly rounded max_step / sqrt(d.d) — the CPU restatement's own two operations — behind the wave's branch, as rcp64 does (the users:
+// c3d_f64_row_finish.inc, the rows of k64_lbfgs_move).  capped = the cap acted on this lane; scl = the seeded scale (1 where it did not).
+__device__ __forceinline__ double cap_scale_wide64(double d2, bool capped, double max_step, double scl) {
+    const bool wide = capped && !seed_range64(d2);
+    if (__builtin_expect(__builtin_amdgcn_ballot_w64(wide) != 0, 0)) scl = wide ? max_step / __builtin_sqrt(d2) : scl;
+    return scl;
+}
+
 // HALF of dE/dDelta of the NOE term without S and w.  GEN = tails with a 1/D^2 part.
 template <int POT, bool GEN>
 __device__ __forceinline__ double half_noe_grad64(const Model64& m, double delta) {
@@ -279,6 +289,19 @@ __global__ __launch_bounds__(kBlock64) __attribute__((amdgpu_waves_per_eu(5))) v
 #undef C3D_F64_CHUNKED
 }
 
+// c3d_lbfgs_move_row.inc in doubles (k64_lbfgs_move, k64_lbfgs_move_rows): the per-bead cap with 1 / |d| as k64_step's clamp forms it,
+// beyond the seed's range included (cap_scale_wide64)
+#define C3D_LBFGS_T double
+#define C3D_LBFGS_FMA fma
+#define C3D_LBFGS_CAP                                                                              \
+        const double l2 = fma(dx, dx, fma(dy, dy, dz * dz));                                       \
+        if (l2 > fp.max_step * fp.max_step) {                                                      \
+            double len, hh;                                                                        \
+            sqrt_hrsqrt64(l2, len, hh);                                                            \
+            hh = fma(fma(-len, hh, 0.5), hh, hh);                                                  \
+            const double scl = cap_scale_wide64(l2, true, fp.max_step, fp.max_step * (hh + hh));   \
+            dx *= scl; dy *= scl; dz *= scl;                                                       \
+        }
 // The move: k_lbfgs_move in doubles.  Every workgroup of a replica forms the replica sums of the tile partials in one fixed order (lane l
 // takes tiles l, l + 64, ..., then the butterfly), thread 0 the compact form (pair test, gamma, the two triangular solves, the descent test
 // with memory drop); then its rows: direction, the per-bead cap at max_step, the move, s into the ring; P = (move.move, F.F, 0, 0) per tile.
@@ -326,34 +349,7 @@ __global__ __launch_bounds__(kLbfgsMoveRows64) void k64_lbfgs_move(const Model64
     const size_t roff = (size_t)rep * 3 * np;
     double d2 = 0.0;
     if (i < m.n) {
-        const size_t ix = roff + i, iy = ix + np, iz = iy + np;
-        const double c = coef[0];
-        double dx = c * fcur[ix], dy = c * fcur[iy], dz = c * fcur[iz];
-        double* hs = hist + (size_t)rep * lbfgs_hist_floats(np) + i;
-        double* hy = hs + (size_t)3 * M * np;
-        const int mask = shi[0];
-#pragma unroll
-        for (int j = 0; j < M; ++j) {
-            if (!(mask & (1 << j))) continue;
-            const double a = coef[1 + j], b = coef[1 + M + j];
-            const double* s = hs + (size_t)3 * j * np;
-            const double* y = hy + (size_t)3 * j * np;
-            dx = fma(a, s[0], fma(b, y[0], dx));
-            dy = fma(a, s[np], fma(b, y[np], dy));
-            dz = fma(a, s[2 * np], fma(b, y[2 * np], dz));
-        }
-        const double l2 = fma(dx, dx, fma(dy, dy, dz * dz));
-        if (l2 > fp.max_step * fp.max_step) {            // the per-bead cap, 1 / |d| as k64_step's clamp forms it
-            double len, hh;
-            sqrt_hrsqrt64(l2, len, hh);
-            hh = fma(fma(-len, hh, 0.5), hh, hh);
-            const double scl = fp.max_step * (hh + hh);
-            dx *= scl; dy *= scl; dz *= scl;
-        }
-        xout[ix] = xin[ix] + dx; xout[iy] = xin[iy] + dy; xout[iz] = xin[iz] + dz;
-        double* sn = hs + (size_t)3 * shi[1] * np;
-        sn[0] = dx; sn[np] = dy; sn[2 * np] = dz;
-        d2 = fma(dx, dx, fma(dy, dy, dz * dz));
+#include "c3d_lbfgs_move_row.inc"
     }
     dd[tid] = d2;
     __syncthreads();
@@ -605,6 +601,32 @@ hipError_t launch_lbfgs_move64(const DevModel& d, const Model64& m, const Step64
     const int q = parity ^ 1;
     hipLaunchKernelGGL(k64_lbfgs_move, dim3((d.n + kLbfgsMoveRows64 - 1) / kLbfgsMoveRows64, d.nrep_g), dim3(kLbfgsMoveRows64), 0, s, m, p, fp,
                        d.rep_base, b.X[parity], b.X[q], b.V[q], lb.hist, lb.part, b.P[q], lb.S[parity], lb.S[q], mem);
+    return hipGetLastError();
+}
+// The rows of k64_lbfgs_move as a table (c3d_debug_lbfgs_move_rows on a precision-64 context): k_lbfgs_move_rows in doubles.
+__global__ void k64_lbfgs_move_rows(const Fire64 fp, const int rows, const int np, const double* __restrict__ coef_in, const int mask_in,
+                                    const int slot, const double* __restrict__ xin, double* __restrict__ xout, const double* __restrict__ fcur,
+                                    double* __restrict__ hist, double* __restrict__ d2out) {
+    constexpr int M = kLbfgsMaxPairs;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= rows) return;
+    double coef[1 + 2 * M];
+    for (int k = 0; k < 1 + 2 * M; ++k) coef[k] = coef_in[k];
+    const int shi[2] = {mask_in, slot};
+    const int rep = 0;
+    const size_t roff = 0;
+    double d2 = 0.0;
+    {
+#include "c3d_lbfgs_move_row.inc"
+    }
+    d2out[i] = d2;
+}
+#undef C3D_LBFGS_CAP
+#undef C3D_LBFGS_FMA
+#undef C3D_LBFGS_T
+hipError_t launch_lbfgs_move_rows64(const Fire64& fp, int rows, int np, const double* coef, int mask, int slot, const double* xin, double* xout,
+                                    const double* fcur, double* hist, double* d2, hipStream_t s) {
+    hipLaunchKernelGGL(k64_lbfgs_move_rows, dim3((rows + 63) / 64), dim3(64), 0, s, fp, rows, np, coef, mask, slot, xin, xout, fcur, hist, d2);
     return hipGetLastError();
 }
 // The serial section of k64_lbfgs_move as a table (c3d_debug_lbfgs_direction on a precision-64 context): k_lbfgs_direction in doubles.

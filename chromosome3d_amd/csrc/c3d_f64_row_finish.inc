@@ -18,7 +18,7 @@
             auto clamp_scale = [&](double d2) {
                 double scl = 1.0;
                 if (d2 > ms2) { double dd, hh; sqrt_hrsqrt64(d2, dd, hh); hh = fma(fma(-dd, hh, 0.5), hh, hh); scl = fp.max_step * (hh + hh); }
-                return scl;
+                return cap_scale_wide64(d2, d2 > ms2, fp.max_step, scl);
             };
             q1 = Fx * Fx + Fy * Fy + Fz * Fz;
             if (p.kind == 5) {
@@ -41,5 +41,6 @@
             const double d2 = dxs * dxs + dys * dys + dzs * dzs;
             double scl = 1.0;
             if (d2 > fp.max_step * fp.max_step) { double dd, hh; sqrt_hrsqrt64(d2, dd, hh); hh = fma(fma(-dd, hh, 0.5), hh, hh); scl = fp.max_step * (hh + hh); }
+            scl = cap_scale_wide64(d2, d2 > fp.max_step * fp.max_step, fp.max_step, scl);
             xn = x0 + scl * dxs; yn = y0 + scl * dys; zn = z0 + scl * dzs;
         }

@@ -192,6 +192,11 @@ hipError_t launch_lbfgs_eval(const DevModel& m, const DevStep& p, const DevBuffe
                              const StepForm& f, hipStream_t s);
 hipError_t launch_lbfgs_move(const DevModel& m, const DevStep& p, const DevFire& fp, const DevBuffers& b, const LbfgsBuffers& lb, int parity,
                              int mem, hipStream_t s);
+// c3d_lbfgs_move_row.inc (the rows of k_lbfgs_move) on `rows` rows, a thread a row (k_lbfgs_move_rows; c3d_debug_lbfgs_move_rows): device
+// buffers in the move's layouts with np columns (rows padded to 256): xin, xout, fcur [3][np], hist lbfgs_hist_floats(np), d2 [np];
+// coef[1 + 2 kLbfgsMaxPairs], the slot mask and the slot of s are uniform over the call
+hipError_t launch_lbfgs_move_rows(const DevFire& fp, int rows, int np, const float* coef, int mask, int slot, const float* xin, float* xout,
+                                  const float* fcur, float* hist, float* d2, hipStream_t s);
 // c3d_lbfgs_serial.inc (the serial section of k_lbfgs_move) on `rows` rows of (sums[kLbfgsQ], LbfgsState, flags = (first, mem0)), a thread a
 // row (c3d_debug_lbfgs_direction): out = the state left, coef[1 + 2 kLbfgsMaxPairs] widened to doubles, shi[2] = (slot mask, slot of s)
 hipError_t launch_lbfgs_direction(const DevModel& m, const DevFire& fp, int rows, const double* sums, const LbfgsState* in, const int* flags,
@@ -258,6 +263,10 @@ hipError_t launch_step_sym(const DevModel& m, const DevStep& p, const DevFire& f
 // scalars [rows][6] = lam, cmx, cmy, cmz, keep, mix; out = the state it leaves
 hipError_t launch_step_scalars(const DevModel& m, const DevStep& p, const DevFire& fp, int rows, const float* psum, const FireState* in,
                                float* scalars, FireState* out, hipStream_t s);
+// finish_row on `rows` rows, a thread a row (c3d_sym.hip k_row_finish; c3d_debug_row_finish): in [rows][16] = x0[3], v0[3], F[3], lam,
+// cmx, cmy, cmz, keep, mix, dt of the state; out [rows][10] = xn[3], vn[3], the row's terms q of the four sums
+constexpr int kRowFinishIn = C3D_ROW_FINISH_IN, kRowFinishOut = C3D_ROW_FINISH_OUT;
+hipError_t launch_row_finish(const DevModel& m, const DevStep& p, const DevFire& fp, int rows, const float* in, float* out, hipStream_t s);
 // fp64 step (c3d_f64.hip, option "precision" = 64): the CPU restatement's algorithm in its precision on the GPU, one launch per SA
 // step of a replica group (k64_step, k64_step_chunked beyond 2560 beads), double buffered by step parity like the fp32 per-step path.
 // Layouts (np = cols64(n): n rounded up to 128): T [n][np] targets in Angstrom (0.1 * t10, 0 = none); X, V [2][nrep][3][np] SoA;
@@ -345,6 +354,8 @@ hipError_t launch_lbfgs_move64(const DevModel& d, const Model64& m, const Step64
                                int parity, int mem, hipStream_t s);
 hipError_t launch_lbfgs_direction64(const Step64& p, const Fire64& fp, int rows, const double* sums, const LbfgsState* in, const int* flags,
                                     LbfgsState* out, double* coef, int* shi, hipStream_t s);      // the same of k64_lbfgs_move
+hipError_t launch_lbfgs_move_rows64(const Fire64& fp, int rows, int np, const double* coef, int mask, int slot, const double* xin, double* xout,
+                                    const double* fcur, double* hist, double* d2, hipStream_t s);      // k_lbfgs_move_rows in doubles
 hipError_t launch_targets64(const Model64& m, const Form64& f, const int32_t* t10, double* T, hipStream_t s);   // in the encoding f's kernel expects
 // the integer tenths of a restraint list (R pairs, 0-based, every pair once) into the zeroed n x n matrix t10, both triangles
 hipError_t launch_tenths64(int n, int R, const int32_t* ri, const int32_t* rj, const int32_t* rt10, int32_t* t10, hipStream_t s);

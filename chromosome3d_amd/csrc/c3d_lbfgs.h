@@ -43,6 +43,21 @@ __global__ __launch_bounds__(64 * TR / RPW) __attribute__((amdgpu_waves_per_eu(W
 // rows per workgroup of the move
 constexpr int kLbfgsMoveRows = 256;
 
+// c3d_lbfgs_move_row.inc in floats (k_lbfgs_move, k_lbfgs_move_rows): the per-bead cap is finish_row's, max_step v_rsq_f32(d.d).  Where
+// d.d is beyond a float with d finite (|d| from 2^63.5 on) v_rsq_f32(inf) = 0 would leave the bead where it is: the root is then taken of
+// d 2^-66, whose square a float holds whatever d (a NaN d.d is no cap: the NaN goes on into the move, as in the CPU restatement)
+#define C3D_LBFGS_T float
+#define C3D_LBFGS_FMA fmaf
+#define C3D_LBFGS_CAP                                                                              \
+        const float ms2 = fp.max_step * fp.max_step;                                               \
+        const float l2 = fmaf(dx, dx, fmaf(dy, dy, dz * dz));                                      \
+        float scl = l2 > ms2 ? fp.max_step * __builtin_amdgcn_rsqf(l2) : 1.0f;                     \
+        if (l2 == __builtin_huge_valf()) {                                                         \
+            const float ex = dx * 0x1p-66f, ey = dy * 0x1p-66f, ez = dz * 0x1p-66f;                \
+            scl = fp.max_step * __builtin_amdgcn_rsqf(fmaf(ex, ex, fmaf(ey, ey, ez * ez))) * 0x1p-66f; \
+        }                                                                                          \
+        dx *= scl; dy *= scl; dz *= scl;
+
 __global__ __launch_bounds__(kLbfgsMoveRows) void k_lbfgs_move(
     const float* __restrict__ xin, float* __restrict__ xout, const float* __restrict__ fcur, float* __restrict__ hist,
     const float* __restrict__ part, float* __restrict__ pout, const LbfgsState* __restrict__ sin, LbfgsState* __restrict__ sout,
@@ -82,34 +97,11 @@ __global__ __launch_bounds__(kLbfgsMoveRows) void k_lbfgs_move(
     __syncthreads();
     // 3. the rows of this workgroup
     const int i = blockIdx.x * kLbfgsMoveRows + tid;
-    const int npad = m.npad;
-    const size_t roff = (size_t)rep * 3 * npad;
+    const int np = m.npad;
+    const size_t roff = (size_t)rep * 3 * np;
     float d2 = 0.0f;
     if (i < m.n) {
-        const size_t ix = roff + i, iy = ix + npad, iz = iy + npad;
-        const float c = coef[0];
-        float dx = c * fcur[ix], dy = c * fcur[iy], dz = c * fcur[iz];
-        float* hs = hist + (size_t)rep * lbfgs_hist_floats(npad) + i;
-        float* hy = hs + (size_t)3 * M * npad;
-        const int mask = shi[0];
-#pragma unroll
-        for (int j = 0; j < M; ++j) {
-            if (!(mask & (1 << j))) continue;
-            const float a = coef[1 + j], b = coef[1 + M + j];
-            const float* s = hs + (size_t)3 * j * npad;
-            const float* y = hy + (size_t)3 * j * npad;
-            dx = fmaf(a, s[0], fmaf(b, y[0], dx));
-            dy = fmaf(a, s[npad], fmaf(b, y[npad], dy));
-            dz = fmaf(a, s[2 * npad], fmaf(b, y[2 * npad], dz));
-        }
-        const float ms2 = fp.max_step * fp.max_step;
-        const float l2 = fmaf(dx, dx, fmaf(dy, dy, dz * dz));
-        const float scl = l2 > ms2 ? fp.max_step * __builtin_amdgcn_rsqf(l2) : 1.0f;
-        dx *= scl; dy *= scl; dz *= scl;
-        xout[ix] = xin[ix] + dx; xout[iy] = xin[iy] + dy; xout[iz] = xin[iz] + dz;
-        float* sn = hs + (size_t)3 * shi[1] * npad;
-        sn[0] = dx; sn[npad] = dy; sn[2 * npad] = dz;
-        d2 = fmaf(dx, dx, fmaf(dy, dy, dz * dz));
+#include "c3d_lbfgs_move_row.inc"
     }
     dd[tid] = d2;
     __syncthreads();
@@ -157,6 +149,36 @@ hipError_t launch_lbfgs_move(const DevModel& m, const DevStep& p, const DevFire&
     const int q = parity ^ 1;
     hipLaunchKernelGGL(k_lbfgs_move, dim3((m.n + kLbfgsMoveRows - 1) / kLbfgsMoveRows, m.nrep_g), dim3(kLbfgsMoveRows), 0, s,
                        b.X[parity], b.X[q], b.V[q], lb.hist, lb.part, b.P[q], lb.S[parity], lb.S[q], m, p, fp, mem);
+    return hipGetLastError();
+}
+
+// ---- the rows of the move as a table (c3d_debug_lbfgs_move_rows) ---------------------------------------------------------------------
+// c3d_lbfgs_move_row.inc — section 3 of k_lbfgs_move — a thread a row over buffers in the kernel's own layouts with np = the rows padded
+// to 256: xin, xout, fcur [3][np], hist [s | y][M][3][np]; coef[1 + 2 M], the slot mask and the slot of s are the call's, as they are a
+// replica's in the move.  d2out[row] = the bead's move.move.
+__global__ void k_lbfgs_move_rows(const DevFire fp, const int rows, const int np, const float* __restrict__ coef_in, const int mask_in,
+                                  const int slot, const float* __restrict__ xin, float* __restrict__ xout, const float* __restrict__ fcur,
+                                  float* __restrict__ hist, float* __restrict__ d2out) {
+    constexpr int M = kLbfgsMaxPairs;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= rows) return;
+    float coef[1 + 2 * M];
+    for (int k = 0; k < 1 + 2 * M; ++k) coef[k] = coef_in[k];
+    const int shi[2] = {mask_in, slot};
+    const int rep = 0;
+    const size_t roff = 0;
+    float d2 = 0.0f;
+    {
+#include "c3d_lbfgs_move_row.inc"
+    }
+    d2out[i] = d2;
+}
+#undef C3D_LBFGS_CAP
+#undef C3D_LBFGS_FMA
+#undef C3D_LBFGS_T
+hipError_t launch_lbfgs_move_rows(const DevFire& fp, int rows, int np, const float* coef, int mask, int slot, const float* xin, float* xout,
+                                  const float* fcur, float* hist, float* d2, hipStream_t s) {
+    hipLaunchKernelGGL(k_lbfgs_move_rows, dim3((rows + 63) / 64), dim3(64), 0, s, fp, rows, np, coef, mask, slot, xin, xout, fcur, hist, d2);
     return hipGetLastError();
 }
 

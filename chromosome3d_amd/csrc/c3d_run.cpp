@@ -578,6 +578,25 @@ extern "C" int c3d_debug_step_scalars(c3d_ctx* c, int kind, float dt, float t_ba
     return C3D_OK;
 }
 
+// Test hook: finish_row on a table of rows (c3d.h) — the row update that consumes c3d_debug_step_scalars' scalars, under the same
+// DevModel / DevStep / DevFire (acc = 418.4 / mass and max_step as the host holds them; the kernel forms dt acc itself).
+extern "C" int c3d_debug_row_finish(c3d_ctx* c, int kind, float dt, int rows, const float* in, float* out) {
+    if (!c || !in || !out) return fail(C3D_ERR_INVALID, "c3d_debug_row_finish: bad arguments");
+    if (rows < 1 || rows > (1 << 20)) return fail(C3D_ERR_INVALID, "c3d_debug_row_finish: rows is 1 .. 2^20");
+    if (kind < 0 || kind > 6) return fail(C3D_ERR_INVALID, "c3d_debug_row_finish: kind is 0, 1, 2, 3, 4, 5 or 6");
+    if (c->n < 1) return fail(C3D_ERR_INVALID, "c3d_debug_row_finish: set the targets first (the model is built for a bead count)");
+    C3D_ENTRY(c, unit_bit(UNIT_SYM));
+    DevTmp<float> d_in, d_out;
+    HIP_TRY(hipMalloc(&d_in.p, sizeof(float) * C3D_ROW_FINISH_IN * (size_t)rows));
+    HIP_TRY(hipMalloc(&d_out.p, sizeof(float) * C3D_ROW_FINISH_OUT * (size_t)rows));
+    HIP_TRY(hipMemcpyAsync(d_in.p, in, sizeof(float) * C3D_ROW_FINISH_IN * (size_t)rows, hipMemcpyHostToDevice, c->stream));
+    LAUNCH_TRY("row finish launch", c3d::launch_row_finish(dev_model(c), dev_step(c, kind, dt, 1.0f, 1.0f, 0.85f, 0.0f), dev_fire(c), rows, d_in.p,
+                                                           d_out.p, c->stream));
+    HIP_TRY(hipMemcpyAsync(out, d_out.p, sizeof(float) * C3D_ROW_FINISH_OUT * (size_t)rows, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return C3D_OK;
+}
+
 // Test hooks: the fp64 controller (c3d_f64_scalars.inc) and the fp64 row update (c3d_f64_row_finish.inc) on tables of rows (c3d.h).
 // Model64 / Step64 / Fire64 come from the builders every fp64 launch uses, so the tables also cover t_fac, inv_n, acc and kacc as the host
 // forms them.  The stage weights of the Step64 (1, 1, 0.85) enter neither text.
@@ -692,6 +711,77 @@ extern "C" int c3d_debug_lbfgs_direction(c3d_ctx* c, int rows, const double* sum
         mask_slot[2 * r] = flags[2 * r]; mask_slot[2 * r + 1] = flags[2 * r + 1];
     }
     return C3D_OK;
+}
+
+// Test hook: the rows of the L-BFGS move (c3d_lbfgs_move_row.inc) on a table of rows (c3d.h) — k_lbfgs_move_rows, or k64_lbfgs_move_rows
+// on a precision-64 context.  The host lays the rows out as the move kernels find them: x, F [3][np], the ring [s | y][8][3][np] with np
+// the rows padded to 256; columns beyond the rows hold zeros and are not run.
+namespace {
+template <class T, class Launch>
+int lbfgs_move_rows(c3d_ctx* c, int rows, const double* coef, int slot, const double* in, double* out, const char* what, Launch&& launch) {
+    constexpr int M = c3d::kLbfgsMaxPairs, NC = C3D_LBFGS_COEFS;
+    const int np = (rows + 255) / 256 * 256;
+    const size_t nh = c3d::lbfgs_hist_floats(np);
+    std::vector<T> hx(3 * (size_t)np, T(0)), hf(3 * (size_t)np, T(0)), hh(nh, T(0)), hc(NC), hd((size_t)np);
+    for (int k = 0; k < NC; ++k) hc[k] = (T)coef[k];
+    for (int r = 0; r < rows; ++r) {
+        const double* a = in + (size_t)C3D_LBFGS_MOVE_ROW_IN * r;
+        for (int k = 0; k < 3; ++k) {
+            hx[(size_t)k * np + r] = (T)a[k]; hf[(size_t)k * np + r] = (T)a[3 + k];
+            for (int j = 0; j < M; ++j) {
+                hh[((size_t)3 * j + k) * np + r] = (T)a[6 + 3 * j + k];                       // s_j
+                hh[((size_t)3 * (M + j) + k) * np + r] = (T)a[6 + 3 * M + 3 * j + k];         // y_j
+            }
+        }
+    }
+    DevTmp<T> d_x, d_xo, d_f, d_h, d_c, d_d;
+    HIP_TRY(hipMalloc(&d_x.p, sizeof(T) * hx.size()));
+    HIP_TRY(hipMalloc(&d_xo.p, sizeof(T) * hx.size()));
+    HIP_TRY(hipMalloc(&d_f.p, sizeof(T) * hf.size()));
+    HIP_TRY(hipMalloc(&d_h.p, sizeof(T) * nh));
+    HIP_TRY(hipMalloc(&d_c.p, sizeof(T) * NC));
+    HIP_TRY(hipMalloc(&d_d.p, sizeof(T) * (size_t)np));
+    HIP_TRY(hipMemcpyAsync(d_x.p, hx.data(), sizeof(T) * hx.size(), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_f.p, hf.data(), sizeof(T) * hf.size(), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_h.p, hh.data(), sizeof(T) * nh, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_c.p, hc.data(), sizeof(T) * NC, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(d_xo.p, 0, sizeof(T) * hx.size(), c->stream));
+    HIP_TRY(hipMemsetAsync(d_d.p, 0, sizeof(T) * (size_t)np, c->stream));
+    if (const hipError_t e = launch(np, d_c.p, d_x.p, d_xo.p, d_f.p, d_h.p, d_d.p); e != hipSuccess)
+        return fail(C3D_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+    HIP_TRY(hipMemcpyAsync(hx.data(), d_xo.p, sizeof(T) * hx.size(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(hh.data(), d_h.p, sizeof(T) * nh, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(hd.data(), d_d.p, sizeof(T) * (size_t)np, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const int next = (slot + 1) % M;
+    for (int r = 0; r < rows; ++r) {
+        double* o = out + (size_t)C3D_LBFGS_MOVE_ROW_OUT * r;
+        for (int k = 0; k < 3; ++k) {
+            o[k] = (double)hx[(size_t)k * np + r];
+            o[3 + k] = (double)hh[((size_t)3 * slot + k) * np + r];
+            o[6 + k] = (double)hh[((size_t)3 * next + k) * np + r];
+        }
+        o[9] = (double)hd[r];
+    }
+    return C3D_OK;
+}
+}  // namespace
+extern "C" int c3d_debug_lbfgs_move_rows(c3d_ctx* c, int rows, const double* coef, int mask, int slot, const double* in, double* out) {
+    if (!c || !coef || !in || !out) return fail(C3D_ERR_INVALID, "c3d_debug_lbfgs_move_rows: bad arguments");
+    if (rows < 1 || rows > (1 << 16)) return fail(C3D_ERR_INVALID, "c3d_debug_lbfgs_move_rows: rows is 1 .. 2^16");
+    if (mask < 0 || mask > 255) return fail(C3D_ERR_INVALID, "c3d_debug_lbfgs_move_rows: mask is 0 .. 255");
+    if (slot < 0 || slot >= c3d::kLbfgsMaxPairs) return fail(C3D_ERR_INVALID, "c3d_debug_lbfgs_move_rows: slot is 0 .. 7");
+    const bool f64 = c->precision == 64;
+    C3D_ENTRY(c, f64 ? unit_bit(UNIT_F64) : 0u);
+    if (f64)
+        return lbfgs_move_rows<double>(c, rows, coef, slot, in, out, "fp64 L-BFGS move rows launch",
+                                       [&](int np, const double* dc, const double* x, double* xo, const double* f, double* h, double* d) {
+                                           return c3d::launch_lbfgs_move_rows64(c3d::fire64(c->fire), rows, np, dc, mask, slot, x, xo, f, h, d, c->stream);
+                                       });
+    return lbfgs_move_rows<float>(c, rows, coef, slot, in, out, "L-BFGS move rows launch",
+                                  [&](int np, const float* dc, const float* x, float* xo, const float* f, float* h, float* d) {
+                                      return c3d::launch_lbfgs_move_rows(dev_fire(c), rows, np, dc, mask, slot, x, xo, f, h, d, c->stream);
+                                  });
 }
 
 // name of the kernel the last op of the last range ran on, as rocprofv3 prints it (without the argument list): the record its launch was made from

@@ -260,6 +260,28 @@ hipError_t launch_step_scalars(const DevModel& m, const DevStep& p, const DevFir
     return hipGetLastError();
 }
 
+// ---- the row update as a table (c3d_debug_row_finish) -----------------------------------------------------------------------------
+// finish_row — what k_update_sym above, k_step, k_cluster and k_cluster_tp call once per row and step — on `rows` independent rows, a
+// thread a row.  in [rows][16] = x0[3], v0[3], F[3], lam, cmx, cmy, cmz, keep, mix, st.dt; out [rows][10] = xn[3], vn[3], q.x .. q.w.
+__global__ void k_row_finish(DevModel m, DevStep p, DevFire fp, int rows, const float* __restrict__ in, float* __restrict__ out) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= rows) return;
+    const float* a = in + kRowFinishIn * (size_t)r;
+    StepScalars sc;
+    sc.lam = a[9]; sc.cmx = a[10]; sc.cmy = a[11]; sc.cmz = a[12]; sc.keep = a[13]; sc.mix = a[14];
+    FireState st;
+    st.dt = a[15]; st.alpha = 0.0f; st.npos = 0; st.pad = 0;
+    float xn, yn, zn, vx, vy, vz;
+    float4 q;
+    finish_row(m, p, fp, sc, st, a[6], a[7], a[8], a[0], a[1], a[2], a[3], a[4], a[5], xn, yn, zn, vx, vy, vz, q);
+    float* o = out + kRowFinishOut * (size_t)r;
+    o[0] = xn; o[1] = yn; o[2] = zn; o[3] = vx; o[4] = vy; o[5] = vz; o[6] = q.x; o[7] = q.y; o[8] = q.z; o[9] = q.w;
+}
+hipError_t launch_row_finish(const DevModel& m, const DevStep& p, const DevFire& fp, int rows, const float* in, float* out, hipStream_t s) {
+    hipLaunchKernelGGL(k_row_finish, dim3((rows + 63) / 64), dim3(64), 0, s, m, p, fp, rows, in, out);
+    return hipGetLastError();
+}
+
 hipError_t preload_sym_unit() {
     hipFuncAttributes a;
     return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_update_sym<0>));

@@ -77,7 +77,9 @@ SIGNATURES = {
     "c3d_debug_step_scalars": (_i, [_vp, _i, _f, _f, _i, _fp, _fp, _i32p, _fp, _fp, _i32p]),
     "c3d_debug_step_scalars_f64": (_i, [_vp, _i, _d, _d, _i, _dp, _dp, _i32p, _dp, _dp, _i32p]),
     "c3d_debug_row_finish_f64": (_i, [_vp, _i, _d, _i, _dp, _dp]),
+    "c3d_debug_row_finish": (_i, [_vp, _i, _f, _i, _fp, _fp]),
     "c3d_debug_lbfgs_direction": (_i, [_vp, _i, _dp, _i32p, _dp, _i32p, _i32p, _i32p, _dp, _dp, _i32p]),
+    "c3d_debug_lbfgs_move_rows": (_i, [_vp, _i, _dp, _i, _i, _dp, _dp]),
     "c3d_dg_smoothed_bounds": (_i, [_vp, _fp, _fp]),
     "c3d_debug_if_ranks": (_i, [_vp, _dp, _i, _dp, _dp, C.POINTER(C.c_size_t)]),
     "c3d_eval": (_i, [_vp, _f, _f, _f, _fp, _dp]),
@@ -122,6 +124,7 @@ BEAD_FIELDS = 3                               # C3D_BEAD_FIELDS
 ACCESS_MAX_POINTS = 1024                      # C3D_ACCESS_MAX_POINTS
 COMPARTMENT_MAX_VECTORS, COMPARTMENT_MAX_ITERS, COMPARTMENT_CONSENSUS = 3, 10000, 1      # C3D_COMPARTMENT_*
 LBFGS_MAX_PAIRS, LBFGS_SUMS, LBFGS_STATE_DOUBLES, LBFGS_COEFS = 8, 36, 129, 17      # C3D_LBFGS_*
+LBFGS_MOVE_ROW_IN, LBFGS_MOVE_ROW_OUT = 54, 10                                       # C3D_LBFGS_MOVE_ROW_*
 ROW_FINISH_IN, ROW_FINISH_OUT = 16, 10                                               # C3D_ROW_FINISH_*
 
 _lib = None

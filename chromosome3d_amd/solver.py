@@ -239,6 +239,26 @@ class Solver:
         _l.check(self._L.c3d_debug_row_finish_f64(self._h, int(kind), float(dt), K, _l.dptr(rows), _l.dptr(out)))
         return out
 
+    def debug_row_finish(self, kind, dt, rows):
+        """The fp32 row update as a table (c3d_debug_row_finish): debug_row_finish_f64's rows in floats, through finish_row."""
+        rows = _l.as_f32(rows)
+        K = rows.shape[0]
+        assert rows.shape == (K, _l.ROW_FINISH_IN)
+        out = np.empty((K, _l.ROW_FINISH_OUT), dtype=np.float32)
+        _l.check(self._L.c3d_debug_row_finish(self._h, int(kind), float(dt), K, _l.fptr(rows), _l.fptr(out)))
+        return out
+
+    def debug_lbfgs_move_rows(self, coef, mask, slot, rows):
+        """The rows of an L-BFGS move as a table (c3d_debug_lbfgs_move_rows), in the context's precision: coef [17] = (gamma, a_j, b_j by
+        slot), the slot mask, the slot of s, rows [K, 54] = x[3], F[3], s_j[3] x 8, y_j[3] x 8 -> [K, 10] = new x[3], ring slot `slot`
+        [3], ring slot (slot + 1) % 8 [3], move.move."""
+        coef, rows = np.ascontiguousarray(coef, dtype=np.float64), np.ascontiguousarray(rows, dtype=np.float64)
+        K = rows.shape[0]
+        assert coef.shape == (_l.LBFGS_COEFS,) and rows.shape == (K, _l.LBFGS_MOVE_ROW_IN)
+        out = np.empty((K, _l.LBFGS_MOVE_ROW_OUT), dtype=np.float64)
+        _l.check(self._L.c3d_debug_lbfgs_move_rows(self._h, K, _l.dptr(coef), int(mask), int(slot), _l.dptr(rows), _l.dptr(out)))
+        return out
+
     def debug_lbfgs_direction(self, sums, state_int, state_dbl, first, mem0):
         """The serial section of the L-BFGS move as a table (c3d_debug_lbfgs_direction), in the context's precision: sums [K, 36], state_int
         [K, 4] = (cnt, head, mem, resets), state_dbl [K, 129] = (gamma, S'Y [8, 8], Y'Y [8, 8]), first [K], mem0 [K] -> (state_int out,

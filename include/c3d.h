@@ -362,6 +362,15 @@ int c3d_debug_step_scalars(c3d_ctx* ctx, int kind, float dt, float t_bath, int r
 int c3d_debug_step_scalars_f64(c3d_ctx* ctx, int kind, double dt, double t_bath, int rows, const double* psum, const double* state_in,
                                const int32_t* npos_in, double* scalars, double* state_out, int32_t* npos_out);
 int c3d_debug_row_finish_f64(c3d_ctx* ctx, int kind, double dt, int rows, const double* in, double* out);
+/* Test hook: the fp32 row update as a table — finish_row, the function every fp32 step kernel (k_cluster, k_cluster_tp, k_step,
+ * k_update_sym) calls once per row and step, a thread a row under the context's own model and FIRE values (418.4 / mass and max_step as
+ * floats; the kernel forms dt 418.4 / mass itself).  Kinds and the row layout are c3d_debug_row_finish_f64's, in floats: in[16 r ..] =
+ * x[3], v[3], F[3], lambda, v_cm[3], keep, mix, dt of the FIRE state -> out[10 r ..] = new x[3], new v[3], the bead's terms of the four
+ * sums.  Domain: the capped move d (FIRE: dt v'; two-point: mix F, and lambda v of the previous move) with |d| < 2^63 in every
+ * component, so that d.d is a finite float; beyond it the cap's 1 / sqrt(d.d) is 0 and the bead stays where it is (a component of d
+ * that is itself infinite gives NaN), while v' and the sums are formed as everywhere.
+ * Refuses (C3D_ERR_INVALID) other kinds and rows outside 1 .. 2^20; needs the bead count (targets set) and touches nothing of the solve. */
+int c3d_debug_row_finish(c3d_ctx* ctx, int kind, float dt, int rows, const float* in, float* out);
 /* Test hook: the serial section of an L-BFGS move (stage kind 8) as a table.  Between its two barriers one thread of every workgroup of
  * the move kernel decides the step from the replica's sums: the pair test s.y > 1e-12 sqrt(s.s y.y), the ring of lbfgs_memory slots,
  * gamma (s.y / y.y after a kept pair, doubled after a rejected one, clamped to [1e-7, 1e2]), the two triangular solves of the compact form
@@ -382,6 +391,19 @@ int c3d_debug_row_finish_f64(c3d_ctx* ctx, int kind, double dt, int rows, const 
 int c3d_debug_lbfgs_direction(c3d_ctx* ctx, int rows, const double* sums, const int32_t* state_int_in, const double* state_dbl_in,
                               const int32_t* first, const int32_t* mem0, int32_t* state_int_out, double* state_dbl_out, double* coef,
                               int32_t* mask_slot);
+/* Test hook: the rows of an L-BFGS move as a table, in the context's precision (as c3d_debug_lbfgs_direction: floats, or doubles on a
+ * precision-64 context).  After the serial section every bead of the move forms its direction gamma F + sum a_j s_j + sum b_j y_j over the
+ * slots of the mask, caps it at max_step, moves, writes the move s into ring slot `slot` and forms its move.move; the statements run are
+ * the one source text both move kernels include, a thread a row over a ring laid out as theirs.  coef[17] = (gamma, a_j, b_j by slot),
+ * mask (bit j: slot j is in the direction) and slot are the call's, as they are a replica's in a move.
+ * Row r in: in[54 r ..] = x[3], F[3], s_j[3] for j = 0 .. 7, y_j[3] for j = 0 .. 7 (narrowed to floats on an fp32 context: pass
+ * float-exact values there).  Row r out: out[10 r ..] = new x[3], ring slot `slot` read back [3], ring slot (slot + 1) % 8 read back [3]
+ * (untouched by the move), move.move.  A ring slot outside the mask is never read.
+ * Domain of the fp32 cap: the direction d finite (d.d may be beyond a float: it is then rescaled before the square root).
+ * Refuses (C3D_ERR_INVALID) slot outside 0 .. 7, mask outside 0 .. 255, rows outside 1 .. 2^16; touches nothing of the solve. */
+#define C3D_LBFGS_MOVE_ROW_IN (6 + 6 * C3D_LBFGS_MAX_PAIRS)
+#define C3D_LBFGS_MOVE_ROW_OUT 10
+int c3d_debug_lbfgs_move_rows(c3d_ctx* ctx, int rows, const double* coef, int mask, int slot, const double* in, double* out);
 /* Test hook of A7 (c3d_embed_replicas): U, L (n*n each, row-major) = the smoothed distance bounds the embedding draws its trial distances
  * from — b0 on |i-j| = 1, the target on restrained pairs, [r0_rep x the last stage's repel, 1e30] elsewhere, then all-pairs shortest
  * paths on U, the inverse triangle inequality on L, L <= U.  The same kernels and arguments as the embedding; no bead limit of its own.

@@ -578,12 +578,20 @@ def table_rows64(kind, t_fac):
     return rows
 
 
-def row_finish_ref(kind, dt, row, consts, fire, mut=None, hits=None):
-    """One row of c3d_debug_row_finish_f64: the per-bead statements of c3o_md_step, c3o_fire_step and c3o_bb_step (oracle/c3d_oracle.c) and the
-    bead's terms of the four sums the next step reads, in float64, one correctly rounded operation per oracle operation.  row (16) = x[3], v[3],
-    F[3], lambda, cm[3], keep, mix, state dt; consts = table_consts64 (acc = dt 418.4 / mass and dt_state (418.4 / mass) as step64 and the
-    kernel form them).  Returns [x'[3], v'[3], q[4]].  mut: one name of TABLE_MUTATIONS; hits: a Counter of the branches taken."""
-    kacc, mass = float(consts[2]), float(consts[4])
+def row_finish_ref(kind, dt, row, consts, fire, mut=None, hits=None, precision=64, probe=None):
+    """One row of c3d_debug_row_finish_f64 (precision 64) or c3d_debug_row_finish (32): the per-bead statements of c3o_md_step, c3o_fire_step
+    and c3o_bb_step (oracle/c3d_oracle.c) and the bead's terms of the four sums the next step reads, in float64, one correctly rounded
+    operation per oracle operation.  row (16) = x[3], v[3], F[3], lambda, cm[3], keep, mix, state dt.  precision 64: consts = table_consts64
+    (acc = dt 418.4 / mass and dt_state (418.4 / mass) as step64 and the kernel form them).  precision 32: consts = table_consts, whose
+    third entry is the host's float F32(418.4) / F32(mass); dt is the float the step holds, and dt acc, dt_state acc are the real products of
+    those floats (the row's values are floats already).  Returns [x'[3], v'[3], q[4]].  mut: one name of TABLE_MUTATIONS; hits: a Counter of
+    the branches taken; probe: a dict that receives the squared length each cap tested ("move_d2", "s_d2")."""
+    kacc = float(consts[2])
+    if precision == 32:
+        dt = float(F32(dt))
+        md_acc = dt * kacc
+    else:
+        md_acc = dt * 418.4 / float(consts[4])
     r = [float(a) for a in row]
     x, v, F = r[0:3], r[3:6], r[6:9]
     lam, cm, keep, mix, sdt = r[9], r[10:13], r[13], r[14], r[15]
@@ -596,6 +604,8 @@ def row_finish_ref(kind, dt, row, consts, fire, mut=None, hits=None):
 
     def cap(d, which):
         d2 = d[0] * d[0] + d[1] * d[1] + d[2] * d[2]
+        if probe is not None:
+            probe[which + "_d2"] = d2
         over = (d2 >= ms2) if mut == "cap_ge" else (d2 > ms2)
         hit(which + ("_at_cap" if d2 == ms2 else ("_capped" if d2 > ms2 else "_uncapped")))
         if not over:
@@ -610,7 +620,7 @@ def row_finish_ref(kind, dt, row, consts, fire, mut=None, hits=None):
             q = [vn[0] * vn[0] + vn[1] * vn[1] + vn[2] * vn[2], vn[0], vn[1], vn[2]]
         elif kind in (0, 1):
             hit("md")
-            acc = dt * 418.4 / mass
+            acc = md_acc
             vn = [lam * ((v[k] - cm[k]) if mut != "no_cm" else v[k]) + acc * F[k] for k in range(3)]
             xn = [x[k] + dt * vn[k] for k in range(3)]
             q = [vn[0] * vn[0] + vn[1] * vn[1] + vn[2] * vn[2], vn[0], vn[1], vn[2]]
@@ -639,6 +649,7 @@ def row_finish_ref(kind, dt, row, consts, fire, mut=None, hits=None):
     return xn + vn + q
 
 
+SEED_EDGE_D2 = (2.0 ** 127, 2.0 ** 128, 1e40, 1e150, 1e300)
 _U = (0.6, -0.64, 0.48)                     # the direction of the tuned rows: every component in play, |u| = 1 to a rounding
 _X0 = (1.5, -2.5, 3.5)                      # coordinates on the displacement's side of 0: x + (capped move) does not cancel
 
@@ -761,4 +772,293 @@ def row_finish_rows(kind, dt, consts, fire):
                 v = -v                                                    # v' = keep v + (mix + acc) F: one sign
             add(row(-sg * rng.uniform(1.0, 4.0, 3), v if kind not in (3, 6) else 0.0 * v, F, lam=0.9 if kind < 5 else 0.02, cm=(0.01, -0.02, 0.03) if kind < 2 else (0.0, 0.0, 0.0),
                     keep=0.7, mix=0.02 if kind >= 5 else 0.1))
+    # the capped quantity either side of the range of the cap's float seed (v_rsq_f32 of (float)d.d is 0 from 2^128 on): d.d in A^2
+    if kind in (2, 3, 5, 6):
+        for d2 in SEED_EDGE_D2:
+            mag = float(np.sqrt(d2))
+            for x0 in (_X0, (0.0, 0.0, 0.0)):
+                if kind in (2, 3):
+                    for keep, mix in ((0.7, 0.7), (0.0, 0.0)):
+                        S = mag / (sdt * (0.5 * keep + mix + sdt * kacc))
+                        add(row(x0, [0.5 * S * u for u in _U], [S * u for u in _U], keep=keep, mix=mix))
+                else:
+                    for a_prev, a in ((0.7, 0.7), (1.0, 1e2)):
+                        F = [-mag / a * u for u in _U]
+                        add(row([-c for c in x0], (0.0, 0.0, 0.0) if kind == 6 else (0.3, -0.2, 0.1), F, lam=a_prev, mix=a))
+                        if kind == 5:
+                            add(row([-c for c in x0], [mag / a_prev * u for u in _U], F, lam=a_prev, mix=a))
+                            add(row([-c for c in x0], [mag / a_prev * u for u in _U], [-0.1 * u for u in _U], lam=a_prev, mix=a))
     return rows
+
+
+# ---------------------------------------------------------------------------------------------
+# the fp32 row update as a table (c3d_debug_row_finish): finish_row, c3d_step_core.h
+# ---------------------------------------------------------------------------------------------
+FLT_MAX, FLT_MIN, FLT_DENORMAL = float(np.finfo(np.float32).max), float(np.finfo(np.float32).tiny), float(F32(1e-42))
+_TWO128 = 2.0 ** 128                        # what stands for a float's infinity when a gap is measured: the float after FLT_MAX
+
+
+def f32(x):
+    return float(F32(x))
+
+
+def _next32(x, up=True):
+    return float(np.nextafter(F32(x), F32(np.inf if up else -np.inf)))
+
+
+def ulps32(got, want):
+    """|got - want| in units of the spacing of floats at want.  want is a float64 value of the restatement: one below the denormals counts in
+    units of the smallest denormal, one beyond FLT_MAX is the float's infinity, and an infinity counts as the float after FLT_MAX."""
+    got, want = float(got), float(want)
+    if got == want:
+        return 0.0
+    if got != got or want != want:
+        return float("inf")
+    g, w = max(min(got, _TWO128), -_TWO128), max(min(want, _TWO128), -_TWO128)
+    return abs(g - w) / float(np.spacing(F32(min(abs(w), _next32(FLT_MAX, False)))))
+
+
+def _cross32(fn, lo, hi, target):
+    """the adjacent floats (z0, z1) in [lo, hi] (positive, fn non-decreasing there) with fn(z0) <= target < fn(z1)"""
+    a, b = int(F32(lo).view(np.int32)), int(F32(hi).view(np.int32))
+    assert fn(f32(lo)) <= target < fn(f32(hi)), (fn(f32(lo)), target, fn(f32(hi)))
+    while b - a > 1:
+        mid = (a + b) // 2
+        if fn(float(np.int32(mid).view(np.float32))) > target:
+            b = mid
+        else:
+            a = mid
+    z0, z1 = float(np.int32(a).view(np.float32)), float(np.int32(b).view(np.float32))
+    assert fn(z0) <= target < fn(z1) and _next32(z0) == z1
+    return z0, z1
+
+
+ROW_TAGS32 = ("plain", "capped", "overflow", "beyond", "beyond_s", "infinite")
+_K7 = f32(0.7)
+
+
+def row_finish_rows32(kind, dt, consts, fire):
+    """[(row16, tag)] of a kind for c3d_debug_row_finish: row_finish_rows' structure with every input exactly a float32.  consts =
+    table_consts.  tag: "plain" (no cap acted), "capped", and beyond what a float carries
+      "overflow"  the capped quantity d finite and d.d at most one float below FLT_MAX (held as a capped row),
+      "beyond"    d finite and d.d beyond FLT_MAX (the move), "beyond_s" the same for kind 5's previous move, "infinite" mix F itself infinite.
+    The capped quantity of a kind (FIRE: dt v'; two-point: mix F, and lambda v of the previous move) sits on the two adjacent floats of one
+    component between which the restatement's d.d crosses max_step^2, at 0, the smallest normal float, a denormal, and 2 and 1e8 max_step
+    (d.d = 4 and 1e16 max_step^2); F = 0, F with a -0, F with a NaN; lambda in {0, 1, 0.93}, keep / mix in {0, 0.7}; kind 5: both caps on
+    either side independently.  Every tuned row stands twice: beside _X0 and at x = 0, where the displacement itself is the output."""
+    from collections import Counter
+    acc = float(consts[2])
+    ms = float(fire.max_step)
+    ms2 = ms * ms
+    sdt = 0.03125
+    rows = []
+    mags = (0.0, FLT_MIN, FLT_DENORMAL, 0.5 * ms, 2.0 * ms, 1e8 * ms)          # |d| of the rows that are not at the edge
+
+    def row(x, v, F, lam=1.0, cm=(0.0, 0.0, 0.0), keep=0.0, mix=0.0, st=sdt):
+        return [f32(a) for a in list(x) + list(v) + list(F) + [lam] + list(cm) + [keep, mix, st]]
+
+    def add(r, tag=None):
+        if tag is None:
+            h = Counter()
+            row_finish_ref(kind, dt, r, consts, fire, hits=h, precision=32)
+            tag = "capped" if (h["move_capped"] or h["s_capped"]) else "plain"
+        rows.append((r, tag))
+
+    def add2(sign, v, F, **kw):
+        """a tuned row beside _X0 (on the move's side of 0: sign) and at x = 0"""
+        add(row([sign * c for c in _X0], v, F, **kw))
+        add(row((0.0, 0.0, 0.0), v, F, **kw))
+
+    def probe_d2(r, which):
+        p = {}
+        row_finish_ref(kind, dt, r, consts, fire, precision=32, probe=p)
+        return p[which]
+
+    if kind in (2, 3):
+        for keep, mix in ((0.0, 0.0), (_K7, _K7), (_K7, 0.0), (0.0, _K7)):
+            gain = mix + sdt * acc
+            S = 0.98 * ms / (sdt * (0.5 * keep + gain))
+            mk = lambda z, S=S, keep=keep, mix=mix: row(_X0, [0.5 * S * u for u in _U], [S * _U[0], S * _U[1], z], keep=keep, mix=mix)
+            for z in _cross32(lambda z: probe_d2(mk(z), "move_d2"), 0.5 * S * _U[2], 4.0 * S * _U[2], ms2):
+                r = mk(z)
+                add2(1.0, r[3:6], r[6:9], keep=keep, mix=mix)
+            for mag in mags:
+                S = mag / (sdt * (0.5 * keep + gain))
+                add2(1.0, [0.5 * S * u for u in _U], [S * u for u in _U], keep=keep, mix=mix)
+            add(row(_X0, (0.3, -0.2, 0.1), (0.0, 0.0, 0.0), keep=keep, mix=mix))
+            add(row(_X0, (0.3, -0.2, 0.1), (1.5, -0.0, 2.5), keep=keep, mix=mix))
+            add(row(_X0, (0.3, -0.2, 0.1), (1.5, NAN, 2.5), keep=keep, mix=mix))
+    elif kind in (5, 6):
+        sides = [("edge", 0), ("edge", 1)] + [("free", mag) for mag in mags]
+
+        def tuned(length, what):
+            """a float vector w along _U with |length w| = what[1] ("free"), or on the lower / upper float of the crossing of max_step^2 ("edge")"""
+            length = f32(length)
+            if what[0] == "free":
+                return [f32(what[1] / length * u) for u in _U]
+            S = 0.98 * ms / length
+            c0, c1 = f32(S * _U[0]), f32(S * _U[1])
+            z = _cross32(lambda z: _d2([length * c0, length * c1, length * z]), 0.5 * S * _U[2], 4.0 * S * _U[2], ms2)[what[1]]
+            return [c0, c1, z]
+
+        for a_prev, a in ((1e-5, 3e-5), (0.7, 0.7), (1.0, 1e2), (0.0, 1e-7)):
+            for mv in sides:
+                F = [-c for c in tuned(a, mv)]                            # the move is along -_U, x0 on that side of 0
+                if kind == 6:
+                    add2(-1.0, (0.0, 0.0, 0.0), F, lam=a_prev, mix=a)
+                    continue
+                for sv in (sides if a_prev > 0 else [("free", 2.0 * ms)]):
+                    # (a previous move at the foot of float's range is a denormal float: its error is 2^-150 whatever its size, and s.y carries
+                    #  that times |y|, so no bound in ulps of s.y holds unless y = F_old - F is as small: such an s meets such moves only)
+                    if sv[0] == "free" and 0.0 < sv[1] <= FLT_MIN and not (mv[0] == "free" and mv[1] <= FLT_MIN):
+                        continue
+                    v = tuned(a_prev, sv) if a_prev > 0 else [3.0 * u for u in _U]
+                    add2(-1.0, v, F, lam=a_prev, mix=a)
+        for a_prev, a in ((1e-5, 3e-5), (0.7, 0.7)):
+            v = (0.0, 0.0, 0.0) if kind == 6 else (0.3, -0.2, 0.1)
+            add(row(_X0, v, (0.0, 0.0, 0.0), lam=a_prev, mix=a))
+            add(row(_X0, v, (1.5, -0.0, 2.5), lam=a_prev, mix=a))
+            add(row(_X0, v, (1.5, NAN, 2.5), lam=a_prev, mix=a))
+    else:
+        step = float(F32(dt)) if kind != 4 else sdt
+        for lam in (0.0, 1.0, 0.93):
+            for cm in ((0.0, 0.0, 0.0), (0.01, -0.02, 0.03)):
+                for mag in mags:
+                    S = mag / step
+                    add2(1.0, [S * u for u in _U], [0.5 * S * u for u in _U], lam=lam, cm=cm)
+                add(row(_X0, (0.3, -0.2, 0.1), (0.0, 0.0, 0.0), lam=lam, cm=cm))
+                add(row(_X0, (0.3, -0.2, 0.1), (1.5, -0.0, 2.5), lam=lam, cm=cm))
+                add(row(_X0, (0.3, -0.2, 0.1), (1.5, NAN, 2.5), lam=lam, cm=cm))
+    # vectors that are not parallel (a swapped component shows), in one sign pattern so that no sum of a capped row cancels: plain and capped
+    rng = np.random.default_rng(3200 + kind)
+    sg = np.array([1.0, -1.0, 1.0])
+    for big in (False, True):
+        for _ in range(8):
+            v = sg * rng.uniform(0.2, 1.0, 3) * (40.0 * ms / sdt if big else 0.01)
+            F = -sg * rng.uniform(0.2, 1.0, 3) * (40.0 * ms / sdt if big else 0.01)
+            if kind in (2, 3):
+                v = -v                                                    # v' = keep v + (mix + acc) F: one sign
+            add(row(-sg * rng.uniform(1.0, 4.0, 3), v if kind not in (3, 6) else 0.0 * v, F, lam=0.9 if kind < 5 else 0.02, cm=(0.01, -0.02, 0.03) if kind < 2 else (0.0, 0.0, 0.0),
+                    keep=_K7, mix=0.02 if kind >= 5 else 0.1))
+    if kind not in (2, 3, 5, 6):
+        return rows
+    # Beyond what a float carries.  The vectors lie along one axis and meet only the factor 1 (FIRE: keep 1, no force, state dt 1; two-point:
+    # length 1), so that the device's d is the row's own float and its d.d that float's square rounded once: finite below the edge
+    # whatever the rounding.  zmax = the float whose square, rounded to float, is the float below FLT_MAX (the next float's is beyond it).
+    zmax = f32(np.sqrt(np.float64(FLT_MAX)))
+    while f32(zmax * zmax) >= FLT_MAX:
+        zmax = _next32(zmax, False)
+    assert f32(zmax * zmax) == _next32(FLT_MAX, False) and _next32(zmax) ** 2 > FLT_MAX
+    zero = (0.0, 0.0, 0.0)
+
+    def axis(k, z):
+        return [z * sg[k] if j == k else 0.0 for j in range(3)]
+
+    for k in range(3):
+        for z, tag in ((zmax, "overflow"), (2.0 ** 64, "beyond"), (1e30, "beyond")):
+            for x0 in (_X0, zero):
+                if kind in (2, 3):
+                    add(row(x0, axis(k, z), zero, keep=1.0, mix=0.0, st=1.0), tag)
+                else:
+                    add(row([-c for c in x0], zero, axis(k, -z), lam=1.0, mix=1.0), tag)
+                    if kind == 5:
+                        add(row(x0, axis(k, z), zero, lam=1.0, mix=1.0), "overflow" if tag == "overflow" else "beyond_s")
+        if kind in (5, 6):
+            for x0 in (_X0, zero):
+                add(row([-c for c in x0], zero, axis(k, -1e37), lam=1.0, mix=1e2), "infinite")
+    # (all three components in play: 2^-18 below FLT_MAX, further than the device's three roundings of d.d can carry it)
+    S = float(np.sqrt(FLT_MAX * (1.0 - 2.0 ** -18)))
+    for x0 in (_X0, zero):
+        if kind in (2, 3):
+            add(row(x0, [S * u for u in _U], zero, keep=1.0, mix=0.0, st=1.0), "overflow")
+        else:
+            add(row([-c for c in x0], zero, [-S * u for u in _U], lam=1.0, mix=1.0), "overflow")
+    return rows
+
+
+def finish_row_emulated32(kind, dt, row, consts, fire, rsq_shift=0):
+    """finish_row (c3d_step_core.h) statement by statement in float32 — every fmaf an exact product plus sum rounded once, every other
+    operation rounded once, v_rsq_f32 as the rounded 1 / sqrt moved by rsq_shift floats (its documented accuracy is 1 ulp).  Not the
+    expected values: what tests/test_controller_ref.py runs against row_finish_ref to admit the table's bounds without a device."""
+    f = F32
+    fma = lambda a, b, c: f(np.float64(a) * np.float64(b) + np.float64(c))
+    mul = lambda a, b: f(np.float64(a) * np.float64(b))
+    sub = lambda a, b: f(np.float64(a) - np.float64(b))
+
+    def rsq(x):
+        y = f(1.0 / np.sqrt(np.float64(x)))
+        for _ in range(abs(rsq_shift)):
+            y = np.nextafter(y, f(np.inf if rsq_shift > 0 else 0.0))
+        return y
+
+    r = [f(a) for a in row]
+    x, v, F = r[0:3], r[3:6], r[6:9]
+    lam, cm, keep, mix, sdt = r[9], r[10:13], r[13], r[14], r[15]
+    acc, ms, dt = f(consts[2]), f(fire.max_step), f(dt)
+    dot = lambda a, b: fma(a[0], b[0], fma(a[1], b[1], mul(a[2], b[2])))
+    with np.errstate(all="ignore"):
+        if kind == 4:
+            vn, xn = list(v), list(x)
+            q = [dot(vn, vn), vn[0], vn[1], vn[2]]
+        elif kind in (0, 1):
+            a = mul(dt, acc)
+            vn = [fma(a, F[k], mul(lam, sub(v[k], cm[k]))) for k in range(3)]
+            xn = [fma(dt, vn[k], x[k]) for k in range(3)]
+            q = [dot(vn, vn), vn[0], vn[1], vn[2]]
+        elif kind in (5, 6):
+            ms2 = mul(ms, ms)
+            q = [f(0.0), dot(F, F), f(0.0), f(0.0)]
+            if kind == 5:
+                s = [mul(lam, v[k]) for k in range(3)]
+                s2 = dot(s, s)
+                scp = mul(ms, rsq(s2)) if s2 > ms2 else f(1.0)
+                s = [mul(a, scp) for a in s]
+                y = [sub(v[k], F[k]) for k in range(3)]
+                q = [dot(s, y), q[1], dot(y, y), dot(s, s)]
+            d = [mul(mix, F[k]) for k in range(3)]
+            d2 = dot(d, d)
+            scl = mul(ms, rsq(d2)) if d2 > ms2 else f(1.0)
+            xn = [fma(scl, d[k], x[k]) for k in range(3)]
+            vn = list(F)
+        else:
+            q = [dot(v, F), dot(F, F), dot(v, v), f(0.0)]
+            a = mul(sdt, acc)
+            vn = [fma(a, F[k], fma(keep, v[k], mul(mix, F[k]))) for k in range(3)]
+            d = [mul(sdt, vn[k]) for k in range(3)]
+            d2 = dot(d, d)
+            scl = mul(ms, rsq(d2)) if d2 > mul(ms, ms) else f(1.0)
+            xn = [fma(scl, d[k], x[k]) for k in range(3)]
+    return [float(a) for a in xn + vn + q]
+
+
+def row_gap32(got, want, tag, row):
+    """The table's assertion on one row, shared by the CPU admission and the device test: got (10 floats) against row_finish_ref's want
+    under the row's tag.  Returns the row's largest gap in float ulps (over what a bound holds); raises AssertionError with the figures.
+      plain 4, capped and overflow 8 float ulps of the expected value; NaN where the restatement has NaN; a zero with the restatement's sign
+      beyond / beyond_s / infinite: v' and the sums as the restatement within 8 — except what the dead cap itself feeds: the coordinates
+      (beyond: x' = x exactly, the bead stays; infinite: NaN in the component whose move is infinite, x elsewhere) and, for beyond_s, the
+      two sums made of the previous move (s.y and s.s are 0: the rebuilt move is scaled by 1 / sqrt(inf) = 0)."""
+    cap = ROW_CAPS32[tag]
+    worst = 0.0
+    for j, (g, w) in enumerate(zip(got, want)):
+        g = float(g)
+        if tag in ("beyond", "infinite") and j < 3:
+            moves_inf = tag == "infinite" and abs(float(row[14]) * float(row[6 + j])) > FLT_MAX
+            assert (g != g) if moves_inf else (g == row[j]), (tag, j, g, row)
+            continue
+        if tag == "beyond_s" and j in (6, 9):
+            assert g == 0.0, (tag, j, g, row)
+            continue
+        if w != w:
+            assert g != g, (tag, j, g, w, row)
+            continue
+        if w == 0.0:
+            assert g == 0.0 and np.signbit(g) == np.signbit(w), (tag, j, g, w, row)
+            continue
+        u = ulps32(g, w)
+        assert u <= cap, (tag, j, g, w, u, cap, row)
+        worst = max(worst, u)
+    return worst
+
+
+ROW_CAPS32 = {"plain": 4.0, "capped": 8.0, "overflow": 8.0, "beyond": 8.0, "beyond_s": 8.0, "infinite": 8.0}

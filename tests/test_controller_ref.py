@@ -365,3 +365,167 @@ def test_fp64_row_restatement_is_the_oracles_step(built):
             x, v = out[:, 0:3], out[:, 3:6]
             sums = tuple(out[:, 6 + k].sum() for k in range(4))
         assert np.abs(x - x.mean(0) - xo).max() < 1e-12 and np.abs(v - vo).max() < 1e-12 * np.abs(vo).max(), stage_kind
+
+
+# ---------------------------------------------------------------------------------------------
+# the fp32 row table (tests/test_gpu_row_finish_table.py runs it on the device): admitted here, without one
+# ---------------------------------------------------------------------------------------------
+def _table32():
+    from chromosome3d_amd import default_fire, default_model
+    m, fire = default_model(**R.TABLE_MODEL), default_fire(**R.TABLE_FIRE)
+    return R.table_consts(m, R.TABLE_N), fire
+
+
+def _probe32(kind, r, consts, fire):
+    from collections import Counter
+    h, p = Counter(), {}
+    out = R.row_finish_ref(kind, ROW_DT, r, consts, fire, precision=32, hits=h, probe=p)
+    return out, h, p
+
+
+def test_fp32_row_table_is_made_of_floats_and_takes_every_branch(built):
+    """every input is a float32; every tuned row stands beside _X0 and at x = 0; each cap on either side (kind 5: the four combinations);
+    at least 50 rows and, where there is a cap, 20 capped rows a kind; every tag the device test treats apart occurs"""
+    from collections import Counter
+    consts, fire = _table32()
+    assert float(fire.max_step) ** 2 == float(np.float32(fire.max_step) * np.float32(fire.max_step))      # F32(max_step)^2 is the device's float too
+    for kind in R.ROW_KINDS:
+        rows = R.row_finish_rows32(kind, ROW_DT, consts, fire)
+        assert 50 <= len(rows) <= 2048, (kind, len(rows))
+        tags, hits, combos, at_zero = Counter(t for _, t in rows), Counter(), set(), 0
+        for r, tag in rows:
+            assert tag in R.ROW_TAGS32 and all(a != a or float(np.float32(a)) == a for a in r), (kind, r)
+            _, h, _ = _probe32(kind, r, consts, fire)
+            hits.update(h)
+            combos.add((bool(h["s_capped"]), bool(h["move_capped"])))
+            at_zero += r[0:3] == [0.0, 0.0, 0.0]
+        assert at_zero >= 20, (kind, at_zero)
+        if kind in (2, 3, 5, 6):
+            assert tags["capped"] >= 20 and tags["overflow"] >= 6 and tags["beyond"] >= 6 and hits["move_uncapped"] and hits["move_capped"], (kind, tags)
+            assert (tags["infinite"] >= 6) == (kind in (5, 6)) and (tags["beyond_s"] >= 6) == (kind == 5)
+        else:
+            assert set(tags) == {"plain"} and hits["md" if kind != 4 else "md_begin"] == len(rows)
+        if kind == 5:
+            assert combos == {(False, False), (False, True), (True, False), (True, True)}
+        # F = 0, a -0 and a NaN among the forces; lambda and keep / mix at the issue's values
+        Fs = [r[6:9] for r, _ in rows]
+        assert any(F == [0.0, 0.0, 0.0] for F in Fs) and any(np.signbit(F[1]) and F[1] == 0.0 for F in Fs) and any(F[1] != F[1] for F in Fs)
+        if kind < 2:
+            assert {r[9] for r, _ in rows} >= {0.0, 1.0, R.f32(0.93)}
+        if kind in (2, 3):
+            assert {(r[13], r[14]) for r, _ in rows} >= {(0.0, 0.0), (R._K7, R._K7), (R._K7, 0.0), (0.0, R._K7)}
+
+
+def test_fp32_row_table_edges_are_at_the_edge(built):
+    """each capped quantity on two ADJACENT floats of one component between which the restatement's d.d crosses F32(max_step)^2, beside
+    _X0 and at 0; at 0, the smallest normal float, a denormal, 2 and 1e8 max_step; and at the float's own edge: d.d at most one float below
+    FLT_MAX with d finite, d.d beyond it with d finite, d itself infinite"""
+    consts, fire = _table32()
+    ms = float(fire.max_step)
+    ms2 = ms * ms
+    for kind in (2, 3, 5, 6):
+        rows = R.row_finish_rows32(kind, ROW_DT, consts, fire)
+        for which in (("move_d2",) if kind != 5 else ("move_d2", "s_d2")):
+            comp = 8 if which == "move_d2" else 5                                       # the tuned component: F's or v's third
+            below, above, sizes = {}, {}, set()
+            for r, tag in rows:
+                if tag not in ("plain", "capped"):
+                    continue
+                d2 = _probe32(kind, r, consts, fire)[2][which]
+                sizes.add(d2)
+                key = tuple(a for j, a in enumerate(r) if j != comp and a == a)
+                if 0.9 * ms2 < d2 <= ms2:
+                    below.setdefault(key, set()).add(abs(r[comp]))
+                if ms2 < d2 < 1.1 * ms2:
+                    above.setdefault(key, set()).add(abs(r[comp]))
+            pairs = [(lo, hi) for key in below if key in above for lo in below[key] for hi in above[key] if R._next32(lo) == hi]
+            assert len(pairs) >= (4 if kind != 5 else 8), (kind, which, len(pairs))      # every (keep, mix) / length pair, at both x0
+            assert 0.0 in sizes and any(0.0 < s <= 1.01 * R.FLT_MIN ** 2 for s in sizes) and any(0.0 < s < 1e-83 for s in sizes), (kind, which)
+            assert any(abs(s / ms2 - 4.0) < 1e-5 for s in sizes) and any(abs(s / ms2 - 1e16) < 1e10 for s in sizes), (kind, which)
+        edge = float(np.nextafter(np.float32(R.FLT_MAX), np.float32(0)))
+        seen = {"overflow": 0, "beyond": 0, "beyond_s": 0, "infinite": 0}
+        for r, tag in rows:
+            if tag in ("plain", "capped"):
+                continue
+            p = _probe32(kind, r, consts, fire)[2]
+            d2 = p["s_d2"] if (tag == "beyond_s" or (kind == 5 and tag == "overflow" and p["s_d2"] > 1.0)) else p["move_d2"]
+            if tag == "overflow":
+                assert 0.999 * R.FLT_MAX < d2 and R.f32(d2) <= edge, (kind, r, d2)
+                seen[tag] += R.f32(d2) == edge                                                  # one float below FLT_MAX: the axis rows
+            elif tag in ("beyond", "beyond_s"):
+                assert d2 > R.FLT_MAX and all(np.isfinite(np.float32(a)) for a in r), (kind, r, d2)
+                seen[tag] += 1
+            else:
+                assert max(abs(r[14] * a) for a in r[6:9]) > R.FLT_MAX and all(np.isfinite(np.float32(a)) for a in r), (kind, r)
+                seen[tag] += 1
+        assert seen["overflow"] >= 6 and seen["beyond"] >= 6, (kind, seen)
+
+
+@pytest.mark.parametrize("mut", ["cap_no_sqrt", "no_cm"])
+def test_fp32_row_table_catches_the_row_mutations(built, mut):
+    """the mutations of TABLE_MUTATIONS that change a row's outputs move some row of the fp32 table by at least 1000 float ulps — 125 times the
+    widest bound (">=" for ">" at the cap changes no output, as test_fp64_table_catches_every_mutation says, and the fp32 rows lie beside the
+    cap, not on it)"""
+    consts, fire = _table32()
+    worst = 0.0
+    for kind in R.ROW_KINDS:
+        for r, tag in R.row_finish_rows32(kind, ROW_DT, consts, fire):
+            if tag not in ("plain", "capped", "overflow"):
+                continue
+            a = R.row_finish_ref(kind, ROW_DT, r, consts, fire, precision=32)
+            b = R.row_finish_ref(kind, ROW_DT, r, consts, fire, precision=32, mut=mut)
+            worst = max([worst] + [R.ulps32(g, w) for g, w in zip(b, a) if w == w and g == g])
+    print(f"{mut} ({R.TABLE_MUTATIONS[mut]}): {worst:.3g} float ulps")
+    assert worst >= 1000.0, worst
+
+
+def test_fp32_row_bounds_hold_for_a_float_emulation_of_finish_row(built):
+    """finish_row restated in float32 (exact-product fma, one rounding an operation, v_rsq_f32 as the rounded 1 / sqrt moved -1, 0 and +1
+    float) against the float64 restatement under the table's own assertion: the arithmetic of the reference and of a correct device text
+    lies inside the bounds (plain 4, capped 8) with room to spare, and behaves beyond the domain as the device test asserts"""
+    consts, fire = _table32()
+    worst = {}
+    for kind in R.ROW_KINDS:
+        for r, tag in R.row_finish_rows32(kind, ROW_DT, consts, fire):
+            want = R.row_finish_ref(kind, ROW_DT, r, consts, fire, precision=32)
+            for shift in (-1, 0, 1):
+                worst[tag] = max(worst.get(tag, 0.0), R.row_gap32(R.finish_row_emulated32(kind, ROW_DT, r, consts, fire, shift), want, tag, r))
+    print({t: round(w, 2) for t, w in worst.items()})
+    assert worst["plain"] <= 3.5 and worst["capped"] <= 4.0 and worst["overflow"] <= 4.0, worst
+    # and a wrong text leaves them: the cap applied to the uncapped side, a swapped component
+    r, tag = next((r, t) for r, t in R.row_finish_rows32(2, ROW_DT, consts, fire) if t == "capped")
+    got = R.finish_row_emulated32(2, ROW_DT, r, consts, fire)
+    with pytest.raises(AssertionError):
+        R.row_gap32(got[:1] + [got[2], got[1]] + got[3:], R.row_finish_ref(2, ROW_DT, r, consts, fire, precision=32), tag, r)
+
+
+def test_row_restatement_precision_switch_leaves_the_fp64_table_alone(built):
+    """precision=32 changes only how dt acc is formed: on the fp64 table's constants the two agree wherever the products agree, and the default
+    is the fp64 form"""
+    consts, fire = _table64()
+    for kind in R.ROW_KINDS:
+        for r, _ in R.row_finish_rows(kind, ROW_DT, consts, fire)[:40]:
+            a, b = R.row_finish_ref(kind, ROW_DT, r, consts, fire), R.row_finish_ref(kind, ROW_DT, r, consts, fire, precision=64)
+            assert all(x == y or (x != x and y != y) for x, y in zip(a, b))
+
+
+def test_fp64_row_table_reaches_beyond_the_caps_float_seed(built):
+    """kinds 2, 3, 5, 6: the capped quantity (and kind 5's previous move) with d.d at 2^127, 2^128, 1e40, 1e150 and 1e300 A^2 — either side
+    of where v_rsq_f32 of (float)d.d turns 0 — beside _X0 and at x = 0, every such row a capped row whose restatement moves by max_step"""
+    consts, fire = _table64()
+    ms = float(fire.max_step)
+    assert R.SEED_EDGE_D2[0] < float(np.finfo(np.float32).max) < R.SEED_EDGE_D2[1]
+    for kind in (2, 3, 5, 6):
+        seen = {w: set() for w in ("move_d2", "s_d2")}
+        for r, tag in R.row_finish_rows(kind, ROW_DT, consts, fire):
+            p = {}
+            out = R.row_finish_ref(kind, ROW_DT, r, consts, fire, probe=p)
+            for w, d2 in p.items():
+                for t in R.SEED_EDGE_D2:
+                    if abs(d2 / t - 1.0) < 1e-9:
+                        assert tag == "capped", (kind, r)
+                        seen[w].add((t, any(r[0:3])))
+                        if w == "move_d2":
+                            assert abs(np.linalg.norm(np.array(out[0:3]) - np.array(r[0:3])) - ms) < 1e-12, (kind, r, out[:3])
+        want = {(t, at) for t in R.SEED_EDGE_D2 for at in (True, False)}
+        assert seen["move_d2"] == want and (kind != 5 or seen["s_d2"] == want), (kind, seen)

@@ -170,6 +170,9 @@ hipError_t launch_step64(const DevModel&, const Model64&, const Step64&, const F
 hipError_t launch_lbfgs_eval64(const DevModel&, const Model64&, const Step64&, const Form64&, const Buffers64&, const LbfgsBuffers64&, int, int, hipStream_t) { LaunchScope ls; return hipSuccess; }
 hipError_t launch_lbfgs_move64(const DevModel&, const Model64&, const Step64&, const Fire64&, const Buffers64&, const LbfgsBuffers64&, int, int, hipStream_t) { LaunchScope ls; return hipSuccess; }
 hipError_t launch_lbfgs_direction64(const Step64&, const Fire64&, int, const double*, const LbfgsState*, const int*, LbfgsState*, double*, int*, hipStream_t) { LaunchScope ls; return hipSuccess; }
+hipError_t launch_lbfgs_move_rows(const DevFire&, int, int, const float*, int, int, const float*, float*, const float*, float*, float*, hipStream_t) { LaunchScope ls; return hipSuccess; }
+hipError_t launch_lbfgs_move_rows64(const Fire64&, int, int, const double*, int, int, const double*, double*, const double*, double*, double*, hipStream_t) { LaunchScope ls; return hipSuccess; }
+hipError_t launch_row_finish(const DevModel&, const DevStep&, const DevFire&, int, const float*, float*, hipStream_t) { LaunchScope ls; return hipSuccess; }
 hipError_t launch_step_scalars64(const Model64&, const Step64&, const Fire64&, int, const double*, const void*, double*, void*, hipStream_t) { LaunchScope ls; return hipSuccess; }
 hipError_t launch_row_finish64(const Step64&, const Fire64&, int, const double*, double*, hipStream_t) { LaunchScope ls; return hipSuccess; }
 hipError_t launch_tenths64(int, int, const int32_t*, const int32_t*, const int32_t*, int32_t*, hipStream_t) { LaunchScope ls; return hipSuccess; }
