@@ -1,7 +1,7 @@
 // c3d_api.cpp — C-ABI host of libc3d.so: the context's lifetime, device buffers, targets (K1), start structures and the embedding,
-// coordinates in floats and doubles, c3d_eval*.  Compiled with hipcc (-x hip) for the HIP runtime API only, like the other four host units:
+// coordinates in floats and doubles, c3d_eval*.  Compiled with hipcc (-x hip) for the HIP runtime API only, like the other five host units:
 // c3d_config.cpp (model, schedule, options, stats), c3d_gate.cpp (code objects, the gate every entry runs under), c3d_run.cpp (schedule ->
-// launch program, its executor) and c3d_analysis.cpp (score, compare, superpose); c3d_ctx.h holds what they share.  The kernels live in
+// launch program, its executor), c3d_debug.cpp (the table test hooks) and c3d_analysis.cpp (score, compare, superpose); c3d_ctx.h holds what they share.  The kernels live in
 // c3d_device.hip (per-step), c3d_cluster.hip (multi-step), c3d_embed.hip, c3d_score.hip, c3d_f64.hip, c3d_sym.hip.
 #include <cstdlib>
 

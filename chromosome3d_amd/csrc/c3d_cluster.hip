@@ -289,7 +289,7 @@ __device__ __forceinline__ void cluster_body(
       if (run != run0) cur = runs[run];
       const DevStep p = cur.p;
       const int count = cur.count;
-      const bool needs_partials = p.kind == 0 || p.kind == 1 || p.kind == 2 || (TWO && p.kind == 5);
+      const bool needs_partials = p.kind == kMdCouple || p.kind == kMdRescale || p.kind == kFire || (TWO && p.kind == kTwoPoint);     // (kind_reads_sums written out, kind 5 in k_cluster_tp only)
       for (int it = run == run0 ? skip0 : 0; it < count; ++it, ++s) {
 #ifdef C3D_STAMPS
         if (cstamper && s == 0) g_pstamps[7] = __builtin_amdgcn_s_memrealtime();
@@ -306,7 +306,7 @@ __device__ __forceinline__ void cluster_body(
         sc.lam = 1.0f; sc.cmx = sc.cmy = sc.cmz = 0.0f; sc.keep = 0.0f; sc.mix = 0.0f;
         if constexpr (ROLE == 0) {
             // ---- K2: pair terms of RPW rows, butterfly sums, three words per row for H0 ------------------
-            if (p.kind != 4) {
+            if (p.kind != kMdBegin) {
                 float Fx, Fy, Fz;
                 if constexpr (PK) tile_pair_sums_pk<RPW, NB, WL>(m, p, pc, mw, xs, ys, zs, row0, lane, Fx, Fy, Fz);
                 else tile_pair_sums_reg<POT, RPW, NB, WL, 1>(m, p, tv, mw, xs, ys, zs, row0, lane, Fx, Fy, Fz);
@@ -318,7 +318,7 @@ __device__ __forceinline__ void cluster_body(
             }
         } else if constexpr (ROLE == 1) {
             // ---- replica sums of the previous step -> scalars of this one (only H0 needs them) -----------
-            if (p.kind != 2 && !(TWO && p.kind == 5)) { st.dt = fp.dt_start; st.alpha = fp.alpha_start; st.npos = 0; st.pad = 0; }
+            if (p.kind != kFire && !(TWO && p.kind == kTwoPoint)) { st.dt = fp.dt_start; st.alpha = fp.alpha_start; st.npos = 0; st.pad = 0; }     // (not kind_continues_state)
             float4 psum = make_float4(0, 0, 0, 0);
             if (needs_partials) {
                 if (late && !solo && s > 0) {
@@ -368,7 +368,7 @@ __device__ __forceinline__ void cluster_body(
             // this row's position: read now, the barrier below is long
             if (lane < RW && hrow < NPAD) { hx0 = xs[hrow]; hy0 = ys[hrow]; hz0 = zs[hrow]; }
             CSTAMP(1);                              // H0: sums + scalars done
-        } else if (p.kind != 4) {                  // ROLE 2
+        } else if (p.kind != kMdBegin) {           // ROLE 2
             // ---- chain terms: lane = (row, neighbour), 16 rows per helper and pass ------------------------
             for (int cb = 16 * (wave - 1); cb < RW; cb += 16 * (NH - 1)) {
                 const int k = cb + (lane >> 2);
@@ -410,7 +410,7 @@ __device__ __forceinline__ void cluster_body(
                 pk.kind = K;
                 if (hfin) {
                     float Fx = 0.0f, Fy = 0.0f, Fz = 0.0f;
-                    if constexpr (K != 4) {
+                    if constexpr (K != kMdBegin) {
                         // nine words, one round trip (lbuf stays zero where there are no left-over columns: read, not used)
                         const float sx0 = fbuf[lane], sy0 = fbuf[64 + lane], sz0 = fbuf[128 + lane];
                         const float lx = lbuf[lane], ly = lbuf[64 + lane], lz = lbuf[128 + lane];
@@ -422,8 +422,8 @@ __device__ __forceinline__ void cluster_body(
                         Fz = row_total<false>(pk, sz, cz);
                     }
                     float vx0 = vcx, vy0 = vcy, vz0 = vcz;
-                    if constexpr (K == 3 || K == 6) { vx0 = vy0 = vz0 = 0.0f; }
-                    else if constexpr (K == 4) { C3D_HROW_INDEX; const float* vinit = io.vinit; vx0 = vinit[ix]; vy0 = vinit[iy]; vz0 = vinit[iz]; }
+                    if constexpr (kind_has_no_velocity(K)) { vx0 = vy0 = vz0 = 0.0f; }
+                    else if constexpr (K == kMdBegin) { C3D_HROW_INDEX; const float* vinit = io.vinit; vx0 = vinit[ix]; vy0 = vinit[iy]; vz0 = vinit[iz]; }
                     finish_row(m, pk, fp, sc, st, Fx, Fy, Fz, hx0, hy0, hz0, vx0, vy0, vz0, xn, yn, zn, vcx, vcy, vcz, q);
                     if (!last && !solo) {               // the row's new position leaves at once; the tile sums follow below
                         u32x4 o;
@@ -436,16 +436,16 @@ __device__ __forceinline__ void cluster_body(
             };
             bool two_point_step = false;
             if constexpr (TWO) {                            // (the two-point minimiser's kinds: k_cluster_tp only)
-                two_point_step = p.kind >= 5;
-                if (p.kind == 5) row_update(std::integral_constant<int, 5>{});
-                else if (p.kind == 6) row_update(std::integral_constant<int, 6>{});
+                two_point_step = p.kind >= kTwoPoint;       // (not kind_is_two_point: one compare, k_cluster_tp never holds kinds 8 / 9)
+                if (p.kind == kTwoPoint) row_update(std::integral_constant<int, kTwoPoint>{});
+                else if (p.kind == kTwoPointFirst) row_update(std::integral_constant<int, kTwoPointFirst>{});
             }
             if (!two_point_step) switch (p.kind) {
-                case 0: row_update(std::integral_constant<int, 0>{}); break;
-                case 1: row_update(std::integral_constant<int, 1>{}); break;
-                case 2: row_update(std::integral_constant<int, 2>{}); break;
-                case 3: row_update(std::integral_constant<int, 3>{}); break;
-                default: row_update(std::integral_constant<int, 4>{}); break;
+                case kMdCouple: row_update(std::integral_constant<int, kMdCouple>{}); break;
+                case kMdRescale: row_update(std::integral_constant<int, kMdRescale>{}); break;
+                case kFire: row_update(std::integral_constant<int, kFire>{}); break;
+                case kFireFirst: row_update(std::integral_constant<int, kFireFirst>{}); break;
+                default: row_update(std::integral_constant<int, kMdBegin>{}); break;
             }
             // B3 (see the other roles below): the rows are out; what follows here — tile sums, their two units — is wanted by the
             // H0s of the replica only, well after the next step has started, and runs while the other waves gather rows

@@ -1,5 +1,5 @@
 // c3d_config.cpp — host unit of libc3d.so: the context's configuration.  The defaults, c3d_set_model, c3d_set_schedule, c3d_set_option and
-// c3d_get_stat — the last two as one table each, a row per key — and the configuration as the kernels take it (dev_model, dev_step).
+// c3d_get_stat — the last two as one table each, a row per key — and the configuration as the kernels take it (dev_model, dev_step, dev_fire).
 #include <climits>
 
 #include "c3d_ctx.h"
@@ -29,7 +29,7 @@ int drop_stale_gated(c3d_ctx* c, unsigned stale) {
     drop_stale(c, stale);
     return C3D_OK;
 }
-bool holds_lbfgs_stage(const c3d_ctx* c) { return std::any_of(c->stages.begin(), c->stages.end(), [](const c3d_stage& s) { return s.kind == 8; }); }
+bool holds_lbfgs_stage(const c3d_ctx* c) { return std::any_of(c->stages.begin(), c->stages.end(), [](const c3d_stage& s) { return s.kind == c3d::kLbfgs; }); }
 
 // ---- options: how a row admits a value.  Each stores the value and returns nullptr, or returns the refusal (the row's, handed in, unless
 // the key has a second one) and stores nothing.  M is the member of c3d_ctx the key sets.
@@ -259,6 +259,12 @@ c3d::DevStep dev_step(const c3d_ctx* c, int kind, float dt, float w_all, float w
     p.t_bath = t_bath;
     return p;
 }
+c3d::DevFire dev_fire(const c3d_ctx* c) {
+    c3d::DevFire f;
+    f.dt_start = c->fire.dt_start; f.dt_max = c->fire.dt_max; f.f_inc = c->fire.f_inc; f.f_dec = c->fire.f_dec;
+    f.alpha_start = c->fire.alpha_start; f.f_alpha = c->fire.f_alpha; f.max_step = c->fire.max_step; f.n_min = c->fire.n_min;
+    return f;
+}
 }  // namespace c3d::host
 
 extern "C" void c3d_default_model(c3d_model* m) {
@@ -344,7 +350,7 @@ extern "C" int c3d_set_schedule(c3d_ctx* c, const c3d_stage* st, int n_stages, c
     if (!c || !st || n_stages < 1) return fail(C3D_ERR_INVALID, "c3d_set_schedule: bad arguments");
     for (int k = 0; k < n_stages; ++k) {
         if (st[k].kind < 0 || (st[k].kind > 2 && st[k].kind != 5 && st[k].kind != 8) || st[k].nsteps < 0) return fail(C3D_ERR_INVALID, "c3d_set_schedule: bad stage");
-        if (st[k].kind == 8 && c->precision == 64 && !c->f64_lbfgs)
+        if (st[k].kind == c3d::kLbfgs && c->precision == 64 && !c->f64_lbfgs)
             return fail(C3D_ERR_INVALID, "c3d_set_schedule: a stage of kind 8 (L-BFGS) has no fp64 form; set precision 32 first");
     }
     c->stages.assign(st, st + n_stages);

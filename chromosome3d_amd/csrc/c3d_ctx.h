@@ -1,4 +1,4 @@
-// c3d_ctx.h — private to the host units of libc3d.so (c3d_api.cpp, c3d_config.cpp, c3d_gate.cpp, c3d_run.cpp, c3d_analysis.cpp): the
+// c3d_ctx.h — private to the host units of libc3d.so (c3d_api.cpp, c3d_config.cpp, c3d_gate.cpp, c3d_run.cpp, c3d_debug.cpp, c3d_analysis.cpp): the
 // context, the error macros, the gate's entry object and the helpers that one unit defines and another calls (namespace c3d::host).  What
 // a single unit uses stays in that unit's anonymous namespace.
 #pragma once
@@ -63,6 +63,7 @@ void dev_free(T*& p) {
 // ---- c3d_config.cpp: the context's configuration as the kernels take it; the keys of its option and stat tables (row k, nullptr past the last)
 c3d::DevModel dev_model(const c3d_ctx* c);
 c3d::DevStep dev_step(const c3d_ctx* c, int kind, float dt, float w_all, float w_vdw, float repel_s, float t_bath);
+c3d::DevFire dev_fire(const c3d_ctx* c);
 const char* option_key(int k);
 const char* stat_key(int k);
 

@@ -318,7 +318,7 @@ __global__ __launch_bounds__(kLbfgsMoveRows64) void k64_lbfgs_move(const Model64
     __shared__ int shi[2];                       // slot mask of the pairs in the direction, slot of the move's s
     __shared__ double dd[ROWS];
     const int rep = rep_base + blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const bool first = p.kind == 9;
+    const bool first = p.kind == kLbfgsFirst;
     // 1. replica sums of the tile partials: the same order in every workgroup, whatever the replica group
     const double* pr = part + (size_t)rep * m.ntiles * Q;
     for (int k = wave; k < Q; k += ROWS / 64) {

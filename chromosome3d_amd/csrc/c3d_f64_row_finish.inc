@@ -5,15 +5,15 @@
 // In:  p (Step64), fp (Fire64), x0, y0, z0, v0x, v0y, v0z, Fx, Fy, Fz, lam, cm0, cm1, cm2, keep, mix, st.dt.
 // Out: xn, yn, zn, vx, vy, vz (declared here), q0 .. q3 (the includer's, zero on entry).
         double vx, vy, vz, xn, yn, zn;
-        if (p.kind == 4) {                              // MD begin: Maxwell velocities, no move
+        if (p.kind == kMdBegin) {                       // MD begin: Maxwell velocities, no move
             vx = v0x; vy = v0y; vz = v0z; xn = x0; yn = y0; zn = z0;
             q0 = vx * vx + vy * vy + vz * vz; q1 = vx; q2 = vy; q3 = vz;
-        } else if (p.kind == 0 || p.kind == 1) {
+        } else if (p.kind == kMdCouple || p.kind == kMdRescale) {
             const double acc = p.acc;
             vx = lam * (v0x - cm0) + acc * Fx; vy = lam * (v0y - cm1) + acc * Fy; vz = lam * (v0z - cm2) + acc * Fz;
             xn = x0 + p.dt * vx; yn = y0 + p.dt * vy; zn = z0 + p.dt * vz;
             q0 = vx * vx + vy * vy + vz * vz; q1 = vx; q2 = vy; q3 = vz;
-        } else if (p.kind == 5 || p.kind == 6) {
+        } else if (p.kind == kTwoPoint || p.kind == kTwoPointFirst) {       // (kind_is_two_point written out: as a call it changes k64_row_finish's machine code)
             const double ms2 = fp.max_step * fp.max_step;
             auto clamp_scale = [&](double d2) {
                 double scl = 1.0;
@@ -21,7 +21,7 @@
                 return cap_scale_wide64(d2, d2 > ms2, fp.max_step, scl);
             };
             q1 = Fx * Fx + Fy * Fy + Fz * Fz;
-            if (p.kind == 5) {
+            if (p.kind == kTwoPoint) {
                 double sx = lam * v0x, sy = lam * v0y, sz = lam * v0z;
                 const double scp = clamp_scale(sx * sx + sy * sy + sz * sz);
                 sx *= scp; sy *= scp; sz *= scp;

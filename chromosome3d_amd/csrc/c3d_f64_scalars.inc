@@ -8,14 +8,14 @@
         //  divisions and sqrt of the straightforward form are ~230 dependent fp64 operations — a microsecond on every workgroup's
         //  critical path, more than the launch boundary hides; these are a rounding or two away from them)
         double lam = 1.0, cm0 = 0, cm1 = 0, cm2 = 0, keep = 0.0, mix = 0.0;
-        if (p.kind == 0 || p.kind == 1) {
+        if (p.kind == kMdCouple || p.kind == kMdRescale) {
             double tprev = m.t_fac * s0;                // mass / kAccel / (ndf kBoltz) * sum v^2
             if (tprev < 1e-2) tprev = 1e-2;
             const double ratio = p.t_bath * rcp64(tprev);
-            if (p.kind == 0) { double l2 = 1.0 + p.dt * m.fbeta * (ratio - 1.0); if (l2 < 0) l2 = 0; lam = sqrt64(l2); }
+            if (p.kind == kMdCouple) { double l2 = 1.0 + p.dt * m.fbeta * (ratio - 1.0); if (l2 < 0) l2 = 0; lam = sqrt64(l2); }
             else lam = sqrt64(ratio);
             cm0 = s1 * m.inv_n; cm1 = s2 * m.inv_n; cm2 = s3 * m.inv_n;
-        } else if (p.kind == 2 || p.kind == 3) {
+        } else if (kind_is_fire(p.kind)) {
             if (s0 > 0) {                               // power of the previous evaluation positive (kind 3: sums are 0)
                 keep = 1.0 - st.alpha;
                 mix = st.alpha * sqrt64(s2 * rcp64(s1 > 1e-30 ? s1 : 1e-30));
@@ -25,8 +25,8 @@
                 st.alpha = fp.alpha_start; st.dt *= fp.f_dec; st.npos = 0;
             }
             C3D_F64_STATE_OUT
-        } else if (p.kind == 5 || p.kind == 6) {        // two-point step size, the length one evaluation late (c3o_bb_step): lam = previous length, mix = this one
-            const int k = p.kind == 6 ? 0 : st.npos;
+        } else if (kind_is_two_point(p.kind)) {        // two-point step size, the length one evaluation late (c3o_bb_step): lam = previous length, mix = this one
+            const int k = p.kind == kTwoPointFirst ? 0 : st.npos;
             const double a_prev = st.dt;
             double a = a_prev;
             if (k == 0) a = fp.dt_start * fp.dt_start * p.kacc;

@@ -63,7 +63,7 @@
 #elif C3D_F64_LBFGS
     // ---- the ring of this step (kind 9 = a stage's first step: no pair yet); v0 = the previous evaluation's force, read from vin ----
     constexpr int Q = kLbfgsQ;
-    const bool first = p.kind == 9;
+    const bool first = p.kind == kLbfgsFirst;
     int mem = mem0, nxt = 0;
     if (!first) {      // (clamped into the ring whatever the state holds: a stage always begins with kind 9, which sets it)
         mem = min(max(lsin[rep].mem, 1), kLbfgsMaxPairs);
@@ -78,8 +78,8 @@
 #endif
 #else
 #if !C3D_F64_CHUNKED
-    if (lane < kRows64 && row < n && p.kind != 3 && p.kind != 6) {
-        const double* vsrc = p.kind == 4 ? vinit : vin;
+    if (lane < kRows64 && row < n && !kind_has_no_velocity(p.kind)) {
+        const double* vsrc = p.kind == kMdBegin ? vinit : vin;
         const size_t ix = roff + row;
         v0x = vsrc[ix]; v0y = vsrc[ix + np]; v0z = vsrc[ix + 2 * np];
     }
@@ -90,9 +90,9 @@
     double* scal = rowq + 4 * kTileRows;                // [8] lam, cm0, cm1, cm2, keep, mix, dt, (unused)
     FireState64 st;
     st.dt = fp.dt_start; st.alpha = fp.alpha_start; st.npos = 0; st.pad = 0;
-    if (wave == 0 && (p.kind == 2 || p.kind == 5)) st = sin[rep];        // (asked for here, used after the sums have arrived)
+    if (wave == 0 && kind_continues_state(p.kind)) st = sin[rep];        // (asked for here, used after the sums have arrived)
     if (wave == 0) {
-        const bool needs = p.kind == 0 || p.kind == 1 || p.kind == 2 || p.kind == 5;
+        const bool needs = kind_reads_sums(p.kind);
         double s0 = 0, s1 = 0, s2 = 0, s3 = 0;
         if (needs) {
             const double* pp = pin + (size_t)rep * m.ntiles * 4;
@@ -114,7 +114,7 @@
     double fxa = 0, fya = 0, fza = 0, fxb = 0, fyb = 0, fzb = 0;
     const double R2 = p.R2;
     const double wr4 = p.wr4;
-    if (p.kind != 4) {
+    if (p.kind != kMdBegin) {
         const double xa = rx[ra], ya = ry[ra], za = rz[ra], xb = rx[rb], yb = ry[rb], zb = rz[rb];
         // (FOLD: the pair terms carry the repel weight relative to the NOE weight, the row sums get the NOE weight below)
         const double nws4p = FOLD ? 1.0 : p.nws4, wr4p = FOLD ? p.wq : wr4;
@@ -206,8 +206,8 @@
 #elif C3D_F64_CHUNKED
     // (the velocities of the two rows the wave finishes are asked for here, not ahead of the pair loop: held across the chunk loop, the
     //  six registers were one more than the kernel has at five waves a SIMD)
-    if (lane < kRows64 && row < n && p.kind != 3 && p.kind != 6) {
-        const double* vsrc = p.kind == 4 ? vinit : vin;
+    if (lane < kRows64 && row < n && !kind_has_no_velocity(p.kind)) {
+        const double* vsrc = p.kind == kMdBegin ? vinit : vin;
         const size_t ix = roff + row;
         v0x = vsrc[ix]; v0y = vsrc[ix + np]; v0z = vsrc[ix + 2 * np];
     }
@@ -218,7 +218,7 @@
     {
         const int r = (lane >> 2) & 1, nb = lane & 3;
         double cx = 0, cy = 0, cz = 0;
-        if (lane < 8 && p.kind != 4) chain64(m, p, wr4, R2, rx, ry, rz, row0 + r, nb < 2 ? nb - 2 : nb - 1, cx, cy, cz);
+        if (lane < 8 && p.kind != kMdBegin) chain64(m, p, wr4, R2, rx, ry, rz, row0 + r, nb < 2 ? nb - 2 : nb - 1, cx, cy, cz);
         cx += dpp_mov64<0xB1>(cx); cy += dpp_mov64<0xB1>(cy); cz += dpp_mov64<0xB1>(cz);
         cx += dpp_mov64<0x4E>(cx); cy += dpp_mov64<0x4E>(cy); cz += dpp_mov64<0x4E>(cz);
         const double ox = dpp_mov64<0x12C>(cx), oy = dpp_mov64<0x12C>(cy), oz = dpp_mov64<0x12C>(cz);   // row_ror:12 = lane + 4

@@ -6,6 +6,7 @@
 #include <type_traits>
 
 #include "../../include/c3d.h"
+#include "c3d_step_kinds.h"
 #include "c3d_superpose.h"
 
 namespace c3d {
@@ -52,7 +53,7 @@ struct DevModel {
 };
 
 struct DevStep {
-    int kind;        // 0 MD T-coupling, 1 MD velocity rescale, 2 FIRE step, 3 first FIRE step of a stage, 4 MD begin,
+    int kind;        // a StepKind (c3d_step_kinds.h): 0 MD T-coupling, 1 MD velocity rescale, 2 FIRE step, 3 first FIRE step of a stage, 4 MD begin,
                      // 5 two-point step-size (Barzilai-Borwein) minimiser step, 6 its first step of a stage,
                      // 8 L-BFGS step, 9 its first step of a stage (k_lbfgs_eval + k_lbfgs_move only: never k_step / k_cluster)
     float dt;

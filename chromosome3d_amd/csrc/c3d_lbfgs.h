@@ -69,7 +69,7 @@ __global__ __launch_bounds__(kLbfgsMoveRows) void k_lbfgs_move(
     __shared__ int shi[2];                       // slot mask of the pairs in the direction, slot of the move's s
     __shared__ float dd[kLbfgsMoveRows];
     const int rep = m.rep_base + blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const bool first = p.kind == 9;
+    const bool first = p.kind == kLbfgsFirst;
     // 1. replica sums of the tile partials in fp64: lane l takes tiles l, l + 64, ... in order, then a butterfly (the same order in every
     //    workgroup, whatever the replica group)
     const float* pr = part + (size_t)rep * m.ntiles * Q;

@@ -31,7 +31,7 @@
     float4 tv[RPW];
     if (pair_targets_in_use<POT, GEN, RPW, NC>(m)) pair_targets_prefetch(m, row0, lane, 0, tv);
     else tile_prefetch<RPW, NC>(m, tgt, row0, lane, 0, tv);
-    const bool first = p.kind == 9;
+    const bool first = p.kind == kLbfgsFirst;
     int mem = mem0, nxt = 0;
     if (!first) {      // (clamped into the ring whatever the state holds: a stage always begins with kind 9, which sets it)
         mem = min(max(sin[rep].mem, 1), kLbfgsMaxPairs);

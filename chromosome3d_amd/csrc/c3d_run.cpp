@@ -1,5 +1,5 @@
 // c3d_run.cpp — host unit of libc3d.so: schedule -> launch program and its executor, the L-BFGS and pair-target allocations, timing,
-// c3d_run_steps / c3d_run / c3d_centre.
+// c3d_run_steps / c3d_run / c3d_centre.  (The table test hooks of the step texts are a unit of their own: c3d_debug.cpp.)
 // Reference boundary: chromosome3D.pl:254-289 (build_models: `cns_solve < dgsa.inp`) and the deck it writes (:882-1846).  What CNS does per
 // model (deck :1574-1829) becomes a flat "program" of SA steps; a range of it runs as ONE cluster launch (run_cluster, c3d_cluster.hip) where
 // the replicas fit the chip's XCDs, else as one launch per step (two replica groups on two streams, replayed from hipGraphs).  Every copy
@@ -10,9 +10,6 @@
 
 using namespace c3d::host;
 
-static bool is_two_point(int kind) { return kind == 5 || kind == 6; }
-static bool is_lbfgs(int kind) { return kind == 8 || kind == 9; }
-
 // ---- what the other host units call (c3d_ctx.h)
 namespace c3d::host {
 void drop_graphs(c3d_ctx* c) {
@@ -20,39 +17,35 @@ void drop_graphs(c3d_ctx* c) {
     c->graphs.clear();
 }
 
+// The kind step k of a minimiser stage runs; kinds 3 / 6 / 9 = first step of a method's run (fresh state).  A stage of kind 5 starts with the
+// two-point step-size minimiser (kinds 6 / 5) and hands over to FIRE (3 / 2) after nbb = bb_steps of them if the exit test has not ended the
+// stage by then: the two-point method has no descent guarantee — one replica in a few hundred ends in a cycle of long moves instead of a
+// minimum — and FIRE finishes what it leaves (the CPU restatement does the same: c3o_run_schedule).  Option final_minimiser = 0 (nbb = 0): kind
+// 5 runs as FIRE throughout.  A stage of kind 8 runs L-BFGS (kinds 9 / 8) for its first final_minimiser_steps steps and hands over to FIRE the
+// same way; option final_minimiser does not apply to it.
+static int minimiser_step_kind(int stage_kind, int k, int nbb) {
+    if (k >= nbb) return k == nbb ? kFireFirst : kFire;
+    return stage_kind == kLbfgs ? (k == 0 ? kLbfgsFirst : kLbfgs) : (k == 0 ? kTwoPointFirst : kTwoPoint);
+}
+
 void build_program(c3d_ctx* c) {
     c->program.clear();
-    int prev_kind = -1;
     for (size_t s = 0; s < c->stages.size(); ++s) {
         const c3d_stage& st = c->stages[s];
-        if (st.kind == 2 || st.kind == 5 || st.kind == 8) {
-            // kind 3 / 6 = first step of a minimiser's run (fresh state).  A stage of kind 5 starts with the two-point step-size minimiser
-            // (kinds 6 / 5) and hands over to FIRE (3 / 2) after bb_steps of them if the exit test has not ended the stage by then: the
-            // two-point method has no descent guarantee — one replica in a few hundred ends in a cycle of long moves instead of a minimum —
-            // and FIRE finishes what it leaves (the CPU restatement does the same: c3o_run_schedule).  Option final_minimiser = 0: kind 5 runs as FIRE throughout.
-            // A stage of kind 8 runs L-BFGS (kinds 9 / 8) for its first final_minimiser_steps steps and hands over to FIRE the same way;
-            // option final_minimiser does not apply to it.
-            const bool lbfgs = st.kind == 8;
-            const int nbb = (st.kind == 5 && c->final_bb) || lbfgs ? std::min(st.nsteps, c->bb_steps) : 0;
-            for (int k = 0; k < st.nsteps; ++k) {
-                const int kind = k < nbb ? (k == 0 ? (lbfgs ? 9 : 6) : (lbfgs ? 8 : 5)) : (k == nbb ? 3 : 2);
-                c->program.push_back({dev_step(c, kind, 0.0f, st.w_all, st.w_vdw, st.repel_s, 0.0f), (int)s, true});
-            }
+        if (stage_is_minimiser(st.kind)) {
+            const int nbb = (st.kind == kTwoPoint && c->final_bb) || st.kind == kLbfgs ? std::min(st.nsteps, c->bb_steps) : 0;
+            for (int k = 0; k < st.nsteps; ++k)
+                c->program.push_back({dev_step(c, minimiser_step_kind(st.kind, k, nbb), 0.0f, st.w_all, st.w_vdw, st.repel_s, 0.0f), (int)s, true});
         } else {
-            if (prev_kind == 2 || prev_kind == 5 || prev_kind == 8 || prev_kind == -1)
-                c->program.push_back({dev_step(c, 4, 0.0f, st.w_all, st.w_vdw, st.repel_s, st.t_bath), (int)s, false});
+            if (s == 0 || stage_is_minimiser(c->stages[s - 1].kind))      // MD begins
+                c->program.push_back({dev_step(c, kMdBegin, 0.0f, st.w_all, st.w_vdw, st.repel_s, st.t_bath), (int)s, false});
             for (int k = 0; k < st.nsteps; ++k)
                 c->program.push_back({dev_step(c, st.kind, st.dt, st.w_all, st.w_vdw, st.repel_s, st.t_bath), (int)s, true});
         }
-        prev_kind = st.kind;
     }
     c->pc = 0;
-    c->zero_weight = false;
-    for (const Op& op : c->program) c->zero_weight = c->zero_weight || op.p.w_rs == 0.0f;
-    c->has_two_point = false;
-    for (const Op& op : c->program) c->has_two_point = c->has_two_point || is_two_point(op.p.kind);
-    c->has_lbfgs = false;
-    for (const Op& op : c->program) c->has_lbfgs = c->has_lbfgs || is_lbfgs(op.p.kind);
+    c->zero_weight = c->has_two_point = c->has_lbfgs = false;
+    for (const Op& op : c->program) { c->zero_weight |= op.p.w_rs == 0.0f; c->has_two_point |= kind_is_two_point(op.p.kind); c->has_lbfgs |= kind_is_lbfgs(op.p.kind); }
     drop_graphs(c);
     // run-length code of the whole program (a FIRE stage is 2 runs, the cool ramp 81) for the cluster kernel
     c->prog_runs.clear();
@@ -110,13 +103,6 @@ int max_rms_force(c3d_ctx* c, double* out) {
 }  // namespace c3d::host
 
 namespace {
-c3d::DevFire dev_fire(const c3d_ctx* c) {
-    c3d::DevFire f;
-    f.dt_start = c->fire.dt_start; f.dt_max = c->fire.dt_max; f.f_inc = c->fire.f_inc; f.f_dec = c->fire.f_dec;
-    f.alpha_start = c->fire.alpha_start; f.f_alpha = c->fire.f_alpha; f.max_step = c->fire.max_step; f.n_min = c->fire.n_min;
-    return f;
-}
-
 void group_range(const c3d_ctx* c, int g, int& base, int& count) {
     const int G = active_groups(c);
     const int q = c->nrep / G, r = c->nrep % G;
@@ -163,14 +149,14 @@ int ensure_pair_targets(c3d_ctx* c, const c3d::DevModel& m) {
 KernelRecord op_kernel(const c3d_ctx* c, const c3d::DevModel& m, const Op& op, const c3d::Model64* m64 = nullptr) {
     KernelRecord k;
     if (c->precision == 64) {
-        k.family = is_lbfgs(op.p.kind) ? KernelRecord::LBFGS_EVAL64 : KernelRecord::STEP64;
+        k.family = c3d::kind_is_lbfgs(op.p.kind) ? KernelRecord::LBFGS_EVAL64 : KernelRecord::STEP64;
         k.f64 = c3d::form64(m64 ? *m64 : c3d::model64(m, c->model), c->stages[op.stage].w_all, c->f64_column_chunk);
-    } else if (!is_lbfgs(op.p.kind) && use_sym(c)) {      // (symmetric tiles do not apply to L-BFGS steps)
+    } else if (!c3d::kind_is_lbfgs(op.p.kind) && use_sym(c)) {      // (symmetric tiles do not apply to L-BFGS steps)
         k.family = KernelRecord::PAIRS_SYM;
         k.pot = c3d::device_pot(m.noe_pot);
         k.rs1 = c3d::sym_rs1(m);
     } else {
-        k.family = is_lbfgs(op.p.kind) ? KernelRecord::LBFGS_EVAL : KernelRecord::STEP;
+        k.family = c3d::kind_is_lbfgs(op.p.kind) ? KernelRecord::LBFGS_EVAL : KernelRecord::STEP;
         k.step = c3d::step_form(m, op.p, c->wide_tiles, c->pair_targets, c->buf.tgs2 != nullptr, c->column_chunk);
     }
     return k;
@@ -185,7 +171,7 @@ int launch_op(c3d_ctx* c, const Op& op, int g, int par) {
         const c3d::Step64 p = c3d::step64(m64, op.p.kind, st.dt, st.w_all, st.w_vdw, st.repel_s, st.t_bath);
         const c3d::Fire64 fp = c3d::fire64(c->fire);
         const c3d::Form64 f = op_kernel(c, m, op, &m64).f64;
-        if (is_lbfgs(op.p.kind)) {         // two launches, as in fp32: forces + tile sums, then sums + direction + move
+        if (c3d::kind_is_lbfgs(op.p.kind)) {         // two launches, as in fp32: forces + tile sums, then sums + direction + move
             hipError_t e = c3d::launch_lbfgs_eval64(m, m64, p, f, c->b64, c->lb64, par, c->lbfgs_mem, c->gstream[g]);
             if (e == hipSuccess) e = c3d::launch_lbfgs_move64(m, m64, p, fp, c->b64, c->lb64, par, c->lbfgs_mem, c->gstream[g]);
             LAUNCH_TRY("fp64 L-BFGS step launch", e);
@@ -265,7 +251,7 @@ int run_cluster(c3d_ctx* c, size_t nops, bool* ran) {
     pl.static_place = c->static_place ? (c->inject_misplaced ? 2 : 1) : 0;
     pl.xcd_base = c->xcd_base;
     pl.two_point = false;
-    for (size_t k = 0; k < nops && !pl.two_point; ++k) pl.two_point = is_two_point(c->program[c->pc + k].p.kind);
+    for (size_t k = 0; k < nops && !pl.two_point; ++k) pl.two_point = c3d::kind_is_two_point(c->program[c->pc + k].p.kind);
     c->inject_misplaced = false;
     c->h_tmo[2] = 0;
     const auto h0 = std::chrono::steady_clock::now();
@@ -363,12 +349,12 @@ int run_ops_segment(c3d_ctx* c, size_t nops, bool zero_w, bool lbfgs = false) {
             }
         } else {
             // one graph per (range, parity, group); homogeneous minimiser ranges (same stage, all kind 2, all 5 or all 8) share a graph
-            // regardless of pc (kind 8 keeps its ring head and counts on the device)
+            // regardless of pc (kind 8 keeps its ring head and counts on the device); a stage of kind 5 or 8 has a minimiser part and a FIRE part
             const Op& first = c->program[c->pc];
             const Op& last = c->program[c->pc + chunk - 1];
+            const int kd = first.p.kind, method = kd == c3d::kTwoPoint ? 1 : kd == c3d::kLbfgs ? 2 : 0;        // (0 FIRE, 1 two-point, 2 L-BFGS)
             long sig = (long)c->pc;
-            if ((first.p.kind == 2 || first.p.kind == 5 || first.p.kind == 8) && last.p.kind == first.p.kind && first.stage == last.stage)
-                sig = -(long)(first.stage + 1) - (first.p.kind == 5 ? 1000000L : first.p.kind == 8 ? 2000000L : 0L);     // (a stage of kind 5 or 8 has a minimiser part and a FIRE part)
+            if (!c3d::kind_is_md(kd) && !c3d::kind_is_first(kd) && last.p.kind == kd && first.stage == last.stage) sig = -(long)(first.stage + 1) - 1000000L * method;
             if (c->graphs.size() >= 2048) {                        // bounded: a caller with ever new ranges starts over
                 for (int g = 0; g < G; ++g) HIP_TRY(hipStreamSynchronize(c->gstream[g]));
                 drop_graphs(c);
@@ -428,11 +414,11 @@ int run_ops(c3d_ctx* c, size_t nops) {
     const size_t end = c->pc + nops;
     while (c->pc < end) {
         const c3d::DevStep& p0 = c->program[c->pc].p;
-        const bool z = !p64 && p0.w_rs == 0.0f, tp = !p64 && is_two_point(p0.kind), lb = is_lbfgs(p0.kind);
+        const bool z = !p64 && p0.w_rs == 0.0f, tp = !p64 && c3d::kind_is_two_point(p0.kind), lb = c3d::kind_is_lbfgs(p0.kind);
         size_t k = 1;
         while (c->pc + k < end) {
             const c3d::DevStep& p = c->program[c->pc + k].p;
-            if ((!p64 && p.w_rs == 0.0f) != z || (!p64 && is_two_point(p.kind)) != tp || is_lbfgs(p.kind) != lb) break;
+            if ((!p64 && p.w_rs == 0.0f) != z || (!p64 && c3d::kind_is_two_point(p.kind)) != tp || c3d::kind_is_lbfgs(p.kind) != lb) break;
             ++k;
         }
         if (int rc = run_ops_segment(c, k, z, lb)) return rc;
@@ -510,7 +496,7 @@ extern "C" int c3d_run(c3d_ctx* c) {
     C3D_ENTRY(c, 0u);
     if (int rc = begin_timing(c)) return rc;
     const int last_stage = (int)c->stages.size() - 1;
-    const bool early = c->gtol > 0.0f && last_stage >= 0 && (c->stages[last_stage].kind == 2 || c->stages[last_stage].kind == 5 || c->stages[last_stage].kind == 8);
+    const bool early = c->gtol > 0.0f && last_stage >= 0 && c3d::stage_is_minimiser(c->stages[last_stage].kind);
     // everything before the final minimisation
     size_t nfixed = c->program.size() - c->pc;
     if (early) {
@@ -547,241 +533,6 @@ extern "C" int c3d_last_timing(const c3d_ctx* c, double* ms_total, long* steps, 
     if (steps) *steps = c->last_steps;
     if (launches) *launches = c->last_launches;
     return C3D_OK;
-}
-
-// Test hook: step_scalars<true> on a table of rows (c3d.h).  The model, the FIRE values and the step are built by the functions every
-// launch uses (dev_model, dev_fire, dev_step), so the table also covers what the host folds into them (acc, t_fac, inv_n).
-extern "C" int c3d_debug_step_scalars(c3d_ctx* c, int kind, float dt, float t_bath, int rows, const float* psum, const float* state_in,
-                                      const int32_t* npos_in, float* scalars, float* state_out, int32_t* npos_out) {
-    if (!c || !psum || !state_in || !npos_in || !scalars || !state_out || !npos_out || rows < 1 || rows > (1 << 20))
-        return fail(C3D_ERR_INVALID, "c3d_debug_step_scalars: bad arguments");
-    if (!(kind == 0 || kind == 1 || kind == 2 || kind == 3 || kind == 5 || kind == 6))
-        return fail(C3D_ERR_INVALID, "c3d_debug_step_scalars: kind is 0, 1, 2, 3, 5 or 6");
-    if (c->n < 1) return fail(C3D_ERR_INVALID, "c3d_debug_step_scalars: set the targets first (the bead count enters the temperature)");
-    C3D_ENTRY(c, unit_bit(UNIT_SYM));
-    std::vector<c3d::FireState> st((size_t)rows);
-    for (int r = 0; r < rows; ++r) st[r] = c3d::FireState{state_in[2 * r], state_in[2 * r + 1], npos_in[r], 0};
-    DevTmp<float> d_psum, d_out;
-    DevTmp<c3d::FireState> d_in, d_st;
-    HIP_TRY(hipMalloc(&d_psum.p, sizeof(float) * 4 * (size_t)rows));
-    HIP_TRY(hipMalloc(&d_out.p, sizeof(float) * 6 * (size_t)rows));
-    HIP_TRY(hipMalloc(&d_in.p, sizeof(c3d::FireState) * (size_t)rows));
-    HIP_TRY(hipMalloc(&d_st.p, sizeof(c3d::FireState) * (size_t)rows));
-    HIP_TRY(hipMemcpyAsync(d_psum.p, psum, sizeof(float) * 4 * (size_t)rows, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_in.p, st.data(), sizeof(c3d::FireState) * (size_t)rows, hipMemcpyHostToDevice, c->stream));
-    LAUNCH_TRY("step scalars launch", c3d::launch_step_scalars(dev_model(c), dev_step(c, kind, dt, 1.0f, 1.0f, 0.85f, t_bath), dev_fire(c), rows,
-                                                               d_psum.p, d_in.p, d_out.p, d_st.p, c->stream));
-    HIP_TRY(hipMemcpyAsync(scalars, d_out.p, sizeof(float) * 6 * (size_t)rows, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(st.data(), d_st.p, sizeof(c3d::FireState) * (size_t)rows, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    for (int r = 0; r < rows; ++r) { state_out[2 * r] = st[r].dt; state_out[2 * r + 1] = st[r].alpha; npos_out[r] = st[r].npos; }
-    return C3D_OK;
-}
-
-// Test hook: finish_row on a table of rows (c3d.h) — the row update that consumes c3d_debug_step_scalars' scalars, under the same
-// DevModel / DevStep / DevFire (acc = 418.4 / mass and max_step as the host holds them; the kernel forms dt acc itself).
-extern "C" int c3d_debug_row_finish(c3d_ctx* c, int kind, float dt, int rows, const float* in, float* out) {
-    if (!c || !in || !out) return fail(C3D_ERR_INVALID, "c3d_debug_row_finish: bad arguments");
-    if (rows < 1 || rows > (1 << 20)) return fail(C3D_ERR_INVALID, "c3d_debug_row_finish: rows is 1 .. 2^20");
-    if (kind < 0 || kind > 6) return fail(C3D_ERR_INVALID, "c3d_debug_row_finish: kind is 0, 1, 2, 3, 4, 5 or 6");
-    if (c->n < 1) return fail(C3D_ERR_INVALID, "c3d_debug_row_finish: set the targets first (the model is built for a bead count)");
-    C3D_ENTRY(c, unit_bit(UNIT_SYM));
-    DevTmp<float> d_in, d_out;
-    HIP_TRY(hipMalloc(&d_in.p, sizeof(float) * C3D_ROW_FINISH_IN * (size_t)rows));
-    HIP_TRY(hipMalloc(&d_out.p, sizeof(float) * C3D_ROW_FINISH_OUT * (size_t)rows));
-    HIP_TRY(hipMemcpyAsync(d_in.p, in, sizeof(float) * C3D_ROW_FINISH_IN * (size_t)rows, hipMemcpyHostToDevice, c->stream));
-    LAUNCH_TRY("row finish launch", c3d::launch_row_finish(dev_model(c), dev_step(c, kind, dt, 1.0f, 1.0f, 0.85f, 0.0f), dev_fire(c), rows, d_in.p,
-                                                           d_out.p, c->stream));
-    HIP_TRY(hipMemcpyAsync(out, d_out.p, sizeof(float) * C3D_ROW_FINISH_OUT * (size_t)rows, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return C3D_OK;
-}
-
-// Test hooks: the fp64 controller (c3d_f64_scalars.inc) and the fp64 row update (c3d_f64_row_finish.inc) on tables of rows (c3d.h).
-// Model64 / Step64 / Fire64 come from the builders every fp64 launch uses, so the tables also cover t_fac, inv_n, acc and kacc as the host
-// forms them.  The stage weights of the Step64 (1, 1, 0.85) enter neither text.
-namespace {
-struct FireRow64 { double dt, alpha; int32_t npos, pad; };       // a FireState64 (c3d_f64.hip) as the host packs it
-bool f64_table_kind(int kind, bool row_finish) {
-    return kind == 0 || kind == 1 || kind == 2 || kind == 3 || kind == 5 || kind == 6 || (row_finish && kind == 4);
-}
-}  // namespace
-extern "C" int c3d_debug_step_scalars_f64(c3d_ctx* c, int kind, double dt, double t_bath, int rows, const double* psum, const double* state_in,
-                                          const int32_t* npos_in, double* scalars, double* state_out, int32_t* npos_out) {
-    if (!c || !psum || !state_in || !npos_in || !scalars || !state_out || !npos_out)
-        return fail(C3D_ERR_INVALID, "c3d_debug_step_scalars_f64: bad arguments");
-    if (rows < 1 || rows > (1 << 20)) return fail(C3D_ERR_INVALID, "c3d_debug_step_scalars_f64: rows is 1 .. 2^20");
-    if (!f64_table_kind(kind, false)) return fail(C3D_ERR_INVALID, "c3d_debug_step_scalars_f64: kind is 0, 1, 2, 3, 5 or 6");
-    if (c->precision != 64) return fail(C3D_ERR_INVALID, "c3d_debug_step_scalars_f64: the context's precision is not 64");
-    if (c->n < 1) return fail(C3D_ERR_INVALID, "c3d_debug_step_scalars_f64: set the targets first (the bead count enters the temperature)");
-    if (sizeof(FireRow64) != c3d::fire_state64_bytes()) return fail(C3D_ERR_INVALID, "c3d_debug_step_scalars_f64: the state's layout is not the one this entry packs");
-    C3D_ENTRY(c, unit_bit(UNIT_F64));
-    std::vector<FireRow64> st((size_t)rows);
-    for (int r = 0; r < rows; ++r) st[r] = FireRow64{state_in[2 * r], state_in[2 * r + 1], npos_in[r], 0};
-    DevTmp<double> d_psum, d_out;
-    DevTmp<FireRow64> d_in, d_st;
-    HIP_TRY(hipMalloc(&d_psum.p, sizeof(double) * 4 * (size_t)rows));
-    HIP_TRY(hipMalloc(&d_out.p, sizeof(double) * 6 * (size_t)rows));
-    HIP_TRY(hipMalloc(&d_in.p, sizeof(FireRow64) * (size_t)rows));
-    HIP_TRY(hipMalloc(&d_st.p, sizeof(FireRow64) * (size_t)rows));
-    HIP_TRY(hipMemcpyAsync(d_psum.p, psum, sizeof(double) * 4 * (size_t)rows, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_in.p, st.data(), sizeof(FireRow64) * (size_t)rows, hipMemcpyHostToDevice, c->stream));
-    const c3d::Model64 m64 = c3d::model64(dev_model(c), c->model);
-    LAUNCH_TRY("fp64 step scalars launch", c3d::launch_step_scalars64(m64, c3d::step64(m64, kind, dt, 1.0, 1.0, 0.85, t_bath), c3d::fire64(c->fire), rows,
-                                                                     d_psum.p, d_in.p, d_out.p, d_st.p, c->stream));
-    HIP_TRY(hipMemcpyAsync(scalars, d_out.p, sizeof(double) * 6 * (size_t)rows, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(st.data(), d_st.p, sizeof(FireRow64) * (size_t)rows, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    for (int r = 0; r < rows; ++r) { state_out[2 * r] = st[r].dt; state_out[2 * r + 1] = st[r].alpha; npos_out[r] = st[r].npos; }
-    return C3D_OK;
-}
-static_assert(C3D_ROW_FINISH_IN == c3d::kRowFinish64In && C3D_ROW_FINISH_OUT == c3d::kRowFinish64Out, "c3d.h states the row table's sizes");
-extern "C" int c3d_debug_row_finish_f64(c3d_ctx* c, int kind, double dt, int rows, const double* in, double* out) {
-    if (!c || !in || !out) return fail(C3D_ERR_INVALID, "c3d_debug_row_finish_f64: bad arguments");
-    if (rows < 1 || rows > (1 << 20)) return fail(C3D_ERR_INVALID, "c3d_debug_row_finish_f64: rows is 1 .. 2^20");
-    if (!f64_table_kind(kind, true)) return fail(C3D_ERR_INVALID, "c3d_debug_row_finish_f64: kind is 0, 1, 2, 3, 4, 5 or 6");
-    if (c->precision != 64) return fail(C3D_ERR_INVALID, "c3d_debug_row_finish_f64: the context's precision is not 64");
-    if (c->n < 1) return fail(C3D_ERR_INVALID, "c3d_debug_row_finish_f64: set the targets first (the model is built for a bead count)");
-    C3D_ENTRY(c, unit_bit(UNIT_F64));
-    DevTmp<double> d_in, d_out;
-    HIP_TRY(hipMalloc(&d_in.p, sizeof(double) * C3D_ROW_FINISH_IN * (size_t)rows));
-    HIP_TRY(hipMalloc(&d_out.p, sizeof(double) * C3D_ROW_FINISH_OUT * (size_t)rows));
-    HIP_TRY(hipMemcpyAsync(d_in.p, in, sizeof(double) * C3D_ROW_FINISH_IN * (size_t)rows, hipMemcpyHostToDevice, c->stream));
-    const c3d::Model64 m64 = c3d::model64(dev_model(c), c->model);
-    LAUNCH_TRY("fp64 row finish launch", c3d::launch_row_finish64(c3d::step64(m64, kind, dt, 1.0, 1.0, 0.85, 0.0), c3d::fire64(c->fire), rows, d_in.p,
-                                                                 d_out.p, c->stream));
-    HIP_TRY(hipMemcpyAsync(out, d_out.p, sizeof(double) * C3D_ROW_FINISH_OUT * (size_t)rows, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return C3D_OK;
-}
-
-// Test hook: the serial section of the L-BFGS move (c3d_lbfgs_serial.inc) on a table of rows (c3d.h) — k_lbfgs_direction, or
-// k64_lbfgs_direction on a precision-64 context.  DevModel / DevFire, Step64 / Fire64 come from the functions every launch uses, so the
-// first step's gamma is formed from what the host folds into them (acc, kacc).
-static_assert(C3D_LBFGS_MAX_PAIRS == c3d::kLbfgsMaxPairs && C3D_LBFGS_SUMS == c3d::kLbfgsQ, "c3d.h states the L-BFGS stage's sizes");
-static_assert(sizeof(c3d::LbfgsState) == 4 * sizeof(int32_t) + C3D_LBFGS_STATE_DOUBLES * sizeof(double), "LbfgsState is 4 ints, then doubles");
-extern "C" int c3d_debug_lbfgs_direction(c3d_ctx* c, int rows, const double* sums, const int32_t* state_int_in, const double* state_dbl_in,
-                                         const int32_t* first, const int32_t* mem0, int32_t* state_int_out, double* state_dbl_out,
-                                         double* coef, int32_t* mask_slot) {
-    if (!c || !sums || !state_int_in || !state_dbl_in || !first || !mem0 || !state_int_out || !state_dbl_out || !coef || !mask_slot ||
-        rows < 1 || rows > (1 << 16))
-        return fail(C3D_ERR_INVALID, "c3d_debug_lbfgs_direction: bad arguments");
-    for (int r = 0; r < rows; ++r)
-        if (mem0[r] < 1 || mem0[r] > c3d::kLbfgsMaxPairs) return fail(C3D_ERR_INVALID, "c3d_debug_lbfgs_direction: mem0 is 1 .. 8 (lbfgs_memory)");
-    if (c->n < 1) return fail(C3D_ERR_INVALID, "c3d_debug_lbfgs_direction: set the targets first (the model is built for a bead count)");
-    const bool f64 = c->precision == 64;
-    C3D_ENTRY(c, f64 ? unit_bit(UNIT_F64) : 0u);
-    constexpr int ND = C3D_LBFGS_STATE_DOUBLES, NC = C3D_LBFGS_COEFS;
-    std::vector<c3d::LbfgsState> st((size_t)rows);
-    std::vector<int> flags(2 * (size_t)rows);
-    for (int r = 0; r < rows; ++r) {
-        c3d::LbfgsState& s = st[r];
-        s.cnt = state_int_in[4 * r]; s.head = state_int_in[4 * r + 1]; s.mem = state_int_in[4 * r + 2]; s.resets = state_int_in[4 * r + 3];
-        memcpy(reinterpret_cast<char*>(&s) + 4 * sizeof(int32_t), state_dbl_in + (size_t)ND * r, sizeof(double) * ND);     // gamma, SY, YY
-        flags[2 * r] = first[r] != 0; flags[2 * r + 1] = mem0[r];
-    }
-    DevTmp<double> d_sums, d_coef;
-    DevTmp<c3d::LbfgsState> d_in, d_out;
-    DevTmp<int> d_flags, d_shi;
-    HIP_TRY(hipMalloc(&d_sums.p, sizeof(double) * C3D_LBFGS_SUMS * (size_t)rows));
-    HIP_TRY(hipMalloc(&d_coef.p, sizeof(double) * NC * (size_t)rows));
-    HIP_TRY(hipMalloc(&d_in.p, sizeof(c3d::LbfgsState) * (size_t)rows));
-    HIP_TRY(hipMalloc(&d_out.p, sizeof(c3d::LbfgsState) * (size_t)rows));
-    HIP_TRY(hipMalloc(&d_flags.p, sizeof(int) * 2 * (size_t)rows));
-    HIP_TRY(hipMalloc(&d_shi.p, sizeof(int) * 2 * (size_t)rows));
-    HIP_TRY(hipMemcpyAsync(d_sums.p, sums, sizeof(double) * C3D_LBFGS_SUMS * (size_t)rows, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_in.p, st.data(), sizeof(c3d::LbfgsState) * (size_t)rows, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_flags.p, flags.data(), sizeof(int) * 2 * (size_t)rows, hipMemcpyHostToDevice, c->stream));
-    if (f64) {
-        const c3d::Model64 m64 = c3d::model64(dev_model(c), c->model);
-        LAUNCH_TRY("fp64 L-BFGS direction launch", c3d::launch_lbfgs_direction64(c3d::step64(m64, 9, 0.0, 1.0, 1.0, 0.85, 0.0), c3d::fire64(c->fire), rows,
-                                                                                 d_sums.p, d_in.p, d_flags.p, d_out.p, d_coef.p, d_shi.p, c->stream));
-    } else {
-        LAUNCH_TRY("L-BFGS direction launch", c3d::launch_lbfgs_direction(dev_model(c), dev_fire(c), rows, d_sums.p, d_in.p, d_flags.p, d_out.p,
-                                                                          d_coef.p, d_shi.p, c->stream));
-    }
-    HIP_TRY(hipMemcpyAsync(coef, d_coef.p, sizeof(double) * NC * (size_t)rows, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(st.data(), d_out.p, sizeof(c3d::LbfgsState) * (size_t)rows, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(flags.data(), d_shi.p, sizeof(int) * 2 * (size_t)rows, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    for (int r = 0; r < rows; ++r) {
-        const c3d::LbfgsState& s = st[r];
-        state_int_out[4 * r] = s.cnt; state_int_out[4 * r + 1] = s.head; state_int_out[4 * r + 2] = s.mem; state_int_out[4 * r + 3] = s.resets;
-        memcpy(state_dbl_out + (size_t)ND * r, reinterpret_cast<const char*>(&s) + 4 * sizeof(int32_t), sizeof(double) * ND);
-        mask_slot[2 * r] = flags[2 * r]; mask_slot[2 * r + 1] = flags[2 * r + 1];
-    }
-    return C3D_OK;
-}
-
-// Test hook: the rows of the L-BFGS move (c3d_lbfgs_move_row.inc) on a table of rows (c3d.h) — k_lbfgs_move_rows, or k64_lbfgs_move_rows
-// on a precision-64 context.  The host lays the rows out as the move kernels find them: x, F [3][np], the ring [s | y][8][3][np] with np
-// the rows padded to 256; columns beyond the rows hold zeros and are not run.
-namespace {
-template <class T, class Launch>
-int lbfgs_move_rows(c3d_ctx* c, int rows, const double* coef, int slot, const double* in, double* out, const char* what, Launch&& launch) {
-    constexpr int M = c3d::kLbfgsMaxPairs, NC = C3D_LBFGS_COEFS;
-    const int np = (rows + 255) / 256 * 256;
-    const size_t nh = c3d::lbfgs_hist_floats(np);
-    std::vector<T> hx(3 * (size_t)np, T(0)), hf(3 * (size_t)np, T(0)), hh(nh, T(0)), hc(NC), hd((size_t)np);
-    for (int k = 0; k < NC; ++k) hc[k] = (T)coef[k];
-    for (int r = 0; r < rows; ++r) {
-        const double* a = in + (size_t)C3D_LBFGS_MOVE_ROW_IN * r;
-        for (int k = 0; k < 3; ++k) {
-            hx[(size_t)k * np + r] = (T)a[k]; hf[(size_t)k * np + r] = (T)a[3 + k];
-            for (int j = 0; j < M; ++j) {
-                hh[((size_t)3 * j + k) * np + r] = (T)a[6 + 3 * j + k];                       // s_j
-                hh[((size_t)3 * (M + j) + k) * np + r] = (T)a[6 + 3 * M + 3 * j + k];         // y_j
-            }
-        }
-    }
-    DevTmp<T> d_x, d_xo, d_f, d_h, d_c, d_d;
-    HIP_TRY(hipMalloc(&d_x.p, sizeof(T) * hx.size()));
-    HIP_TRY(hipMalloc(&d_xo.p, sizeof(T) * hx.size()));
-    HIP_TRY(hipMalloc(&d_f.p, sizeof(T) * hf.size()));
-    HIP_TRY(hipMalloc(&d_h.p, sizeof(T) * nh));
-    HIP_TRY(hipMalloc(&d_c.p, sizeof(T) * NC));
-    HIP_TRY(hipMalloc(&d_d.p, sizeof(T) * (size_t)np));
-    HIP_TRY(hipMemcpyAsync(d_x.p, hx.data(), sizeof(T) * hx.size(), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_f.p, hf.data(), sizeof(T) * hf.size(), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_h.p, hh.data(), sizeof(T) * nh, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_c.p, hc.data(), sizeof(T) * NC, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemsetAsync(d_xo.p, 0, sizeof(T) * hx.size(), c->stream));
-    HIP_TRY(hipMemsetAsync(d_d.p, 0, sizeof(T) * (size_t)np, c->stream));
-    if (const hipError_t e = launch(np, d_c.p, d_x.p, d_xo.p, d_f.p, d_h.p, d_d.p); e != hipSuccess)
-        return fail(C3D_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-    HIP_TRY(hipMemcpyAsync(hx.data(), d_xo.p, sizeof(T) * hx.size(), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(hh.data(), d_h.p, sizeof(T) * nh, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(hd.data(), d_d.p, sizeof(T) * (size_t)np, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    const int next = (slot + 1) % M;
-    for (int r = 0; r < rows; ++r) {
-        double* o = out + (size_t)C3D_LBFGS_MOVE_ROW_OUT * r;
-        for (int k = 0; k < 3; ++k) {
-            o[k] = (double)hx[(size_t)k * np + r];
-            o[3 + k] = (double)hh[((size_t)3 * slot + k) * np + r];
-            o[6 + k] = (double)hh[((size_t)3 * next + k) * np + r];
-        }
-        o[9] = (double)hd[r];
-    }
-    return C3D_OK;
-}
-}  // namespace
-extern "C" int c3d_debug_lbfgs_move_rows(c3d_ctx* c, int rows, const double* coef, int mask, int slot, const double* in, double* out) {
-    if (!c || !coef || !in || !out) return fail(C3D_ERR_INVALID, "c3d_debug_lbfgs_move_rows: bad arguments");
-    if (rows < 1 || rows > (1 << 16)) return fail(C3D_ERR_INVALID, "c3d_debug_lbfgs_move_rows: rows is 1 .. 2^16");
-    if (mask < 0 || mask > 255) return fail(C3D_ERR_INVALID, "c3d_debug_lbfgs_move_rows: mask is 0 .. 255");
-    if (slot < 0 || slot >= c3d::kLbfgsMaxPairs) return fail(C3D_ERR_INVALID, "c3d_debug_lbfgs_move_rows: slot is 0 .. 7");
-    const bool f64 = c->precision == 64;
-    C3D_ENTRY(c, f64 ? unit_bit(UNIT_F64) : 0u);
-    if (f64)
-        return lbfgs_move_rows<double>(c, rows, coef, slot, in, out, "fp64 L-BFGS move rows launch",
-                                       [&](int np, const double* dc, const double* x, double* xo, const double* f, double* h, double* d) {
-                                           return c3d::launch_lbfgs_move_rows64(c3d::fire64(c->fire), rows, np, dc, mask, slot, x, xo, f, h, d, c->stream);
-                                       });
-    return lbfgs_move_rows<float>(c, rows, coef, slot, in, out, "L-BFGS move rows launch",
-                                  [&](int np, const float* dc, const float* x, float* xo, const float* f, float* h, float* d) {
-                                      return c3d::launch_lbfgs_move_rows(dev_fire(c), rows, np, dc, mask, slot, x, xo, f, h, d, c->stream);
-                                  });
 }
 
 // name of the kernel the last op of the last range ran on, as rocprofv3 prints it (without the argument list): the record its launch was made from

@@ -43,7 +43,9 @@
     const bool fin_lane = lane < RPW;
     const bool finisher = fin_lane && row < m.n;
     const size_t ix = roff + row, iy = ix + npad, iz = iy + npad;
-    const bool needs_partials = p.kind == 0 || p.kind == 1 || p.kind == 2 || p.kind == 5;
+    // (kind_reads_sums, and below kind_has_no_velocity, kind_continues_state, kind_stores_state of c3d_step_kinds.h, written out: as calls they
+    // change k_step's machine code)
+    const bool needs_partials = p.kind == kMdCouple || p.kind == kMdRescale || p.kind == kFire || p.kind == kTwoPoint;
 
     // ---- 1. every independent global load is issued before anything waits -------------------
     if constexpr (COLS::kStaged) {
@@ -56,18 +58,18 @@
     float4 q0 = make_float4(0, 0, 0, 0);
     if (needs_partials && lane < m.ntiles && (!WIDE || !C3D_SHARE_SCALARS || wave == 0)) q0 = pp[lane];      // (wave 0 alone forms the replica sums, below)
     float4 tv[RPW];
-    if (p.kind != 4) {
+    if (p.kind != kMdBegin) {
         if (pair_targets_in_use<POT, GEN, RPW, NC>(m)) pair_targets_prefetch(m, row0, lane, 0, tv);
         else tile_prefetch<RPW, NC>(m, tgt, row0, lane, 0, tv);
     }
     float vx0 = 0.0f, vy0 = 0.0f, vz0 = 0.0f;
-    if (finisher && p.kind != 3 && p.kind != 6) {
-        const float* vsrc = p.kind == 4 ? vinit : vin;
+    if (finisher && p.kind != kFireFirst && p.kind != kTwoPointFirst) {
+        const float* vsrc = p.kind == kMdBegin ? vinit : vin;
         vx0 = vsrc[ix]; vy0 = vsrc[iy]; vz0 = vsrc[iz];
     }
     FireState st;
     st.dt = fp.dt_start; st.alpha = fp.alpha_start; st.npos = 0; st.pad = 0;
-    if (p.kind == 2 || p.kind == 5) st = sin[rep];
+    if (p.kind == kFire || p.kind == kTwoPoint) st = sin[rep];
     // WIDE (large N: hundreds of tile sums): ONE wave of the workgroup forms the replica sums and the step's scalars and hands them to the
     // others through LDS across the barrier that waits for the coordinates anyway — the same values, the same bits (every wave used to
     // derive them for itself: ~90 of a wave's ~2200 VALU instructions per step at N = 2500, three quarters of them redundant)
@@ -91,7 +93,7 @@
     if (sums_here) {
         if (needs_partials) psum = wave_sum4(psum);
         sc = step_scalars(m, p, fp, psum, st);
-        if ((p.kind == 2 || p.kind == 3 || p.kind == 5 || p.kind == 6) && tile == 0 && tid == 0) sout[rep] = st;
+        if ((p.kind == kFire || p.kind == kFireFirst || p.kind == kTwoPoint || p.kind == kTwoPointFirst) && tile == 0 && tid == 0) sout[rep] = st;
         if constexpr (SHARE) {
             if (lane == 0) {
                 scb[0] = sc.lam; scb[1] = sc.cmx; scb[2] = sc.cmy; scb[3] = sc.cmz; scb[4] = sc.keep; scb[5] = sc.mix;
@@ -111,7 +113,7 @@
 
     // ---- 3. K2: pair forces for this wave's rows ---------------------------------------------
     float Fx = 0.0f, Fy = 0.0f, Fz = 0.0f;
-    if (p.kind != 4) tile_forces<POT, GEN, RPW, NC, true, WIDE>(m, p, tgt, xs, ys, zs, cols, row0, lane, tv, Fx, Fy, Fz);
+    if (p.kind != kMdBegin) tile_forces<POT, GEN, RPW, NC, true, WIDE>(m, p, tgt, xs, ys, zs, cols, row0, lane, tv, Fx, Fy, Fz);
 
     if constexpr (COLS::kStaged) C3D_STAMP(4);
     // ---- 4. epilogue: lanes 0..RPW-1 finish one row each --------------------------------------

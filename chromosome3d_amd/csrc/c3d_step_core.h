@@ -865,28 +865,30 @@ struct StepScalars {
 //       FIRE kind 2 = (v.F, F.F, v.v) of the previous evaluation; kind 3 (first step of a stage) = 0, fresh state
 //       two-point step size kind 5 = (s.y, F.F, y.y, s.s) of the previous evaluation; kind 6 (first step of a stage) = nothing, fresh state
 // TWO = false: a kernel that never runs the two-point minimiser's kinds (5 / 6) does not carry their branch (c3d_cluster.hip: k_cluster)
+// (here and in finish_row the families are written out, kind_is_md / kind_is_fire / kind_is_two_point of c3d_step_kinds.h by name: as calls
+// they change the machine code of the kernels these two are inlined into)
 template <bool TWO = true>
 __device__ __forceinline__ StepScalars step_scalars(const DevModel& m, const DevStep& p, const DevFire& fp, const float4 psum,
                                                     FireState& st) {
     StepScalars s;
     s.lam = 1.0f; s.cmx = s.cmy = s.cmz = 0.0f; s.keep = 0.0f; s.mix = 0.0f;
-    if (p.kind == 0 || p.kind == 1) {
+    if (p.kind == kMdCouple || p.kind == kMdRescale) {
         // hardware reciprocal / square root (1 ulp): these few scalars sit on every workgroup's critical path
         // between the arrival of the sums and the pair loop, and the correctly rounded sequences are ~35
         // dependent instructions each
         const float tprev = fmaxf(m.t_fac * psum.x, 1e-2f);
         // (T0 / T - 1 as ONE explicit fma: what every instantiation's backend made of "product, then - 1" under -ffp-contract=fast; see row_total)
         const float rt = __builtin_amdgcn_rcpf(tprev);
-        if (p.kind == 0) s.lam = __builtin_amdgcn_sqrtf(fmaxf(fmaf(p.dt * m.fbeta, fmaf(p.t_bath, rt, -1.0f), 1.0f), 0.0f));
+        if (p.kind == kMdCouple) s.lam = __builtin_amdgcn_sqrtf(fmaxf(fmaf(p.dt * m.fbeta, fmaf(p.t_bath, rt, -1.0f), 1.0f), 0.0f));
         else s.lam = __builtin_amdgcn_sqrtf(p.t_bath * rt);
         s.cmx = psum.y * m.inv_n; s.cmy = psum.z * m.inv_n; s.cmz = psum.w * m.inv_n;
         // products that a subtraction follows (finish_row: v - v_cm): hidden from the instruction selector, so that "product, then difference"
         // is what every kernel computes whatever the backend would like to fuse under -ffp-contract=fast (see row_total)
         asm("" : "+v"(s.cmx), "+v"(s.cmy), "+v"(s.cmz));
-    } else if (TWO && (p.kind == 5 || p.kind == 6)) {
+    } else if (TWO && (p.kind == kTwoPoint || p.kind == kTwoPointFirst)) {
         // two-point step size (Barzilai-Borwein) with the length one evaluation late (the CPU restatement: c3o_bb_step): lam = the length of the previous
         // move (to rebuild it from the force kept in the velocity slot), mix = the length of this one; st.dt / st.npos carry them on
-        const int k = p.kind == 6 ? 0 : st.npos;
+        const int k = p.kind == kTwoPointFirst ? 0 : st.npos;
         const float a_prev = st.dt;
         float a = a_prev;
         if (k == 0) a = fp.dt_start * fp.dt_start * m.acc;
@@ -898,7 +900,7 @@ __device__ __forceinline__ StepScalars step_scalars(const DevModel& m, const Dev
         }
         s.lam = a_prev; s.mix = a;
         st.dt = a; st.npos = k + 1;
-    } else if (p.kind == 2 || p.kind == 3) {
+    } else if (p.kind == kFire || p.kind == kFireFirst) {
         // FIRE (Bitzek et al. 2006) with the power test on the previous step's sums
         if (psum.x > 0.0f) {
             s.keep = 1.0f - st.alpha;
@@ -923,9 +925,9 @@ __device__ __forceinline__ void finish_row(const DevModel& m, const DevStep& p, 
                                            const FireState& st, float Fx, float Fy, float Fz, float x0, float y0, float z0,
                                            float vx0, float vy0, float vz0, float& xn, float& yn, float& zn, float& vx,
                                            float& vy, float& vz, float4& q) {
-    const bool is_md = p.kind == 0 || p.kind == 1 || p.kind == 4;
+    const bool is_md = p.kind == kMdCouple || p.kind == kMdRescale || p.kind == kMdBegin;
     if (is_md) {
-        if (p.kind == 4) {            // MD begin: take the Maxwell velocities, no move
+        if (p.kind == kMdBegin) {     // MD begin: take the Maxwell velocities, no move
             vx = vx0; vy = vy0; vz = vz0;
             xn = x0; yn = y0; zn = z0;
         } else {
@@ -938,11 +940,11 @@ __device__ __forceinline__ void finish_row(const DevModel& m, const DevStep& p, 
             zn = fmaf(p.dt, vz, z0);
         }
         q = make_float4(fmaf(vx, vx, fmaf(vy, vy, vz * vz)), vx, vy, vz);
-    } else if (p.kind == 5 || p.kind == 6) {
+    } else if (p.kind == kTwoPoint || p.kind == kTwoPointFirst) {
         // v0 = the force of the previous evaluation; the previous move is rebuilt from it (same clamp), y = F_old - F
         const float ms2 = fp.max_step * fp.max_step;
         const float ff = fmaf(Fx, Fx, fmaf(Fy, Fy, Fz * Fz));
-        if (p.kind == 5) {
+        if (p.kind == kTwoPoint) {
             float sx = sc.lam * vx0, sy = sc.lam * vy0, sz = sc.lam * vz0;
             const float s2 = fmaf(sx, sx, fmaf(sy, sy, sz * sz));
             const float scp = s2 > ms2 ? fp.max_step * __builtin_amdgcn_rsqf(s2) : 1.0f;

@@ -414,7 +414,7 @@ def test_host_helpers_refuse_coordinates_a_pdb_cannot_hold(tmp_path):
 
 
 def test_executor_and_loader_under_thread_sanitizer(tmp_path):
-    """The host units of csrc/ (c3d_api.cpp context, c3d_config.cpp configuration, c3d_gate.cpp code-object loader, c3d_run.cpp executor of c3d_run, c3d_analysis.cpp) and csrc/c3d_batch_main.cpp (device lists, lanes, XCD broker)
+    """The host units of csrc/ (c3d_api.cpp context, c3d_config.cpp configuration, c3d_gate.cpp code-object loader, c3d_run.cpp executor of c3d_run, c3d_debug.cpp table test hooks, c3d_analysis.cpp) and csrc/c3d_batch_main.cpp (device lists, lanes, XCD broker)
     as they are, built with -fsanitize=thread against a fake HIP layer (tools/sanitize/hip_stub.cpp: device memory is host memory, kernels
     compute nothing) and driven through the start that met a device exception in round 5 — eight contexts of one process on one device —,
     the production shape (8 devices x 3 lanes) and an API storm through every code object.  Passes when ThreadSanitizer reports nothing

@@ -48,7 +48,7 @@ def test_without_a_context_they_refuse_and_name_themselves(built):
 
 def test_the_refusals_name_the_entry():
     """every refusal the entries state (precision, kind, rows) is a C3D_ERR_INVALID that begins with the entry's name"""
-    text = open(os.path.join(SRC, "c3d_run.cpp")).read()
+    text = open(os.path.join(SRC, "c3d_debug.cpp")).read()
     for name, kinds in (("c3d_debug_step_scalars_f64", "kind is 0, 1, 2, 3, 5 or 6"), ("c3d_debug_row_finish_f64", "kind is 0, 1, 2, 3, 4, 5 or 6")):
         body = text[text.index('extern "C" int ' + name):]
         body = body[:body.index("C3D_ENTRY")]

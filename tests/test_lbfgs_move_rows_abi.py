@@ -41,7 +41,7 @@ def test_without_a_context_it_refuses_and_names_itself(built):
 
 
 def test_the_refusals_name_the_entry():
-    text = open(os.path.join(SRC, "c3d_run.cpp")).read()
+    text = open(os.path.join(SRC, "c3d_debug.cpp")).read()
     body = text[text.index('extern "C" int c3d_debug_lbfgs_move_rows('):]
     body = body[:body.index("C3D_ENTRY")]
     for what in ("bad arguments", "rows is 1 .. 2^16", "mask is 0 .. 255", "slot is 0 .. 7"):

@@ -38,7 +38,7 @@ def test_without_a_context_it_refuses_and_names_itself(built):
 
 
 def test_the_refusals_name_the_entry():
-    text = open(os.path.join(SRC, "c3d_run.cpp")).read()
+    text = open(os.path.join(SRC, "c3d_debug.cpp")).read()
     body = text[text.index('extern "C" int c3d_debug_row_finish('):]
     body = body[:body.index("C3D_ENTRY")]
     for what in ("bad arguments", "kind is 0, 1, 2, 3, 4, 5 or 6", "rows is 1 .. 2^20"):
@@ -61,7 +61,7 @@ def test_the_table_kernel_calls_the_step_kernels_function():
         assert stmt not in kernel, stmt
     for user in ("c3d_step_body.inc", "c3d_cluster.hip"):
         assert "finish_row(m, p" in open(os.path.join(SRC, user)).read(), user
-    run = open(os.path.join(SRC, "c3d_run.cpp")).read()
+    run = open(os.path.join(SRC, "c3d_debug.cpp")).read()
     assert "c3d::launch_row_finish(dev_model(c), dev_step(c, kind, dt, 1.0f, 1.0f, 0.85f, 0.0f), dev_fire(c), rows," in run
     assert "hipError_t launch_row_finish(" in open(os.path.join(SRC, "c3d_internal.h")).read()
     assert "hipError_t launch_row_finish(" in open(os.path.join(ROOT, "tools", "sanitize", "hip_stub.cpp")).read()

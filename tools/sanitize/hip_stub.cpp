@@ -1,6 +1,6 @@
 // hip_stub.cpp — a fake HIP layer for ThreadSanitizer runs of libc3d's HOST code on a box without a GPU (tools/sanitize/run.sh).
 //
-// The host units — c3d_api.cpp (context), c3d_config.cpp (configuration), c3d_gate.cpp (code-object loader), c3d_run.cpp (launch program, executor of c3d_run),
+// The host units — c3d_api.cpp (context), c3d_config.cpp (configuration), c3d_gate.cpp (code-object loader), c3d_run.cpp (launch program, executor of c3d_run), c3d_debug.cpp (table test hooks),
 // c3d_analysis.cpp (scoring) — and c3d_batch_main.cpp (per-device lists, lanes, the XCD broker) are compiled as they are, with -fsanitize=thread, and linked against THIS file instead of libamdhip64 and the kernels'
 // translation units: "device" memory is host memory, a stream is a counter, a copy is a memcpy, every kernel launcher returns success and
 // computes nothing — except K1, which is restated on the host so that the executor has restraints to write, and the multi-step launcher,

@@ -1,7 +1,7 @@
 #!/bin/bash
 # AddressSanitizer + UBSan (+ float-cast-overflow) over the host-only translation unit of libc3d, then a ThreadSanitizer
 # build of the same for the threaded matrix parser and concurrent callers of the host helpers, then (round 6) ThreadSanitizer over the
-# CONTEXT code and the c3d_batch executor — the five host units (c3d_api / c3d_config / c3d_gate / c3d_run / c3d_analysis .cpp) + c3d_batch_main.cpp as they are, against the fake HIP layer of hip_stub.cpp:
+# CONTEXT code and the c3d_batch executor — the six host units (c3d_api / c3d_config / c3d_gate / c3d_run / c3d_debug / c3d_analysis .cpp) + c3d_batch_main.cpp as they are, against the fake HIP layer of hip_stub.cpp:
 # eight contexts on one device, 8 devices x 3 lanes, and an API storm through every code object (executor_tsan_main.cpp).
 # CPU builds; GPU sanitizers are not available on this pool.   usage: run.sh [executor]   (executor: the round-6 part alone)
 set -e
@@ -19,7 +19,7 @@ fi
 # the executor and the context code under TSan, fake HIP layer (no libamdhip64, no kernels)
 CSRC="$ROOT/chromosome3d_amd/csrc"
 TF="-std=c++17 -O1 -g -fsanitize=thread -fno-omit-frame-pointer -D__HIP_PLATFORM_AMD__ -I${ROCM_PATH:-/opt/rocm}/include -Wno-unused-result"
-UNITS="api config gate run analysis host"     # the host units of libc3d: every translation unit without device code
+UNITS="api config gate run debug analysis host"     # the host units of libc3d: every translation unit without device code
 for u in $UNITS; do g++ $TF -c "$CSRC/c3d_$u.cpp" -o "$TMP/$u.o" & done
 g++ $TF -Dmain=c3d_batch_main -c "$CSRC/c3d_batch_main.cpp" -o "$TMP/batch.o" &
 g++ $TF -c "$HERE/hip_stub.cpp" -o "$TMP/stub.o" &
