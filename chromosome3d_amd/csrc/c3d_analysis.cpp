@@ -1,6 +1,6 @@
 // c3d_analysis.cpp — host unit of libc3d.so: the output side.  What a run's models are worth and how they relate, from the coordinates
 // resident on the device (kernels: c3d_score.hip): c3d_score_replicas, c3d_compare_replicas, c3d_superpose_replicas, c3d_rmsd_table,
-// c3d_ensemble_map, c3d_ensemble_score, c3d_geometry_replicas, c3d_separation_profile, c3d_stratified_score, c3d_bead_scores, c3d_accessibility (with the host-only c3d_sphere_points), c3d_compartments (with the host-only c3d_compartment_start) and the test hooks c3d_debug_if_ranks / c3d_debug_distance_ranks.  What they share comes first: typed
+// c3d_ensemble_map, c3d_ensemble_score, c3d_geometry_replicas, c3d_separation_profile, c3d_stratified_score, c3d_bead_scores, c3d_accessibility (with the host-only c3d_sphere_points), c3d_compartments (with the host-only c3d_compartment_start), c3d_insulation and the test hooks c3d_debug_if_ranks / c3d_debug_distance_ranks.  What they share comes first: typed
 // scratch slots (Slot, Block, Carve, CallScratch), the ranker (rank_matrix) and the models of a call (model_set_check, model_set_coords, gather_models).
 #include <limits>
 
@@ -1119,6 +1119,108 @@ extern "C" int c3d_compartments(c3d_ctx* c, const double* IF, const double* extr
             }
         }
     }
+    if (device_ms) {
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+        *device_ms = ms;
+    }
+    return C3D_OK;
+}
+
+// ---- insulation profiles and domain boundaries (c3d_score.hip k_ins_*) ----
+// c3d_insulation's one allocation: 24 n K of coordinates, the pick list, 16 n w_max per band (IF's, packed by the host; the consensus',
+// written on the device), 28 Q n_win n of results (mean, score, strength, boundary) and the fit's (Q - 1) n_win doubles and 4-tuples.
+// 455 beads x 20 models with IF, the consensus and windows {5, 10, 25}: 1.4 MB; 16384 x 20 with windows {8, 32, 128}: 105 MB (7.9 MB of
+// coordinates, 33.6 MB a band, 30.3 MB of results) — no n x n map, which alone is 2 GiB there.
+struct InsulationScratch : Carve {
+    Slot<double> xyz, band_if, band_cons, mean, score, strength, fit_r;
+    Slot<int32_t> pick, boundary, fit_counts;
+    InsulationScratch(int n, int K, int Kp, int Q, int nw, int wmax, bool has_if, bool consensus) {
+        const size_t rows = (size_t)Q * nw * n, band = (size_t)n * 2 * wmax, fits = has_if ? (size_t)(Q - 1) * nw : 0;
+        xyz = take<double>(3 * (size_t)n * K);
+        pick = take<int32_t>((size_t)Kp);
+        band_if = take<double>(has_if ? band : 0);
+        band_cons = take<double>(consensus ? band : 0);
+        mean = take<double>(rows);
+        score = take<double>(rows);
+        strength = take<double>(rows);
+        boundary = take<int32_t>(rows);
+        fit_r = take<double>(fits);
+        fit_counts = take<int32_t>(4 * fits);
+    }
+};
+
+extern "C" int c3d_insulation(c3d_ctx* c, const double* IF, const double* extra_xyz, int n_extra, const int32_t* pick, int n_pick, int flags, const int32_t* windows,
+                              int n_win, double cutoff, double min_strength, int tol, double* mean, double* score, int32_t* boundary, double* strength, double* fit_r,
+                              int32_t* fit_counts, double* device_ms) {
+    const char* const who = "c3d_insulation";
+    std::vector<int32_t> list;
+    if (int rc = ensemble_check(c, who, extra_xyz, n_extra, pick, n_pick, &list)) return rc;
+    const int n = c->n, K = c->nrep + n_extra, Kp = (int)list.size(), nw = n_win;
+    if (n < 3) return fail(C3D_ERR_INVALID, "c3d_insulation: maps of fewer than 3 beads have no bead with a square (n < 3)");
+    if (Kp > C3D_COMPARE_MAX_MODELS) return fail(C3D_ERR_INVALID, "c3d_insulation: more than 256 picks");
+    if (flags & ~(C3D_INSULATION_CONSENSUS | C3D_INSULATION_CONTACT | C3D_INSULATION_STAGE)) return fail(C3D_ERR_INVALID, "c3d_insulation: unknown flag bits");
+    const bool consensus = (flags & C3D_INSULATION_CONSENSUS) != 0, contact = (flags & C3D_INSULATION_CONTACT) != 0;
+    if (nw < 1 || nw > C3D_INSULATION_MAX_WINDOWS || !windows) return fail(C3D_ERR_INVALID, "c3d_insulation: n_win outside 1..C3D_INSULATION_MAX_WINDOWS, or no windows");
+    for (int k = 0; k < nw; ++k) {
+        if (windows[k] < 1 || windows[k] > C3D_INSULATION_MAX_WINDOW) return fail(C3D_ERR_INVALID, "c3d_insulation: a window outside 1..C3D_INSULATION_MAX_WINDOW");
+        if (k > 0 && windows[k] <= windows[k - 1]) return fail(C3D_ERR_INVALID, "c3d_insulation: the windows are not strictly ascending");
+        if (2 * windows[k] + 1 > n) return fail(C3D_ERR_INVALID, "c3d_insulation: a window leaves no bead inside (2w + 1 > n)");
+    }
+    if (consensus && Kp < 1) return fail(C3D_ERR_INVALID, "c3d_insulation: the consensus of an empty list");
+    if (contact && !ensemble_cutoff_ok(cutoff)) return fail(C3D_ERR_INVALID, "c3d_insulation: the contact flag needs a finite cutoff > 0");
+    if (!std::isfinite(min_strength) || min_strength < 0.0) return fail(C3D_ERR_INVALID, "c3d_insulation: min_strength is not finite or < 0");
+    if (tol < 0) return fail(C3D_ERR_INVALID, "c3d_insulation: tol < 0");
+    if (!mean && !score && !boundary && !strength && !fit_r && !fit_counts) return fail(C3D_ERR_INVALID, "c3d_insulation: every output is NULL");
+    if ((fit_r || fit_counts) && !IF) return fail(C3D_ERR_INVALID, "c3d_insulation: fit_r and fit_counts need the IF matrix");
+    if (int rc = model_set_coords(c, who, extra_xyz, n_extra)) return rc;
+    const int wmax = windows[nw - 1], W2 = 2 * wmax, has_if = IF ? 1 : 0, Q = has_if + Kp + (consensus ? 1 : 0);
+    // IF's upper band, row a the cells (a, a+1 .. a + 2 w_max), zeros beyond the matrix; what the squares read of it, 2 <= b - a, is checked here
+    std::vector<double> band;
+    if (has_if) {
+        band.assign((size_t)n * W2, 0.0);
+        for (int a = 0; a < n; ++a)
+            for (int col = 0; col < W2 && a + 1 + col < n; ++col) {
+                const int b = a + 1 + col;
+                const double v = IF[(size_t)a * n + b];
+                if (col >= 1) {
+                    if (!std::isfinite(v)) return fail(C3D_ERR_INVALID, "c3d_insulation: an IF entry is not finite");
+                    if (v < 0.0) return fail(C3D_ERR_INVALID, "c3d_insulation: an IF entry is negative");
+                    if (v != IF[(size_t)b * n + a]) return fail(C3D_ERR_INVALID, "c3d_insulation: the IF matrix is not symmetric");
+                }
+                band[(size_t)a * W2 + col] = v;
+            }
+    }
+    C3D_ENTRY(c, unit_bit(UNIT_SCORE));
+    const InsulationScratch L(n, K, Kp, Q, nw, wmax, has_if != 0, consensus);
+    CallScratch tmp;
+    if (int rc = tmp.alloc(L.total, who)) return rc;
+    PassEvents ev;
+    for (int k = 0; k < 2; ++k) HIP_TRY(hipEventCreate(&ev.e[k]));
+    c3d::InsJob job{};
+    job.n = n; job.Q = Q; job.has_if = has_if; job.n_models = Kp; job.consensus = consensus ? 1 : 0; job.contact = contact ? 1 : 0; job.nw = nw; job.wmax = wmax;
+    for (int k = 0; k < nw; ++k) job.w[k] = windows[k];
+    job.cutoff = cutoff;
+    job.xyz = L.xyz.at(tmp.p); job.pick = L.pick.at(tmp.p); job.band_if = L.band_if.at(tmp.p); job.band_cons = L.band_cons.at(tmp.p);
+    HIP_TRY(hipEventRecord(ev.e[0], c->stream));
+    if (int rc = gather_models(c, ModelSource::STATE, 0, c->nrep, L.xyz.at(tmp.p), extra_xyz, n_extra, "insulation launch")) return rc;
+    HIP_TRY(hipMemcpyAsync(L.pick.at(tmp.p), list.data(), sizeof(int32_t) * (size_t)Kp, hipMemcpyHostToDevice, c->stream));
+    if (has_if) HIP_TRY(hipMemcpyAsync(L.band_if.at(tmp.p), band.data(), L.band_if.bytes(), hipMemcpyHostToDevice, c->stream));
+    if (consensus) LAUNCH_TRY("insulation launch", c3d::launch_insulation_band(job, c->stream));
+    const bool stage = wmax <= c3d::kInsStageMax && (flags & C3D_INSULATION_STAGE) != 0;
+    LAUNCH_TRY("insulation launch", c3d::launch_insulation_squares(job, stage, L.mean.at(tmp.p), c->stream));
+    LAUNCH_TRY("insulation launch", c3d::launch_insulation_profile(job, L.mean.at(tmp.p), L.score.at(tmp.p), L.boundary.at(tmp.p), L.strength.at(tmp.p), c->stream));
+    if (has_if && Q > 1 && (fit_r || fit_counts))
+        LAUNCH_TRY("insulation launch", c3d::launch_insulation_fit(job, L.score.at(tmp.p), L.boundary.at(tmp.p), L.strength.at(tmp.p), min_strength, tol,
+                                                                   L.fit_r.at(tmp.p), L.fit_counts.at(tmp.p), c->stream));
+    if (mean) HIP_TRY(hipMemcpyAsync(mean, L.mean.at(tmp.p), L.mean.bytes(), hipMemcpyDeviceToHost, c->stream));
+    if (score) HIP_TRY(hipMemcpyAsync(score, L.score.at(tmp.p), L.score.bytes(), hipMemcpyDeviceToHost, c->stream));
+    if (strength) HIP_TRY(hipMemcpyAsync(strength, L.strength.at(tmp.p), L.strength.bytes(), hipMemcpyDeviceToHost, c->stream));
+    if (boundary) HIP_TRY(hipMemcpyAsync(boundary, L.boundary.at(tmp.p), L.boundary.bytes(), hipMemcpyDeviceToHost, c->stream));
+    if (Q > 1 && fit_r) HIP_TRY(hipMemcpyAsync(fit_r, L.fit_r.at(tmp.p), L.fit_r.bytes(), hipMemcpyDeviceToHost, c->stream));
+    if (Q > 1 && fit_counts) HIP_TRY(hipMemcpyAsync(fit_counts, L.fit_counts.at(tmp.p), L.fit_counts.bytes(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipEventRecord(ev.e[1], c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     if (device_ms) {
         float ms = 0;
         HIP_TRY(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));

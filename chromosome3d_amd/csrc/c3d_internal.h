@@ -544,6 +544,31 @@ hipError_t launch_compartment_build(const CptMaps& maps, const CptWork& w, int m
 hipError_t launch_compartment_round(const CptMaps& maps, const CptWork& w, int nv, bool first, hipStream_t s);
 hipError_t launch_compartment_finish(const CptMaps& maps, const CptWork& w, int nv, hipStream_t s);
 hipError_t launch_compartment_fit(const CptMaps& maps, const CptWork& w, int nv, hipStream_t s);
+// Insulation profiles and domain boundaries (c3d_insulation; k_ins_*, c3d_score_insulation.inc).  The Q maps of a call: map 0 is IF when
+// has_if — its upper band at band_if, row a the n x 2 wmax doubles M(a, a+1 .. a + 2 wmax), zeros beyond the matrix, packed and checked by
+// the host — the n_models maps after it one picked model each (pick, device: indices into the K models of xyz) and, with `consensus`, a
+// last map whose band launch_insulation_band writes to band_cons in the same layout: the pick list's mean distance, or with `contact`
+// the number of its models closer than cutoff.  w[0..nw) are the windows, ascending, wmax the last.  Every result row is n long and row
+// (q nw + k) belongs to map q and window k.
+// launch_insulation_band: band_cons.  launch_insulation_squares: mean (Q nw rows); `stage` (C3D_INSULATION_STAGE) picks the form that computes a tile's
+// distances once into LDS (wmax <= kInsStageMax only), the same bytes either way.  launch_insulation_profile: score, boundary and strength from
+// mean.  launch_insulation_fit: fit_r ((Q - 1) nw) and fit_counts ((Q - 1) nw x 4) of the maps after IF from score, boundary, strength.
+constexpr int kInsTile = 32;          // beads a workgroup of k_ins_squares owns
+constexpr int kInsStageMax = 40;      // the largest wmax at which the tile's (kInsTile + wmax - 1)^2 distances can be staged in LDS
+struct InsJob {
+    int n, Q, has_if, n_models, consensus, contact, nw, wmax;
+    int w[8];                         // C3D_INSULATION_MAX_WINDOWS
+    double cutoff;
+    const double* xyz;
+    const int* pick;
+    const double* band_if;
+    double* band_cons;
+};
+hipError_t launch_insulation_band(const InsJob& job, hipStream_t s);
+hipError_t launch_insulation_squares(const InsJob& job, bool stage, double* mean, hipStream_t s);
+hipError_t launch_insulation_profile(const InsJob& job, const double* mean, double* score, int* boundary, double* strength, hipStream_t s);
+hipError_t launch_insulation_fit(const InsJob& job, const double* score, const int* boundary, const double* strength, double min_strength, int tol,
+                                 double* fit_r, int* fit_counts, hipStream_t s);
 
 // Target matrix entry: NOE target in Angstrom, 0 = no restraint (host c3d_set_restraints and K1).
 inline float encode_target_host(float t) { return t > 0 ? t : 0.0f; }

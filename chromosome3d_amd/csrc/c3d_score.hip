@@ -31,6 +31,8 @@
 //   c3d_score_access.inc      k_access   a bead's exposed surface: a neighbour search in LDS feeding point-in-sphere tests (c3d_accessibility)
 //   c3d_score_compartment.inc k_cpt_*    compartment eigenvectors: the O/E map of IF, a model or the consensus, and orthogonal iteration on the
 //                             correlation of its rows through matrix-vector products with the map (c3d_compartments)
+//   c3d_score_insulation.inc  k_ins_*    insulation profiles and domain boundaries: a banded all-pairs sum a bead, the tile's distances staged
+//                             in LDS, every window out of one walk over nested squares (c3d_insulation)
 #include "c3d_score_core.h"
 
 namespace c3d {
@@ -268,6 +270,7 @@ hipError_t launch_if_rank_sort(double* M, int n, int range, unsigned long long* 
 #include "c3d_score_bead.inc"
 #include "c3d_score_access.inc"
 #include "c3d_score_compartment.inc"
+#include "c3d_score_insulation.inc"
 
 // loads the unit's code object on the current device and gives the k_str_* and k_bead_* kernels their dynamic-LDS allowance (c3d_gate.cpp "code objects":
 // once per device, never beside a launch)

@@ -19,11 +19,14 @@
 //       which loci lie on the surface of the fold and which are buried in it
 //   --compartments <prefix> writes <prefix>_compartments.txt — the first compartment eigenvector (PC1 of the correlation of the observed/expected
 //       map) of IF, of the models' consensus distance map and of every model, and how well each agrees with IF's
+//   --insulation <prefix> writes <prefix>_insulation.txt — the insulation profile and the domain boundaries of IF and of the models' consensus
+//       map per window, how many models place a boundary at each bead, and how well every model's profile fits IF's
 //
 // Success convention of the reference: <ID>_<M>.pdb exists, iam.running removed; on failure
 // iam.running is renamed iam.failed and the exit code is non-zero (:266-283).
 #include <sys/stat.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -96,6 +99,17 @@ static void usage() {
             "                 [--compartment-vectors <1..3>   eigenvectors computed and reported in the header lines; default 1]\n"
             "                 [--compartment-iters <k>   rounds of orthogonal iteration, 0..10000; default 200]\n"
             "                 [--compartment-min-sep <s>   pairs closer than s bins along the chain count as 1 in the observed/expected map; default 1]\n"
+            "                 [--insulation <prefix>   do the models reproduce the domain (TAD) boundaries of the data?  Computed on the device.\n"
+            "                                          <prefix>_insulation.txt: header lines `# window <w> consensus|model <r>: fit_r n_IF n_map IF_matched map_matched`\n"
+            "                                          (Pearson r of the map's insulation score against IF's — negative is good for distances, positive for contacts —\n"
+            "                                          and the boundaries of strength >= 0.1: IF's, the map's, IF's with one of the map's within tol beads, the map's\n"
+            "                                          with one of IF's), then one row per bead per window,\n"
+            "                                          `window bead IF consensus IF_boundary IF_strength consensus_boundary consensus_strength models`: the scores\n"
+            "                                          (log2 of the mean over the w x w square that straddles the bead over the row's mean; nan where the square does\n"
+            "                                          not fit), the boundary marks and their prominences, and the number of models with a boundary within tol beads]\n"
+            "                 [--insulation-windows <a,b,c>   half-widths of the squares in beads, ascending, 1..128; default 5,10,25, those that fit (2w + 1 <= n)]\n"
+            "                 [--insulation-contact <cutoff>   models and consensus: count contacts (distance < cutoff, in A) in the square instead of averaging the distance]\n"
+            "                 [--insulation-tol <beads>   how far apart two boundaries may lie and still match; default 1]\n"
             "                 [--accepted   also write <ID>a_<k>.pdb beside every <ID>_<k>.pdb, as CNS does for structures it accepts]\n");
 }
 
@@ -127,6 +141,10 @@ int main(int argc, char** argv) {
     const double t_start = now_s();
     std::string if_path, tbl_path, out_dir, id, seq_arg, similarity_path, rmsf_path, ensemble_prefix, geometry_prefix, stratified_prefix, per_bead_prefix, accessibility_prefix, compartments_prefix;
     int compartment_vectors = 1, compartment_iters = 200, compartment_min_sep = 1;
+    std::string insulation_prefix, insulation_windows = "5,10,25";
+    bool insulation_windows_given = false;
+    double insulation_contact = 0;                   // 0: mean distance
+    int insulation_tol = 1;
     double bead_radius = -1, probe_radius = -1;      // < 0: half of b0
     int sphere_points = 96;
     int superpose = 0, ensemble_top = 0, stratified_max_sep = 0;
@@ -182,6 +200,10 @@ int main(int argc, char** argv) {
         else if (s == "--compartment-vectors") compartment_vectors = atoi(next("--compartment-vectors"));
         else if (s == "--compartment-iters") compartment_iters = atoi(next("--compartment-iters"));
         else if (s == "--compartment-min-sep") compartment_min_sep = atoi(next("--compartment-min-sep"));
+        else if (s == "--insulation") insulation_prefix = next("--insulation");   // insulation profiles and domain boundaries (c3d_insulation)
+        else if (s == "--insulation-windows") { insulation_windows = next("--insulation-windows"); insulation_windows_given = true; }
+        else if (s == "--insulation-contact") insulation_contact = atof(next("--insulation-contact"));
+        else if (s == "--insulation-tol") insulation_tol = atoi(next("--insulation-tol"));
         else if (s == "--bead-radius") bead_radius = atof(next("--bead-radius"));
         else if (s == "--probe-radius") probe_radius = atof(next("--probe-radius"));
         else if (s == "--sphere-points") sphere_points = atoi(next("--sphere-points"));
@@ -194,6 +216,7 @@ int main(int argc, char** argv) {
     if (!stratified_prefix.empty() && if_path.empty()) { fprintf(stderr, "c3d_solve: --stratified needs --if: a run started from --tbl has no IF matrix\n"); return 2; }
     if (!per_bead_prefix.empty() && if_path.empty()) { fprintf(stderr, "c3d_solve: --per-bead needs --if: a run started from --tbl has no IF matrix\n"); return 2; }
     if (!compartments_prefix.empty() && if_path.empty()) { fprintf(stderr, "c3d_solve: --compartments needs --if: a run started from --tbl has no IF matrix\n"); return 2; }
+    if (!insulation_prefix.empty() && if_path.empty()) { fprintf(stderr, "c3d_solve: --insulation needs --if: a run started from --tbl has no IF matrix\n"); return 2; }
     if (id.empty()) {
         std::string base = if_path.empty() ? std::string("model") : if_path.substr(if_path.find_last_of('/') + 1);
         if (base.size() > 4 && base.substr(base.size() - 4) == ".txt") base.resize(base.size() - 4);
@@ -496,6 +519,57 @@ int main(int argc, char** argv) {
             for (int k = 1; k <= models; ++k) fprintf(f, " %.6f", vectors[(size_t)k * nv * n + i]);
             fprintf(f, "\n");
         }
+        fclose(f);
+    }
+    if (!insulation_prefix.empty()) {
+        std::vector<int32_t> order(models), win;
+        CHECK(c3d_rank(ctx, order.data()));
+        // the default windows are clipped to those that fit the chain; a list of the user's goes to the entry as it is
+        for (const char* p = insulation_windows.c_str(); *p;) {
+            char* end = nullptr;
+            const long w = strtol(p, &end, 10);
+            if (end == p) { fprintf(stderr, "c3d_solve: --insulation-windows takes a comma-separated list of integers\n"); return fail_exit(out_dir); }
+            if (insulation_windows_given || 2 * w + 1 <= n) win.push_back((int32_t)w);
+            p = *end == ',' ? end + 1 : end;
+            if (*end && *end != ',') { fprintf(stderr, "c3d_solve: --insulation-windows takes a comma-separated list of integers\n"); return fail_exit(out_dir); }
+        }
+        // the maps: IF, the models in rank order, their consensus
+        const int Q = models + 2, nw = (int)win.size();
+        const size_t rows = (size_t)Q * (nw > 0 ? nw : 1) * n, fits = (size_t)(Q - 1) * (nw > 0 ? nw : 1);
+        const double min_strength = 0.1;
+        std::vector<double> score(rows), strength(rows), fit_r(fits);
+        std::vector<int32_t> boundary(rows), counts(4 * fits);
+        CHECK(c3d_insulation(ctx, IF, nullptr, 0, order.data(), models, C3D_INSULATION_CONSENSUS | (insulation_contact != 0 ? C3D_INSULATION_CONTACT : 0), win.data(), nw,
+                             insulation_contact, min_strength, insulation_tol, nullptr, score.data(), boundary.data(), strength.data(), fit_r.data(), counts.data(), nullptr));
+        const std::string path = insulation_prefix + "_insulation.txt";
+        FILE* f = fopen(path.c_str(), "w");
+        if (!f) { fprintf(stderr, "c3d_solve: cannot write %s\n", path.c_str()); return fail_exit(out_dir); }
+        fprintf(f, "# window bead IF consensus IF_boundary IF_strength consensus_boundary consensus_strength models   (insulation scores; models: how many of the %d models have a boundary of strength >= %.1f within %d beads; model r is %s_<r>.pdb)\n",
+                models, min_strength, insulation_tol, id.c_str());
+        fprintf(f, "# models:");
+        for (int k = 0; k < models; ++k) fprintf(f, " %u", first_rep + (unsigned)order[k] + 1u);
+        if (insulation_contact != 0) fprintf(f, "\n# contacts below %.3f A; per map and window: fit_r n_IF n_map IF_matched map_matched\n", insulation_contact);
+        else fprintf(f, "\n# mean distance; per map and window: fit_r n_IF n_map IF_matched map_matched\n");
+        for (int k = 0; k < nw; ++k)
+            for (int q = 1; q < Q; ++q) {
+                const size_t at = (size_t)(q - 1) * nw + k;
+                if (q == Q - 1) fprintf(f, "# window %d consensus:", win[k]);
+                else fprintf(f, "# window %d model %d:", win[k], q);
+                fprintf(f, " %.6f %d %d %d %d\n", fit_r[at], counts[4 * at], counts[4 * at + 1], counts[4 * at + 2], counts[4 * at + 3]);
+            }
+        for (int k = 0; k < nw; ++k)
+            for (int i = 0; i < n; ++i) {
+                const size_t a_if = (size_t)k * n + i, a_co = ((size_t)(Q - 1) * nw + k) * n + i;
+                int support = 0;
+                for (int q = 1; q <= models; ++q) {
+                    const size_t row = ((size_t)q * nw + k) * n;
+                    bool near = false;
+                    for (int j = i - std::min(insulation_tol, i); j <= i + std::min(insulation_tol, n - 1 - i); ++j)
+                        near = near || (boundary[row + j] && strength[row + j] >= min_strength);
+                    support += near;
+                }
+                fprintf(f, "%d %d %.6f %.6f %d %.6f %d %.6f %d\n", win[k], i + 1, score[a_if], score[a_co], boundary[a_if], strength[a_if], boundary[a_co], strength[a_co], support);
+            }
         fclose(f);
     }
     double ms = 0;

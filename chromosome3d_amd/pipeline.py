@@ -267,6 +267,24 @@ def compartment_report(solver, IF, extra=None, pick=None, min_sep=1, n_vec=1, it
     return out
 
 
+def insulation_report(solver, IF, extra=None, pick=None, windows=(5, 10, 25), contact=None, min_strength=0.1, tol=1):
+    """Do the models reproduce the domain boundaries of the data?  Solver.insulation's dict for IF, every picked model and the consensus
+    map over the windows that fit the chain (2w + 1 <= n), with "support" [W, n] int32 — the number of model maps (not the consensus)
+    with a boundary of strength >= min_strength within tol beads of the bead — and "best" [W], per window the index into "maps" of the
+    model map whose score fits IF's best (the most negative fit_r for distance maps, the most positive for contact maps)."""
+    fit = [int(w) for w in windows if 2 * int(w) + 1 <= solver.n]
+    out = solver.insulation(IF, extra, pick, True, fit, contact, min_strength, tol)
+    marks = (out["boundary"][1:-1] == 1) & (out["strength"][1:-1] >= min_strength)                 # [models, W, n]
+    near = marks.copy()
+    for d in range(1, min(int(tol), solver.n - 1) + 1):
+        near[:, :, d:] |= marks[:, :, :-d]
+        near[:, :, :-d] |= marks[:, :, d:]
+    out["support"] = near.sum(axis=0).astype(np.int32)
+    r = out["fit_r"][:-1] * (1.0 if contact is not None else -1.0)
+    out["best"] = [1 + int(np.nanargmax(r[:, k])) if np.isfinite(r[:, k]).any() else -1 for k in range(len(fit))]
+    return out
+
+
 def build_models(solver, model_count=MODELCOUNT, seed=MD_SEED, first_replica=0, model=None, stages=None, fire=None,
                  gtol=1e-2, check_every=250, final_kind=5):
     """The replacement of `cns_solve < dgsa.inp` (:254-289): runs the whole annealing schedule

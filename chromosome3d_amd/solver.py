@@ -545,6 +545,47 @@ class Solver:
         out["device_ms"] = ms.value
         return out
 
+    def insulation(self, IF=None, extra=None, pick=None, consensus=False, windows=(5, 10, 25), contact=None, min_strength=0.0, tol=1, stage=False):
+        """Insulation profiles and domain boundaries on the device (c3d_insulation), for Q maps in this order: IF [n, n] if given, every
+        picked model (pick: indices into the K models of compare(), None: all; precision 64: the fp64 state), and with consensus=True
+        the pick list's mean distance map.  windows: strictly ascending half-widths w of the squares (1..128, 2w + 1 <= n).  contact: a
+        cutoff in Angstrom — the model and consensus maps then count contacts (d < cutoff) in the square instead of averaging the
+        distance.  A dict: "mean" [Q, W, n] (the map's mean over the w x w square that straddles the bead, NaN where the square does not
+        fit), "score" [Q, W, n] (log2 of mean over the row's mean; NaN for a bead without a positive mean), "boundary" [Q, W, n] int32
+        (1 at a strict minimum of IF's or a contact map's score, at a strict maximum of a distance map's), "strength" [Q, W, n] (the
+        extremum's prominence, 0 elsewhere), "maps" (the names of the Q maps), "windows", "device_ms", and with IF "fit_r" [Q-1, W]
+        (Pearson r of a map's score against IF's: a good distance map has r < 0, a good contact map r > 0) and "fit_counts" [Q-1, W, 4]
+        int32 (boundaries of strength >= min_strength: of IF, of the map, IF's with one of the map's within tol beads, the map's with
+        one of IF's).  stage=True stages a tile's distances in LDS where the largest window is <= 40 (the same bytes; for measurements).  Nothing of the solve
+        changes."""
+        n = self.n
+        m = None
+        if IF is not None:
+            m = np.ascontiguousarray(IF, dtype=np.float64)
+            assert m.shape == (n, n)
+        w = np.ascontiguousarray(windows, dtype=np.int32).reshape(-1)
+        W = len(w)
+        xptr, E = self._extra_models(extra)
+        p, n_pick = self._picked(pick)
+        Kp = n_pick if p is not None else self.nrep + E
+        has_if = 1 if m is not None else 0
+        Q = has_if + Kp + (1 if consensus else 0)
+        out = {"mean": np.empty((Q, W, n)), "score": np.empty((Q, W, n)), "boundary": np.empty((Q, W, n), dtype=np.int32), "strength": np.empty((Q, W, n))}
+        if has_if:
+            out["fit_r"] = np.empty((Q - 1, W))
+            out["fit_counts"] = np.empty((Q - 1, W, 4), dtype=np.int32)
+        flags = (_l.INSULATION_CONSENSUS if consensus else 0) | (_l.INSULATION_CONTACT if contact is not None else 0) | (_l.INSULATION_STAGE if stage else 0)
+        ms = C.c_double()
+        _l.check(self._L.c3d_insulation(self._h, _l.dptr(m) if has_if else None, xptr, E, _l.i32ptr(p) if p is not None else None, n_pick, flags,
+                                        _l.i32ptr(w), W, float(contact) if contact is not None else 0.0, float(min_strength), int(tol),
+                                        _l.dptr(out["mean"]), _l.dptr(out["score"]), _l.i32ptr(out["boundary"]), _l.dptr(out["strength"]),
+                                        _l.dptr(out["fit_r"]) if has_if else None, _l.i32ptr(out["fit_counts"]) if has_if else None, C.byref(ms)))
+        models = [int(k) for k in p] if p is not None else list(range(Kp))
+        out["maps"] = (["IF"] if has_if else []) + ["model %d" % k for k in models] + (["consensus"] if consensus else [])
+        out["windows"] = [int(x) for x in w]
+        out["device_ms"] = ms.value
+        return out
+
     def rank(self):
         r = np.empty(self.nrep, dtype=np.int32)
         _l.check(self._L.c3d_rank(self._h, _l.i32ptr(r)))

@@ -789,6 +789,70 @@ int c3d_compartments(c3d_ctx* ctx, const double* IF, const double* extra_xyz, in
                      int flags, int min_sep, int n_vec, int iters, const double* start,
                      double* expected, double* vectors, double* share, double* residual,
                      double* agreement, double* same_side, double* device_ms);
+/* Insulation profiles and domain boundaries on the device (c3d_score_insulation.inc k_ins_*): do the models reproduce the domains (TADs) of
+ * the data?  Compartments are the large-scale feature of a contact map, domain boundaries the local one; the standard read-out is the
+ * insulation profile: for every bin the mean of the map over the square that straddles the bin.  Its minima on a contact map, or maxima on
+ * a distance map, are the boundaries, and each boundary has a strength.
+ *
+ * Maps, in order, Q in all: IF if non-NULL (n x n with the context's n); then one map per picked model; then, with
+ *   C3D_INSULATION_CONSENSUS in flags, the consensus of the pick list.  Models, pick, n_pick (at most 256), extra models and the fp64
+ *   state of a precision-64 context are taken exactly as c3d_compartments takes them, and the pair distance d is the same:
+ *   sqrt(((ux ux) + uy uy) + uz uz), every operation rounded on its own.
+ * Windows.  `windows` holds n_win (1..C3D_INSULATION_MAX_WINDOWS) strictly ascending w with 1 <= w <= C3D_INSULATION_MAX_WINDOW and
+ *   2w + 1 <= n.  w_max is the last of them.
+ * Definitions, per map M, window w and bead i:
+ *   1. Square.  Bead i is inside when w <= i <= n-1-w; its square is the w^2 cells (a, b) with a in [i-w, i-1] and b in [i+1, i+w].  Only
+ *      the band 2 <= b-a <= 2 w_max of a map is ever read.
+ *   2. mean[q][w][i] is NaN for a bead that is not inside.  For a bead that is inside, without C3D_INSULATION_CONTACT:
+ *      IF: (sum M(a,b)) / w^2.  Model: (sum d(a,b)) / w^2.  Consensus: (sum c(a,b)) / w^2, c(a,b) the pick list's mean distance, summed
+ *      in list order from 0 and divided once by Kp, as c3d_ensemble_map defines `mean`.
+ *      With C3D_INSULATION_CONTACT: model: #{cells: d < cutoff} / w^2; consensus: #{(k, cell): d_k < cutoff} / (w^2 Kp); both exact
+ *      integer counts (they are below 2^53 and are carried in doubles, where every count is exact), divided once; the < is strict, as in
+ *      c3d_ensemble_map.  IF is unchanged.
+ *   3. score[q][w][i] = log2(mean_i / mbar), mbar the mean of mean_i over the valid beads; a bead is valid when it is inside and
+ *      mean_i > 0, every other bead gets NaN; if no bead is valid the whole row is NaN.
+ *   4. Boundaries are a function of the score row alone, through exact operations only (comparisons, min/max, one subtraction).
+ *      y = -score for IF and for contact maps, where boundaries are minima; y = +score for distance maps, where they are maxima.  Bead i
+ *      is a boundary if i-1, i and i+1 are valid and y_i > y_{i-1} and y_i > y_{i+1}.  Its strength is the prominence as
+ *      scipy.signal.peak_prominences defines it: walk left from i-1 while the bead is valid and y_j <= y_i, keeping the minimum; the same
+ *      to the right; strength = y_i - max(left minimum, right minimum).  boundary is 0 or 1; strength is 0 where boundary is 0.
+ *   5. Fit to IF (only with IF), for the Q - 1 maps after it, per window.  fit_r = Pearson r of the map's score against IF's score over
+ *      the beads valid in both: the means first, then the centred sums, r = sxy / sqrt(sxx syy); NaN with fewer than 3 such beads or a
+ *      constant side.  Its sign is left as it comes: a good distance map has r < 0, a good contact map r > 0, the convention of
+ *      c3d_ensemble_score.  fit_counts[4] = {n_IF, n_map, IF_matched, map_matched}: the boundaries counted are those with strength >=
+ *      min_strength, and one is matched when the other set has a counted boundary within tol beads.  Integers, exact given the boundary
+ *      and strength arrays.
+ * Outputs, any may be NULL but not all of them; fit_r and fit_counts are refused without IF.  mean, score, strength: Q x n_win x n
+ *   doubles; boundary: Q x n_win x n int32; fit_r: (Q - 1) x n_win doubles; fit_counts: (Q - 1) x n_win x 4 int32; device_ms, optional:
+ *   the HIP-event time of the call (there is no stat key for it).
+ * How it runs.  No n x n map is formed for anything: the host packs IF's upper band (row a holds M(a, a+1 .. a + 2 w_max)) and uploads
+ *   n x 2 w_max doubles, k_ins_band writes the consensus in the same layout, and a model's squares come straight from its coordinates.
+ *   The squares of a bead are nested — the square of w is the union of the rings r = max(i-a, b-i) = 1..w — so every listed window comes
+ *   out of one walk over the largest square a bead is inside.  A workgroup owns a map and 32 consecutive beads, their coordinates and a halo of w_max
+ *   on either side in LDS, and every bead's walk computes its distances from them.  With C3D_INSULATION_STAGE, up to w_max = 40, the
+ *   tile's distinct distances are computed once into LDS and the walks read them: the same values in the same order, the same bytes.
+ *   Measured (profiles/r31_insulation.md) the staged form is not faster at any w_max it fits, so it is not the default.
+ * Every floating-point sum is one of positive terms whose order follows from n, the window and the pick list alone, through the scoring
+ * unit's one block reduction: no atomics on floating-point data, no prefix sums, two calls return the same bytes, a model's rows are
+ * the same bytes whether it is analysed alone or among others, and a window's whether it is listed alone or with others.  No state of
+ * the solve changes.
+ * C3D_ERR_INVALID with the function's name, before any launch and with nothing written: the refusals of c3d_compartments for the context,
+ * models, picks, extra coordinates and unknown flag bits; n < 3; n_win outside 1..C3D_INSULATION_MAX_WINDOWS or windows NULL; a window out
+ * of range, not ascending or with 2w + 1 > n; consensus with an empty list; C3D_INSULATION_CONTACT with a cutoff that is not finite or
+ * <= 0; min_strength not finite or < 0; tol < 0; the outputs as above; IF asymmetric, not finite or negative anywhere in the band that is
+ * read (the host checks while it packs the band).  C3D_ERR_NOMEM: no device memory for the scratch.
+ * Scratch, one allocation per call, freed before it returns: 24 n K of coordinates + 16 n w_max per band (IF, consensus) +
+ * 28 Q n_win n of results: 1.4 MB at 455 beads x 20 models with IF, the consensus and windows {5, 10, 25}; 105 MB at 16384 x 20 with
+ * windows {8, 32, 128} (7.9 MB of coordinates, 33.6 MB a band, 30.3 MB of results), where one n x n map alone is 2 GiB. */
+#define C3D_INSULATION_MAX_WINDOW   128
+#define C3D_INSULATION_MAX_WINDOWS  8
+#define C3D_INSULATION_CONSENSUS    1   /* one more map after the models: the pick list's mean distance map / pooled contacts */
+#define C3D_INSULATION_CONTACT      2   /* model and consensus maps: contacts (d < cutoff) in the square, not the mean distance */
+#define C3D_INSULATION_STAGE        4   /* stage a tile's distances in LDS where w_max <= 40: the same bytes, measured no faster; for measurements */
+int c3d_insulation(c3d_ctx* ctx, const double* IF, const double* extra_xyz, int n_extra, const int32_t* pick, int n_pick,
+                   int flags, const int32_t* windows, int n_win, double cutoff, double min_strength, int tol,
+                   double* mean, double* score, int32_t* boundary, double* strength,
+                   double* fit_r, int32_t* fit_counts, double* device_ms);
 /* rank[k] = replica index with the k-th lowest int(E_noe) (chromosome3D.pl:796-802,822-828);
  * ties broken by replica id. */
 int c3d_rank(c3d_ctx* ctx, int32_t* rank);

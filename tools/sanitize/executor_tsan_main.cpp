@@ -121,6 +121,17 @@ static void api_storm(int device_count) {
                                             cres.data(), cagree.data(), cside.data(), &cpt_ms) == C3D_OK && cpt_ms >= 0;
                 ok = ok && c3d_compartments(c, nullptr, nullptr, 0, picked, 3, 0, 1, C3D_COMPARTMENT_MAX_VECTORS + 1, 0, nullptr, nullptr, cvec.data(), nullptr, nullptr,
                                             nullptr, nullptr, nullptr) == C3D_ERR_INVALID;
+                // (IF + 4 models + consensus: 6 maps, 2 windows)
+                const int32_t iwin[2] = {2, 5}, ibad[2] = {5, 2};
+                std::vector<double> imean(6 * 2 * (size_t)n), iscore(6 * 2 * (size_t)n), istr(6 * 2 * (size_t)n), ifit(5 * 2);
+                std::vector<int32_t> ibound(6 * 2 * (size_t)n), icounts(5 * 2 * 4);
+                double ins_ms = -1;
+                ok = ok && c3d_insulation(c, IF.data(), nullptr, 0, nullptr, 0, C3D_INSULATION_CONSENSUS, iwin, 2, 0.0, 0.1, 1, imean.data(), iscore.data(), ibound.data(),
+                                          istr.data(), ifit.data(), icounts.data(), &ins_ms) == C3D_OK && ins_ms >= 0;
+                ok = ok && c3d_insulation(c, nullptr, nullptr, 0, picked, 3, C3D_INSULATION_CONTACT, iwin, 2, 7.6, 0.0, 0, imean.data(), nullptr, ibound.data(), nullptr,
+                                          nullptr, nullptr, nullptr) == C3D_OK;
+                ok = ok && c3d_insulation(c, nullptr, nullptr, 0, picked, 3, 0, ibad, 2, 0.0, 0.0, 0, imean.data(), nullptr, nullptr, nullptr, nullptr, nullptr,
+                                          nullptr) == C3D_ERR_INVALID;
                 if (what == 2) { unsigned long long a, b, d; ok = ok && c3d_debug_tear16(c, 4, &a, &b, &d) == C3D_OK; }
             }
             if (!ok) { fprintf(stderr, "api storm thread %d: %s\n", t, c3d_last_error()); ++failures; }

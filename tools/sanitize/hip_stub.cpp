@@ -694,4 +694,107 @@ hipError_t launch_compartment_fit(const CptMaps& S, const CptWork& w, int nv, hi
     return hipSuccess;
 }
 
+// c3d_insulation: the four launchers restated on the host with plain loops in index order (the definitions of include/c3d.h; no tiles,
+// no rings, no block reduction: the sums' orders are not the device's)
+static double stub_ins_cell(const InsJob& J, int q, int a, int b) {
+    const int n = J.n, mi = q - J.has_if;
+    if (J.has_if && q == 0) return J.band_if[(size_t)a * 2 * J.wmax + (b - a - 1)];
+    if (mi >= J.n_models) return J.band_cons[(size_t)a * 2 * J.wmax + (b - a - 1)];
+    const double d = stub_dist(J.xyz + (size_t)J.pick[mi] * 3 * n, a, b);
+    return J.contact ? (d < J.cutoff ? 1.0 : 0.0) : d;
+}
+hipError_t launch_insulation_band(const InsJob& J, hipStream_t) {
+    LaunchScope ls;
+    const int n = J.n, W2 = 2 * J.wmax;
+    for (int a = 0; a < n; ++a)
+        for (int col = 0; col < W2; ++col) {
+            const int b = a + 1 + col;
+            double v = 0.0;
+            if (col >= 1 && b < n) {
+                for (int k = 0; k < J.n_models; ++k) {
+                    const double d = stub_dist(J.xyz + (size_t)J.pick[k] * 3 * n, a, b);
+                    v += J.contact ? (d < J.cutoff ? 1.0 : 0.0) : d;
+                }
+                if (!J.contact) v /= (double)J.n_models;
+            }
+            J.band_cons[(size_t)a * W2 + col] = v;
+        }
+    return hipSuccess;
+}
+hipError_t launch_insulation_squares(const InsJob& J, bool, double* mean, hipStream_t) {
+    LaunchScope ls;
+    const int n = J.n;
+    for (int q = 0; q < J.Q; ++q)
+        for (int k = 0; k < J.nw; ++k)
+            for (int i = 0; i < n; ++i) {
+                const int w = J.w[k];
+                double sum = 0.0;
+                const bool inside = i >= w && i <= n - 1 - w;
+                for (int a = i - w; inside && a <= i - 1; ++a)
+                    for (int b = i + 1; b <= i + w; ++b) sum += stub_ins_cell(J, q, a, b);
+                const bool pooled = J.contact && q - J.has_if >= J.n_models;
+                mean[((size_t)q * J.nw + k) * n + i] = inside ? sum / (double)(w * w * (pooled ? J.n_models : 1)) : std::nan("");
+            }
+    return hipSuccess;
+}
+hipError_t launch_insulation_profile(const InsJob& J, const double* mean, double* score, int* boundary, double* strength, hipStream_t) {
+    LaunchScope ls;
+    const int n = J.n;
+    for (int row = 0; row < J.Q * J.nw; ++row) {
+        const double* m = mean + (size_t)row * n;
+        double* s = score + (size_t)row * n;
+        double sum = 0.0, cnt = 0.0;
+        for (int i = 0; i < n; ++i)
+            if (m[i] > 0.0) { sum += m[i]; cnt += 1.0; }
+        for (int i = 0; i < n; ++i) s[i] = m[i] > 0.0 ? std::log2(m[i] / (sum / cnt)) : std::nan("");
+        const bool minima = (J.has_if && row / J.nw == 0) || J.contact;
+        for (int i = 0; i < n; ++i) {
+            const double yi = minima ? -s[i] : s[i];
+            int mark = 0;
+            double prom = 0.0;
+            if (i >= 1 && i + 1 < n && yi > (minima ? -s[i - 1] : s[i - 1]) && yi > (minima ? -s[i + 1] : s[i + 1])) {
+                double lmin = yi, rmin = yi;
+                for (int j = i - 1; j >= 0 && (minima ? -s[j] : s[j]) <= yi; --j) lmin = std::fmin(lmin, minima ? -s[j] : s[j]);
+                for (int j = i + 1; j < n && (minima ? -s[j] : s[j]) <= yi; ++j) rmin = std::fmin(rmin, minima ? -s[j] : s[j]);
+                mark = 1;
+                prom = yi - std::fmax(lmin, rmin);
+            }
+            boundary[(size_t)row * n + i] = mark;
+            strength[(size_t)row * n + i] = prom;
+        }
+    }
+    return hipSuccess;
+}
+hipError_t launch_insulation_fit(const InsJob& J, const double* score, const int* boundary, const double* strength, double min_strength, int tol, double* fit_r,
+                                 int* fit_counts, hipStream_t) {
+    LaunchScope ls;
+    const int n = J.n;
+    for (int q = 1; q < J.Q; ++q)
+        for (int k = 0; k < J.nw; ++k) {
+            const size_t rf = (size_t)k * n, rm = ((size_t)q * J.nw + k) * n, out = (size_t)(q - 1) * J.nw + k;
+            double sx = 0.0, sy = 0.0, cnt = 0.0, sxy = 0.0, sxx = 0.0, syy = 0.0;
+            for (int i = 0; i < n; ++i)
+                if (!std::isnan(score[rm + i]) && !std::isnan(score[rf + i])) { sx += score[rm + i]; sy += score[rf + i]; cnt += 1.0; }
+            const double mx = sx / cnt, my = sy / cnt;
+            for (int i = 0; i < n; ++i)
+                if (!std::isnan(score[rm + i]) && !std::isnan(score[rf + i])) {
+                    const double ex = score[rm + i] - mx, ey = score[rf + i] - my;
+                    sxy += ex * ey; sxx += ex * ex; syy += ey * ey;
+                }
+            if (fit_r) fit_r[out] = cnt >= 3.0 && sxx > 0.0 && syy > 0.0 ? sxy / sqrt(sxx * syy) : std::nan("");
+            int c[4] = {0, 0, 0, 0};
+            for (int i = 0; i < n; ++i) {
+                const bool in_f = boundary[rf + i] && strength[rf + i] >= min_strength, in_m = boundary[rm + i] && strength[rm + i] >= min_strength;
+                bool near_f = false, near_m = false;
+                for (int j = i - std::min(tol, i); j <= i + std::min(tol, n - 1 - i); ++j) {
+                    near_f = near_f || (boundary[rf + j] && strength[rf + j] >= min_strength);
+                    near_m = near_m || (boundary[rm + j] && strength[rm + j] >= min_strength);
+                }
+                c[0] += in_f; c[1] += in_m; c[2] += in_f && near_m; c[3] += in_m && near_f;
+            }
+            for (int f = 0; f < 4 && fit_counts; ++f) fit_counts[out * 4 + f] = c[f];
+        }
+    return hipSuccess;
+}
+
 }  // namespace c3d
