@@ -343,6 +343,7 @@ extern "C" int c3d_set_restraints(c3d_ctx* c, int n, int R, const int32_t* ri, c
         const int i = ri[k] - 1, j = rj[k] - 1;
         if (i < 0 || j < 0 || i >= n || j >= n || i == j) return fail(C3D_ERR_INVALID, "c3d_set_restraints: index out of range");
         if (rt10[k] <= 0) continue;
+        if ((i > j ? i - j : j - i) < c->model.min_sep) continue;      // closer than min_sep: no restraint, as in the matrix entry and k64_targets
         const float t = (float)((double)rt10[k] / 10.0);
         enc[(size_t)i * c->npad + j] = c3d::encode_target_host(t);
         enc[(size_t)j * c->npad + i] = c3d::encode_target_host(t);
@@ -353,6 +354,8 @@ extern "C" int c3d_set_restraints(c3d_ctx* c, int n, int R, const int32_t* ri, c
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->h_dist10.clear();
     // the list itself, for a precision-64 context (c3d_init_replicas): 0-based, i < j, the last entry of a pair as in `enc` above
+    // (k64_targets drops the pairs closer than min_sep itself); `held` = the pairs that carry a restraint, what c3d_num_restraints reports
+    int held = 0;
     {
         std::vector<std::pair<uint64_t, int>> key;
         key.reserve(R);
@@ -367,10 +370,11 @@ extern "C" int c3d_set_restraints(c3d_ctx* c, int n, int R, const int32_t* ri, c
             if (rt10[key[q].second] > 0) last = rt10[key[q].second];
             if (q + 1 < key.size() && key[q + 1].first == key[q].first) continue;
             if (last > 0) { c->r_i.push_back((int32_t)(key[q].first / n)); c->r_j.push_back((int32_t)(key[q].first % n)); c->r_t10.push_back(last); }
+            if (last > 0 && (int)(key[q].first % n) - (int)(key[q].first / n) >= c->model.min_sep) ++held;
             last = 0;
         }
     }
-    c->R = R;
+    c->R = held;
     c->have_targets = true;
     build_program(c);
     return C3D_OK;

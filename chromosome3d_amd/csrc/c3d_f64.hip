@@ -9,8 +9,9 @@
 //              replica's N x N pair matrix, 2 rows per wave; the replica's coordinates are staged once in LDS as
 //              structure-of-arrays doubles (3 x 8 x npad bytes), lanes run along the columns (column 64 k + lane: every
 //              target load is one 512-byte line per wave, every coordinate read a conflict-free ds_read_b64), two columns
-//              in flight per lane.  1 / d comes from v_rsq_f64 (23 bits) and two coupled Newton steps that deliver d and
-//              1 / d together (8 fused operations instead of the ~30 of a correctly rounded sqrt and a division); the two
+//              in flight per lane.  1 / d comes from a 23-bit seed (v_rsq_f32) and ONE coupled Newton step that delivers d and
+//              1 / d together, each to about 5e-14 relative (sqrt_hrsqrt64 below; 5 fused operations instead of the ~30 of a
+//              correctly rounded sqrt and a division); the two
 //              rows of a wave are reduced in ONE transposing DPP butterfly on the 32-bit halves.  The row's owner lane
 //              adds the chain terms, integrates the row and leaves its contribution to the replica sums; the sums a step
 //              needs (kinetic energy, centre-of-mass velocity, FIRE power and norms) are the per-tile partial sums the
@@ -77,8 +78,14 @@ __device__ __forceinline__ double reduce_rows64(double a0, double a1, int lane) 
     return xrow_sum64(k);
 }
 
-// d = sqrt(r2) and h = 1 / (2 d) together: v_rsq_f64 (2^29 ulp: 23 bits) + two coupled Newton steps (Goldschmidt form);
-// the results are within an ulp or two of the correctly rounded values (r2 >= 1e-12: no denormal, no zero)
+// d = sqrt(r2) and h = 1 / (2 d) together: a 23-bit seed + ONE coupled Newton step (Goldschmidt form).  With the seed's relative error
+// e (v_rsq_f32's ulp and the rounding of r2 to float: |e| <= 1.5 x 2^-23 = 1.8e-7), g = sqrt(r2) (1 + e) and h = (1 + e) / (2 sqrt(r2)),
+// so r = 1/2 - g h = -e - e^2 / 2 and g (1 + r) = sqrt(r2) (1 - 1.5 e^2): d and h come out within 1.5 e^2 = 4.8e-14 relative, some
+// 200 double ulps, not "an ulp or two" — measured pair by pair in tests/test_gpu_pair_table.py (profiles/r34_pair_table.md).  Under the
+// suite's fp64 force cap (1e-11 of a row's scale) that is two hundred times inside; against a pair's OWN force near d = T it is
+// unbounded in relative terms (the force is 2 w S (d - T) / d), which is why that table bounds a component by the row's term scales.
+// The second step (C3D_F64_TWO_NEWTON, defined by no build) would bring both within an ulp or two at three more fused operations a
+// pair.  (r2 >= 1e-30: no denormal, no zero.)
 __device__ __forceinline__ void sqrt_hrsqrt64(double r2, double& d, double& h) {
     // 23-bit seeds from the fp32 unit (v_rsq_f64 is no better and no faster), the halving done there too; 1e-30 <= r2 <= 1e9
     const float yf = __builtin_amdgcn_rsqf((float)r2);
@@ -144,7 +151,8 @@ __device__ __forceinline__ double half_noe_grad64(const Model64& m, double delta
         else if constexpr (POT == 3) return fmin(fmax(delta, -m.mrs), m.rs);
         else if constexpr (POT == 4) {
             // lower side beyond mrs: dE/dD = 2 mrs^4 / D^3 (soft form, exponent 2, no asymptote) = the lower bound -mrs (mrs / D)^3 of
-            // the same clamp; 1 / D from v_rcp_f64 and two Newton steps, D held at >= mrs (the bound is -mrs inside the square part)
+            // the same clamp; 1 / D from a 23-bit seed (v_rcp_f32) and ONE Newton step: with the seed's relative error e (|e| <= 1.5 x 2^-23)
+            // y (2 - D y) = (1 - e^2) / D, 3.2e-14 relative, three times that in the bound (see sqrt_hrsqrt64; C3D_F64_TWO_NEWTON as there)
             // D = |delta| (a free source modifier; round 4, second session: it was max(-delta, mrs)): inside the square part and above the
             // target the bound -mrs^4 / D^3 then lies BELOW delta and does not bind; delta = 0 (or below the fp32 seed's range): the seed is
             // inf, the Newton step NaN, and max(delta, NaN) = delta

@@ -114,11 +114,16 @@ int c3d_default_schedule(c3d_stage* stages, int cap, int min_steps);
 /* K1 on device: D = K * mean(IF^alpha) / IF^alpha, quantised like "%.1f"; builds the n x n
  * target matrix (restraints for |i-j| >= min_sep, IF > 0).  IF is row-major n*n (host). */
 int c3d_set_if_matrix(c3d_ctx* ctx, const double* IF, int n, double alpha, double K);
-/* Alternative entry: restraint rows as in contact.tbl (1-based i, j; target in tenths of A). */
+/* Alternative entry: restraint rows as in contact.tbl (1-based i, j; target in tenths of A).  A row with a target <= 0 carries no
+ * restraint; of several rows of one pair the last with a positive target holds.  Pairs closer than min_sep carry no restraint, as in
+ * the matrix — in every precision and every kernel form.  min_sep is the model's at this call and stays it: once targets are set
+ * (here or by c3d_set_if_matrix) c3d_set_model refuses a model with another min_sep (C3D_ERR_INVALID). */
 int c3d_set_restraints(c3d_ctx* ctx, int n, int R, const int32_t* ri, const int32_t* rj, const int32_t* rt10);
 /* n*n int32, tenths of an Angstrom, -10 where IF == 0 (the <ID>.dist content). */
 int c3d_get_dist10(c3d_ctx* ctx, int32_t* dist10);
 int c3d_num_beads(const c3d_ctx* ctx);
+/* The pairs that carry a restraint: i < j, j - i >= min_sep, target > 0 — counted once a pair, whichever entry set the targets (a list
+ * with rows closer than min_sep, rows without a target or several rows of one pair reports fewer than its R). */
 int c3d_num_restraints(const c3d_ctx* ctx);
 
 int c3d_set_model(c3d_ctx* ctx, const c3d_model* m);
@@ -161,7 +166,7 @@ int c3d_set_schedule(c3d_ctx* ctx, const c3d_stage* stages, int n_stages, const 
  *                   2560 beads by default and up to 16384 behind f64_max_beads (below; c3d_init_replicas returns C3D_ERR_INVALID beyond
  *                   the limit in force).  The fp32 path takes up to 5120 beads by default and up to 16384 behind max_beads (below);
  *                   c3d_set_if_matrix / c3d_set_restraints refuse more.  A precision-64 context takes its targets from the integer tenths
- *                   of c3d_set_if_matrix or from c3d_set_restraints' list (pairs closer than min_sep carry no restraint, as in the matrix).
+ *                   of c3d_set_if_matrix or from c3d_set_restraints' list.
  *                   64 and a schedule with a stage of kind 8 exclude each other unless f64_lbfgs is 1 (below): whichever call comes second
  *                   returns C3D_ERR_INVALID
  *   max_beads       5120 (default) .. 16384 (C3D_MAX_BEADS_DEFAULT .. C3D_MAX_BEADS_LIMIT): the largest matrix c3d_set_if_matrix and
