@@ -1,6 +1,6 @@
 // c3d_analysis.cpp — host unit of libc3d.so: the output side.  What a run's models are worth and how they relate, from the coordinates
 // resident on the device (kernels: c3d_score.hip): c3d_score_replicas, c3d_compare_replicas, c3d_superpose_replicas, c3d_rmsd_table,
-// c3d_ensemble_map, c3d_ensemble_score, c3d_geometry_replicas, c3d_separation_profile, c3d_stratified_score, c3d_bead_scores, c3d_accessibility (with the host-only c3d_sphere_points), c3d_compartments (with the host-only c3d_compartment_start), c3d_insulation and the test hooks c3d_debug_if_ranks / c3d_debug_distance_ranks.  What they share comes first: typed
+// c3d_ensemble_map, c3d_ensemble_score, c3d_geometry_replicas, c3d_separation_profile, c3d_stratified_score, c3d_bead_scores, c3d_accessibility (with the host-only c3d_sphere_points), c3d_compartments (with the host-only c3d_compartment_start), c3d_insulation, the input side's c3d_balance_matrix and the test hooks c3d_debug_if_ranks / c3d_debug_distance_ranks.  What they share comes first: typed
 // scratch slots (Slot, Block, Carve, CallScratch), the ranker (rank_matrix) and the models of a call (model_set_check, model_set_coords, gather_models).
 #include <limits>
 
@@ -1226,5 +1226,137 @@ extern "C" int c3d_insulation(c3d_ctx* c, const double* IF, const double* extra_
         HIP_TRY(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
         *device_ms = ms;
     }
+    return C3D_OK;
+}
+
+// ---- balancing a raw contact matrix (c3d_score.hip k_bal_*) ----
+// c3d_balance_matrix's one allocation: the call's copy of the matrix, n rows of pitch np = n rounded up to even (8 n np bytes; `balanced` is
+// formed in place over it), then O(n): the weights (np), the marginals, the mask codes and counts, the history (max_iters + 1), the round
+// record and the check's flags.  455 beads, 200 rounds: 1.67 MB; 16384 beads: 2 GiB + 0.4 MB.
+struct BalanceScratch : Carve {
+    Slot<double> M, w, s, history, rec;
+    Slot<int> code, cnt, flags;
+    BalanceScratch(int n, int np, int max_iters) {
+        M = take<double>((size_t)n * np);
+        w = take<double>((size_t)np);
+        s = take<double>((size_t)n);
+        code = take<int>((size_t)n);
+        cnt = take<int>((size_t)n);
+        history = take<double>((size_t)max_iters + 1);
+        rec = take<double>(c3d::kBalRecord);
+        flags = take<int>(1);
+    }
+};
+
+extern "C" int c3d_balance_matrix(c3d_ctx* c, const double* M, int n, int method, int flags, int ignore_diags, int min_nnz, const int32_t* mask_in, const double* w0,
+                                  double tol, int max_iters, double target, double* weights, int32_t* masked, double* balanced, double* history, double* report,
+                                  double* device_ms) {
+    const char* const who = "c3d_balance_matrix";
+    if (!c) return fail(C3D_ERR_INVALID, "c3d_balance_matrix: null context");
+    if (!M) return fail(C3D_ERR_INVALID, "c3d_balance_matrix: no matrix");
+    if (n < 2) return fail(C3D_ERR_INVALID, "c3d_balance_matrix: fewer than 2 bins (n < 2)");
+    if (n > c->max_beads)
+        return fail(C3D_ERR_INVALID, "c3d_balance_matrix: " + std::to_string(n) + " bins: more than max_beads = " + std::to_string(c->max_beads) +
+                                         " (c3d_set_option(\"max_beads\", n) goes up to " + std::to_string(C3D_MAX_BEADS_LIMIT) + ")");
+    if (method != C3D_BALANCE_ICE && method != C3D_BALANCE_VC && method != C3D_BALANCE_SQRT_VC) return fail(C3D_ERR_INVALID, "c3d_balance_matrix: unknown method");
+    if (flags & ~C3D_BALANCE_CHECK_EVERY_ROUND) return fail(C3D_ERR_INVALID, "c3d_balance_matrix: unknown flag bits");
+    if (ignore_diags < 0) return fail(C3D_ERR_INVALID, "c3d_balance_matrix: ignore_diags < 0");
+    if (!(target > 0.0) || !std::isfinite(target)) return fail(C3D_ERR_INVALID, "c3d_balance_matrix: target is not finite or <= 0");
+    if (method == C3D_BALANCE_ICE) {
+        if (!(tol >= 0.0)) return fail(C3D_ERR_INVALID, "c3d_balance_matrix: tol < 0 (or not a number)");
+        if (max_iters < 0 || max_iters > C3D_BALANCE_MAX_ITERS) return fail(C3D_ERR_INVALID, "c3d_balance_matrix: max_iters outside 0..C3D_BALANCE_MAX_ITERS");
+    } else {
+        if (w0) return fail(C3D_ERR_INVALID, "c3d_balance_matrix: VC and sqrt-VC take no start weights (w0 != NULL)");
+        max_iters = 1;              // VC and sqrt-VC are the loop with one update and no tolerance
+        tol = 0.0;
+    }
+    const bool half_power = method == C3D_BALANCE_SQRT_VC;
+    const int np = c3d::balance_pitch(n);
+    C3D_ENTRY(c, unit_bit(UNIT_SCORE));
+    const BalanceScratch L(n, np, max_iters);
+    CallScratch tmp;
+    if (int rc = tmp.alloc(L.total, who)) return rc;
+    PassEvents ev;
+    for (int k = 0; k < 2; ++k) HIP_TRY(hipEventCreate(&ev.e[k]));
+    c3d::BalJob job{};
+    job.n = n; job.np = np; job.ignore_diags = ignore_diags;
+    job.M = L.M.at(tmp.p); job.w = L.w.at(tmp.p); job.s = L.s.at(tmp.p); job.code = L.code.at(tmp.p); job.cnt = L.cnt.at(tmp.p);
+    job.rec = L.rec.at(tmp.p); job.history = L.history.at(tmp.p);
+    const size_t row_bytes = sizeof(double) * (size_t)n;
+    // the matrix as the caller holds it (pitch n) for the check that c3d_compartments makes of IF, then in the call's pitch
+    HIP_TRY(hipMemsetAsync(L.flags.at(tmp.p), 0, L.flags.bytes(), c->stream));
+    HIP_TRY(hipMemcpyAsync(job.M, M, row_bytes * n, hipMemcpyHostToDevice, c->stream));
+    LAUNCH_TRY("balance launch", c3d::launch_compartment_if_check(job.M, n, L.flags.at(tmp.p), c->stream));
+    if (int rc = read_back(c, L.flags.at(tmp.p), L.flags.bytes())) return rc;
+    const int bad = static_cast<const int*>(c->h_stage)[0];
+    if (bad & 2) return fail(C3D_ERR_INVALID, "c3d_balance_matrix: an entry of the matrix is not finite");
+    if (bad & 4) return fail(C3D_ERR_INVALID, "c3d_balance_matrix: an entry of the matrix is negative");
+    if (bad & 1) return fail(C3D_ERR_INVALID, "c3d_balance_matrix: the matrix is not symmetric");
+    if (np != n) {
+        HIP_TRY(hipMemsetAsync(job.M, 0, L.M.bytes(), c->stream));
+        HIP_TRY(hipMemcpy2DAsync(job.M, sizeof(double) * (size_t)np, M, row_bytes, row_bytes, (size_t)n, hipMemcpyHostToDevice, c->stream));
+    }
+    HIP_TRY(hipEventRecord(ev.e[0], c->stream));
+    // the mask: nnz over all columns, then the closure over the kept ones until it removes nothing
+    std::vector<int32_t> code(n, 0);
+    HIP_TRY(hipMemsetAsync(job.code, 0, L.code.bytes(), c->stream));
+    LAUNCH_TRY("balance launch", c3d::launch_balance_count(job, c->stream));
+    if (int rc = read_back(c, job.cnt, L.cnt.bytes())) return rc;
+    const int need = std::max(min_nnz, 1);
+    for (int i = 0; i < n; ++i) code[i] = mask_in && mask_in[i] != 0 ? 1 : static_cast<const int*>(c->h_stage)[i] < need ? 2 : 0;
+    for (bool removed = true; removed;) {
+        HIP_TRY(hipMemcpyAsync(job.code, code.data(), L.code.bytes(), hipMemcpyHostToDevice, c->stream));
+        LAUNCH_TRY("balance launch", c3d::launch_balance_count(job, c->stream));
+        if (int rc = read_back(c, job.cnt, L.cnt.bytes())) return rc;      // (synchronised: `code` may change now)
+        removed = false;
+        for (int i = 0; i < n; ++i)
+            if (code[i] == 0 && static_cast<const int*>(c->h_stage)[i] == 0) { code[i] = 3; removed = true; }
+    }
+    int by[4] = {0, 0, 0, 0};
+    for (int i = 0; i < n; ++i) ++by[code[i]];
+    const int kept = by[0];
+    if (kept < 2) return fail(C3D_ERR_INVALID, "c3d_balance_matrix: the mask leaves fewer than 2 bins (|U| < 2)");
+    std::vector<double> w(np, 0.0);
+    for (int i = 0; i < n; ++i) {
+        if (code[i] != 0) continue;
+        if (w0 && !(w0[i] > 0.0 && std::isfinite(w0[i]))) return fail(C3D_ERR_INVALID, "c3d_balance_matrix: a start weight of a kept bin is not finite or <= 0");
+        w[i] = w0 ? w0[i] : 1.0;
+    }
+    HIP_TRY(hipMemcpyAsync(job.w, w.data(), L.w.bytes(), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(job.rec, 0, L.rec.bytes(), c->stream));
+    // the rounds, kBalBatch of them (one with C3D_BALANCE_CHECK_EVERY_ROUND) between two looks at the record; rounds enqueued beyond the
+    // stopping one return at once
+    const int batch = (flags & C3D_BALANCE_CHECK_EVERY_ROUND) ? 1 : c3d::kBalBatch;
+    double rec[c3d::kBalRecord] = {0, 0, 0, 0};
+    for (int t = 0; t <= max_iters && rec[3] == 0.0;) {
+        for (int k = 0; k < batch && t <= max_iters; ++k, ++t)
+            LAUNCH_TRY("balance launch", c3d::launch_balance_round(job, kept, t, max_iters, tol, half_power, c->stream));
+        if (int rc = read_back(c, job.rec, L.rec.bytes())) return rc;
+        memcpy(rec, c->h_stage, sizeof rec);
+    }
+    if ((int)rec[3] == c3d::kBalDiverged) return fail(C3D_ERR_DIVERGED, "c3d_balance_matrix: a weight stopped being finite and positive in round " + std::to_string((int)rec[2]));
+    if (rec[3] == 0.0) return fail(C3D_ERR_HIP, "c3d_balance_matrix: the rounds ended without a stop word");
+    const int T = (int)rec[2];
+    LAUNCH_TRY("balance launch", c3d::launch_balance_apply(job, target, balanced != nullptr, c->stream));
+    HIP_TRY(hipEventRecord(ev.e[1], c->stream));
+    // read-backs: into the call's own buffers first, so that a failure leaves the caller's untouched
+    std::vector<double> hw(weights ? n : 0), hh(history ? (size_t)T + 1 : 0);
+    if (weights) HIP_TRY(hipMemcpyAsync(hw.data(), job.w, row_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (history) HIP_TRY(hipMemcpyAsync(hh.data(), job.history, sizeof(double) * hh.size(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    float ms = 0;
+    if (device_ms) HIP_TRY(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+    if (balanced) {                  // the one output too large for a second copy: written last, when nothing can fail but this copy
+        HIP_TRY(hipMemcpy2DAsync(balanced, row_bytes, job.M, sizeof(double) * (size_t)np, row_bytes, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    if (weights) memcpy(weights, hw.data(), row_bytes);
+    if (history) memcpy(history, hh.data(), sizeof(double) * hh.size());
+    if (masked) memcpy(masked, code.data(), sizeof(int32_t) * (size_t)n);
+    if (report) {
+        const double r[C3D_BALANCE_REPORT] = {(double)T, (int)rec[3] == c3d::kBalConverged ? 1.0 : 0.0, rec[0], (double)kept, (double)by[1], (double)by[2], (double)by[3], rec[1]};
+        memcpy(report, r, sizeof r);
+    }
+    if (device_ms) *device_ms = ms;
     return C3D_OK;
 }

@@ -569,6 +569,31 @@ hipError_t launch_insulation_squares(const InsJob& job, bool stage, double* mean
 hipError_t launch_insulation_profile(const InsJob& job, const double* mean, double* score, int* boundary, double* strength, hipStream_t s);
 hipError_t launch_insulation_fit(const InsJob& job, const double* score, const int* boundary, const double* strength, double min_strength, int tol,
                                  double* fit_r, int* fit_counts, hipStream_t s);
+// Balancing a raw contact matrix (c3d_balance_matrix; k_bal_*, c3d_score_balance.inc).  M is the call's copy of the matrix, n rows of pitch
+// np = balance_pitch(n) doubles with the pad column 0; w has np entries, s, code and cnt n each; code[i] is 0 for a kept bin, else the
+// mask's reason (C3D_BALANCE's `masked`).  rec is the round record, kBalRecord doubles { var_t, mbar, t, stop word }, zeroed by the host
+// before the first round; history has max_iters + 1 doubles.
+// launch_balance_count: cnt[i] = #{ j : |i-j| >= ignore_diags, M(i,j) > 0, code[j] == 0 }.  launch_balance_round: round t — the marginals
+// s from w, then the update, which writes rec and history[t] and, unless the round stops, the new w (`kept` = |U|; half_power: sqrt-VC).
+// Both kernels return at once when the stop word is set, so rounds may be enqueued beyond the stopping one.  launch_balance_apply: the
+// final scale of w by sqrt(target / mbar) and, with `matrix`, M(i,j) <- (w_i w_j) M(i,j) in place.
+constexpr int kBalRecord = 4;
+constexpr int kBalConverged = 1, kBalExhausted = 2, kBalDiverged = 3;      // the stop word
+constexpr int kBalBatch = 16;         // rounds the host enqueues between two looks at the record
+inline int balance_pitch(int n) { return (n + 1) & ~1; }
+struct BalJob {
+    int n, np, ignore_diags;
+    double* M;
+    double* w;
+    double* s;
+    int* code;
+    int* cnt;
+    double* rec;
+    double* history;
+};
+hipError_t launch_balance_count(const BalJob& job, hipStream_t s);
+hipError_t launch_balance_round(const BalJob& job, int kept, int t, int max_iters, double tol, bool half_power, hipStream_t s);
+hipError_t launch_balance_apply(const BalJob& job, double target, bool matrix, hipStream_t s);
 
 // Target matrix entry: NOE target in Angstrom, 0 = no restraint (host c3d_set_restraints and K1).
 inline float encode_target_host(float t) { return t > 0 ? t : 0.0f; }

@@ -33,6 +33,8 @@
 //                             correlation of its rows through matrix-vector products with the map (c3d_compartments)
 //   c3d_score_insulation.inc  k_ins_*    insulation profiles and domain boundaries: a banded all-pairs sum a bead, the tile's distances staged
 //                             in LDS, every window out of one walk over nested squares (c3d_insulation)
+//   c3d_score_balance.inc     k_bal_*    the input side: a raw contact matrix balanced by ICE, VC or sqrt-VC, one streaming matrix-vector pass
+//                             a round, the stop decided on the device (c3d_balance_matrix)
 #include "c3d_score_core.h"
 
 namespace c3d {
@@ -271,6 +273,7 @@ hipError_t launch_if_rank_sort(double* M, int n, int range, unsigned long long* 
 #include "c3d_score_access.inc"
 #include "c3d_score_compartment.inc"
 #include "c3d_score_insulation.inc"
+#include "c3d_score_balance.inc"
 
 // loads the unit's code object on the current device and gives the k_str_* and k_bead_* kernels their dynamic-LDS allowance (c3d_gate.cpp "code objects":
 // once per device, never beside a launch)

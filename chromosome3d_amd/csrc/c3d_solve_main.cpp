@@ -21,6 +21,8 @@
 //       map) of IF, of the models' consensus distance map and of every model, and how well each agrees with IF's
 //   --insulation <prefix> writes <prefix>_insulation.txt — the insulation profile and the domain boundaries of IF and of the models' consensus
 //       map per window, how many models place a boundary at each bead, and how well every model's profile fits IF's
+//   --balance <ice|vc|sqrt-vc> balances the matrix of --if on the device first (raw contact counts in, a normalised matrix out): the solve and
+//       every analysis option of the run use the balanced matrix; --balance-out <prefix> writes the weights and the matrix
 //
 // Success convention of the reference: <ID>_<M>.pdb exists, iam.running removed; on failure
 // iam.running is renamed iam.failed and the exit code is non-zero (:266-283).
@@ -110,6 +112,15 @@ static void usage() {
             "                 [--insulation-windows <a,b,c>   half-widths of the squares in beads, ascending, 1..128; default 5,10,25, those that fit (2w + 1 <= n)]\n"
             "                 [--insulation-contact <cutoff>   models and consensus: count contacts (distance < cutoff, in A) in the square instead of averaging the distance]\n"
             "                 [--insulation-tol <beads>   how far apart two boundaries may lie and still match; default 1]\n"
+            "                 [--balance <ice|vc|sqrt-vc>   the matrix of --if holds raw contact counts: balance it on the device first (iterative correction, vanilla\n"
+            "                                          coverage or its square root); the solve and every analysis option of the run use the balanced matrix.  Bins that\n"
+            "                                          cannot be balanced get weight 0 and no restraints]\n"
+            "                 [--balance-ignore-diags <k>   the diagonals |i-j| < k do not count in the marginals; default 2]\n"
+            "                 [--balance-min-nnz <m>   bins with fewer non-zero entries are masked; default 10]\n"
+            "                 [--balance-tol <v>   ice stops when the variance of the relative marginals is below v; default 1e-5]\n"
+            "                 [--balance-iters <k>   at most k updates of ice, 0..10000; default 200]\n"
+            "                 [--balance-out <prefix>   writes <prefix>_weights.txt (header `bead weight masked`; masked: 0 kept, 1 listed, 2 too few non-zeros,\n"
+            "                                          3 no kept partner) and <prefix>_matrix.txt, the balanced matrix in the format --if reads, with 17 digits]\n"
             "                 [--accepted   also write <ID>a_<k>.pdb beside every <ID>_<k>.pdb, as CNS does for structures it accepts]\n");
 }
 
@@ -145,6 +156,9 @@ int main(int argc, char** argv) {
     bool insulation_windows_given = false;
     double insulation_contact = 0;                   // 0: mean distance
     int insulation_tol = 1;
+    std::string balance_method, balance_out;          // empty: the matrix of --if is taken as it is
+    int balance_ignore_diags = 2, balance_min_nnz = 10, balance_iters = 200;
+    double balance_tol = 1e-5;
     double bead_radius = -1, probe_radius = -1;      // < 0: half of b0
     int sphere_points = 96;
     int superpose = 0, ensemble_top = 0, stratified_max_sep = 0;
@@ -204,6 +218,12 @@ int main(int argc, char** argv) {
         else if (s == "--insulation-windows") { insulation_windows = next("--insulation-windows"); insulation_windows_given = true; }
         else if (s == "--insulation-contact") insulation_contact = atof(next("--insulation-contact"));
         else if (s == "--insulation-tol") insulation_tol = atoi(next("--insulation-tol"));
+        else if (s == "--balance") balance_method = next("--balance");   // balance the raw matrix first (c3d_balance_matrix)
+        else if (s == "--balance-ignore-diags") balance_ignore_diags = atoi(next("--balance-ignore-diags"));
+        else if (s == "--balance-min-nnz") balance_min_nnz = atoi(next("--balance-min-nnz"));
+        else if (s == "--balance-tol") balance_tol = atof(next("--balance-tol"));
+        else if (s == "--balance-iters") balance_iters = atoi(next("--balance-iters"));
+        else if (s == "--balance-out") balance_out = next("--balance-out");
         else if (s == "--bead-radius") bead_radius = atof(next("--bead-radius"));
         else if (s == "--probe-radius") probe_radius = atof(next("--probe-radius"));
         else if (s == "--sphere-points") sphere_points = atoi(next("--sphere-points"));
@@ -217,6 +237,12 @@ int main(int argc, char** argv) {
     if (!per_bead_prefix.empty() && if_path.empty()) { fprintf(stderr, "c3d_solve: --per-bead needs --if: a run started from --tbl has no IF matrix\n"); return 2; }
     if (!compartments_prefix.empty() && if_path.empty()) { fprintf(stderr, "c3d_solve: --compartments needs --if: a run started from --tbl has no IF matrix\n"); return 2; }
     if (!insulation_prefix.empty() && if_path.empty()) { fprintf(stderr, "c3d_solve: --insulation needs --if: a run started from --tbl has no IF matrix\n"); return 2; }
+    if ((!balance_method.empty() || !balance_out.empty()) && if_path.empty()) { fprintf(stderr, "c3d_solve: --balance needs --if: a run started from --tbl has no matrix to balance\n"); return 2; }
+    if (!balance_out.empty() && balance_method.empty()) { fprintf(stderr, "c3d_solve: --balance-out needs --balance <ice|vc|sqrt-vc>\n"); return 2; }
+    if (!balance_method.empty() && balance_method != "ice" && balance_method != "vc" && balance_method != "sqrt-vc") {
+        fprintf(stderr, "c3d_solve: --balance takes ice, vc or sqrt-vc\n");
+        return 2;
+    }
     if (id.empty()) {
         std::string base = if_path.empty() ? std::string("model") : if_path.substr(if_path.find_last_of('/') + 1);
         if (base.size() > 4 && base.substr(base.size() - 4) == ".txt") base.resize(base.size() - 4);
@@ -252,6 +278,31 @@ int main(int argc, char** argv) {
         CHECK(c3d_parse_if_file(if_path.c_str(), &IF, &n));
         // a matrix beyond the default limit is what the user asked for: raise the limit to it (the library refuses beyond its ceiling)
         if (n > C3D_MAX_BEADS_DEFAULT && n <= C3D_MAX_BEADS_LIMIT) CHECK(c3d_set_option(ctx, "max_beads", n));
+        if (!balance_method.empty()) {
+            // raw counts in, the balanced matrix over IF: everything below reads IF
+            const int method = balance_method == "ice" ? C3D_BALANCE_ICE : balance_method == "vc" ? C3D_BALANCE_VC : C3D_BALANCE_SQRT_VC;
+            std::vector<double> weights(n), balanced((size_t)n * n), report(C3D_BALANCE_REPORT);
+            std::vector<int32_t> masked(n);
+            CHECK(c3d_balance_matrix(ctx, IF, n, method, 0, balance_ignore_diags, balance_min_nnz, nullptr, nullptr, balance_tol, balance_iters, 1.0, weights.data(),
+                                     masked.data(), balanced.data(), nullptr, report.data(), nullptr));
+            memcpy(IF, balanced.data(), sizeof(double) * balanced.size());
+            if (!quiet)
+                printf("Balanced   : %s, %d rounds, %s, variance %.3g, %d of %d bins kept\n", balance_method.c_str(), (int)report[0],
+                       report[1] != 0 ? "converged" : "not converged", report[2], (int)report[3], n);
+            if (!balance_out.empty()) {
+                const std::string wpath = balance_out + "_weights.txt", mpath = balance_out + "_matrix.txt";
+                FILE* f = fopen(wpath.c_str(), "w");
+                if (!f) { fprintf(stderr, "c3d_solve: cannot write %s\n", wpath.c_str()); return fail_exit(out_dir); }
+                fprintf(f, "bead weight masked\n");
+                for (int i = 0; i < n; ++i) fprintf(f, "%d %.17g %d\n", i + 1, weights[i], masked[i]);
+                fclose(f);
+                f = fopen(mpath.c_str(), "w");
+                if (!f) { fprintf(stderr, "c3d_solve: cannot write %s\n", mpath.c_str()); return fail_exit(out_dir); }
+                for (int i = 0; i < n; ++i)
+                    for (int j = 0; j < n; ++j) fprintf(f, j + 1 < n ? "%.17g " : "%.17g\n", IF[(size_t)i * n + j]);
+                fclose(f);
+            }
+        }
         CHECK(c3d_set_if_matrix(ctx, IF, n, alpha, K));
         std::vector<int32_t> d10((size_t)n * n);
         CHECK(c3d_get_dist10(ctx, d10.data()));

@@ -285,6 +285,23 @@ def insulation_report(solver, IF, extra=None, pick=None, windows=(5, 10, 25), co
     return out
 
 
+def balance_if(path_or_matrix, solver=None, device=0, **kw):
+    """A raw contact matrix (a path in the text format of parse_if_file, or an array) balanced on the device and ready for set_if_matrix:
+    Solver.balance's "balanced", rows of bins that cannot be balanced all 0 (set_if_matrix reads 0 as no restraint).  kw: the arguments of
+    Solver.balance (method, ignore_diags, min_nnz, mask, w0, tol, max_iters, target).  Without a solver a context is opened on `device`
+    for the call, with max_beads raised to the matrix where it is beyond the default."""
+    M = parse_if_file(path_or_matrix) if isinstance(path_or_matrix, (str, bytes, os.PathLike)) else np.asarray(path_or_matrix, dtype=np.float64)
+    own = solver is None
+    s = Solver(device) if own else solver
+    try:
+        if own and M.shape[0] > 5120:
+            s.set_option("max_beads", M.shape[0])
+        return s.balance(M, want_matrix=True, **kw)["balanced"]
+    finally:
+        if own:
+            s.close()
+
+
 def build_models(solver, model_count=MODELCOUNT, seed=MD_SEED, first_replica=0, model=None, stages=None, fire=None,
                  gtol=1e-2, check_every=250, final_kind=5):
     """The replacement of `cns_solve < dgsa.inp` (:254-289): runs the whole annealing schedule

@@ -586,6 +586,37 @@ class Solver:
         out["device_ms"] = ms.value
         return out
 
+    def balance(self, M, method="ice", ignore_diags=2, min_nnz=10, mask=None, w0=None, tol=1e-5, max_iters=200, target=1.0, want_matrix=True,
+                check_every_round=False):
+        """A raw contact matrix balanced on the device (c3d_balance_matrix): M [n, n], symmetric, finite, >= 0, n up to the context's
+        max_beads; it needs no targets and no replicas and changes nothing of the solve.  method: "ice" (iterative correction until the
+        variance of the relative marginals is below tol, at most max_iters updates), "vc" or "sqrt-vc" (one update; no w0).
+        ignore_diags: the diagonals |i-j| < ignore_diags do not count in the marginals.  Bins listed in mask (non-zero entries), bins with
+        fewer than max(min_nnz, 1) non-zeros and bins left without a kept partner get weight 0.  w0: start weights [n].  A dict:
+        "weights" [n], "masked" [n] int32 (0 kept, 1 mask, 2 too few non-zeros, 3 closure), "balanced" [n, n] = (w w^T) M over all
+        diagonals (None with want_matrix=False), ready for set_if_matrix, "history" (the variance of every pass, T + 1 of them), "rounds"
+        (T), "converged", "var", "kept" (|U|), "masked_counts" (by reason 1, 2, 3), "mean_marginal" (before the scale to target),
+        "device_ms".  check_every_round=True makes the host look at the device's round record after every round (the same bytes)."""
+        m = np.ascontiguousarray(M, dtype=np.float64)
+        assert m.ndim == 2 and m.shape[0] == m.shape[1]
+        n = m.shape[0]
+        code = {"ice": _l.BALANCE_ICE, "vc": _l.BALANCE_VC, "sqrt-vc": _l.BALANCE_SQRT_VC}.get(method, method)
+        mk = np.ascontiguousarray(mask, dtype=np.int32).reshape(-1) if mask is not None else None
+        start = np.ascontiguousarray(w0, dtype=np.float64).reshape(-1) if w0 is not None else None
+        assert (mk is None or len(mk) == n) and (start is None or len(start) == n)
+        iters = int(max_iters)
+        slots = iters + 1 if code == _l.BALANCE_ICE and 0 <= iters <= _l.BALANCE_MAX_ITERS else 2
+        out = {"weights": np.empty(n), "masked": np.empty(n, dtype=np.int32), "balanced": np.empty((n, n)) if want_matrix else None}
+        hist, rep, ms = np.full(slots, np.nan), np.empty(_l.BALANCE_REPORT), C.c_double()
+        _l.check(self._L.c3d_balance_matrix(self._h, _l.dptr(m), n, int(code), _l.BALANCE_CHECK_EVERY_ROUND if check_every_round else 0, int(ignore_diags),
+                                            int(min_nnz), _l.i32ptr(mk) if mk is not None else None, _l.dptr(start) if start is not None else None, float(tol),
+                                            iters, float(target), _l.dptr(out["weights"]), _l.i32ptr(out["masked"]),
+                                            _l.dptr(out["balanced"]) if want_matrix else None, _l.dptr(hist), _l.dptr(rep), C.byref(ms)))
+        T = int(rep[0])
+        out.update(history=hist[:T + 1].copy(), rounds=T, converged=bool(rep[1]), var=float(rep[2]), kept=int(rep[3]),
+                   masked_counts=[int(rep[4]), int(rep[5]), int(rep[6])], mean_marginal=float(rep[7]), device_ms=ms.value)
+        return out
+
     def rank(self):
         r = np.empty(self.nrep, dtype=np.int32)
         _l.check(self._L.c3d_rank(self._h, _l.i32ptr(r)))

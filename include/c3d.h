@@ -858,6 +858,71 @@ int c3d_insulation(c3d_ctx* ctx, const double* IF, const double* extra_xyz, int 
                    int flags, const int32_t* windows, int n_win, double cutoff, double min_strength, int tol,
                    double* mean, double* score, int32_t* boundary, double* strength,
                    double* fit_r, int32_t* fit_counts, double* device_ms);
+/* Balancing a raw contact matrix on the device (c3d_score_balance.inc k_bal_*): the input side.  c3d_set_if_matrix expects a normalised
+ * matrix; this entry turns raw contact counts into one by iterative correction (ICE), vanilla coverage (VC) or its square root (sqrt-VC).
+ * It needs a context, but no targets and no replicas, and changes no state of the solve.  Bins that cannot be balanced get weight 0, so
+ * their rows of the balanced matrix are 0: c3d_set_if_matrix reads IF == 0 as "no restraint" and the analyses read an all-zero row as an
+ * unmappable bin, so masked bins need no special case anywhere.
+ *
+ * Input.  M is n x n row-major doubles, 2 <= n <= the context's max_beads in force (5120, or up to 16384 after
+ *   c3d_set_option("max_beads", n), which is the consent to the memory).  Every value is finite and >= 0 and M(i,j) == M(j,i) exactly;
+ *   anything else is C3D_ERR_INVALID, found on the device before any round (the check c3d_compartments makes of IF).
+ * Definitions.
+ *   1. The matrix the marginals see: A'(i,j) = M(i,j) if |i-j| >= ignore_diags, else 0.  ignore_diags >= 0; 0 keeps everything, 2 is
+ *      the customary value.
+ *   2. The mask.  nnz_i = #{ j : A'(i,j) > 0 } over all j, exact integers.
+ *      U0 = { i : (mask_in == NULL or mask_in[i] == 0) and nnz_i >= max(min_nnz, 1) }.  Closure: repeat
+ *      O = { i in U : A'(i,j) == 0 for every j in U }, U <- U \ O, until O is empty (a count of positive entries, so exact; usually one
+ *      pass).  masked[i] is 0 for a kept bin, 1 for one listed in mask_in, 2 for too few non-zeros, 3 for one removed by the closure.
+ *      |U| < 2 is C3D_ERR_INVALID.
+ *   3. The start.  w_i = w0[i] on U if w0 is given (every such value finite and > 0, else C3D_ERR_INVALID; values at masked bins are not
+ *      read), else w_i = 1 on U; w_i = 0 off U, always.
+ *   4. Rounds t = 0, 1, ... with the exponent p = 1 for ICE and VC, p = 1/2 for sqrt-VC:
+ *        s_i = w_i * sum_j A'(i,j) w_j for i in U;  mbar = (sum_{i in U} s_i) / |U|;  r_i = s_i / mbar;
+ *        var_t = sum_{i in U} (r_i - 1)^2 / |U|, and history[t] = var_t;
+ *        if var_t < tol: stop converged with T = t; else if t == max_iters: stop unconverged with T = max_iters;
+ *        else w_i <- w_i / r_i^p (for p = 1/2: w_i / sqrt(r_i)).
+ *      So there are at most max_iters updates and max_iters + 1 marginal passes; max_iters = 0 only evaluates w0.  VC and sqrt-VC are
+ *      this loop with max_iters forced to 1 and tol forced to 0, and they refuse w0 != NULL.  For ICE 0 <= max_iters <=
+ *      C3D_BALANCE_MAX_ITERS and tol >= 0.  A weight that stops being finite and positive is C3D_ERR_DIVERGED.
+ *   5. The scale, with the mbar of the last pass: w_i <- w_i * sqrt(target / mbar), target > 0 and finite.  The mean row sum of the
+ *      balanced A' over U is then target.  K1 is scale-invariant, so structures do not depend on target.
+ *   6. Outputs, any may be NULL.  weights[n]: the final weights.  masked[n]: as in 2.  balanced (n x n) = fl(fl(w_i * w_j) * M(i,j))
+ *      over ALL diagonals, the ignored ones included: the weights are multiplied first, so the result is symmetric bit for bit (device
+ *      ranking and c3d_compartments refuse an asymmetric IF) and equals numpy's (w[:,None] * w[None,:]) * M bit for bit; two
+ *      multiplications, never a fused form.  history: max_iters + 1 doubles, entries beyond T are not written.  report[C3D_BALANCE_REPORT]
+ *      = { T, converged (1 / 0), var_T, |U|, #masked by 1, #masked by 2, #masked by 3, mbar of the last pass before scaling }.
+ *      device_ms: the HIP-event time of the device part — from the first count of non-zeros, after the matrix is uploaded and checked,
+ *      to the kernel that forms `balanced`; the read-backs are not in it.  There is no stat key for the call.
+ * Determinism.  Every sum is a fixed tree (the scoring unit's block_reduce), no atomics.  A row's s_i is the sum of the products of the
+ *   column pairs 2t + 512k a thread t takes, low column first, closed by one block_reduce of a workgroup that owns 4 consecutive rows,
+ *   times w_i: it depends on n, ignore_diags, the row's values and w only — not on the grid, the method, the other outputs asked for or
+ *   how often the host looks.  mbar and var_t are two passes over s in that order, the mean first, then the centred sum, thread t the
+ *   bins t + 256k.  Two calls return the same bytes.
+ * Stopping without a host round-trip per round.  The update kernel writes the round record (var_t, mbar, t and a stop word) on the
+ *   device, and every later kernel of the call reads the stop word and returns at once.  The host enqueues rounds in batches of 16 and
+ *   reads the record between them; with C3D_BALANCE_CHECK_EVERY_ROUND in flags it reads it after every round.  Both ways return the same
+ *   bytes and the same T as the definition.
+ * C3D_ERR_INVALID with the function's name and with nothing written: no context, no matrix, n < 2 or above max_beads, an unknown method
+ * or flag bit, ignore_diags < 0, target not finite or <= 0, tol < 0 or max_iters out of range (ICE), w0 with VC or sqrt-VC — all before
+ * any launch; a bad matrix, |U| < 2 (ignore_diags >= n ends there) and a bad w0 on U after the pass that finds them.  C3D_ERR_DIVERGED and
+ * C3D_ERR_NOMEM (no device memory for the scratch) write nothing either.
+ * Measured on an MI355X (profiles/r32_balance.md, tools/balance.py): a round — one streaming pass over the matrix and the update — takes
+ * 10 us at 455 beads, 19 us at 2048, 69 us at 5792, 134 us at 8192 and 461 us at 16384, where the 2 GiB are read at 4.65 TB/s, 74 % of
+ * the 6.3 TB/s a streaming read achieves; one round of the numpy restatement on the same host: 20 ms at 16384.
+ * Scratch, one allocation per call, freed before it returns: 8 n np bytes for the call's copy of the matrix — np = n rounded up to even,
+ * so that every row starts 16-byte aligned, the pad column 0; `balanced` is formed in place over that copy after the last round and read
+ * back from there — plus 8 np + 16 n + 8 (max_iters + 1) bytes of weights, marginals, mask codes, counts and history: 1.67 MB at 455
+ * beads, 2 GiB + 0.4 MB at 16384 beads. */
+#define C3D_BALANCE_ICE      0
+#define C3D_BALANCE_VC       1
+#define C3D_BALANCE_SQRT_VC  2
+#define C3D_BALANCE_CHECK_EVERY_ROUND 1      /* flags: the host reads the round record after every round (test and measurement knob) */
+#define C3D_BALANCE_MAX_ITERS 10000
+#define C3D_BALANCE_REPORT 8
+int c3d_balance_matrix(c3d_ctx* ctx, const double* M, int n, int method, int flags, int ignore_diags, int min_nnz,
+                       const int32_t* mask_in, const double* w0, double tol, int max_iters, double target,
+                       double* weights, int32_t* masked, double* balanced, double* history, double* report, double* device_ms);
 /* rank[k] = replica index with the k-th lowest int(E_noe) (chromosome3D.pl:796-802,822-828);
  * ties broken by replica id. */
 int c3d_rank(c3d_ctx* ctx, int32_t* rank);

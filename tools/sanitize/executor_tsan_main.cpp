@@ -132,6 +132,18 @@ static void api_storm(int device_count) {
                                           nullptr, nullptr, nullptr) == C3D_OK;
                 ok = ok && c3d_insulation(c, nullptr, nullptr, 0, picked, 3, 0, ibad, 2, 0.0, 0.0, 0, imean.data(), nullptr, nullptr, nullptr, nullptr, nullptr,
                                           nullptr) == C3D_ERR_INVALID;
+                // (the raw matrix: IF itself, an odd and an even n over the threads; bin 1 masked by the caller)
+                std::vector<double> bw(n), bbal((size_t)n * n), bhist(51), brep(C3D_BALANCE_REPORT);
+                std::vector<int32_t> bmask(n, 0), bcode(n);
+                bmask[1] = 1;
+                double bal_ms = -1;
+                ok = ok && c3d_balance_matrix(c, IF.data(), n, C3D_BALANCE_ICE, round == 1 ? C3D_BALANCE_CHECK_EVERY_ROUND : 0, 2, 10, bmask.data(), nullptr, 1e-5, 50, 1.0,
+                                              bw.data(), bcode.data(), bbal.data(), bhist.data(), brep.data(), &bal_ms) == C3D_OK && bal_ms >= 0 && bcode[1] == 1 && bw[1] == 0.0 &&
+                           brep[3] == (double)(n - 1);
+                ok = ok && c3d_balance_matrix(c, IF.data(), n, C3D_BALANCE_SQRT_VC, 0, 0, 1, nullptr, nullptr, 0.0, 0, 2.0, bw.data(), nullptr, nullptr, nullptr, brep.data(),
+                                              nullptr) == C3D_OK && brep[0] == 1.0;
+                ok = ok && c3d_balance_matrix(c, IF.data(), n, C3D_BALANCE_VC, 0, 2, 10, nullptr, bw.data(), 0.0, 0, 1.0, bw.data(), nullptr, nullptr, nullptr, nullptr,
+                                              nullptr) == C3D_ERR_INVALID;
                 if (what == 2) { unsigned long long a, b, d; ok = ok && c3d_debug_tear16(c, 4, &a, &b, &d) == C3D_OK; }
             }
             if (!ok) { fprintf(stderr, "api storm thread %d: %s\n", t, c3d_last_error()); ++failures; }

@@ -89,6 +89,11 @@ hipError_t hipHostFree(void* p) { LaunchScope ls; free(p); return hipSuccess; }
 hipError_t hipHostGetDevicePointer(void** d, void* h, unsigned) { *d = h; return hipSuccess; }
 hipError_t hipMemcpyAsync(void* dst, const void* src, size_t n, hipMemcpyKind, hipStream_t) { LaunchScope ls; memcpy(dst, src, n); return hipSuccess; }
 hipError_t hipMemsetAsync(void* dst, int v, size_t n, hipStream_t) { LaunchScope ls; memset(dst, v, n); return hipSuccess; }
+hipError_t hipMemcpy2DAsync(void* dst, size_t dpitch, const void* src, size_t spitch, size_t width, size_t height, hipMemcpyKind, hipStream_t) {
+    LaunchScope ls;
+    for (size_t r = 0; r < height; ++r) memcpy(static_cast<char*>(dst) + r * dpitch, static_cast<const char*>(src) + r * spitch, width);
+    return hipSuccess;
+}
 hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { LaunchScope ls; *s = reinterpret_cast<hipStream_t>(calloc(1, 8)); return hipSuccess; }
 hipError_t hipStreamDestroy(hipStream_t s) { LaunchScope ls; free(s); return hipSuccess; }
 hipError_t hipStreamSynchronize(hipStream_t) { LaunchScope ls; return hipSuccess; }
@@ -794,6 +799,55 @@ hipError_t launch_insulation_fit(const InsJob& J, const double* score, const int
             }
             for (int f = 0; f < 4 && fit_counts; ++f) fit_counts[out * 4 + f] = c[f];
         }
+    return hipSuccess;
+}
+
+// c3d_balance_matrix: the three launchers restated on the host with plain loops in index order (the definitions of include/c3d.h; no
+// tiles, no column pairs, no block reduction: the sums' orders are not the device's)
+hipError_t launch_balance_count(const BalJob& J, hipStream_t) {
+    LaunchScope ls;
+    for (int i = 0; i < J.n; ++i) {
+        int cnt = 0;
+        for (int j = 0; j < J.n; ++j)
+            if (std::abs(i - j) >= J.ignore_diags && J.code[j] == 0 && J.M[(size_t)i * J.np + j] > 0.0) ++cnt;
+        J.cnt[i] = cnt;
+    }
+    return hipSuccess;
+}
+hipError_t launch_balance_round(const BalJob& J, int kept, int t, int max_iters, double tol, bool half_power, hipStream_t) {
+    LaunchScope ls;
+    if (J.rec[3] != 0.0) return hipSuccess;
+    const int n = J.n;
+    double sum = 0.0;
+    for (int i = 0; i < n; ++i) {
+        double row = 0.0;
+        for (int j = 0; j < n && J.code[i] == 0; ++j)
+            if (std::abs(i - j) >= J.ignore_diags) row += J.M[(size_t)i * J.np + j] * J.w[j];
+        J.s[i] = J.code[i] == 0 ? J.w[i] * row : 0.0;
+        sum += J.s[i];
+    }
+    const double mbar = sum / (double)kept;
+    double var = 0.0;
+    for (int i = 0; i < n; ++i)
+        if (J.code[i] == 0) var += (J.s[i] / mbar - 1.0) * (J.s[i] / mbar - 1.0);
+    var /= (double)kept;
+    int stop = var < tol ? kBalConverged : t == max_iters ? kBalExhausted : 0;
+    for (int i = 0; i < n && !stop; ++i) {
+        if (J.code[i] != 0) continue;
+        const double r = J.s[i] / mbar;
+        J.w[i] /= half_power ? std::sqrt(r) : r;
+        if (!(J.w[i] > 0.0 && std::isfinite(J.w[i]))) stop = kBalDiverged;
+    }
+    J.history[t] = var;
+    J.rec[0] = var; J.rec[1] = mbar; J.rec[2] = (double)t; J.rec[3] = (double)stop;
+    return hipSuccess;
+}
+hipError_t launch_balance_apply(const BalJob& J, double target, bool matrix, hipStream_t) {
+    LaunchScope ls;
+    const double f = std::sqrt(target / J.rec[1]);
+    for (int i = 0; i < J.n; ++i) J.w[i] *= f;
+    for (int i = 0; i < J.n && matrix; ++i)
+        for (int j = 0; j < J.n; ++j) J.M[(size_t)i * J.np + j] = (J.w[i] * J.w[j]) * J.M[(size_t)i * J.np + j];
     return hipSuccess;
 }
 
