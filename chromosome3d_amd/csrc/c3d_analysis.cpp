@@ -1,6 +1,6 @@
 // c3d_analysis.cpp — host unit of libc3d.so: the output side.  What a run's models are worth and how they relate, from the coordinates
 // resident on the device (kernels: c3d_score.hip): c3d_score_replicas, c3d_compare_replicas, c3d_superpose_replicas, c3d_rmsd_table,
-// c3d_ensemble_map, c3d_ensemble_score, c3d_geometry_replicas, c3d_separation_profile, c3d_stratified_score, c3d_bead_scores, c3d_accessibility (with the host-only c3d_sphere_points), c3d_compartments (with the host-only c3d_compartment_start), c3d_insulation, the input side's c3d_balance_matrix and the test hooks c3d_debug_if_ranks / c3d_debug_distance_ranks.  What they share comes first: typed
+// c3d_ensemble_map, c3d_ensemble_score, c3d_geometry_replicas, c3d_separation_profile, c3d_stratified_score, c3d_bead_scores, c3d_accessibility (with the host-only c3d_sphere_points), c3d_compartments (with the host-only c3d_compartment_start), c3d_insulation, c3d_loops, the input side's c3d_balance_matrix and the test hooks c3d_debug_if_ranks / c3d_debug_distance_ranks.  What they share comes first: typed
 // scratch slots (Slot, Block, Carve, CallScratch), the ranker (rank_matrix) and the models of a call (model_set_check, model_set_coords, gather_models).
 #include <limits>
 
@@ -1221,6 +1221,160 @@ extern "C" int c3d_insulation(c3d_ctx* c, const double* IF, const double* extra_
     if (Q > 1 && fit_counts) HIP_TRY(hipMemcpyAsync(fit_counts, L.fit_counts.at(tmp.p), L.fit_counts.bytes(), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipEventRecord(ev.e[1], c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    if (device_ms) {
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+        *device_ms = ms;
+    }
+    return C3D_OK;
+}
+
+// ---- loop enrichment (c3d_score.hip k_loop_*) ----
+// c3d_loops' one allocation: 24 n K of coordinates, the pick list, the mask (4 n), 8 n S per band (IF's, packed by the host; the
+// consensus', written on the device; S = B + 4w separations, fewer where n - 1 clips them), 8 Q S of expected values; with IF the scan's
+// 32 B n of ratios (only when `ratio` is asked for), 2 B n of pixel flags, 16 n of row counts and offsets and 8 max_peaks of peaks; the
+// list (8 L) with its 48 Q L of `at`, and 8 Q ((2w+1)^2 + 2) of pile-ups, P2LL and `closed`.
+// 455 beads x 20 models with IF and the consensus, w = 5, separations 11..200, ratio and 4096 peaks: 9.1 MB (1.5 MB of bands, 2.8 MB of
+// ratios, 4.3 MB for the list); 16384 x 20 with w = 20, B = 512 and a list of 4096 pixels, no IF: 12.3 MB (7.9 MB of coordinates, 4.2 MB
+// for the list and its pile-ups), 90.1 MB with the consensus band; IF alone there, dense: 77.6 MB of band, 268 MB of ratios, 16.8 MB of flags.
+struct LoopScratch : Carve {
+    Slot<double> xyz, band_if, band_cons, expected, ratio, at, apa, p2ll;
+    Slot<int32_t> pick, mask, rows, offset, peaks, report, list, closed;
+    Slot<unsigned char> cand, peak;
+    LoopScratch(int n, int K, int Kp, int Q, int S, int B, int w, bool has_if, bool consensus, bool want_ratio, bool want_peaks, int max_peaks, int Lmax) {
+        const size_t pixels = (size_t)B * n, side = 2 * (size_t)w + 1;
+        xyz = take<double>(Kp > 0 ? 3 * (size_t)n * K : 0);
+        pick = take<int32_t>((size_t)Kp);
+        mask = take<int32_t>((size_t)n);
+        band_if = take<double>(has_if ? (size_t)n * S : 0);
+        band_cons = take<double>(consensus ? (size_t)n * S : 0);
+        expected = take<double>((size_t)Q * S);
+        ratio = take<double>(want_ratio ? 4 * pixels : 0);
+        cand = take<unsigned char>(want_peaks ? pixels : 0);
+        peak = take<unsigned char>(want_peaks ? pixels : 0);
+        rows = take<int32_t>(want_peaks ? 3 * (size_t)n : 0);
+        offset = take<int32_t>(want_peaks ? (size_t)n : 0);
+        peaks = take<int32_t>(want_peaks ? 2 * (size_t)max_peaks : 0);
+        report = take<int32_t>(C3D_LOOP_REPORT);
+        list = take<int32_t>(2 * (size_t)Lmax);
+        at = take<double>(6 * (size_t)Q * Lmax);
+        closed = take<int32_t>(2 * (size_t)Q);
+        apa = take<double>((size_t)Q * side * side);
+        p2ll = take<double>((size_t)Q);
+    }
+};
+
+extern "C" int c3d_loops(c3d_ctx* c, const double* IF, const double* extra_xyz, int n_extra, const int32_t* pick, int n_pick, int flags, const int32_t* mask, int p, int w,
+                         int min_sep, int max_sep, const double* thr, double min_obs, int merge, int corner, const int32_t* list_in, int n_list, int max_peaks,
+                         double* expected, double* ratio, int32_t* peaks, int32_t* report, double* at, int32_t* closed, double* apa, double* p2ll, double* device_ms) {
+    const char* const who = "c3d_loops";
+    std::vector<int32_t> list;
+    if (int rc = ensemble_check(c, who, extra_xyz, n_extra, pick, n_pick, &list)) return rc;
+    if (flags & ~(C3D_LOOP_CONSENSUS | C3D_LOOP_IF_ONLY)) return fail(C3D_ERR_INVALID, "c3d_loops: unknown flag bits");
+    const bool consensus = (flags & C3D_LOOP_CONSENSUS) != 0, if_only = (flags & C3D_LOOP_IF_ONLY) != 0;
+    if (if_only && (n_pick > 0 || consensus)) return fail(C3D_ERR_INVALID, "c3d_loops: C3D_LOOP_IF_ONLY with a pick list or the consensus");
+    if (if_only) list.clear();
+    const int n = c->n, K = c->nrep + n_extra, Kp = (int)list.size();
+    if (Kp > C3D_COMPARE_MAX_MODELS) return fail(C3D_ERR_INVALID, "c3d_loops: more than 256 picks");
+    if (!IF && Kp < 1) return fail(C3D_ERR_INVALID, "c3d_loops: neither the IF matrix nor a model (C3D_LOOP_IF_ONLY without IF)");
+    if (w < 1 || w > C3D_LOOP_MAX_WINDOW) return fail(C3D_ERR_INVALID, "c3d_loops: w outside 1..C3D_LOOP_MAX_WINDOW");
+    if (p < 0 || p >= w) return fail(C3D_ERR_INVALID, "c3d_loops: p outside 0..w-1");
+    if (min_sep < 2 * w + 1) return fail(C3D_ERR_INVALID, "c3d_loops: min_sep < 2w + 1 (a window would touch the diagonal)");
+    if (max_sep < min_sep || max_sep > n - 1) return fail(C3D_ERR_INVALID, "c3d_loops: max_sep outside min_sep..n-1");
+    const int B = max_sep - min_sep + 1;
+    if (B > C3D_LOOP_MAX_BAND) return fail(C3D_ERR_INVALID, "c3d_loops: more than C3D_LOOP_MAX_BAND separations (B)");
+    if (merge < 0 || merge > w) return fail(C3D_ERR_INVALID, "c3d_loops: merge outside 0..w");
+    if (corner < 1 || corner > w) return fail(C3D_ERR_INVALID, "c3d_loops: corner outside 1..w");
+    if (!std::isfinite(min_obs) || min_obs < 0.0) return fail(C3D_ERR_INVALID, "c3d_loops: min_obs is not finite or < 0");
+    if (max_peaks < 0 || max_peaks > C3D_LOOP_MAX_LIST) return fail(C3D_ERR_INVALID, "c3d_loops: max_peaks outside 0..C3D_LOOP_MAX_LIST");
+    if (!expected && !ratio && !peaks && !report && !at && !closed && !apa && !p2ll) return fail(C3D_ERR_INVALID, "c3d_loops: every output is NULL");
+    if ((ratio || peaks || report) && !IF) return fail(C3D_ERR_INVALID, "c3d_loops: ratio, peaks and report need the IF matrix");
+    const bool want_list = at || closed || apa || p2ll;
+    if (want_list && !list_in && !IF) return fail(C3D_ERR_INVALID, "c3d_loops: at, closed, apa and p2ll need a list: list_in, or the peaks of the IF matrix");
+    if (list_in && (n_list < 0 || n_list > C3D_LOOP_MAX_LIST)) return fail(C3D_ERR_INVALID, "c3d_loops: n_list outside 0..C3D_LOOP_MAX_LIST");
+    if (!list_in && n_list != 0) return fail(C3D_ERR_INVALID, "c3d_loops: n_list without list_in");
+    const bool want_peaks = IF && (peaks || report || (want_list && !list_in));
+    if (want_peaks) {
+        if (!thr) return fail(C3D_ERR_INVALID, "c3d_loops: peaks without thresholds (thr is NULL)");
+        for (int x = 0; x < 4; ++x)
+            if (!std::isfinite(thr[x]) || thr[x] <= 0.0) return fail(C3D_ERR_INVALID, "c3d_loops: a threshold (thr) is not finite or <= 0");
+    }
+    for (int l = 0; list_in && l < n_list; ++l) {
+        const int i = list_in[2 * l], j = list_in[2 * l + 1];
+        if (i < 0 || i >= j || j > n - 1 || j - i < min_sep || j - i > max_sep)
+            return fail(C3D_ERR_INVALID, "c3d_loops: a list entry is not a pair i < j <= n-1 with j - i in min_sep..max_sep");
+    }
+    if (Kp > 0)
+        if (int rc = model_set_coords(c, who, extra_xyz, n_extra)) return rc;
+    const int has_if = IF ? 1 : 0, Q = has_if + Kp + (consensus ? 1 : 0);
+    const int s_lo = min_sep - 2 * w, s_hi = std::min(max_sep + 2 * w, n - 1), S = s_hi - s_lo + 1;
+    // IF's band, row a the cells (a, a + s_lo .. a + s_hi), zeros beyond the matrix; all of it is read (E of every separation), all of it checked
+    std::vector<double> band;
+    if (has_if) {
+        band.assign((size_t)n * S, 0.0);
+        for (int a = 0; a < n; ++a)
+            for (int col = 0; col < S && a + s_lo + col < n; ++col) {
+                const int b = a + s_lo + col;
+                const double v = IF[(size_t)a * n + b];
+                if (!std::isfinite(v)) return fail(C3D_ERR_INVALID, "c3d_loops: an IF entry is not finite");
+                if (v < 0.0) return fail(C3D_ERR_INVALID, "c3d_loops: an IF entry is negative");
+                if (v != IF[(size_t)b * n + a]) return fail(C3D_ERR_INVALID, "c3d_loops: the IF matrix is not symmetric");
+                band[(size_t)a * S + col] = v;
+            }
+    }
+    std::vector<int32_t> bins((size_t)n, 0);
+    for (int i = 0; mask && i < n; ++i) bins[(size_t)i] = mask[i] != 0;
+    C3D_ENTRY(c, unit_bit(UNIT_SCORE));
+    const int Lmax = list_in ? n_list : (want_list ? max_peaks : 0);
+    const LoopScratch L(n, K, Kp, Q, S, B, w, has_if != 0, consensus, ratio != nullptr, want_peaks, max_peaks, Lmax);
+    CallScratch tmp;
+    if (int rc = tmp.alloc(L.total, who)) return rc;
+    PassEvents ev;
+    for (int k = 0; k < 2; ++k) HIP_TRY(hipEventCreate(&ev.e[k]));
+    c3d::LoopJob job{};
+    job.n = n; job.Q = Q; job.has_if = has_if; job.n_models = Kp; job.consensus = consensus ? 1 : 0; job.p = p; job.w = w; job.min_sep = min_sep; job.max_sep = max_sep;
+    job.s_lo = s_lo; job.S = S;
+    job.xyz = L.xyz.at(tmp.p); job.pick = L.pick.at(tmp.p); job.mask = L.mask.at(tmp.p); job.band_if = L.band_if.at(tmp.p); job.band_cons = L.band_cons.at(tmp.p);
+    job.expected = L.expected.at(tmp.p);
+    HIP_TRY(hipEventRecord(ev.e[0], c->stream));
+    if (Kp > 0) {
+        if (int rc = gather_models(c, ModelSource::STATE, 0, c->nrep, L.xyz.at(tmp.p), extra_xyz, n_extra, "loop launch")) return rc;
+        HIP_TRY(hipMemcpyAsync(L.pick.at(tmp.p), list.data(), sizeof(int32_t) * (size_t)Kp, hipMemcpyHostToDevice, c->stream));
+    }
+    HIP_TRY(hipMemcpyAsync(L.mask.at(tmp.p), bins.data(), L.mask.bytes(), hipMemcpyHostToDevice, c->stream));
+    if (has_if) HIP_TRY(hipMemcpyAsync(L.band_if.at(tmp.p), band.data(), L.band_if.bytes(), hipMemcpyHostToDevice, c->stream));
+    LAUNCH_TRY("loop launch", c3d::launch_loop_expected(job, c->stream));
+    int32_t rep[C3D_LOOP_REPORT] = {0, 0, 0, 0};
+    if (has_if && (ratio || want_peaks)) {
+        c3d::LoopPeakRule rule{};
+        for (int x = 0; x < 4 && want_peaks; ++x) rule.thr[x] = thr[x];
+        rule.min_obs = min_obs;
+        LAUNCH_TRY("loop launch", c3d::launch_loop_scan(job, rule, ratio ? L.ratio.at(tmp.p) : nullptr, want_peaks ? L.cand.at(tmp.p) : nullptr, c->stream));
+        if (want_peaks) {
+            LAUNCH_TRY("loop launch", c3d::launch_loop_peaks(job, merge, max_peaks, L.cand.at(tmp.p), L.peak.at(tmp.p), L.rows.at(tmp.p), L.offset.at(tmp.p),
+                                                             L.peaks.at(tmp.p), L.report.at(tmp.p), c->stream));
+            // the number of written peaks sizes the list pass: the one look of the host at the device inside the call
+            HIP_TRY(hipMemcpyAsync(rep, L.report.at(tmp.p), sizeof(rep), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+        }
+    }
+    const int n_listed = list_in ? n_list : rep[2];
+    const int32_t* d_list = list_in ? L.list.at(tmp.p) : L.peaks.at(tmp.p);
+    if (want_list) {
+        if (list_in && n_list > 0) HIP_TRY(hipMemcpyAsync(L.list.at(tmp.p), list_in, sizeof(int32_t) * 2 * (size_t)n_list, hipMemcpyHostToDevice, c->stream));
+        if (at || closed) LAUNCH_TRY("loop launch", c3d::launch_loop_list(job, d_list, n_listed, L.at.at(tmp.p), L.closed.at(tmp.p), c->stream));
+        if (apa || p2ll) LAUNCH_TRY("loop launch", c3d::launch_loop_apa(job, d_list, n_listed, corner, L.apa.at(tmp.p), L.p2ll.at(tmp.p), c->stream));
+    }
+    if (expected) HIP_TRY(hipMemcpyAsync(expected, L.expected.at(tmp.p), L.expected.bytes(), hipMemcpyDeviceToHost, c->stream));
+    if (ratio) HIP_TRY(hipMemcpyAsync(ratio, L.ratio.at(tmp.p), L.ratio.bytes(), hipMemcpyDeviceToHost, c->stream));
+    if (peaks && rep[2] > 0) HIP_TRY(hipMemcpyAsync(peaks, L.peaks.at(tmp.p), sizeof(int32_t) * 2 * (size_t)rep[2], hipMemcpyDeviceToHost, c->stream));
+    if (at && n_listed > 0) HIP_TRY(hipMemcpyAsync(at, L.at.at(tmp.p), sizeof(double) * 6 * (size_t)Q * n_listed, hipMemcpyDeviceToHost, c->stream));
+    if (closed) HIP_TRY(hipMemcpyAsync(closed, L.closed.at(tmp.p), L.closed.bytes(), hipMemcpyDeviceToHost, c->stream));
+    if (apa) HIP_TRY(hipMemcpyAsync(apa, L.apa.at(tmp.p), L.apa.bytes(), hipMemcpyDeviceToHost, c->stream));
+    if (p2ll) HIP_TRY(hipMemcpyAsync(p2ll, L.p2ll.at(tmp.p), L.p2ll.bytes(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipEventRecord(ev.e[1], c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (report) std::copy(rep, rep + C3D_LOOP_REPORT, report);
     if (device_ms) {
         float ms = 0;
         HIP_TRY(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));

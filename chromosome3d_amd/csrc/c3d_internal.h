@@ -594,6 +594,36 @@ struct BalJob {
 hipError_t launch_balance_count(const BalJob& job, hipStream_t s);
 hipError_t launch_balance_round(const BalJob& job, int kept, int t, int max_iters, double tol, bool half_power, hipStream_t s);
 hipError_t launch_balance_apply(const BalJob& job, double target, bool matrix, hipStream_t s);
+// Loop enrichment (c3d_loops; k_loop_*, c3d_score_loop.inc).  The Q maps of a call as in InsJob: map 0 is IF when has_if, its band at
+// band_if — row a the S doubles M(a, a + s_lo .. a + s_lo + S - 1), s_lo = min_sep - 2w, zeros beyond the matrix, packed and checked by
+// the host — then n_models picked models (pick, device: indices into the models of xyz) and, with `consensus`, a last map whose band
+// launch_loop_expected writes to band_cons first.  mask: n ints on the device, non-zero for a bin that is not mappable (all zero when
+// the caller gave none).  expected: Q x S, row q map q's E[s_lo .. s_lo + S - 1].  A pixel flag array is B x n bytes, [s - min_sep][i].
+// launch_loop_expected: band_cons, expected.  launch_loop_scan (IF only): ratio (4 x B x n, may be null) and cand (may be null), the
+// candidate flags under `rule`.  launch_loop_peaks: peak (the candidates that survive the suppression), rows (3 n: a row's candidates,
+// peaks, inside pixels with a masked end), offset (n: the peaks before row i), peaks (max_peaks x 2, ascending (i, j)) and report[4].
+// launch_loop_list: at (Q x L x 6) and closed (Q x 2) for the L pairs of `list` (device, L x 2).  launch_loop_apa: apa
+// (Q x (2w+1)^2) and p2ll (Q).
+constexpr int kLoopTile = 32;         // k_loop_scan: a workgroup owns kLoopTile x kLoopTile pixels
+struct LoopJob {
+    int n, Q, has_if, n_models, consensus, p, w, min_sep, max_sep, s_lo, S;
+    const double* xyz;
+    const int* pick;
+    const int* mask;
+    const double* band_if;
+    double* band_cons;
+    double* expected;
+};
+struct LoopPeakRule {
+    double thr[4];                    // donut, lower-left, horizontal, vertical
+    double min_obs;
+};
+hipError_t launch_loop_expected(const LoopJob& job, hipStream_t s);
+hipError_t launch_loop_scan(const LoopJob& job, const LoopPeakRule& rule, double* ratio, unsigned char* cand, hipStream_t s);
+hipError_t launch_loop_peaks(const LoopJob& job, int merge, int max_peaks, const unsigned char* cand, unsigned char* peak, int* rows, int* offset, int* peaks, int* report,
+                             hipStream_t s);
+hipError_t launch_loop_list(const LoopJob& job, const int* list, int L, double* at, int* closed, hipStream_t s);
+hipError_t launch_loop_apa(const LoopJob& job, const int* list, int L, int corner, double* apa, double* p2ll, hipStream_t s);
 
 // Target matrix entry: NOE target in Angstrom, 0 = no restraint (host c3d_set_restraints and K1).
 inline float encode_target_host(float t) { return t > 0 ? t : 0.0f; }

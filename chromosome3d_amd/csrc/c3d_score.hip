@@ -35,6 +35,8 @@
 //                             in LDS, every window out of one walk over nested squares (c3d_insulation)
 //   c3d_score_balance.inc     k_bal_*    the input side: a raw contact matrix balanced by ICE, VC or sqrt-VC, one streaming matrix-vector pass
 //                             a round, the stop decided on the device (c3d_balance_matrix)
+//   c3d_score_loop.inc        k_loop_*   loop enrichment: a pixel's four local-background ratios out of one walk over its window, IF's tiles
+//                             staged in LDS, peaks by exact suppression, listed pixels in every map and their pile-up (c3d_loops)
 #include "c3d_score_core.h"
 
 namespace c3d {
@@ -274,6 +276,7 @@ hipError_t launch_if_rank_sort(double* M, int n, int range, unsigned long long* 
 #include "c3d_score_compartment.inc"
 #include "c3d_score_insulation.inc"
 #include "c3d_score_balance.inc"
+#include "c3d_score_loop.inc"
 
 // loads the unit's code object on the current device and gives the k_str_* and k_bead_* kernels their dynamic-LDS allowance (c3d_gate.cpp "code objects":
 // once per device, never beside a launch)

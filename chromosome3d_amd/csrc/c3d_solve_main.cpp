@@ -19,6 +19,7 @@
 //       which loci lie on the surface of the fold and which are buried in it
 //   --compartments <prefix> writes <prefix>_compartments.txt — the first compartment eigenvector (PC1 of the correlation of the observed/expected
 //       map) of IF, of the models' consensus distance map and of every model, and how well each agrees with IF's
+//   --loops <prefix> writes <prefix>_loops.txt — the peaks of IF with their local-background ratios, and whether the models close them
 //   --insulation <prefix> writes <prefix>_insulation.txt — the insulation profile and the domain boundaries of IF and of the models' consensus
 //       map per window, how many models place a boundary at each bead, and how well every model's profile fits IF's
 //   --balance <ice|vc|sqrt-vc> balances the matrix of --if on the device first (raw contact counts in, a normalised matrix out): the solve and
@@ -29,6 +30,7 @@
 #include <sys/stat.h>
 
 #include <algorithm>
+#include <cctype>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -112,6 +114,15 @@ static void usage() {
             "                 [--insulation-windows <a,b,c>   half-widths of the squares in beads, ascending, 1..128; default 5,10,25, those that fit (2w + 1 <= n)]\n"
             "                 [--insulation-contact <cutoff>   models and consensus: count contacts (distance < cutoff, in A) in the square instead of averaging the distance]\n"
             "                 [--insulation-tol <beads>   how far apart two boundaries may lie and still match; default 1]\n"
+            "                 [--loops <prefix>   which pixels of IF are loops, and do the models close them?  Computed on the device.\n"
+            "                                          <prefix>_loops.txt: a line a peak of IF, `i j IF r_donut r_ll r_h r_v consensus_d consensus_r_donut consensus_r_ll models_closed`\n"
+            "                                          (beads from 1; the four local-background ratios of the pixel; the consensus' distance and ratios, below 1 where\n"
+            "                                          the models close the loop; how many models have both ratios below 1), then per map `# <map> scored closed P2LL`]\n"
+            "                 [--loop-window <w>   half-width of a pixel's window in beads, 1..20; default 5]\n"
+            "                 [--loop-peak <p>   half-width of the peak square left out of the backgrounds, 0..w-1; default 2]\n"
+            "                 [--loop-sep <MIN:MAX>   separations j - i that are scanned; default 2w+1 : min(n-1, 2w+1024)]\n"
+            "                 [--loop-thr <a,b,c,d>   least ratio against the donut, lower-left, horizontal and vertical background; default 1.75,1.75,1.5,1.5]\n"
+            "                 [--loop-list <FILE>   score these pixels (lines `i j`, beads from 1) instead of the peaks of IF]\n"
             "                 [--balance <ice|vc|sqrt-vc>   the matrix of --if holds raw contact counts: balance it on the device first (iterative correction, vanilla\n"
             "                                          coverage or its square root); the solve and every analysis option of the run use the balanced matrix.  Bins that\n"
             "                                          cannot be balanced get weight 0 and no restraints]\n"
@@ -156,6 +167,8 @@ int main(int argc, char** argv) {
     bool insulation_windows_given = false;
     double insulation_contact = 0;                   // 0: mean distance
     int insulation_tol = 1;
+    std::string loops_prefix, loop_sep, loop_thr = "1.75,1.75,1.5,1.5", loop_list;
+    int loop_window = 5, loop_peak = 2;
     std::string balance_method, balance_out;          // empty: the matrix of --if is taken as it is
     int balance_ignore_diags = 2, balance_min_nnz = 10, balance_iters = 200;
     double balance_tol = 1e-5;
@@ -218,6 +231,12 @@ int main(int argc, char** argv) {
         else if (s == "--insulation-windows") { insulation_windows = next("--insulation-windows"); insulation_windows_given = true; }
         else if (s == "--insulation-contact") insulation_contact = atof(next("--insulation-contact"));
         else if (s == "--insulation-tol") insulation_tol = atoi(next("--insulation-tol"));
+        else if (s == "--loops") loops_prefix = next("--loops");                  // loop enrichment of IF and the models (c3d_loops)
+        else if (s == "--loop-window") loop_window = atoi(next("--loop-window"));
+        else if (s == "--loop-peak") loop_peak = atoi(next("--loop-peak"));
+        else if (s == "--loop-sep") loop_sep = next("--loop-sep");
+        else if (s == "--loop-thr") loop_thr = next("--loop-thr");
+        else if (s == "--loop-list") loop_list = next("--loop-list");
         else if (s == "--balance") balance_method = next("--balance");   // balance the raw matrix first (c3d_balance_matrix)
         else if (s == "--balance-ignore-diags") balance_ignore_diags = atoi(next("--balance-ignore-diags"));
         else if (s == "--balance-min-nnz") balance_min_nnz = atoi(next("--balance-min-nnz"));
@@ -237,6 +256,7 @@ int main(int argc, char** argv) {
     if (!per_bead_prefix.empty() && if_path.empty()) { fprintf(stderr, "c3d_solve: --per-bead needs --if: a run started from --tbl has no IF matrix\n"); return 2; }
     if (!compartments_prefix.empty() && if_path.empty()) { fprintf(stderr, "c3d_solve: --compartments needs --if: a run started from --tbl has no IF matrix\n"); return 2; }
     if (!insulation_prefix.empty() && if_path.empty()) { fprintf(stderr, "c3d_solve: --insulation needs --if: a run started from --tbl has no IF matrix\n"); return 2; }
+    if (!loops_prefix.empty() && if_path.empty()) { fprintf(stderr, "c3d_solve: --loops needs --if: a run started from --tbl has no IF matrix\n"); return 2; }
     if ((!balance_method.empty() || !balance_out.empty()) && if_path.empty()) { fprintf(stderr, "c3d_solve: --balance needs --if: a run started from --tbl has no matrix to balance\n"); return 2; }
     if (!balance_out.empty() && balance_method.empty()) { fprintf(stderr, "c3d_solve: --balance-out needs --balance <ice|vc|sqrt-vc>\n"); return 2; }
     if (!balance_method.empty() && balance_method != "ice" && balance_method != "vc" && balance_method != "sqrt-vc") {
@@ -621,6 +641,75 @@ int main(int argc, char** argv) {
                 }
                 fprintf(f, "%d %d %.6f %.6f %d %.6f %d %.6f %d\n", win[k], i + 1, score[a_if], score[a_co], boundary[a_if], strength[a_if], boundary[a_co], strength[a_co], support);
             }
+        fclose(f);
+    }
+    if (!loops_prefix.empty()) {
+        std::vector<int32_t> order(models), listed;
+        CHECK(c3d_rank(ctx, order.data()));
+        const int w = loop_window;
+        int lo = 2 * w + 1, hi = std::min(n - 1, lo + C3D_LOOP_MAX_BAND - 1);
+        if (!loop_sep.empty() && sscanf(loop_sep.c_str(), "%d:%d", &lo, &hi) != 2) { fprintf(stderr, "c3d_solve: --loop-sep takes MIN:MAX\n"); return fail_exit(out_dir); }
+        double thr[4];
+        if (sscanf(loop_thr.c_str(), "%lf,%lf,%lf,%lf", &thr[0], &thr[1], &thr[2], &thr[3]) != 4) { fprintf(stderr, "c3d_solve: --loop-thr takes four numbers a,b,c,d\n"); return fail_exit(out_dir); }
+        if (!loop_list.empty()) {
+            FILE* lf = fopen(loop_list.c_str(), "r");
+            if (!lf) { fprintf(stderr, "c3d_solve: cannot read %s\n", loop_list.c_str()); return fail_exit(out_dir); }
+            // a line is `i j` and whatever columns follow (a <prefix>_loops.txt can be fed back); blank lines and `#` lines are skipped
+            char line[4096];
+            int row = 0;
+            while (fgets(line, sizeof line, lf)) {
+                ++row;
+                const char* q = line;
+                while (*q == ' ' || *q == '\t') ++q;
+                if (*q == '#' || *q == '\n' || *q == '\r' || *q == 0) continue;
+                int a, b, used = 0;
+                if (sscanf(q, "%d %d%n", &a, &b, &used) != 2 || (q[used] && !isspace((unsigned char)q[used])) || listed.size() / 2 >= (size_t)C3D_LOOP_MAX_LIST) {
+                    fprintf(stderr, "c3d_solve: --loop-list %s, line %d: not a pair of bead numbers `i j`, or more than %d pairs\n", loop_list.c_str(), row, C3D_LOOP_MAX_LIST);
+                    fclose(lf);
+                    return fail_exit(out_dir);
+                }
+                listed.push_back(a - 1);
+                listed.push_back(b - 1);
+            }
+            fclose(lf);
+            if (listed.empty()) { fprintf(stderr, "c3d_solve: --loop-list %s holds no pair\n", loop_list.c_str()); return fail_exit(out_dir); }
+        }
+        // the maps: IF, the models in rank order, their consensus; the list: the file's pixels, else the peaks of IF
+        const int Q = models + 2, max_peaks = 4096, merge = std::min(2, w), corner = std::min(3, w);
+        const size_t Lmax = loop_list.empty() ? (size_t)max_peaks : listed.size() / 2;
+        std::vector<double> at(6 * (size_t)Q * Lmax), p2ll(Q);               // Lmax >= 1: what the call can write
+        std::vector<int32_t> peaks(2 * (size_t)max_peaks), closed(2 * (size_t)Q);
+        int32_t report[C3D_LOOP_REPORT];
+        CHECK(c3d_loops(ctx, IF, nullptr, 0, order.data(), models, C3D_LOOP_CONSENSUS, nullptr, loop_peak, w, lo, hi, thr, 0.0, merge, corner,
+                        loop_list.empty() ? nullptr : listed.data(), (int)(listed.size() / 2), max_peaks, nullptr, nullptr, peaks.data(), report, at.data(), closed.data(),
+                        nullptr, p2ll.data(), nullptr));
+        const int L = loop_list.empty() ? report[2] : (int)(listed.size() / 2);
+        const int32_t* px = loop_list.empty() ? peaks.data() : listed.data();
+        const std::string path = loops_prefix + "_loops.txt";
+        FILE* f = fopen(path.c_str(), "w");
+        if (!f) { fprintf(stderr, "c3d_solve: cannot write %s\n", path.c_str()); return fail_exit(out_dir); }
+        fprintf(f, "# i j IF r_donut r_ll r_h r_v consensus_d consensus_r_donut consensus_r_ll models_closed   (window %d, peak %d, separations %d..%d; %d candidates, %d peaks, %d listed; model r is %s_<r>.pdb)\n",
+                w, loop_peak, lo, hi, report[0], report[1], L, id.c_str());
+        fprintf(f, "# models:");
+        for (int k = 0; k < models; ++k) fprintf(f, " %u", first_rep + (unsigned)order[k] + 1u);
+        fprintf(f, "\n");
+        for (int l = 0; l < L; ++l) {
+            const double* a_if = at.data() + 6 * (size_t)l;
+            const double* a_co = at.data() + 6 * ((size_t)(Q - 1) * L + l);
+            int shut = 0;
+            for (int q = 1; q <= models; ++q) {
+                const double* a = at.data() + 6 * ((size_t)q * L + l);
+                shut += a[2] < 1.0 && a[3] < 1.0;
+            }
+            fprintf(f, "%d %d %.6g %.4f %.4f %.4f %.4f %.3f %.4f %.4f %d\n", px[2 * l] + 1, px[2 * l + 1] + 1, a_if[0], a_if[2], a_if[3], a_if[4], a_if[5], a_co[0], a_co[2],
+                    a_co[3], shut);
+        }
+        for (int q = 0; q < Q; ++q) {
+            if (q == 0) fprintf(f, "# IF");
+            else if (q == Q - 1) fprintf(f, "# consensus");
+            else fprintf(f, "# model %d", q);
+            fprintf(f, " %d %d %.4f\n", closed[2 * q], closed[2 * q + 1], p2ll[q]);
+        }
         fclose(f);
     }
     double ms = 0;

@@ -285,6 +285,27 @@ def insulation_report(solver, IF, extra=None, pick=None, windows=(5, 10, 25), co
     return out
 
 
+def loop_report(solver, IF, extra=None, pick=None, mask=None, pixels=None, **kw):
+    """Which pixels of IF are loops, and do the models close them?  Solver.loops' dict for IF, every picked model and the consensus
+    (kw: its p, w, min_sep, max_sep, thr, min_obs, merge, corner, max_peaks), with "text": a table of the listed pixels — bead numbers
+    from 1, IF's value and four ratios, the consensus' distance and its donut and lower-left ratios, and the number of models that
+    close the pixel (both ratios below 1) — and below it, per map, `closed` and P2LL."""
+    out = solver.loops(IF, extra, pick, True, mask, pixels=pixels, **kw)
+    at, names = out["at"], out["maps"]
+    model_rows = at[1:-1]
+    shut = ((model_rows[:, :, 2] < 1.0) & (model_rows[:, :, 3] < 1.0)).sum(axis=0)
+    lines = ["# i j IF r_donut r_ll r_h r_v consensus_d consensus_r_donut consensus_r_ll models_closed   (%d of %d candidates are peaks, %d listed; %d models)"
+             % (out["found"], out["candidates"], len(out["pixels"]), len(model_rows))]
+    for l, (i, j) in enumerate(out["pixels"]):
+        lines.append("%d %d %.6g %.4f %.4f %.4f %.4f %.3f %.4f %.4f %d" % ((i + 1, j + 1) + tuple(at[0, l, [0, 2, 3, 4, 5]]) + tuple(at[-1, l, [0, 2, 3]]) + (shut[l],)))
+    lines.append("# map scored closed P2LL")
+    for q, name in enumerate(names):
+        lines.append("# %s %d %d %.4f" % (name, out["closed"][q, 0], out["closed"][q, 1], out["p2ll"][q]))
+    out["models_closed"] = shut.astype(np.int32)
+    out["text"] = "\n".join(lines) + "\n"
+    return out
+
+
 def balance_if(path_or_matrix, solver=None, device=0, **kw):
     """A raw contact matrix (a path in the text format of parse_if_file, or an array) balanced on the device and ready for set_if_matrix:
     Solver.balance's "balanced", rows of bins that cannot be balanced all 0 (set_if_matrix reads 0 as no restraint).  kw: the arguments of

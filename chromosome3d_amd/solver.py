@@ -586,6 +586,76 @@ class Solver:
         out["device_ms"] = ms.value
         return out
 
+    def loops(self, IF=None, extra=None, pick=None, consensus=False, mask=None, p=2, w=5, min_sep=None, max_sep=None, thr=(1.75, 1.75, 1.5, 1.5),
+              min_obs=0.0, merge=2, corner=3, pixels=None, max_peaks=4096, want_ratio=False, models=True):
+        """Loop enrichment on the device (c3d_loops), for Q maps in this order: IF [n, n] if given, every picked model's distance map
+        (pick: indices into the K models of compare(), None: all; models=False: none, IF alone) and with consensus=True the pick list's
+        mean distance map.  mask: [n], non-zero for an unmappable bin (balance()'s "masked").  Windows of half-width w with the inner
+        p x p peak left out, over pixels (i, j) with min_sep <= j - i <= max_sep (defaults: 2w + 1 and min(n - 1, 2w + 1024)).  With IF
+        the pixels whose four background ratios reach thr (donut, lower-left, horizontal, vertical) and whose value reaches min_obs are
+        candidates, and the peaks are the candidates no other candidate within `merge` beats.  pixels: [L, 2] pairs to score in every
+        map; None: the written peaks (at most max_peaks).  A dict: "expected" [Q, S] (E of the separations "separations"), with IF
+        "peaks" [written, 2] int32, "candidates", "found", "masked_pixels" and with want_ratio "ratio" [4, B, n]; with a list "pixels"
+        [L, 2], "at" [Q, L, 6] (M, E, r_donut, r_ll, r_h, r_v), "closed" [Q, 2] int32 (pixels with r_donut and r_ll, of those on the loop
+        side: > 1 for IF, < 1 for distances), "apa" [Q, 2w+1, 2w+1] and "p2ll" [Q]; "maps", "device_ms".  Nothing of the solve changes."""
+        n = self.n
+        m = None
+        if IF is not None:
+            m = np.ascontiguousarray(IF, dtype=np.float64)
+            assert m.shape == (n, n)
+        p, w = int(p), int(w)
+        lo = 2 * w + 1 if min_sep is None else int(min_sep)
+        hi = min(n - 1, lo + _l.LOOP_MAX_BAND - 1) if max_sep is None else int(max_sep)
+        if models:
+            xptr, E = self._extra_models(extra)
+            pk, n_pick = self._picked(pick)
+            Kp = n_pick if pk is not None else self.nrep + E
+        else:
+            xptr, E, pk, n_pick, Kp = None, 0, None, 0, 0
+        has_if = 1 if m is not None else 0
+        Q = has_if + Kp + (1 if consensus else 0)
+        S = max(0, min(hi + 2 * w, n - 1) - (lo - 2 * w) + 1)
+        B = max(0, hi - lo + 1)
+        side = 2 * max(w, 0) + 1
+        mk = np.ascontiguousarray(mask, dtype=np.int32).reshape(-1) if mask is not None else None
+        assert mk is None or len(mk) == n
+        t = np.ascontiguousarray(thr, dtype=np.float64).reshape(-1)
+        assert len(t) == 4
+        lst = np.ascontiguousarray(pixels, dtype=np.int32).reshape(-1, 2) if pixels is not None else None
+        listed = lst is not None or has_if
+        Lmax = len(lst) if lst is not None else max(int(max_peaks), 0)
+        out = {"expected": np.empty((Q, S))}
+        ratio = np.empty((4, B, n)) if (want_ratio and has_if) else None
+        peaks = np.empty((max(int(max_peaks), 0), 2), dtype=np.int32) if has_if else None
+        report = np.zeros(4, dtype=np.int32) if has_if else None
+        at = np.empty((Q, Lmax, 6)) if listed else None
+        closed = np.empty((Q, 2), dtype=np.int32) if listed else None
+        apa = np.empty((Q, side, side)) if listed else None
+        p2ll = np.empty(Q) if listed else None
+        dp = lambda a: _l.dptr(a) if a is not None else None
+        ip = lambda a: _l.i32ptr(a) if a is not None else None
+        flags = (_l.LOOP_CONSENSUS if consensus else 0) | (0 if models else _l.LOOP_IF_ONLY)
+        ms = C.c_double()
+        _l.check(self._L.c3d_loops(self._h, dp(m), xptr, E, ip(pk), n_pick, flags, ip(mk), p, w, lo, hi, _l.dptr(t), float(min_obs), int(merge), int(corner),
+                                   ip(lst) if lst is not None and len(lst) else (ip(np.zeros(2, np.int32)) if lst is not None else None),
+                                   len(lst) if lst is not None else 0, int(max_peaks), _l.dptr(out["expected"]), dp(ratio), ip(peaks), ip(report),
+                                   dp(at), ip(closed), dp(apa), dp(p2ll), C.byref(ms)))
+        out["separations"] = list(range(lo - 2 * w, lo - 2 * w + S))
+        if has_if:
+            out["candidates"], out["found"], out["masked_pixels"] = int(report[0]), int(report[1]), int(report[3])
+            out["peaks"] = peaks[:int(report[2])].copy()
+            if ratio is not None:
+                out["ratio"] = ratio
+        if listed:
+            L = len(lst) if lst is not None else int(report[2])
+            out["pixels"] = lst if lst is not None else out["peaks"]
+            out["at"] = np.ascontiguousarray(at.reshape(-1)[:Q * L * 6].reshape(Q, L, 6))
+            out["closed"], out["apa"], out["p2ll"] = closed, apa, p2ll
+        names = [int(k) for k in pk] if pk is not None else list(range(Kp))
+        out["maps"] = (["IF"] if has_if else []) + ["model %d" % k for k in names] + (["consensus"] if consensus else [])
+        out["device_ms"] = ms.value
+        return out
+
     def balance(self, M, method="ice", ignore_diags=2, min_nnz=10, mask=None, w0=None, tol=1e-5, max_iters=200, target=1.0, want_matrix=True,
                 check_every_round=False):
         """A raw contact matrix balanced on the device (c3d_balance_matrix): M [n, n], symmetric, finite, >= 0, n up to the context's

@@ -858,6 +858,95 @@ int c3d_insulation(c3d_ctx* ctx, const double* IF, const double* extra_xyz, int 
                    int flags, const int32_t* windows, int n_win, double cutoff, double min_strength, int tol,
                    double* mean, double* score, int32_t* boundary, double* strength,
                    double* fit_r, int32_t* fit_counts, double* device_ms);
+/* Loop enrichment on the device (c3d_score_loop.inc k_loop_*): which pixels of IF are loops, and do the models close them?  Compartments
+ * are the large-scale feature of a contact map and domain boundaries the local one; loops are the point feature: pixels (i, j) whose
+ * contact frequency stands out against their own neighbourhood beyond what the distance decay explains.  The read-outs are the four
+ * local-background ratios of HiCCUPS and aggregate peak analysis (APA).  A model closes a loop when the two anchors sit nearer than
+ * the pixel's surroundings: the same ratios on its distance map, below 1.
+ *
+ * Maps, in order, Q in all: IF if non-NULL (n x n with the context's n); then one map per picked model, its distance map; then, with
+ *   C3D_LOOP_CONSENSUS in flags, the consensus: the pick list's mean distance, summed in list order and divided once by Kp, as
+ *   c3d_ensemble_map defines `mean`.  Models, pick, n_pick (at most 256), extra models and the fp64 state of a precision-64 context are
+ *   taken exactly as c3d_insulation takes them (pick NULL and n_pick 0: all models), and the pair distance is the same:
+ *   sqrt(((ux ux) + uy uy) + uz uz), every operation rounded on its own.  C3D_LOOP_IF_ONLY in flags leaves the models out (it refuses a
+ *   pick list and the consensus).  A call needs at least one of: IF, a non-empty pick list.
+ * Mask.  `mask` is optional and holds n int32 values; non-zero means an unmappable bin (c3d_balance_matrix's `masked` can be passed as
+ *   it is).  A cell (a, b) is live when neither a nor b is masked.  The mask applies to every map alike.
+ * Geometry.  0 <= p < w <= C3D_LOOP_MAX_WINDOW.  Separations s = j - i with min_sep <= s <= max_sep, min_sep >= 2w + 1, max_sep <= n - 1,
+ *   B = max_sep - min_sep + 1 <= C3D_LOOP_MAX_BAND.  Only the separations s_lo = min_sep - 2w through s_hi = min(max_sep + 2w, n - 1) of
+ *   any map are ever read, S = s_hi - s_lo + 1 of them; no window touches the diagonal.  A pixel (i, j = i + s) is inside when i >= w
+ *   and j + w <= n - 1.
+ * Definitions, per map M:
+ *   1. Expected.  E[s] = (sum over i ascending, with (i, i+s) live, of M(i, i+s)) / (the number of such i), 0 when there is none.
+ *      `expected` is Q x S.
+ *   2. Neighbourhoods of a pixel, over cells (i + a, j + b) with a, b in [-w, w]; P = {|a| <= p and |b| <= p}.
+ *      donut: not P, a != 0, b != 0.  lower-left: not P, a >= 1, b <= -1 (the quadrant towards the diagonal).
+ *      horizontal: |a| <= 1, |b| > p.  vertical: |b| <= 1, |a| > p.
+ *   3. Sums.  SM_x = the sum of M(cell) over the live cells of neighbourhood x, SE_x = the sum of E[separation of the cell] over the
+ *      same cells.  Each of the eight sums is one accumulator that takes its cells in row-major order: a ascending, then b ascending.
+ *      A pixel's numbers are therefore a function of the pixel alone: the same bytes from the dense scan and from the list pass, alone
+ *      or among others, on any grid.
+ *   4. Ratios.  r_x = M(i,j) / ((SM_x / SE_x) * E[s]), three roundings in that order.  NaN when the pixel is not inside, when i or j is
+ *      masked, when E[s] == 0, or when SM_x == 0 or SE_x == 0.  The sign is left as it comes: a loop is r > 1 on IF and r < 1 on a
+ *      distance map.
+ *   5. Dense scan, IF only.  `ratio` is 4 x B x n doubles, [x][s - min_sep][i], x in the order donut, lower-left, horizontal,
+ *      vertical; NaN wherever i + s > n - 1.
+ *   6. Peaks, IF only.  thr[4] in the same order.  A pixel is a candidate when all four ratios are non-NaN, r_x >= thr[x] for each and
+ *      M(i,j) >= min_obs.  A candidate is a peak unless another candidate within Chebyshev distance `merge` (0 <= merge <= w) has a
+ *      larger M(i,j), or an equal one and a lexicographically smaller (i, j).  Exact comparisons of the ratio bytes and of input
+ *      values.  `peaks`: max_peaks x 2 int32, the peaks in ascending (i, j) order; only the written ones are stored.
+ *      report[C3D_LOOP_REPORT] = {candidates, peaks found, peaks written = min(found, max_peaks), inside pixels with a masked end}.
+ *      Finding more than max_peaks is not an error.
+ *   7. The list.  list_in non-NULL: L = n_list pairs (i, j) in the caller's order, at most C3D_LOOP_MAX_LIST, each with i < j,
+ *      j - i in [min_sep, max_sep] and j <= n - 1; a pair may be not inside, its ratios are then NaN.  Otherwise the list is the written
+ *      peaks of this call (this needs IF), L = report[2]: size `at` for max_peaks.  `at`: Q x L x 6 doubles
+ *      {M(i,j), E[s], r_donut, r_ll, r_h, r_v}; on a model row M(i,j) is the pair distance; IF's rows hold the same bytes as `ratio`
+ *      at those pixels.  `closed`: Q x 2 int32 {listed pixels whose r_donut and r_ll are both non-NaN, of those the number with both
+ *      on the loop side}: > 1 for IF, < 1 for models and the consensus.
+ *   8. APA.  For offsets (a, b) in [-w, w]^2, apa[q][a][b] is the mean of M(i+a, j+b) / E[separation of the cell] over the listed
+ *      pixels that are inside and whose cell is live with E != 0: the quotient rounded first, the terms added in list order through the
+ *      scoring unit's block reduction (thread t takes the pixels t, t + 256, ...) and divided once by their number; NaN when there are
+ *      none.  `apa` is Q x (2w+1)^2 doubles.  p2ll[q] = apa[q][0][0] / (the mean of the corner x corner cells a in [w - corner + 1, w],
+ *      b in [-w, -w + corner - 1], added row-major), 1 <= corner <= w; NaN if any term is NaN.
+ * Outputs, any may be NULL but not all of them.  ratio, peaks and report are refused without IF; at, closed, apa and p2ll are refused
+ *   when the list would be empty by construction: no list_in and no IF.  device_ms, optional: the HIP-event time of the device part
+ *   (there is no stat key for it).
+ * How it runs.  No n x n map is formed for anything: the host packs IF's band (row a holds M(a, a + s_lo .. a + s_hi), n x S doubles)
+ *   and uploads it with the mask, k_loop_band writes the consensus in the same layout, a model's cells come from its coordinates.
+ *   k_loop_expected: a workgroup a (separation, map).  k_loop_scan, the hot kernel: a workgroup owns a 32 x 32 tile of pixels, stages
+ *   the (32 + 2w)^2 cells and their E values by separation in LDS (at most 72^2 doubles, 41 KiB) and gives every thread four pixels,
+ *   each walking its (2w+1)^2 cells once.  k_loop_nms, k_loop_rows, k_loop_offsets, k_loop_write: the suppression and the ordered
+ *   compaction, on integer counts and an integer scan.  k_loop_list: a thread a (listed pixel, map).  k_loop_apa: a workgroup a (cell
+ *   offset, map).  With the list taken from the peaks the host reads the report once between the two parts.
+ * Determinism.  No atomics on floating-point data and no floating-point prefix sums; two calls return the same bytes; a model's rows
+ *   are the same bytes whether it is analysed alone or among others, and a listed pixel's whether it is listed alone or in a longer
+ *   list (apa and p2ll are sums over the list and depend on it).  No state of the solve changes.
+ * C3D_ERR_INVALID with the function's name, before any launch and with nothing written: the refusals of c3d_insulation for the context,
+ * models, picks, extra coordinates and unknown flag bits; p, w, min_sep, max_sep, B, merge or corner out of the ranges above; thr NULL
+ * when peaks are wanted (peaks, report, or a list taken from the peaks), or a threshold that is not finite or is <= 0; min_obs not
+ * finite or < 0; max_peaks < 0 or above C3D_LOOP_MAX_LIST; a bad list entry or n_list; the consensus of no model (C3D_LOOP_IF_ONLY with C3D_LOOP_CONSENSUS); the output
+ * rules above; IF asymmetric, not finite or negative anywhere in the band that is read (the host checks while it packs the band).
+ * C3D_ERR_NOMEM: no device memory for the scratch.
+ * Measured on an MI355X (profiles/r33_loops.md, tools/loops.py; the entry's device_ms): 455 x 20 with IF and the consensus, w = 5,
+ * separations 11..200: 0.52 ms; 4096 x 20 with IF, w = 10, B = 512: 2.5 ms; 16384 x 20 without IF on a list of 4096 pixels: 6.4 ms; 16384
+ * with IF alone, w = 20, B = 512: 19.6 ms, of which k_loop_scan and the suppression take 15.2 ms — 9.1e11 cells/s, 10 % of the LDS read
+ * rate and 19 % of the fp64 addition rate: the walk is VALU-bound; the numpy restatement on the same host: about 10 minutes, scaled.
+ * Scratch, one allocation per call, freed before it returns: 24 n K of coordinates + 8 n S per band (IF, consensus) + 8 Q S of
+ * expected values + with IF 32 B n of ratios (when asked for) and 2 B n of flags + 48 Q L for the list: 9.1 MB at 455 beads x 20 models
+ * with IF, the consensus, w = 5, separations 11..200, `ratio` and max_peaks = 4096; 12.3 MB at 16384 x 20 with w = 20, B = 512 and a
+ * list of 4096 pixels (90.1 MB with the consensus band), where one n x n map alone is 2 GiB. */
+#define C3D_LOOP_MAX_WINDOW  20
+#define C3D_LOOP_MAX_BAND    1024
+#define C3D_LOOP_MAX_LIST    65536
+#define C3D_LOOP_CONSENSUS   1      /* one more map after the models: the pick list's mean distance map */
+#define C3D_LOOP_IF_ONLY     2      /* no model maps: IF alone (refuses a pick list and the consensus) */
+#define C3D_LOOP_REPORT      4
+int c3d_loops(c3d_ctx* ctx, const double* IF, const double* extra_xyz, int n_extra, const int32_t* pick, int n_pick,
+              int flags, const int32_t* mask, int p, int w, int min_sep, int max_sep,
+              const double* thr, double min_obs, int merge, int corner,
+              const int32_t* list_in, int n_list, int max_peaks,
+              double* expected, double* ratio, int32_t* peaks, int32_t* report,
+              double* at, int32_t* closed, double* apa, double* p2ll, double* device_ms);
 /* Balancing a raw contact matrix on the device (c3d_score_balance.inc k_bal_*): the input side.  c3d_set_if_matrix expects a normalised
  * matrix; this entry turns raw contact counts into one by iterative correction (ICE), vanilla coverage (VC) or its square root (sqrt-VC).
  * It needs a context, but no targets and no replicas, and changes no state of the solve.  Bins that cannot be balanced get weight 0, so

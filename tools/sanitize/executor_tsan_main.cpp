@@ -132,6 +132,20 @@ static void api_storm(int device_count) {
                                           nullptr, nullptr, nullptr) == C3D_OK;
                 ok = ok && c3d_insulation(c, nullptr, nullptr, 0, picked, 3, 0, ibad, 2, 0.0, 0.0, 0, imean.data(), nullptr, nullptr, nullptr, nullptr, nullptr,
                                           nullptr) == C3D_ERR_INVALID;
+                // (IF + 4 models + consensus: 6 maps, w = 2, separations 5..20, the list taken from the peaks; then a list of two with a masked bin)
+                const double lthr[4] = {0.5, 0.5, 0.5, 0.5};
+                const int32_t lpix[4] = {8, 20, 1, 12};
+                std::vector<double> lexp(6 * 28), lratio(4 * 16 * (size_t)n), lat(6 * 6 * 64), lapa(6 * 25), lp2(6);
+                std::vector<int32_t> lpeaks(2 * 64), lclosed(2 * 6), lmask(n, 0);
+                int32_t lrep[C3D_LOOP_REPORT];
+                lmask[3] = 1;
+                double loop_ms = -1;
+                ok = ok && c3d_loops(c, IF.data(), nullptr, 0, nullptr, 0, C3D_LOOP_CONSENSUS, nullptr, 0, 2, 5, 20, lthr, 0.0, 1, 1, nullptr, 0, 64, lexp.data(), lratio.data(),
+                                     lpeaks.data(), lrep, lat.data(), lclosed.data(), lapa.data(), lp2.data(), &loop_ms) == C3D_OK && loop_ms >= 0 && lrep[2] <= 64;
+                ok = ok && c3d_loops(c, nullptr, nullptr, 0, picked, 3, 0, lmask.data(), 1, 2, 5, 20, nullptr, 0.0, 0, 2, lpix, 2, 0, nullptr, nullptr, nullptr, nullptr,
+                                     lat.data(), lclosed.data(), lapa.data(), lp2.data(), nullptr) == C3D_OK && lclosed[0] <= 2;
+                ok = ok && c3d_loops(c, nullptr, nullptr, 0, picked, 3, 0, nullptr, 2, 2, 5, 20, nullptr, 0.0, 0, 1, lpix, 2, 0, nullptr, nullptr, nullptr, nullptr,
+                                     lat.data(), nullptr, nullptr, nullptr, nullptr) == C3D_ERR_INVALID;
                 // (the raw matrix: IF itself, an odd and an even n over the threads; bin 1 masked by the caller)
                 std::vector<double> bw(n), bbal((size_t)n * n), bhist(51), brep(C3D_BALANCE_REPORT);
                 std::vector<int32_t> bmask(n, 0), bcode(n);

@@ -802,6 +802,138 @@ hipError_t launch_insulation_fit(const InsJob& J, const double* score, const int
     return hipSuccess;
 }
 
+// c3d_loops: the five launchers restated on the host with plain loops in the order of the definitions (include/c3d.h; no tiles, no LDS,
+// no block reduction: the orders of E's and the pile-up's sums are not the device's)
+static double stub_loop_cell(const LoopJob& J, int q, int a, int b) {
+    const int mi = q - J.has_if;
+    if (J.has_if && q == 0) return J.band_if[(size_t)a * J.S + (b - a - J.s_lo)];
+    if (mi >= J.n_models) return J.band_cons[(size_t)a * J.S + (b - a - J.s_lo)];
+    return stub_dist(J.xyz + (size_t)J.pick[mi] * 3 * J.n, a, b);
+}
+static void stub_loop_pixel(const LoopJob& J, int q, int i, int j, double* out6) {
+    const int n = J.n, w = J.w, p = J.p;
+    const double* E = J.expected + (size_t)q * J.S;
+    const double m = stub_loop_cell(J, q, i, j), e = E[j - i - J.s_lo];
+    out6[0] = m; out6[1] = e;
+    for (int x = 0; x < 4; ++x) out6[2 + x] = std::nan("");
+    if (i < w || j + w > n - 1 || J.mask[i] || J.mask[j] || e == 0.0) return;
+    double sm[4] = {0, 0, 0, 0}, se[4] = {0, 0, 0, 0};
+    for (int a = -w; a <= w; ++a)
+        for (int b = -w; b <= w; ++b) {
+            const int ca = i + a, cb = j + b;
+            if (J.mask[ca] || J.mask[cb]) continue;
+            const bool out = std::abs(a) > p || std::abs(b) > p;
+            const bool in[4] = {out && a != 0 && b != 0, out && a >= 1 && b <= -1, std::abs(a) <= 1 && std::abs(b) > p, std::abs(b) <= 1 && std::abs(a) > p};
+            const double cm = stub_loop_cell(J, q, ca, cb), ce = E[cb - ca - J.s_lo];
+            for (int x = 0; x < 4; ++x)
+                if (in[x]) { sm[x] += cm; se[x] += ce; }
+        }
+    for (int x = 0; x < 4; ++x)
+        if (sm[x] != 0.0 && se[x] != 0.0) out6[2 + x] = m / ((sm[x] / se[x]) * e);
+}
+hipError_t launch_loop_expected(const LoopJob& J, hipStream_t) {
+    LaunchScope ls;
+    const int n = J.n;
+    for (int a = 0; J.consensus && a < n; ++a)
+        for (int col = 0; col < J.S; ++col) {
+            const int b = a + J.s_lo + col;
+            double v = 0.0;
+            for (int k = 0; b < n && k < J.n_models; ++k) v += stub_dist(J.xyz + (size_t)J.pick[k] * 3 * n, a, b);
+            J.band_cons[(size_t)a * J.S + col] = b < n ? v / (double)J.n_models : 0.0;
+        }
+    for (int q = 0; q < J.Q; ++q)
+        for (int col = 0; col < J.S; ++col) {
+            const int s = J.s_lo + col;
+            double sum = 0.0, cnt = 0.0;
+            for (int i = 0; i + s < n; ++i)
+                if (!J.mask[i] && !J.mask[i + s]) { sum += stub_loop_cell(J, q, i, i + s); cnt += 1.0; }
+            J.expected[(size_t)q * J.S + col] = cnt > 0.0 ? sum / cnt : 0.0;
+        }
+    return hipSuccess;
+}
+hipError_t launch_loop_scan(const LoopJob& J, const LoopPeakRule& rule, double* ratio, unsigned char* cand, hipStream_t) {
+    LaunchScope ls;
+    const int n = J.n, B = J.max_sep - J.min_sep + 1;
+    for (int s = J.min_sep; s <= J.max_sep; ++s)
+        for (int i = 0; i < n; ++i) {
+            double v[6] = {-1.0, 0.0, std::nan(""), std::nan(""), std::nan(""), std::nan("")};
+            if (i + s <= n - 1) stub_loop_pixel(J, 0, i, i + s, v);
+            const size_t out = (size_t)(s - J.min_sep) * n + i;
+            for (int x = 0; x < 4 && ratio; ++x) ratio[(size_t)x * B * n + out] = v[2 + x];
+            if (cand) cand[out] = v[2] >= rule.thr[0] && v[3] >= rule.thr[1] && v[4] >= rule.thr[2] && v[5] >= rule.thr[3] && v[0] >= rule.min_obs;
+        }
+    return hipSuccess;
+}
+hipError_t launch_loop_peaks(const LoopJob& J, int merge, int max_peaks, const unsigned char* cand, unsigned char* peak, int* rows, int* offset, int* peaks, int* report,
+                             hipStream_t) {
+    LaunchScope ls;
+    const int n = J.n;
+    int total[3] = {0, 0, 0};
+    for (int i = 0; i < n; ++i) {
+        int c = 0, pk = 0, lost = 0;
+        for (int s = J.min_sep; s <= J.max_sep; ++s) {
+            const size_t at = (size_t)(s - J.min_sep) * n + i;
+            const int j = i + s;
+            bool keep = cand[at] != 0;
+            for (int di = -merge; keep && di <= merge; ++di)
+                for (int dj = -merge; keep && dj <= merge; ++dj) {
+                    const int i2 = i + di, j2 = j + dj, s2 = j2 - i2;
+                    if ((di == 0 && dj == 0) || i2 < 0 || i2 >= n || s2 < J.min_sep || s2 > J.max_sep || !cand[(size_t)(s2 - J.min_sep) * n + i2]) continue;
+                    const double m = stub_loop_cell(J, 0, i, j), m2 = stub_loop_cell(J, 0, i2, j2);
+                    if (m2 > m || (m2 == m && (i2 < i || (i2 == i && j2 < j)))) keep = false;
+                }
+            peak[at] = keep;
+            c += cand[at]; pk += keep;
+            lost += i >= J.w && j + J.w <= n - 1 && (J.mask[i] || J.mask[j]);
+            if (keep && total[1] + pk - 1 < max_peaks) { peaks[2 * (total[1] + pk - 1)] = i; peaks[2 * (total[1] + pk - 1) + 1] = j; }
+        }
+        rows[3 * i] = c; rows[3 * i + 1] = pk; rows[3 * i + 2] = lost;
+        offset[i] = total[1];
+        total[0] += c; total[1] += pk; total[2] += lost;
+    }
+    report[0] = total[0]; report[1] = total[1]; report[2] = std::min(total[1], max_peaks); report[3] = total[2];
+    return hipSuccess;
+}
+hipError_t launch_loop_list(const LoopJob& J, const int* list, int L, double* at, int* closed, hipStream_t) {
+    LaunchScope ls;
+    for (int q = 0; q < J.Q; ++q) {
+        int scored = 0, shut = 0;
+        for (int l = 0; l < L; ++l) {
+            double* v = at + ((size_t)q * L + l) * 6;
+            stub_loop_pixel(J, q, list[2 * l], list[2 * l + 1], v);
+            if (std::isnan(v[2]) || std::isnan(v[3])) continue;
+            ++scored;
+            shut += J.has_if && q == 0 ? (v[2] > 1.0 && v[3] > 1.0) : (v[2] < 1.0 && v[3] < 1.0);
+        }
+        closed[2 * q] = scored; closed[2 * q + 1] = shut;
+    }
+    return hipSuccess;
+}
+hipError_t launch_loop_apa(const LoopJob& J, const int* list, int L, int corner, double* apa, double* p2ll, hipStream_t) {
+    LaunchScope ls;
+    const int n = J.n, w = J.w, side = 2 * w + 1;
+    for (int q = 0; q < J.Q; ++q) {
+        double* A = apa + (size_t)q * side * side;
+        for (int a = -w; a <= w; ++a)
+            for (int b = -w; b <= w; ++b) {
+                double sum = 0.0, cnt = 0.0;
+                for (int l = 0; l < L; ++l) {
+                    const int i = list[2 * l], j = list[2 * l + 1], ca = i + a, cb = j + b;
+                    if (i < w || j + w > n - 1 || J.mask[ca] || J.mask[cb]) continue;
+                    const double e = J.expected[(size_t)q * J.S + (cb - ca - J.s_lo)];
+                    if (e == 0.0) continue;
+                    sum += stub_loop_cell(J, q, ca, cb) / e; cnt += 1.0;
+                }
+                A[(a + w) * side + (b + w)] = cnt > 0.0 ? sum / cnt : std::nan("");
+            }
+        double sum = 0.0;
+        for (int a = w - corner + 1; a <= w; ++a)
+            for (int b = -w; b <= -w + corner - 1; ++b) sum += A[(a + w) * side + (b + w)];
+        p2ll[q] = A[w * side + w] / (sum / (double)(corner * corner));
+    }
+    return hipSuccess;
+}
+
 // c3d_balance_matrix: the three launchers restated on the host with plain loops in index order (the definitions of include/c3d.h; no
 // tiles, no column pairs, no block reduction: the sums' orders are not the device's)
 hipError_t launch_balance_count(const BalJob& J, hipStream_t) {
