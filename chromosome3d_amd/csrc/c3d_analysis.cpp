@@ -1,6 +1,6 @@
 // c3d_analysis.cpp — host unit of libc3d.so: the output side.  What a run's models are worth and how they relate, from the coordinates
 // resident on the device (kernels: c3d_score.hip): c3d_score_replicas, c3d_compare_replicas, c3d_superpose_replicas, c3d_rmsd_table,
-// c3d_ensemble_map, c3d_ensemble_score, c3d_geometry_replicas, c3d_separation_profile, c3d_stratified_score, c3d_bead_scores, c3d_accessibility (with the host-only c3d_sphere_points), c3d_compartments (with the host-only c3d_compartment_start), c3d_insulation, c3d_loops, the input side's c3d_balance_matrix and the test hooks c3d_debug_if_ranks / c3d_debug_distance_ranks.  What they share comes first: typed
+// c3d_ensemble_map, c3d_ensemble_score, c3d_geometry_replicas, c3d_separation_profile, c3d_stratified_score, c3d_bead_scores, c3d_accessibility (with the host-only c3d_sphere_points), c3d_compartments (with the host-only c3d_compartment_start), c3d_insulation, c3d_loops, c3d_entanglement, the input side's c3d_balance_matrix and the test hooks c3d_debug_if_ranks / c3d_debug_distance_ranks.  What they share comes first: typed
 // scratch slots (Slot, Block, Carve, CallScratch), the ranker (rank_matrix) and the models of a call (model_set_check, model_set_coords, gather_models).
 #include <limits>
 
@@ -1375,6 +1375,77 @@ extern "C" int c3d_loops(c3d_ctx* c, const double* IF, const double* extra_xyz, 
     HIP_TRY(hipEventRecord(ev.e[1], c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (report) std::copy(rep, rep + C3D_LOOP_REPORT, report);
+    if (device_ms) {
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+        *device_ms = ms;
+    }
+    return C3D_OK;
+}
+
+// ---- entanglement: writhe, average crossing number, linking (c3d_score.hip k_ent_*) ----
+// c3d_entanglement's one allocation: the models, per segment the two row sums, per model the two totals, and when a table is asked for the
+// bounds and the two K x D x D tables
+struct EntangleScratch : Carve {
+    Slot<double> xyz, seg_writhe, seg_acn, writhe, acn, link, link_abs;
+    Slot<int32_t> bounds;
+    EntangleScratch(int n, int K, int D) {
+        xyz = take<double>(3 * (size_t)n * K);
+        seg_writhe = take<double>((size_t)(n - 1) * K);
+        seg_acn = take<double>((size_t)(n - 1) * K);
+        writhe = take<double>((size_t)K);
+        acn = take<double>((size_t)K);
+        if (D > 0) {
+            bounds = take<int32_t>((size_t)D + 1);
+            link = take<double>((size_t)D * D * K);
+            link_abs = take<double>((size_t)D * D * K);
+        }
+    }
+};
+
+extern "C" int c3d_entanglement(c3d_ctx* c, const double* extra_xyz, int n_extra, int min_sep, int max_sep, const int32_t* bounds, int n_domains, double* writhe,
+                                double* acn, double* seg_writhe, double* seg_acn, double* link, double* link_abs, double* device_ms) {
+    const char* const who = "c3d_entanglement";
+    if (int rc = model_set_check(c, who, 4, "no pair of segments that is not adjacent", extra_xyz, n_extra)) return rc;
+    const int n = c->n, K = c->nrep + n_extra, S = n - 1;
+    if (!writhe && !acn && !seg_writhe && !seg_acn && !link && !link_abs) return fail(C3D_ERR_INVALID, "c3d_entanglement: every output is NULL");
+    if (min_sep < 2 || min_sep > S - 1) return fail(C3D_ERR_INVALID, "c3d_entanglement: min_sep outside 2..S-1 (S = n-1 segments)");
+    if (max_sep < 0 || max_sep > S - 1 || (max_sep > 0 && max_sep < min_sep)) return fail(C3D_ERR_INVALID, "c3d_entanglement: max_sep is 0 (for S-1) or in min_sep..S-1");
+    const bool table = link || link_abs;
+    if (table) {
+        if (!bounds) return fail(C3D_ERR_INVALID, "c3d_entanglement: a domain table needs bounds");
+        if (n_domains < 1 || n_domains > C3D_ENTANGLE_MAX_DOMAINS) return fail(C3D_ERR_INVALID, "c3d_entanglement: n_domains outside 1..C3D_ENTANGLE_MAX_DOMAINS");
+        if (bounds[0] != 0 || bounds[n_domains] != S) return fail(C3D_ERR_INVALID, "c3d_entanglement: bounds do not run from 0 to S");
+        for (int p = 0; p < n_domains; ++p)
+            if (bounds[p + 1] <= bounds[p]) return fail(C3D_ERR_INVALID, "c3d_entanglement: bounds are not strictly increasing");
+    }
+    if (int rc = model_set_coords(c, who, extra_xyz, n_extra)) return rc;
+    const int D = table ? n_domains : 0, hi = max_sep == 0 ? S - 1 : max_sep;
+    C3D_ENTRY(c, unit_bit(UNIT_SCORE));
+    const EntangleScratch L(n, K, D);
+    CallScratch tmp;
+    if (int rc = tmp.alloc(L.total, who)) return rc;
+    PassEvents ev;
+    for (int k = 0; k < 2; ++k) HIP_TRY(hipEventCreate(&ev.e[k]));
+    double* const d_xyz = L.xyz.at(tmp.p);
+    HIP_TRY(hipEventRecord(ev.e[0], c->stream));
+    if (int rc = gather_models(c, ModelSource::STATE, 0, c->nrep, d_xyz, extra_xyz, n_extra, "entanglement launch")) return rc;
+    if (writhe || acn || seg_writhe || seg_acn)
+        LAUNCH_TRY("entanglement launch", c3d::launch_entangle_rows(d_xyz, n, K, min_sep, hi, L.seg_writhe.at(tmp.p), L.seg_acn.at(tmp.p), L.writhe.at(tmp.p),
+                                                                     L.acn.at(tmp.p), c->stream));
+    if (table) {
+        HIP_TRY(hipMemcpyAsync(L.bounds.at(tmp.p), bounds, L.bounds.bytes(), hipMemcpyHostToDevice, c->stream));
+        LAUNCH_TRY("entanglement launch", c3d::launch_entangle_table(d_xyz, n, K, min_sep, hi, L.bounds.at(tmp.p), D, L.link.at(tmp.p), L.link_abs.at(tmp.p), c->stream));
+    }
+    // straight into the caller's arrays, as c3d_geometry_replicas copies its per-bead ones
+    if (writhe) HIP_TRY(hipMemcpyAsync(writhe, L.writhe.at(tmp.p), L.writhe.bytes(), hipMemcpyDeviceToHost, c->stream));
+    if (acn) HIP_TRY(hipMemcpyAsync(acn, L.acn.at(tmp.p), L.acn.bytes(), hipMemcpyDeviceToHost, c->stream));
+    if (seg_writhe) HIP_TRY(hipMemcpyAsync(seg_writhe, L.seg_writhe.at(tmp.p), L.seg_writhe.bytes(), hipMemcpyDeviceToHost, c->stream));
+    if (seg_acn) HIP_TRY(hipMemcpyAsync(seg_acn, L.seg_acn.at(tmp.p), L.seg_acn.bytes(), hipMemcpyDeviceToHost, c->stream));
+    if (link) HIP_TRY(hipMemcpyAsync(link, L.link.at(tmp.p), L.link.bytes(), hipMemcpyDeviceToHost, c->stream));
+    if (link_abs) HIP_TRY(hipMemcpyAsync(link_abs, L.link_abs.at(tmp.p), L.link_abs.bytes(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipEventRecord(ev.e[1], c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     if (device_ms) {
         float ms = 0;
         HIP_TRY(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));

@@ -624,6 +624,15 @@ hipError_t launch_loop_peaks(const LoopJob& job, int merge, int max_peaks, const
                              hipStream_t s);
 hipError_t launch_loop_list(const LoopJob& job, const int* list, int L, double* at, int* closed, hipStream_t s);
 hipError_t launch_loop_apa(const LoopJob& job, const int* list, int L, int corner, double* apa, double* p2ll, hipStream_t s);
+// Entanglement of a model (c3d_entanglement; k_ent_*, c3d_score_entangle.inc).  xyz: K models of n x 3 doubles on the device; S = n - 1
+// segments; a pair of segments is counted when min_sep <= |s - t| <= max_sep (max_sep already resolved: never 0 here).
+// launch_entangle_rows: seg_writhe, seg_acn (K x S) = a segment's sums of g and |g| over its counted partners, writhe, acn (K) = their sums.
+// launch_entangle_table: link, link_abs (K x D x D) = the sums over the pairs of domain p with domain q, domains the runs
+// bounds[p] .. bounds[p+1] - 1 (bounds: D + 1 ints on the device); (p, q) and (q, p) hold the same bits.
+hipError_t launch_entangle_rows(const double* xyz, int n, int K, int min_sep, int max_sep, double* seg_writhe, double* seg_acn, double* writhe, double* acn,
+                                hipStream_t s);
+hipError_t launch_entangle_table(const double* xyz, int n, int K, int min_sep, int max_sep, const int* bounds, int D, double* link, double* link_abs,
+                                 hipStream_t s);
 
 // Target matrix entry: NOE target in Angstrom, 0 = no restraint (host c3d_set_restraints and K1).
 inline float encode_target_host(float t) { return t > 0 ? t : 0.0f; }

@@ -37,6 +37,8 @@
 //                             a round, the stop decided on the device (c3d_balance_matrix)
 //   c3d_score_loop.inc        k_loop_*   loop enrichment: a pixel's four local-background ratios out of one walk over its window, IF's tiles
 //                             staged in LDS, peaks by exact suppression, listed pixels in every map and their pile-up (c3d_loops)
+//   c3d_score_entangle.inc    k_ent_*    entanglement: the Gauss integral of every pair of chain segments as two atan2, summed a segment, a
+//                             model and a pair of domains — writhe, average crossing number, linking (c3d_entanglement)
 #include "c3d_score_core.h"
 
 namespace c3d {
@@ -277,6 +279,7 @@ hipError_t launch_if_rank_sort(double* M, int n, int range, unsigned long long* 
 #include "c3d_score_insulation.inc"
 #include "c3d_score_balance.inc"
 #include "c3d_score_loop.inc"
+#include "c3d_score_entangle.inc"
 
 // loads the unit's code object on the current device and gives the k_str_* and k_bead_* kernels their dynamic-LDS allowance (c3d_gate.cpp "code objects":
 // once per device, never beside a launch)

@@ -22,6 +22,9 @@
 //   --loops <prefix> writes <prefix>_loops.txt — the peaks of IF with their local-background ratios, and whether the models close them
 //   --insulation <prefix> writes <prefix>_insulation.txt — the insulation profile and the domain boundaries of IF and of the models' consensus
 //       map per window, how many models place a boundary at each bead, and how well every model's profile fits IF's
+//   --entanglement <prefix> writes <prefix>_entanglement.txt — per model the writhe and the average crossing number of the chain (Gauss
+//       integrals) with the ensemble's mean, sd and sign agreement — and <prefix>_segments.txt, every segment's share; with --entangle-bounds
+//       also <prefix>_link.txt, the linking table of the given domains
 //   --balance <ice|vc|sqrt-vc> balances the matrix of --if on the device first (raw contact counts in, a normalised matrix out): the solve and
 //       every analysis option of the run use the balanced matrix; --balance-out <prefix> writes the weights and the matrix
 //
@@ -123,6 +126,14 @@ static void usage() {
             "                 [--loop-sep <MIN:MAX>   separations j - i that are scanned; default 2w+1 : min(n-1, 2w+1024)]\n"
             "                 [--loop-thr <a,b,c,d>   least ratio against the donut, lower-left, horizontal and vertical background; default 1.75,1.75,1.5,1.5]\n"
             "                 [--loop-list <FILE>   score these pixels (lines `i j`, beads from 1) instead of the peaks of IF]\n"
+            "                 [--entanglement <prefix>   how entangled are the models, and with which handedness?  Gauss integrals over the chain, on the device.\n"
+            "                                          <prefix>_entanglement.txt: one row per model in rank order, `rank model writhe acn acn_per_segment`, under a header\n"
+            "                                          with the writhe's mean, sd and sign agreement over the models; <prefix>_segments.txt: `model segment seg_writhe seg_acn`\n"
+            "                                          (segment s joins beads s and s+1, from 1)]\n"
+            "                 [--entangle-sep <a:b>   the segment pairs that count: a <= |s-t| <= b, a >= 2; b = 0: all; default 2:0.  A small b gives the local writhe]\n"
+            "                 [--entangle-bounds <FILE>   domain bounds in segments, ascending whole numbers from 0 to n-1 separated by white space; adds\n"
+            "                                          <prefix>_link.txt: `model p q link link_abs` for p <= q (the Gauss linking integral of domains p and q, from 1;\n"
+            "                                          p = q: the domain's own writhe)]\n"
             "                 [--balance <ice|vc|sqrt-vc>   the matrix of --if holds raw contact counts: balance it on the device first (iterative correction, vanilla\n"
             "                                          coverage or its square root); the solve and every analysis option of the run use the balanced matrix.  Bins that\n"
             "                                          cannot be balanced get weight 0 and no restraints]\n"
@@ -169,6 +180,7 @@ int main(int argc, char** argv) {
     int insulation_tol = 1;
     std::string loops_prefix, loop_sep, loop_thr = "1.75,1.75,1.5,1.5", loop_list;
     int loop_window = 5, loop_peak = 2;
+    std::string entanglement_prefix, entangle_sep, entangle_bounds;
     std::string balance_method, balance_out;          // empty: the matrix of --if is taken as it is
     int balance_ignore_diags = 2, balance_min_nnz = 10, balance_iters = 200;
     double balance_tol = 1e-5;
@@ -231,6 +243,9 @@ int main(int argc, char** argv) {
         else if (s == "--insulation-windows") { insulation_windows = next("--insulation-windows"); insulation_windows_given = true; }
         else if (s == "--insulation-contact") insulation_contact = atof(next("--insulation-contact"));
         else if (s == "--insulation-tol") insulation_tol = atoi(next("--insulation-tol"));
+        else if (s == "--entanglement") entanglement_prefix = next("--entanglement");   // writhe, average crossing number, linking (c3d_entanglement)
+        else if (s == "--entangle-sep") entangle_sep = next("--entangle-sep");
+        else if (s == "--entangle-bounds") entangle_bounds = next("--entangle-bounds");
         else if (s == "--loops") loops_prefix = next("--loops");                  // loop enrichment of IF and the models (c3d_loops)
         else if (s == "--loop-window") loop_window = atoi(next("--loop-window"));
         else if (s == "--loop-peak") loop_peak = atoi(next("--loop-peak"));
@@ -711,6 +726,64 @@ int main(int argc, char** argv) {
             fprintf(f, " %d %d %.4f\n", closed[2 * q], closed[2 * q + 1], p2ll[q]);
         }
         fclose(f);
+    }
+    if (!entanglement_prefix.empty()) {
+        std::vector<int32_t> order(models), bounds;
+        CHECK(c3d_rank(ctx, order.data()));
+        const int S = n - 1;
+        int lo = 2, hi = 0;
+        if (!entangle_sep.empty() && sscanf(entangle_sep.c_str(), "%d:%d", &lo, &hi) != 2) { fprintf(stderr, "c3d_solve: --entangle-sep takes a:b\n"); return fail_exit(out_dir); }
+        if (!entangle_bounds.empty()) {
+            FILE* bf = fopen(entangle_bounds.c_str(), "r");
+            if (!bf) { fprintf(stderr, "c3d_solve: cannot read %s\n", entangle_bounds.c_str()); return fail_exit(out_dir); }
+            int v;
+            while (fscanf(bf, "%d", &v) == 1 && bounds.size() <= (size_t)C3D_ENTANGLE_MAX_DOMAINS + 1) bounds.push_back(v);
+            const bool whole = feof(bf) != 0;
+            fclose(bf);
+            if (!whole || bounds.size() < 2) { fprintf(stderr, "c3d_solve: --entangle-bounds %s: not a list of 2 to %d whole numbers\n", entangle_bounds.c_str(), C3D_ENTANGLE_MAX_DOMAINS + 1); return fail_exit(out_dir); }
+        }
+        const int D = bounds.empty() ? 0 : (int)bounds.size() - 1;
+        std::vector<double> writhe(models), acn(models), seg_w((size_t)models * S), seg_a((size_t)models * S), link((size_t)models * D * D), link_abs((size_t)models * D * D);
+        CHECK(c3d_entanglement(ctx, nullptr, 0, lo, hi, D ? bounds.data() : nullptr, D, writhe.data(), acn.data(), seg_w.data(), seg_a.data(), D ? link.data() : nullptr,
+                               D ? link_abs.data() : nullptr, nullptr));
+        double mean = 0, var = 0;
+        for (int k = 0; k < models; ++k) mean += writhe[k];
+        mean /= models;
+        int agree = 0;
+        for (int k = 0; k < models; ++k) { var += (writhe[k] - mean) * (writhe[k] - mean); agree += (writhe[k] > 0) == (mean > 0) && (writhe[k] < 0) == (mean < 0); }
+        std::string path = entanglement_prefix + "_entanglement.txt";
+        FILE* f = fopen(path.c_str(), "w");
+        if (!f) { fprintf(stderr, "c3d_solve: cannot write %s\n", path.c_str()); return fail_exit(out_dir); }
+        fprintf(f, "# rank model writhe acn acn_per_segment   (%d segments, separations %d..%d; writhe mean %.6f sd %.6f, sign agreement %.3f; model r is %s_<r>.pdb)\n", S, lo,
+                hi ? hi : S - 1, mean, std::sqrt(var / models), (double)agree / models, id.c_str());
+        for (int k = 0; k < models; ++k) {
+            const int r = order[k];
+            fprintf(f, "%d %u %.9f %.9f %.9f\n", k + 1, first_rep + (unsigned)r + 1u, writhe[r], acn[r], acn[r] / S);
+        }
+        fclose(f);
+        path = entanglement_prefix + "_segments.txt";
+        f = fopen(path.c_str(), "w");
+        if (!f) { fprintf(stderr, "c3d_solve: cannot write %s\n", path.c_str()); return fail_exit(out_dir); }
+        fprintf(f, "# model segment seg_writhe seg_acn   (models in rank order; segment s joins beads s and s+1)\n");
+        for (int k = 0; k < models; ++k)
+            for (int s = 0; s < S; ++s)
+                fprintf(f, "%u %d %.9f %.9f\n", first_rep + (unsigned)order[k] + 1u, s + 1, seg_w[(size_t)order[k] * S + s], seg_a[(size_t)order[k] * S + s]);
+        fclose(f);
+        if (D) {
+            path = entanglement_prefix + "_link.txt";
+            f = fopen(path.c_str(), "w");
+            if (!f) { fprintf(stderr, "c3d_solve: cannot write %s\n", path.c_str()); return fail_exit(out_dir); }
+            fprintf(f, "# model p q link link_abs   (%d domains of segments, bounds", D);
+            for (int v : bounds) fprintf(f, " %d", v);
+            fprintf(f, "; p = q: the domain's own writhe)\n");
+            for (int k = 0; k < models; ++k)
+                for (int p = 0; p < D; ++p)
+                    for (int q = p; q < D; ++q) {
+                        const size_t o = ((size_t)order[k] * D + p) * D + q;
+                        fprintf(f, "%u %d %d %.9f %.9f\n", first_rep + (unsigned)order[k] + 1u, p + 1, q + 1, link[o], link_abs[o]);
+                    }
+            fclose(f);
+        }
     }
     double ms = 0;
     long steps = 0, launches = 0;

@@ -102,6 +102,7 @@ SIGNATURES = {
     "c3d_compartments": (_i, [_vp, _dp, _dp, _i, _i32p, _i, _i, _i, _i, _i, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "c3d_insulation": (_i, [_vp, _dp, _dp, _i, _i32p, _i, _i, _i32p, _i, _d, _d, _i, _dp, _dp, _i32p, _dp, _dp, _i32p, _dp]),
     "c3d_loops": (_i, [_vp, _dp, _dp, _i, _i32p, _i, _i, _i32p, _i, _i, _i, _i, _dp, _d, _i, _i, _i32p, _i, _i, _dp, _dp, _i32p, _i32p, _dp, _i32p, _dp, _dp, _dp]),
+    "c3d_entanglement": (_i, [_vp, _dp, _i, _i, _i, _i32p, _i, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "c3d_balance_matrix": (_i, [_vp, _dp, _i, _i, _i, _i, _i, _i32p, _dp, _d, _i, _d, _dp, _i32p, _dp, _dp, _dp, _dp]),
     "c3d_rank": (_i, [_vp, _i32p]),
     "c3d_reduce_model": (_i, [_dp, _i, _dp]),
@@ -130,6 +131,7 @@ INSULATION_MAX_WINDOW, INSULATION_MAX_WINDOWS = 128, 8                          
 INSULATION_CONSENSUS, INSULATION_CONTACT, INSULATION_STAGE = 1, 2, 4                    # C3D_INSULATION_* (flags)
 LOOP_MAX_WINDOW, LOOP_MAX_BAND, LOOP_MAX_LIST, LOOP_REPORT = 20, 1024, 65536, 4               # C3D_LOOP_*
 LOOP_CONSENSUS, LOOP_IF_ONLY = 1, 2                                                     # C3D_LOOP_* (flags)
+ENTANGLE_MAX_DOMAINS = 256                                                              # C3D_ENTANGLE_MAX_DOMAINS
 BALANCE_ICE, BALANCE_VC, BALANCE_SQRT_VC = 0, 1, 2                                      # C3D_BALANCE_* (methods)
 BALANCE_CHECK_EVERY_ROUND, BALANCE_MAX_ITERS, BALANCE_REPORT = 1, 10000, 8             # C3D_BALANCE_*
 LBFGS_MAX_PAIRS, LBFGS_SUMS, LBFGS_STATE_DOUBLES, LBFGS_COEFS = 8, 36, 129, 17      # C3D_LBFGS_*

@@ -306,6 +306,28 @@ def loop_report(solver, IF, extra=None, pick=None, mask=None, pixels=None, **kw)
     return out
 
 
+def entanglement_report(solver, extra=None, min_sep=2, max_sep=0, bounds=None):
+    """How entangled are the models, and do they agree in it?  Solver.entanglement's dict with "order" — the replicas in rank order
+    (Solver.rank), then the extra models — "acn_per_segment" [K], "writhe_mean" and "writhe_sd" (population) over the models,
+    "sign_agreement" — the share of models whose writhe has the sign of the mean — and "text": one row per model in that order
+    (model number from 1, writhe, ACN, ACN per segment) under a header line with the ensemble's figures."""
+    out = solver.entanglement(extra, min_sep, max_sep, bounds)
+    K = len(out["writhe"])
+    order = [int(k) for k in solver.rank()] + list(range(solver.nrep, K))
+    S = solver.n - 1
+    w = out["writhe"]
+    out["order"] = np.array(order, dtype=np.int32)
+    out["acn_per_segment"] = out["acn"] / S
+    out["writhe_mean"], out["writhe_sd"] = float(w.mean()), float(w.std())
+    out["sign_agreement"] = float((np.sign(w) == np.sign(out["writhe_mean"])).mean())
+    lines = ["# model writhe acn acn_per_segment   (%d models of %d segments, separations %d..%d; writhe mean %.6f sd %.6f, sign agreement %.3f)"
+             % (K, S, min_sep, max_sep if max_sep else S - 1, out["writhe_mean"], out["writhe_sd"], out["sign_agreement"])]
+    for k in order:
+        lines.append("%d %.9f %.9f %.9f" % (k + 1, w[k], out["acn"][k], out["acn_per_segment"][k]))
+    out["text"] = "\n".join(lines) + "\n"
+    return out
+
+
 def balance_if(path_or_matrix, solver=None, device=0, **kw):
     """A raw contact matrix (a path in the text format of parse_if_file, or an array) balanced on the device and ready for set_if_matrix:
     Solver.balance's "balanced", rows of bins that cannot be balanced all 0 (set_if_matrix reads 0 as no restraint).  kw: the arguments of

@@ -656,6 +656,33 @@ class Solver:
         out["device_ms"] = ms.value
         return out
 
+    def entanglement(self, extra=None, min_sep=2, max_sep=0, bounds=None, segments=True):
+        """How entangled are the models, and with which handedness?  A dict of arrays over the K models of compare() — the replicas at
+        their current coordinates (precision 64: the fp64 state), then `extra` [E, n, 3] — from the Gauss double integrals over the
+        chain's S = n - 1 segments, on the device (c3d_entanglement): "writhe" [K] and "acn" [K] (the average crossing number), the sums
+        of the pair term g and of |g| over the ordered segment pairs min_sep <= |s - t| <= max_sep (0: S - 1); with segments=True
+        "seg_writhe" and "seg_acn" [K, S], every segment's share; with bounds [D + 1] (0 = bounds[0] < ... < bounds[D] = S: D domains
+        of consecutive segments) "link" and "link_abs" [K, D, D]: off the diagonal the Gauss linking integral of two domains, on it a
+        domain's own writhe, symmetric bit for bit; "device_ms".  A small max_sep gives the local writhe: chirality at that scale.
+        Mirroring a model negates the signed outputs exactly.  Nothing of the solve changes."""
+        xptr, E = self._extra_models(extra)
+        K, S = self.nrep + E, self.n - 1
+        out = {"writhe": np.empty(K, dtype=np.float64), "acn": np.empty(K, dtype=np.float64)}
+        if segments:
+            out["seg_writhe"], out["seg_acn"] = np.empty((K, S), dtype=np.float64), np.empty((K, S), dtype=np.float64)
+        b, D = None, 0
+        if bounds is not None:
+            b = np.ascontiguousarray(bounds, dtype=np.int32).reshape(-1)
+            D = len(b) - 1
+            if D >= 1:
+                out["link"], out["link_abs"] = np.empty((K, D, D), dtype=np.float64), np.empty((K, D, D), dtype=np.float64)
+        ptr = lambda k: _l.dptr(out[k]) if k in out else None
+        ms = C.c_double()
+        _l.check(self._L.c3d_entanglement(self._h, xptr, E, int(min_sep), int(max_sep), _l.i32ptr(b) if b is not None else None, D, ptr("writhe"), ptr("acn"),
+                                          ptr("seg_writhe"), ptr("seg_acn"), ptr("link"), ptr("link_abs"), C.byref(ms)))
+        out["device_ms"] = ms.value
+        return out
+
     def balance(self, M, method="ice", ignore_diags=2, min_nnz=10, mask=None, w0=None, tol=1e-5, max_iters=200, target=1.0, want_matrix=True,
                 check_every_round=False):
         """A raw contact matrix balanced on the device (c3d_balance_matrix): M [n, n], symmetric, finite, >= 0, n up to the context's

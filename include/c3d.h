@@ -947,6 +947,58 @@ int c3d_loops(c3d_ctx* ctx, const double* IF, const double* extra_xyz, int n_ext
               const int32_t* list_in, int n_list, int max_peaks,
               double* expected, double* ratio, int32_t* peaks, int32_t* report,
               double* at, int32_t* closed, double* apa, double* p2ll, double* device_ms);
+/* Entanglement of the models on the device (c3d_score_entangle.inc k_ent_*): writhe, average crossing number and linking.  Every other
+ * analysis entry measures a model through its distances, which are blind to handedness and to topology: a mirror pair has the same
+ * distance map and opposite chirality at every scale, and the annealer, whose only repulsion is the soft k_rep term, passes beads through
+ * one another at high temperature, so the replicas of a run are where the topology varies.  The measures are the Gauss double integrals
+ * over the chain.  No state of the solve changes.
+ * Models and segments.  The models are K = n_replicas + n_extra, numbered, taken and checked exactly as c3d_geometry_replicas takes them:
+ * on a precision-64 context the fp64 state bit for bit, else the floats widened; extra models are n x 3 doubles.  A model of n beads has
+ * S = n - 1 segments, segment s joins beads s and s+1; the entry needs n >= 4.
+ * The pair term g(s,t) of segments s != t of one model with bead positions x:
+ *     a = x[t]   - x[s]        c = x[t+1] - x[s]
+ *     d = x[t]   - x[s+1]      b = x[t+1] - x[s+1]
+ *     T(u,v,w) = 2 atan2( u.(v x w),  |u||v||w| + (u.v)|w| + (u.w)|v| + (v.w)|u| )
+ *     g(s,t)   = ( T(a,b,c) + T(a,d,b) ) / (4 pi)
+ * the Van Oosterom-Strackee signed solid angle of the planar parallelogram {p_t - p_s} spanned by the two segments, seen from the origin,
+ * split into two triangles of the same orientation: exact for straight segments, equal to
+ * (1/4 pi) of the double integral of (r_s - r_t).(dr_s x dr_t)/|r_s - r_t|^3, and with the integral's sign (a right-handed helix is
+ * positive).  A triangle with numerator 0 and denominator 0 contributes 0 (coincident beads are one such case).  g(s,t) := 0 for
+ * |s - t| <= 1: adjacent segments are coplanar.  The device forms the two numerators as c.(a x b) and -(d.(a x b)), the same triple
+ * products turned, and divides a sum by 2 pi once at its end; a bead-to-bead length is sqrt(((ux ux) + uy uy) + uz uz).
+ * Counted pairs.  (s,t) is counted iff min_sep <= |s-t| <= max_sep, 2 <= min_sep <= S-1; max_sep = 0 means S-1, otherwise
+ * min_sep <= max_sep <= S-1.  A small max_sep gives the local writhe: chirality at that scale.
+ * Outputs; any may be NULL, but not all of them.  C(s) is the set of t for which (s,t) is counted.
+ *     seg_writhe[k S + s] = sum over t in C(s) of g_k(s,t)          seg_acn[k S + s] = the same sum of |g_k(s,t)|
+ *     writhe[k] = sum over s of seg_writhe[k S + s], which is 2 sum_{s<t} g: the writhe of the open chain
+ *     acn[k]    = the same sum over seg_acn: the average crossing number
+ *     link[(k D + p) D + q] = sum over s in domain p, t in domain q, (s,t) counted, of g_k(s,t)       link_abs[...] = the same sum of |g|
+ * Domains are D = n_domains consecutive runs of segments given by bounds[0..D], strictly increasing with bounds[0] = 0 and
+ * bounds[D] = S; domain p is the segments bounds[p] .. bounds[p+1]-1; 1 <= D <= C3D_ENTANGLE_MAX_DOMAINS.  bounds == NULL is allowed
+ * only if link and link_abs are NULL too.  Off the diagonal `link` is the Gauss linking integral of the two sub-chains (two closed,
+ * once-linked rings joined into one chain give +-1 in their block), on the diagonal the domain's own writhe; the entries of a model's
+ * table sum to writhe[k] up to rounding.  g(s,t) and g(t,s) agree to rounding only, so every entry is taken from the p <= q side — s in
+ * domain p — and copied across: the table is symmetric bit for bit.  The natural bounds are the boundaries c3d_insulation reports.  The
+ * table costs one more evaluation of every counted pair with p <= q, a workgroup a block: its time is set by the largest block.
+ * `ms`, if not NULL, receives the device time of the call in milliseconds, as c3d_loops reports it.
+ * Guarantees.  No floating-point atomics; every sum has an order that follows from n, min_sep, max_sep and bounds alone: a thread adds
+ * its pairs in the order of its walk, the sixteen threads of a row segment meet in index order, a model's S row sums and a block's
+ * partial sums meet in the fixed tree.  Two calls on the same state return the same bits; extra models leave the replicas' entries
+ * their bits.  Mirroring a model (one coordinate negated) negates seg_writhe, writhe and link exactly and leaves the acn outputs' bits:
+ * numerators negate, denominators keep their bits.
+ * C3D_ERR_INVALID, before any launch: the refusals of c3d_geometry_replicas that apply (no context, no replicas, n_extra < 0 or extra
+ * models without coordinates, K > C3D_COMPARE_MAX_MODELS, extra coordinates that are not finite or have |x| >= 1e6), n < 4, min_sep or
+ * max_sep out of range, every output NULL, n_domains outside 1..C3D_ENTANGLE_MAX_DOMAINS when a table is asked for, bad bounds,
+ * bounds == NULL with a table asked for.  C3D_ERR_NOMEM: no device memory for the scratch, one allocation per call, freed before it
+ * returns: 24 n K of coordinates + 16 S K of row sums + 16 K + 16 D D K + 4 (D + 1) bytes.  The entry keeps no stat key.
+ * Measured on an MI355X (profiles/r34_entanglement.md, tools/entanglement.py; the entry's ms): 455 x 20: 0.19 ms, with a 64-domain table
+ * 0.42 ms; 16384 x 20: 58 ms for 5.4e9 ordered segment pairs, 9.2e10 pairs/s, bound by the two atan2 of a pair; with the table 97 ms;
+ * the numpy restatement on the same host: 0.9 s and about 7 minutes (scaled). */
+#define C3D_ENTANGLE_MAX_DOMAINS 256
+int c3d_entanglement(c3d_ctx* ctx, const double* extra_xyz, int n_extra, int min_sep, int max_sep,
+                     const int32_t* bounds, int n_domains,
+                     double* writhe, double* acn, double* seg_writhe, double* seg_acn,
+                     double* link, double* link_abs, double* ms);
 /* Balancing a raw contact matrix on the device (c3d_score_balance.inc k_bal_*): the input side.  c3d_set_if_matrix expects a normalised
  * matrix; this entry turns raw contact counts into one by iterative correction (ICE), vanilla coverage (VC) or its square root (sqrt-VC).
  * It needs a context, but no targets and no replicas, and changes no state of the solve.  Bins that cannot be balanced get weight 0, so

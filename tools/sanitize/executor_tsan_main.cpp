@@ -146,6 +146,14 @@ static void api_storm(int device_count) {
                                      lat.data(), lclosed.data(), lapa.data(), lp2.data(), nullptr) == C3D_OK && lclosed[0] <= 2;
                 ok = ok && c3d_loops(c, nullptr, nullptr, 0, picked, 3, 0, nullptr, 2, 2, 5, 20, nullptr, 0.0, 0, 1, lpix, 2, 0, nullptr, nullptr, nullptr, nullptr,
                                      lat.data(), nullptr, nullptr, nullptr, nullptr) == C3D_ERR_INVALID;
+                // (4 models of n - 1 segments, three domains; then a window that cuts the chain short; then bounds that do not end at S)
+                const int32_t ebounds[4] = {0, 7, 8, n - 1}, ebad[4] = {0, 7, 8, n};
+                std::vector<double> ewr(4), eacn(4), eseg(2 * 4 * (size_t)(n - 1)), elink(2 * 4 * 9);
+                double ent_ms = -1;
+                ok = ok && c3d_entanglement(c, nullptr, 0, 2, 0, ebounds, 3, ewr.data(), eacn.data(), eseg.data(), eseg.data() + 4 * (size_t)(n - 1), elink.data(),
+                                            elink.data() + 4 * 9, &ent_ms) == C3D_OK && ent_ms >= 0 && elink[1] == elink[3];
+                ok = ok && c3d_entanglement(c, nullptr, 0, 3, 10, nullptr, 0, ewr.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) == C3D_OK;
+                ok = ok && c3d_entanglement(c, nullptr, 0, 2, 0, ebad, 3, nullptr, nullptr, nullptr, nullptr, elink.data(), nullptr, nullptr) == C3D_ERR_INVALID;
                 // (the raw matrix: IF itself, an odd and an even n over the threads; bin 1 masked by the caller)
                 std::vector<double> bw(n), bbal((size_t)n * n), bhist(51), brep(C3D_BALANCE_REPORT);
                 std::vector<int32_t> bmask(n, 0), bcode(n);

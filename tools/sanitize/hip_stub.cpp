@@ -983,4 +983,69 @@ hipError_t launch_balance_apply(const BalJob& J, double target, bool matrix, hip
     return hipSuccess;
 }
 
+// c3d_entanglement: the two launchers restated on the host with plain loops in index order (include/c3d.h; no tiles, no LDS)
+static double stub_half_angle(const double* u, const double* v, const double* w) {
+    const double nu = sqrt(((u[0] * u[0]) + u[1] * u[1]) + u[2] * u[2]), nv = sqrt(((v[0] * v[0]) + v[1] * v[1]) + v[2] * v[2]),
+                 nw = sqrt(((w[0] * w[0]) + w[1] * w[1]) + w[2] * w[2]);
+    const double num = u[0] * (v[1] * w[2] - v[2] * w[1]) + u[1] * (v[2] * w[0] - v[0] * w[2]) + u[2] * (v[0] * w[1] - v[1] * w[0]);
+    const double den = nu * nv * nw + (u[0] * v[0] + u[1] * v[1] + u[2] * v[2]) * nw + (u[0] * w[0] + u[1] * w[1] + u[2] * w[2]) * nv +
+                       (v[0] * w[0] + v[1] * w[1] + v[2] * w[2]) * nu;
+    return num == 0.0 && den == 0.0 ? 0.0 : atan2(num, den);
+}
+// 2 pi g(s, t)
+static double stub_ent_pair(const double* x, int s, int t) {
+    double a[3], b[3], c[3], d[3];
+    for (int q = 0; q < 3; ++q) {
+        a[q] = x[3 * t + q] - x[3 * s + q]; c[q] = x[3 * (t + 1) + q] - x[3 * s + q];
+        d[q] = x[3 * t + q] - x[3 * (s + 1) + q]; b[q] = x[3 * (t + 1) + q] - x[3 * (s + 1) + q];
+    }
+    return stub_half_angle(a, b, c) + stub_half_angle(a, d, b);
+}
+hipError_t launch_entangle_rows(const double* xyz, int n, int K, int min_sep, int max_sep, double* seg_writhe, double* seg_acn, double* writhe, double* acn,
+                                hipStream_t) {
+    LaunchScope ls;
+    const int S = n - 1;
+    const double two_pi = 2.0 * M_PI;
+    for (int k = 0; k < K; ++k) {
+        const double* x = xyz + (size_t)k * 3 * n;
+        double tw = 0, ta = 0;
+        for (int s = 0; s < S; ++s) {
+            double w = 0, a = 0;
+            for (int t = 0; t < S; ++t) {
+                const int gap = s > t ? s - t : t - s;
+                if (gap < min_sep || gap > max_sep) continue;
+                const double g = stub_ent_pair(x, s, t);
+                w += g; a += fabs(g);
+            }
+            seg_writhe[(size_t)k * S + s] = w / two_pi; seg_acn[(size_t)k * S + s] = a / two_pi;
+            tw += w / two_pi; ta += a / two_pi;
+        }
+        writhe[k] = tw; acn[k] = ta;
+    }
+    return hipSuccess;
+}
+hipError_t launch_entangle_table(const double* xyz, int n, int K, int min_sep, int max_sep, const int* bounds, int D, double* link, double* link_abs,
+                                 hipStream_t) {
+    LaunchScope ls;
+    const double two_pi = 2.0 * M_PI;
+    for (int k = 0; k < K; ++k) {
+        const double* x = xyz + (size_t)k * 3 * n;
+        for (int p = 0; p < D; ++p)
+            for (int q = p; q < D; ++q) {
+                double w = 0, a = 0;
+                for (int s = bounds[p]; s < bounds[p + 1]; ++s)
+                    for (int t = bounds[q]; t < bounds[q + 1]; ++t) {
+                        const int gap = s > t ? s - t : t - s;
+                        if (gap < min_sep || gap > max_sep) continue;
+                        const double g = stub_ent_pair(x, s, t);
+                        w += g; a += fabs(g);
+                    }
+                const size_t base = (size_t)k * D * D;
+                link[base + (size_t)p * D + q] = link[base + (size_t)q * D + p] = w / two_pi;
+                link_abs[base + (size_t)p * D + q] = link_abs[base + (size_t)q * D + p] = a / two_pi;
+            }
+    }
+    return hipSuccess;
+}
+
 }  // namespace c3d
