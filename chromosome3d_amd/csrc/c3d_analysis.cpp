@@ -1,6 +1,6 @@
 // c3d_analysis.cpp — host unit of libc3d.so: the output side.  What a run's models are worth and how they relate, from the coordinates
 // resident on the device (kernels: c3d_score.hip): c3d_score_replicas, c3d_compare_replicas, c3d_superpose_replicas, c3d_rmsd_table,
-// c3d_ensemble_map, c3d_ensemble_score, c3d_geometry_replicas, c3d_separation_profile, c3d_stratified_score, c3d_bead_scores, c3d_accessibility (with the host-only c3d_sphere_points), c3d_compartments (with the host-only c3d_compartment_start), c3d_insulation, c3d_loops, c3d_entanglement, the input side's c3d_balance_matrix and the test hooks c3d_debug_if_ranks / c3d_debug_distance_ranks.  What they share comes first: typed
+// c3d_ensemble_map, c3d_ensemble_score, c3d_geometry_replicas, c3d_separation_profile, c3d_stratified_score, c3d_bead_scores, c3d_accessibility (with the host-only c3d_sphere_points), c3d_compartments (with the host-only c3d_compartment_start), c3d_insulation, c3d_loops, c3d_entanglement, the input side's c3d_balance_matrix and c3d_map_similarity, and the test hooks c3d_debug_if_ranks / c3d_debug_distance_ranks.  What they share comes first: typed
 // scratch slots (Slot, Block, Carve, CallScratch), the ranker (rank_matrix) and the models of a call (model_set_check, model_set_coords, gather_models).
 #include <limits>
 
@@ -1582,6 +1582,123 @@ extern "C" int c3d_balance_matrix(c3d_ctx* c, const double* M, int n, int method
         const double r[C3D_BALANCE_REPORT] = {(double)T, (int)rec[3] == c3d::kBalConverged ? 1.0 : 0.0, rec[0], (double)kept, (double)by[1], (double)by[2], (double)by[3], rec[1]};
         memcpy(report, r, sizeof r);
     }
+    if (device_ms) *device_ms = ms;
+    return C3D_OK;
+}
+
+// ---- two contact maps against one another: the stratum-adjusted coefficient (c3d_score.hip k_sim_*) ----
+// c3d_map_similarity's one allocation: the call's copy of the maps (8 n_maps n^2 bytes), one half-width's smoothed bands, diagonal-major
+// (8 n_maps S n), that half-width's moments and counts (48 P S) and the check's flags.
+struct MapSimScratch : Carve {
+    Slot<double> maps, band, moments;
+    Slot<long long> counts;
+    Slot<int> flags;
+    MapSimScratch(int n, int n_maps, int S, int pairs) {
+        maps = take<double>((size_t)n_maps * n * n);
+        band = take<double>((size_t)n_maps * S * n);
+        moments = take<double>((size_t)pairs * S * 3);
+        counts = take<long long>((size_t)pairs * S * 3);
+        flags = take<int>(1);
+    }
+};
+// a start and an end event a half-width, destroyed when the call goes
+struct MapSimEvents {
+    std::vector<hipEvent_t> e;
+    ~MapSimEvents() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+};
+
+extern "C" int c3d_map_similarity(c3d_ctx* c, const double* maps, int n_maps, int n, const int32_t* h, int n_h, int min_sep, int max_sep, int flags, double* scc,
+                                  double* rho, double* moments, int64_t* counts, double* smoothed, double* device_ms) {
+    const char* const who = "c3d_map_similarity";
+    if (!c) return fail(C3D_ERR_INVALID, "c3d_map_similarity: null context");
+    if (!maps) return fail(C3D_ERR_INVALID, "c3d_map_similarity: no maps");
+    if (n_maps < 2 || n_maps > C3D_MAPSIM_MAX_MAPS) return fail(C3D_ERR_INVALID, "c3d_map_similarity: n_maps outside 2..C3D_MAPSIM_MAX_MAPS");
+    if (n < 3) return fail(C3D_ERR_INVALID, "c3d_map_similarity: fewer than 3 bins (n < 3)");
+    if (n > c->max_beads)
+        return fail(C3D_ERR_INVALID, "c3d_map_similarity: " + std::to_string(n) + " bins: more than max_beads = " + std::to_string(c->max_beads) +
+                                         " (c3d_set_option(\"max_beads\", n) goes up to " + std::to_string(C3D_MAX_BEADS_LIMIT) + ")");
+    if (!h || n_h < 1 || n_h > C3D_MAPSIM_MAX_WIDTHS) return fail(C3D_ERR_INVALID, "c3d_map_similarity: n_h outside 1..C3D_MAPSIM_MAX_WIDTHS (or no half-widths)");
+    for (int k = 0; k < n_h; ++k) {
+        if (h[k] < 0 || h[k] > C3D_MAPSIM_MAX_H) return fail(C3D_ERR_INVALID, "c3d_map_similarity: a half-width outside 0..C3D_MAPSIM_MAX_H");
+        if (k > 0 && h[k] <= h[k - 1]) return fail(C3D_ERR_INVALID, "c3d_map_similarity: the half-widths are not strictly ascending");
+    }
+    if (min_sep < 0 || min_sep > n - 1) return fail(C3D_ERR_INVALID, "c3d_map_similarity: min_sep outside 0..n-1");
+    if (max_sep < 0 || max_sep > n - 1 || (max_sep > 0 && max_sep < min_sep)) return fail(C3D_ERR_INVALID, "c3d_map_similarity: max_sep is 0 (for n-1) or in min_sep..n-1");
+    if (flags & ~C3D_MAPSIM_KEEP_ZEROS) return fail(C3D_ERR_INVALID, "c3d_map_similarity: unknown flag bits");
+    const int lo = min_sep, hi = max_sep ? max_sep : n - 1, S = hi - lo + 1, pairs = n_maps * (n_maps - 1) / 2;
+    C3D_ENTRY(c, unit_bit(UNIT_SCORE));
+    const MapSimScratch L(n, n_maps, S, pairs);
+    CallScratch tmp;
+    if (int rc = tmp.alloc(L.total, who)) return rc;
+    MapSimEvents ev;
+    ev.e.assign(2 * (size_t)n_h, nullptr);
+    for (hipEvent_t& x : ev.e) HIP_TRY(hipEventCreate(&x));
+    static_assert(sizeof(long long) == sizeof(int64_t), "the device's counts are the caller's int64_t");
+    double* const d_maps = L.maps.at(tmp.p);
+    const size_t map_count = (size_t)n * n;
+    HIP_TRY(hipMemcpyAsync(d_maps, maps, sizeof(double) * map_count * n_maps, hipMemcpyHostToDevice, c->stream));
+    for (int m = 0; m < n_maps; ++m) {
+        HIP_TRY(hipMemsetAsync(L.flags.at(tmp.p), 0, L.flags.bytes(), c->stream));
+        LAUNCH_TRY("map similarity launch", c3d::launch_compartment_if_check(d_maps + map_count * m, n, L.flags.at(tmp.p), c->stream));
+        if (int rc = read_back(c, L.flags.at(tmp.p), L.flags.bytes())) return rc;
+        const int bad = static_cast<const int*>(c->h_stage)[0];
+        const std::string which = "c3d_map_similarity: map " + std::to_string(m) + ": ";
+        if (bad & 2) return fail(C3D_ERR_INVALID, which + "an entry of the matrix is not finite");
+        if (bad & 4) return fail(C3D_ERR_INVALID, which + "an entry of the matrix is negative");
+        if (bad & 1) return fail(C3D_ERR_INVALID, which + "the matrix is not symmetric");
+    }
+    // a half-width at a time: the bands, the strata, then the read-backs into the call's own buffers (`smoothed`, the one output too large
+    // for a second copy, straight into the caller's)
+    const size_t per_h = (size_t)pairs * S * 3, band_count = (size_t)n_maps * S * n;
+    std::vector<double> hm(per_h * n_h);
+    std::vector<int64_t> hc(per_h * n_h);
+    for (int k = 0; k < n_h; ++k) {
+        HIP_TRY(hipEventRecord(ev.e[2 * k], c->stream));
+        LAUNCH_TRY("map similarity launch", c3d::launch_mapsim_smooth(d_maps, n, n_maps, h[k], lo, hi, L.band.at(tmp.p), c->stream));
+        LAUNCH_TRY("map similarity launch", c3d::launch_mapsim_strata(L.band.at(tmp.p), n, n_maps, lo, hi, (flags & C3D_MAPSIM_KEEP_ZEROS) != 0, L.moments.at(tmp.p),
+                                                                      L.counts.at(tmp.p), c->stream));
+        HIP_TRY(hipEventRecord(ev.e[2 * k + 1], c->stream));
+        HIP_TRY(hipMemcpyAsync(hm.data() + per_h * k, L.moments.at(tmp.p), L.moments.bytes(), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(hc.data() + per_h * k, L.counts.at(tmp.p), L.counts.bytes(), hipMemcpyDeviceToHost, c->stream));
+        if (smoothed) HIP_TRY(hipMemcpyAsync(smoothed + band_count * k, L.band.at(tmp.p), L.band.bytes(), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    double ms = 0;
+    for (int k = 0; k < n_h && device_ms; ++k) {
+        float one = 0;
+        HIP_TRY(hipEventElapsedTime(&one, ev.e[2 * k], ev.e[2 * k + 1]));
+        ms += (double)one;
+    }
+    // rho, w and scc on the host, from the moments and the integers, with the header's expressions in the header's order
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    for (int k = 0; k < n_h && (rho || scc); ++k) {
+        double* const table = scc ? scc + (size_t)k * n_maps * n_maps : nullptr;
+        for (int m = 0; m < n_maps && table; ++m) table[(size_t)m * n_maps + m] = 1.0;
+        for (int pr = 0; pr < pairs; ++pr) {
+            double num = 0, den = 0;
+            bool any = false;
+            for (int s = 0; s < S; ++s) {
+                const size_t at = per_h * k + ((size_t)pr * S + s) * 3;
+                const double* const mo = hm.data() + at;
+                const int64_t* const q = hc.data() + at;
+                double r = nan;
+                if (q[0] >= 3 && q[1] > 0 && q[2] > 0 && mo[1] > 0.0 && mo[2] > 0.0) {
+                    const double N = (double)q[0];
+                    const double w = sqrt((double)q[1] * (double)q[2]) / (((4.0 * N) * N) * N);
+                    r = mo[0] / sqrt(mo[1] * mo[2]);
+                    num += w * r;
+                    den += w;
+                    any = true;
+                }
+                if (rho) rho[((size_t)k * pairs + pr) * S + s] = r;
+            }
+            int p, q;
+            c3d::mapsim_pair(pr, n_maps, &p, &q);
+            if (table) table[(size_t)p * n_maps + q] = table[(size_t)q * n_maps + p] = any ? num / den : nan;
+        }
+    }
+    if (moments) memcpy(moments, hm.data(), sizeof(double) * hm.size());
+    if (counts) memcpy(counts, hc.data(), sizeof(int64_t) * hc.size());
     if (device_ms) *device_ms = ms;
     return C3D_OK;
 }

@@ -633,6 +633,19 @@ hipError_t launch_entangle_rows(const double* xyz, int n, int K, int min_sep, in
                                 hipStream_t s);
 hipError_t launch_entangle_table(const double* xyz, int n, int K, int min_sep, int max_sep, const int* bounds, int D, double* link, double* link_abs,
                                  hipStream_t s);
+// Two contact maps against one another (c3d_map_similarity; k_sim_*, c3d_score_mapsim.inc).  maps: n_maps matrices of n x n doubles on the
+// device; strata lo <= s <= hi, S = hi - lo + 1.  launch_mapsim_smooth: band (n_maps x S x n, cleared here) = row s - lo of map m holds the
+// smoothed X_m(i, i + s) at half-width h for i < n - s, zeros behind.  launch_mapsim_strata: moments and counts (P x S x 3, P the pairs
+// p < q in the order (0,1), (0,2), ..., (1,2), ...) = { Cxy, Cxx, Cyy } and { N, A, B } of include/c3d.h's definitions 2 to 4.
+// pair index -> (p, q), p < q
+__host__ __device__ inline void mapsim_pair(int idx, int n_maps, int* p, int* q) {
+    int a = 0;
+    while (idx >= n_maps - 1 - a) { idx -= n_maps - 1 - a; ++a; }
+    *p = a;
+    *q = a + 1 + idx;
+}
+hipError_t launch_mapsim_smooth(const double* maps, int n, int n_maps, int h, int lo, int hi, double* band, hipStream_t s);
+hipError_t launch_mapsim_strata(const double* band, int n, int n_maps, int lo, int hi, bool keep_zeros, double* moments, long long* counts, hipStream_t s);
 
 // Target matrix entry: NOE target in Angstrom, 0 = no restraint (host c3d_set_restraints and K1).
 inline float encode_target_host(float t) { return t > 0 ? t : 0.0f; }

@@ -39,6 +39,8 @@
 //                             staged in LDS, peaks by exact suppression, listed pixels in every map and their pile-up (c3d_loops)
 //   c3d_score_entangle.inc    k_ent_*    entanglement: the Gauss integral of every pair of chain segments as two atan2, summed a segment, a
 //                             model and a pair of domains — writhe, average crossing number, linking (c3d_entanglement)
+//   c3d_score_mapsim.inc      k_sim_*    the input side: two contact maps against one another, HiCRep's stratum-adjusted coefficient — a clipped box
+//                             mean over the band staged in LDS, then a masked Pearson and two LDS sorts a (stratum, pair) (c3d_map_similarity)
 #include "c3d_score_core.h"
 
 namespace c3d {
@@ -280,8 +282,9 @@ hipError_t launch_if_rank_sort(double* M, int n, int range, unsigned long long* 
 #include "c3d_score_balance.inc"
 #include "c3d_score_loop.inc"
 #include "c3d_score_entangle.inc"
+#include "c3d_score_mapsim.inc"
 
-// loads the unit's code object on the current device and gives the k_str_* and k_bead_* kernels their dynamic-LDS allowance (c3d_gate.cpp "code objects":
+// loads the unit's code object on the current device and gives the k_str_*, k_sim_stratum and k_bead_* kernels their dynamic-LDS allowance (c3d_gate.cpp "code objects":
 // once per device, never beside a launch)
 hipError_t preload_score_unit() {
     hipFuncAttributes a;

@@ -205,8 +205,12 @@ hipError_t launch_stratified_models(const double* xyz, int n, int K, int lo, int
 }
 
 // the dynamic LDS of the longest stratum a context accepts (16384 keys): set once when the unit loads (preload_score_unit), never beside a launch
+// (k_sim_stratum: c3d_score_mapsim.inc, the same network over two maps' smoothed values)
+__global__ void k_sim_stratum(const double* __restrict__ band, int n, int n_maps, int lo, int hi, int s_first, int P, int keep_zeros, double* __restrict__ moments,
+                              long long* __restrict__ counts);
 static hipError_t str_prepare_unit() {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_str_if), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(unsigned long long) * 16384));
     if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_str_model), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(unsigned) * 16384));
+    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sim_stratum), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(unsigned long long) * 16384));
     return e;
 }

@@ -27,6 +27,8 @@
 //       also <prefix>_link.txt, the linking table of the given domains
 //   --balance <ice|vc|sqrt-vc> balances the matrix of --if on the device first (raw contact counts in, a normalised matrix out): the solve and
 //       every analysis option of the run use the balanced matrix; --balance-out <prefix> writes the weights and the matrix
+//   --map-similarity <file> (repeatable) compares the matrix of --if as read, before any --balance, with the listed matrices on the device:
+//       HiCRep's stratum-adjusted correlation coefficient of every pair, printed as a table per half-width (c3d_map_similarity)
 //
 // Success convention of the reference: <ID>_<M>.pdb exists, iam.running removed; on failure
 // iam.running is renamed iam.failed and the exit code is non-zero (:266-283).
@@ -143,6 +145,13 @@ static void usage() {
             "                 [--balance-iters <k>   at most k updates of ice, 0..10000; default 200]\n"
             "                 [--balance-out <prefix>   writes <prefix>_weights.txt (header `bead weight masked`; masked: 0 kept, 1 listed, 2 too few non-zeros,\n"
             "                                          3 no kept partner) and <prefix>_matrix.txt, the balanced matrix in the format --if reads, with 17 digits]\n"
+            "                 [--map-similarity <file>   repeatable, up to 15: compare the matrix of --if as read (before any --balance) with these matrices of the same\n"
+            "                                          size, before the solve: the stratum-adjusted correlation coefficient (HiCRep's SCC) of every pair of maps, map 1 the\n"
+            "                                          matrix of --if, printed as `Similarity : h <h> map <m> : <scc to every map>` a half-width and map]\n"
+            "                 [--map-similarity-h <list>   half-widths of the box mean, ascending, each 0..20, at most 8; default 0]\n"
+            "                 [--map-similarity-sep <lo>:<hi>   the separations correlated; default 1:0, 0 meaning n - 1]\n"
+            "                 [--map-similarity-out <prefix>   writes <prefix>_scc.txt (header `h map scc...`, the tables with 17 digits) and <prefix>_strata.txt\n"
+            "                                          (header `h map_p map_q separation kept rho`, one row a half-width, pair and separation)]\n"
             "                 [--accepted   also write <ID>a_<k>.pdb beside every <ID>_<k>.pdb, as CNS does for structures it accepts]\n");
 }
 
@@ -182,6 +191,8 @@ int main(int argc, char** argv) {
     int loop_window = 5, loop_peak = 2;
     std::string entanglement_prefix, entangle_sep, entangle_bounds;
     std::string balance_method, balance_out;          // empty: the matrix of --if is taken as it is
+    std::vector<std::string> mapsim_files;             // matrices to compare the one of --if with (c3d_map_similarity)
+    std::string mapsim_h = "0", mapsim_sep, mapsim_out;
     int balance_ignore_diags = 2, balance_min_nnz = 10, balance_iters = 200;
     double balance_tol = 1e-5;
     double bead_radius = -1, probe_radius = -1;      // < 0: half of b0
@@ -258,6 +269,10 @@ int main(int argc, char** argv) {
         else if (s == "--balance-tol") balance_tol = atof(next("--balance-tol"));
         else if (s == "--balance-iters") balance_iters = atoi(next("--balance-iters"));
         else if (s == "--balance-out") balance_out = next("--balance-out");
+        else if (s == "--map-similarity") mapsim_files.push_back(next("--map-similarity"));   // compare contact maps (c3d_map_similarity)
+        else if (s == "--map-similarity-h") mapsim_h = next("--map-similarity-h");
+        else if (s == "--map-similarity-sep") mapsim_sep = next("--map-similarity-sep");
+        else if (s == "--map-similarity-out") mapsim_out = next("--map-similarity-out");
         else if (s == "--bead-radius") bead_radius = atof(next("--bead-radius"));
         else if (s == "--probe-radius") probe_radius = atof(next("--probe-radius"));
         else if (s == "--sphere-points") sphere_points = atoi(next("--sphere-points"));
@@ -273,6 +288,9 @@ int main(int argc, char** argv) {
     if (!insulation_prefix.empty() && if_path.empty()) { fprintf(stderr, "c3d_solve: --insulation needs --if: a run started from --tbl has no IF matrix\n"); return 2; }
     if (!loops_prefix.empty() && if_path.empty()) { fprintf(stderr, "c3d_solve: --loops needs --if: a run started from --tbl has no IF matrix\n"); return 2; }
     if ((!balance_method.empty() || !balance_out.empty()) && if_path.empty()) { fprintf(stderr, "c3d_solve: --balance needs --if: a run started from --tbl has no matrix to balance\n"); return 2; }
+    if (!mapsim_files.empty() && if_path.empty()) { fprintf(stderr, "c3d_solve: --map-similarity needs --if: a run started from --tbl has no matrix to compare\n"); return 2; }
+    if (mapsim_files.empty() && !mapsim_out.empty()) { fprintf(stderr, "c3d_solve: --map-similarity-out needs --map-similarity <file>\n"); return 2; }
+    if ((int)mapsim_files.size() > C3D_MAPSIM_MAX_MAPS - 1) { fprintf(stderr, "c3d_solve: --map-similarity: at most %d files\n", C3D_MAPSIM_MAX_MAPS - 1); return 2; }
     if (!balance_out.empty() && balance_method.empty()) { fprintf(stderr, "c3d_solve: --balance-out needs --balance <ice|vc|sqrt-vc>\n"); return 2; }
     if (!balance_method.empty() && balance_method != "ice" && balance_method != "vc" && balance_method != "sqrt-vc") {
         fprintf(stderr, "c3d_solve: --balance takes ice, vc or sqrt-vc\n");
@@ -313,6 +331,65 @@ int main(int argc, char** argv) {
         CHECK(c3d_parse_if_file(if_path.c_str(), &IF, &n));
         // a matrix beyond the default limit is what the user asked for: raise the limit to it (the library refuses beyond its ceiling)
         if (n > C3D_MAX_BEADS_DEFAULT && n <= C3D_MAX_BEADS_LIMIT) CHECK(c3d_set_option(ctx, "max_beads", n));
+        if (!mapsim_files.empty()) {
+            // the matrix as read against the listed ones, before anything changes it
+            const int Q = 1 + (int)mapsim_files.size();
+            std::vector<double> maps((size_t)Q * n * n);
+            memcpy(maps.data(), IF, sizeof(double) * (size_t)n * n);
+            for (int m = 1; m < Q; ++m) {
+                double* other = nullptr;
+                int no = 0;
+                CHECK(c3d_parse_if_file(mapsim_files[m - 1].c_str(), &other, &no));
+                if (no != n) { fprintf(stderr, "c3d_solve: --map-similarity %s has %d bins, the matrix of --if %d\n", mapsim_files[m - 1].c_str(), no, n); c3d_free(other); return fail_exit(out_dir); }
+                memcpy(maps.data() + (size_t)m * n * n, other, sizeof(double) * (size_t)n * n);
+                c3d_free(other);
+            }
+            std::vector<int32_t> hw;
+            for (const char* q = mapsim_h.c_str(); *q;) {
+                char* end = nullptr;
+                const long v = strtol(q, &end, 10);
+                if (end == q) { fprintf(stderr, "c3d_solve: --map-similarity-h takes a list such as 0,1,2\n"); return fail_exit(out_dir); }
+                hw.push_back((int32_t)v);
+                q = *end == ',' ? end + 1 : end;
+                if (*end && *end != ',') { fprintf(stderr, "c3d_solve: --map-similarity-h takes a list such as 0,1,2\n"); return fail_exit(out_dir); }
+            }
+            int lo = 1, hi = 0;
+            if (!mapsim_sep.empty() && sscanf(mapsim_sep.c_str(), "%d:%d", &lo, &hi) != 2) { fprintf(stderr, "c3d_solve: --map-similarity-sep takes lo:hi\n"); return fail_exit(out_dir); }
+            const int H = (int)hw.size(), top = hi ? hi : n - 1, S = top >= lo ? top - lo + 1 : 1, P = Q * (Q - 1) / 2;
+            std::vector<double> scc((size_t)H * Q * Q), rho((size_t)H * P * S);
+            std::vector<int64_t> counts((size_t)H * P * S * 3);
+            CHECK(c3d_map_similarity(ctx, maps.data(), Q, n, hw.data(), H, lo, hi, 0, scc.data(), rho.data(), nullptr, counts.data(), nullptr, nullptr));
+            for (int k = 0; k < H; ++k)
+                for (int m = 0; m < Q; ++m) {
+                    printf("Similarity : h %d map %d :", hw[k], m + 1);
+                    for (int q = 0; q < Q; ++q) printf(" %.17g", scc[((size_t)k * Q + m) * Q + q]);
+                    printf("\n");
+                }
+            if (!mapsim_out.empty()) {
+                const std::string spath = mapsim_out + "_scc.txt", tpath = mapsim_out + "_strata.txt";
+                FILE* f = fopen(spath.c_str(), "w");
+                if (!f) { fprintf(stderr, "c3d_solve: cannot write %s\n", spath.c_str()); return fail_exit(out_dir); }
+                fprintf(f, "h map scc...\n");
+                for (int k = 0; k < H; ++k)
+                    for (int m = 0; m < Q; ++m) {
+                        fprintf(f, "%d %d", hw[k], m + 1);
+                        for (int q = 0; q < Q; ++q) fprintf(f, " %.17g", scc[((size_t)k * Q + m) * Q + q]);
+                        fprintf(f, "\n");
+                    }
+                fclose(f);
+                f = fopen(tpath.c_str(), "w");
+                if (!f) { fprintf(stderr, "c3d_solve: cannot write %s\n", tpath.c_str()); return fail_exit(out_dir); }
+                fprintf(f, "h map_p map_q separation kept rho\n");
+                for (int k = 0; k < H; ++k)
+                    for (int p = 0, pr = 0; p < Q; ++p)
+                        for (int q = p + 1; q < Q; ++q, ++pr)
+                            for (int s = 0; s < S; ++s) {
+                                const size_t at = ((size_t)k * P + pr) * S + s;
+                                fprintf(f, "%d %d %d %d %lld %.17g\n", hw[k], p + 1, q + 1, lo + s, (long long)counts[at * 3], rho[at]);
+                            }
+                fclose(f);
+            }
+        }
         if (!balance_method.empty()) {
             // raw counts in, the balanced matrix over IF: everything below reads IF
             const int method = balance_method == "ice" ? C3D_BALANCE_ICE : balance_method == "vc" ? C3D_BALANCE_VC : C3D_BALANCE_SQRT_VC;

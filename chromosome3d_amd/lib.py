@@ -104,6 +104,7 @@ SIGNATURES = {
     "c3d_loops": (_i, [_vp, _dp, _dp, _i, _i32p, _i, _i, _i32p, _i, _i, _i, _i, _dp, _d, _i, _i, _i32p, _i, _i, _dp, _dp, _i32p, _i32p, _dp, _i32p, _dp, _dp, _dp]),
     "c3d_entanglement": (_i, [_vp, _dp, _i, _i, _i, _i32p, _i, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "c3d_balance_matrix": (_i, [_vp, _dp, _i, _i, _i, _i, _i, _i32p, _dp, _d, _i, _d, _dp, _i32p, _dp, _dp, _dp, _dp]),
+    "c3d_map_similarity": (_i, [_vp, _dp, _i, _i, _i32p, _i, _i, _i, _i, _dp, _dp, _dp, C.POINTER(C.c_int64), _dp, _dp]),
     "c3d_rank": (_i, [_vp, _i32p]),
     "c3d_reduce_model": (_i, [_dp, _i, _dp]),
     "c3d_model_similarity": (_i, [_dp, _dp, _i, _dp, _dp]),
@@ -134,6 +135,7 @@ LOOP_CONSENSUS, LOOP_IF_ONLY = 1, 2                                             
 ENTANGLE_MAX_DOMAINS = 256                                                              # C3D_ENTANGLE_MAX_DOMAINS
 BALANCE_ICE, BALANCE_VC, BALANCE_SQRT_VC = 0, 1, 2                                      # C3D_BALANCE_* (methods)
 BALANCE_CHECK_EVERY_ROUND, BALANCE_MAX_ITERS, BALANCE_REPORT = 1, 10000, 8             # C3D_BALANCE_*
+MAPSIM_KEEP_ZEROS, MAPSIM_MAX_MAPS, MAPSIM_MAX_H, MAPSIM_MAX_WIDTHS = 1, 16, 20, 8        # C3D_MAPSIM_*
 LBFGS_MAX_PAIRS, LBFGS_SUMS, LBFGS_STATE_DOUBLES, LBFGS_COEFS = 8, 36, 129, 17      # C3D_LBFGS_*
 LBFGS_MOVE_ROW_IN, LBFGS_MOVE_ROW_OUT = 54, 10                                       # C3D_LBFGS_MOVE_ROW_*
 ROW_FINISH_IN, ROW_FINISH_OUT = 16, 10                                               # C3D_ROW_FINISH_*

@@ -345,6 +345,39 @@ def balance_if(path_or_matrix, solver=None, device=0, **kw):
             s.close()
 
 
+def map_similarity_report(solver, maps, names=None, h=(0,), min_sep=0, max_sep=0, keep_zeros=False):
+    """Do the maps agree?  Solver.map_similarity's dict with "names", "counted" [n_h, P] (how many strata count in every pair) and "text":
+    per half-width a header line and the n_maps x n_maps table of the stratum-adjusted coefficient, one row a map, then one line a pair
+    with its coefficient and its counted strata."""
+    out = solver.map_similarity(maps, h, min_sep, max_sep, keep_zeros)
+    Q = out["scc"].shape[1]
+    names = ["map %d" % (m + 1) for m in range(Q)] if names is None else [str(x) for x in names]
+    assert len(names) == Q
+    out["names"] = names
+    out["counted"] = np.isfinite(out["rho"]).sum(axis=2)
+    n, S = np.asarray(maps).shape[-1], out["rho"].shape[2]
+    lines = []
+    for k, hk in enumerate(out["h"]):
+        lines.append("# h = %d   (%d maps of %d bins, separations %d..%d%s)" % (hk, Q, n, min_sep, min_sep + S - 1, ", zeros kept" if keep_zeros else ""))
+        for m in range(Q):
+            lines.append(" ".join(["%s" % names[m]] + ["%.9f" % v for v in out["scc"][k, m]]))
+        for pr, (p, q) in enumerate(out["pairs"]):
+            lines.append("# %s : %s  scc %.9f  strata %d of %d" % (names[p], names[q], out["scc"][k, p, q], out["counted"][k, pr], S))
+    out["text"] = "\n".join(lines) + "\n"
+    return out
+
+
+def choose_smoothing(scc_by_h, gain=0.01):
+    """HiCRep's rule for the half-width: the smallest listed h whose successor gains less than `gain` — scc(h_next) - scc(h) < gain — or
+    the largest listed h if every step still gains.  scc_by_h: a dict h -> scc, or pairs (h, scc); read in ascending h.  Host only."""
+    table = sorted((int(h), float(v)) for h, v in (scc_by_h.items() if hasattr(scc_by_h, "items") else scc_by_h))
+    assert table, "no half-width listed"
+    for (h0, v0), (_, v1) in zip(table, table[1:]):
+        if v1 - v0 < gain:
+            return h0
+    return table[-1][0]
+
+
 def build_models(solver, model_count=MODELCOUNT, seed=MD_SEED, first_replica=0, model=None, stages=None, fire=None,
                  gtol=1e-2, check_every=250, final_kind=5):
     """The replacement of `cns_solve < dgsa.inp` (:254-289): runs the whole annealing schedule

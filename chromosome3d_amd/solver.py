@@ -714,6 +714,32 @@ class Solver:
                    masked_counts=[int(rep[4]), int(rep[5]), int(rep[6])], mean_marginal=float(rep[7]), device_ms=ms.value)
         return out
 
+    def map_similarity(self, maps, h=(0,), min_sep=0, max_sep=0, keep_zeros=False, want_smoothed=False):
+        """Do contact maps agree?  HiCRep's stratum-adjusted correlation coefficient of every pair of maps [Q, n, n] (2 <= Q <= 16, each
+        symmetric, finite, >= 0, n up to the context's max_beads), on the device (c3d_map_similarity); it needs no targets and no
+        replicas and changes nothing of the solve.  h: the half-widths of the box mean, strictly ascending, each 0..20; the strata are
+        the separations min_sep..max_sep (0: n - 1); pairs that are 0 in both smoothed maps are dropped unless keep_zeros.  A dict:
+        "scc" [n_h, Q, Q] (symmetric, unit diagonal, NaN where no stratum counts), "rho" [n_h, P, S] (NaN for a stratum that does not
+        count), "moments" [n_h, P, S, 3] (Cxy, Cxx, Cyy), "counts" [n_h, P, S, 3] int64 (N, A, B), "pairs" (the P pairs (p, q) in the
+        outputs' order), "h", with want_smoothed "smoothed" [n_h, Q, S, n] (row s - min_sep: X(i, i + s), zeros behind), "device_ms"."""
+        m = np.ascontiguousarray(maps, dtype=np.float64)
+        assert m.ndim == 3 and m.shape[1] == m.shape[2]
+        Q, n = m.shape[0], m.shape[1]
+        hw = np.ascontiguousarray(h, dtype=np.int32).reshape(-1)
+        hi = int(max_sep) if max_sep else n - 1
+        S, P, H = max(hi - int(min_sep) + 1, 1), Q * (Q - 1) // 2, len(hw)
+        out = {"scc": np.empty((H, Q, Q)), "rho": np.empty((H, P, S)), "moments": np.empty((H, P, S, 3)), "counts": np.empty((H, P, S, 3), dtype=np.int64)}
+        if want_smoothed:
+            out["smoothed"] = np.empty((H, Q, S, n))
+        ms = C.c_double()
+        _l.check(self._L.c3d_map_similarity(self._h, _l.dptr(m), Q, n, _l.i32ptr(hw), H, int(min_sep), int(max_sep), _l.MAPSIM_KEEP_ZEROS if keep_zeros else 0,
+                                            _l.dptr(out["scc"]), _l.dptr(out["rho"]), _l.dptr(out["moments"]), out["counts"].ctypes.data_as(C.POINTER(C.c_int64)),
+                                            _l.dptr(out["smoothed"]) if want_smoothed else None, C.byref(ms)))
+        out["pairs"] = [(p, q) for p in range(Q) for q in range(p + 1, Q)]
+        out["h"] = [int(x) for x in hw]
+        out["device_ms"] = ms.value
+        return out
+
     def rank(self):
         r = np.empty(self.nrep, dtype=np.int32)
         _l.check(self._L.c3d_rank(self._h, _l.i32ptr(r)))

@@ -1064,6 +1064,63 @@ int c3d_entanglement(c3d_ctx* ctx, const double* extra_xyz, int n_extra, int min
 int c3d_balance_matrix(c3d_ctx* ctx, const double* M, int n, int method, int flags, int ignore_diags, int min_nnz,
                        const int32_t* mask_in, const double* w0, double tol, int max_iters, double target,
                        double* weights, int32_t* masked, double* balanced, double* history, double* report, double* device_ms);
+/* Reproducibility of contact maps: HiCRep's stratum-adjusted correlation coefficient (SCC) of every pair of n_maps maps, on the device.
+ * Do the replicates agree, does the balanced map still agree with the raw one, how far is condition A from condition B: each map is
+ * smoothed with a (2h+1) x (2h+1) box mean, the two maps are correlated inside every genomic separation, pairs that are empty in both maps
+ * are dropped and the strata are combined with rank-variance weights.  Any symmetric non-negative map will do — IF, c3d_balance_matrix's
+ * `balanced`, the contact-frequency map of c3d_ensemble_map.  The entry needs a context, no targets and no replicas; it changes no state
+ * of the solve and keeps no stat key and no option key.
+ *
+ * Input.  maps is n_maps matrices of n x n row-major doubles, 2 <= n_maps <= C3D_MAPSIM_MAX_MAPS, 3 <= n <= the max_beads in force.  Every
+ *   value is finite and >= 0 and M(i,j) == M(j,i) exactly; anything else is C3D_ERR_INVALID with the map's index in the message, found on
+ *   the device before any other kernel (the check c3d_compartments makes of IF, once a map).  h holds n_h half-widths, 1 <= n_h <=
+ *   C3D_MAPSIM_MAX_WIDTHS, each in 0..C3D_MAPSIM_MAX_H, strictly ascending.  0 <= min_sep <= max_sep <= n - 1; max_sep == 0 means n - 1.
+ *   lo = min_sep, hi = the resolved max_sep, S = hi - lo + 1.  flags: 0 or C3D_MAPSIM_KEEP_ZEROS.
+ * Definitions.
+ *   1. Smoothing.  For a map M and a half-width h, the row window of (i,j) is r in [max(0,i-h), min(n-1,i+h)] and the column window
+ *      c in [max(0,j-h), min(n-1,j+h)].  t(r) = M(r,c0) + M(r,c0+1) + ... over the column window in ascending c, starting from the first
+ *      term; X(i,j) = (t(r0) + t(r0+1) + ...) / (double)(rows x cols) over the row window in ascending r, with one IEEE division.  A row
+ *      sum depends only on (r, column window), so forming the row sums once and adding them down the columns gives the bits of the direct
+ *      double loop.  Only additions and one division occur.  h = 0 is the map itself.
+ *   2. A stratum.  Stratum s of a pair of maps (p, q), p < q, holds the pairs (i, i+s), i = 0..n-s-1, with x_i = X_p(i,i+s) and
+ *      y_i = X_q(i,i+s).  Pair i is kept unless x_i == 0 and y_i == 0; with C3D_MAPSIM_KEEP_ZEROS all pairs are kept.  N is the number of
+ *      kept pairs.
+ *   3. Moments, over the kept pairs.  mx = (sum x) / N and my likewise (both 0 if N == 0); Cxy = sum (x - mx)(y - my), Cxx = sum (x - mx)^2,
+ *      Cyy = sum (y - my)^2, every product rounded on its own.  Every sum goes through the scoring unit's block_reduce: thread t brings the
+ *      pairs i = t + 256k in ascending k, and an unkept pair brings 0.  A stratum's bytes therefore depend on the two maps, h and s only.
+ *   4. Ranks.  Inside the kept pairs, a_i and b_i are the doubled average ranks of x and y, each on its own: #{smaller} + #{not larger} + 1,
+ *      the definition c3d_stratified_score uses; -0.0 ranks as 0.0.  A = N sum a^2 - T^2, B = N sum b^2 - T^2, T = N(N+1), exact in int64
+ *      (4 N^4 < 2.9e17 at N = 16384).  Only the two sums of squares are needed, so neither sort keeps an index; unkept pairs take the pad
+ *      key and sort behind the kept ones.
+ *   5. Per stratum, on the host, in doubles.  rho_s = Cxy / sqrt(Cxx * Cyy).  w_s = sqrt((double)A * (double)B) / (4 N^3), with
+ *      4 N^3 = ((4.0 * N) * N) * N: N times the square root of the product of the variances of rank/N, which are HiCRep's weights.  The
+ *      stratum counts if N >= 3, A > 0, B > 0, Cxx > 0 and Cyy > 0.  Otherwise rho_s is NaN and w_s is 0.
+ *   6. SCC.  scc(p,q) = (sum w_s rho_s) / (sum w_s), the two sums sequential over ascending counted s; NaN if no stratum counts.
+ *      scc(q,p) = scc(p,q).  scc(p,p) = 1.0, written by the host.
+ * Outputs, any may be NULL.  P = n_maps (n_maps - 1) / 2 pairs, in the order (0,1), (0,2), ..., (1,2), ...
+ *   scc [n_h][n_maps][n_maps] the combined coefficient;  rho [n_h][P][S] rho_s;  moments [n_h][P][S][3] { Cxy, Cxx, Cyy };
+ *   counts [n_h][P][S][3], int64 { N, A, B };  smoothed [n_h][n_maps][S][n]: row s - lo holds X(i, i+s) for i < n - s, then zeros;
+ *   device_ms: one double, the HIP-event time from after the upload and check to the last kernel (the sum over the half-widths; the
+ *   read-backs between them are not in it).
+ * Determinism.  There are no atomics.  Two calls return the same bytes.  A pair's results do not depend on n_maps, on the other
+ *   half-widths or on which outputs are asked for.  Passing the maps in another order permutes the outputs and changes no bit of them:
+ *   every product and every sum under a square root is commutative in the two maps.
+ * C3D_ERR_INVALID with the function's name and with nothing written, before any launch: no context or no maps; n_maps, n, n_h, a
+ * half-width, the order of the half-widths, min_sep or max_sep out of range; unknown flag bits.  A bad matrix after the check pass, before
+ * any other kernel.  C3D_ERR_NOMEM when the scratch does not fit, with nothing written.
+ * Measured on an MI355X (profiles/r35_map_similarity.md, tools/map_similarity.py): 455 x 2 maps, h = 0..5, all strata: 0.74 ms; 4096 x 4,
+ * separations 1..500, h = 3: 0.86 ms; 16384 x 2, separations 1..2000, h = 5: 6.9 ms, against about 51 s of the numpy restatement (scaled).
+ * Scratch, one allocation per call, freed before it returns: 8 n_maps n^2 bytes for the call's copy of the maps, 8 n_maps S n bytes for
+ * one half-width's smoothed bands at a time in diagonal-major storage (the stratum kernel reads contiguously; there is no second n x n
+ * array per map), and 48 P S bytes of moments and counts: 3.3 MB + 3.3 MB at 455 x 2 with all strata, 4 GiB + 0.5 GiB at 16384 x 2 with
+ * 2000 strata.
+ * Out of scope: HiCRep's depth down-sampling, its variance estimate, and sparse input. */
+#define C3D_MAPSIM_KEEP_ZEROS 1      /* flags: pairs that are 0 in both maps stay in their stratum */
+#define C3D_MAPSIM_MAX_MAPS  16
+#define C3D_MAPSIM_MAX_H     20
+#define C3D_MAPSIM_MAX_WIDTHS 8
+int c3d_map_similarity(c3d_ctx* ctx, const double* maps, int n_maps, int n, const int32_t* h, int n_h, int min_sep, int max_sep, int flags,
+                       double* scc, double* rho, double* moments, int64_t* counts, double* smoothed, double* device_ms);
 /* rank[k] = replica index with the k-th lowest int(E_noe) (chromosome3D.pl:796-802,822-828);
  * ties broken by replica id. */
 int c3d_rank(c3d_ctx* ctx, int32_t* rank);

@@ -166,6 +166,19 @@ static void api_storm(int device_count) {
                                               nullptr) == C3D_OK && brep[0] == 1.0;
                 ok = ok && c3d_balance_matrix(c, IF.data(), n, C3D_BALANCE_VC, 0, 2, 10, nullptr, bw.data(), 0.0, 0, 1.0, bw.data(), nullptr, nullptr, nullptr, nullptr,
                                               nullptr) == C3D_ERR_INVALID;
+                // (IF against itself and against IF with one pair of entries doubled: three maps, two half-widths, separations 1..8; then
+                // half-widths out of order)
+                std::vector<double> smaps(3 * (size_t)n * n);
+                for (int m = 0; m < 3; ++m) std::copy(IF.begin(), IF.end(), smaps.begin() + (size_t)m * n * n);
+                smaps[2 * (size_t)n * n + 1 * n + 3] *= 2.0; smaps[2 * (size_t)n * n + 3 * n + 1] *= 2.0;
+                const int32_t sh[2] = {0, 2}, shbad[2] = {2, 2};
+                std::vector<double> sscc2(2 * 9), srho2(2 * 3 * 8), smom(2 * 3 * 8 * 3), ssm(2 * 3 * 8 * (size_t)n);
+                std::vector<int64_t> scnt(2 * 3 * 8 * 3);
+                double sim_ms = -1;
+                ok = ok && c3d_map_similarity(c, smaps.data(), 3, n, sh, 2, 1, 8, round == 1 ? C3D_MAPSIM_KEEP_ZEROS : 0, sscc2.data(), srho2.data(), smom.data(), scnt.data(),
+                                              ssm.data(), &sim_ms) == C3D_OK && sim_ms >= 0 && sscc2[0] == 1.0 && memcmp(&sscc2[1], &sscc2[3], sizeof(double)) == 0 && ssm[0] == IF[1];
+                ok = ok && c3d_map_similarity(c, smaps.data(), 2, n, sh, 1, 0, 0, 0, sscc2.data(), nullptr, nullptr, nullptr, nullptr, nullptr) == C3D_OK;
+                ok = ok && c3d_map_similarity(c, smaps.data(), 3, n, shbad, 2, 1, 8, 0, sscc2.data(), nullptr, nullptr, nullptr, nullptr, nullptr) == C3D_ERR_INVALID;
                 if (what == 2) { unsigned long long a, b, d; ok = ok && c3d_debug_tear16(c, 4, &a, &b, &d) == C3D_OK; }
             }
             if (!ok) { fprintf(stderr, "api storm thread %d: %s\n", t, c3d_last_error()); ++failures; }

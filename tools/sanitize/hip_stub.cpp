@@ -1048,4 +1048,61 @@ hipError_t launch_entangle_table(const double* xyz, int n, int K, int min_sep, i
     return hipSuccess;
 }
 
+// c3d_map_similarity: the two launchers restated on the host with plain loops in index order (the definitions of include/c3d.h: the
+// direct double loop of the box mean, sequential sums, the doubled average ranks by counting; no tiles, no sort, no block reduction)
+hipError_t launch_mapsim_smooth(const double* maps, int n, int n_maps, int h, int lo, int hi, double* band, hipStream_t) {
+    LaunchScope ls;
+    const int S = hi - lo + 1;
+    for (int m = 0; m < n_maps; ++m) {
+        const double* M = maps + (size_t)m * n * n;
+        for (int s = lo; s <= hi; ++s)
+            for (int i = 0; i < n; ++i) {
+                double X = 0.0;
+                if (i < n - s) {
+                    const int j = i + s, r0 = std::max(0, i - h), r1 = std::min(n - 1, i + h), c0 = std::max(0, j - h), c1 = std::min(n - 1, j + h);
+                    for (int r = r0; r <= r1; ++r) {
+                        double t = M[(size_t)r * n + c0];
+                        for (int c = c0 + 1; c <= c1; ++c) t += M[(size_t)r * n + c];
+                        X = r == r0 ? t : X + t;
+                    }
+                    X /= (double)((r1 - r0 + 1) * (c1 - c0 + 1));
+                }
+                band[((size_t)m * S + (s - lo)) * n + i] = X;
+            }
+    }
+    return hipSuccess;
+}
+hipError_t launch_mapsim_strata(const double* band, int n, int n_maps, int lo, int hi, bool keep_zeros, double* moments, long long* counts, hipStream_t) {
+    LaunchScope ls;
+    const int S = hi - lo + 1, pairs = n_maps * (n_maps - 1) / 2;
+    for (int pr = 0; pr < pairs; ++pr) {
+        int p, q;
+        mapsim_pair(pr, n_maps, &p, &q);
+        for (int s = lo; s <= hi; ++s) {
+            const double* x = band + ((size_t)p * S + (s - lo)) * n;
+            const double* y = band + ((size_t)q * S + (s - lo)) * n;
+            const int N0 = n - s;
+            std::vector<int> kept;
+            for (int i = 0; i < N0; ++i)
+                if (keep_zeros || !(x[i] == 0.0 && y[i] == 0.0)) kept.push_back(i);
+            const long long N = (long long)kept.size();
+            double sx = 0, sy = 0, cxy = 0, cxx = 0, cyy = 0;
+            for (int i : kept) { sx += x[i]; sy += y[i]; }
+            const double mx = N ? sx / (double)N : 0.0, my = N ? sy / (double)N : 0.0;
+            long long saa = 0, sbb = 0;
+            for (int i : kept) {
+                cxy += (x[i] - mx) * (y[i] - my); cxx += (x[i] - mx) * (x[i] - mx); cyy += (y[i] - my) * (y[i] - my);
+                long long a = 1, b = 1;
+                for (int k : kept) { a += (x[k] < x[i]) + (x[k] <= x[i]); b += (y[k] < y[i]) + (y[k] <= y[i]); }
+                saa += a * a; sbb += b * b;
+            }
+            const size_t at = ((size_t)pr * S + (s - lo)) * 3;
+            const long long T = N * (N + 1);
+            moments[at] = cxy; moments[at + 1] = cxx; moments[at + 2] = cyy;
+            counts[at] = N; counts[at + 1] = N * saa - T * T; counts[at + 2] = N * sbb - T * T;
+        }
+    }
+    return hipSuccess;
+}
+
 }  // namespace c3d
